@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- encode+decode throughput of the HIP GVRS tile codec on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload etopo1|dem1024|gebco_shard]
+    python bench.py --gpus N --steps K --warmup W [--workload etopo1|dem1024|gebco_shard] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic elevation tiles:
 CodecHuffman.encode of every tile (all predictors tried, shortest kept) followed by
@@ -73,7 +73,13 @@ def parse_args():
     ap.add_argument("--cpu-sample-tiles", type=int, default=-1, help="tiles timed on the CPU oracle (0 = skip)")
     ap.add_argument("--cpu-all-cores", action="store_true", help="(kept for old command lines: the all-cores figure is always reported now)")
     ap.add_argument("--no-verify", action="store_true", help="skip the bit-exactness checks")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the tiles where the whole batch is larger)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _replay_is_current(rec):
@@ -277,6 +283,8 @@ def run_float(args, ctxs, rank, world, dist, torch, single_multi=False):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        _dump_float(args.dump_outputs, shards, n_rows, n_cols, int(lib().gf_float_planes_bytes(n_rows, n_cols)), pstride)
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
@@ -368,6 +376,63 @@ class _BorrowedContext:
         from gridfour_amd import lib
         from gridfour_amd._lib import check
         check(lib().gf_context_reserve(self._h, n_rows, n_cols, n_tiles), "gf_context_reserve")
+
+
+DUMP_BYTES = 60 * 2 ** 20     # --dump-outputs: what all files together may hold (under 64 MB)
+DUMP_SEED = 0x5EED            # --dump-outputs: the tile sample of a shard too large to write whole
+
+
+def _dump_sample(n_tiles, tile_bytes, budget):
+    """The tiles of one shard that --dump-outputs writes: all of them where they fit `budget`, else a fixed, seeded sample in
+    tile order.  tile_bytes is a bound from the shapes alone, so the sample never depends on what the outputs hold."""
+    k = int(max(1, min(n_tiles, budget // tile_bytes)))
+    if k == n_tiles:
+        return np.arange(n_tiles)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_tiles, k, replace=False))
+
+
+def _dump_save(out_dir, name, a, dtype):
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+
+def _dump_batches(out_dir, batches):
+    """--dump-outputs for the integer codecs: what a caller of encode + decode receives from the last timed step, per shard.
+    For every tile the packing length, the predictor (not LSOP12: its batch entry point reports none) and both statuses; for
+    the sampled tiles (`tiles`) their packings' bytes, concatenated in tile order (the lengths split them), and the decoded
+    cells.  Integers as float64 (exact), bytes as float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_tiles = batches[0].n_tiles
+    budget = DUMP_BYTES // len(batches) - (6 * 8 * n_tiles + 8192)        # the per-tile arrays and the files' headers
+    for g, b in enumerate(batches):
+        pre = "shard%d_" % g if len(batches) > 1 else ""
+        tiles = _dump_sample(b.n_tiles, 8 * b.cells + 4 * b.stride, budget)
+        lengths = b.get_lengths()
+        _dump_save(out_dir, pre + "tiles", tiles, np.float64)
+        _dump_save(out_dir, pre + "lengths", lengths, np.float64)
+        if b.codec != "lsop":
+            _dump_save(out_dir, pre + "predictors", b.get_predictors(), np.float64)
+        _dump_save(out_dir, pre + "enc_status", b.get_enc_status(), np.float64)
+        _dump_save(out_dir, pre + "dec_status", b.get_dec_status(), np.float64)
+        packs = [np.frombuffer(b.get_packing(int(t), min(int(lengths[t]), b.stride)), np.uint8) for t in tiles]
+        _dump_save(out_dir, pre + "packings", np.concatenate(packs), np.float32)
+        decoded = np.stack([b.get_decoded(int(t), 1)[0] for t in tiles]).reshape(len(tiles), b.n_rows, b.n_cols)
+        _dump_save(out_dir, pre + "decoded", decoded, np.float64)
+
+
+def _dump_float(out_dir, shards, n_rows, n_cols, plane_bytes, pstride):
+    """--dump-outputs for CodecFloat's plane stage: per shard, for the sampled tiles (`tiles`), the byte planes the encode
+    wrote (as float32) and the floats the decode gave back."""
+    os.makedirs(out_dir, exist_ok=True)
+    cells = n_rows * n_cols
+    for g, sh in enumerate(shards):
+        d_planes, d_out, n_tiles = sh[3], sh[4], len(sh[1])
+        pre = "shard%d_" % g if len(shards) > 1 else ""
+        tiles = _dump_sample(n_tiles, 4 * cells + 4 * plane_bytes, DUMP_BYTES // len(shards) - (8 * n_tiles + 4096))
+        _dump_save(out_dir, pre + "tiles", tiles, np.float64)
+        planes = np.stack([d_planes.download(np.uint8, plane_bytes, int(t) * pstride) for t in tiles])
+        _dump_save(out_dir, pre + "planes", planes, np.float32)
+        decoded = np.stack([d_out.download(np.float32, cells, int(t) * cells * 4) for t in tiles])
+        _dump_save(out_dir, pre + "decoded", decoded.reshape(len(tiles), n_rows, n_cols), np.float32)
 
 
 def _verify_shard(args, batch, n_rows, n_cols, n_tiles, with_oracle, codec=None):
@@ -1022,6 +1087,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # (before anything below refills the batches' buffers)
+    if args.dump_outputs and rank == 0:
+        _dump_batches(args.dump_outputs, batches)
 
     # ---------------- verification (outside the timed region): EVERY shard, on every rank ----------------
     ok_all, packed_bytes, vals0 = True, 0, None
