@@ -2003,8 +2003,10 @@ gf_status gf_lsop12_reconstruct_dev(gf_context *c, void *stream, int nRows, int 
     if (!c || !dValues || !dResiduals || !dCoefs || !dStatus) return GF_ERR_ARG;
     GF_HIP(hipSetDevice(c->device));                        // launches and copies below go to the context's device
     if (nRows < 6 || nCols < 6 || resStride < gf_lsop12_residual_count(nRows, nCols)) return GF_ERR_ARG;
+    // planes: word GF_LSOP_FMT_WORD says how a tile's interior residuals lie -- 0 in a record the caller built (the ABI asks for
+    // words 13 .. 15 = 0) or one gf_lsop12_predict_dev wrote, 1 for a byte plane gf_lsop12_decode_batch_i32_dev left
     GF_HIP(gf_launch_lsop_reconstruct(dResiduals, resStride, dCoefs, dInStatus, dValues, dStatus, nTiles, nRows, nCols,
-                                      stream ? (hipStream_t)stream : c->stream));
+                                      stream ? (hipStream_t)stream : c->stream, true));
     return GF_OK;
 }
 

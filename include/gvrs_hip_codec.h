@@ -337,7 +337,9 @@ gf_status gf_lsop12_predict_dev(gf_context *ctx, void *stream, int n_rows, int n
                                 const int32_t *d_values, int32_t *d_residuals, size_t res_stride, uint32_t *d_coefs,
                                 int32_t *d_status);
 /* LsDecoder12.unpackInitializers + unpackInterior: residual streams -> tile.  d_in_status (may be NULL): tiles whose
- * entry is not GF_OK are skipped and that value is passed through to d_status.                                     */
+ * entry is not GF_OK are skipped and that value is passed through to d_status.  A tile's 16 words of d_coefs: seed,
+ * the 12 float bit patterns, then words 13 .. 15, which a caller-built record must set to 0 (gf_lsop12_predict_dev
+ * writes 0 there).  The d_residuals / d_coefs that gf_lsop12_decode_batch_i32_dev leaves behind are valid input.      */
 gf_status gf_lsop12_reconstruct_dev(gf_context *ctx, void *stream, int n_rows, int n_cols, size_t n_tiles,
                                     const int32_t *d_residuals, size_t res_stride, const uint32_t *d_coefs,
                                     const int32_t *d_in_status, int32_t *d_values, int32_t *d_status);
