@@ -65,6 +65,11 @@ CODEC_STATS_DTYPE = np.dtype([("n_tiles", "<i8"), ("n_bytes", "<i8"), ("n_symbol
                               ("n_m32_counted", "<i8"), ("sum_length_m32", "<i8"), ("sum_observed_m32", "<i8"),
                               ("sum_entropy_m32", "<f8")])
 
+# struct gf_canon_stats (include/gvrs_hip_codec.h) = the sums of compress/canonicalHuffman/CanonHuffmanStats.java
+CANON_STATS_DTYPE = np.dtype([("n_tiles", "<i8"), ("n_bytes", "<i8"), ("n_symbols", "<i8"), ("n_bits_overhead", "<i8"),
+                              ("n_text_counted", "<i8"), ("sum_length", "<i8"), ("sum_observed", "<i8"), ("sum_entropy", "<f8"),
+                              ("sum_escape_bits", "<i8")])
+
 
 class CodecHuffmanHip:
     """Drop-in for org.gridfour.compress.CodecHuffman, computed on the MI355X."""
@@ -236,6 +241,71 @@ class CodecCanonHuffmanHip(CodecHuffmanHip):
     current Gridfour, GvrsFileSpecification.java:229), computed on the MI355X."""
 
     _PREFIX = "gf_canon"
+
+    # ---- analysis (CodecCanonHuffman.java:217-324 over CanonHuffmanStats.java) ----
+    _ESCAPE_BITS = (2, 4, 6, 8, 16, 24)                  # CanonicalHuffman.getEscapeBitCounts()[0]
+
+    def analyze(self, nRows, nColumns, packing):
+        st = self.analyze_batch(nRows, nColumns, [packing])
+        if st[0] != 0:
+            raise IOError(lib().gf_status_string(int(st[0])).decode())
+
+    def analyze_batch(self, nRows, nCols, packings):
+        """analyze() of every packing in one GPU pass; returns the per-packing status (non-zero: analyze would throw)."""
+        nt = len(packings)
+        status = np.zeros(nt, np.int32)
+        if nt == 0:
+            return status
+        if getattr(self, "_stats", None) is None:
+            self._stats = np.zeros(6, dtype=CANON_STATS_DTYPE)
+            self._escapes = np.zeros(6, np.int64)
+        offsets = np.zeros(nt + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(p) for p in packings])
+        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)
+        check(lib().gf_canon_analyze_batch(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(self._stats),
+                                           _ptr(self._escapes), _ptr(status)), "gf_canon_analyze_batch")
+        return status
+
+    def analysis_data(self):
+        """The accumulated sums, one record per predictor byte 0..4 (0: the uniform form) and one for all (CanonHuffmanStats fields)."""
+        s = getattr(self, "_stats", None)
+        return None if s is None else s.copy()
+
+    def escape_counts(self):
+        """escapeBitCounts[1]: how many values took 2, 4, 6, 8, 16, 24 escape bits."""
+        e = getattr(self, "_escapes", None)
+        return None if e is None else e.copy()
+
+    def reportAnalysisData(self, ps, nTilesInRaster):
+        ps.write("GVRS Canonical Huffman                          Compressed Output    |       Predictor Residuals\n")
+        s = getattr(self, "_stats", None)
+        if s is None or nTilesInRaster == 0:
+            ps.write("   Tiles Compressed:  0\n")
+            return
+        ps.write("  Predictor                Times Used         bits/sym    bits/tile  |    ext-bits    avg-unique  entropy | bits in tree\n")
+        for label, r in zip(self._STAT_LABELS, s):
+            if label == "None":
+                label = "Uniform Value"                  # the uniform case is counted under predictor code 0
+                if r["n_tiles"] == 0:
+                    continue
+            n, nt = int(r["n_tiles"]), int(r["n_text_counted"])
+            line_label = "%-20.20s %8d (%4.1f %%)" % (label, n, 100.0 * n / nTilesInRaster)
+            ps.write("   %-39.39s     %5.2f  %12.1f   | %10.1f      %6.1f    %6.2f   | %6.1f\n" % (
+                line_label, (8.0 * r["n_bytes"] / r["n_symbols"] if r["n_symbols"] else 0.0),
+                (r["n_bytes"] / n * 8 if n else 0.0), (r["sum_escape_bits"] / n if n else 0.0),
+                (r["sum_observed"] / n if n else 0.0), (r["sum_entropy"] / nt if nt else 0.0),
+                (r["n_bits_overhead"] / n if n else 0.0)))
+        total = float(s[5]["n_tiles"])
+        if total <= 0:
+            total = 1.0                                  # just for averaging
+        ps.write("Escape sequences\n")
+        ps.write("length    count     n/tile  bits/tile\n")
+        for bits, count in zip(self._ESCAPE_BITS, self._escapes):
+            ps.write("  %2d  %10d    %7.2f    %7.2f\n" % (bits, count, count / total, bits * (count / total)))
+
+    def clearAnalysisData(self):
+        self._stats = None
+        self._escapes = None
 
 
 class DeviceBuffer:

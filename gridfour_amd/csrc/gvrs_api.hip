@@ -548,7 +548,13 @@ static gf_status decodeBatchDev(int kind, gf_context *c, void *stream, int nRows
             else GF_HIP(gf_launch_huffman_decode_canon(f, st));
         }
     }
-    if (kind == KIND_CANON) {
+    if (kind == KIND_CANON && analysis) {
+        // CodecCanonHuffman.analyze: the text of every tile (the 256-thread build) and its symbol statistics, records to analysis
+        a.ldsM32Bytes = 0;
+        a.ldsTextBytes = gf_canon_decode_lds_text(nRows, nCols);
+        a.ldsStageBytes = gf_canon_decode_lds_stage(nRows, nCols);
+        GF_HIP(gf_launch_canon_analyze(a, stream ? (hipStream_t)stream : c->stream));
+    } else if (kind == KIND_CANON) {
         // two builds as for the legacy decoder below: 256 threads (up to five workgroups per CU) or 512 (four = 32 waves)
         a.ldsM32Bytes = 0;
         GfDecodeArgs b = a;
@@ -3055,11 +3061,10 @@ gf_status gf_tile_record_decode_batch(gf_context *c, const int *codecs, int nCod
 // 100-141) are then accumulated here in tile order.  stats[p], p = 0..4 by predictor code (PredictorModelType ordinal),
 // stats[5] = "All Predictors"; counts ADD to what stats already holds (clearAnalysisData = zero the array).  The pair
 // counts behind CodecStats.getH2 (sA / sB) come from the same pass when the caller hands in tables for them.
-static gf_status analyzeBatch(gf_context *c, int nRows, int nCols, size_t nTiles, const uint8_t *blob, const uint64_t *offsets,
-                              gf_codec_stats *stats, int64_t *pairCounts, int32_t *status)
+// The packings of an analysis batch to the device (c->dBlob, c->dOffsets, c->dLengths; c->dStatus sized), the lengths kept in
+// *lengths for the host's part.  Arguments as checked by the callers.
+static gf_status analyzeStage(gf_context *c, size_t nTiles, const uint8_t *blob, const uint64_t *offsets, std::vector<uint32_t> *lengths)
 {
-    if (!c || nRows < 1 || nCols < 1 || !blob || !offsets || !stats) return GF_ERR_ARG;
-    if (!offsetsValid(offsets, nTiles)) return GF_ERR_ARG;    // a bad array must not become an out-of-bounds read
     GF_HIP(hipSetDevice(c->device));
     const uint64_t total = offsets[nTiles];
     gf_status s;
@@ -3067,6 +3072,26 @@ static gf_status analyzeBatch(gf_context *c, int nRows, int nCols, size_t nTiles
     if ((s = c->dLengths.ensure(nTiles * 4 + 16)) != GF_OK) return s;
     if ((s = c->dStatus.ensure(nTiles * 4 + 16)) != GF_OK) return s;
     if ((s = c->dOffsets.ensure((nTiles + 1) * 8 + 16)) != GF_OK) return s;
+    lengths->resize(nTiles);
+    for (size_t t = 0; t < nTiles; t++) {
+        if (offsets[t + 1] < offsets[t]) return GF_ERR_ARG;
+        (*lengths)[t] = (uint32_t)(offsets[t + 1] - offsets[t]);
+    }
+    GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, total, hipMemcpyHostToDevice, c->stream));
+    GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nTiles + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    GF_HIP(hipMemcpyAsync(c->dLengths.p, lengths->data(), nTiles * 4, hipMemcpyHostToDevice, c->stream));
+    return GF_OK;
+}
+
+static gf_status analyzeBatch(gf_context *c, int nRows, int nCols, size_t nTiles, const uint8_t *blob, const uint64_t *offsets,
+                              gf_codec_stats *stats, int64_t *pairCounts, int32_t *status)
+{
+    if (!c || nRows < 1 || nCols < 1 || !blob || !offsets || !stats) return GF_ERR_ARG;
+    if (!offsetsValid(offsets, nTiles)) return GF_ERR_ARG;    // a bad array must not become an out-of-bounds read
+    const uint64_t total = offsets[nTiles];
+    std::vector<uint32_t> lengths;
+    gf_status s = analyzeStage(c, nTiles, blob, offsets, &lengths);
+    if (s != GF_OK) return s;
     if ((s = c->dResiduals.ensure(nTiles * GF_ANALYSIS_WORDS * 4 + 16)) != GF_OK) return s;
     if ((s = c->dValues.ensure(16)) != GF_OK) return s;
     uint32_t *dPairs = nullptr;
@@ -3076,14 +3101,6 @@ static gf_status analyzeBatch(gf_context *c, int nRows, int nCols, size_t nTiles
         dPairs = (uint32_t *)c->dCoefs.p;
         GF_HIP(hipMemsetAsync(dPairs, 0, pairWords * 4, c->stream));
     }
-    std::vector<uint32_t> lengths(nTiles);
-    for (size_t t = 0; t < nTiles; t++) {
-        if (offsets[t + 1] < offsets[t]) return GF_ERR_ARG;
-        lengths[t] = (uint32_t)(offsets[t + 1] - offsets[t]);
-    }
-    GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, total, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nTiles + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(c->dLengths.p, lengths.data(), nTiles * 4, hipMemcpyHostToDevice, c->stream));
     s = decodeBatchDev(KIND_HUFFMAN, c, c->stream, nRows, nCols, nTiles, (const uint8_t *)c->dBlob.p, total,
                        (const uint64_t *)c->dOffsets.p, 0, (const uint32_t *)c->dLengths.p, (int32_t *)c->dValues.p,
                        (int32_t *)c->dStatus.p, (uint32_t *)c->dResiduals.p, dPairs);
@@ -3156,6 +3173,80 @@ gf_status gf_huffman_analyze_batch_h2(gf_context *c, int nRows, int nCols, size_
     GF_CTX_LOCK(c);
     if (!pairCounts) return GF_ERR_ARG;
     return analyzeBatch(c, nRows, nCols, nTiles, blob, offsets, stats, pairCounts, status);
+}
+
+// ------------------------------------------------------------------ CodecCanonHuffman.analyze
+
+// ICompressionDecoder.analyze for a batch of CodecCanonHuffman packings (canonicalHuffman/CodecCanonHuffman.java:217-271):
+// k_canon_decode<true> decodes the text of every packing on the GPU and k_canon_stats counts its symbols (CanonicalHuffman.
+// countSymbols / getEntropy / getEscapeBitCountTotal); the host copies back a small record per tile and adds it to the
+// CanonHuffmanStats sums in tile order -- the uniform form, the escape table and the record chosen by the predictor byte
+// are decided here, from the packing, as analyze decides them.  stats[0..4] by PredictorModelType ordinal, stats[5] = "All
+// Predictors"; stats and escape_counts are added to (clearAnalysisData = zero them).
+gf_status gf_canon_analyze_batch(gf_context *c, int nRows, int nCols, size_t nTiles, const uint8_t *blob, const uint64_t *offsets,
+                                 gf_canon_stats *stats, int64_t *escapeCounts, int32_t *status)
+{
+    // (the arguments are checked before the context is touched)
+    if (!c || nRows < 1 || nCols < 1 || !blob || !offsets || !stats || !escapeCounts) return GF_ERR_ARG;
+    if (!offsetsValid(offsets, nTiles)) return GF_ERR_ARG;    // a bad array must not become an out-of-bounds read
+    const size_t cells = (size_t)nRows * (size_t)nCols;
+    if (cells >= (1ull << 28)) return GF_ERR_UNSUPPORTED;
+    GF_CTX_LOCK(c);
+    if (nTiles == 0) return GF_OK;
+    std::vector<uint32_t> lengths;
+    gf_status s = analyzeStage(c, nTiles, blob, offsets, &lengths);
+    if (s != GF_OK) return s;
+    const size_t stride = gf_canon_stats_stride((uint32_t)cells);
+    if ((s = c->dValues.ensure(nTiles * stride * 4 + 16)) != GF_OK) return s;
+    if ((s = c->dResiduals.ensure(nTiles * GF_CANON_STAT_WORDS * 4 + 16)) != GF_OK) return s;
+    s = decodeBatchDev(KIND_CANON, c, c->stream, nRows, nCols, nTiles, (const uint8_t *)c->dBlob.p, offsets[nTiles],
+                       (const uint64_t *)c->dOffsets.p, 0, (const uint32_t *)c->dLengths.p, (int32_t *)c->dValues.p,
+                       (int32_t *)c->dStatus.p, (uint32_t *)c->dResiduals.p);
+    if (s != GF_OK) return s;
+    std::vector<uint32_t> rec(nTiles * GF_CANON_STAT_WORDS);
+    std::vector<int32_t> st(nTiles);
+    GF_HIP(hipMemcpyAsync(rec.data(), c->dResiduals.p, rec.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    GF_HIP(hipMemcpyAsync(st.data(), c->dStatus.p, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
+    GF_HIP(hipStreamSynchronize(c->stream));
+    const int64_t n = (int64_t)cells;
+    auto add = [&](gf_canon_stats &g, int64_t nBytes, int64_t bitsInCodeTable, int64_t observed, double entropy) {
+        g.n_tiles++;                                                    // CanonHuffmanStats.addToCounts
+        g.n_bytes += nBytes;
+        g.n_symbols += n;
+        g.n_bits_overhead += bitsInCodeTable;
+        g.n_text_counted++;                                             // addCountsForSymbols
+        g.sum_length += n;
+        g.sum_observed += observed;
+        g.sum_entropy += entropy;
+    };
+    for (size_t t = 0; t < nTiles; t++) {
+        int32_t tileStatus = st[t];
+        if (tileStatus == GF_OK) {
+            const uint8_t *pk = blob + offsets[t];
+            const uint32_t predictor = pk[1];                           // packing[1] & 0xff
+            if (predictor == 0 && lengths[t] == 6) {                    // the uniform form: n zeros, one symbol observed
+                add(stats[0], 0, 0, 1, 0.0);
+                add(stats[5], 0, 0, 1, 0.0);
+            } else {
+                const uint32_t *r = rec.data() + t * GF_CANON_STAT_WORDS;
+                for (int k = 0; k < 6; k++) escapeCounts[k] += r[2 + k];   // before the predictor byte is used as an index
+                if (predictor >= 6) {
+                    tileStatus = GF_ERR_BOUNDS;                         // codecStats[predictor]: ArrayIndexOutOfBoundsException
+                } else {
+                    const int64_t escBits = (int64_t)(((uint64_t)r[9] << 32) | r[8]);
+                    double entropy;
+                    const uint64_t eb = ((uint64_t)r[11] << 32) | r[10];
+                    std::memcpy(&entropy, &eb, 8);
+                    add(stats[predictor], (int64_t)lengths[t] - 6, r[0], r[1], entropy);
+                    add(stats[5], (int64_t)lengths[t] - 6, r[0], r[1], entropy);
+                    stats[predictor].sum_escape_bits += escBits;        // (predictor byte 5: "All Predictors" twice)
+                    stats[5].sum_escape_bits += escBits;
+                }
+            }
+        }
+        if (status) status[t] = tileStatus;
+    }
+    return GF_OK;
 }
 
 // CodecStats.getH2 (CodecStats.java:157-190) from one table of pair counts: sA[v] is the column sum of sB

@@ -1,8 +1,11 @@
-// gvrs_aux.hip -- small helper kernels: packing compaction and the synthetic DEM generator.
+// gvrs_aux.hip -- small helper kernels: packing compaction and the synthetic DEM generator; and the two kernels of
+// CodecCanonHuffman.analyze (k_canon_decode<true>, k_canon_stats), kept out of gvrs_canon_decode.hip's translation unit
+// (see gvrs_canon_decode_kernel.h).
 
 #include <hip/hip_runtime.h>
 
 #include "gvrs_kernels.h"
+#include "huff_build.h"
 
 namespace {
 
@@ -221,5 +224,179 @@ hipError_t gf_launch_synth_dem(uint64_t seed, int nRows, int nCols, int64_t tile
     if (nTiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_synth_dem, dim3(4096), dim3(256), 0, stream, seed, nRows, nCols, tilesPerRow, tile0, nTiles,
                        maskPerMille, style, values);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// CodecCanonHuffman.analyze: the decoder's 256-thread build in analysis mode, then the symbol statistics of its text
+
+namespace {
+
+constexpr int DEC_THREADS = 256;                // = the 256-thread build of gvrs_canon_decode.hip, whose LDS sizes the host passes
+constexpr int DEC_WAVES = DEC_THREADS / 64;
+
+#include "gvrs_decode_common.h"
+
+#include "gvrs_canon_decode_common.h"
+
+#include "gvrs_canon_decode_kernel.h"
+
+// ---------------------------------------------------------------------------------------------------------------
+// CanonicalHuffman.countSymbols (:352-418), getEntropy (:709-751) and getEscapeBitCountTotal (:656-662) over the text that
+// k_canon_decode<true> left of each tile: a workgroup per tile, the tile's nCells values read four at a time.  Byte values
+// (nearly all of a terrain tile, most of them 0) go to a replicated 256-bin histogram of their own; the rest -- escapes,
+// nulls -- are classified by cn_classify_count and counted into the target bins, count2bit, count8bit and the low-byte
+// presence set, with the index expressions of countSymbols (the single 2-bit escape counts count2bit[(s >> 2) & 3]).
+// Record per tile (GF_CANON_STAT_WORDS words): bits in the code tables (getBitsInCodeTableCount: the pre-pass record's
+// text position less the 48 bits of the header), distinct low bytes (CanonHuffmanStats.addCountsForSymbols), the six
+// escape-class counts (2, 4, 6, 8, 16, 24 bits), the escape-bit total (uint64), the entropy (double), 1; all zero where
+// the tile has no text to count (a failed decode, the uniform form).
+constexpr uint32_t CS_THREADS = 256;
+constexpr uint32_t CS_R = 8;                    // replicas of the byte-value histogram (value 0 is most of a terrain tile)
+
+struct CanonStatsLds {
+    uint32_t plain[256 * CS_R];                 // symbol value + 128, replica
+    uint32_t target[256];                       // target symbols of escaped values
+    uint32_t count8[256];
+    uint32_t seen[256];                         // low bytes of escaped and null values
+    uint32_t count2[4];
+    uint32_t cls[8];                            // values per escape kind 1..6, nulls (cn_classify_count)
+    uint32_t observed;
+    double part[CS_THREADS / 64];
+};
+
+__global__ __launch_bounds__(CS_THREADS) void k_canon_stats(const uint32_t *__restrict__ values, const int32_t *__restrict__ status,
+                                                           const uint32_t *__restrict__ lengths, const uint32_t *__restrict__ recs,
+                                                           uint32_t *__restrict__ out, size_t nTiles, uint32_t nCells)
+{
+    __shared__ CanonStatsLds L;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    GF_FOR_WG_TILE(t, nTiles) {
+        uint32_t *r = out + t * (size_t)GF_CANON_STAT_WORDS;
+        if (status[t] != GF_K_OK || lengths[t] <= 6u) {           // analyze throws / the uniform form (counted by the host)
+            if (tid < (uint32_t)GF_CANON_STAT_WORDS) r[tid] = 0;
+            continue;
+        }
+        for (uint32_t i = tid; i < 256u * CS_R; i += CS_THREADS) L.plain[i] = 0;
+        L.target[tid] = 0;
+        L.count8[tid] = 0;
+        L.seen[tid] = 0;
+        if (tid < 4u) L.count2[tid] = 0;
+        if (tid < 8u) L.cls[tid] = 0;
+        if (tid == 0) L.observed = 0;
+        __syncthreads();
+
+        const uint4 *__restrict__ v4 = reinterpret_cast<const uint4 *>(values + t * (size_t)gf_canon_stats_stride(nCells));
+        uint32_t *const h = L.plain + (lane & (CS_R - 1u));
+        uint32_t k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t q = tid; 4u * q < nCells; q += CS_THREADS) {
+            const uint4 x4 = v4[q];
+            const uint32_t x[4] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++) {
+                const uint32_t v = x[j];
+                if (4u * q + j >= nCells) break;                   // (the padding of the last four)
+                if (v + 128u < 256u) {
+                    atomicAdd(h + (v + 128u) * CS_R, 1u);
+                    continue;
+                }
+                const int32_t s = (int32_t)v;
+                uint32_t kind;
+                const uint32_t target = cn_classify_count(v, &kind);
+                L.seen[v & 0xffu] = 1u;
+                k[kind]++;
+                if (kind == 7u) continue;                          // the null symbol: no target, no escape
+                atomicAdd(&L.target[target], 1u);
+                if (kind == 1u) atomicAdd(&L.count2[(s >> 2) & 3], 1u);
+                if (kind == 2u || kind == 3u) {
+                    atomicAdd(&L.count2[(s >> 2) & 3], 1u);
+                    atomicAdd(&L.count2[s & 3], 1u);
+                }
+                if (kind == 3u) atomicAdd(&L.count2[(s >> 4) & 3], 1u);
+                if (kind >= 4u) atomicAdd(&L.count8[(s >> 8) & 0xff], 1u);
+                if (kind >= 5u) atomicAdd(&L.count8[(s >> 16) & 0xff], 1u);
+                if (kind == 6u) atomicAdd(&L.count8[(s >> 24) & 0xff], 1u);
+            }
+        }
+#pragma unroll
+        for (int c = 1; c < 8; c++)
+            if (k[c]) atomicAdd(&L.cls[c - 1], k[c]);
+        __syncthreads();
+
+        // node counts: byte symbols 0..255 (a thread each), null, 1-byte escape, 2-bit escape, end of text (counted once);
+        // d = their total = nCells + the escape symbols + 1
+        const uint32_t nEsc2 = L.cls[0] + 2u * L.cls[1] + 3u * L.cls[2], nEsc1 = L.cls[3] + 2u * L.cls[4] + 3u * L.cls[5];
+        const double d = (double)nCells + (double)nEsc1 + (double)nEsc2 + 1.0;
+        uint32_t plainCount = 0;
+#pragma unroll
+        for (uint32_t m = 0; m < CS_R; m++) plainCount += L.plain[tid * CS_R + m];
+        auto plogp = [d](uint32_t n) -> double {
+            if (n == 0) return 0.0;
+            const double p = (double)n / d;
+            return p * log(p);
+        };
+        double e = plogp(plainCount + L.target[tid]);
+        if (tid == 0) e += plogp(L.cls[6]) + plogp(nEsc1) + plogp(nEsc2) + plogp(1u);
+        // the escape bits' conditional terms (getEntropy :731-749)
+        if (nEsc2 > 0 && tid < 4u && L.count2[tid] > 0) {
+            const double q = (double)L.count2[tid] / (double)nEsc2;
+            e += ((double)nEsc2 / d) * q * log(q);
+        }
+        if (nEsc1 > 0 && L.count8[tid] > 0) {
+            const double q = (double)L.count8[tid] / (double)nEsc1;
+            e += ((double)nEsc1 / d) * q * log(q);
+        }
+        // distinct low bytes: byte b was seen as the byte value (int8_t)b, i.e. symbol b ^ 0x80, or as the low byte of a wider value
+        uint32_t asByte = 0;
+#pragma unroll
+        for (uint32_t m = 0; m < CS_R; m++) asByte += L.plain[(tid ^ 0x80u) * CS_R + m];
+        const bool present = asByte != 0u || L.seen[tid] != 0u;
+#pragma unroll
+        for (int sh = 32; sh >= 1; sh >>= 1) e += __shfl_xor(e, sh, 64);
+        const uint32_t nPresent = (uint32_t)__popcll(__ballot(present));
+        if (lane == 0) {
+            L.part[wave] = e;
+            atomicAdd(&L.observed, nPresent);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double sum = 0;
+            for (uint32_t w = 0; w < CS_THREADS / 64u; w++) sum += L.part[w];
+            const double entropy = -sum / log(2.0);
+            const uint64_t escBits = 2ull * L.cls[0] + 4ull * L.cls[1] + 8ull * L.cls[3] + 16ull * L.cls[4] + 24ull * L.cls[5];   // (6-bit class left out, sic)
+            uint64_t eb;
+            __builtin_memcpy(&eb, &entropy, 8);
+            r[0] = recs[t * (size_t)GF_CANON_REC_WORDS + 1] - 48u;
+            r[1] = L.observed;
+            for (int c = 0; c < 6; c++) r[2 + c] = L.cls[c];
+            r[8] = (uint32_t)escBits;
+            r[9] = (uint32_t)(escBits >> 32);
+            r[10] = (uint32_t)eb;
+            r[11] = (uint32_t)(eb >> 32);
+            r[12] = 1u;
+            r[13] = L.cls[6];
+            r[14] = 0;
+            r[15] = 0;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+// CodecCanonHuffman.analyze of a batch: k_canon_decode<true> (the 256-thread build's LDS sizes in a) behind the code-length pre-pass
+// (a.trees), then k_canon_stats over what it left in a.values; the records go to a.analysis
+hipError_t gf_launch_canon_analyze(const GfDecodeArgs &a, hipStream_t stream)
+{
+    if (a.nTiles == 0) return hipSuccess;
+    if (!a.trees || !a.analysis) return hipErrorInvalidValue;
+    const size_t dyn = (size_t)a.ldsTextBytes + a.ldsStageBytes;
+    static GfDynLdsOptIn opt;
+    hipError_t e = gf_opt_in_dyn_lds(k_canon_decode<true>, dyn, opt);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_canon_decode<true>, gf_tile_grid(a.nTiles), dim3(DEC_THREADS), dyn, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_canon_stats, gf_tile_grid(a.nTiles), dim3(CS_THREADS), 0, stream, reinterpret_cast<const uint32_t *>(a.values),
+                       a.status, a.lengths, a.trees, a.analysis, a.nTiles, (uint32_t)a.nRows * (uint32_t)a.nCols);
     return hipGetLastError();
 }

@@ -5,9 +5,8 @@
 
 #include <type_traits>
 
-constexpr int CN_SYMS = 260;
-constexpr int CN_NULL = 256, CN_ESC1 = 257, CN_ESC2 = 258, CN_EOT = 259;
-constexpr int CN_META = 20;
+#include "gvrs_canon_symbols.h"
+
 constexpr int CD_LUT_BITS = 11;
 constexpr int CD_MAXQ = 512;
 constexpr int CD_NCUR = CD_MAXQ / DEC_THREADS > 0 ? CD_MAXQ / DEC_THREADS : 1;   // subsequences per thread: tid, tid + DEC_THREADS, ...

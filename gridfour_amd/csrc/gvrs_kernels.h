@@ -135,7 +135,8 @@ struct GfDecodeArgs {
     int lean;                  // 1 (the one-tile-per-call path): the fast kernel alone; what it leaves behind keeps the status
                                // GF_K_LEAN_RETRY and the caller takes the batch path for it
     uint32_t *analysis;        // non-null: CodecHuffman.analyze mode -- per tile GF_ANALYSIS_WORDS words (predictor, nM32,
-                               // bits in tree, packing bytes - 10, 256-bin histogram of the M32 bytes); no values are written
+                               // bits in tree, packing bytes - 10, 256-bin histogram of the M32 bytes); no values are written.
+                               // CodecCanonHuffman batches: GF_CANON_STAT_WORDS words per tile from k_canon_stats (gf_launch_canon_analyze)
     uint32_t *pairCounts;      // analyze mode, may be null: GF_PAIR_TABLES x 65536 counters, [predictor][prior << 8 | value] of
                                // neighbouring M32 bytes (CodecStats.addCountsForM32 :150-156), added to with atomics
     int noRoomyRun;            // (set by gf_launch_huffman_decode, round 6) the roomy run is not launched for this batch: the first run
@@ -227,6 +228,12 @@ uint32_t gf_canon_decode_lds_text_t512(int nRows, int nCols);
 uint32_t gf_canon_decode_lds_stage_t512(int nRows, int nCols);
 size_t gf_canon_decode_lds_per_wg(const GfDecodeArgs &a);
 size_t gf_canon_decode_lds_per_wg_t512(const GfDecodeArgs &a);
+// CodecCanonHuffman.analyze (gvrs_aux.hip): k_canon_decode<true> writes each tile's text -- nRows * nCols values in
+// stream order, zero behind the end of the text -- to a.values at a stride of gf_canon_stats_stride(cells) values, k_canon_stats
+// counts it into GF_CANON_STAT_WORDS words per tile at a.analysis (see there); the 256-thread build's LDS sizes, a.trees set
+constexpr int GF_CANON_STAT_WORDS = 16;
+__host__ __device__ inline uint32_t gf_canon_stats_stride(uint32_t nCells) { return (nCells + 3u) & ~3u; }
+hipError_t gf_launch_canon_analyze(const GfDecodeArgs &a, hipStream_t stream);
 uint32_t gf_lsop_unpack_lds_text(int nRows, int nCols);      // the same for k_lsop_unpack2 (trimmed where that gains a workgroup per CU)
 uint32_t gf_canon_decode_lds_stage(int nRows, int nCols);
 

@@ -6,6 +6,7 @@
 //   org.gridfour.compress.ICompressionEncoder   core/src/main/java/org/gridfour/compress/ICompressionEncoder.java:46-92
 //   org.gridfour.compress.ICompressionDecoder   .../ICompressionDecoder.java:49-107
 //   org.gridfour.compress.CodecHuffman          .../CodecHuffman.java:50-260
+//   org.gridfour.compress.canonicalHuffman.CodecCanonHuffman   .../canonicalHuffman/CodecCanonHuffman.java:61-337
 // Java `null` results are empty std::optional, Java IOException is gridfour::IOException.
 // The Java adapter that binds the same C ABI through JNI is in gridfour_amd/java/.
 #pragma once
@@ -257,12 +258,71 @@ public:
         return out;
     }
     std::optional<std::vector<float>> decodeFloats(int, int, const std::vector<uint8_t> &) override { return std::nullopt; }
-    void analyze(int, int, const std::vector<uint8_t> &) override {}
-    void reportAnalysisData(std::FILE *ps, int) override { std::fprintf(ps, "GVRS Canonical Huffman (HIP)\n"); }
-    void clearAnalysisData() override {}
+
+    // statistics (CodecCanonHuffman.java:217-324 over CanonHuffmanStats.java): the text is decoded and its symbols counted on
+    // the GPU (gf_canon_analyze_batch); the sums and the escape table live here
+    void analyze(int nRows, int nColumns, const std::vector<uint8_t> &packing) override
+    {
+        const uint64_t offsets[2] = {0, packing.size()};
+        std::vector<uint8_t> padded(packing);
+        padded.resize(packing.size() + 16);
+        int32_t st = 0;
+        counted_ = true;
+        check(gf_canon_analyze_batch(ctx_, nRows, nColumns, 1, padded.data(), offsets, stats_, escapes_, &st), "gf_canon_analyze_batch");
+        if (st != GF_OK) throw IOException(gf_status_string((gf_status)st));
+    }
+    // analyze() of a whole batch in one GPU pass; returns the per-packing status
+    std::vector<int32_t> analyzeBatch(int nRows, int nColumns, size_t nTiles, const uint8_t *blob, const uint64_t *offsets)
+    {
+        std::vector<int32_t> st(nTiles);
+        if (nTiles) counted_ = true;
+        check(gf_canon_analyze_batch(ctx_, nRows, nColumns, nTiles, blob, offsets, stats_, escapes_, st.data()), "gf_canon_analyze_batch");
+        return st;
+    }
+    const gf_canon_stats *analysisData() const { return stats_; }    // by predictor byte 0..4 (0: the uniform form), [5] = all
+    const int64_t *escapeCounts() const { return escapes_; }          // values with 2, 4, 6, 8, 16, 24 escape bits
+    void reportAnalysisData(std::FILE *ps, int nTilesInRaster) override
+    {
+        std::fprintf(ps, "GVRS Canonical Huffman                          Compressed Output    |       Predictor Residuals\n");
+        if (!counted_ || nTilesInRaster == 0) {
+            std::fprintf(ps, "   Tiles Compressed:  0\n");
+            return;
+        }
+        std::fprintf(ps, "  Predictor                Times Used         bits/sym    bits/tile  |    ext-bits    avg-unique  entropy | bits in tree\n");
+        static const char *names[6] = {"Uniform Value", "Differencing", "Linear", "Triangle", "DifferencingWithNulls", "All Predictors"};
+        for (int p = 0; p < 6; p++) {
+            const gf_canon_stats &r = stats_[p];
+            if (p == 0 && r.n_tiles == 0) continue;
+            const double n = (double)r.n_tiles, nt = (double)r.n_text_counted;
+            char lineLabel[96];
+            std::snprintf(lineLabel, sizeof lineLabel, "%-20.20s %8ld (%4.1f %%)", names[p], (long)r.n_tiles, 100.0 * n / nTilesInRaster);
+            std::fprintf(ps, "   %-39.39s     %5.2f  %12.1f   | %10.1f      %6.1f    %6.2f   | %6.1f\n", lineLabel,
+                         r.n_symbols ? 8.0 * r.n_bytes / r.n_symbols : 0.0, n ? r.n_bytes / n * 8 : 0.0, n ? r.sum_escape_bits / n : 0.0,
+                         n ? r.sum_observed / n : 0.0, nt ? r.sum_entropy / nt : 0.0, n ? r.n_bits_overhead / n : 0.0);
+        }
+        const double totalTiles = stats_[5].n_tiles > 0 ? (double)stats_[5].n_tiles : 1.0;
+        std::fprintf(ps, "Escape sequences\n");
+        std::fprintf(ps, "length    count     n/tile  bits/tile\n");
+        static const int bits[6] = {2, 4, 6, 8, 16, 24};
+        for (int i = 0; i < 6; i++)
+            std::fprintf(ps, "  %2d  %10ld    %7.2f    %7.2f\n", bits[i], (long)escapes_[i], escapes_[i] / totalTiles, bits[i] * (escapes_[i] / totalTiles));
+    }
+    void clearAnalysisData() override
+    {
+        std::memset(stats_, 0, sizeof stats_);
+        std::memset(escapes_, 0, sizeof escapes_);
+        counted_ = false;
+    }
 
 private:
+    static void check(gf_status s, const char *where)
+    {
+        if (s < 0) throw std::runtime_error(std::string(where) + ": " + gf_status_string(s) + " [" + gf_last_error() + "]");
+    }
     gf_context *ctx_ = nullptr;
+    gf_canon_stats stats_[6] = {};          // by predictor byte 0..4, [5] = all predictors
+    int64_t escapes_[6] = {};               // escapeBitCounts[1]
+    bool counted_ = false;                  // analyze was called since the last clear (Java: codecStats != null)
 };
 
 /** Drop-in for org.gridfour.lsop.LsEncoder12 + LsDecoder12 (codec id "LSOP12"). */

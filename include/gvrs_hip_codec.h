@@ -448,6 +448,29 @@ gf_status gf_huffman_analyze_batch_h2(gf_context *ctx, int n_rows, int n_cols, s
                                       const uint64_t *offsets, gf_codec_stats *stats, int64_t *pair_counts, int32_t *status);
 double gf_codec_stats_h2(const int64_t *pair_table);
 
+/* ---- ICompressionDecoder.analyze for CodecCanonHuffman (compress/canonicalHuffman/CodecCanonHuffman.java:217-324,
+ * CanonHuffmanStats.java, CanonicalHuffman.countSymbols / getEntropy / getEscapeBitCounts): the text of every packing is
+ * decoded and its symbols counted on the GPU, the sums of CanonHuffmanStats are added to on the host in tile order.
+ * stats[0..4] by the predictor byte (PredictorModelType ordinal; 0 holds the uniform form, reported as "Uniform Value"),
+ * stats[5] = "All Predictors"; a predictor byte of 5 counts twice there.  escape_counts[6] = escapeBitCounts[1] of the
+ * codec: values with 2, 4, 6, 8, 16, 24 escape bits.  Both are ADDED to (zero them = clearAnalysisData).  status[t] != GF_OK
+ * (status may be null): the reference's analyze would throw -- nothing counted, except that a predictor byte >= 6 throws
+ * only after the tile's escape counts went into escape_counts.  sum_escape_bits leaves the 6-bit class out, as
+ * getEscapeBitCountTotal does.                                                                                          */
+typedef struct gf_canon_stats {
+    int64_t n_tiles;          /* nTilesCounted         */
+    int64_t n_bytes;          /* nBytesTotal           : packing bytes - 6 */
+    int64_t n_symbols;        /* nSymbolsTotal         : cells */
+    int64_t n_bits_overhead;  /* nBitsOverheadTotal    : bits of the code tables (getBitsInCodeTableCount) */
+    int64_t n_text_counted;   /* nSymbolsInTextCounted */
+    int64_t sum_length;       /* sumLength             : cells */
+    int64_t sum_observed;     /* sumObserved           : distinct low bytes of the text per tile, summed */
+    double sum_entropy;       /* sumEntropy            : CanonicalHuffman.getEntropy per tile, summed */
+    int64_t sum_escape_bits;  /* sumEscapeBits         */
+} gf_canon_stats;
+gf_status gf_canon_analyze_batch(gf_context *ctx, int n_rows, int n_cols, size_t n_tiles, const uint8_t *blob,
+                                 const uint64_t *offsets, gf_canon_stats *stats, int64_t *escape_counts, int32_t *status);
+
 /* ---- tile records (gvrs/RecordManager.java:153-204, 217-262, 386-520; gvrs/TileElementInt.java:196-219,
  * gvrs/TileElementShort.java:211-250; util/GridfourCRC32C.java): what RecordManager.writeTile appends to the file for a
  * tile of one integer-coded element, for a whole batch of dirty tiles in one call (flush()):
