@@ -1051,7 +1051,7 @@ __global__ __launch_bounds__(ENC_THREADS, CN_PACK_WGS) void k_canon_pack(GfEncod
 
 }  // namespace
 
-hipError_t gf_launch_canon_encode(const GfEncodeArgs &a, hipStream_t stream)
+hipError_t gf_launch_canon_encode(const GfEncodeArgs &a, hipStream_t stream, uint32_t *launched)
 {
     if (a.nTiles == 0) return hipSuccess;
     const dim3 grid = gf_tile_grid(a.nTiles);
@@ -1061,10 +1061,13 @@ hipError_t gf_launch_canon_encode(const GfEncodeArgs &a, hipStream_t stream)
         if (a.plane) hipLaunchKernelGGL((k_canon_encode<1, true>), grid, dim3(ENC_THREADS), 0, stream, a);
         else hipLaunchKernelGGL(k_canon_encode<1>, grid, dim3(ENC_THREADS), 0, stream, a);
         hipLaunchKernelGGL(k_canon_trees, gf_tile_grid((a.nTiles + CN_TW - 1) / CN_TW), dim3(64 * CN_TW), 0, stream, a);
+        if (launched) *launched |= GF_RT_CANON_ENC_1 | (a.plane ? GF_RT_ENC_PLANE : 0u);
     } else {
         hipLaunchKernelGGL(k_canon_encode<0>, grid, dim3(ENC_THREADS), 0, stream, a);
+        if (launched) *launched |= GF_RT_CANON_ENC_0;
     }
     hipLaunchKernelGGL(k_canon_pack, grid, dim3(ENC_THREADS), 0, stream, a);
+    if (launched) *launched |= GF_RT_CANON_PACK;
     return hipGetLastError();
 }
 

@@ -3692,16 +3692,23 @@ size_t gf_huffman_decode_lds_per_wg(const GfDecodeArgs &a)
     return sizeof(DecShared) + decodeDynLds(a.ldsM32Bytes, a.ldsTextBytes);
 }
 
-hipError_t gf_launch_huffman_decode(const GfDecodeArgs &a, hipStream_t stream, unsigned grid, const GfSideStream *side)
+hipError_t gf_launch_huffman_decode(const GfDecodeArgs &a, hipStream_t stream, unsigned grid, const GfSideStream *side, int roomyForm,
+                                    uint32_t *launched)
 {
     if (a.nTiles == 0) return hipSuccess;
+    uint32_t ran = 0;                                              // (gf_rt_dec_bit of every launch below, for the route report)
+    auto done = [&]() {
+        if (launched) *launched |= ran;
+        return hipGetLastError();
+    };
     const size_t dyn = decodeDynLds(a.ldsM32Bytes, a.ldsTextBytes);
     static GfDynLdsOptIn optG, optA, optF;
     hipError_t e;
     if (a.analysis) {
         if ((e = gf_opt_in_dyn_lds(k_huffman_decode<DEC_ANALYZE>, dyn, optA)) != hipSuccess) return e;
         hipLaunchKernelGGL(k_huffman_decode<DEC_ANALYZE>, dim3(grid), dim3(DEC_THREADS), dyn, stream, a);
-        return hipGetLastError();
+        ran |= gf_rt_dec_bit(DEC_ANALYZE, DEC_THREADS);
+        return done();
     }
     if ((e = gf_opt_in_dyn_lds(k_huffman_decode<DEC_GENERAL>, dyn, optG)) != hipSuccess) return e;
     if (a.retryFlag) {
@@ -3713,35 +3720,17 @@ hipError_t gf_launch_huffman_decode(const GfDecodeArgs &a, hipStream_t stream, u
         if (a.lean) {
             // the one-tile-per-call path: the fast kernel alone (a tile it leaves behind keeps GF_K_RETRY; the caller sees to it)
             hipLaunchKernelGGL(k_huffman_decode<DEC_FAST>, gf_tile_grid(a.nTiles), dim3(DEC_THREADS), dyn, stream, f);
-            return hipGetLastError();
+            ran |= gf_rt_dec_bit(DEC_FAST, DEC_THREADS);
+            return done();
         }
         if (!a.flagsCleared && (e = hipMemsetAsync(a.retryFlag, 0, 8, stream)) != hipSuccess) return e;
         // The roomy run -- the tiles the pre-pass marked GF_TREE_ROOMY, with LDS for two M32 bytes per cell; the workgroups of
-        // the other tiles leave at once -- BESIDE the first run (round 5): it is a few hundred tiles of a rough batch at two
-        // workgroups per CU, a chain of latencies that took 0.33 ms behind the first run's 1.2.  The roomy run stays on the
-        // caller's stream, directly behind the pre-pass, and the FIRST run goes to the context's side stream: the roomy workgroups
-        // must reach the CUs first -- once four workgroups of the first run hold a CU's LDS (4 x 40 KB), a 55 KB workgroup finds
-        // no room until two of them end together, i.e. until the first run drains (measured: the other order gained 0.06 ms of
-        // the 0.33).
-        // (a small batch -- BASELINE config 2: 1,024 tiles, 0.18 ms per decode -- loses more to the two hand-overs between the
-        // streams, ~10 us each, than the roomy run could hide: 0.183 -> 0.201 ms measured; there the runs follow one another)
-        // ... and a batch whose predecessors on this context listed no tile for the roomy run (smooth terrain: the run is 7 us of empty
-        // workgroups) keeps everything on one stream: the hand-overs were 15-20 us of its 0.70 ms.  The hint (roomySeenHost: 1 + the
-        // count of the last batch whose general kernel has finished, 0 before the first) may be a batch or two old; either order of
-        // the runs is correct for any data.
-        const bool roomyLikely = !a.roomySeenHost || *(volatile const uint32_t *)a.roomySeenHost != 1u;
-        const bool beside = a.ldsM32Roomy && side && side->stream && a.nTiles >= 4096 && roomyLikely;
-        // (round 6) a SMALL batch whose predecessors listed no tile for the roomy run does without its launch (5 us of BASELINE config
-        // 2's 165): should the pre-pass list a tile after all, the first run tries it, the general kernel takes it, and the next batch
-        // knows.  What a stale hint costs (-DGF_DEC_FORCE_NO_ROOMY on the rough surface): 1,024 tiles of 120 x 150 0.304 -> 0.339 ms,
-        // 1,300 0.350 -> 0.384, 3,000 0.530 -> 0.669 -- hence small batches only.  (For every batch, with a reduced grid for the run
-        // where none is expected: a caller that queues a smooth batch and then rough ones without waiting had each of them draw
-        // its 650 roomy tiles through 64 workgroups -- the default bench line's rough sub-record, 1.37 -> 2.38 ms; taken back.)
-#ifdef GF_DEC_FORCE_NO_ROOMY                                        // (experiment builds)
-        const bool noRoomy = a.ldsM32Roomy && a.nTiles < 4096;
-#else
-        const bool noRoomy = a.ldsM32Roomy && !roomyLikely && a.nTiles < 2048;
-#endif
+        // the other tiles leave at once -- beside the first run, behind it, or not at all: roomyForm, decided by the host plan
+        // (gf_internal_route_plan in gvrs_api.hip, where the measurements behind each form are)
+        const bool beside = a.ldsM32Roomy && roomyForm == GF_ROOMY_BESIDE;
+        const bool noRoomy = a.ldsM32Roomy && roomyForm == GF_ROOMY_SKIPPED;
+        if (beside && !(side && side->stream)) return hipErrorInvalidValue;
+        if (!a.ldsM32Roomy != (roomyForm == GF_ROOMY_NONE)) return hipErrorInvalidValue;
         f.noRoomyRun = noRoomy ? 1 : 0;
         GfDecodeArgs r = f;
         r.ldsM32Bytes = a.ldsM32Roomy;
@@ -3767,20 +3756,26 @@ hipError_t gf_launch_huffman_decode(const GfDecodeArgs &a, hipStream_t stream, u
             if ((e = hipStreamWaitEvent(side->stream, side->fork, 0)) != hipSuccess) return e;
             hipLaunchKernelGGL(k_huffman_decode<DEC_FAST_ROOMY>, dim3(roomyGrid), dim3(DEC_THREADS), dynRoomy, stream, r);
             hipLaunchKernelGGL(k_huffman_decode<DEC_FAST>, gf_tile_grid(a.nTiles), dim3(DEC_THREADS), dyn, side->stream, f);
+            ran |= gf_rt_dec_bit(DEC_FAST_ROOMY, DEC_THREADS) | gf_rt_dec_bit(DEC_FAST, DEC_THREADS);
             if ((e = hipEventRecord(side->join, side->stream)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(stream, side->join, 0)) != hipSuccess) return e;
         } else {
-            if (a.ldsM32Roomy && !noRoomy) hipLaunchKernelGGL(k_huffman_decode<DEC_FAST_ROOMY>, dim3(roomyGrid), dim3(DEC_THREADS), dynRoomy, stream, r);
+            if (a.ldsM32Roomy && !noRoomy) {
+                hipLaunchKernelGGL(k_huffman_decode<DEC_FAST_ROOMY>, dim3(roomyGrid), dim3(DEC_THREADS), dynRoomy, stream, r);
+                ran |= gf_rt_dec_bit(DEC_FAST_ROOMY, DEC_THREADS);
+            }
             hipLaunchKernelGGL(k_huffman_decode<DEC_FAST>, gf_tile_grid(a.nTiles), dim3(DEC_THREADS), dyn, stream, f);
+            ran |= gf_rt_dec_bit(DEC_FAST, DEC_THREADS);
         }
     }
     hipLaunchKernelGGL(k_huffman_decode<DEC_GENERAL>, dim3(grid), dim3(DEC_THREADS), dyn, stream, a);
-    return hipGetLastError();
+    ran |= gf_rt_dec_bit(DEC_GENERAL, DEC_THREADS);
+    return done();
 }
 
 // The canonical run (DEC_FAST_CANON): a.trees = the records of k_canon_parse_lengths, a.retryFlag[0] = zero before the launch and
 // non-zero behind it when some tile is left to k_canon_decode (status GF_K_RETRY).
-hipError_t gf_launch_huffman_decode_canon(const GfDecodeArgs &a, hipStream_t stream)
+hipError_t gf_launch_huffman_decode_canon(const GfDecodeArgs &a, hipStream_t stream, uint32_t *launched)
 {
     if (a.nTiles == 0) return hipSuccess;
     if (!a.retryFlag || !a.trees || a.ldsM32Roomy) return hipErrorInvalidValue;
@@ -3789,6 +3784,7 @@ hipError_t gf_launch_huffman_decode_canon(const GfDecodeArgs &a, hipStream_t str
     const hipError_t e = gf_opt_in_dyn_lds(k_huffman_decode<DEC_FAST_CANON>, dyn, opt);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_huffman_decode<DEC_FAST_CANON>, gf_tile_grid(a.nTiles), dim3(DEC_THREADS), dyn, stream, a);
+    if (launched) *launched |= gf_rt_dec_bit(DEC_FAST_CANON, DEC_THREADS);
     return hipGetLastError();
 }
 

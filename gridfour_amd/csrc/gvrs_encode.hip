@@ -1978,20 +1978,22 @@ __global__ __launch_bounds__(ENC_THREADS, 4) void k_m32_streams(GfM32Args a)
 // latencies -- phase A a round trip to memory per turn, the packer likewise --, and sixteen waves take a 120x150 tile in three turns
 // instead of nine (84 -> 76 us per call).  Only the two kernels a tile usually needs; what they leave behind keeps GF_K_RETRY
 // (GfEncodeArgs::lean).
-hipError_t gf_launch_huffman_encode_lean_t1024(const GfEncodeArgs &a, hipStream_t stream)
+hipError_t gf_launch_huffman_encode_lean_t1024(const GfEncodeArgs &a, hipStream_t stream, uint32_t *launched)
 {
     if (a.nTiles == 0) return hipSuccess;
     const size_t nCells = (size_t)a.nRows * (size_t)a.nCols;
     if (!a.packRecs || !a.retryFlag || !a.lean || 6ull * nCells >= (1ull << 23)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_huffman_encode<true>, gf_tile_grid(a.nTiles), dim3(ENC_THREADS), 0, stream, a);
     hipLaunchKernelGGL(k_huffman_pack, gf_tile_grid(a.nTiles), dim3(ENC_THREADS), 0, stream, a);
+    if (launched) *launched |= GF_RT_ENC_LEAN_T1024 | GF_RT_ENC_FAST | GF_RT_ENC_PACK;
     return hipGetLastError();
 }
 #else
-hipError_t gf_launch_huffman_encode(const GfEncodeArgs &a, hipStream_t stream)
+hipError_t gf_launch_huffman_encode(const GfEncodeArgs &a, hipStream_t stream, uint32_t *launched)
 {
     if (a.nTiles == 0) return hipSuccess;
     if (!a.packRecs) return hipErrorInvalidValue;
+    uint32_t ran = 0;                                              // (GF_RT_ENC_* of every launch below, for the route report)
     const unsigned grid = (unsigned)(a.nTiles < 65536 * 16 ? a.nTiles : 65536 * 16);
     const size_t nCells = (size_t)a.nRows * (size_t)a.nCols;
     // word 0: tiles for k_huffman_encode<false> (experiment builds only), word 1: for k_huffman_pack_rare -- zeroed by the fast
@@ -2015,22 +2017,32 @@ hipError_t gf_launch_huffman_encode(const GfEncodeArgs &a, hipStream_t stream)
             if (a.plane) hipLaunchKernelGGL((k_huffman_encode<true, 1, true>), gf_tile_grid(a.nTiles), dim3(ENC_THREADS), 0, stream, a);
             else hipLaunchKernelGGL((k_huffman_encode<true, 1>), gf_tile_grid(a.nTiles), dim3(ENC_THREADS), 0, stream, a);
             hipLaunchKernelGGL(k_huffman_trees, gf_tile_grid(a.nTiles), dim3(64), 0, stream, a);
-        } else
+            ran |= GF_RT_ENC_SPLIT | (a.plane ? GF_RT_ENC_PLANE : 0u);
+        } else {
         hipLaunchKernelGGL(k_huffman_encode<true>, gf_tile_grid(a.nTiles), dim3(ENC_THREADS), 0, stream, a);
+            ran |= GF_RT_ENC_FAST;
+        }
 #ifdef GF_ENC_NULLS_RETRY
         // (only this experiment build's fast kernel leaves tiles behind: the shipping one takes every tile of up to 2^23 / 6 cells, and
         // the general kernel's launch -- 4-5 us to find nothing to do -- went in round 4)
         hipLaunchKernelGGL(k_huffman_encode<false>, dim3(grid < 2048 ? grid : 2048), dim3(ENC_THREADS), 0, stream, a);
+        ran |= GF_RT_ENC_GENERAL;
 #endif
     } else {
         GfEncodeArgs g = a;
         g.retryFlag = nullptr;
         hipLaunchKernelGGL(k_huffman_encode<false>, dim3(grid), dim3(ENC_THREADS), 0, stream, g);
+        ran |= GF_RT_ENC_GENERAL;
     }
     // (round 6: the packer with a wave or two per tile -- a 64- and a 128-thread build of this file, 4 KB of window per wave -- was
     // measured: 0.192 / 0.176 ms against 0.176 with four waves on the bench batch, 0.42 / 0.36 against 0.32 on 200x200 tiles)
     hipLaunchKernelGGL(k_huffman_pack, gf_tile_grid(a.nTiles), dim3(ENC_THREADS), 0, stream, a);
-    if (!a.lean) hipLaunchKernelGGL(k_huffman_pack_rare, dim3(grid < 1024 ? grid : 1024), dim3(ENC_THREADS), 0, stream, a);
+    ran |= GF_RT_ENC_PACK;
+    if (!a.lean) {
+        hipLaunchKernelGGL(k_huffman_pack_rare, dim3(grid < 1024 ? grid : 1024), dim3(ENC_THREADS), 0, stream, a);
+        ran |= GF_RT_ENC_PACK_RARE;
+    }
+    if (launched) *launched |= ran;
     return hipGetLastError();
 }
 

@@ -192,16 +192,52 @@ struct GfLsopM32Args {
 
 hipError_t gf_launch_lsop_unpack_m32(const GfLsopM32Args &a, hipStream_t stream, unsigned grid);
 
-hipError_t gf_launch_huffman_encode(const GfEncodeArgs &a, hipStream_t stream);
-hipError_t gf_launch_huffman_encode_lean_t1024(const GfEncodeArgs &a, hipStream_t stream);   // 1024-thread workgroups, GfEncodeArgs::lean only
-hipError_t gf_launch_huffman_decode(const GfDecodeArgs &a, hipStream_t stream, unsigned grid, const GfSideStream *side = nullptr);
-hipError_t gf_launch_huffman_decode_t512(const GfDecodeArgs &a, hipStream_t stream, unsigned grid, const GfSideStream *side = nullptr);   // 512-thread workgroups
-hipError_t gf_launch_huffman_decode_t1024(const GfDecodeArgs &a, hipStream_t stream, unsigned grid, const GfSideStream *side = nullptr);  // 1024-thread workgroups
+// The kernels a batch launched, as bits set in host code at the launch sites (the launchers' `launched` argument, may be null):
+// what gf_internal_route_report hands to tests.  Decode: k_huffman_decode<MODE> of the 256-, 512- and 1024-thread builds is bit
+// 3 * MODE + build (MODE = DEC_GENERAL 0, DEC_ANALYZE 1, DEC_FAST 2, DEC_FAST_ROOMY 3, DEC_FAST_CANON 4; build 0, 1, 2).
+constexpr int GF_RT_DEC_MODE_BITS = 3;
+constexpr uint32_t GF_RT_CANON_DEC_T256 = 1u << 15;      // k_canon_decode<false>, 256 threads
+constexpr uint32_t GF_RT_CANON_DEC_T512 = 1u << 16;      // ... 512 threads
+constexpr uint32_t GF_RT_CANON_ANALYZE = 1u << 17;       // k_canon_decode<true> + k_canon_stats
+constexpr uint32_t GF_RT_TREES_1 = 1u << 18;             // k_huffman_parse_trees<1>
+constexpr uint32_t GF_RT_TREES_64 = 1u << 19;            // k_huffman_parse_trees<64>
+constexpr uint32_t GF_RT_LENGTHS_1 = 1u << 20;           // k_canon_parse_lengths<1>
+constexpr uint32_t GF_RT_LENGTHS_64 = 1u << 21;          // k_canon_parse_lengths<64>
+__host__ __device__ constexpr uint32_t gf_rt_dec_bit(int mode, int threads)
+{
+    return 1u << (GF_RT_DEC_MODE_BITS * mode + (threads == 1024 ? 2 : threads == 512 ? 1 : 0));
+}
+// encode
+constexpr uint32_t GF_RT_ENC_SPLIT = 1u << 0;            // k_huffman_encode<true, 1> + k_huffman_trees (the batch form)
+constexpr uint32_t GF_RT_ENC_FAST = 1u << 1;             // k_huffman_encode<true> alone
+constexpr uint32_t GF_RT_ENC_GENERAL = 1u << 2;          // k_huffman_encode<false> (tiles of 2^23 / 6 cells and more)
+constexpr uint32_t GF_RT_ENC_PACK = 1u << 3;             // k_huffman_pack
+constexpr uint32_t GF_RT_ENC_PACK_RARE = 1u << 4;        // k_huffman_pack_rare
+constexpr uint32_t GF_RT_ENC_LEAN_T1024 = 1u << 5;       // the kernels above from the 1024-thread one-tile build
+constexpr uint32_t GF_RT_CANON_ENC_1 = 1u << 6;          // k_canon_encode<1> + k_canon_trees
+constexpr uint32_t GF_RT_CANON_ENC_0 = 1u << 7;          // k_canon_encode<0>
+constexpr uint32_t GF_RT_CANON_PACK = 1u << 8;           // k_canon_pack
+constexpr uint32_t GF_RT_ENC_PLANE = 1u << 9;            // the phase-A kernel wrote the byte plane (GfEncodeArgs::plane)
+// The fast decode kernel's roomy run (GfDecodeArgs::ldsM32Roomy): which form gf_launch_huffman_decode* gives it
+enum { GF_ROOMY_NONE = 0,      // no roomy budget (ldsM32Roomy == 0): one run of the fast kernel, or none
+       GF_ROOMY_BESIDE = 1,    // the roomy run on the caller's stream, the first run on the context's side stream
+       GF_ROOMY_BEHIND = 2,    // both runs on the caller's stream, the roomy run first
+       GF_ROOMY_SKIPPED = 3 }; // no roomy launch (GfDecodeArgs::noRoomyRun): the first run tries the listed tiles as well
+
+hipError_t gf_launch_huffman_encode(const GfEncodeArgs &a, hipStream_t stream, uint32_t *launched = nullptr);
+hipError_t gf_launch_huffman_encode_lean_t1024(const GfEncodeArgs &a, hipStream_t stream, uint32_t *launched = nullptr);   // 1024-thread workgroups, GfEncodeArgs::lean only
+// roomyForm: GF_ROOMY_* (gf_internal_route_plan); GF_ROOMY_BESIDE needs side
+hipError_t gf_launch_huffman_decode(const GfDecodeArgs &a, hipStream_t stream, unsigned grid, const GfSideStream *side, int roomyForm,
+                                    uint32_t *launched = nullptr);
+hipError_t gf_launch_huffman_decode_t512(const GfDecodeArgs &a, hipStream_t stream, unsigned grid, const GfSideStream *side, int roomyForm,
+                                         uint32_t *launched = nullptr);   // 512-thread workgroups
+hipError_t gf_launch_huffman_decode_t1024(const GfDecodeArgs &a, hipStream_t stream, unsigned grid, const GfSideStream *side, int roomyForm,
+                                          uint32_t *launched = nullptr);  // 1024-thread workgroups
 // CodecCanonHuffman packings without escapes through the fast body (DEC_FAST_CANON in gvrs_decode.hip); the tiles it leaves carry
 // GF_K_RETRY and a.retryFlag[0] != 0: k_canon_decode (launched with the same retryFlag) takes those
-hipError_t gf_launch_huffman_decode_canon(const GfDecodeArgs &a, hipStream_t stream);
-hipError_t gf_launch_huffman_decode_canon_t512(const GfDecodeArgs &a, hipStream_t stream);
-hipError_t gf_launch_huffman_decode_canon_t1024(const GfDecodeArgs &a, hipStream_t stream);
+hipError_t gf_launch_huffman_decode_canon(const GfDecodeArgs &a, hipStream_t stream, uint32_t *launched = nullptr);
+hipError_t gf_launch_huffman_decode_canon_t512(const GfDecodeArgs &a, hipStream_t stream, uint32_t *launched = nullptr);
+hipError_t gf_launch_huffman_decode_canon_t1024(const GfDecodeArgs &a, hipStream_t stream, uint32_t *launched = nullptr);
 size_t gf_huffman_decode_lds_per_wg(const GfDecodeArgs &a);           // LDS bytes per workgroup, 256-thread build
 size_t gf_huffman_decode_lds_per_wg_t512(const GfDecodeArgs &a);      // ... 512-thread build
 size_t gf_huffman_decode_lds_per_wg_t1024(const GfDecodeArgs &a);     // ... 1024-thread build
@@ -217,7 +253,7 @@ hipError_t gf_launch_canon_parse_lengths(const uint8_t *blob, size_t blobBytes, 
                                          hipStream_t stream, uint32_t *clearFlags = nullptr);   // clearFlags: GfDecodeArgs::retryFlag, zeroed
 
 // CodecCanonHuffman (gvrs_canon_encode.hip / gvrs_canon_decode.hip); same argument blocks as the legacy codec
-hipError_t gf_launch_canon_encode(const GfEncodeArgs &a, hipStream_t stream);
+hipError_t gf_launch_canon_encode(const GfEncodeArgs &a, hipStream_t stream, uint32_t *launched = nullptr);
 size_t gf_canon_stat_words();          // words per tile of GfEncodeArgs::encStats for the canonical encoder
 size_t gf_canon_pack_rec_words();      // words per tile of GfEncodeArgs::packRecs for the canonical encoder
 hipError_t gf_launch_canon_decode(const GfDecodeArgs &a, hipStream_t stream, unsigned grid);

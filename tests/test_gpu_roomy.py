@@ -31,10 +31,14 @@ def _roundtrip(b, ctx, style, tile0=0, sample=53, check_oracle=True):
     return vals
 
 
+def _fast_lds_m32(cells):
+    """gf_huffman_decode_lds_m32 (gvrs_decode.hip); tests/test_route_plan.py holds it to the library's route plan"""
+    return (min(max(cells + cells // 8 + 512, 8192), 98304) + 31) // 32 * 32
+
+
 def _n_roomy(vals, n_rows, n_cols, lengths, b):
     """tiles of the batch whose packing's nM32 field is beyond the fast run's LDS budget (what the pre-pass lists)"""
-    cells = n_rows * n_cols
-    lim = (min(max(cells + cells // 8 + 512, 8192), 98304) + 31) // 32 * 32      # gf_huffman_decode_lds_m32 (gvrs_decode.hip)
+    lim = _fast_lds_m32(n_rows * n_cols)
     n = 0
     for t in range(b.n_tiles):
         hdr = b.get_packing(t, 10)
