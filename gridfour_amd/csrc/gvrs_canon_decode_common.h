@@ -871,6 +871,9 @@ __device__ __forceinline__ int32_t cd_decode_stream(CanonDec &S, const Text T, u
     const uint32_t qStar = S.qStar;
     int32_t tileStatus = GF_K_OK;
     if (qStar == 0xFFFFFFFFu || S.qe[qStar] != CD_END_EOT) tileStatus = GF_K_ERR_BOUNDS;   // no end-of-text: read past the data
+    // the end-of-text code must end inside the packing: a text read in place (not staged in LDS, which is zero behind endBit) sees
+    // the bytes behind the packing -- slot padding or the next packing -- and those can complete the code
+    else if (S.qx[qStar] > endBit) tileStatus = GF_K_ERR_BOUNDS;
     // exclusive prefix sum of the counts over the chain
     uint32_t base[CD_NCUR], myCount[CD_NCUR], firstHalf = 0;              // firstHalf: values of subsequences 0..DEC_THREADS-1 (uniform)
     {

@@ -128,3 +128,26 @@ def domains(shapes=None):
 def reached(dom, name):
     """the variants' domains of one instantiation, merged"""
     return [s for k, v in dom.items() if k.split(":", 1)[1] == name for s in v]
+
+
+def square_ends(dom, name, min_cells=1, max_cells=1 << 16):
+    """first and last square of an instantiation's domain within the sweep, among squares of 2x2 and min_cells..max_cells cells
+    ([None] where there is none: the caller's test fails on it)"""
+    sq = [s for s in dom.get(name, []) if s[0] == s[1] >= 2 and min_cells <= s[0] * s[1] <= max_cells]
+    if not sq:
+        return [None]
+    return [sq[0], sq[-1]] if sq[-1] != sq[0] else [sq[0]]
+
+
+def roomy_tiles(r, c, n, seed, p):
+    """tiles whose M32 stream outgrows the fast run's buffer and fits the roomy one (plan p): small noise with spikes of 450 (two
+    M32 bytes) at a density chosen on the oracle's packing of the first tile"""
+    import numpy as np
+    import oracle
+    for q in (0.2, 0.12, 0.06):
+        rng = np.random.default_rng(seed + r * 7 + c)
+        tiles = [(rng.integers(0, 4, r * c) + 450 * (rng.random(r * c) < q)).astype(np.int32) for _ in range(n)]
+        n_m32 = int.from_bytes(oracle.codec_huffman_encode(0, r, c, tiles[0])[0][6:10], "little")
+        if p.fastM32 < n_m32 <= p.ldsM32Roomy - 4096:
+            return tiles
+    raise AssertionError("no spike density puts a %dx%d tile between the fast and the roomy budget" % (r, c))

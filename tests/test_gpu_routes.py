@@ -26,10 +26,7 @@ def _ctx():
 
 def _ends(name, min_cells=1, max_cells=1 << 16):
     """first and last square of the instantiation's domain within the sweep, among squares of 2x2 and min_cells..max_cells cells"""
-    dom = [s for s in DOMAINS.get(name, []) if s[0] == s[1] >= 2 and min_cells <= s[0] * s[1] <= max_cells]
-    if not dom:
-        return [None]                                # (a case that fails: _need)
-    return [dom[0], dom[-1]] if dom[-1] != dom[0] else [dom[0]]
+    return rp.square_ends(DOMAINS, name, min_cells, max_cells)
 
 
 def _need(shape):
@@ -98,16 +95,7 @@ def _retry_word(p):
     return 1 if p.ldsM32Roomy else 0
 
 
-def _roomy_tiles(r, c, n, seed, p):
-    """tiles whose M32 stream outgrows the fast run's buffer and fits the roomy one: small noise with spikes of 450 (two M32
-    bytes) at a density chosen on the oracle's packing of the first tile"""
-    for q in (0.2, 0.12, 0.06):
-        rng = np.random.default_rng(seed + r * 7 + c)
-        tiles = [(rng.integers(0, 4, r * c) + 450 * (rng.random(r * c) < q)).astype(np.int32) for _ in range(n)]
-        n_m32 = int.from_bytes(oracle.codec_huffman_encode(0, r, c, tiles[0])[0][6:10], "little")
-        if p.fastM32 < n_m32 <= p.ldsM32Roomy - 4096:
-            return tiles
-    raise AssertionError("no spike density puts a %dx%d tile between the fast and the roomy budget" % (r, c))
+_roomy_tiles = rp.roomy_tiles
 
 
 def _max_stride(r, c):
