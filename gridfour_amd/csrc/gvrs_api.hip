@@ -423,9 +423,7 @@ static gf_status routePlan(int kind, int nRows, int nCols, size_t nTiles, int le
     if (kind == KIND_CANON) {
         // (encodeBatchDev always hands the canonical encoder its statistics records: the <1> + k_canon_trees form)
         p.encBits = GF_RT_CANON_ENC_1 | GF_RT_CANON_PACK;
-#ifndef GF_ENC_NO_PLANE
         if (!lean) p.encBits |= GF_RT_ENC_PLANE;
-#endif
     } else if (kind == KIND_HUFFMAN) {
         p.leanEncode = lean && smallEnc;
         if (p.leanEncode) p.encBits = GF_RT_ENC_LEAN_T1024 | GF_RT_ENC_FAST | GF_RT_ENC_PACK;
@@ -437,12 +435,7 @@ static gf_status routePlan(int kind, int nRows, int nCols, size_t nTiles, int le
                 const bool split = !lean;
 #endif
                 p.encBits = split ? GF_RT_ENC_SPLIT : GF_RT_ENC_FAST;
-#ifndef GF_ENC_NO_PLANE
                 if (split) p.encBits |= GF_RT_ENC_PLANE;
-#endif
-#ifdef GF_ENC_NULLS_RETRY
-                p.encBits |= GF_RT_ENC_GENERAL;
-#endif
             } else p.encBits = GF_RT_ENC_GENERAL;
             p.encBits |= GF_RT_ENC_PACK | (lean ? 0u : GF_RT_ENC_PACK_RARE);
         }
@@ -477,9 +470,6 @@ static gf_status routePlan(int kind, int nRows, int nCols, size_t nTiles, int le
         // prefix-coded byte string like any other, and that kernel decodes it once (symbol pool, byte path) where k_canon_decode
         // decodes it twice.  For tile shapes its byte path takes; what it leaves (GF_K_RETRY) k_canon_decode picks up.
         p.viaFast = !analysis && nRows >= 2 && nCols >= 4 && nCols <= 256 && cells + 8 <= p.fastM32;
-#ifdef GF_CANON_NO_FAST_RUN                                       // (experiment builds: tools/ab.sh)
-        p.viaFast = 0;
-#endif
         if (p.viaFast) {
             p.decThreads = lean ? 1024 : huffmanBuild(p.fastM32, 0);
             p.decBits |= gf_rt_dec_bit(4 /* DEC_FAST_CANON */, p.decThreads);
@@ -529,9 +519,6 @@ static gf_status routePlan(int kind, int nRows, int nCols, size_t nTiles, int le
     // per cell; the pre-pass sorts the tiles
     const size_t roomy = std::min<size_t>(98304, (2 * cells + 1024 + 31) & ~(size_t)31);
     p.ldsM32Roomy = roomy > p.fastM32 ? (uint32_t)roomy : 0u;
-#ifdef GF_DEC_NO_ROOMY                                              // (experiment builds)
-    p.ldsM32Roomy = 0u;
-#endif
     if (!p.ldsM32Roomy) return GF_OK;
     // The roomy run BESIDE the first run (round 5): it is a few hundred tiles of a rough batch at two workgroups per CU, a chain of
     // latencies that took 0.33 ms behind the first run's 1.2.  The roomy run stays on the caller's stream, directly behind the
@@ -545,21 +532,15 @@ static gf_status routePlan(int kind, int nRows, int nCols, size_t nTiles, int le
     // last batch whose general kernel has finished, 0 before the first) may be a batch or two old; either order of the runs is
     // correct for any data.
     const bool roomyLikely = roomySeen != 1u;
-#ifdef GF_DEC_ROOMY_BEHIND                                          // (experiment builds: the roomy run behind the first, as in round 4)
-    side = 0;
-#endif
     const bool beside = side && nTiles >= 4096 && roomyLikely;
     // (round 6) a SMALL batch whose predecessors listed no tile for the roomy run does without its launch (5 us of BASELINE config
     // 2's 165): should the pre-pass list a tile after all, the first run tries it, the general kernel takes it, and the next batch
-    // knows.  What a stale hint costs (-DGF_DEC_FORCE_NO_ROOMY on the rough surface): 1,024 tiles of 120 x 150 0.304 -> 0.339 ms,
-    // 1,300 0.350 -> 0.384, 3,000 0.530 -> 0.669 -- hence small batches only.  (For every batch, with a reduced grid for the run
-    // where none is expected: a caller that queues a smooth batch and then rough ones without waiting had each of them draw
-    // its 650 roomy tiles through 64 workgroups -- the default bench line's rough sub-record, 1.37 -> 2.38 ms; taken back.)
-#ifdef GF_DEC_FORCE_NO_ROOMY                                        // (experiment builds)
-    const bool noRoomy = nTiles < 4096;
-#else
+    // knows.  What a stale hint costs (measured on the rough surface with the launch left out of every batch below 4,096 tiles):
+    // 1,024 tiles of 120 x 150 0.304 -> 0.339 ms, 1,300 0.350 -> 0.384, 3,000 0.530 -> 0.669 -- hence small batches only.  (For
+    // every batch, with a reduced grid for the run where none is expected: a caller that queues a smooth batch and then rough ones
+    // without waiting had each of them draw its 650 roomy tiles through 64 workgroups -- the default bench line's rough sub-record,
+    // 1.37 -> 2.38 ms; taken back.)
     const bool noRoomy = !roomyLikely && nTiles < 2048;
-#endif
     p.roomyForm = beside ? GF_ROOMY_BESIDE : noRoomy ? GF_ROOMY_SKIPPED : GF_ROOMY_BEHIND;
     if (p.roomyForm != GF_ROOMY_SKIPPED) p.decBits |= gf_rt_dec_bit(3 /* DEC_FAST_ROOMY */, p.decThreads);
     return GF_OK;
@@ -684,12 +665,10 @@ static gf_status encodeBatchDev(int kind, gf_context *c, void *stream, int codec
         // (round 6) the byte plane of raw row differences between phase A and the packer (GfEncodeArgs::plane), behind the records
         a.plane = nullptr;
         a.planeStride = 0;
-#ifndef GF_ENC_NO_PLANE
         if ((kind == KIND_HUFFMAN || kind == KIND_CANON) && !a.lean) {
             a.planeStride = encPlaneStride(nRows, nCols);
             a.plane = (uint8_t *)c->packRecs.p + roundUp(need, 256);
         }
-#endif
     }
     uint32_t ran = 0;
     if (kind == KIND_CANON) GF_HIP(gf_launch_canon_encode(a, stream ? (hipStream_t)stream : c->stream, &ran));
@@ -2349,20 +2328,12 @@ gf_status gf_lsop12_decode_batch_i32_dev(gf_context *c, void *stream, int nRows,
     gf_status s = lsopParseLengths(c, st, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths);
     if (s != GF_OK) return s;
     // (round 6) interior residuals as byte planes in the reconstruction's order where a tile's values allow (gvrs_kernels.h)
-#ifdef GF_LSOP_NO_PLANES                                    // (experiment builds: tools/ab_kernels.sh)
-    const bool lsopPlanes = false;
-#else
     const bool lsopPlanes = true;
-#endif
     GF_HIP(gf_launch_lsop_unpack2(dBlob, blobBytes, dOffsets, slotStride, dLengths, dResiduals, resStride, dCoefs,
                                   dScratchStatus, nTiles, nRows, nCols, gf_lsop_unpack_lds_text(nRows, nCols), grid, st,
                                   (const uint32_t *)c->trees.p, g_decodeDebug,
                                   // (the serial walk of a lane pays where sixty-four tiles share a wave: large batches)
-#ifdef GF_LSOP_NO_HEAD                                      // (experiment builds: tools/ab_kernels.sh)
-                                  nullptr,
-#else
                                   gf_prepass_tiles_per_wave(nTiles) == 64u ? (uint32_t *)c->trees.p + nTiles * (size_t)GF_CANON_REC_WORDS : nullptr,
-#endif
                                   lsopPlanes));
     s = lsopUnpackM32Deflate(c, st, nRows, nCols, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths, dResiduals, resStride,
                              dCoefs, dScratchStatus);

@@ -195,7 +195,6 @@ __device__ __forceinline__ int cn_code_lengths(CanonScratch &S, CanonPM &M, uint
 {
     uint32_t K[8];
     int n = 0;
-#ifndef GF_CN_NO_COMPACT
     if constexpr (NREG > 1) {
         // The symbols in use first, side by side (round 5): a terrain tile uses 60 to 130 of the 260, and the sorting network over the
         // 512 slots that hold them all is 45 stages of eight registers -- a fifth of cn_build's instructions -- where 128 slots take
@@ -222,9 +221,7 @@ __device__ __forceinline__ int cn_code_lengths(CanonScratch &S, CanonPM &M, uint
         else if (n <= 128) wave_bitonic_sort<2>(K, lane);
         else if (NREG <= 4 || n <= 256) wave_bitonic_sort<(NREG < 4 ? NREG : 4)>(K, lane);
         else wave_bitonic_sort<NREG>(K, lane);
-    } else
-#endif
-    {
+    } else {
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             K[r] = CN_DEAD;

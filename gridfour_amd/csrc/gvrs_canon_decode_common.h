@@ -936,7 +936,6 @@ __device__ __forceinline__ int32_t cd_decode_stream(CanonDec &S, const Text T, u
             const uint32_t bound = Bn == endBit ? 0xFFFFFFF0u : Bn;
             uint32_t k = base[j], a = mine ? (CD_NCUR == 1 ? myStart[j] : S.qs[q]) : 0u, v = 0;
             bool fin = !mine, pend = false, started = q != 0;
-#ifndef GF_CD_NO_PLAIN_LOOP
             // A code without escapes, null and spare symbol (round 5; wave-uniform: the tile's code lengths say so): every symbol
             // is a complete value the moment it is read -- nothing pends, two values per lookup where the table pairs them.
             if (plainOnly) {
@@ -953,7 +952,6 @@ __device__ __forceinline__ int32_t cd_decode_stream(CanonDec &S, const Text T, u
                     fin = fin || !take;
                 }
             }
-#endif
             while (__any(!fin)) {
                 const uint32_t w = cd_peek(T, a);
                 const uint32_t e = cd_entry_of(S, w);

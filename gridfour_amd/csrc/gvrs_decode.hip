@@ -913,7 +913,7 @@ __device__ int32_t huffman_to_m32_fast(DecShared &S, const uint32_t *__restrict_
     (void)dbg;
 #endif
     if (S.chainTotal < nM32) status = GF_K_ERR_BOUNDS;                   // ran out of bits
-#ifdef GF_DEC_POOL_FORCE_OVERFLOW                                        // (experiment builds: the fall-back behind a pool that overflowed)
+#ifdef GF_DEC_POOL_FORCE_OVERFLOW                                        // (stress builds: the fall-back behind a pool that overflowed)
     if (false) {
 #else
     if (poolWords && !S.poolOverflow) {
@@ -2089,9 +2089,6 @@ __device__ __forceinline__ int32_t m32_to_tile(DecShared &S, M32Ptr m32, uint32_
             __syncthreads();
             GF_CSTAMP(tcC);
             if (!skipRows) finishRows(it);
-#ifdef GF_DEC_END_BARRIER2
-            __syncthreads();
-#endif
             // (no barrier behind the rows -- round 5: what they read from the ring is overwritten by the NEXT chunk's ring writes,
             // and those stand behind that chunk's scan barrier, which no wave passes before every wave has finished these rows)
         }
@@ -2463,11 +2460,7 @@ __global__ __launch_bounds__(DEC_THREADS, MODE >= 2 ? GF_DEC_WGS : GF_DEC_WGS_GE
         // The fast kernel's leaf records (round 4): where they lie depends on the tile's index alone, so they are asked for HERE, with
         // the packing's offset and length, and arrive while the header is read -- the tile's start was four dependent round trips
         // to memory (offset / length, header, record scalars, leaf arrays), now two.
-#ifdef GF_DEC_NO_PREFETCH                                          // (experiment builds: tools/ab.sh)
-        constexpr bool PRE = CANON;
-#else
         constexpr bool PRE = FAST;
-#endif
         unsigned long long preCode = 0;
         uint32_t preLen = 0, preSym = 0, preRec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         // (and the header's twelve bytes, before the packing's length is known, where the blob has that many behind the offset)
@@ -2858,11 +2851,7 @@ __global__ __launch_bounds__(DEC_THREADS, MODE >= 2 ? GF_DEC_WGS : GF_DEC_WGS_GE
                                                            // the symbol pool of the single-decode form: the tile's own output area (not
                                                            // in the one-tile-per-call path, whose output lies in host memory); the spare
                                                            // byte: in the second-level table's area behind the stream, dead by then
-#ifdef GF_DEC_NO_POOL                                      // (experiment builds: tools/ab.sh)
-                                                           nullptr, 0u, 0u);
-#else
                                                            a.lean ? nullptr : o, nCells * 4u, a.ldsM32Bytes + 4u);
-#endif
                 } else if (pkWords * 4u <= a.ldsTextBytes) {
                     // stage the packing in LDS: one coalesced pass, then every symbol waits on LDS only
                     uint32_t *txt = reinterpret_cast<uint32_t *>(ldsDyn + a.ldsM32Bytes + bmArea);
@@ -3308,7 +3297,6 @@ __global__ __launch_bounds__(64) void k_huffman_parse_trees(const uint8_t *__res
     // M32 bytes apart (the lanes do that over the finished records), it does not switch the wave's lanes off and on around three LDS
     // stores (every lane stores the same record, four words in one store), it takes its minima on the scalar unit.)
     __shared__ __attribute__((aligned(16))) uint32_t leafLds[perWave == 1u ? 4 * 256 : 4];
-#ifndef GF_PT_NO_SCAN                                               // (experiment builds: the walk alone)
     if constexpr (perWave == 1u) {
         // THE WALK AS SCANS (round 6).  What is sequential in a serialised tree is less than the walk makes it:
         //   * where the records start -- a branch is one bit, a leaf nine -- is a transducer with nine states (bits still to skip): a
@@ -3440,7 +3428,6 @@ __global__ __launch_bounds__(64) void k_huffman_parse_trees(const uint8_t *__res
             __syncthreads();                                            // (the walk below writes the same LDS words)
         }
     }
-#endif
     if constexpr (perWave == 1u) {
       if (!walked) {
         uint64_t fbuf = buf, c = 0;

@@ -504,11 +504,7 @@ __device__ PackStateOk pack_flat_waves(const uint32_t *__restrict__ tile, uint32
             GF_JOIN8_OR(wwin, bits + incl - myBits, GF_CD, GF_LN, n01, n45, n0);
 #undef GF_LN
 #undef GF_CD
-#ifdef GF_PACK_NO_PAIRS                                             // (experiment builds: tools/ab.sh)
-        } else if (false) {
-#else
         } else if (hard == 0u && max(max(n01, n23), max(n45, n67)) <= 64u) {
-#endif
             uint32_t pos = bits + incl - myBits;
 #pragma unroll
             for (int q = 0; q < CPT; q += 2) {
@@ -714,11 +710,11 @@ constexpr int ENC_AB_WGS = ENC_THREADS == 256 ? 6 : 1, ENC_PACK_WGS = ENC_THREAD
 
 constexpr int GF_K_RETRY = 0x7fff0002;          // internal: the fast kernel leaves this tile to the general one
 
-// Two instantiations of one body.  FAST is what a batch of terrain tiles consists of: no null cells, symbol counts below
-// 2^23 (the in-register sort and the data-parallel tree rounds).  A tile with nulls (its own predictor, seed from a mean,
-// a second histogram pass) is marked GF_K_RETRY and left to the general instantiation, which with a.retryFlag touches only
-// marked tiles and returns at once when there are none.  The general body is twice the size of the fast one and carries the
-// register pressure of the rare paths into every tile's allocation.
+// Two instantiations of one body.  FAST is what a batch of terrain tiles consists of: symbol counts below 2^23 (the in-register
+// sort and the data-parallel tree rounds); it takes every tile of such a batch, those with nulls included (their own predictor,
+// seed from a mean, a second histogram pass).  The general instantiation takes the larger tiles; with a.retryFlag it would touch
+// only tiles marked GF_K_RETRY and return at once when there are none, but its launcher passes none.  The general body is twice
+// the size of the fast one and carries the register pressure of the rare paths into every tile's allocation.
 // PART 0: phases A and B and the selection in one kernel (the general kernel, the one-tile-per-call build, the diagnostic flavour).
 // PART 1 (round 4, CodecHuffman batches): phase A alone -- the histograms and what else the trees need go to GfEncodeArgs::encStats,
 // and k_huffman_trees takes it from there with ONE WAVE PER TILE.  In the one-kernel form the tree of a tile is built by one wave
@@ -788,11 +784,7 @@ __global__ __launch_bounds__(ENC_THREADS, PART == 1 && ENC_THREADS == 256 && GF_
             const uint32_t cStep = STEP_CELLS % nC;
             for (uint32_t i0 = (uint32_t)tid * CPT; i0 < nCells; i0 += STEP_CELLS) {
                 Cells8 Q;
-#ifdef GF_ENC_HALO_LOADS                                                 // (experiment builds: the halo words as three loads per lane)
-                load_cells8(tile, nC, nCells, i0, Q);
-#else
                 load_cells8_wave(tile, nC, nCells, i0, Q);
-#endif
                 uint32_t c = c0;
                 // a tile with a null cell takes the nulls predictor alone, with a histogram of its own (below): once a lane of the wave
                 // has seen one, the three histograms of this pass are not needed any more -- only the scan for valid cells goes on
@@ -891,35 +883,12 @@ __global__ __launch_bounds__(ENC_THREADS, PART == 1 && ENC_THREADS == 256 && GF_
                 }
                 if (__all(widest <= 252u && lowest != (int32_t)0x80000000)) {
                     myFlags |= 2u;
-#ifdef GF_ENC_HIST_AGG
-                    // (experiment build, round 6: the round-5 review's wave-level aggregation of the hot bins -- the value the first lane
-                    // holds is counted once for all the lanes that hold it when they are sixteen or more; measured in profiles/HISTORY.md)
-                    auto addAgg = [&](uint32_t *h, uint32_t d) {
-                        d &= 0xffu;
-                        const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)d);
-                        const unsigned long long m = __ballot(d == d0);
-                        const uint32_t n = (uint32_t)__popcll(m);
-                        if (n >= 16u) {
-                            if (lane == 0) atomicAdd(h + d0 * HR, n);
-                            if (d != d0) atomicAdd(h + d * HR, 1u);
-                        } else {
-                            atomicAdd(h + d * HR, 1u);
-                        }
-                    };
-#pragma unroll
-                    for (int j = 0; j < CPT; j++) {
-                        addAgg(h0, D1[j]);
-                        addAgg(h1, D2[j]);
-                        if (triOk) addAgg(h2, D3[j]);
-                    }
-#else
 #pragma unroll
                     for (int j = 0; j < CPT; j++) {
                         atomicAdd(h0 + (D1[j] & 0xffu) * HR, 1u);
                         atomicAdd(h1 + (D2[j] & 0xffu) * HR, 1u);
                         if (triOk) atomicAdd(h2 + (D3[j] & 0xffu) * HR, 1u);
                     }
-#endif
                 } else {
 #pragma unroll
                     for (int j = 0; j < CPT; j++) {
@@ -999,18 +968,6 @@ __global__ __launch_bounds__(ENC_THREADS, PART == 1 && ENC_THREADS == 256 && GF_
             continue;
         }
 
-#ifdef GF_ENC_NULLS_RETRY
-        if constexpr (FAST) {
-            if (anyNull) {
-                if (tid == 0) {
-                    a.status[t] = GF_K_RETRY;
-                    atomicOr(a.retryFlag, 1u);
-                }
-                __syncthreads();
-                continue;
-            }
-        }
-#endif
         if (anyNull) {
             // ---- nulls path: seed (PredictorModelDifferencingWithNulls.java:79-105), then one histogram ----
             // A cell's residual is v - prior, prior = left neighbour (column 0: the first cell of the row above), and the seed in
@@ -1996,13 +1953,9 @@ hipError_t gf_launch_huffman_encode(const GfEncodeArgs &a, hipStream_t stream, u
     uint32_t ran = 0;                                              // (GF_RT_ENC_* of every launch below, for the route report)
     const unsigned grid = (unsigned)(a.nTiles < 65536 * 16 ? a.nTiles : 65536 * 16);
     const size_t nCells = (size_t)a.nRows * (size_t)a.nCols;
-    // word 0: tiles for k_huffman_encode<false> (experiment builds only), word 1: for k_huffman_pack_rare -- zeroed by the fast
-    // kernel's first workgroup, or here where that kernel does not run or sets word 0 itself
-#ifndef GF_ENC_NULLS_RETRY
+    // word 1: the tiles left to k_huffman_pack_rare -- zeroed by the fast kernel's first workgroup, or here where that kernel does
+    // not run (word 0: the fast kernel leaves no tile to k_huffman_encode<false>, which runs without a.retryFlag)
     if (a.retryFlag && !a.lean && 6ull * nCells >= (1ull << 23)) {
-#else
-    if (a.retryFlag && !a.lean) {
-#endif
         const hipError_t e = hipMemsetAsync(a.retryFlag, 0, 8, stream);
         if (e != hipSuccess) return e;
     }
@@ -2022,12 +1975,6 @@ hipError_t gf_launch_huffman_encode(const GfEncodeArgs &a, hipStream_t stream, u
         hipLaunchKernelGGL(k_huffman_encode<true>, gf_tile_grid(a.nTiles), dim3(ENC_THREADS), 0, stream, a);
             ran |= GF_RT_ENC_FAST;
         }
-#ifdef GF_ENC_NULLS_RETRY
-        // (only this experiment build's fast kernel leaves tiles behind: the shipping one takes every tile of up to 2^23 / 6 cells, and
-        // the general kernel's launch -- 4-5 us to find nothing to do -- went in round 4)
-        hipLaunchKernelGGL(k_huffman_encode<false>, dim3(grid < 2048 ? grid : 2048), dim3(ENC_THREADS), 0, stream, a);
-        ran |= GF_RT_ENC_GENERAL;
-#endif
     } else {
         GfEncodeArgs g = a;
         g.retryFlag = nullptr;

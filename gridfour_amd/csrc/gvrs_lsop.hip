@@ -2169,12 +2169,8 @@ __global__ __launch_bounds__(64, RECON_PLANE_WAVES) void k_lsop_reconstruct_plan
                     const int32_t cq = (int32_t)d.x + 4 * (int32_t)q;
                     const bool vCurQ = (d.y >> 30) & 1u, vNextQ = (d.y >> 31) != 0u;
                     int32_t *const vrowQ = vPair + (d.y & 0x3fffffffu);
-#ifdef GF_RP_NO_STORES                                      // (experiment builds: what the kernel costs without its stores)
-                    const bool full = false, part = false;
-#else
                     const bool full = vCurQ && cq >= 0 && cq + 3 < (int32_t)nC;
                     const bool part = !full && ((vCurQ && cq + 3 >= 0 && cq < (int32_t)nC) || (vNextQ && cq + 3 >= P));
-#endif
                     if (full || part) {
                         const lsop_lds_u32 *src = stageAll + rho * RP_STAGE_STRIDE + 4u * q;
                         GfU4 x;
@@ -2308,9 +2304,6 @@ hipError_t gf_launch_lsop_reconstruct(const int32_t *residuals, size_t resStride
 {
     if (nTiles == 0) return hipSuccess;
     const GfLsopPlaneGeom g = gf_lsop_plane_geom((uint32_t)nRows, (uint32_t)nCols);
-#ifndef GF_RP_LDS_PAD
-#define GF_RP_LDS_PAD 0
-#endif
     planes = planes && g.ok;
     GfLsopReconArgs a{residuals, resStride, coefs, inStatus, values, status, nTiles, nRows, nCols, planes};
     const size_t dyn = (64 * (2 * RECON_ROUND + 1) + 2 * (size_t)nCols) * 4;      // 64 staging rings + 2 row buffers
@@ -2319,7 +2312,7 @@ hipError_t gf_launch_lsop_reconstruct(const int32_t *residuals, size_t resStride
         // the tiles whose interior residuals lie as byte planes (k_lsop_unpack2 says which: terrain, nearly all of them), two to a
         // wave; the others through the old pipeline by the launch's first workgroups where the shape is that kernel's, else by the
         // kernels below
-        const size_t dynP = std::max<size_t>(g.ldsBytes + GF_RP_LDS_PAD, pipe ? dyn : 0);      // (GF_RP_LDS_PAD: experiment builds, fewer waves per CU)
+        const size_t dynP = std::max<size_t>(g.ldsBytes, pipe ? dyn : 0);
         static GfDynLdsOptIn optPlane;
         const hipError_t e = gf_opt_in_dyn_lds(k_lsop_reconstruct_plane, dynP, optPlane);
         if (e != hipSuccess) return e;

@@ -399,10 +399,7 @@ __global__ __launch_bounds__(DEC_THREADS, GF_LSOP_UNPACK_WAVES) void k_lsop_unpa
                     wide = wide || x + 128u > 255u;
                     if (i == (uint32_t)tid) specMine = x;
                 }
-#ifndef GF_LSOP_WINDOW_DIV
-#define GF_LSOP_WINDOW_DIV 1                                   // (experiment builds: several windows where one would do)
-#endif
-                if (!__syncthreads_or(wide ? 1 : 0)) window = min(nInt, stageCap / GF_LSOP_WINDOW_DIV / wI * wI);
+                if (!__syncthreads_or(wide ? 1 : 0)) window = min(nInt, stageCap / wI * wI);
             }
             CdCellSink sink1{reinterpret_cast<uint32_t *>(res + nInit), GfCellMap::make(4, 1u, 2u), nInt, true,
                              reinterpret_cast<uint8_t *>(S.qs), reinterpret_cast<uint8_t *>(cdLdsText + usedWords),

@@ -1,8 +1,10 @@
 #!/bin/bash
 # A/B on ONE box with per-kernel times: rocprofv3 kernel statistics of tools/shape_time.py for the shipping library and experiment builds.
 # usage: tools/ab_kernels.sh "<variant> ..." <outdir> [nRows nCols nTiles [codec]]     ("" = the shipping library only)
+set -eu
 V=$1; O=$2; shift; shift
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)                # the repository: this script lives in its tools/
+cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 mkdir -p $O
 for v in "" $V; do
   n=${v:-shipping}
