@@ -151,3 +151,54 @@ def roomy_tiles(r, c, n, seed, p):
         if p.fastM32 < n_m32 <= p.ldsM32Roomy - 4096:
             return tiles
     raise AssertionError("no spike density puts a %dx%d tile between the fast and the roomy budget" % (r, c))
+
+
+DEM_SEED = 0x5EED_0F_2047                  # the synthetic terrain of device_roundtrip(style=...)
+
+
+def sampled(n, k=23):
+    """about k tile indices spread over n"""
+    return range(0, n, max(1, n // k))
+
+
+def _oracle_encode(kind, r, c, tile, predictor_mask=0xF):
+    import oracle
+    f = oracle.codec_canon_encode if kind == KIND_CANON else oracle.codec_huffman_encode
+    return f(0, r, c, tile, predictor_mask=predictor_mask)
+
+
+def device_roundtrip(ctx, kind, r, c, tiles=None, style=None, n_tiles=None, sample=None, check_decode=True, slot_stride=None,
+                    seed=DEM_SEED, predictor_mask=0xF):
+    """values -> encode -> decode on one DeviceTileBatch (one encodeBatchDev and one decodeBatchDev call), against the oracle;
+    returns (batch, report after encode, report after decode, plan of the decode)"""
+    import gridfour_amd
+    import numpy as np
+    nt = len(tiles) if tiles is not None else n_tiles
+    b = gridfour_amd.DeviceTileBatch(ctx, r, c, nt, slot_stride=slot_stride, codec="canon" if kind == KIND_CANON else "huffman")
+    if tiles is not None:
+        b.values.upload(np.ascontiguousarray(np.stack(tiles), dtype=np.int32))
+    else:
+        b.synth_dem(seed, 144, style=style)
+    b.encode(codec_index=0, predictor_mask=predictor_mask)
+    ctx.synchronize()
+    enc = report(ctx)
+    vals = b.get_values()
+    assert (b.get_enc_status() == 0).all()
+    lengths, preds = b.get_lengths(), b.get_predictors()
+    for t in (range(nt) if sample is None else sampled(nt, sample)):
+        ref, used = _oracle_encode(kind, r, c, vals[t], predictor_mask)
+        assert preds[t] == used and b.get_packing(t, int(lengths[t])) == ref, ("packing", r, c, t)
+    seen = enc.roomySeen                             # the hint the decode's plan reads
+    b.decoded.fill(0)
+    b.decode()
+    ctx.synchronize()
+    dec = report(ctx)
+    p = plan(kind, r, c, nt, 0, 0, seen)
+    if check_decode:
+        assert (b.get_dec_status() == 0).all()
+        assert np.array_equal(b.get_decoded(), vals), ("decoded", r, c)
+    assert enc.encKind == kind and dec.decKind == kind
+    assert enc.encBits == p.encBits, (hex(enc.encBits), hex(p.encBits))
+    assert dec.decBits == p.decBits, (hex(dec.decBits), hex(p.decBits))
+    assert dec.roomyForm == p.roomyForm and dec.prepass == p.prepass
+    return b, enc, dec, p

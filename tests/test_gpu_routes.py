@@ -15,7 +15,6 @@ from route_plan import KIND_CANON, KIND_HUFFMAN, KIND_RAW_M32
 from tilegen import NULL, make_tile
 
 pytestmark = pytest.mark.gpu
-SEED = 0x5EED_0F_2047
 DOMAINS = rp.domains()
 
 
@@ -46,48 +45,7 @@ def _n_tiles(shape, want=6):
     return max(1, min(want, (1 << 19) // (shape[0] * shape[1])))
 
 
-def _sample(n, k=23):
-    return range(0, n, max(1, n // k))
-
-
-def _oracle_encode(kind, r, c, tile):
-    f = oracle.codec_canon_encode if kind == KIND_CANON else oracle.codec_huffman_encode
-    return f(0, r, c, tile)
-
-
-def _device_roundtrip(ctx, kind, r, c, tiles=None, style=None, n_tiles=None, sample=None, check_decode=True, slot_stride=None):
-    """values -> encode -> decode on one DeviceTileBatch (one encodeBatchDev and one decodeBatchDev call), against the oracle;
-    returns (batch, report after encode, report after decode, plan of the decode)"""
-    import gridfour_amd
-    nt = len(tiles) if tiles is not None else n_tiles
-    b = gridfour_amd.DeviceTileBatch(ctx, r, c, nt, slot_stride=slot_stride, codec="canon" if kind == KIND_CANON else "huffman")
-    if tiles is not None:
-        b.values.upload(np.ascontiguousarray(np.stack(tiles), dtype=np.int32))
-    else:
-        b.synth_dem(SEED, 144, style=style)
-    b.encode(codec_index=0)
-    ctx.synchronize()
-    enc = rp.report(ctx)
-    vals = b.get_values()
-    assert (b.get_enc_status() == 0).all()
-    lengths, preds = b.get_lengths(), b.get_predictors()
-    for t in (range(nt) if sample is None else _sample(nt, sample)):
-        ref, used = _oracle_encode(kind, r, c, vals[t])
-        assert preds[t] == used and b.get_packing(t, int(lengths[t])) == ref, ("packing", r, c, t)
-    seen = enc.roomySeen                             # the hint the decode's plan reads
-    b.decoded.fill(0)
-    b.decode()
-    ctx.synchronize()
-    dec = rp.report(ctx)
-    p = rp.plan(kind, r, c, nt, 0, 0, seen)
-    if check_decode:
-        assert (b.get_dec_status() == 0).all()
-        assert np.array_equal(b.get_decoded(), vals), ("decoded", r, c)
-    assert enc.encKind == kind and dec.decKind == kind
-    assert enc.encBits == p.encBits, (hex(enc.encBits), hex(p.encBits))
-    assert dec.decBits == p.decBits, (hex(dec.decBits), hex(p.decBits))
-    assert dec.roomyForm == p.roomyForm and dec.prepass == p.prepass
-    return b, enc, dec, p
+_device_roundtrip = rp.device_roundtrip
 
 
 def _retry_word(p):
