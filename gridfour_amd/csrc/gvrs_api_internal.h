@@ -1,0 +1,249 @@
+// gvrs_api_internal.h -- what the translation units of the C ABI (gvrs_api*.hip) share: the context, its buffers and lock, the
+// error helpers and the functions that cross files.  Host code only: no kernel source includes it.  Nothing declared here is an
+// export of the library (hidden visibility); what a file keeps to itself stays static there.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <atomic>
+#include <memory>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include <sched.h>
+#include <zlib.h>
+
+#include "../../include/gvrs_hip_codec.h"
+#include "gvrs_kernels.h"
+#include "gvrs_encode_layout.h"
+
+#pragma GCC visibility push(hidden)
+
+extern thread_local std::string g_lastError;   // (gvrs_api.hip: gf_last_error)
+#ifdef GF_DIAG
+// the diagnostic flavour of the library only (libgvrs_hip_diag.so, tools/): process-wide hooks for phase ablation and
+// the kernels' cycle stamps.  The shipping library has no mutable global state.
+extern int g_encPhaseLimit, g_decPhaseLimit;
+extern uint32_t *g_decodeDebug;   // 16 cycle stamps per tile
+extern uint32_t *g_encodeDebug;   // dump target of the next encode launches
+#else
+constexpr int g_encPhaseLimit = 0, g_decPhaseLimit = 0;
+constexpr uint32_t *g_decodeDebug = nullptr, *g_encodeDebug = nullptr;
+#endif
+
+inline gf_status hipFail(hipError_t e, const char *what)
+{
+    char buf[256];
+    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
+    g_lastError = buf;
+    return GF_ERR_HIP;
+}
+
+#define GF_HIP(call)                                   \
+    do {                                               \
+        hipError_t e_ = (call);                        \
+        if (e_ != hipSuccess) return hipFail(e_, #call); \
+    } while (0)
+
+inline size_t roundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// offsets[nTiles + 1] of a caller's blob: non-decreasing, every packing shorter than 4 GiB (lengths travel as uint32)
+inline bool offsetsValid(const uint64_t *offsets, size_t nTiles)
+{
+    for (size_t t = 0; t < nTiles; t++)
+        if (offsets[t + 1] < offsets[t] || offsets[t + 1] - offsets[t] > 0xFFFFFFFFull) return false;
+    return true;
+}
+
+// Counts the device buffers that moved (a move is rare: buffers only grow).  A recorded hipGraph holds the addresses it was
+// captured with: the one-tile graphs (gf_single) remember the count they were recorded at and are dropped when it has changed --
+// a batch that grew the context's tree / selection records between two replays used to leave them pointing at freed memory.
+// Round 6 (advice): a context's buffers count on the CONTEXT's counter (gf_context::bufMoves) -- with one counter for the process
+// another GPU's shard or another thread's batch made every context drop and re-record its graphs; this one is what is left for
+// buffers that belong to no context.
+inline std::atomic<uint64_t> g_devBufMoves{0};
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    std::atomic<uint64_t> *moves = &g_devBufMoves;
+    gf_status ensure(size_t need)
+    {
+        if (need <= bytes) return GF_OK;
+        moves->fetch_add(1, std::memory_order_relaxed);
+        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        need = roundUp(need + need / 8, 1 << 20);
+        GF_HIP(hipMalloc(&p, need));
+        bytes = need;
+        return GF_OK;
+    }
+    void release()
+    {
+        if (p) {
+            moves->fetch_add(1, std::memory_order_relaxed);
+            (void)hipFree(p);
+        }
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+struct gf_context {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    DevBuf workspace;      // decode spill: grid * 6*cells
+    DevBuf trees;          // leaf records of the tree pre-pass: GF_TREE_REC_WORDS per tile
+    DevBuf flags;          // one word: tiles the fast decode kernel left to the general one (GfDecodeArgs::retryFlag)
+    DevBuf packRecs;       // encoder: selection records between k_huffman_encode and k_huffman_pack
+    // staging for the host-memory entry points
+    DevBuf dValues, dSlots, dBlob, dLengths, dPred, dStatus, dOffsets;
+    DevBuf dPlanes;        // CodecFloat plane staging
+    DevBuf dResiduals, dCoefs, dStatus2;   // LSOP staging
+    DevBuf dM32, dM32Len, dM32Models, dSeeds;   // CodecDeflate staging
+    DevBuf dInflate, dInflOut, dInflMeta;       // GPU inflate: stream descriptors, inflated bytes, produced / status
+    std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
+    std::array<DevBuf *, 22> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
+    {
+        return {&workspace, &trees, &flags, &packRecs, &dValues, &dSlots, &dBlob, &dLengths, &dPred, &dStatus, &dOffsets, &dPlanes,
+                &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta};
+    }
+    gf_context()
+    {
+        for (DevBuf *b : buffers()) b->moves = &bufMoves;
+    }
+    // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
+    // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
+    // scratch buffers, staging slots and recorded graphs are one set.  Recursive: entry points call each other.
+    std::recursive_mutex mu;
+    GfSideStream side{nullptr, nullptr, nullptr};   // second stream + fork / join events: the fast decode kernel's roomy run (gvrs_kernels.h)
+    uint32_t *hRoomySeen = nullptr;                 // page-locked word: GfDecodeArgs::roomySeenHost
+    // what the last encode and the last decode batch launched (host side only: gf_internal_route_report)
+    uint32_t routeEnc = 0, routeDec = 0;            // GF_RT_* bits
+    int routeEncKind = -1, routeDecKind = -1, routeRoomy = GF_ROOMY_NONE, routePrepass = 0;
+    struct gf_host_pipe *pipe = nullptr;        // pipelined staging of the host-memory batch entry points (created on first use)
+    struct gf_single *single = nullptr;         // one tile per call: page-locked buffers and replayed graphs (created on first use)
+};
+void gf_host_pipe_destroy(struct gf_host_pipe *p);   // (gvrs_api_host.hip, as the next)
+void gf_single_destroy(struct gf_single *s);
+#define GF_CTX_LOCK(c)                                       \
+    std::unique_lock<std::recursive_mutex> gfCtxLock_;       \
+    if (c) gfCtxLock_ = std::unique_lock<std::recursive_mutex>((c)->mu)
+
+// the caller's stream, or the context's own
+inline hipStream_t streamOf(const gf_context *c, void *stream) { return stream ? (hipStream_t)stream : c->stream; }
+
+// page-locked host memory that grows on demand (the staging slots of gvrs_api_host.hip)
+struct PinBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    gf_status ensure(size_t need)
+    {
+        if (need <= bytes) return GF_OK;
+        if (p) { (void)hipHostFree(p); p = nullptr; bytes = 0; }
+        need = roundUp(need + need / 8, 1 << 20);
+        GF_HIP(hipHostMalloc(&p, need, hipHostMallocDefault));
+        bytes = need;
+        return GF_OK;
+    }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+// codec kinds behind the shared batch plumbing
+enum { KIND_HUFFMAN = 0, KIND_CANON = 1, KIND_RAW_M32 = 2, KIND_DEFLATE = 3, KIND_FLOAT = 4 };
+
+inline size_t decodeWorkspaceStride(int nRows, int nCols)
+{
+    // spill layout of the decode kernel: M32 bytes (6 per cell, rounded to 32), start bitmap, rank bases
+    const size_t cap = roundUp((size_t)6 * (size_t)nRows * (size_t)nCols, 32);
+    return roundUp(cap + 2 * ((cap >> 5) + 2) * 4 + 64, 16);
+}
+
+// the encoders' per-tile records between their kernels (selection records, statistics) and, behind them, the legacy encoder's byte
+// plane of raw row differences (GfEncodeArgs::plane): one allocation of the context
+inline size_t encPlaneStride(int nRows, int nCols) { return roundUp((size_t)nRows * (size_t)nCols, 16); }
+inline size_t encRecordBytes(int nRows, int nCols, size_t nTiles)
+{
+    const size_t recs = nTiles * std::max((size_t)GF_PACK_REC_WORDS + GF_ENC_STAT_WORDS, gf_canon_pack_rec_words() + gf_canon_stat_words()) * 4 + 16;
+    return roundUp(recs, 256) + nTiles * encPlaneStride(nRows, nCols) + 256;
+}
+
+constexpr size_t INFLATE_SCRATCH_BYTES = (size_t)1 << 30;     // thousands of streams per launch: a stream is one serial chain
+
+unsigned hostCores();   // (gvrs_api.hip)
+
+// tiles are independent: the host-side zlib stages run on every core the process may use
+template <class F>
+static void parallelFor(size_t n, F f)
+{
+    unsigned nt = hostCores();
+    if (nt > n) nt = (unsigned)n;
+    if (nt == 1) { for (size_t i = 0; i < n; i++) f(i); return; }
+    std::vector<std::thread> th;
+    for (unsigned w = 0; w < nt; w++)
+        th.emplace_back([=]() { for (size_t i = w; i < n; i += nt) f(i); });
+    for (auto &x : th) x.join();
+}
+
+inline void putLE32(uint8_t *p, uint32_t x) { p[0] = (uint8_t)x; p[1] = (uint8_t)(x >> 8); p[2] = (uint8_t)(x >> 16); p[3] = (uint8_t)(x >> 24); }
+inline uint32_t getLE32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+// One tile through a codec's batch entry point (the ICompressionEncoder / ICompressionDecoder form): batch(offsets, &tileStatus) is
+// that call for one tile.  *outLen is written even when it fails; the tile's status replaces GF_OK only.
+template <class Batch>
+static gf_status oneTileEncode(size_t *outLen, Batch batch)
+{
+    if (!outLen) return GF_ERR_ARG;
+    uint64_t offsets[2] = {0, 0};
+    int32_t st = 0;
+    const gf_status s = batch(offsets, &st);
+    *outLen = (size_t)offsets[1];
+    return s != GF_OK ? s : (gf_status)st;
+}
+template <class Batch>
+static gf_status oneTileDecode(size_t len, Batch batch)
+{
+    uint64_t offsets[2] = {0, (uint64_t)len};
+    int32_t st = 0;
+    const gf_status s = batch(offsets, &st);
+    return s != GF_OK ? s : (gf_status)st;
+}
+
+// ---- the functions that cross files.  lean: 1 from the one-tile-per-call path alone (GfEncodeArgs::lean, GfDecodeArgs::lean)
+// gvrs_api_route.hip
+gf_status encodeBatchDev(int kind, gf_context *c, void *stream, int codecIndex, int nRows, int nCols, size_t nTiles,
+                         const int32_t *dValues, uint8_t *dOut, size_t slotStride, uint32_t *dLengths, uint8_t *dPredictors,
+                         int32_t *dStatus, int predictorMask, int lean);
+gf_status decodeBatchDev(int kind, gf_context *c, void *stream, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob,
+                         size_t blobBytes, const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues,
+                         int32_t *dStatus, int lean, uint32_t *analysis = nullptr, uint32_t *pairCounts = nullptr);
+// gvrs_api_host.hip
+gf_status decodeBatchHostG(int kind, gf_context *c, int nRows, int nCols, size_t nTiles, const uint8_t *blob, const uint64_t *offsets,
+                           const uint64_t *starts, const uint32_t *lens, const uint32_t *dstTile, int32_t *values, int32_t *status);
+gf_status decodeBatchHost(int kind, gf_context *c, int nRows, int nCols, size_t nTiles, const uint8_t *blob, const uint64_t *offsets,
+                          int32_t *values, int32_t *status);
+// gvrs_api_float.hip
+gf_status floatDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
+                         const uint64_t *dOffsets, const uint32_t *dLengths, float *dValues, int32_t *dStatus);
+bool zDeflate(const uint8_t *in, size_t n, int level, std::vector<uint8_t> &out);
+bool zDeflateUpTo(const uint8_t *in, size_t n, int level, size_t limit, std::vector<uint8_t> &out);
+// gvrs_api_deflate.hip
+gf_status deflateDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
+                           const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues, int32_t *dStatus);
+gf_status codecMasterDecodeScattered(gf_context *c, const int *codecs, int nCodecs, int nRows, int nCols, size_t nTiles,
+                                     const uint8_t *blob, const uint64_t *starts, const uint32_t *lens, const uint8_t *skip,
+                                     int32_t *values, int32_t *st);
+
+#pragma GCC visibility pop

@@ -7,7 +7,7 @@
 //                           first cell of the previous row, row 0 to 0)
 //   decodeFloats :395-458   the inverse (decodeDeltas :315-325 = byte-wise running sums)
 // The Deflate stage of the five planes (doDeflate :268-283) stays on the host (libz) because its
-// bytes are only defined by zlib itself; see gvrs_api.hip gf_float_*.
+// bytes are only defined by zlib itself; see gvrs_api_float.hip gf_float_*.
 //
 // Plane buffer of a tile (same layout as the oracle): [sign: ceil(n/8)] [exponent: n] [m1: n]
 // [m2: n] [m3: n], tiles at a fixed stride.  Pure streaming: 4 B/cell in, 4.125 B/cell out.

@@ -4,7 +4,7 @@
 // with no exchange between devices and no collective: what one JVM's CodecMaster (gvrs/CodecMaster.java:142-203) or
 // RecordManager.writeTile (gvrs/RecordManager.java:386-490) would call to use the whole node.  A gf_multi owns one
 // gf_context per listed device (a device may be listed more than once: several contexts then share it).
-//   host memory    one host thread per context runs the pipelined staging of gvrs_api.hip on its tile range; the packings
+//   host memory    one host thread per context runs the pipelined staging of gvrs_api_host.hip on its tile range; the packings
 //                  of the ranges are concatenated by an exclusive scan of the range totals
 //   device memory  launches are asynchronous, so the calling thread enqueues every device's work on that device's stream
 //                  and returns; gf_multi_synchronize waits for all of them

@@ -1,4 +1,4 @@
-"""The library's route plan (gf_internal_route_plan, gvrs_api.hip) and route report (gf_internal_route_report) through ctypes,
+"""The library's route plan (gf_internal_route_plan, gvrs_api_route.hip) and route report (gf_internal_route_report) through ctypes,
 and the tile-shape sweep the route tests share.  The plan is a pure host function: it needs the library, not a device."""
 import ctypes as C
 

@@ -24,7 +24,7 @@ SWITCHES = {
     # layout / host
     "GF_ENC_HIST_SEPARATE": "the reduced histograms as an array of their own: the diagnostic dump's layout",
     "GF_ENC_LAYOUT_FULL": "that layout outside the diagnostic build: tests/csrc/host_harness.cpp",
-    "GF_HOST_HAS_CRC32_INSN": "defined by gvrs_api.hip on x86-64 hosts: CRC-32C by the SSE4.2 instruction",
+    "GF_HOST_HAS_CRC32_INSN": "defined by gvrs_api_records.hip on x86-64 hosts: CRC-32C by the SSE4.2 instruction",
     # numeric tunables: #ifndef X / #define X value, the sweep in the comment beside it
     "GF_ENC_PACK_WGS": "workgroups per CU of the Huffman packer",
     "GF_ENC_HIST_R_A": "histogram replicas of the encoder's phase-A kernel",

@@ -1,4 +1,4 @@
-"""The route plan of the Huffman and canonical paths (gf_internal_route_plan, gvrs_api.hip), on the CPU: which k_huffman_decode
+"""The route plan of the Huffman and canonical paths (gf_internal_route_plan, gvrs_api_route.hip), on the CPU: which k_huffman_decode
 build, fast-run form, k_canon_decode build, pre-pass form, roomy-run form and encoder form every tile shape of the sweep selects.
 The plan is what encodeBatchDev and decodeBatchDev launch (they check their launchers' report against it), so this pins the
 dispatch: the inline decisions it replaced, restated below, must agree with it on the whole sweep; the anchors the code
