@@ -10,8 +10,18 @@
 namespace {
 
 // ---- compaction: exclusive scan of the lengths (one workgroup), then one workgroup per tile copies ----
-// status (optional): a tile whose status is not GF_K_OK contributes no bytes
-__global__ __launch_bounds__(1024) void k_scan_lengths(size_t nTiles, const uint32_t *__restrict__ lengths,
+// status (optional): a tile whose status is not GF_K_OK contributes no bytes; nor does a tile whose length is greater than the
+// slot stride (an encoder reported GF_OVERFLOW, "length is still reported", and left the slot untouched: there is nothing to copy,
+// and len bytes from the slot's start would run through the following slots and past the end of the slot array)
+__device__ __forceinline__ uint32_t compact_len(const uint32_t *__restrict__ lengths, const int32_t *__restrict__ status, size_t t,
+                                                size_t slotStride)
+{
+    if (status && status[t] != GF_K_OK) return 0u;
+    const uint32_t len = lengths[t];
+    return len > slotStride ? 0u : len;
+}
+
+__global__ __launch_bounds__(1024) void k_scan_lengths(size_t nTiles, size_t slotStride, const uint32_t *__restrict__ lengths,
                                                        const int32_t *__restrict__ status, uint64_t *__restrict__ offsets)
 {
     __shared__ unsigned long long waveSum[16];
@@ -21,7 +31,7 @@ __global__ __launch_bounds__(1024) void k_scan_lengths(size_t nTiles, const uint
     __syncthreads();
     for (size_t base = 0; base < nTiles; base += 1024) {
         const size_t i = base + tid;
-        const unsigned long long v = (i < nTiles && !(status && status[i] != GF_K_OK)) ? lengths[i] : 0ull;
+        const unsigned long long v = i < nTiles ? compact_len(lengths, status, i, slotStride) : 0ull;
         unsigned long long incl = v;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -51,7 +61,7 @@ __global__ __launch_bounds__(256) void k_gather(size_t nTiles, const uint8_t *__
     for (size_t t = blockIdx.x; t < nTiles; t += gridDim.x) {
         const uint8_t *src = slots + t * slotStride;
         const uint64_t off = offsets[t];
-        const uint32_t len = (status && status[t] != GF_K_OK) ? 0u : lengths[t];
+        const uint32_t len = compact_len(lengths, status, t, slotStride);
         if (off + len > blobCap) continue;
         uint8_t *dst = blob + off;
         // head bytes up to 4-byte alignment of dst, then dwords assembled from the (aligned) slot
@@ -209,7 +219,7 @@ __global__ __launch_bounds__(256) void k_synth_dem(uint64_t seed, int nRows, int
 hipError_t gf_launch_compact(size_t nTiles, const uint8_t *slots, size_t slotStride, const uint32_t *lengths,
                              uint64_t *offsets, uint8_t *blob, size_t blobCap, hipStream_t stream, const int32_t *status)
 {
-    hipLaunchKernelGGL(k_scan_lengths, dim3(1), dim3(1024), 0, stream, nTiles, lengths, status, offsets);
+    hipLaunchKernelGGL(k_scan_lengths, dim3(1), dim3(1024), 0, stream, nTiles, slotStride, lengths, status, offsets);
     if (nTiles) {
         const unsigned grid = (unsigned)(nTiles < 8192 ? nTiles : 8192);
         hipLaunchKernelGGL(k_gather, dim3(grid), dim3(256), 0, stream, nTiles, slots, slotStride, lengths, status, offsets,

@@ -128,7 +128,12 @@ gf_status gf_huffman_decode_batch_i32(gf_context *ctx, int n_rows, int n_cols, s
  * d_lengths : packing length per tile (bytes; 0 = declined)
  * d_predictors (optional, may be NULL), d_status: per tile
  * predictor_mask: GF_PM_ALL for reference behaviour; a subset restricts the
- *             models tried (test hook, mirrors the oracle)                   */
+ *             models tried (test hook, mirrors the oracle)
+ * A tile reported GF_OVERFLOW or GF_DECLINED leaves its slot untouched: no byte
+ * of the slot is written (d_lengths[t] is the full length for GF_OVERFLOW, 0 for
+ * GF_DECLINED).  A tile reported GF_OK writes inside its own slot only.  This
+ * holds for every _dev encoder that writes into slots (gf_huffman_*, gf_canon_*,
+ * gf_lsop12_*; gf_m32_* per sub-slot, see there).                             */
 gf_status gf_huffman_encode_batch_i32_dev(gf_context *ctx, void *stream, int codec_index,
                                           int n_rows, int n_cols, size_t n_tiles,
                                           const int32_t *d_values, uint8_t *d_out,
@@ -150,7 +155,10 @@ gf_status gf_compact_dev(gf_context *ctx, void *stream, size_t n_tiles, const ui
                          uint8_t *d_blob, size_t blob_cap);
 
 /* gf_compact_dev cannot report a blob that is too small without synchronising: a packing that would end behind blob_cap
- * is skipped; d_offsets[n_tiles] > blob_cap tells the caller (after its own synchronisation) that this happened.        */
+ * is skipped; d_offsets[n_tiles] > blob_cap tells the caller (after its own synchronisation) that this happened.
+ * A tile with d_lengths[t] > slot_stride -- what a _dev encoder leaves behind for a tile it reported GF_OVERFLOW, whose
+ * slot it did not write -- contributes no bytes: d_offsets[t+1] == d_offsets[t], as for a declined tile (length 0).
+ * The caller tells the two apart by d_lengths[t] or the encoder's status array.                                          */
 
 /* ---- page-locked host memory ---------------------------------------------------------------------------------------
  * The host-memory batch entry points cut a batch into chunks of about 64 MB of cells and pipeline them through three
@@ -284,8 +292,11 @@ gf_status gf_canon_decode_batch_i32_dev(gf_context *ctx, void *stream, int n_row
  * predictor and keeps the strictly shortest packing (:176-199).  The predictor + M32 stage is available on its own:
  *   gf_m32_encode_batch_i32_dev: per tile three candidate streams (sub-slots of sub_stride bytes, order Differencing, Linear,
  *     Triangle; a tile with nulls has the DifferencingWithNulls stream in sub-slot 0), d_lengths[3 n], d_models[3 n]
- *     (predictor code, 0 = no candidate), d_seeds[n]; per-tile status GF_OVERFLOW when a stream is longer than sub_stride
- *     (its length is still exact).
+ *     (predictor code, 0 = no candidate), d_seeds[n].  A candidate stream is written only when length + 8 <= sub_stride:
+ *     the packer stores whole 32-bit words, up to 8 bytes behind the stream's last byte.  gf_m32_default_stride and
+ *     gf_m32_max_stream include that margin.  A candidate with length + 8 > sub_stride leaves its sub-slot untouched
+ *     and makes the tile's status GF_OVERFLOW (every length is still exact; the tile's other candidates, where they
+ *     fit, are written).
  *   gf_m32_decode_batch_i32_dev: "raw" containers = 10-byte CodecDeflate/CodecHuffman header followed by the M32 bytes
  *     themselves -> tiles (the stage after Inflater.inflate, CodecDeflate.java:141-147); layout as gf_huffman_decode_batch_i32_dev. */
 size_t gf_m32_default_stride(int n_rows, int n_cols);
