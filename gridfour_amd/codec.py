@@ -755,6 +755,81 @@ class CodecMasterHip:
                                                 _ptr(status)), "gf_tile_record_decode_batch")
         return idx, out, status
 
+    # ---- the same two readers for bytes in device memory: one upload of the bytes, everything else on the GPU ----
+    def _codecs_arg(self):
+        return self.codecs if self.codecs.size else np.zeros(1, np.int32)
+
+    def record_blob_dev(self, nRows, nCols, blob, offsets, element="int", verify_checksums=True):
+        """gf_tile_record_decode_batch_dev on records as they lie in a byte array: record t = blob[offsets[t]:offsets[t+1]]
+        (any byte alignment, anything between and behind the records).  Uploads blob and offsets, downloads the results:
+        (tile indices, values [nt, cells] int32 / int16, status per record).  A caller whose bytes or consumer are on the
+        device calls the entry point itself, with DeviceBuffer pointers."""
+        short = element == "short"
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nt = offsets.size - 1
+        cells = nRows * nCols
+        item = 2 if short else 4
+        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
+        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
+        d_idx = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0xff)
+        d_val = DeviceBuffer(self.ctx, nt * cells * item + 16).fill(0)
+        d_st = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0)
+        try:
+            check(lib().gf_tile_record_decode_batch_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, int(short),
+                                                        nRows, nCols, nt, d_blob.ptr, blob.size, d_off.ptr,
+                                                        int(bool(verify_checksums)), d_idx.ptr, d_val.ptr, d_st.ptr),
+                  "gf_tile_record_decode_batch_dev")
+            self.ctx.synchronize()
+            idx = d_idx.download(np.int32, nt)
+            out = d_val.download(np.int16 if short else np.int32, nt * cells).reshape(nt, cells)
+            status = d_st.download(np.int32, nt)
+        finally:
+            for b in (d_blob, d_off, d_idx, d_val, d_st):
+                b.free()
+        return idx, out, status
+
+    def tiles_from_records_dev(self, nRows, nCols, records, element="int", verify_checksums=True):
+        """tiles_from_records with the records decoded where they lie in device memory (gf_tile_record_decode_batch_dev)."""
+        offsets = np.zeros(len(records) + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(p) for p in records])
+        blob = np.frombuffer(b"".join(records) + b"\0" * 16, dtype=np.uint8)[:int(offsets[-1])]
+        return self.record_blob_dev(nRows, nCols, blob, offsets, element=element, verify_checksums=verify_checksums)
+
+    def packing_blob_dev(self, nRows, nCols, blob, offsets, lengths):
+        """gf_codec_master_decode_batch_i32_dev: packing t = blob[offsets[t]:offsets[t]+lengths[t]].  Returns (values, status)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        nt = lengths.size
+        assert offsets.size == nt
+        cells = nRows * nCols
+        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
+        d_off = DeviceBuffer(self.ctx, offsets.nbytes + 16).upload(offsets)
+        d_len = DeviceBuffer(self.ctx, lengths.nbytes + 16).upload(lengths)
+        d_val = DeviceBuffer(self.ctx, nt * cells * 4 + 16).fill(0)
+        d_st = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0)
+        try:
+            check(lib().gf_codec_master_decode_batch_i32_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, nRows,
+                                                             nCols, nt, d_blob.ptr, blob.size, d_off.ptr, d_len.ptr, d_val.ptr,
+                                                             d_st.ptr), "gf_codec_master_decode_batch_i32_dev")
+            self.ctx.synchronize()
+            out = d_val.download(np.int32, nt * cells).reshape(nt, cells)
+            status = d_st.download(np.int32, nt)
+        finally:
+            for b in (d_blob, d_off, d_len, d_val, d_st):
+                b.free()
+        return out, status
+
+    def decode_batch_dev(self, nRows, nCols, packings):
+        """decode_batch with the packings decoded where they lie in device memory (gf_codec_master_decode_batch_i32_dev)."""
+        lengths = np.array([len(p) for p in packings], np.uint32)
+        offsets = np.zeros(len(packings), np.uint64)
+        if len(packings):
+            offsets[1:] = np.cumsum(lengths[:-1], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)[:int(lengths.sum())]
+        return self.packing_blob_dev(nRows, nCols, blob, offsets, lengths)
+
     def tiles_from_payloads(self, nRows, nCols, payloads):
         nt = len(payloads)
         offsets = np.zeros(nt + 1, np.uint64)

@@ -146,6 +146,7 @@ void gf_context_destroy(gf_context *c)
     c->single = nullptr;
     for (DevBuf *b : c->buffers()) b->release();
     gf_host_pipe_destroy(c->pipe);
+    gf_rec_counts_destroy(c->hRecCounts);
     if (c->hRoomySeen) (void)hipHostFree(c->hRoomySeen);
     if (c->side.stream) {
         (void)hipStreamSynchronize(c->side.stream);

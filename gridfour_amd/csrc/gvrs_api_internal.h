@@ -109,11 +109,13 @@ struct gf_context {
     DevBuf dResiduals, dCoefs, dStatus2;   // LSOP staging
     DevBuf dM32, dM32Len, dM32Models, dSeeds;   // CodecDeflate staging
     DevBuf dInflate, dInflOut, dInflMeta;       // GPU inflate: stream descriptors, inflated bytes, produced / status
+    DevBuf dRecMeta, dRecSub, dRecTmp;          // records / mixed packings in device memory (gvrs_api_records_dev.hip): per-record framing
+                                                // results, the partition by codec, decoded tiles on their way to their place
     std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
-    std::array<DevBuf *, 22> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
+    std::array<DevBuf *, 25> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
     {
         return {&workspace, &trees, &flags, &packRecs, &dValues, &dSlots, &dBlob, &dLengths, &dPred, &dStatus, &dOffsets, &dPlanes,
-                &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta};
+                &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta, &dRecMeta, &dRecSub, &dRecTmp};
     }
     gf_context()
     {
@@ -125,6 +127,7 @@ struct gf_context {
     std::recursive_mutex mu;
     GfSideStream side{nullptr, nullptr, nullptr};   // second stream + fork / join events: the fast decode kernel's roomy run (gvrs_kernels.h)
     uint32_t *hRoomySeen = nullptr;                 // page-locked word: GfDecodeArgs::roomySeenHost
+    struct PinBuf *hRecCounts = nullptr;            // page-locked: the partition's counts on their way to the host (created on first use)
     // what the last encode and the last decode batch launched (host side only: gf_internal_route_report)
     uint32_t routeEnc = 0, routeDec = 0;            // GF_RT_* bits
     int routeEncKind = -1, routeDecKind = -1, routeRoomy = GF_ROOMY_NONE, routePrepass = 0;
@@ -160,6 +163,8 @@ struct PinBuf {
         bytes = 0;
     }
 };
+
+void gf_rec_counts_destroy(PinBuf *p);             // (gvrs_api_records_dev.hip)
 
 // codec kinds behind the shared batch plumbing
 enum { KIND_HUFFMAN = 0, KIND_CANON = 1, KIND_RAW_M32 = 2, KIND_DEFLATE = 3, KIND_FLOAT = 4 };

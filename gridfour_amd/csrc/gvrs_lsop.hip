@@ -31,6 +31,7 @@ namespace {
 
 #include "gvrs_encode_common.h"
 #include "gvrs_canon_common.h"
+#include "gvrs_crc32c.h"
 
 // ------------------------------------------------------------------------------------------------
 // shared by predict and reconstruct
@@ -1111,29 +1112,9 @@ __device__ void p2_append_bits(const uint32_t *img, uint32_t nbits, uint32_t *wi
 // polynomial's table (in LDS, made by the workgroup), and the runs' checksums are joined by the CRC's linearity:
 //   crc(A || B) = crc(A) * x^(8 |B|)  xor  crc(B)    in GF(2)[x] modulo the (reflected) polynomial,
 // so the tile's checksum is the XOR over the lanes of crc(run) * x^(8 bytes behind the run).  The multiplications are 32 steps
-// of shift-and-conditional-xor each, the powers by square and multiply.  Word 13 of the tile's coefficient record receives it.
+// of shift-and-conditional-xor each, the powers by square and multiply (gvrs_crc32c.h, shared with the tile records' checksum).
+// Word 13 of the tile's coefficient record receives it.
 // ------------------------------------------------------------------------------------------------
-constexpr uint32_t CRC32C_POLY = 0x82F63B78u;
-__device__ __forceinline__ uint32_t crc_mulmod(uint32_t a, uint32_t b)        // a * b mod P, operands and result bit-reflected
-{
-    uint32_t p = 0;
-#pragma unroll 1
-    for (uint32_t m = 0x80000000u; m; m >>= 1) {
-        p ^= (a & m) ? b : 0u;
-        b = (b & 1u) ? (b >> 1) ^ CRC32C_POLY : b >> 1;
-    }
-    return p;
-}
-__device__ __forceinline__ uint32_t crc_xpow8n(uint32_t nBytes)               // x^(8 nBytes) mod P
-{
-    uint32_t p = 0x80000000u, sq = 0x00800000u;                               // x^0; x^8
-#pragma unroll 1
-    for (uint32_t n = nBytes; n; n >>= 1) {
-        if (n & 1u) p = crc_mulmod(sq, p);
-        sq = crc_mulmod(sq, sq);
-    }
-    return p;
-}
 __global__ __launch_bounds__(256) void k_lsop_value_crc(const int32_t *__restrict__ values, uint32_t nCells, size_t nTiles,
                                                         const int32_t *__restrict__ inStatus, uint32_t *__restrict__ coefs)
 {

@@ -1,0 +1,316 @@
+// gvrs_records.hip -- tile records and mixed-codec packings that already lie in device memory: the framing walk, the records'
+// CRC-32C, the partition of a batch by codec and the pass that moves decoded tiles to their place (gvrs_api_records_dev.hip
+// drives them; the codecs' own decode kernels run between k_codec_partition and k_tile_scatter, untouched).
+//
+// Reference paths are relative to core/src/main/java/org/gridfour/: gvrs/RecordManager.java:456-459, 472-520 (readTile),
+// gvrs/RasterTile.java:243-253, gvrs/CodecMaster.java:195-203, gvrs/TileElementShort.java:239-246, util/GridfourCRC32C.java.
+
+#include <hip/hip_runtime.h>
+
+#include "gvrs_kernels.h"
+#include "gvrs_common.h"
+#include "gvrs_crc32c.h"
+
+namespace {
+
+// little-endian int32 at any byte address
+__device__ __forceinline__ uint32_t rec_le32(const uint8_t *p)
+{
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_record_parse: a lane per record.  Record mode (a.lengths == nullptr): record t is blob[offsets[t] .. offsets[t + 1]); the
+// framing rules of gf_tile_record_decode_batch in its order.  A record's first 20 bytes (the 16-byte head and the first byte of
+// the element, which names the codec of a packing) are fetched in one go -- every record that reaches them spans 20 bytes --
+// so that the checks behind them wait for memory once.  Packing mode: packing t is lengths[t] bytes at offsets[t].
+// Per record: where its element bytes start, how many they are, the record's size (for k_record_crc32c) and its class -- failed,
+// the standard form, or the index of its codec -- and the status (GF_K_OK for a packing until its decoder has spoken).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_record_parse(const GfRecordParseArgs a)
+{
+    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= a.nTiles) return;
+    const uint8_t *__restrict__ blob = a.blob;
+    int32_t st = GF_K_OK, cls = GF_REC_FAILED;
+    uint64_t start = 0;
+    uint32_t n = 0, size = 0, first = 0;
+    bool element = false;                                  // the element bytes lie inside the blob: classify them
+    if (a.lengths) {
+        start = a.offsets[t];
+        n = a.lengths[t];
+        if (start > a.blobBytes || (uint64_t)n > a.blobBytes - start) st = GF_K_ERR_BOUNDS;
+        else {
+            element = true;
+            if (n) first = blob[start];
+        }
+    } else {
+        const uint64_t o0 = a.offsets[t], o1 = a.offsets[t + 1];
+        if (o0 > o1 || o1 > a.blobBytes || o1 - o0 < 20u) st = GF_K_ERR_BOUNDS;      // (nothing of such a record is read)
+        else {
+            const uint8_t *r = blob + o0;
+            uint32_t h0, h1, h2, h3, h4;
+            if ((o0 & 3u) == 0u) {
+                const GfU4 q = *reinterpret_cast<const GfU4 *>(r);
+                h4 = *reinterpret_cast<const uint32_t *>(r + 16);
+                h0 = q.x, h1 = q.y, h2 = q.z, h3 = q.w;
+            } else {
+                h0 = rec_le32(r), h1 = rec_le32(r + 4), h2 = rec_le32(r + 8), h3 = rec_le32(r + 12), h4 = r[16];
+            }
+            size = h0;
+            if ((uint64_t)size > o1 - o0 || size < 20u || (size & 7u)) st = GF_K_ERR_BOUNDS;
+            else if ((h1 & 0xffu) != 2u) st = GF_K_ERR_FORMAT;                        // not RecordType.Tile
+            else {
+                if (a.tileIndices) a.tileIndices[t] = (int32_t)h2;
+                n = h3;
+                if (16ull + n > size) st = GF_K_ERR_BOUNDS;
+                else {
+                    element = true;
+                    start = o0 + 16u;
+                    first = h4 & 0xffu;
+                }
+            }
+        }
+    }
+    if (element) {
+        if (a.stdSize && n == a.stdSize) cls = GF_REC_STANDARD;
+        else if (a.nCodecs < 1 || n == 0u || (int)first >= a.nCodecs) st = GF_K_ERR_FORMAT;
+        else {
+            // (the list's integer codecs as a bit set in four words: no indexed kernel argument)
+            const uint64_t w = first < 64u ? a.codecSet0 : first < 128u ? a.codecSet1 : first < 192u ? a.codecSet2 : a.codecSet3;
+            if ((w >> (first & 63u)) & 1ull) cls = (int32_t)first;
+            else st = GF_K_ERR_FORMAT;                                              // an entry without an integer decoder
+        }
+    }
+    a.starts[t] = start;
+    a.lens[t] = n;
+    a.sizes[t] = size;
+    a.cls[t] = cls;
+    a.status[t] = st;
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_record_crc32c: a wave per record that passed the framing (class not failed): the CRC-32C of its first size - 4 bytes against
+// the stored one in its last four.  Lane l takes the l-th of 64 runs (a multiple of 16 bytes each) through the byte table in
+// LDS; the runs are joined as gvrs_crc32c.h says.  A record that starts at a multiple of 4 (file records start at multiples of
+// 8) is read in 16-byte and 4-byte pieces, any other byte by byte.  Nothing outside [start - 16, start - 16 + size) is read.
+// A mismatch makes the record GF_K_ERR_FORMAT and takes it out of the partition.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t crc_word(const uint32_t *table, uint32_t crc, uint32_t w)
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        crc = table[(crc ^ w) & 0xffu] ^ (crc >> 8);
+        w >>= 8;
+    }
+    return crc;
+}
+
+__global__ __launch_bounds__(256) void k_record_crc32c(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ starts,
+                                                       const uint32_t *__restrict__ sizes, int32_t *__restrict__ cls,
+                                                       int32_t *__restrict__ status, size_t nTiles)
+{
+    __shared__ uint32_t table[256];
+    table[threadIdx.x] = crc_table_entry(threadIdx.x);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t t = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (t >= nTiles || cls[t] == GF_REC_FAILED) return;
+    const uint64_t o0 = starts[t] - 16u;
+    const uint32_t size = sizes[t], nBytes = size - 4u;
+    const uint8_t *__restrict__ r = blob + o0;
+    const uint32_t per = ((nBytes + 63u) / 64u + 15u) & ~15u, begin = min(nBytes, lane * per), end = min(nBytes, begin + per);
+    uint32_t crc = 0xffffffffu, i = begin;
+    if ((o0 & 3u) == 0u) {
+        for (; i + 16u <= end; i += 16u) {
+            const GfU4 q = *reinterpret_cast<const GfU4 *>(r + i);
+            crc = crc_word(table, crc, q.x);
+            crc = crc_word(table, crc, q.y);
+            crc = crc_word(table, crc, q.z);
+            crc = crc_word(table, crc, q.w);
+        }
+        for (; i + 4u <= end; i += 4u) crc = crc_word(table, crc, *reinterpret_cast<const uint32_t *>(r + i));
+    }
+    for (; i < end; i++) crc = table[(crc ^ r[i]) & 0xffu] ^ (crc >> 8);
+    crc ^= 0xffffffffu;                                                       // the run's own checksum (an empty run: 0)
+    uint32_t part = crc_mulmod(crc_xpow8n(nBytes - end), crc);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
+    if (lane == 0 && part != rec_le32(r + nBytes)) {
+        status[t] = GF_K_ERR_FORMAT;
+        cls[t] = GF_REC_FAILED;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_codec_partition: ONE workgroup sorts the batch's records by class, stably: segment s < nCodecs holds the packings of codec s in
+// record order, segment nCodecs the records in standard form; the segments follow one another in the three output arrays
+// (subOffsets: where the element bytes start in the blob, subLengths, subDst: the record's number) and counts[s] says how long each
+// is.  First the segment totals (LDS counters), then 1,024 records at a time: a wave finds each member's rank among its own lanes
+// with one ballot per segment present in the wave, the waves' counts meet in LDS, and a record's place is its segment's start + the
+// members before this round + those in earlier waves + its rank.  No global atomics; the order never depends on timing.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t PART_THREADS = 1024, PART_WAVES = PART_THREADS / 64, PART_SEGS = 256;
+
+__global__ __launch_bounds__(PART_THREADS) void k_codec_partition(const GfPartitionArgs a)
+{
+    __shared__ uint32_t waveCnt[PART_WAVES][PART_SEGS];
+    __shared__ uint32_t segBase[PART_SEGS], run[PART_SEGS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t nSeg = (uint32_t)a.nCodecs + 1u;
+    if (tid < PART_SEGS) run[tid] = 0u;
+    for (uint32_t i = tid; i < PART_WAVES * PART_SEGS; i += PART_THREADS) (&waveCnt[0][0])[i] = 0u;
+    __syncthreads();
+    for (size_t t = tid; t < a.nTiles; t += PART_THREADS) {
+        const int32_t c = a.cls[t];
+        if (c != GF_REC_FAILED) atomicAdd(&run[c == GF_REC_STANDARD ? nSeg - 1u : (uint32_t)c], 1u);     // (LDS)
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t base = 0;
+        for (uint32_t s = 0; s < nSeg; s++) {
+            segBase[s] = base;
+            base += run[s];
+        }
+    }
+    __syncthreads();
+    if (tid < nSeg) {
+        a.counts[tid] = run[tid];
+        run[tid] = 0u;
+    }
+    __syncthreads();
+    for (size_t t0 = 0; t0 < a.nTiles; t0 += PART_THREADS) {
+        const size_t t = t0 + tid;
+        int32_t seg = -1;
+        if (t < a.nTiles) {
+            const int32_t c = a.cls[t];
+            seg = c == GF_REC_FAILED ? -1 : c == GF_REC_STANDARD ? (int32_t)nSeg - 1 : c;
+        }
+        uint32_t rank = 0;
+        uint64_t todo = __ballot(seg >= 0);
+        while (todo) {                                                         // (wave-uniform)
+            const int leader = __ffsll((unsigned long long)todo) - 1;
+            const int32_t s = __shfl(seg, leader);
+            const uint64_t m = __ballot(seg == s);
+            if (seg == s) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if ((int)lane == leader) waveCnt[wave][s] = (uint32_t)__popcll(m);
+            todo &= ~m;
+        }
+        __syncthreads();
+        if (seg >= 0) {
+            uint32_t before = 0;
+            for (uint32_t w = 0; w < wave; w++) before += waveCnt[w][seg];
+            const uint32_t j = segBase[seg] + run[seg] + before + rank;
+            a.subOffsets[j] = a.starts[t];
+            a.subLengths[j] = a.lens[t];
+            a.subDst[j] = (uint32_t)t;
+        }
+        __syncthreads();
+        if (tid < nSeg) {
+            uint32_t sum = 0;
+            for (uint32_t w = 0; w < PART_WAVES; w++) {
+                sum += waveCnt[w][tid];
+                waveCnt[w][tid] = 0u;
+            }
+            run[tid] += sum;
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_tile_scatter: a workgroup per entry of the partition.  Entries below nPacked are decoded tiles: tile j of the temporary goes
+// to tile subDst[j] of the caller's array (int32 as it is; short elements narrowed, INT4_NULL_CODE -> -32768) when its decoder
+// said GF_K_OK, and the decoder's status to status[subDst[j]].  The entries behind them are records in standard form: their
+// element bytes are the cells (4 * cells bytes, or 2 * cells for shorts), copied from wherever they lie in the blob.  Pure
+// bandwidth: 16 bytes per lane and instruction wherever source, destination and length allow.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void rec_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, size_t nBytes)
+{
+    const uintptr_t both = (uintptr_t)dst | (uintptr_t)src | (uintptr_t)nBytes;
+    if ((both & 15u) == 0u) {
+        for (size_t i = (size_t)threadIdx.x * 16u; i < nBytes; i += (size_t)blockDim.x * 16u)
+            *reinterpret_cast<uint4 *>(dst + i) = *reinterpret_cast<const uint4 *>(src + i);
+    } else if ((both & 7u) == 0u) {
+        for (size_t i = (size_t)threadIdx.x * 8u; i < nBytes; i += (size_t)blockDim.x * 8u)
+            *reinterpret_cast<uint2 *>(dst + i) = *reinterpret_cast<const uint2 *>(src + i);
+    } else if ((both & 3u) == 0u) {
+        for (size_t i = (size_t)threadIdx.x * 4u; i < nBytes; i += (size_t)blockDim.x * 4u)
+            *reinterpret_cast<uint32_t *>(dst + i) = *reinterpret_cast<const uint32_t *>(src + i);
+    } else {
+        for (size_t i = threadIdx.x; i < nBytes; i += blockDim.x) dst[i] = src[i];
+    }
+}
+
+__device__ __forceinline__ uint32_t rec_narrow2(uint32_t lo, uint32_t hi)     // two cells -> two shorts in a word
+{
+    lo = lo == GF_NULL_CODE ? 0x8000u : (lo & 0xffffu);
+    hi = hi == GF_NULL_CODE ? 0x8000u : (hi & 0xffffu);
+    return lo | (hi << 16);
+}
+
+__global__ __launch_bounds__(256) void k_tile_scatter(const GfTileScatterArgs a)
+{
+    GF_FOR_WG_TILE(j, a.nTotal)
+    {
+        const size_t dst = a.subDst[j], cells = a.cells;
+        if (j >= a.nPacked) {
+            const size_t nBytes = cells * (a.elemShort ? 2u : 4u);
+            rec_copy(reinterpret_cast<uint8_t *>(a.values) + dst * nBytes, a.blob + a.subOffsets[j], nBytes);
+            continue;
+        }
+        const int32_t st = a.subStatus[j];
+        if (threadIdx.x == 0) a.status[dst] = st;
+        if (st != GF_K_OK) continue;
+        const int32_t *__restrict__ src = a.tmp + j * cells;
+        if (!a.elemShort) {
+            rec_copy(reinterpret_cast<uint8_t *>(a.values) + dst * cells * 4u, reinterpret_cast<const uint8_t *>(src), cells * 4u);
+            continue;
+        }
+        int16_t *__restrict__ out = reinterpret_cast<int16_t *>(a.values) + dst * cells;
+        if ((cells & 7u) == 0u && (((uintptr_t)out | (uintptr_t)src) & 15u) == 0u) {
+            for (size_t i = (size_t)threadIdx.x * 8u; i < cells; i += 256u * 8u) {
+                const uint4 p = *reinterpret_cast<const uint4 *>(src + i), q = *reinterpret_cast<const uint4 *>(src + i + 4);
+                uint4 o;
+                o.x = rec_narrow2(p.x, p.y), o.y = rec_narrow2(p.z, p.w), o.z = rec_narrow2(q.x, q.y), o.w = rec_narrow2(q.z, q.w);
+                *reinterpret_cast<uint4 *>(out + i) = o;
+            }
+        } else {
+            for (size_t i = threadIdx.x; i < cells; i += 256u) {
+                const int32_t v = src[i];
+                out[i] = v == (int32_t)GF_NULL_CODE ? (int16_t)-32768 : (int16_t)v;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t gf_launch_record_parse(const GfRecordParseArgs &a, hipStream_t stream)
+{
+    if (a.nTiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_record_parse, dim3((unsigned)((a.nTiles + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_record_crc32c(const uint8_t *blob, const uint64_t *starts, const uint32_t *sizes, int32_t *cls, int32_t *status,
+                                   size_t nTiles, hipStream_t stream)
+{
+    if (nTiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_record_crc32c, dim3((unsigned)((nTiles + 3) / 4)), dim3(256), 0, stream, blob, starts, sizes, cls, status, nTiles);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_codec_partition(const GfPartitionArgs &a, hipStream_t stream)
+{
+    if (a.nCodecs < 0 || a.nCodecs > 255) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_codec_partition, dim3(1), dim3(PART_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_tile_scatter(const GfTileScatterArgs &a, hipStream_t stream)
+{
+    if (a.nTotal == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_tile_scatter, gf_tile_grid(a.nTotal), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}

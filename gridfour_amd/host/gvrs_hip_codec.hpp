@@ -418,4 +418,30 @@ private:
     gf_context *ctx_ = nullptr;
 };
 
+/** RecordManager.readTile + TileElementInt/Short.decode for tile records that already lie in device memory
+ *  (gf_tile_record_decode_batch_dev): record t = dBlob[dOffsets[t] .. dOffsets[t+1]); tile indices (may be null), values
+ *  (int32 or int16 per elemType) and statuses stay on the device.  The call synchronises `stream` once; per-record
+ *  failures are statuses, anything else throws. */
+inline void tileRecordsDecodeDev(gf_context *ctx, void *stream, const std::vector<int> &codecs, int elemType, int nRows, int nCols,
+                                 size_t nTiles, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets, bool verifyChecksums,
+                                 int32_t *dTileIndices, void *dValues, int32_t *dStatus)
+{
+    const gf_status s = gf_tile_record_decode_batch_dev(ctx, stream, codecs.data(), (int)codecs.size(), elemType, nRows, nCols, nTiles, dBlob,
+                                                        blobBytes, dOffsets, verifyChecksums ? 1 : 0, dTileIndices, dValues, dStatus);
+    if (s == GF_ERR_ARG) throw std::invalid_argument("gf_tile_record_decode_batch_dev: bad argument");
+    if (s < 0) throw std::runtime_error(std::string("gf_tile_record_decode_batch_dev: ") + gf_status_string(s) + " [" + gf_last_error() + "]");
+}
+
+/** CodecMaster.decode for packings of mixed codecs in device memory (gf_codec_master_decode_batch_i32_dev): packing t =
+ *  dLengths[t] bytes at dBlob + dOffsets[t]. */
+inline void codecMasterDecodeDev(gf_context *ctx, void *stream, const std::vector<int> &codecs, int nRows, int nCols, size_t nTiles,
+                                 const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets, const uint32_t *dLengths,
+                                 int32_t *dValues, int32_t *dStatus)
+{
+    const gf_status s = gf_codec_master_decode_batch_i32_dev(ctx, stream, codecs.data(), (int)codecs.size(), nRows, nCols, nTiles, dBlob,
+                                                             blobBytes, dOffsets, dLengths, dValues, dStatus);
+    if (s == GF_ERR_ARG) throw std::invalid_argument("gf_codec_master_decode_batch_i32_dev: bad argument");
+    if (s < 0) throw std::runtime_error(std::string("gf_codec_master_decode_batch_i32_dev: ") + gf_status_string(s) + " [" + gf_last_error() + "]");
+}
+
 }  // namespace gridfour

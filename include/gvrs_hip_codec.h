@@ -502,6 +502,37 @@ gf_status gf_tile_record_decode_batch(gf_context *ctx, const int *codecs, int n_
                                       size_t n_tiles, const uint8_t *blob, const uint64_t *offsets, int verify_checksum,
                                       int32_t *tile_indices, void *values, int32_t *status);
 
+/* ---- tile records and mixed-codec packings that already lie in device memory -------------------------------------------
+ * The device-resident forms of gf_tile_record_decode_batch and gf_codec_master_decode_batch_i32, for a caller that has read a
+ * file region into device memory or whose consumer of the cells is on the GPU: the framing walk, the CRC-32C, the sorting
+ * of the packings by the codec their first byte names, the codecs' decoders, the narrowing of shorts and the copy of raw
+ * tiles all run on `stream`; nothing is gathered, every decoder reads its packings where they lie in d_blob.
+ *   d_blob, d_offsets, d_lengths, d_tile_indices, d_values, d_status are device memory; `codecs` is a host array.
+ *   d_blob is 4-byte aligned and readable up to the end of the aligned 4-byte word that holds byte blob_bytes - 1; records
+ *   and packings may start at any byte.
+ *   gf_tile_record_decode_batch_dev: record t lies in d_blob[d_offsets[t] .. d_offsets[t+1]) (n_tiles + 1 offsets); d_values
+ *     is int32 or int16 per elem_type; d_tile_indices may be NULL.
+ *   gf_codec_master_decode_batch_i32_dev: packing t = d_lengths[t] bytes at d_blob + d_offsets[t] (n_tiles offsets).
+ * Per tile, status, values and tile index are exactly what the host call produces for the same bytes (the values of a tile
+ * whose status is not GF_OK are unspecified, as there).  One deliberate difference: the offsets are on the device, so a bad
+ * offsets array cannot fail the call as a whole -- a record with d_offsets[t] > d_offsets[t+1] or d_offsets[t+1] > blob_bytes,
+ * or a packing with d_offsets[t] + d_lengths[t] > blob_bytes, gets GF_ERR_BOUNDS and nothing of it is read.
+ * GF_ERR_ARG, before the device is touched: null pointers, another elem_type, n_rows < 1 or n_cols < 1, a codec kind outside
+ * GF_CODEC_NONE .. GF_CODEC_LSOP12, n_codecs > 255 (and, for the codec-master form, n_codecs < 1).  n_tiles == 0 is GF_OK.
+ * NOT capture-safe, unlike the other _dev entry points: the host must learn how many tiles each codec has before it can launch
+ * the decoders, so these calls SYNCHRONISE `stream` ONCE (a copy of the per-codec counts into page-locked memory) and grow
+ * context-owned buffers on demand (the per-record tables; a temporary for the decoded tiles of a batch that mixes codecs,
+ * standard-form records or failed records -- a batch in which every record names the same codec is decoded straight into
+ * d_values).  Everything before and after the synchronisation is only enqueued.                                          */
+gf_status gf_codec_master_decode_batch_i32_dev(gf_context *ctx, void *stream, const int *codecs, int n_codecs, int n_rows,
+                                               int n_cols, size_t n_tiles, const uint8_t *d_blob, size_t blob_bytes,
+                                               const uint64_t *d_offsets, const uint32_t *d_lengths, int32_t *d_values,
+                                               int32_t *d_status);
+gf_status gf_tile_record_decode_batch_dev(gf_context *ctx, void *stream, const int *codecs, int n_codecs, int elem_type,
+                                          int n_rows, int n_cols, size_t n_tiles, const uint8_t *d_blob, size_t blob_bytes,
+                                          const uint64_t *d_offsets, int verify_checksum, int32_t *d_tile_indices,
+                                          void *d_values, int32_t *d_status);
+
 /* ---- CodecFloat (compress/CodecFloat.java:328-458): float32 tiles ---------------------------
  * The five byte planes (sign bits, exponent, three byte-delta coded mantissa bytes) are split and
  * merged on the GPU; the Deflate stage of each plane runs on the host's zlib (its bytes are defined

@@ -3,7 +3,13 @@ RecordManager.writeTile (gvrs/RecordManager.java:386-490) would call with the st
 CanonHuffman... of GvrsFileSpecification.java:221-230 -- gf_codec_master_{encode,decode}_batch_i32 and
 gf_tile_record_{encode,decode}_batch on an ETOPO1-shaped batch in host memory; next to it the rate of the host's zlib alone on
 the M32 streams the Deflate candidates consist of (the bound of anything that must reproduce zlib's bytes).
-    python tools/codec_master_rate.py [nTiles] [codec list, e.g. 1,2,0,3]"""
+    python tools/codec_master_rate.py [nTiles] [codec list, e.g. 1,2,0,3]
+Device-records mode: the same batch as tile records (gf_tile_record_encode_batch), decoded where they lie in device memory by
+gf_tile_record_decode_batch_dev -- HIP events on one stream, with and without checksum verification, with and without the one
+H2D copy of the blob (from page-locked memory) -- beside the host call gf_tile_record_decode_batch in the same run:
+    python tools/codec_master_rate.py --device-records [nTiles] [codec list] [--once] [--out profiles/device_records_rate.json]
+    python tools/codec_master_rate.py --merge-kernel-stats <rocprofv3 kernel_stats.csv> <the JSON written above>
+(--once: one call of each form and no timing loops, the run to put behind `rocprofv3 --kernel-trace --stats --`)"""
 import ctypes as C
 import json
 import os
@@ -116,5 +122,128 @@ def main():
     print(json.dumps(out))
 
 
+RECORD_KERNELS = ("k_record_parse", "k_record_crc32c", "k_codec_partition", "k_tile_scatter")
+
+
+def device_records(argv):
+    once = "--once" in argv
+    out_path = argv[argv.index("--out") + 1] if "--out" in argv else None
+    pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] != "--out")]
+    nt = int(pos[0]) if pos else 12960
+    codecs = [int(x) for x in (pos[1] if len(pos) > 1 else "1,2,0,3").split(",")]
+    n_rows, n_cols = 120, 150
+    cells = n_rows * n_cols
+    ctx = gridfour_amd.GvrsHipContext(0)
+    b = DeviceTileBatch(ctx, n_rows, n_cols, nt, slot_stride=16)
+    b.synth_dem(0x9E3779B97F4A7C15 + 2, 144)
+    ctx.synchronize()
+    vals = b.get_values().reshape(nt, cells)
+    del b
+    L = lib()
+    cd = (C.c_int * len(codecs))(*codecs)
+    gb = vals.nbytes / 1e9
+    rcap = nt * int(L.gf_tile_record_max_bytes(0, n_rows, n_cols))
+    rblob = np.empty(rcap, np.uint8)
+    roff = np.zeros(nt + 1, np.uint64)
+    idx = np.arange(nt, dtype=np.int32)
+    used = np.zeros(nt, np.uint8)
+    check(L.gf_tile_record_encode_batch(ctx.handle, cd, len(codecs), 0, -2 ** 31, n_rows, n_cols, nt, _p(idx), _p(vals), 1, _p(rblob), rcap,
+                                        _p(roff), _p(used)), "tile_record_encode")
+    total = int(roff[nt])
+    u, c = np.unique(used, return_counts=True)
+    out = {"workload": "etopo1: %d tile records of %dx%d int32 (%.2f GB of cells, %.3f GB of records)" % (nt, n_rows, n_cols, gb, total / 1e9),
+           "codec_list": codecs, "winners": {int(a): int(n) for a, n in zip(u, c)}, "threads": len(os.sched_getaffinity(0))}
+    # the records in page-locked memory (a reader's file buffer), and the device side
+    pinned = C.c_void_p()
+    check(L.gf_host_alloc(total + 64, C.byref(pinned)), "gf_host_alloc")
+    C.memmove(pinned, _p(rblob), total)
+    d_blob = gridfour_amd.DeviceBuffer(ctx, total + 64)
+    d_off = gridfour_amd.DeviceBuffer(ctx, roff.nbytes).upload(roff)
+    d_idx = gridfour_amd.DeviceBuffer(ctx, nt * 4)
+    d_val = gridfour_amd.DeviceBuffer(ctx, nt * cells * 4)
+    d_st = gridfour_amd.DeviceBuffer(ctx, nt * 4)
+    timer = gridfour_amd.GpuTimer(ctx)
+
+    def upload():
+        check(L.gf_dev_upload(ctx.handle, d_blob.ptr, pinned, total), "gf_dev_upload")
+
+    def decode(verify):
+        check(L.gf_tile_record_decode_batch_dev(ctx.handle, None, cd, len(codecs), 0, n_rows, n_cols, nt, d_blob.ptr, total, d_off.ptr, verify,
+                                                d_idx.ptr, d_val.ptr, d_st.ptr), "gf_tile_record_decode_batch_dev")
+
+    def measure(fn, reps):
+        ms, wall = 1e30, 1e30
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            timer.start()
+            fn()
+            timer.stop()
+            ms = min(ms, timer.elapsed_ms())
+            wall = min(wall, time.perf_counter() - t0)
+        return {"event_ms": round(ms, 4), "wall_seconds": round(wall, 5), "GBps_of_cells": round(gb / (ms / 1e3), 2)}
+
+    back = np.empty_like(vals)
+    ridx = np.zeros(nt, np.int32)
+    st = np.zeros(nt, np.int32)
+
+    def host():
+        check(L.gf_tile_record_decode_batch(ctx.handle, cd, len(codecs), 0, n_rows, n_cols, nt, _p(rblob), _p(roff), 1, _p(ridx), _p(back),
+                                            _p(st)), "tile_record_decode")
+
+    upload()
+    decode(1)                                             # (grows the context's buffers: not part of any timing)
+    ctx.synchronize()
+    assert (d_st.download(np.int32, nt) == 0).all() and np.array_equal(d_idx.download(np.int32, nt), idx)
+    assert np.array_equal(d_val.download(np.int32, nt * cells).reshape(nt, cells), vals)
+    reps = 1 if once else 5
+    out["device_verify"] = measure(lambda: decode(1), reps)
+    out["device_no_verify"] = measure(lambda: decode(0), reps)
+    out["device_verify_with_h2d"] = measure(lambda: (upload(), decode(1)), reps)
+    out["device_no_verify_with_h2d"] = measure(lambda: (upload(), decode(0)), reps)
+    host()                                                # (warm: staging buffers of the host pipeline)
+    t = 1e30
+    for _ in range(1 if once else 3):
+        t0 = time.perf_counter()
+        host()
+        t = min(t, time.perf_counter() - t0)
+    assert (st == 0).all() and np.array_equal(back, vals) and np.array_equal(ridx, idx)
+    out["host_call_verify"] = {"wall_seconds": round(t, 5), "GBps_of_cells": round(gb / t, 2),
+                               "note": "gf_tile_record_decode_batch: bytes and cells in pageable host memory, the D2H copy of the cells included"}
+    out["device_with_h2d_not_slower_than_host"] = bool(out["device_verify_with_h2d"]["wall_seconds"] <= t)
+    L.gf_host_free(pinned)
+    text = json.dumps(out)
+    print(text)
+    if out_path and not once:
+        with open(out_path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+def merge_kernel_stats(csv_path, json_path):
+    """per-kernel times of the four record kernels from one `rocprofv3 --kernel-trace --stats` run into the JSON of the mode above"""
+    import csv
+    with open(json_path) as f:
+        out = json.load(f)
+    rows = {}
+    with open(csv_path, newline="") as f:
+        for row in csv.DictReader(f):
+            name = row.get("Name", "")
+            for k in RECORD_KERNELS:
+                if k in name:
+                    rows[k] = {"calls": int(row["Calls"]), "average_us": round(float(row["AverageNs"]) / 1e3, 2),
+                               "min_us": round(float(row["MinNs"]) / 1e3, 2), "max_us": round(float(row["MaxNs"]) / 1e3, 2)}
+    out["kernels"] = rows
+    with open(json_path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rows))
+
+
 if __name__ == "__main__":
-    main()
+    if "--merge-kernel-stats" in sys.argv:
+        i = sys.argv.index("--merge-kernel-stats")
+        merge_kernel_stats(sys.argv[i + 1], sys.argv[i + 2])
+    elif "--device-records" in sys.argv:
+        device_records([a for a in sys.argv[1:] if a != "--device-records"])
+    else:
+        main()
