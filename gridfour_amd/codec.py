@@ -665,6 +665,9 @@ class LsCodecHip:
 
 CODEC_NONE, CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_CANON_HUFFMAN, CODEC_LSOP12 = 0, 1, 2, 3, 4
 STANDARD_CODEC_LIST = (CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_NONE, CODEC_CANON_HUFFMAN)    # GvrsFileSpecification.java:221-230
+ELEM_TYPES = {"int": 0, "short": 1, "float": 2, "icf": 3}                                 # GF_ELEM_*
+_ELEM_SPEC = np.dtype([("type", np.int32), ("fill_i", np.int32), ("scale", np.float32), ("offset", np.float32),
+                       ("fill_f", np.float32)])                                           # gf_elem_spec
 
 
 class CodecMasterHip:
@@ -795,6 +798,66 @@ class CodecMasterHip:
         offsets[1:] = np.cumsum([len(p) for p in records])
         blob = np.frombuffer(b"".join(records) + b"\0" * 16, dtype=np.uint8)[:int(offsets[-1])]
         return self.record_blob_dev(nRows, nCols, blob, offsets, element=element, verify_checksums=verify_checksums)
+
+    # ---- records of several elements, float and int-coded-float elements (gf_tile_record_decode_batch_elems[_dev]) ----
+    @staticmethod
+    def _elem_specs(elems):
+        """elems: per element "int" | "short" | "float" | ("icf", scale, offset, fill_i, fill_f) -> (gf_elem_spec array, value dtypes)"""
+        specs = np.zeros(len(elems), _ELEM_SPEC)
+        dtypes = []
+        for e, el in enumerate(elems):
+            kind = el if isinstance(el, str) else el[0]
+            specs[e]["type"] = ELEM_TYPES[kind]
+            specs[e]["scale"] = 1.0
+            if kind == "icf":
+                _, scale, offset, fill_i, fill_f = el
+                specs[e]["scale"], specs[e]["offset"], specs[e]["fill_i"], specs[e]["fill_f"] = scale, offset, fill_i, fill_f
+            dtypes.append({"int": np.int32, "short": np.int16}.get(kind, np.float32))
+        return specs, dtypes
+
+    def record_blob_elems_dev(self, nRows, nCols, blob, offsets, elems, verify_checksums=True):
+        """gf_tile_record_decode_batch_elems_dev on records as they lie in a byte array (as record_blob_dev), for tiles of
+        len(elems) elements (see _elem_specs).  Uploads blob and offsets, downloads the results: (tile indices, [values
+        [nt, cells] per element: int32 / int16 / float32], status [n_elems, nt]).  A tile is good iff all its statuses are 0."""
+        specs, dtypes = self._elem_specs(elems)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nt, ne, cells = offsets.size - 1, len(dtypes), nRows * nCols
+        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
+        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
+        d_idx = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0xff)
+        d_val = [DeviceBuffer(self.ctx, nt * cells * np.dtype(dt).itemsize + 16).fill(0) for dt in dtypes]
+        d_st = DeviceBuffer(self.ctx, ne * nt * 4 + 16).fill(0)
+        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_val])
+        try:
+            check(lib().gf_tile_record_decode_batch_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs),
+                                                              ne, nRows, nCols, nt, d_blob.ptr, blob.size, d_off.ptr,
+                                                              int(bool(verify_checksums)), d_idx.ptr, ptrs, d_st.ptr),
+                  "gf_tile_record_decode_batch_elems_dev")
+            self.ctx.synchronize()
+            idx = d_idx.download(np.int32, nt)
+            out = [b.download(dt, nt * cells).reshape(nt, cells) for b, dt in zip(d_val, dtypes)]
+            status = d_st.download(np.int32, ne * nt).reshape(ne, nt)
+        finally:
+            for b in [d_blob, d_off, d_idx, d_st] + d_val:
+                b.free()
+        return idx, out, status
+
+    def record_blob_elems(self, nRows, nCols, blob, offsets, elems, verify_checksums=True):
+        """The same through gf_tile_record_decode_batch_elems, the host-memory form (staged by the library, not pipelined);
+        offsets[-1] bytes of blob are read."""
+        specs, dtypes = self._elem_specs(elems)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        blob = np.concatenate([np.ascontiguousarray(blob, dtype=np.uint8), np.zeros(16, np.uint8)])
+        nt, ne, cells = offsets.size - 1, len(dtypes), nRows * nCols
+        idx = np.full(nt, -1, np.int32)
+        out = [np.zeros((nt, cells), dt) for dt in dtypes]
+        status = np.zeros((ne, nt), np.int32)
+        ptrs = (C.c_void_p * ne)(*[a.ctypes.data for a in out])
+        check(lib().gf_tile_record_decode_batch_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, nRows,
+                                                      nCols, nt, _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), _ptr(idx), ptrs,
+                                                      _ptr(status)), "gf_tile_record_decode_batch_elems")
+        return idx, out, status
 
     def packing_blob_dev(self, nRows, nCols, blob, offsets, lengths):
         """gf_codec_master_decode_batch_i32_dev: packing t = blob[offsets[t]:offsets[t]+lengths[t]].  Returns (values, status)."""

@@ -11,34 +11,6 @@ void gf_rec_counts_destroy(PinBuf *p)
     delete p;
 }
 
-namespace {
-
-struct RecBatch {
-    const int *codecs;
-    int nCodecs;
-    int elemShort;
-    int nRows, nCols;
-    size_t nTiles;
-    const uint8_t *dBlob;
-    size_t blobBytes;
-    const uint64_t *dOffsets;
-    const uint32_t *dLengths;       // null: tile records
-    int verifyChecksum;
-    int32_t *dTileIndices;
-    void *dValues;
-    int32_t *dStatus;
-};
-
-// what the host can check without a device
-gf_status recArgs(const gf_context *c, const RecBatch &b)
-{
-    if (!c || !b.dBlob || !b.dOffsets || !b.dValues || !b.dStatus || (!b.codecs && b.nCodecs > 0)) return GF_ERR_ARG;
-    if (b.nRows < 1 || b.nCols < 1 || b.nCodecs > 255 || ((uintptr_t)b.dBlob & 3) != 0) return GF_ERR_ARG;
-    for (int k = 0; k < b.nCodecs; k++)
-        if (b.codecs[k] < GF_CODEC_NONE || b.codecs[k] > GF_CODEC_LSOP12) return GF_ERR_ARG;
-    return GF_OK;
-}
-
 // one codec's share of the batch through its device decoder: packing j = lengths[j] bytes at dBlob + offsets[j]
 gf_status decodeSublist(gf_context *c, hipStream_t st, int codec, const RecBatch &b, size_t n, const uint64_t *offsets,
                         const uint32_t *lengths, int32_t *values, int32_t *status)
@@ -61,6 +33,18 @@ gf_status decodeSublist(gf_context *c, hipStream_t st, int codec, const RecBatch
     }
     default: return GF_ERR_ARG;
     }
+}
+
+namespace {
+
+// what the host can check without a device
+gf_status recArgs(const gf_context *c, const RecBatch &b)
+{
+    if (!c || !b.dBlob || !b.dOffsets || !b.dValues || !b.dStatus || (!b.codecs && b.nCodecs > 0)) return GF_ERR_ARG;
+    if (b.nRows < 1 || b.nCols < 1 || b.nCodecs > 255 || ((uintptr_t)b.dBlob & 3) != 0) return GF_ERR_ARG;
+    for (int k = 0; k < b.nCodecs; k++)
+        if (b.codecs[k] < GF_CODEC_NONE || b.codecs[k] > GF_CODEC_LSOP12) return GF_ERR_ARG;
+    return GF_OK;
 }
 
 gf_status recDecodeDev(gf_context *c, void *stream, const RecBatch &b)

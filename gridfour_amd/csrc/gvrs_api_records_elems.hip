@@ -1,0 +1,211 @@
+// gvrs_api_records_elems.hip -- tile records of several elements and of float / int-coded-float elements, decoded where they lie
+// in device memory (gf_tile_record_decode_batch_elems_dev), and the same call for bytes in host memory.  The layer that joins
+// the record kernels of gvrs_records.hip with the integer codecs' device decoders and CodecFloat's (floatDecodeDev): every
+// element of every record is one INSTANCE, the instances lie element-major (i = e * nTiles + t), and one partition by codec index,
+// one count read-back and one launch per codec serve all elements together.
+// Reference: gvrs/RecordManager.java:492-515, gvrs/RasterTile.java:234-256, TileElement{Int,Short,Float,IntCodedFloat}.decode,
+// gvrs/CodecMaster.java:195-203 (decode), 296-304 (decodeFloats).
+
+#include "gvrs_api_internal.h"
+
+namespace {
+
+// what the host can check without a device (values: device or host pointers, only looked at for null)
+gf_status elemsArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows, int nCols,
+                    const uint8_t *blob, bool blobOnDevice, const uint64_t *offsets, void *const *values, const int32_t *status)
+{
+    if (!c || !elems || !blob || !offsets || !values || !status || (!codecs && nCodecs > 0)) return GF_ERR_ARG;
+    if (nElems < 1 || nElems > GF_MAX_ELEMS || nRows < 1 || nCols < 1 || nCodecs > 255) return GF_ERR_ARG;
+    if (blobOnDevice && ((uintptr_t)blob & 3) != 0) return GF_ERR_ARG;
+    for (int e = 0; e < nElems; e++) {
+        if (!values[e] || elems[e].type < GF_ELEM_INT || elems[e].type > GF_ELEM_ICF) return GF_ERR_ARG;
+        if (elems[e].type == GF_ELEM_ICF && (elems[e].scale == 0.0f || std::isnan(elems[e].scale))) return GF_ERR_ARG;
+    }
+    for (int k = 0; k < nCodecs; k++)
+        if (codecs[k] < GF_CODEC_NONE || codecs[k] > GF_CODEC_LSOP12) return GF_ERR_ARG;
+    return GF_OK;
+}
+
+size_t elemItemBytes(int type) { return type == GF_ELEM_SHORT ? 2 : 4; }
+
+gf_status elemsDecodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
+                         int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets, int verifyChecksum,
+                         int32_t *dTileIndices, void *const *dValues, int32_t *dStatus)
+{
+    const size_t cells = (size_t)nRows * (size_t)nCols, n = nTiles, nInst = (size_t)nElems * n;
+    if (cells >= (1ull << 28)) return GF_ERR_UNSUPPORTED;
+    GF_HIP(hipSetDevice(c->device));
+    const hipStream_t st = streamOf(c, stream);
+    const int nSeg = nCodecs + 1;                                                 // the codecs, then the standard form
+    const size_t nPad = roundUp(nInst, 4), nRecPad = roundUp(n, 4);
+    gf_status s;
+    if ((s = c->dRecMeta.ensure(nPad * 16 + nRecPad * 4 + 16)) != GF_OK) return s;
+    if ((s = c->dRecSub.ensure(nPad * 20 + 256 * 4 + GF_MAX_ELEMS * sizeof(GfElemDesc) + 16)) != GF_OK) return s;
+    if (!c->hRecCounts) {
+        c->hRecCounts = new (std::nothrow) PinBuf();
+        if (!c->hRecCounts) return GF_ERR_HIP;
+    }
+    if ((s = c->hRecCounts->ensure(256 * 4)) != GF_OK) return s;
+    uint64_t *starts = (uint64_t *)c->dRecMeta.p;
+    uint32_t *lens = (uint32_t *)(starts + nPad);
+    int32_t *cls = (int32_t *)(lens + nPad);
+    uint32_t *sizes = (uint32_t *)(cls + nPad);
+    uint64_t *subOffsets = (uint64_t *)c->dRecSub.p;
+    uint32_t *subLengths = (uint32_t *)(subOffsets + nPad), *subDst = subLengths + nPad;
+    int32_t *subStatus = (int32_t *)(subDst + nPad);
+    uint32_t *dCounts = (uint32_t *)(subStatus + nPad);
+    GfElemDesc *dElems = (GfElemDesc *)(dCounts + 256);                            // (16-byte aligned: every part is a multiple of 16)
+
+    // the element table for k_elem_scatter; the walk takes the types as a packed word.  (A pageable source: the runtime has
+    // staged the copy when the call returns, and the table outlives the synchronisation below anyway.)
+    GfElemDesc table[GF_MAX_ELEMS] = {};
+    uint32_t types = 0;
+    for (int e = 0; e < nElems; e++) {
+        table[e].values = dValues[e];
+        table[e].type = elems[e].type;
+        table[e].fillI = elems[e].fill_i;
+        table[e].scale = elems[e].scale;
+        table[e].offset = elems[e].offset;
+        table[e].fillF = elems[e].fill_f;
+        types |= (uint32_t)elems[e].type << (2 * e);
+    }
+    GF_HIP(hipMemcpyAsync(dElems, table, (size_t)nElems * sizeof(GfElemDesc), hipMemcpyHostToDevice, st));
+
+    GfRecordParseElemsArgs p{};
+    p.blob = dBlob;
+    p.blobBytes = blobBytes;
+    p.offsets = dOffsets;
+    p.nTiles = n;
+    p.nElems = nElems;
+    p.elemTypes = types;
+    p.cells = (uint32_t)cells;
+    p.nCodecs = nCodecs;
+    uint64_t iset[4] = {0, 0, 0, 0}, fset[4] = {0, 0, 0, 0};
+    for (int k = 0; k < nCodecs; k++) (codecs[k] != GF_CODEC_NONE ? iset : fset)[k >> 6] |= 1ull << (k & 63);
+    p.intSet0 = iset[0], p.intSet1 = iset[1], p.intSet2 = iset[2], p.intSet3 = iset[3];
+    p.floatSet0 = fset[0], p.floatSet1 = fset[1], p.floatSet2 = fset[2], p.floatSet3 = fset[3];
+    p.tileIndices = dTileIndices;
+    p.starts = starts;
+    p.lens = lens;
+    p.cls = cls;
+    p.status = dStatus;
+    p.sizes = sizes;
+    GF_HIP(gf_launch_record_parse_elems(p, st));
+    if (verifyChecksum) GF_HIP(gf_launch_record_crc32c_elems(dBlob, dOffsets, sizes, cls, dStatus, n, nElems, st));
+    GfPartitionArgs q{};
+    q.cls = cls;
+    q.starts = starts;
+    q.lens = lens;
+    q.nTiles = nInst;
+    q.nCodecs = nCodecs;
+    q.subOffsets = subOffsets;
+    q.subLengths = subLengths;
+    q.subDst = subDst;
+    q.counts = dCounts;
+    GF_HIP(gf_launch_codec_partition(q, st));
+    // the one synchronisation of the call: the host has to know which decoders to launch, and for how many instances
+    const uint32_t *counts = (const uint32_t *)c->hRecCounts->p;
+    GF_HIP(hipMemcpyAsync(c->hRecCounts->p, dCounts, (size_t)nSeg * 4, hipMemcpyDeviceToHost, st));
+    GF_HIP(hipStreamSynchronize(st));
+    size_t nPacked = 0;
+    for (int k = 0; k < nCodecs; k++) nPacked += counts[k];
+    const size_t nStd = counts[nCodecs];
+    RecBatch b{};                                                                  // (what decodeSublist reads: the shape and the blob)
+    b.nRows = nRows, b.nCols = nCols, b.dBlob = dBlob, b.blobBytes = blobBytes;
+    // one INT or FLOAT element and every record names the same codec: the partition is the identity, the decoder writes to the caller's arrays
+    if (nElems == 1 && (elems[0].type == GF_ELEM_INT || elems[0].type == GF_ELEM_FLOAT))
+        for (int k = 0; k < nCodecs; k++)
+            if (counts[k] == n) {
+                if (codecs[k] == GF_CODEC_NONE) return floatDecodeDev(c, st, nRows, nCols, n, dBlob, blobBytes, starts, lens, (float *)dValues[0], dStatus);
+                return decodeSublist(c, st, codecs[k], b, n, starts, lens, (int32_t *)dValues[0], dStatus);
+            }
+    if (nPacked && (s = c->dRecTmp.ensure(nPacked * cells * 4 + 64)) != GF_OK) return s;
+    int32_t *tmp = (int32_t *)c->dRecTmp.p;
+    size_t j0 = 0;
+    for (int k = 0; k < nCodecs; k++) {                                            // in list order, on the caller's stream
+        const size_t nk = counts[k];
+        if (!nk) continue;
+        if (codecs[k] == GF_CODEC_NONE)
+            s = floatDecodeDev(c, st, nRows, nCols, nk, dBlob, blobBytes, subOffsets + j0, subLengths + j0, (float *)(tmp + j0 * cells), subStatus + j0);
+        else s = decodeSublist(c, st, codecs[k], b, nk, subOffsets + j0, subLengths + j0, tmp + j0 * cells, subStatus + j0);
+        if (s != GF_OK) return s;
+        j0 += nk;
+    }
+    GfElemScatterArgs g{};
+    g.blob = dBlob;
+    g.tmp = tmp;
+    g.subStatus = subStatus;
+    g.subOffsets = subOffsets;
+    g.subDst = subDst;
+    g.nPacked = nPacked;
+    g.nTotal = nPacked + nStd;
+    g.nTiles = n;
+    g.cells = (uint32_t)cells;
+    g.elems = dElems;
+    g.status = dStatus;
+    GF_HIP(gf_launch_elem_scatter(g, st));
+    return GF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gf_status gf_tile_record_decode_batch_elems_dev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems,
+                                                int nElems, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
+                                                const uint64_t *dOffsets, int verifyChecksum, int32_t *dTileIndices, void *const *dValues,
+                                                int32_t *dStatus)
+{
+    if (nCodecs < 0) nCodecs = 0;
+    const gf_status s = elemsArgs(c, codecs, nCodecs, elems, nElems, nRows, nCols, dBlob, true, dOffsets, dValues, dStatus);
+    if (s != GF_OK) return s;
+    if (nTiles > 0x7fffffffull / (size_t)nElems) return GF_ERR_UNSUPPORTED;         // instance numbers travel as 32 bits
+    if (nTiles == 0) return GF_OK;
+    GF_CTX_LOCK(c);
+    return elemsDecodeDev(c, stream, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, dBlob, blobBytes, dOffsets, verifyChecksum,
+                          dTileIndices, dValues, dStatus);
+}
+
+gf_status gf_tile_record_decode_batch_elems(gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems,
+                                            int nRows, int nCols, size_t nTiles, const uint8_t *blob, const uint64_t *offsets,
+                                            int verifyChecksum, int32_t *tileIndices, void *const *values, int32_t *status)
+{
+    if (nCodecs < 0) nCodecs = 0;
+    gf_status s = elemsArgs(c, codecs, nCodecs, elems, nElems, nRows, nCols, blob, false, offsets, values, status);
+    if (s != GF_OK) return s;
+    if (nTiles > 0x7fffffffull / (size_t)nElems) return GF_ERR_UNSUPPORTED;
+    if (nTiles == 0) return GF_OK;
+    GF_CTX_LOCK(c);
+    const size_t cells = (size_t)nRows * (size_t)nCols, nInst = (size_t)nElems * nTiles;
+    if (cells >= (1ull << 28)) return GF_ERR_UNSUPPORTED;
+    GF_HIP(hipSetDevice(c->device));
+    const size_t blobBytes = (size_t)offsets[nTiles];
+    // staging: blob | offsets | values of element 0, 1, ... (each part a multiple of 16 bytes) | statuses, tile indices
+    size_t valueBytes = 0, at[GF_MAX_ELEMS];
+    for (int e = 0; e < nElems; e++) {
+        at[e] = valueBytes;
+        valueBytes += roundUp(nTiles * cells * elemItemBytes(elems[e].type), 16);
+    }
+    if ((s = c->dBlob.ensure(blobBytes + 32)) != GF_OK) return s;
+    if ((s = c->dOffsets.ensure((nTiles + 1) * 8 + 16)) != GF_OK) return s;
+    if ((s = c->dValues.ensure(valueBytes + 16)) != GF_OK) return s;
+    if ((s = c->dStatus.ensure((nInst + nTiles) * 4 + 16)) != GF_OK) return s;
+    int32_t *dStatus = (int32_t *)c->dStatus.p, *dIndices = dStatus + nInst;
+    void *dValues[GF_MAX_ELEMS];
+    for (int e = 0; e < nElems; e++) dValues[e] = (uint8_t *)c->dValues.p + at[e];
+    GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, blobBytes, hipMemcpyHostToDevice, c->stream));
+    GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nTiles + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (tileIndices) GF_HIP(hipMemcpyAsync(dIndices, tileIndices, nTiles * 4, hipMemcpyHostToDevice, c->stream));   // (a failed record keeps the caller's entry)
+    GF_HIP(hipMemsetAsync(c->dValues.p, 0, valueBytes, c->stream));               // (an element that fails reads as zeros, not as an earlier batch)
+    s = elemsDecodeDev(c, c->stream, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, (const uint8_t *)c->dBlob.p, blobBytes,
+                       (const uint64_t *)c->dOffsets.p, verifyChecksum, tileIndices ? dIndices : nullptr, dValues, dStatus);
+    if (s != GF_OK) return s;
+    for (int e = 0; e < nElems; e++)
+        GF_HIP(hipMemcpyAsync(values[e], dValues[e], nTiles * cells * elemItemBytes(elems[e].type), hipMemcpyDeviceToHost, c->stream));
+    GF_HIP(hipMemcpyAsync(status, dStatus, nInst * 4, hipMemcpyDeviceToHost, c->stream));
+    if (tileIndices) GF_HIP(hipMemcpyAsync(tileIndices, dIndices, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
+    GF_HIP(hipStreamSynchronize(c->stream));
+    return GF_OK;
+}
+
+}  // extern "C"

@@ -462,3 +462,53 @@ struct GfTileScatterArgs {
     int32_t *status;
 };
 hipError_t gf_launch_tile_scatter(const GfTileScatterArgs &a, hipStream_t stream);
+
+// Tile records of several elements (gf_tile_record_decode_batch_elems_dev; driven by gvrs_api_records_elems.hip).  Every per-element
+// array is ELEMENT-MAJOR: instance i = e * nTiles + t is element e of record t, so that k_codec_partition sorts the instances of all
+// elements in one run and a codec's decoder is launched once for all of them.
+constexpr int GF_K_MAX_ELEMS = 16;               // (= GF_MAX_ELEMS of the C ABI)
+constexpr int GF_K_ELEM_INT = 0, GF_K_ELEM_SHORT = 1, GF_K_ELEM_FLOAT = 2, GF_K_ELEM_ICF = 3;    // (= GF_ELEM_*)
+struct GfElemDesc {            // an element of the tile, in device memory for k_elem_scatter (32 bytes)
+    void *values;              // nTiles * cells cells: int32 (INT), int16 (SHORT), float32 (FLOAT, ICF)
+    int32_t type;              // GF_K_ELEM_*
+    int32_t fillI;             // ICF: the stored code of "no data" ...
+    float scale, offset;       // ... value = code / scale + offset
+    float fillF;               // ... and what a cell equal to fillI is delivered as
+    uint32_t pad;
+};
+struct GfRecordParseElemsArgs {
+    const uint8_t *blob;       // 4-byte aligned
+    size_t blobBytes;
+    const uint64_t *offsets;   // nTiles + 1 entries, record t = [offsets[t], offsets[t + 1])
+    size_t nTiles;
+    int nElems;                // 1 .. GF_K_MAX_ELEMS
+    uint32_t elemTypes;        // two bits per element: its GF_K_ELEM_* (no indexed kernel argument)
+    uint32_t cells;
+    int nCodecs;
+    uint64_t intSet0, intSet1, intSet2, intSet3;       // bit k: entry k of the codec list has an integer decoder
+    uint64_t floatSet0, floatSet1, floatSet2, floatSet3;   // bit k: entry k is GF_CODEC_NONE, the slot of CodecFloat
+    int32_t *tileIndices;      // may be null
+    uint64_t *starts;          // per instance: where the element bytes start in the blob
+    uint32_t *lens;            // ... how many they are
+    int32_t *cls;              // ... its class (GF_REC_FAILED, GF_REC_STANDARD or the index of its codec)
+    int32_t *status;           // ... GF_K_OK or the framing's verdict
+    uint32_t *sizes;           // per RECORD: its size field when the record is one whose checksum the host call verifies, else 0
+};
+hipError_t gf_launch_record_parse_elems(const GfRecordParseElemsArgs &a, hipStream_t stream);
+// the CRC-32C of every record with sizes[t] != 0; a mismatch: status GF_K_ERR_FORMAT, class GF_REC_FAILED for all nElems instances
+hipError_t gf_launch_record_crc32c_elems(const uint8_t *blob, const uint64_t *offsets, const uint32_t *sizes, int32_t *cls, int32_t *status,
+                                         size_t nTiles, int nElems, hipStream_t stream);
+struct GfElemScatterArgs {
+    const uint8_t *blob;
+    const int32_t *tmp;        // decoded tiles (int32 cells or float bit patterns), entry j of the partition at tmp + j * cells
+    const int32_t *subStatus;  // their decoders' statuses
+    const uint64_t *subOffsets;
+    const uint32_t *subDst;    // the entry's instance number
+    size_t nPacked;            // entries with a decoded tile; [nPacked, nTotal): elements in standard form
+    size_t nTotal;
+    size_t nTiles;
+    uint32_t cells;
+    const GfElemDesc *elems;   // device memory, nElems entries
+    int32_t *status;           // per instance
+};
+hipError_t gf_launch_elem_scatter(const GfElemScatterArgs &a, hipStream_t stream);

@@ -284,6 +284,216 @@ __global__ __launch_bounds__(256) void k_tile_scatter(const GfTileScatterArgs a)
     }
 }
 
+// ================================================================================================
+// Tile records of several elements (gf_tile_record_decode_batch_elems_dev): TileElementInt / Short / Float / IntCodedFloat, any
+// number of them per tile (RasterTile.java:234-256 loops over tile.elements; TileElement*.decode).  The per-element arrays are
+// element-major (gvrs_kernels.h), k_codec_partition runs over them unchanged.
+// ================================================================================================
+
+// k_record_parse_elems: a lane per record.  The record's head exactly as k_record_parse fetches and judges it (a head that fails
+// gives every element that status), then the short serial walk over the elements' length words: element 0's at byte 12, each next
+// one directly behind the bytes of the one before, at any byte address.  An element whose length word or bytes do not fit the
+// record is GF_K_ERR_BOUNDS, and so is every element behind it (they cannot be located); the ones in front keep their own class.
+// A packing of an INT, SHORT or ICF element must name an integer codec of the list, a packing of a FLOAT element an entry that is
+// GF_CODEC_NONE (the slot of CodecFloat).  sizes[t] != 0 marks the records whose checksum the host call would look at: the head
+// passed and element 0 fits (gf_tile_record_decode_batch's order).
+__global__ __launch_bounds__(256) void k_record_parse_elems(const GfRecordParseElemsArgs a)
+{
+    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= a.nTiles) return;
+    const uint8_t *__restrict__ blob = a.blob;
+    const uint64_t o0 = a.offsets[t], o1 = a.offsets[t + 1];
+    int32_t headSt = GF_K_OK;
+    uint32_t size = 0, h3 = 0, h4 = 0;
+    if (o0 > o1 || o1 > a.blobBytes || o1 - o0 < 20u) headSt = GF_K_ERR_BOUNDS;          // (nothing of such a record is read)
+    else {
+        const uint8_t *r = blob + o0;
+        uint32_t h0, h1, h2;
+        if ((o0 & 3u) == 0u) {
+            const GfU4 q = *reinterpret_cast<const GfU4 *>(r);
+            h4 = *reinterpret_cast<const uint32_t *>(r + 16);
+            h0 = q.x, h1 = q.y, h2 = q.z, h3 = q.w;
+        } else {
+            h0 = rec_le32(r), h1 = rec_le32(r + 4), h2 = rec_le32(r + 8), h3 = rec_le32(r + 12), h4 = r[16];
+        }
+        size = h0;
+        if ((uint64_t)size > o1 - o0 || size < 20u || (size & 7u)) headSt = GF_K_ERR_BOUNDS;
+        else if ((h1 & 0xffu) != 2u) headSt = GF_K_ERR_FORMAT;                            // not RecordType.Tile
+        else if (a.tileIndices) a.tileIndices[t] = (int32_t)h2;
+    }
+    const uint8_t *r = blob + o0;
+    bool located = headSt == GF_K_OK;                       // the next element's length word is known to be at r + pos
+    uint32_t pos = 12, crcSize = 0;
+    for (int e = 0; e < a.nElems; e++) {
+        int32_t st = headSt, cls = GF_REC_FAILED;
+        uint64_t start = 0;
+        uint32_t n = 0;
+        if (headSt == GF_K_OK) {
+            st = GF_K_ERR_BOUNDS;
+            if (located && (uint64_t)pos + 4u <= size) n = e == 0 ? h3 : rec_le32(r + pos);
+            else located = false;
+            if (located && (uint64_t)pos + 4u + n > size) located = false;
+            if (located) {
+                const uint32_t type = (a.elemTypes >> (2 * e)) & 3u;
+                // TileElement.java:86-93: bytes per sample * cells, rounded up to a multiple of 4
+                const uint32_t stdSize = type == (uint32_t)GF_K_ELEM_SHORT ? ((a.cells * 2u + 3u) & ~3u) : a.cells * 4u;
+                start = o0 + pos + 4u;
+                st = GF_K_OK;
+                if (e == 0) crcSize = size;
+                if (n == stdSize) cls = GF_REC_STANDARD;
+                else if (a.nCodecs < 1 || n == 0u) st = GF_K_ERR_FORMAT;
+                else {
+                    const uint32_t first = e == 0 ? (h4 & 0xffu) : (uint32_t)r[pos + 4u];
+                    const bool f = type == (uint32_t)GF_K_ELEM_FLOAT;
+                    // (the list's decoders for this element type as a bit set in four words: no indexed kernel argument)
+                    const uint64_t w = first < 64u    ? (f ? a.floatSet0 : a.intSet0)
+                                       : first < 128u ? (f ? a.floatSet1 : a.intSet1)
+                                       : first < 192u ? (f ? a.floatSet2 : a.intSet2)
+                                                      : (f ? a.floatSet3 : a.intSet3);
+                    if ((int)first < a.nCodecs && ((w >> (first & 63u)) & 1ull)) cls = (int32_t)first;
+                    else st = GF_K_ERR_FORMAT;                                      // outside the list, or no decoder for this type
+                }
+                pos += 4u + n;
+            }
+        }
+        const size_t i = (size_t)e * a.nTiles + t;
+        a.starts[i] = start;
+        a.lens[i] = n;
+        a.cls[i] = cls;
+        a.status[i] = st;
+    }
+    a.sizes[t] = crcSize;
+}
+
+// k_record_crc32c_elems: k_record_crc32c for records of several elements -- a wave per record with sizes[t] != 0, the record's
+// origin from the offsets, the same runs.  A mismatch reaches all nElems instances of the record (lane e writes element e's):
+// class failed, GF_K_ERR_FORMAT, whatever the walk said about them.
+__global__ __launch_bounds__(256) void k_record_crc32c_elems(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets,
+                                                             const uint32_t *__restrict__ sizes, int32_t *__restrict__ cls,
+                                                             int32_t *__restrict__ status, size_t nTiles, int nElems)
+{
+    __shared__ uint32_t table[256];
+    table[threadIdx.x] = crc_table_entry(threadIdx.x);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t t = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (t >= nTiles) return;
+    const uint32_t size = sizes[t];
+    if (size == 0u) return;
+    const uint64_t o0 = offsets[t];
+    const uint32_t nBytes = size - 4u;
+    const uint8_t *__restrict__ r = blob + o0;
+    const uint32_t per = ((nBytes + 63u) / 64u + 15u) & ~15u, begin = min(nBytes, lane * per), end = min(nBytes, begin + per);
+    uint32_t crc = 0xffffffffu, i = begin;
+    if ((o0 & 3u) == 0u) {
+        for (; i + 16u <= end; i += 16u) {
+            const GfU4 q = *reinterpret_cast<const GfU4 *>(r + i);
+            crc = crc_word(table, crc, q.x);
+            crc = crc_word(table, crc, q.y);
+            crc = crc_word(table, crc, q.z);
+            crc = crc_word(table, crc, q.w);
+        }
+        for (; i + 4u <= end; i += 4u) crc = crc_word(table, crc, *reinterpret_cast<const uint32_t *>(r + i));
+    }
+    for (; i < end; i++) crc = table[(crc ^ r[i]) & 0xffu] ^ (crc >> 8);
+    crc ^= 0xffffffffu;                                                       // the run's own checksum (an empty run: 0)
+    uint32_t part = crc_mulmod(crc_xpow8n(nBytes - end), crc);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
+    if ((int)lane < nElems && part != rec_le32(r + nBytes)) {
+        status[(size_t)lane * nTiles + t] = GF_K_ERR_FORMAT;
+        cls[(size_t)lane * nTiles + t] = GF_REC_FAILED;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_elem_scatter: a workgroup per entry of the partition; the entry's instance number says which element of which record it is.
+// Decoded tiles (entries below nPacked) go from the temporary to their place when their decoder said GF_K_OK: INT and FLOAT cells
+// copied, SHORT narrowed as k_tile_scatter does, ICF converted; the decoder's status to status[instance].  The entries behind
+// them are elements in standard form: INT, FLOAT and SHORT cells copied from wherever they lie in the blob, ICF converted from
+// raw little-endian ints at any byte alignment.  Every path issues its loads before its stores and leaves the wave in rows of
+// 16 (8, 4, 2) bytes per lane (DESIGN section 8 on requests and on loads queued behind stores).
+// ------------------------------------------------------------------------------------------------
+// TileElementIntCodedFloat.java:172-176: values[index] / scale + offset in single precision, each step rounded once
+__device__ __forceinline__ uint32_t rec_icf(uint32_t code, const GfElemDesc &d)
+{
+    const float v = __fadd_rn(__fdiv_rn((float)(int32_t)code, d.scale), d.offset);
+    return (int32_t)code == d.fillI ? __float_as_uint(d.fillF) : __float_as_uint(v);
+}
+
+__device__ __forceinline__ uint4 rec_icf4(const uint4 c, const GfElemDesc &d)
+{
+    uint4 o;
+    o.x = rec_icf(c.x, d), o.y = rec_icf(c.y, d), o.z = rec_icf(c.z, d), o.w = rec_icf(c.w, d);
+    return o;
+}
+
+// cells ints at src (any byte address) -> floats at dst: eight cells per lane, then four, in 16-byte pieces where both sides are
+// 16-byte aligned, and a tail of single cells; single words where only the source is 4-byte aligned; bytes otherwise
+__device__ __forceinline__ void rec_icf_tile(uint32_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t cells, const GfElemDesc &d)
+{
+    if ((((uintptr_t)dst | (uintptr_t)src) & 15u) == 0u) {
+        const uint32_t n8 = cells & ~7u, n4 = cells & ~3u;
+#pragma unroll 1
+        for (uint32_t i = threadIdx.x * 8u; i < n8; i += 256u * 8u) {
+            const uint4 p = *reinterpret_cast<const uint4 *>(src + (size_t)i * 4u), q = *reinterpret_cast<const uint4 *>(src + (size_t)i * 4u + 16u);
+            const uint4 u = rec_icf4(p, d), v = rec_icf4(q, d);
+            *reinterpret_cast<uint4 *>(dst + i) = u;
+            *reinterpret_cast<uint4 *>(dst + i + 4) = v;
+        }
+        if (threadIdx.x == 0 && n4 > n8) *reinterpret_cast<uint4 *>(dst + n8) = rec_icf4(*reinterpret_cast<const uint4 *>(src + (size_t)n8 * 4u), d);
+        if (n4 + threadIdx.x < cells) dst[n4 + threadIdx.x] = rec_icf(*reinterpret_cast<const uint32_t *>(src + (size_t)(n4 + threadIdx.x) * 4u), d);
+    } else if (((uintptr_t)src & 3u) == 0u) {
+#pragma unroll 1
+        for (uint32_t i = threadIdx.x; i < cells; i += 256u) dst[i] = rec_icf(*reinterpret_cast<const uint32_t *>(src + (size_t)i * 4u), d);
+    } else {
+#pragma unroll 1
+        for (uint32_t i = threadIdx.x; i < cells; i += 256u) dst[i] = rec_icf(rec_le32(src + (size_t)i * 4u), d);
+    }
+}
+
+// decoded cells -> shorts (TileElementShort.java:239-246), as k_tile_scatter narrows them
+__device__ __forceinline__ void rec_narrow_tile(int16_t *__restrict__ out, const int32_t *__restrict__ src, uint32_t cells)
+{
+    if ((cells & 7u) == 0u && (((uintptr_t)out | (uintptr_t)src) & 15u) == 0u) {
+        for (uint32_t i = threadIdx.x * 8u; i < cells; i += 256u * 8u) {
+            const uint4 p = *reinterpret_cast<const uint4 *>(src + i), q = *reinterpret_cast<const uint4 *>(src + i + 4);
+            uint4 o;
+            o.x = rec_narrow2(p.x, p.y), o.y = rec_narrow2(p.z, p.w), o.z = rec_narrow2(q.x, q.y), o.w = rec_narrow2(q.z, q.w);
+            *reinterpret_cast<uint4 *>(out + i) = o;
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < cells; i += 256u) {
+            const int32_t v = src[i];
+            out[i] = v == (int32_t)GF_NULL_CODE ? (int16_t)-32768 : (int16_t)v;
+        }
+    }
+}
+
+// (8 waves per SIMD asked for: left alone the compiler interleaves the eight divisions of the ICF loop over 113 VGPRs, 4 waves per SIMD for
+// every path of a kernel that is bandwidth; held to 64 it needs 58 and no scratch)
+__global__ __launch_bounds__(256, 8) void k_elem_scatter(const GfElemScatterArgs a)
+{
+    GF_FOR_WG_TILE(j, a.nTotal)
+    {
+        const uint32_t inst = a.subDst[j], e = inst / (uint32_t)a.nTiles;
+        const size_t t = inst - (size_t)e * a.nTiles, cells = a.cells;
+        const GfElemDesc d = a.elems[e];                                       // (workgroup-uniform: scalar loads)
+        const uint8_t *__restrict__ src;
+        if (j >= a.nPacked) src = a.blob + a.subOffsets[j];
+        else {
+            const int32_t st = a.subStatus[j];
+            if (threadIdx.x == 0) a.status[inst] = st;
+            if (st != GF_K_OK) continue;
+            src = reinterpret_cast<const uint8_t *>(a.tmp + j * cells);
+        }
+        if (d.type == GF_K_ELEM_ICF) rec_icf_tile(reinterpret_cast<uint32_t *>(d.values) + t * cells, src, (uint32_t)cells, d);
+        else if (d.type != GF_K_ELEM_SHORT) rec_copy(reinterpret_cast<uint8_t *>(d.values) + t * cells * 4u, src, cells * 4u);
+        else if (j >= a.nPacked) rec_copy(reinterpret_cast<uint8_t *>(d.values) + t * cells * 2u, src, cells * 2u);
+        else rec_narrow_tile(reinterpret_cast<int16_t *>(d.values) + t * cells, reinterpret_cast<const int32_t *>(src), (uint32_t)cells);
+    }
+}
+
 }  // namespace
 
 hipError_t gf_launch_record_parse(const GfRecordParseArgs &a, hipStream_t stream)
@@ -312,5 +522,29 @@ hipError_t gf_launch_tile_scatter(const GfTileScatterArgs &a, hipStream_t stream
 {
     if (a.nTotal == 0) return hipSuccess;
     hipLaunchKernelGGL(k_tile_scatter, gf_tile_grid(a.nTotal), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_record_parse_elems(const GfRecordParseElemsArgs &a, hipStream_t stream)
+{
+    if (a.nElems < 1 || a.nElems > GF_K_MAX_ELEMS) return hipErrorInvalidValue;
+    if (a.nTiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_record_parse_elems, dim3((unsigned)((a.nTiles + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_record_crc32c_elems(const uint8_t *blob, const uint64_t *offsets, const uint32_t *sizes, int32_t *cls, int32_t *status,
+                                         size_t nTiles, int nElems, hipStream_t stream)
+{
+    if (nTiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_record_crc32c_elems, dim3((unsigned)((nTiles + 3) / 4)), dim3(256), 0, stream, blob, offsets, sizes, cls, status,
+                       nTiles, nElems);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_elem_scatter(const GfElemScatterArgs &a, hipStream_t stream)
+{
+    if (a.nTotal == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_elem_scatter, gf_tile_grid(a.nTotal), dim3(256), 0, stream, a);
     return hipGetLastError();
 }

@@ -484,7 +484,8 @@ gf_status gf_canon_analyze_batch(gf_context *ctx, int n_rows, int n_cols, size_t
 
 /* ---- tile records (gvrs/RecordManager.java:153-204, 217-262, 386-520; gvrs/TileElementInt.java:196-219,
  * gvrs/TileElementShort.java:211-250; util/GridfourCRC32C.java): what RecordManager.writeTile appends to the file for a
- * tile of one integer-coded element, for a whole batch of dirty tiles in one call (flush()):
+ * tile of one integer-coded element, for a whole batch of dirty tiles in one call (flush()) -- tiles of several elements and of
+ * float / int-coded-float elements are read by gf_tile_record_decode_batch_elems[_dev] below:
  *   [int32 LE size, multiple of 8][type 2][0 0 0][int32 tileIndex][int32 n][n element bytes][zeros][CRC-32C | 0]
  * element bytes = CodecMaster packing, or the standard (raw little-endian) form when no codec is listed / produced a
  * packing / it is not shorter (codec_used[t] = 255).  GF_ELEM_SHORT: values are int16, widened with fill_value mapped to
@@ -532,6 +533,56 @@ gf_status gf_tile_record_decode_batch_dev(gf_context *ctx, void *stream, const i
                                           int n_rows, int n_cols, size_t n_tiles, const uint8_t *d_blob, size_t blob_bytes,
                                           const uint64_t *d_offsets, int verify_checksum, int32_t *d_tile_indices,
                                           void *d_values, int32_t *d_status);
+
+/* ---- tile records of several elements, and float / int-coded-float elements, in device memory -------------------------
+ * (gvrs/RecordManager.java:492-515, gvrs/RasterTile.java:234-256, gvrs/TileElementFloat.java:222-232,
+ * gvrs/TileElementIntCodedFloat.java:172-176, 233-244, gvrs/CodecMaster.java:195-203, 296-304)
+ * A tile has n_elems elements, each of one of the four TileElement types; its record holds, behind the tile index, per element
+ * [int32 LE n][n bytes] with no padding between elements: element 0's length word is at byte 12 of the record, element e+1's
+ * directly behind the bytes of element e.  n == standard size (4*cells for INT, FLOAT and ICF; 2*cells rounded up to 4 for SHORT)
+ * means the raw little-endian cells; anything else is a packing whose first byte names an entry of the codec list -- an integer
+ * codec for an INT, SHORT or ICF element, a GF_CODEC_NONE entry (the slot of CodecFloat) for a FLOAT element; another entry or an
+ * index outside the list is GF_ERR_FORMAT.
+ *   elems, codecs and the array d_values itself (n_elems pointers) are HOST memory; d_values[e] points to n_tiles * cells values
+ *   of element e in device memory: int32 for INT, int16 for SHORT (INT4_NULL_CODE -> -32768), float32 for FLOAT and ICF.  ICF
+ *   delivers code == fill_i ? fill_f : (float)code / scale + offset, single precision, each step rounded once.
+ *   d_status is element-major, d_status[e * n_tiles + t]; d_tile_indices may be NULL.  d_blob, d_offsets, record placement, the
+ *   bounds rule for a bad d_offsets entry and "synchronises `stream` once, not capture-safe" are exactly as for
+ *   gf_tile_record_decode_batch_dev; one partition, one count read-back and one synchronisation serve all elements, and every
+ *   codec's decoder is launched once for the packings of all elements.
+ * Per record: the record head, the type byte and (verify_checksum) the CRC-32C are judged as gf_tile_record_decode_batch_dev judges
+ * them, in its order, and a failure there is the status of EVERY element of the record.  An element whose length word or bytes
+ * do not fit the record (position + 4 + n > size) is GF_ERR_BOUNDS, and so is every element behind it, which cannot be located;
+ * the elements in front of it are decoded and keep their own status.  A decoder's verdict on one element does not change the
+ * other elements of the record.  The reference reads a tile as a whole and would throw: A TILE IS GOOD IFF ALL ITS ELEMENT
+ * STATUSES ARE GF_OK.  With n_elems == 1 and type INT or SHORT the call answers exactly as gf_tile_record_decode_batch_dev.
+ * GF_ERR_ARG, before the device is touched: null pointers (ctx, codecs with n_codecs > 0, elems, d_blob, d_offsets, d_values or
+ * one of its entries, d_status), n_elems < 1 or > GF_MAX_ELEMS, a type outside 0..3, an ICF scale that is 0 or NaN, a codec kind
+ * outside GF_CODEC_NONE .. GF_CODEC_LSOP12, n_codecs > 255, n_rows < 1, n_cols < 1, an unaligned d_blob.  GF_ERR_UNSUPPORTED:
+ * n_elems * n_tiles > 0x7fffffff.  n_tiles == 0 is GF_OK.
+ * gf_tile_record_decode_batch_elems is the same call for bytes in host memory (values[e], tile_indices, status: host arrays;
+ * offsets[n_tiles] bytes of blob are read): it stages blob and offsets into buffers of the context, calls the device form on
+ * the context's stream and copies values, indices and statuses back.  It is NOT pipelined as gf_tile_record_decode_batch is: a
+ * convenience for ctypes / JNI callers, not a rate.                                                                         */
+#define GF_ELEM_FLOAT 2   /* TileElementFloat: float32 cells; a packing is a CodecFloat packing */
+#define GF_ELEM_ICF   3   /* TileElementIntCodedFloat: stored exactly as GF_ELEM_INT, delivered as float32 */
+#define GF_MAX_ELEMS 16
+typedef struct gf_elem_spec {
+    int32_t type;      /* GF_ELEM_*                                                      */
+    int32_t fill_i;    /* ICF: fillValueI, the stored code of "no data"; otherwise ignored */
+    float scale;       /* ICF: value = code / scale + offset (TileElementIntCodedFloat.java:172-176) */
+    float offset;
+    float fill_f;      /* ICF: what a cell equal to fill_i is delivered as (may be NaN)  */
+} gf_elem_spec;
+gf_status gf_tile_record_decode_batch_elems_dev(gf_context *ctx, void *stream, const int *codecs, int n_codecs,
+                                                const gf_elem_spec *elems, int n_elems, int n_rows, int n_cols, size_t n_tiles,
+                                                const uint8_t *d_blob, size_t blob_bytes, const uint64_t *d_offsets,
+                                                int verify_checksum, int32_t *d_tile_indices, void *const *d_values,
+                                                int32_t *d_status);
+gf_status gf_tile_record_decode_batch_elems(gf_context *ctx, const int *codecs, int n_codecs, const gf_elem_spec *elems,
+                                            int n_elems, int n_rows, int n_cols, size_t n_tiles, const uint8_t *blob,
+                                            const uint64_t *offsets, int verify_checksum, int32_t *tile_indices,
+                                            void *const *values, int32_t *status);
 
 /* ---- CodecFloat (compress/CodecFloat.java:328-458): float32 tiles ---------------------------
  * The five byte planes (sign bits, exponent, three byte-delta coded mantissa bytes) are split and

@@ -8,8 +8,14 @@ Device-records mode: the same batch as tile records (gf_tile_record_encode_batch
 gf_tile_record_decode_batch_dev -- HIP events on one stream, with and without checksum verification, with and without the one
 H2D copy of the blob (from page-locked memory) -- beside the host call gf_tile_record_decode_batch in the same run:
     python tools/codec_master_rate.py --device-records [nTiles] [codec list] [--once] [--out profiles/device_records_rate.json]
+                                      [--elements short,float]
     python tools/codec_master_rate.py --merge-kernel-stats <rocprofv3 kernel_stats.csv> <the JSON written above>
-(--once: one call of each form and no timing loops, the run to put behind `rocprofv3 --kernel-trace --stats --`)"""
+(--once: one call of each form and no timing loops, the run to put behind `rocprofv3 --kernel-trace --stats --`)
+--elements LIST (int, short, float, icf; e.g. short,float) adds gf_tile_record_decode_batch_elems_dev to the same run, checksums
+verified, medians of 20 event timings with the calls taken in turn: (1) gf_tile_record_decode_batch_dev on the int records, the
+baseline, (2) the new call on the same records as one INT element -- the gate: its median within the spread (max - min) that (1)
+shows in this run --, (3) the new call on records of the listed elements, framed here from the existing encoders' packings
+(reported, not gated)."""
 import ctypes as C
 import json
 import os
@@ -122,13 +128,129 @@ def main():
     print(json.dumps(out))
 
 
-RECORD_KERNELS = ("k_record_parse", "k_record_crc32c", "k_codec_partition", "k_tile_scatter")
+RECORD_KERNELS = ("k_record_parse", "k_record_crc32c", "k_codec_partition", "k_tile_scatter", "k_record_parse_elems", "k_record_crc32c_elems",
+                  "k_elem_scatter")
+ELEM_TYPES = {"int": 0, "short": 1, "float": 2, "icf": 3}
+
+
+def _frame_records(L, elements):
+    """[record][element] bytes -> (blob, offsets) of RecordManager's framing with CRC-32C, tile index = record number"""
+    import struct
+    recs = []
+    for i, els in enumerate(elements):
+        body = b"".join(struct.pack("<i", len(el)) + el for el in els)
+        size = (4 + len(body) + 12 + 7) // 8 * 8
+        r = bytearray(size)
+        struct.pack_into("<iB3xi", r, 0, size, 2, i)
+        r[12:12 + len(body)] = body
+        struct.pack_into("<I", r, size - 4, L.gf_crc32c(C.c_char_p(bytes(r[:size - 4])), size - 4))
+        recs.append(bytes(r))
+    off = np.zeros(len(recs) + 1, np.uint64)
+    off[1:] = np.cumsum([len(r) for r in recs])
+    return np.frombuffer(b"".join(recs) + b"\0" * 64, np.uint8), off
+
+
+def _series(timer, fns, reps):
+    """event timings of several calls taken in turn, reps of each: median, extremes and the spread a call shows against itself"""
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            timer.start()
+            fn()
+            timer.stop()
+            ms[k].append(timer.elapsed_ms())
+    return {k: {"median_ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
+                "spread_ms": round(max(v) - min(v), 4), "reps": reps} for k, v in ms.items()}
+
+
+def _elements_run(L, ctx, timer, cd, codecs, names, n_rows, n_cols, vals, old_call, d_blob, total, d_off, d_idx, d_val, d_st, once):
+    from gridfour_amd.codec import _ELEM_SPEC
+    nt, cells = vals.shape
+    idx = np.arange(nt, dtype=np.int32)
+    reps = 1 if once else 20
+    # (2) the int records of the baseline as ONE INT element
+    spec1 = np.zeros(1, _ELEM_SPEC)
+    spec1["scale"] = 1.0
+    ptr1 = (C.c_void_p * 1)(d_val.ptr.value)
+
+    def one_element():
+        check(L.gf_tile_record_decode_batch_elems_dev(ctx.handle, None, cd, len(codecs), _p(spec1), 1, n_rows, n_cols, nt, d_blob.ptr, total,
+                                                      d_off.ptr, 1, d_idx.ptr, ptr1, d_st.ptr), "gf_tile_record_decode_batch_elems_dev")
+    d_val.fill(0)
+    one_element()
+    ctx.synchronize()
+    assert (d_st.download(np.int32, nt) == 0).all() and np.array_equal(d_idx.download(np.int32, nt), idx)
+    assert np.array_equal(d_val.download(np.int32, nt * cells).reshape(nt, cells), vals)
+    # (3) records of the listed elements: int-coded elements hold the batch's cells (shorts clipped), float elements a tenth of them
+    shorts = np.clip(vals, -32767, 32767).astype(np.int32)
+    floats = (vals.astype(np.float32) * np.float32(0.1)).astype(np.float32)
+    src = {"int": vals, "icf": vals, "short": shorts, "float": floats}
+    cap = nt * (5 * cells + 4096)
+    packs = {}
+    for kind in set(names):
+        blob = np.empty(cap, np.uint8)
+        off = np.zeros(nt + 1, np.uint64)
+        if kind == "float":
+            check(L.gf_float_encode_batch_f32(ctx.handle, codecs.index(0), n_rows, n_cols, nt, _p(floats), 6, _p(blob), cap, _p(off)), "float_encode")
+        else:
+            used, st = np.zeros(nt, np.uint8), np.zeros(nt, np.int32)
+            check(L.gf_codec_master_encode_batch_i32(ctx.handle, cd, len(codecs), n_rows, n_cols, nt, _p(src[kind]), _p(blob), cap, _p(off), _p(used),
+                                                     _p(st)), "codec_master_encode")
+            assert (st == 0).all()
+        packs[kind] = (blob, off)
+    std = {"int": src["int"].astype("<i4"), "icf": src["icf"].astype("<i4"), "short": shorts.astype("<i2"), "float": floats.astype("<f4")}
+    elements = []
+    for t in range(nt):
+        els = []
+        for kind in names:
+            blob, off = packs[kind]
+            pk = bytes(blob[int(off[t]):int(off[t + 1])])
+            raw = std[kind][t].tobytes()
+            els.append(pk if len(pk) < len(raw) else raw)                 # (120 x 150 cells: the short form needs no padding)
+        elements.append(els)
+    eblob, eoff = _frame_records(L, elements)
+    etotal = int(eoff[nt])
+    specs = np.zeros(len(names), _ELEM_SPEC)
+    specs["type"] = [ELEM_TYPES[k] for k in names]
+    specs["scale"], specs["fill_i"], specs["fill_f"] = 1.0, -2 ** 31, np.nan
+    dtypes = [{"int": np.int32, "short": np.int16}.get(k, np.float32) for k in names]
+    e_blob = gridfour_amd.DeviceBuffer(ctx, etotal + 64).upload(eblob[:etotal + 64])
+    e_off = gridfour_amd.DeviceBuffer(ctx, eoff.nbytes).upload(eoff)
+    e_val = [gridfour_amd.DeviceBuffer(ctx, nt * cells * np.dtype(dt).itemsize).fill(0) for dt in dtypes]
+    e_st = gridfour_amd.DeviceBuffer(ctx, len(names) * nt * 4)
+    ptrs = (C.c_void_p * len(names))(*[b.ptr.value for b in e_val])
+
+    def listed_elements():
+        check(L.gf_tile_record_decode_batch_elems_dev(ctx.handle, None, cd, len(codecs), _p(specs), len(names), n_rows, n_cols, nt, e_blob.ptr,
+                                                      etotal, e_off.ptr, 1, d_idx.ptr, ptrs, e_st.ptr), "gf_tile_record_decode_batch_elems_dev")
+    listed_elements()
+    ctx.synchronize()
+    assert (e_st.download(np.int32, len(names) * nt) == 0).all() and np.array_equal(d_idx.download(np.int32, nt), idx)
+    for k, b, dt in zip(names, e_val, dtypes):
+        got = b.download(dt, nt * cells).reshape(nt, cells)
+        want = src[k].astype(np.float32) if k == "icf" else src[k].astype(dt)
+        assert np.array_equal(got.view(np.uint8), np.ascontiguousarray(want).view(np.uint8)), k
+    res = _series(timer, {"old_call": old_call, "new_call_one_element": one_element, "new_call_elements": listed_elements}, reps)
+    gb = vals.nbytes / 1e9
+    res["old_call"]["GBps_of_cells"] = round(gb / (res["old_call"]["median_ms"] / 1e3), 2)
+    res["new_call_one_element"]["GBps_of_cells"] = round(gb / (res["new_call_one_element"]["median_ms"] / 1e3), 2)
+    cell_bytes = sum(nt * cells * np.dtype(dt).itemsize for dt in dtypes)
+    res["new_call_elements"].update({"elements": list(names), "record_bytes": etotal, "cell_bytes": cell_bytes,
+                                     "GBps_of_cells": round(cell_bytes / 1e9 / (res["new_call_elements"]["median_ms"] / 1e3), 2)})
+    gap = res["new_call_one_element"]["median_ms"] - res["old_call"]["median_ms"]
+    res["one_element_gap_ms"] = round(gap, 4)
+    res["one_element_within_old_spread"] = bool(abs(gap) <= res["old_call"]["spread_ms"])
+    for b in [e_blob, e_off, e_st] + e_val:
+        b.free()
+    return res
 
 
 def device_records(argv):
     once = "--once" in argv
     out_path = argv[argv.index("--out") + 1] if "--out" in argv else None
-    pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] != "--out")]
+    names = argv[argv.index("--elements") + 1].split(",") if "--elements" in argv else None
+    assert names is None or (names and all(k in ELEM_TYPES for k in names)), names
+    pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] not in ("--out", "--elements"))]
     nt = int(pos[0]) if pos else 12960
     codecs = [int(x) for x in (pos[1] if len(pos) > 1 else "1,2,0,3").split(",")]
     n_rows, n_cols = 120, 150
@@ -210,6 +332,10 @@ def device_records(argv):
     out["host_call_verify"] = {"wall_seconds": round(t, 5), "GBps_of_cells": round(gb / t, 2),
                                "note": "gf_tile_record_decode_batch: bytes and cells in pageable host memory, the D2H copy of the cells included"}
     out["device_with_h2d_not_slower_than_host"] = bool(out["device_verify_with_h2d"]["wall_seconds"] <= t)
+    if names:
+        upload()
+        out["elems"] = _elements_run(L, ctx, timer, cd, codecs, names, n_rows, n_cols, vals, lambda: decode(1), d_blob, total, d_off, d_idx, d_val,
+                                     d_st, once)
     L.gf_host_free(pinned)
     text = json.dumps(out)
     print(text)
@@ -220,7 +346,7 @@ def device_records(argv):
 
 
 def merge_kernel_stats(csv_path, json_path):
-    """per-kernel times of the four record kernels from one `rocprofv3 --kernel-trace --stats` run into the JSON of the mode above"""
+    """per-kernel times of the record kernels from one `rocprofv3 --kernel-trace --stats` run into the JSON of the mode above"""
     import csv
     with open(json_path) as f:
         out = json.load(f)
@@ -228,10 +354,11 @@ def merge_kernel_stats(csv_path, json_path):
     with open(csv_path, newline="") as f:
         for row in csv.DictReader(f):
             name = row.get("Name", "")
-            for k in RECORD_KERNELS:
-                if k in name:
-                    rows[k] = {"calls": int(row["Calls"]), "average_us": round(float(row["AverageNs"]) / 1e3, 2),
-                               "min_us": round(float(row["MinNs"]) / 1e3, 2), "max_us": round(float(row["MaxNs"]) / 1e3, 2)}
+            hits = [k for k in RECORD_KERNELS if k in name]
+            if hits:
+                k = max(hits, key=len)                                   # (k_record_parse is not k_record_parse_elems)
+                rows[k] = {"calls": int(row["Calls"]), "average_us": round(float(row["AverageNs"]) / 1e3, 2),
+                           "min_us": round(float(row["MinNs"]) / 1e3, 2), "max_us": round(float(row["MaxNs"]) / 1e3, 2)}
     out["kernels"] = rows
     with open(json_path, "w") as f:
         json.dump(out, f, indent=1)
