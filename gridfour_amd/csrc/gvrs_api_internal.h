@@ -166,23 +166,6 @@ struct PinBuf {
 
 void gf_rec_counts_destroy(PinBuf *p);             // (gvrs_api_records_dev.hip)
 
-// a batch of tile records or mixed-codec packings in device memory (gvrs_api_records_dev.hip)
-struct RecBatch {
-    const int *codecs;
-    int nCodecs;
-    int elemShort;
-    int nRows, nCols;
-    size_t nTiles;
-    const uint8_t *dBlob;
-    size_t blobBytes;
-    const uint64_t *dOffsets;
-    const uint32_t *dLengths;       // null: tile records
-    int verifyChecksum;
-    int32_t *dTileIndices;
-    void *dValues;
-    int32_t *dStatus;
-};
-
 // codec kinds behind the shared batch plumbing
 enum { KIND_HUFFMAN = 0, KIND_CANON = 1, KIND_RAW_M32 = 2, KIND_DEFLATE = 3, KIND_FLOAT = 4 };
 
@@ -267,8 +250,5 @@ gf_status deflateDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, 
 gf_status codecMasterDecodeScattered(gf_context *c, const int *codecs, int nCodecs, int nRows, int nCols, size_t nTiles,
                                      const uint8_t *blob, const uint64_t *starts, const uint32_t *lens, const uint8_t *skip,
                                      int32_t *values, int32_t *st);
-// gvrs_api_records_dev.hip: one integer codec's share of a batch through its device decoder (b: shape and blob)
-gf_status decodeSublist(gf_context *c, hipStream_t st, int codec, const RecBatch &b, size_t n, const uint64_t *offsets,
-                        const uint32_t *lengths, int32_t *values, int32_t *status);
 
 #pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // gvrs_crc32c.h -- CRC-32C (Castagnoli, util/GridfourCRC32C.java) arithmetic shared by the kernels that compute one with a whole
-// wave: k_lsop_value_crc (gvrs_lsop.hip) and k_record_crc32c (gvrs_records.hip).  Each lane runs its share of the bytes through
+// wave: k_lsop_value_crc (gvrs_lsop.hip) and k_record_crc32c_elems (gvrs_records.hip).  Each lane runs its share of the bytes through
 // the polynomial's byte table (in LDS, made by the workgroup) and the shares are joined by the CRC's linearity:
 //   crc(A || B) = crc(A) * x^(8 |B|)  xor  crc(B)    in GF(2)[x] modulo the (reflected) polynomial,
 // so the whole checksum is the XOR over the lanes of crc(run) * x^(8 bytes behind the run).  The multiplications are 32 steps of

@@ -411,61 +411,13 @@ struct GfM32Args {
 };
 hipError_t gf_launch_m32_streams(const GfM32Args &a, hipStream_t stream);
 
-// Tile records and mixed-codec packings in device memory (gvrs_records.hip; driven by gvrs_api_records_dev.hip).
-// A record's class after the framing walk: the index of the codec its packing names, or one of
-constexpr int32_t GF_REC_FAILED = -1;        // no element to decode or copy: the record's status says why
+// Tile records and mixed-codec packings in device memory (gvrs_records.hip; driven by gvrs_api_records_dev.hip): one pipeline of
+// k_record_parse_elems, k_record_crc32c_elems, k_codec_partition, the codecs' decoders and k_elem_scatter.  A tile record holds one
+// or more elements; every per-element array is ELEMENT-MAJOR: instance i = e * nTiles + t is element e of record t, so that
+// k_codec_partition sorts the instances of all elements in one run and a codec's decoder is launched once for all of them.
+// An instance's class after the framing walk: the index of the codec its packing names, or one of
+constexpr int32_t GF_REC_FAILED = -1;        // no element to decode or copy: the instance's status says why
 constexpr int32_t GF_REC_STANDARD = 256;     // the standard form: the element bytes are the cells themselves
-struct GfRecordParseArgs {
-    const uint8_t *blob;       // 4-byte aligned
-    size_t blobBytes;
-    const uint64_t *offsets;   // records: nTiles + 1 entries, record t = [offsets[t], offsets[t + 1]); packings: nTiles entries
-    const uint32_t *lengths;   // null: tile records with their framing; else packing t = lengths[t] bytes at offsets[t]
-    size_t nTiles;
-    uint32_t stdSize;          // bytes of an element in standard form (records); 0: there is no such form (packings)
-    int nCodecs;
-    uint64_t codecSet0, codecSet1, codecSet2, codecSet3;   // bit k: entry k of the codec list has an integer decoder
-    int32_t *tileIndices;      // may be null
-    uint64_t *starts;          // per record: where the element bytes start in the blob
-    uint32_t *lens;            // ... how many they are
-    uint32_t *sizes;           // ... the record's size field (0 in packing mode and where the framing failed before it)
-    int32_t *cls;              // ... its class
-    int32_t *status;           // ... GF_K_OK or the framing's verdict
-};
-hipError_t gf_launch_record_parse(const GfRecordParseArgs &a, hipStream_t stream);
-// the CRC-32C of every record whose class is not GF_REC_FAILED; a mismatch: status GF_K_ERR_FORMAT, class GF_REC_FAILED
-hipError_t gf_launch_record_crc32c(const uint8_t *blob, const uint64_t *starts, const uint32_t *sizes, int32_t *cls, int32_t *status,
-                                   size_t nTiles, hipStream_t stream);
-// stable partition by class: segments 0 .. nCodecs - 1 (the codecs' packings) and nCodecs (standard form) one behind the other
-struct GfPartitionArgs {
-    const int32_t *cls;
-    const uint64_t *starts;
-    const uint32_t *lens;
-    size_t nTiles;             // < 2^32
-    int nCodecs;               // <= 255
-    uint64_t *subOffsets;      // nTiles entries each
-    uint32_t *subLengths;
-    uint32_t *subDst;
-    uint32_t *counts;          // nCodecs + 1 entries
-};
-hipError_t gf_launch_codec_partition(const GfPartitionArgs &a, hipStream_t stream);
-struct GfTileScatterArgs {
-    const uint8_t *blob;
-    const int32_t *tmp;        // decoded tiles, tile j of the partition at tmp + j * cells
-    const int32_t *subStatus;  // their decoders' statuses
-    const uint64_t *subOffsets;
-    const uint32_t *subDst;
-    size_t nPacked;            // entries with a decoded tile; [nPacked, nTotal): records in standard form
-    size_t nTotal;
-    uint32_t cells;
-    int elemShort;             // values are int16 (decoded cells narrowed, raw shorts copied) instead of int32
-    void *values;
-    int32_t *status;
-};
-hipError_t gf_launch_tile_scatter(const GfTileScatterArgs &a, hipStream_t stream);
-
-// Tile records of several elements (gf_tile_record_decode_batch_elems_dev; driven by gvrs_api_records_elems.hip).  Every per-element
-// array is ELEMENT-MAJOR: instance i = e * nTiles + t is element e of record t, so that k_codec_partition sorts the instances of all
-// elements in one run and a codec's decoder is launched once for all of them.
 constexpr int GF_K_MAX_ELEMS = 16;               // (= GF_MAX_ELEMS of the C ABI)
 constexpr int GF_K_ELEM_INT = 0, GF_K_ELEM_SHORT = 1, GF_K_ELEM_FLOAT = 2, GF_K_ELEM_ICF = 3;    // (= GF_ELEM_*)
 struct GfElemDesc {            // an element of the tile, in device memory for k_elem_scatter (32 bytes)
@@ -479,7 +431,9 @@ struct GfElemDesc {            // an element of the tile, in device memory for k
 struct GfRecordParseElemsArgs {
     const uint8_t *blob;       // 4-byte aligned
     size_t blobBytes;
-    const uint64_t *offsets;   // nTiles + 1 entries, record t = [offsets[t], offsets[t + 1])
+    const uint64_t *offsets;   // records: nTiles + 1 entries, record t = [offsets[t], offsets[t + 1]); packings: nTiles entries
+    const uint32_t *lengths;   // null: tile records with their framing; else packing t = lengths[t] bytes at offsets[t]: no head, no
+                               // standard form, no tile index, one INT element
     size_t nTiles;
     int nElems;                // 1 .. GF_K_MAX_ELEMS
     uint32_t elemTypes;        // two bits per element: its GF_K_ELEM_* (no indexed kernel argument)
@@ -493,11 +447,25 @@ struct GfRecordParseElemsArgs {
     int32_t *cls;              // ... its class (GF_REC_FAILED, GF_REC_STANDARD or the index of its codec)
     int32_t *status;           // ... GF_K_OK or the framing's verdict
     uint32_t *sizes;           // per RECORD: its size field when the record is one whose checksum the host call verifies, else 0
+                               // (always 0 in packing mode)
 };
 hipError_t gf_launch_record_parse_elems(const GfRecordParseElemsArgs &a, hipStream_t stream);
 // the CRC-32C of every record with sizes[t] != 0; a mismatch: status GF_K_ERR_FORMAT, class GF_REC_FAILED for all nElems instances
 hipError_t gf_launch_record_crc32c_elems(const uint8_t *blob, const uint64_t *offsets, const uint32_t *sizes, int32_t *cls, int32_t *status,
                                          size_t nTiles, int nElems, hipStream_t stream);
+// stable partition by class: segments 0 .. nCodecs - 1 (the codecs' packings) and nCodecs (standard form) one behind the other
+struct GfPartitionArgs {
+    const int32_t *cls;
+    const uint64_t *starts;
+    const uint32_t *lens;
+    size_t nTiles;             // instances; < 2^32
+    int nCodecs;               // <= 255
+    uint64_t *subOffsets;      // nTiles entries each
+    uint32_t *subLengths;
+    uint32_t *subDst;
+    uint32_t *counts;          // nCodecs + 1 entries
+};
+hipError_t gf_launch_codec_partition(const GfPartitionArgs &a, hipStream_t stream);
 struct GfElemScatterArgs {
     const uint8_t *blob;
     const int32_t *tmp;        // decoded tiles (int32 cells or float bit patterns), entry j of the partition at tmp + j * cells

@@ -1,6 +1,9 @@
-// gvrs_records.hip -- tile records and mixed-codec packings that already lie in device memory: the framing walk, the records'
-// CRC-32C, the partition of a batch by codec and the pass that moves decoded tiles to their place (gvrs_api_records_dev.hip
-// drives them; the codecs' own decode kernels run between k_codec_partition and k_tile_scatter, untouched).
+// gvrs_records.hip -- tile records and mixed-codec packings that already lie in device memory, in the order in which
+// gvrs_api_records_dev.hip launches them: the framing walk over a record's elements (k_record_parse_elems), the records'
+// CRC-32C (k_record_crc32c_elems), the partition of all element instances by codec (k_codec_partition) and, behind the codecs'
+// own decode kernels, which run untouched, the pass that moves and converts decoded tiles to their place (k_elem_scatter).
+// A tile holds any number of TileElementInt / Short / Float / IntCodedFloat elements (RasterTile.java:234-256 loops over
+// tile.elements; TileElement*.decode); the per-element arrays are element-major (gvrs_kernels.h).
 //
 // Reference paths are relative to core/src/main/java/org/gridfour/: gvrs/RecordManager.java:456-459, 472-520 (readTile),
 // gvrs/RasterTile.java:243-253, gvrs/CodecMaster.java:195-203, gvrs/TileElementShort.java:239-246, util/GridfourCRC32C.java.
@@ -19,82 +22,118 @@ __device__ __forceinline__ uint32_t rec_le32(const uint8_t *p)
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
+// the class of a packing of n bytes that begins with the byte `first`: the index of its codec when the list has a decoder for the
+// element's type there, else GF_REC_FAILED (empty, outside the list, or an entry without such a decoder: GF_K_ERR_FORMAT)
+__device__ __forceinline__ int32_t rec_packing_class(const GfRecordParseElemsArgs &a, bool isFloat, uint32_t n, uint32_t first)
+{
+    if (n == 0u || (int)first >= a.nCodecs) return GF_REC_FAILED;
+    // (the list's decoders for this element type as a bit set in four words: no indexed kernel argument)
+    const uint64_t w = first < 64u    ? (isFloat ? a.floatSet0 : a.intSet0)
+                       : first < 128u ? (isFloat ? a.floatSet1 : a.intSet1)
+                       : first < 192u ? (isFloat ? a.floatSet2 : a.intSet2)
+                                      : (isFloat ? a.floatSet3 : a.intSet3);
+    return ((w >> (first & 63u)) & 1ull) ? (int32_t)first : GF_REC_FAILED;
+}
+
 // ------------------------------------------------------------------------------------------------
-// k_record_parse: a lane per record.  Record mode (a.lengths == nullptr): record t is blob[offsets[t] .. offsets[t + 1]); the
+// k_record_parse_elems: a lane per record.  Record mode (a.lengths == nullptr): record t is blob[offsets[t] .. offsets[t + 1]); the
 // framing rules of gf_tile_record_decode_batch in its order.  A record's first 20 bytes (the 16-byte head and the first byte of
-// the element, which names the codec of a packing) are fetched in one go -- every record that reaches them spans 20 bytes --
-// so that the checks behind them wait for memory once.  Packing mode: packing t is lengths[t] bytes at offsets[t].
-// Per record: where its element bytes start, how many they are, the record's size (for k_record_crc32c) and its class -- failed,
-// the standard form, or the index of its codec -- and the status (GF_K_OK for a packing until its decoder has spoken).
+// element 0, which names the codec of a packing) are fetched in one go -- every record that reaches them spans 20 bytes -- so
+// that the checks behind them wait for memory once; a head that fails gives every element that status.  Then the short serial
+// walk over the elements' length words: element 0's at byte 12, each next one directly behind the bytes of the one before, at any
+// byte address.  An element whose length word or bytes do not fit the record is GF_K_ERR_BOUNDS, and so is every element behind it
+// (they cannot be located); the ones in front keep their own class.  A packing of an INT, SHORT or ICF element must name an
+// integer codec of the list, a packing of a FLOAT element an entry that is GF_CODEC_NONE (the slot of CodecFloat).
+// Per instance: where its element bytes start, how many they are, its class -- failed, the standard form, or the index of its
+// codec -- and the status (GF_K_OK for a packing until its decoder has spoken).  sizes[t] != 0 marks the records whose checksum the
+// host call would look at: the head passed and element 0 fits (gf_tile_record_decode_batch's order).
+// Packing mode (a.lengths != nullptr, one INT element): packing t is lengths[t] bytes at offsets[t] -- no head, no standard form,
+// no tile index, sizes[t] = 0.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_record_parse(const GfRecordParseArgs a)
+__global__ __launch_bounds__(256) void k_record_parse_elems(const GfRecordParseElemsArgs a)
 {
     const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (t >= a.nTiles) return;
     const uint8_t *__restrict__ blob = a.blob;
-    int32_t st = GF_K_OK, cls = GF_REC_FAILED;
-    uint64_t start = 0;
-    uint32_t n = 0, size = 0, first = 0;
-    bool element = false;                                  // the element bytes lie inside the blob: classify them
     if (a.lengths) {
-        start = a.offsets[t];
-        n = a.lengths[t];
+        const uint64_t start = a.offsets[t];
+        const uint32_t n = a.lengths[t];
+        int32_t st = GF_K_OK, cls = GF_REC_FAILED;
         if (start > a.blobBytes || (uint64_t)n > a.blobBytes - start) st = GF_K_ERR_BOUNDS;
         else {
-            element = true;
-            if (n) first = blob[start];
+            cls = rec_packing_class(a, false, n, n ? blob[start] : 0u);
+            if (cls == GF_REC_FAILED) st = GF_K_ERR_FORMAT;
         }
-    } else {
-        const uint64_t o0 = a.offsets[t], o1 = a.offsets[t + 1];
-        if (o0 > o1 || o1 > a.blobBytes || o1 - o0 < 20u) st = GF_K_ERR_BOUNDS;      // (nothing of such a record is read)
-        else {
-            const uint8_t *r = blob + o0;
-            uint32_t h0, h1, h2, h3, h4;
-            if ((o0 & 3u) == 0u) {
-                const GfU4 q = *reinterpret_cast<const GfU4 *>(r);
-                h4 = *reinterpret_cast<const uint32_t *>(r + 16);
-                h0 = q.x, h1 = q.y, h2 = q.z, h3 = q.w;
-            } else {
-                h0 = rec_le32(r), h1 = rec_le32(r + 4), h2 = rec_le32(r + 8), h3 = rec_le32(r + 12), h4 = r[16];
-            }
-            size = h0;
-            if ((uint64_t)size > o1 - o0 || size < 20u || (size & 7u)) st = GF_K_ERR_BOUNDS;
-            else if ((h1 & 0xffu) != 2u) st = GF_K_ERR_FORMAT;                        // not RecordType.Tile
-            else {
-                if (a.tileIndices) a.tileIndices[t] = (int32_t)h2;
-                n = h3;
-                if (16ull + n > size) st = GF_K_ERR_BOUNDS;
+        a.starts[t] = start;
+        a.lens[t] = n;
+        a.cls[t] = cls;
+        a.status[t] = st;
+        a.sizes[t] = 0u;
+        return;
+    }
+    const uint64_t o0 = a.offsets[t], o1 = a.offsets[t + 1];
+    int32_t headSt = GF_K_OK;
+    uint32_t size = 0, h3 = 0, h4 = 0;
+    if (o0 > o1 || o1 > a.blobBytes || o1 - o0 < 20u) headSt = GF_K_ERR_BOUNDS;          // (nothing of such a record is read)
+    else {
+        const uint8_t *r = blob + o0;
+        uint32_t h0, h1, h2;
+        if ((o0 & 3u) == 0u) {
+            const GfU4 q = *reinterpret_cast<const GfU4 *>(r);
+            h4 = *reinterpret_cast<const uint32_t *>(r + 16);
+            h0 = q.x, h1 = q.y, h2 = q.z, h3 = q.w;
+        } else {
+            h0 = rec_le32(r), h1 = rec_le32(r + 4), h2 = rec_le32(r + 8), h3 = rec_le32(r + 12), h4 = r[16];
+        }
+        size = h0;
+        if ((uint64_t)size > o1 - o0 || size < 20u || (size & 7u)) headSt = GF_K_ERR_BOUNDS;
+        else if ((h1 & 0xffu) != 2u) headSt = GF_K_ERR_FORMAT;                            // not RecordType.Tile
+        else if (a.tileIndices) a.tileIndices[t] = (int32_t)h2;
+    }
+    const uint8_t *r = blob + o0;
+    bool located = headSt == GF_K_OK;                       // the next element's length word is known to be at r + pos
+    uint32_t pos = 12, crcSize = 0;
+    for (int e = 0; e < a.nElems; e++) {
+        int32_t st = headSt, cls = GF_REC_FAILED;
+        uint64_t start = 0;
+        uint32_t n = 0;
+        if (headSt == GF_K_OK) {
+            st = GF_K_ERR_BOUNDS;
+            if (located && (uint64_t)pos + 4u <= size) n = e == 0 ? h3 : rec_le32(r + pos);
+            else located = false;
+            if (located && (uint64_t)pos + 4u + n > size) located = false;
+            if (located) {
+                const uint32_t type = (a.elemTypes >> (2 * e)) & 3u;
+                // TileElement.java:86-93: bytes per sample * cells, rounded up to a multiple of 4
+                const uint32_t stdSize = type == (uint32_t)GF_K_ELEM_SHORT ? ((a.cells * 2u + 3u) & ~3u) : a.cells * 4u;
+                start = o0 + pos + 4u;
+                st = GF_K_OK;
+                if (e == 0) crcSize = size;
+                if (n == stdSize) cls = GF_REC_STANDARD;
                 else {
-                    element = true;
-                    start = o0 + 16u;
-                    first = h4 & 0xffu;
+                    const uint32_t first = n == 0u ? 0u : e == 0 ? (h4 & 0xffu) : (uint32_t)r[pos + 4u];
+                    cls = rec_packing_class(a, type == (uint32_t)GF_K_ELEM_FLOAT, n, first);
+                    if (cls == GF_REC_FAILED) st = GF_K_ERR_FORMAT;
                 }
+                pos += 4u + n;
             }
         }
+        const size_t i = (size_t)e * a.nTiles + t;
+        a.starts[i] = start;
+        a.lens[i] = n;
+        a.cls[i] = cls;
+        a.status[i] = st;
     }
-    if (element) {
-        if (a.stdSize && n == a.stdSize) cls = GF_REC_STANDARD;
-        else if (a.nCodecs < 1 || n == 0u || (int)first >= a.nCodecs) st = GF_K_ERR_FORMAT;
-        else {
-            // (the list's integer codecs as a bit set in four words: no indexed kernel argument)
-            const uint64_t w = first < 64u ? a.codecSet0 : first < 128u ? a.codecSet1 : first < 192u ? a.codecSet2 : a.codecSet3;
-            if ((w >> (first & 63u)) & 1ull) cls = (int32_t)first;
-            else st = GF_K_ERR_FORMAT;                                              // an entry without an integer decoder
-        }
-    }
-    a.starts[t] = start;
-    a.lens[t] = n;
-    a.sizes[t] = size;
-    a.cls[t] = cls;
-    a.status[t] = st;
+    a.sizes[t] = crcSize;
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_record_crc32c: a wave per record that passed the framing (class not failed): the CRC-32C of its first size - 4 bytes against
+// k_record_crc32c_elems: verification only.  A wave per record with sizes[t] != 0: the CRC-32C of its first size - 4 bytes against
 // the stored one in its last four.  Lane l takes the l-th of 64 runs (a multiple of 16 bytes each) through the byte table in
 // LDS; the runs are joined as gvrs_crc32c.h says.  A record that starts at a multiple of 4 (file records start at multiples of
-// 8) is read in 16-byte and 4-byte pieces, any other byte by byte.  Nothing outside [start - 16, start - 16 + size) is read.
-// A mismatch makes the record GF_K_ERR_FORMAT and takes it out of the partition.
+// 8) is read in 16-byte and 4-byte pieces, any other byte by byte.  Nothing outside [offsets[t], offsets[t] + size) is read.
+// A mismatch reaches all nElems instances of the record (lane e writes element e's): class failed -- out of the partition --
+// and GF_K_ERR_FORMAT, whatever the walk said about them.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t crc_word(const uint32_t *table, uint32_t crc, uint32_t w)
 {
@@ -106,18 +145,20 @@ __device__ __forceinline__ uint32_t crc_word(const uint32_t *table, uint32_t crc
     return crc;
 }
 
-__global__ __launch_bounds__(256) void k_record_crc32c(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ starts,
-                                                       const uint32_t *__restrict__ sizes, int32_t *__restrict__ cls,
-                                                       int32_t *__restrict__ status, size_t nTiles)
+__global__ __launch_bounds__(256) void k_record_crc32c_elems(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets,
+                                                             const uint32_t *__restrict__ sizes, int32_t *__restrict__ cls,
+                                                             int32_t *__restrict__ status, size_t nTiles, int nElems)
 {
     __shared__ uint32_t table[256];
     table[threadIdx.x] = crc_table_entry(threadIdx.x);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     const size_t t = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (t >= nTiles || cls[t] == GF_REC_FAILED) return;
-    const uint64_t o0 = starts[t] - 16u;
-    const uint32_t size = sizes[t], nBytes = size - 4u;
+    if (t >= nTiles) return;
+    const uint32_t size = sizes[t];
+    if (size == 0u) return;
+    const uint64_t o0 = offsets[t];
+    const uint32_t nBytes = size - 4u;
     const uint8_t *__restrict__ r = blob + o0;
     const uint32_t per = ((nBytes + 63u) / 64u + 15u) & ~15u, begin = min(nBytes, lane * per), end = min(nBytes, begin + per);
     uint32_t crc = 0xffffffffu, i = begin;
@@ -136,9 +177,9 @@ __global__ __launch_bounds__(256) void k_record_crc32c(const uint8_t *__restrict
     uint32_t part = crc_mulmod(crc_xpow8n(nBytes - end), crc);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
-    if (lane == 0 && part != rec_le32(r + nBytes)) {
-        status[t] = GF_K_ERR_FORMAT;
-        cls[t] = GF_REC_FAILED;
+    if ((int)lane < nElems && part != rec_le32(r + nBytes)) {
+        status[(size_t)lane * nTiles + t] = GF_K_ERR_FORMAT;
+        cls[(size_t)lane * nTiles + t] = GF_REC_FAILED;
     }
 }
 
@@ -219,11 +260,12 @@ __global__ __launch_bounds__(PART_THREADS) void k_codec_partition(const GfPartit
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_tile_scatter: a workgroup per entry of the partition.  Entries below nPacked are decoded tiles: tile j of the temporary goes
-// to tile subDst[j] of the caller's array (int32 as it is; short elements narrowed, INT4_NULL_CODE -> -32768) when its decoder
-// said GF_K_OK, and the decoder's status to status[subDst[j]].  The entries behind them are records in standard form: their
-// element bytes are the cells (4 * cells bytes, or 2 * cells for shorts), copied from wherever they lie in the blob.  Pure
-// bandwidth: 16 bytes per lane and instruction wherever source, destination and length allow.
+// k_elem_scatter: a workgroup per entry of the partition; the entry's instance number says which element of which record it is.
+// Decoded tiles (entries below nPacked) go from the temporary to their place when their decoder said GF_K_OK: INT and FLOAT cells
+// copied, SHORT narrowed (INT4_NULL_CODE -> -32768), ICF converted; the decoder's status to status[instance].  The entries behind
+// them are elements in standard form: INT, FLOAT and SHORT cells copied from wherever they lie in the blob, ICF converted from
+// raw little-endian ints at any byte alignment.  Every path issues its loads before its stores and leaves the wave in rows of
+// 16 (8, 4, 2) bytes per lane (DESIGN section 8 on requests and on loads queued behind stores).
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void rec_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, size_t nBytes)
 {
@@ -249,171 +291,6 @@ __device__ __forceinline__ uint32_t rec_narrow2(uint32_t lo, uint32_t hi)     //
     return lo | (hi << 16);
 }
 
-__global__ __launch_bounds__(256) void k_tile_scatter(const GfTileScatterArgs a)
-{
-    GF_FOR_WG_TILE(j, a.nTotal)
-    {
-        const size_t dst = a.subDst[j], cells = a.cells;
-        if (j >= a.nPacked) {
-            const size_t nBytes = cells * (a.elemShort ? 2u : 4u);
-            rec_copy(reinterpret_cast<uint8_t *>(a.values) + dst * nBytes, a.blob + a.subOffsets[j], nBytes);
-            continue;
-        }
-        const int32_t st = a.subStatus[j];
-        if (threadIdx.x == 0) a.status[dst] = st;
-        if (st != GF_K_OK) continue;
-        const int32_t *__restrict__ src = a.tmp + j * cells;
-        if (!a.elemShort) {
-            rec_copy(reinterpret_cast<uint8_t *>(a.values) + dst * cells * 4u, reinterpret_cast<const uint8_t *>(src), cells * 4u);
-            continue;
-        }
-        int16_t *__restrict__ out = reinterpret_cast<int16_t *>(a.values) + dst * cells;
-        if ((cells & 7u) == 0u && (((uintptr_t)out | (uintptr_t)src) & 15u) == 0u) {
-            for (size_t i = (size_t)threadIdx.x * 8u; i < cells; i += 256u * 8u) {
-                const uint4 p = *reinterpret_cast<const uint4 *>(src + i), q = *reinterpret_cast<const uint4 *>(src + i + 4);
-                uint4 o;
-                o.x = rec_narrow2(p.x, p.y), o.y = rec_narrow2(p.z, p.w), o.z = rec_narrow2(q.x, q.y), o.w = rec_narrow2(q.z, q.w);
-                *reinterpret_cast<uint4 *>(out + i) = o;
-            }
-        } else {
-            for (size_t i = threadIdx.x; i < cells; i += 256u) {
-                const int32_t v = src[i];
-                out[i] = v == (int32_t)GF_NULL_CODE ? (int16_t)-32768 : (int16_t)v;
-            }
-        }
-    }
-}
-
-// ================================================================================================
-// Tile records of several elements (gf_tile_record_decode_batch_elems_dev): TileElementInt / Short / Float / IntCodedFloat, any
-// number of them per tile (RasterTile.java:234-256 loops over tile.elements; TileElement*.decode).  The per-element arrays are
-// element-major (gvrs_kernels.h), k_codec_partition runs over them unchanged.
-// ================================================================================================
-
-// k_record_parse_elems: a lane per record.  The record's head exactly as k_record_parse fetches and judges it (a head that fails
-// gives every element that status), then the short serial walk over the elements' length words: element 0's at byte 12, each next
-// one directly behind the bytes of the one before, at any byte address.  An element whose length word or bytes do not fit the
-// record is GF_K_ERR_BOUNDS, and so is every element behind it (they cannot be located); the ones in front keep their own class.
-// A packing of an INT, SHORT or ICF element must name an integer codec of the list, a packing of a FLOAT element an entry that is
-// GF_CODEC_NONE (the slot of CodecFloat).  sizes[t] != 0 marks the records whose checksum the host call would look at: the head
-// passed and element 0 fits (gf_tile_record_decode_batch's order).
-__global__ __launch_bounds__(256) void k_record_parse_elems(const GfRecordParseElemsArgs a)
-{
-    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (t >= a.nTiles) return;
-    const uint8_t *__restrict__ blob = a.blob;
-    const uint64_t o0 = a.offsets[t], o1 = a.offsets[t + 1];
-    int32_t headSt = GF_K_OK;
-    uint32_t size = 0, h3 = 0, h4 = 0;
-    if (o0 > o1 || o1 > a.blobBytes || o1 - o0 < 20u) headSt = GF_K_ERR_BOUNDS;          // (nothing of such a record is read)
-    else {
-        const uint8_t *r = blob + o0;
-        uint32_t h0, h1, h2;
-        if ((o0 & 3u) == 0u) {
-            const GfU4 q = *reinterpret_cast<const GfU4 *>(r);
-            h4 = *reinterpret_cast<const uint32_t *>(r + 16);
-            h0 = q.x, h1 = q.y, h2 = q.z, h3 = q.w;
-        } else {
-            h0 = rec_le32(r), h1 = rec_le32(r + 4), h2 = rec_le32(r + 8), h3 = rec_le32(r + 12), h4 = r[16];
-        }
-        size = h0;
-        if ((uint64_t)size > o1 - o0 || size < 20u || (size & 7u)) headSt = GF_K_ERR_BOUNDS;
-        else if ((h1 & 0xffu) != 2u) headSt = GF_K_ERR_FORMAT;                            // not RecordType.Tile
-        else if (a.tileIndices) a.tileIndices[t] = (int32_t)h2;
-    }
-    const uint8_t *r = blob + o0;
-    bool located = headSt == GF_K_OK;                       // the next element's length word is known to be at r + pos
-    uint32_t pos = 12, crcSize = 0;
-    for (int e = 0; e < a.nElems; e++) {
-        int32_t st = headSt, cls = GF_REC_FAILED;
-        uint64_t start = 0;
-        uint32_t n = 0;
-        if (headSt == GF_K_OK) {
-            st = GF_K_ERR_BOUNDS;
-            if (located && (uint64_t)pos + 4u <= size) n = e == 0 ? h3 : rec_le32(r + pos);
-            else located = false;
-            if (located && (uint64_t)pos + 4u + n > size) located = false;
-            if (located) {
-                const uint32_t type = (a.elemTypes >> (2 * e)) & 3u;
-                // TileElement.java:86-93: bytes per sample * cells, rounded up to a multiple of 4
-                const uint32_t stdSize = type == (uint32_t)GF_K_ELEM_SHORT ? ((a.cells * 2u + 3u) & ~3u) : a.cells * 4u;
-                start = o0 + pos + 4u;
-                st = GF_K_OK;
-                if (e == 0) crcSize = size;
-                if (n == stdSize) cls = GF_REC_STANDARD;
-                else if (a.nCodecs < 1 || n == 0u) st = GF_K_ERR_FORMAT;
-                else {
-                    const uint32_t first = e == 0 ? (h4 & 0xffu) : (uint32_t)r[pos + 4u];
-                    const bool f = type == (uint32_t)GF_K_ELEM_FLOAT;
-                    // (the list's decoders for this element type as a bit set in four words: no indexed kernel argument)
-                    const uint64_t w = first < 64u    ? (f ? a.floatSet0 : a.intSet0)
-                                       : first < 128u ? (f ? a.floatSet1 : a.intSet1)
-                                       : first < 192u ? (f ? a.floatSet2 : a.intSet2)
-                                                      : (f ? a.floatSet3 : a.intSet3);
-                    if ((int)first < a.nCodecs && ((w >> (first & 63u)) & 1ull)) cls = (int32_t)first;
-                    else st = GF_K_ERR_FORMAT;                                      // outside the list, or no decoder for this type
-                }
-                pos += 4u + n;
-            }
-        }
-        const size_t i = (size_t)e * a.nTiles + t;
-        a.starts[i] = start;
-        a.lens[i] = n;
-        a.cls[i] = cls;
-        a.status[i] = st;
-    }
-    a.sizes[t] = crcSize;
-}
-
-// k_record_crc32c_elems: k_record_crc32c for records of several elements -- a wave per record with sizes[t] != 0, the record's
-// origin from the offsets, the same runs.  A mismatch reaches all nElems instances of the record (lane e writes element e's):
-// class failed, GF_K_ERR_FORMAT, whatever the walk said about them.
-__global__ __launch_bounds__(256) void k_record_crc32c_elems(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets,
-                                                             const uint32_t *__restrict__ sizes, int32_t *__restrict__ cls,
-                                                             int32_t *__restrict__ status, size_t nTiles, int nElems)
-{
-    __shared__ uint32_t table[256];
-    table[threadIdx.x] = crc_table_entry(threadIdx.x);
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    const size_t t = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (t >= nTiles) return;
-    const uint32_t size = sizes[t];
-    if (size == 0u) return;
-    const uint64_t o0 = offsets[t];
-    const uint32_t nBytes = size - 4u;
-    const uint8_t *__restrict__ r = blob + o0;
-    const uint32_t per = ((nBytes + 63u) / 64u + 15u) & ~15u, begin = min(nBytes, lane * per), end = min(nBytes, begin + per);
-    uint32_t crc = 0xffffffffu, i = begin;
-    if ((o0 & 3u) == 0u) {
-        for (; i + 16u <= end; i += 16u) {
-            const GfU4 q = *reinterpret_cast<const GfU4 *>(r + i);
-            crc = crc_word(table, crc, q.x);
-            crc = crc_word(table, crc, q.y);
-            crc = crc_word(table, crc, q.z);
-            crc = crc_word(table, crc, q.w);
-        }
-        for (; i + 4u <= end; i += 4u) crc = crc_word(table, crc, *reinterpret_cast<const uint32_t *>(r + i));
-    }
-    for (; i < end; i++) crc = table[(crc ^ r[i]) & 0xffu] ^ (crc >> 8);
-    crc ^= 0xffffffffu;                                                       // the run's own checksum (an empty run: 0)
-    uint32_t part = crc_mulmod(crc_xpow8n(nBytes - end), crc);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
-    if ((int)lane < nElems && part != rec_le32(r + nBytes)) {
-        status[(size_t)lane * nTiles + t] = GF_K_ERR_FORMAT;
-        cls[(size_t)lane * nTiles + t] = GF_REC_FAILED;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_elem_scatter: a workgroup per entry of the partition; the entry's instance number says which element of which record it is.
-// Decoded tiles (entries below nPacked) go from the temporary to their place when their decoder said GF_K_OK: INT and FLOAT cells
-// copied, SHORT narrowed as k_tile_scatter does, ICF converted; the decoder's status to status[instance].  The entries behind
-// them are elements in standard form: INT, FLOAT and SHORT cells copied from wherever they lie in the blob, ICF converted from
-// raw little-endian ints at any byte alignment.  Every path issues its loads before its stores and leaves the wave in rows of
-// 16 (8, 4, 2) bytes per lane (DESIGN section 8 on requests and on loads queued behind stores).
-// ------------------------------------------------------------------------------------------------
 // TileElementIntCodedFloat.java:172-176: values[index] / scale + offset in single precision, each step rounded once
 __device__ __forceinline__ uint32_t rec_icf(uint32_t code, const GfElemDesc &d)
 {
@@ -452,7 +329,7 @@ __device__ __forceinline__ void rec_icf_tile(uint32_t *__restrict__ dst, const u
     }
 }
 
-// decoded cells -> shorts (TileElementShort.java:239-246), as k_tile_scatter narrows them
+// decoded cells -> shorts (TileElementShort.java:239-246)
 __device__ __forceinline__ void rec_narrow_tile(int16_t *__restrict__ out, const int32_t *__restrict__ src, uint32_t cells)
 {
     if ((cells & 7u) == 0u && (((uintptr_t)out | (uintptr_t)src) & 15u) == 0u) {
@@ -496,38 +373,10 @@ __global__ __launch_bounds__(256, 8) void k_elem_scatter(const GfElemScatterArgs
 
 }  // namespace
 
-hipError_t gf_launch_record_parse(const GfRecordParseArgs &a, hipStream_t stream)
-{
-    if (a.nTiles == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_record_parse, dim3((unsigned)((a.nTiles + 255) / 256)), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t gf_launch_record_crc32c(const uint8_t *blob, const uint64_t *starts, const uint32_t *sizes, int32_t *cls, int32_t *status,
-                                   size_t nTiles, hipStream_t stream)
-{
-    if (nTiles == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_record_crc32c, dim3((unsigned)((nTiles + 3) / 4)), dim3(256), 0, stream, blob, starts, sizes, cls, status, nTiles);
-    return hipGetLastError();
-}
-
-hipError_t gf_launch_codec_partition(const GfPartitionArgs &a, hipStream_t stream)
-{
-    if (a.nCodecs < 0 || a.nCodecs > 255) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_codec_partition, dim3(1), dim3(PART_THREADS), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t gf_launch_tile_scatter(const GfTileScatterArgs &a, hipStream_t stream)
-{
-    if (a.nTotal == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_tile_scatter, gf_tile_grid(a.nTotal), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
 hipError_t gf_launch_record_parse_elems(const GfRecordParseElemsArgs &a, hipStream_t stream)
 {
     if (a.nElems < 1 || a.nElems > GF_K_MAX_ELEMS) return hipErrorInvalidValue;
+    if (a.lengths && (a.nElems != 1 || a.elemTypes != (uint32_t)GF_K_ELEM_INT)) return hipErrorInvalidValue;
     if (a.nTiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_record_parse_elems, dim3((unsigned)((a.nTiles + 255) / 256)), dim3(256), 0, stream, a);
     return hipGetLastError();
@@ -539,6 +388,13 @@ hipError_t gf_launch_record_crc32c_elems(const uint8_t *blob, const uint64_t *of
     if (nTiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_record_crc32c_elems, dim3((unsigned)((nTiles + 3) / 4)), dim3(256), 0, stream, blob, offsets, sizes, cls, status,
                        nTiles, nElems);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_codec_partition(const GfPartitionArgs &a, hipStream_t stream)
+{
+    if (a.nCodecs < 0 || a.nCodecs > 255) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_codec_partition, dim3(1), dim3(PART_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -54,6 +54,20 @@ def _frame(index, element, crc=True):
     return bytes(r)
 
 
+def _frame_elems(index, elements, crc=True, size=None):
+    """RecordManager's framing of a tile of several elements: size, type 2, index, per element [n][bytes], padding, CRC-32C"""
+    body = b"".join(struct.pack("<i", len(el)) + el for el in elements)
+    if size is None:
+        size = (4 + len(body) + 12 + 7) // 8 * 8
+    r = bytearray(max(size, 12 + len(body)))
+    struct.pack_into("<iB3xi", r, 0, size, 2, index)
+    r[12:12 + len(body)] = body
+    r = r[:size]
+    if crc:
+        struct.pack_into("<I", r, size - 4, _crc(r[:size - 4]))
+    return bytes(r)
+
+
 def _refresh_crc(r):
     size = len(r)
     r = bytearray(r)
@@ -65,6 +79,23 @@ def _concat(records):
     offsets = np.zeros(len(records) + 1, np.uint64)
     offsets[1:] = np.cumsum([len(r) for r in records])
     return np.frombuffer(b"".join(records) + b"\0" * 16, np.uint8)[:int(offsets[-1])], offsets
+
+
+def _shifted(records, seed):
+    """record i at a byte offset = i mod 8 with filler in front of it and behind the last one (a record's span runs through the filler)"""
+    rng = np.random.default_rng(seed)
+    parts, offsets, pos = [], [], 0
+    for i, rec in enumerate(records):
+        gap = int(rng.integers(1, 24))
+        gap += (i % 8 - (pos + gap)) % 8
+        parts.append(bytes(rng.integers(1, 256, gap, dtype=np.uint8)))
+        pos += gap
+        offsets.append(pos)
+        parts.append(rec)
+        pos += len(rec)
+    parts.append(bytes(rng.integers(1, 256, 13, dtype=np.uint8)))
+    offsets.append(pos + 13)
+    return np.frombuffer(b"".join(parts), np.uint8), np.array(offsets, np.uint64)
 
 
 def _host_records(master, nr, nc, blob, offsets, element, verify):
@@ -489,12 +520,74 @@ def test_context_reuse_and_buffer_growth(mixed_int):
     first = master.record_blob_dev(NR, NC, blob, offsets, verify_checksums=True)
     assert (first[2] == 0).all() and np.array_equal(first[1], tiles)
     again = master.record_blob_dev(NR, NC, blob, offsets, verify_checksums=True)
+    # the three device entry points carve the same scratch buffers: several elements (one record holding the same element three
+    # times), then packings without framing, between the one-element calls
+    triple = [_frame_elems(7 * i, [el, el, el]) for i, el in enumerate(elements)]
+    t_blob, t_offsets = _concat(triple)
+    _, t_vals, t_st = master.record_blob_elems_dev(NR, NC, t_blob, t_offsets, ["int", "int", "int"], verify_checksums=True)
+    assert (t_st == 0).all() and all(np.array_equal(v, tiles) for v in t_vals)
+    packs = [el for el in elements if len(el) != NR * NC * 4]
+    p_vals, p_st = master.decode_batch_dev(NR, NC, packs)
+    assert (p_st == 0).all() and np.array_equal(p_vals, tiles[[len(el) != NR * NC * 4 for el in elements]])
     big_records, big_tiles = _alternating(ctx, 257, 64, 64, (0, 3, None, 4, 1))
     big_blob, big_offsets = _concat(big_records)
     idx, vals, st = master.record_blob_dev(64, 64, big_blob, big_offsets, verify_checksums=True)
     assert (st == 0).all() and np.array_equal(vals, big_tiles)
+    _, t_vals, t_st = master.record_blob_elems_dev(NR, NC, t_blob, t_offsets, ["int", "int", "int"], verify_checksums=True)
+    assert (t_st == 0).all() and all(np.array_equal(v, tiles) for v in t_vals)
     third = master.record_blob_dev(NR, NC, blob, offsets, verify_checksums=True)
     for a, b, c in zip(first, again, third):
         assert np.array_equal(a, b) and np.array_equal(a, c)
     assert np.array_equal(huff.decode(NR, NC, pk), one)
     ctx.close()
+
+
+# ---------------------------------------------------------------- 9. the scatter route at small shapes
+
+SMALL = [(1, 1), (5, 5), (7, 9), (40, 60)]
+
+
+@pytest.mark.parametrize("element", ["int", "short"])
+@pytest.mark.parametrize("nr,nc", SMALL)
+def test_scatter_route_at_small_shapes(ctx, master5, nr, nc, element):
+    """a mixed batch (temporary + scatter) through the one-element entry points where cells is no multiple of 8 and a tile's bytes
+    no multiple of 16: the scalar narrowing loop and the 8-, 4- and 1-byte copies of the scatter kernel.  Twenty records at byte
+    offsets of every residue mod 8: four tiles offered to each integer codec of LIST5 (one that declines the shape or does not
+    shorten the tile leaves it in standard form), three in standard form, one more whose stored checksum has a flipped bit."""
+    import gridfour_amd
+    cells, short = nr * nc, element == "short"
+    std = (2 * cells + 3) & ~3 if short else 4 * cells
+    kinds = ["smooth", "uniform", "noise8", "steps", "ramp"]
+    tiles = np.stack([make_tile(kinds[i % 5], nr, nc, seed=500 + i) for i in range(19)]).astype(np.int32)
+    if short:
+        tiles = np.clip(tiles, -32767, 32767)
+    tiles[2, 0] = tiles[11, cells // 2] = tiles[17, cells - 1] = NULL
+    enc = {0: gridfour_amd.CodecHuffmanHip(context=ctx), 1: gridfour_amd.CodecDeflateHip(context=ctx),
+           3: gridfour_amd.CodecCanonHuffmanHip(context=ctx), 4: gridfour_amd.LsCodecHip(context=ctx)}
+    packings = sum((codec.encode_batch(slot, nr, nc, tiles[4 * k:4 * k + 4])[0] for k, (slot, codec) in enumerate(enc.items())), []) + [None] * 3
+    elements = []
+    for tile, pk in zip(tiles, packings):
+        if pk is not None and len(pk) < std:
+            elements.append(pk)
+        elif short:
+            elements.append(np.where(tile == NULL, -32768, tile).astype("<i2").tobytes() + b"\0" * (std - 2 * cells))
+        else:
+            elements.append(tile.astype("<i4").tobytes())
+    n_packed = sum(len(el) != std for el in elements)
+    assert n_packed <= 16 and (n_packed >= 1 or (nr, nc) == (1, 1)), n_packed      # (and at least three in standard form)
+    records = [_frame(300 + 5 * i, el) for i, el in enumerate(elements)]
+    records.append(_flip(records[-1], len(records[-1]) - 2, 4))
+    blob, offsets = _shifted(records, seed=cells)
+    assert {int(o) % 8 for o in offsets[:-1]} == set(range(8))
+    want = np.where(tiles == NULL, -32768, tiles).astype(np.int16) if short else tiles
+    for verify in (True, False):
+        idx, vals, st = _same_as_host(master5, nr, nc, blob, offsets, element, verify, (nr, nc))
+        assert list(st) == [0] * 19 + [-1 if verify else 0], st
+        assert list(idx) == [300 + 5 * i for i in range(19)] + [300 + 5 * 18]
+        assert np.array_equal(vals[:19], want) and (not verify or (vals[19] == 0).all())
+    packs = [el for el in elements if len(el) != std]
+    if packs:
+        hv, hs = master5.decode_batch(nr, nc, packs)
+        dv, ds = master5.decode_batch_dev(nr, nc, packs)
+        assert (hs == 0).all() and np.array_equal(ds, hs) and np.array_equal(dv, hv)
+        assert np.array_equal(dv, tiles[[len(el) != std for el in elements]])

@@ -1,7 +1,7 @@
 """Tile records of several elements and of float / int-coded-float elements (gf_tile_record_decode_batch_elems_dev and its host
-form): the reference's own sample files; one element against gf_tile_record_decode_batch_dev; three elements framed here from
-the existing encoders' packings against the existing host decoders; the ICF arithmetic bit for bit against numpy float32;
-damaged records; the host form against the device form."""
+form): the reference's own sample files; one element, and gf_tile_record_decode_batch_dev beside it, against the host call
+gf_tile_record_decode_batch; three elements framed here from the existing encoders' packings against the existing host decoders;
+the ICF arithmetic bit for bit against numpy float32; damaged records; the host form against the device form."""
 import itertools
 import os
 import struct
@@ -11,7 +11,7 @@ import pytest
 
 import damage as D
 from gvrs_walk import walk_records
-from test_gpu_records_dev import LIST5, NC, NR, _concat, _crc, _flip, _put32, _refresh_crc
+from test_gpu_records_dev import LIST5, NC, NR, _concat, _crc, _flip, _frame_elems, _host_records, _put32, _refresh_crc, _shifted
 from test_gpu_records_dev import ctx, master5, mixed_int, mixed_short      # noqa: F401  (fixtures)
 from tilegen import make_tile
 
@@ -33,37 +33,6 @@ def _icf_expect(codes, el):
     with np.errstate(all="ignore"):
         v = codes.astype(np.float32) / np.float32(scale) + np.float32(offset)
     return np.where(codes == np.int32(fill_i), np.float32(fill_f), v).astype(np.float32)
-
-
-def _frame_elems(index, elements, crc=True, size=None):
-    """RecordManager's framing of a tile of several elements: size, type 2, index, per element [n][bytes], padding, CRC-32C"""
-    body = b"".join(struct.pack("<i", len(el)) + el for el in elements)
-    if size is None:
-        size = (4 + len(body) + 12 + 7) // 8 * 8
-    r = bytearray(max(size, 12 + len(body)))
-    struct.pack_into("<iB3xi", r, 0, size, 2, index)
-    r[12:12 + len(body)] = body
-    r = r[:size]
-    if crc:
-        struct.pack_into("<I", r, size - 4, _crc(r[:size - 4]))
-    return bytes(r)
-
-
-def _shifted(records, seed):
-    """record i at a byte offset = i mod 8 with filler in front of it and behind the last one (a record's span runs through the filler)"""
-    rng = np.random.default_rng(seed)
-    parts, offsets, pos = [], [], 0
-    for i, rec in enumerate(records):
-        gap = int(rng.integers(1, 24))
-        gap += (i % 8 - (pos + gap)) % 8
-        parts.append(bytes(rng.integers(1, 256, gap, dtype=np.uint8)))
-        pos += gap
-        offsets.append(pos)
-        parts.append(rec)
-        pos += len(rec)
-    parts.append(bytes(rng.integers(1, 256, 13, dtype=np.uint8)))
-    offsets.append(pos + 13)
-    return np.frombuffer(b"".join(parts), np.uint8), np.array(offsets, np.uint64)
 
 
 # ---------------------------------------------------------------- 1. the reference's own bytes
@@ -144,7 +113,7 @@ def test_reference_sample_model_coordinates(golden_dir, ctx):
     assert np.isfinite(vals[0]).all() and abs(float(vals[0].max()) - 1.0) < 1e-6           # z = sin(x pi) sin(y pi) on [0, 1]^2
 
 
-# ---------------------------------------------------------------- 2. one element equals the old call
+# ---------------------------------------------------------------- 2. one element: both device calls equal the host call
 
 @pytest.fixture(scope="module")
 def damaged_packings():
@@ -177,14 +146,16 @@ def test_one_element_equals_the_old_call(master5, mixed_int, mixed_short, damage
     blob, offsets = _shifted(batch, seed=3)
     assert {int(o) % 2 for o in offsets[:-1]} == {0, 1}
     for verify in (True, False):
+        hi, hv, hs = _host_records(master5, NR, NC, blob, offsets, element, verify)      # (gf_tile_record_decode_batch: its own code)
         oi, ov, os_ = master5.record_blob_dev(NR, NC, blob, offsets, element=element, verify_checksums=verify)
         ni, nv, ns = master5.record_blob_elems_dev(NR, NC, blob, offsets, [element], verify_checksums=verify)
         assert ns.shape == (1, len(batch))
-        assert np.array_equal(ns[0], os_), (verify, ns[0].tolist(), os_.tolist())
-        assert np.array_equal(ni, oi)
-        ok = os_ == 0
-        assert nv[0].dtype == ov.dtype and np.array_equal(nv[0][ok], ov[ok])
-        assert ok.sum() >= len(records) and (os_ == -1).sum() >= 5 and (os_ == -2).sum() >= 3
+        ok = hs == 0
+        for what, di, dv, ds in (("the record call", oi, ov, os_), ("the elements call", ni, nv[0], ns[0])):
+            assert np.array_equal(ds, hs), (what, verify, ds.tolist(), hs.tolist())
+            assert np.array_equal(di, hi), (what, verify)
+            assert dv.dtype == hv.dtype and np.array_equal(dv[ok], hv[ok]), (what, verify)
+        assert ok.sum() >= len(records) and (hs == -1).sum() >= 5 and (hs == -2).sum() >= 3
 
 
 # ---------------------------------------------------------------- 3. three elements

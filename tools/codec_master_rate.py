@@ -8,14 +8,20 @@ Device-records mode: the same batch as tile records (gf_tile_record_encode_batch
 gf_tile_record_decode_batch_dev -- HIP events on one stream, with and without checksum verification, with and without the one
 H2D copy of the blob (from page-locked memory) -- beside the host call gf_tile_record_decode_batch in the same run:
     python tools/codec_master_rate.py --device-records [nTiles] [codec list] [--once] [--out profiles/device_records_rate.json]
-                                      [--elements short,float]
+                                      [--elements short,float] [--parent-lib <libgvrs_hip.so of the parent commit>]
     python tools/codec_master_rate.py --merge-kernel-stats <rocprofv3 kernel_stats.csv> <the JSON written above>
 (--once: one call of each form and no timing loops, the run to put behind `rocprofv3 --kernel-trace --stats --`)
 --elements LIST (int, short, float, icf; e.g. short,float) adds gf_tile_record_decode_batch_elems_dev to the same run, checksums
 verified, medians of 20 event timings with the calls taken in turn: (1) gf_tile_record_decode_batch_dev on the int records, the
 baseline, (2) the new call on the same records as one INT element -- the gate: its median within the spread (max - min) that (1)
 shows in this run --, (3) the new call on records of the listed elements, framed here from the existing encoders' packings
-(reported, not gated)."""
+(reported, not gated).
+--parent-lib PATH runs this alone: gf_tile_record_decode_batch_dev of the library at PATH (a build of the parent commit; the C ABI
+is the same) and of this tree's, in one process on one stream, checksums verified, 20 event timings each taken in turn, on (int)
+the batch's INT records, every record on one codec: the straight route, (short) the batch as SHORT records: every tile decoded to
+the temporary and narrowed, (half_standard) INT records with every second record left in standard form: half the tiles copied
+from the temporary, half from the blob.  The gate per case: this tree's median <= the parent's median + the parent's own spread.
+With --out the result replaces the key "parent_vs_unified" of that file and nothing else."""
 import ctypes as C
 import json
 import os
@@ -128,8 +134,7 @@ def main():
     print(json.dumps(out))
 
 
-RECORD_KERNELS = ("k_record_parse", "k_record_crc32c", "k_codec_partition", "k_tile_scatter", "k_record_parse_elems", "k_record_crc32c_elems",
-                  "k_elem_scatter")
+RECORD_KERNELS = ("k_codec_partition", "k_record_parse_elems", "k_record_crc32c_elems", "k_elem_scatter")
 ELEM_TYPES = {"int": 0, "short": 1, "float": 2, "icf": 3}
 
 
@@ -245,12 +250,70 @@ def _elements_run(L, ctx, timer, cd, codecs, names, n_rows, n_cols, vals, old_ca
     return res
 
 
+def _parent_vs_unified(L, ctx, timer, parent_path, cd, codecs, n_rows, n_cols, vals, int_records, once):
+    from gridfour_amd._lib import SIGNATURES
+    nt, cells = vals.shape
+    P = C.CDLL(parent_path)
+    for name in ("gf_context_create", "gf_context_destroy", "gf_tile_record_decode_batch_dev"):
+        getattr(P, name).restype, getattr(P, name).argtypes = SIGNATURES[name]
+    pctx = C.c_void_p()
+    check(P.gf_context_create(0, C.byref(pctx)), "gf_context_create (parent)")
+    stream = ctx.stream                                  # both builds run on this context's stream, where the timer's events are
+    assert stream
+    idx = np.arange(nt, dtype=np.int32)
+    shorts = np.clip(vals, -32767, 32767).astype(np.int32)
+
+    def packings(values):
+        cap = nt * (4 * cells + 1024) + 64
+        blob, off = np.empty(cap, np.uint8), np.zeros(nt + 1, np.uint64)
+        used, st = np.zeros(nt, np.uint8), np.zeros(nt, np.int32)
+        check(L.gf_codec_master_encode_batch_i32(ctx.handle, cd, len(codecs), n_rows, n_cols, nt, _p(values), _p(blob), cap, _p(off), _p(used),
+                                                 _p(st)), "codec_master_encode")
+        assert (st == 0).all()
+        return [bytes(blob[int(off[t]):int(off[t + 1])]) for t in range(nt)]
+
+    def framed(elements):
+        blob, off = _frame_records(L, [[el] for el in elements])
+        total = int(off[nt])
+        return gridfour_amd.DeviceBuffer(ctx, total + 64).upload(blob[:total + 64]), total, gridfour_amd.DeviceBuffer(ctx, off.nbytes).upload(off)
+
+    raw2 = shorts.astype("<i2")
+    raw4 = vals.astype("<i4")
+    cases = {"int": (0, vals, int_records),
+             "short": (1, shorts.astype(np.int16), framed([pk if len(pk) < 2 * cells else raw2[t].tobytes() for t, pk in enumerate(packings(shorts))])),
+             "half_standard": (0, vals, framed([pk if t % 2 == 0 and len(pk) < 4 * cells else raw4[t].tobytes() for t, pk in enumerate(packings(vals))]))}
+    d_idx = gridfour_amd.DeviceBuffer(ctx, nt * 4)
+    d_val = gridfour_amd.DeviceBuffer(ctx, nt * cells * 4)
+    d_st = gridfour_amd.DeviceBuffer(ctx, nt * 4)
+    res = {}
+    for name, (elem, want, (d_blob, total, d_off)) in cases.items():
+        def call(lib, handle):
+            check(lib.gf_tile_record_decode_batch_dev(handle, stream, cd, len(codecs), elem, n_rows, n_cols, nt, d_blob.ptr, total, d_off.ptr, 1,
+                                                      d_idx.ptr, d_val.ptr, d_st.ptr), "gf_tile_record_decode_batch_dev")
+        fns = {"parent": lambda: call(P, pctx), "unified": lambda: call(L, ctx.handle)}
+        for fn in fns.values():                           # (grows the contexts' buffers, and the answer is checked once per build)
+            d_val.fill(0)
+            d_st.fill(0xff)
+            fn()
+            ctx.synchronize()
+            assert (d_st.download(np.int32, nt) == 0).all() and np.array_equal(d_idx.download(np.int32, nt), idx)
+            assert np.array_equal(d_val.download(want.dtype, nt * cells).reshape(nt, cells), want), name
+        r = _series(timer, fns, 1 if once else 20)
+        r["record_bytes"] = total
+        r["gap_ms"] = round(r["unified"]["median_ms"] - r["parent"]["median_ms"], 4)
+        r["unified_within_parent_spread"] = bool(r["unified"]["median_ms"] <= r["parent"]["median_ms"] + r["parent"]["spread_ms"])
+        res[name] = r
+    P.gf_context_destroy(pctx)
+    return res
+
+
 def device_records(argv):
     once = "--once" in argv
     out_path = argv[argv.index("--out") + 1] if "--out" in argv else None
     names = argv[argv.index("--elements") + 1].split(",") if "--elements" in argv else None
     assert names is None or (names and all(k in ELEM_TYPES for k in names)), names
-    pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] not in ("--out", "--elements"))]
+    parent = argv[argv.index("--parent-lib") + 1] if "--parent-lib" in argv else None
+    pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] not in ("--out", "--elements", "--parent-lib"))]
     nt = int(pos[0]) if pos else 12960
     codecs = [int(x) for x in (pos[1] if len(pos) > 1 else "1,2,0,3").split(",")]
     n_rows, n_cols = 120, 150
@@ -317,6 +380,18 @@ def device_records(argv):
     ctx.synchronize()
     assert (d_st.download(np.int32, nt) == 0).all() and np.array_equal(d_idx.download(np.int32, nt), idx)
     assert np.array_equal(d_val.download(np.int32, nt * cells).reshape(nt, cells), vals)
+    if parent:
+        res = _parent_vs_unified(L, ctx, timer, parent, cd, codecs, n_rows, n_cols, vals, (d_blob, total, d_off), once)
+        print(json.dumps({"workload": out["workload"], "parent_vs_unified": res}))
+        if out_path and not once:
+            with open(out_path) as f:
+                merged = json.load(f)
+            merged["parent_vs_unified"] = res
+            with open(out_path, "w") as f:
+                json.dump(merged, f, indent=1)
+                f.write("\n")
+        L.gf_host_free(pinned)
+        return
     reps = 1 if once else 5
     out["device_verify"] = measure(lambda: decode(1), reps)
     out["device_no_verify"] = measure(lambda: decode(0), reps)
@@ -356,7 +431,8 @@ def merge_kernel_stats(csv_path, json_path):
             name = row.get("Name", "")
             hits = [k for k in RECORD_KERNELS if k in name]
             if hits:
-                k = max(hits, key=len)                                   # (k_record_parse is not k_record_parse_elems)
+                assert len(hits) == 1, (name, hits)                      # (no name in RECORD_KERNELS may be part of another)
+                k = hits[0]
                 rows[k] = {"calls": int(row["Calls"]), "average_us": round(float(row["AverageNs"]) / 1e3, 2),
                            "min_us": round(float(row["MinNs"]) / 1e3, 2), "max_us": round(float(row["MaxNs"]) / 1e3, 2)}
     out["kernels"] = rows
