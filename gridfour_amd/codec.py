@@ -48,6 +48,25 @@ class GvrsHipContext:
     def reserve(self, n_rows, n_cols, n_tiles):
         check(lib().gf_context_reserve(self._h, n_rows, n_cols, n_tiles), "gf_context_reserve")
 
+    def block_from_tiles_dev(self, grid, rect, elem_type, fill_bits, n_tiles, d_tile_indices, d_tiles, d_block, d_tile_status=None,
+                             stream=None):
+        """gf_block_from_tiles_dev on device pointers: grid = (n_rows_grid, n_cols_grid, n_rows_tile, n_cols_tile), rect = (row0,
+        col0, n_rows, n_cols), elem_type one of ELEM_TYPES' values.  Enqueues only."""
+        grid, rect = np.ascontiguousarray(grid, np.int32), np.ascontiguousarray(rect, np.int32)
+        assert grid.size == 4 and rect.size == 4
+        check(lib().gf_block_from_tiles_dev(self._h, stream, _ptr(grid), _ptr(rect), int(elem_type),
+                                            int(fill_bits) & 0xffffffff, int(n_tiles), d_tile_indices, d_tile_status, d_tiles, d_block),
+              "gf_block_from_tiles_dev")
+
+    def tiles_from_block_dev(self, grid, rect, elem_type, fill_bits, d_block, n_tiles, d_tile_indices, d_tiles, d_status=None,
+                             keep_outside=False, stream=None):
+        """gf_tiles_from_block_dev on device pointers, the inverse of block_from_tiles_dev.  Enqueues only."""
+        grid, rect = np.ascontiguousarray(grid, np.int32), np.ascontiguousarray(rect, np.int32)
+        assert grid.size == 4 and rect.size == 4
+        check(lib().gf_tiles_from_block_dev(self._h, stream, _ptr(grid), _ptr(rect), int(elem_type),
+                                            int(fill_bits) & 0xffffffff, int(bool(keep_outside)), d_block, int(n_tiles), d_tile_indices,
+                                            d_tiles, d_status), "gf_tiles_from_block_dev")
+
     def close(self):
         if self._h:
             lib().gf_context_destroy(self._h)
@@ -858,6 +877,67 @@ class CodecMasterHip:
                                                       nCols, nt, _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), _ptr(idx), ptrs,
                                                       _ptr(status)), "gf_tile_record_decode_batch_elems")
         return idx, out, status
+
+    # ---- grid blocks: GvrsElement.readBlock for a batch of records (gf_block_read_elems[_dev]) ----
+    @staticmethod
+    def _fill_specs(specs, elems, fills):
+        """fills: per element None (INT4_NULL_CODE / -32768 / NaN) or the block's fill value; an ICF element's is its own fill_f"""
+        for e, el in enumerate(elems):
+            kind = el if isinstance(el, str) else el[0]
+            f = None if fills is None else fills[e]
+            if kind in ("int", "short"):
+                specs[e]["fill_i"] = (INT4_NULL_CODE if kind == "int" else -32768) if f is None else f
+            elif kind == "float":
+                specs[e]["fill_f"] = np.float32(np.nan) if f is None else f
+            else:
+                assert f is None, "an int-coded-float element is filled with the fill_f of its description"
+        return specs
+
+    def read_block_dev(self, nRows, nCols, grid_shape, rect, blob, offsets, elems, fills=None, verify_checksums=True):
+        """gf_block_read_elems_dev: the rectangle rect = (row0, col0, n_rows, n_cols) of a grid of grid_shape = (rows, columns)
+        cells cut into nRows x nCols tiles, read from tile records as they lie in a byte array (as record_blob_elems_dev; records
+        in any order, tiles the bytes do not hold read as fill).  Uploads blob and offsets, downloads the results: ([block
+        [n_rows, n_cols] per element: int32 / int16 / float32], status [n_elems, nt]).  The block is good iff every status is 0."""
+        specs, dtypes = self._elem_specs(elems)
+        self._fill_specs(specs, elems, fills)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nt, ne = offsets.size - 1, len(dtypes)
+        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
+        rect = np.ascontiguousarray(rect, np.int32)
+        n_block = int(rect[2]) * int(rect[3])
+        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
+        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
+        d_blk = [DeviceBuffer(self.ctx, n_block * np.dtype(dt).itemsize + 16).fill(0) for dt in dtypes]
+        d_st = DeviceBuffer(self.ctx, ne * nt * 4 + 16).fill(0)
+        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_blk])
+        try:
+            check(lib().gf_block_read_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, _ptr(grid),
+                                                _ptr(rect), nt, d_blob.ptr, blob.size, d_off.ptr, int(bool(verify_checksums)), ptrs, d_st.ptr),
+                  "gf_block_read_elems_dev")
+            self.ctx.synchronize()
+            out = [b.download(dt, n_block).reshape(int(rect[2]), int(rect[3])) for b, dt in zip(d_blk, dtypes)]
+            status = d_st.download(np.int32, ne * nt).reshape(ne, nt)
+        finally:
+            for b in [d_blob, d_off, d_st] + d_blk:
+                b.free()
+        return out, status
+
+    def read_block(self, nRows, nCols, grid_shape, rect, blob, offsets, elems, fills=None, verify_checksums=True):
+        """The same through gf_block_read_elems, the host-memory form (staged by the library); offsets[-1] bytes of blob are read."""
+        specs, dtypes = self._elem_specs(elems)
+        self._fill_specs(specs, elems, fills)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        blob = np.concatenate([np.ascontiguousarray(blob, dtype=np.uint8), np.zeros(16, np.uint8)])
+        nt, ne = offsets.size - 1, len(dtypes)
+        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
+        rect = np.ascontiguousarray(rect, np.int32)
+        out = [np.zeros((int(rect[2]), int(rect[3])), dt) for dt in dtypes]
+        status = np.zeros((ne, nt), np.int32)
+        ptrs = (C.c_void_p * ne)(*[a.ctypes.data for a in out])
+        check(lib().gf_block_read_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, _ptr(grid), _ptr(rect), nt,
+                                        _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), ptrs, _ptr(status)), "gf_block_read_elems")
+        return out, status
 
     def packing_blob_dev(self, nRows, nCols, blob, offsets, lengths):
         """gf_codec_master_decode_batch_i32_dev: packing t = blob[offsets[t]:offsets[t]+lengths[t]].  Returns (values, status)."""

@@ -109,13 +109,16 @@ struct gf_context {
     DevBuf dResiduals, dCoefs, dStatus2;   // LSOP staging
     DevBuf dM32, dM32Len, dM32Models, dSeeds;   // CodecDeflate staging
     DevBuf dInflate, dInflOut, dInflMeta;       // GPU inflate: stream descriptors, inflated bytes, produced / status
+    DevBuf dBlockTmp, dBlockIdx, dBlockSlots;   // grid blocks (gvrs_api_blocks.hip): the records' decoded tiles on their way into a block, the
+                                                // gather's element table and the records' tile indices, the slot table of the block's tiles
     DevBuf dRecMeta, dRecSub, dRecTmp;          // records / mixed packings in device memory (gvrs_api_records_dev.hip): per-record framing
                                                 // results, the partition by codec, decoded tiles on their way to their place
     std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
-    std::array<DevBuf *, 25> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
+    std::array<DevBuf *, 28> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
     {
         return {&workspace, &trees, &flags, &packRecs, &dValues, &dSlots, &dBlob, &dLengths, &dPred, &dStatus, &dOffsets, &dPlanes,
-                &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta, &dRecMeta, &dRecSub, &dRecTmp};
+                &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta, &dRecMeta, &dRecSub, &dRecTmp,
+                &dBlockTmp, &dBlockIdx, &dBlockSlots};
     }
     gf_context()
     {
@@ -244,6 +247,15 @@ gf_status floatDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, si
                          const uint64_t *dOffsets, const uint32_t *dLengths, float *dValues, int32_t *dStatus);
 bool zDeflate(const uint8_t *in, size_t n, int level, std::vector<uint8_t> &out);
 bool zDeflateUpTo(const uint8_t *in, size_t n, int level, size_t limit, std::vector<uint8_t> &out);
+// gvrs_api_records_dev.hip: the argument checks of the elements calls, an element's bytes per cell, and the one device pipeline
+// (no lock taken, no argument checked: its callers hold the context's lock)
+gf_status elemsArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows, int nCols,
+                    size_t nTiles, const uint8_t *blob, bool blobOnDevice, const uint64_t *offsets, void *const *values,
+                    const int32_t *status);
+size_t elemItemBytes(int type);
+gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
+                           int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets,
+                           const uint32_t *dLengths, int verifyChecksum, int32_t *dTileIndices, void *const *dValues, int32_t *dStatus);
 // gvrs_api_deflate.hip
 gf_status deflateDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
                            const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues, int32_t *dStatus);

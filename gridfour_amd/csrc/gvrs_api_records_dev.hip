@@ -42,6 +42,8 @@ gf_status decodeSublist(gf_context *c, hipStream_t st, int codec, int nRows, int
     }
 }
 
+}  // namespace
+
 // what the host can check without a device (values: device or host pointers, only looked at for null); a negative nCodecs is an
 // empty list
 gf_status elemsArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows, int nCols,
@@ -178,6 +180,8 @@ gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int n
     GF_HIP(gf_launch_elem_scatter(g, st));
     return GF_OK;
 }
+
+namespace {
 
 // the checks and the lock that the three device entry points share
 gf_status recordsDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows, int nCols,

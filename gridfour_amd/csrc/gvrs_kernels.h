@@ -480,3 +480,47 @@ struct GfElemScatterArgs {
     int32_t *status;           // per instance
 };
 hipError_t gf_launch_elem_scatter(const GfElemScatterArgs &a, hipStream_t stream);
+
+// Grid blocks (gvrs_blocks.hip; driven by gvrs_api_blocks.hip): a rectangle of the grid gathered from decoded tiles (k_block_slots,
+// k_block_gather: the loops of gvrs/GvrsElement.java:348-402) and a raster cut into tiles (k_grid_cut).  The grid is nRowsOfTiles x
+// nColsOfTiles tiles of nRowsTile x nColsTile cells, tile index = tileRow * nColsOfTiles + tileCol (TileAccessIndices.java:86-88);
+// every byte address is 64 bits wide.
+struct GfBlockGeom {
+    int32_t nRowsTile, nColsTile;
+    int32_t nColsOfTiles, nTilesGrid;                // nTilesGrid = nRowsOfTiles * nColsOfTiles <= 0x7fffffff
+    int32_t row0, col0, nRows, nCols;                // the rectangle, in grid coordinates
+    int32_t tileRow0, tileCol0, nTileRows, nTileCols;   // the rectangle of tiles it touches
+};
+struct GfBlockElem {           // an element of the block, in device memory for k_block_gather (32 bytes)
+    const void *tiles;         // decoded tiles of the element, record j at tiles + j * cells items
+    void *block;               // nRows * nCols items, row-major
+    const int32_t *status;     // may be null; per record: the element's status, anything but GF_K_OK reads as fill
+    uint32_t fillBits;         // the fill value's bits (SHORT: the low 16)
+    uint32_t itemBytes;        // 2 (SHORT) or 4
+};
+struct GfBlockSlotsArgs {
+    const int32_t *tileIndices;   // per record
+    size_t nRecords;              // <= 0x7fffffff
+    int32_t *slots;               // nTileRows * nTileCols entries, pre-set to -1: the highest record number of each tile
+    GfBlockGeom g;
+};
+hipError_t gf_launch_block_slots(const GfBlockSlotsArgs &a, hipStream_t stream);
+struct GfBlockGatherArgs {
+    const int32_t *slots;
+    const GfBlockElem *elems;     // device memory, nElems entries; null: the one element of `one` (no table to upload: capture-safe)
+    GfBlockElem one;
+    int nElems;
+    GfBlockGeom g;
+};
+hipError_t gf_launch_block_gather(const GfBlockGatherArgs &a, hipStream_t stream);
+struct GfGridCutArgs {
+    const void *block;            // the rectangle's cells, row-major
+    void *tiles;                  // listed tile j at tiles + j * cells items
+    const int32_t *tileIndices;   // per listed tile: its index in the grid
+    int32_t *status;              // may be null; GF_K_OK, or GF_K_ERR_BOUNDS for an index outside [0, nTilesGrid): nothing of it is written
+    size_t nTiles;
+    uint32_t fillBits, itemBytes;
+    int keepOutside;              // != 0: cells outside the rectangle are left as they are
+    GfBlockGeom g;
+};
+hipError_t gf_launch_grid_cut(const GfGridCutArgs &a, hipStream_t stream);

@@ -569,10 +569,10 @@ gf_status gf_tile_record_decode_batch_dev(gf_context *ctx, void *stream, const i
 #define GF_MAX_ELEMS 16
 typedef struct gf_elem_spec {
     int32_t type;      /* GF_ELEM_*                                                      */
-    int32_t fill_i;    /* ICF: fillValueI, the stored code of "no data"; otherwise ignored */
+    int32_t fill_i;    /* ICF: fillValueI, the stored code of "no data"; INT, SHORT: the fill value of a block read, else ignored */
     float scale;       /* ICF: value = code / scale + offset (TileElementIntCodedFloat.java:172-176) */
     float offset;
-    float fill_f;      /* ICF: what a cell equal to fill_i is delivered as (may be NaN)  */
+    float fill_f;      /* ICF: what a cell equal to fill_i is delivered as (may be NaN); FLOAT, ICF: the fill value of a block read */
 } gf_elem_spec;
 gf_status gf_tile_record_decode_batch_elems_dev(gf_context *ctx, void *stream, const int *codecs, int n_codecs,
                                                 const gf_elem_spec *elems, int n_elems, int n_rows, int n_cols, size_t n_tiles,
@@ -583,6 +583,56 @@ gf_status gf_tile_record_decode_batch_elems(gf_context *ctx, const int *codecs, 
                                             int n_elems, int n_rows, int n_cols, size_t n_tiles, const uint8_t *blob,
                                             const uint64_t *offsets, int verify_checksum, int32_t *tile_indices,
                                             void *const *values, int32_t *status);
+
+/* ---- grid blocks: a rectangle of the raster read from tiles, and a raster cut into tiles, in device memory ------------------
+ * (gvrs/GvrsElement.java:298-404 readBlock / readBlockInt, gvrs/TileAccessIndices.java:79-88, gvrs/GvrsFileSpecification.java:423-424)
+ * The grid is cut into tiles of n_rows_tile x n_cols_tile cells: ceil(n_cols_grid / n_cols_tile) tiles across, ceil(n_rows_grid /
+ * n_rows_tile) down, tile index = tileRow * nColsOfTiles + tileCol; the tiles of the last tile row and column reach beyond the
+ * grid.  A gf_rect is in grid coordinates and lies wholly inside the grid.  A block is the rectangle's cells, row-major, n_rows x
+ * n_cols items of the element's delivered type: 2 bytes for GF_ELEM_SHORT, 4 for INT, FLOAT and ICF.  Cells move as bits (NaN
+ * payloads and -0.0 survive); fill_bits is the fill value's bit pattern (the low 16 bits for SHORT).  All cell counts and
+ * addresses are 64 bits wide on host and device.
+ *   gf_block_from_tiles_dev: d_tiles holds n_tiles decoded tiles (tile j = cells items at d_tiles + j * cells), d_tile_indices[j]
+ *   the tile index of each, in any order.  Every cell of d_block is written exactly once: from the tile that covers it, or with
+ *   the fill value where no listed tile does or d_tile_status (may be NULL) of that tile is not GF_OK.  An index that is
+ *   negative, beyond the grid's tiles or outside the rectangle's tiles places nothing; of two entries with one index the later
+ *   one wins, whatever the timing.  Never synchronises and allocates only when the context's slot table has to grow (call it
+ *   once before a capture): safe for hipGraph capture.  The slot table is ONE buffer of the context, written and read by the work
+ *   this call enqueues: the gathers of one context (this call and the two record forms) must all be enqueued on one stream, or
+ *   be ordered by the caller; and a recorded graph holds the table's address, so it is invalid once a later gather of the
+ *   context with a larger rectangle of tiles has made the table grow (it never shrinks: gather the largest rectangle first).
+ *   gf_tiles_from_block_dev, the inverse: d_block is the rectangle's cells; for each listed tile (tile j of d_tiles is tile
+ *   d_tile_indices[j] of the grid) every cell whose grid coordinate lies inside the rectangle takes the block's value; every
+ *   other cell, those beyond the grid included, takes the fill value when keep_outside == 0 and is left untouched otherwise (a
+ *   block written into existing tiles).  d_status (may be NULL): GF_OK, or GF_ERR_BOUNDS for an index outside the grid's tiles,
+ *   of which nothing is written.  Capture-safe.
+ *   gf_block_read_elems_dev: gf_tile_record_decode_batch_elems_dev into a temporary of the context, then the gather: d_blocks
+ *   (a HOST array of n_elems device pointers) receives one block per element in its delivered type (no int-to-float conversion
+ *   as in readBlock on an integer element).  Records come in any order; records of tiles that do not touch the rectangle are
+ *   decoded and ignored.  d_status is exactly what gf_tile_record_decode_batch_elems_dev reports; the cells of a failed element
+ *   read as fill (the reference would throw: THE BLOCK IS GOOD IFF EVERY STATUS IS GF_OK).  Fill per element: fill_i for INT
+ *   and SHORT (outside int16 for a SHORT: GF_ERR_ARG), fill_f for FLOAT and ICF.  Synchronises `stream` once, not capture-safe.
+ *   With n_records == 0 the blocks are all fill.  gf_block_read_elems is the same for bytes, blocks and statuses in host memory,
+ *   staged as gf_tile_record_decode_batch_elems stages; only the blocks and the statuses are copied back.
+ * GF_ERR_ARG, before the context or a device is looked at: null pointers, one of the eight numbers < 1 (row0 / col0 < 0), a
+ * rectangle not wholly inside the grid (the reference throws), an elem_type outside GF_ELEM_*, and for the two record forms
+ * whatever gf_tile_record_decode_batch_elems[_dev] rejects (n_rows, n_cols: the tile's).  GF_ERR_UNSUPPORTED: more than 0x7fffffff
+ * tiles in the grid or entries in a list, 2^28 or more cells in a tile.                                                          */
+typedef struct gf_grid_spec { int32_t n_rows_grid, n_cols_grid, n_rows_tile, n_cols_tile; } gf_grid_spec;
+typedef struct gf_rect      { int32_t row0, col0, n_rows, n_cols; } gf_rect;   /* grid coordinates */
+gf_status gf_block_from_tiles_dev(gf_context *ctx, void *stream, const gf_grid_spec *grid, const gf_rect *rect, int elem_type,
+                                  uint32_t fill_bits, size_t n_tiles, const int32_t *d_tile_indices, const int32_t *d_tile_status,
+                                  const void *d_tiles, void *d_block);
+gf_status gf_tiles_from_block_dev(gf_context *ctx, void *stream, const gf_grid_spec *grid, const gf_rect *rect, int elem_type,
+                                  uint32_t fill_bits, int keep_outside, const void *d_block, size_t n_tiles,
+                                  const int32_t *d_tile_indices, void *d_tiles, int32_t *d_status);
+gf_status gf_block_read_elems_dev(gf_context *ctx, void *stream, const int *codecs, int n_codecs, const gf_elem_spec *elems,
+                                  int n_elems, const gf_grid_spec *grid, const gf_rect *rect, size_t n_records,
+                                  const uint8_t *d_blob, size_t blob_bytes, const uint64_t *d_offsets, int verify_checksum,
+                                  void *const *d_blocks, int32_t *d_status);
+gf_status gf_block_read_elems(gf_context *ctx, const int *codecs, int n_codecs, const gf_elem_spec *elems, int n_elems,
+                              const gf_grid_spec *grid, const gf_rect *rect, size_t n_records, const uint8_t *blob,
+                              const uint64_t *offsets, int verify_checksum, void *const *blocks, int32_t *status);
 
 /* ---- CodecFloat (compress/CodecFloat.java:328-458): float32 tiles ---------------------------
  * The five byte planes (sign bits, exponent, three byte-delta coded mantissa bytes) are split and
