@@ -6,7 +6,8 @@
 //   lsop/LsDecoder12.java:127-141             two streams of M32 bytes
 // What an inflater produces is defined by the stream, not by the implementation, so the bytes equal the JDK's (and the
 // host zlib's) by construction; tests/test_gpu_inflate.py holds the kernel to the host's zlib on every block type, on
-// the reference's sample files and on corrupted streams.
+// the reference's sample files and on corrupted streams; tests/test_gpu_inflate_crafted.py on hand-built streams that name
+// every rule of inflate.c / inftrees.c (tests/deflate_craft.py), whole, at every byte prefix and with every amount of room.
 //
 // Decomposition: a deflate stream is one serial chain (every code's position depends on the lengths of all codes before
 // it, every match on the bytes before it), so the parallelism is across streams -- a batch has one to five per tile,
@@ -416,7 +417,14 @@ __global__ __launch_bounds__(64 * INF_WAVES) void k_inflate(GfInflateArgs a)
                                                                    // empty or one-code distance set would read as "invalid distance code")
                 const int ds = inf_sym(z, T.dd, D_BITS, T.dCount, T.dSym);
                 if (ds < 0) {
-                    if (ds == -1) status = GF_K_ERR_FORMAT;
+                    // No code fits.  With an EMPTY distance set that is every bit pattern, the zero padding behind the input
+                    // included: zlib's table for such a set holds invalid-code markers of ONE bit and it asks for that bit
+                    // before it looks at a marker (inflate.c, DIST: `if (here.bits <= bits) break; PULLBYTE()`), so with
+                    // nothing buffered and no input left it waits -- only a real bit makes "invalid distance code".  (A failed
+                    // look-up consumes nothing and inf_need keeps bits buffered while there is input: bitcnt == 0 says both.
+                    // A one-code set reads its code in the padding and is starved by inf_sym itself.)
+                    if (ds == -1 && z.bitcnt == 0u) z.starved = true;
+                    else if (ds == -1) status = GF_K_ERR_FORMAT;
                     break;
                 }
                 if (ds > 29) { status = GF_K_ERR_FORMAT; break; }

@@ -10,8 +10,10 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _inflate(streams, caps):
-    """streams: list of bytes; caps: room per stream.  Returns (outputs, produced, status)."""
+def _inflate(streams, caps, residues=None, odd_out=False):
+    """streams: list of bytes; caps: room per stream.  Returns (outputs, produced, status).
+    residues: where each stream begins modulo 4 in the input buffer (default: on a 4-byte boundary); odd_out: every output
+    begins at an odd offset.  0xEE guard bytes surround every output."""
     import gridfour_amd
     from gridfour_amd import DeviceBuffer, lib
     from gridfour_amd._lib import check
@@ -22,15 +24,24 @@ def _inflate(streams, caps):
     in_len = np.array([len(s) for s in streams], np.uint32)
     pos = 0
     for i, s in enumerate(streams):
-        in_off[i] = pos
-        pos += (len(s) + 7) // 4 * 4
+        r = int(residues[i]) if residues is not None else 0
+        in_off[i] = pos + r
+        pos += (len(s) + r + 7) // 4 * 4
     blob = np.zeros(pos + 16, np.uint8)
     for i, s in enumerate(streams):
         blob[int(in_off[i]):int(in_off[i]) + len(s)] = np.frombuffer(s, np.uint8)
     out_cap = np.array(caps, np.uint32)
     out_off = np.zeros(n, np.uint64)
-    out_off[1:] = np.cumsum((out_cap[:-1].astype(np.uint64) + 15) // 16 * 16)
-    total_out = int(out_off[-1]) + int(out_cap[-1]) + 16
+    if odd_out:
+        # 16 guard bytes and more between neighbours; the offsets run through 1, 3, 5 .. 15 modulo 16
+        step = (out_cap.astype(np.uint64) + 15) // 16 * 16 + 32
+        out_off[0] = 16
+        out_off[1:] = 16 + np.cumsum(step[:-1])
+        out_off += (2 * np.arange(n, dtype=np.uint64) + 1) % 16
+        total_out = int(out_off[-1]) + int(out_cap[-1]) + 32
+    else:
+        out_off[1:] = np.cumsum((out_cap[:-1].astype(np.uint64) + 15) // 16 * 16)
+        total_out = int(out_off[-1]) + int(out_cap[-1]) + 16
     d_in, d_out = DeviceBuffer(ctx, blob.size), DeviceBuffer(ctx, total_out)
     d_prod, d_st = DeviceBuffer(ctx, n * 4 + 16), DeviceBuffer(ctx, n * 4 + 16)
     d_in.upload(blob)
@@ -42,8 +53,10 @@ def _inflate(streams, caps):
     prod = d_prod.download(np.uint32, n)
     st = d_st.download(np.int32, n)
     outs = [raw[int(out_off[i]):int(out_off[i]) + int(prod[i])].tobytes() for i in range(n)]
-    # nothing may be written behind a stream's room
+    # nothing may be written in front of the first stream's room, between two rooms or behind the last
+    assert (raw[:int(out_off[0])] == 0xEE).all()
     for i in range(n):
+        assert prod[i] <= out_cap[i], i
         end = int(out_off[i]) + int(out_cap[i])
         nxt = int(out_off[i + 1]) if i + 1 < n else total_out
         assert (raw[end:nxt] == 0xEE).all(), i
