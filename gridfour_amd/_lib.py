@@ -100,6 +100,11 @@ SIGNATURES = {
                                                         _vp, C.c_int, _vp, _vp, _vp]),
     "gf_tile_record_decode_batch_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, _vp, _vp, C.c_int, _vp,
                                                     _vp, _vp]),
+    "gf_tile_record_max_bytes_elems": (C.c_size_t, [_vp, C.c_int, C.c_int, C.c_int]),
+    "gf_tile_record_encode_batch_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, _vp, _vp, C.c_int,
+                                                        _vp, C.c_size_t, _vp, _vp, _vp]),
+    "gf_tile_record_encode_batch_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, _vp, _vp, C.c_int, _vp,
+                                                    C.c_size_t, _vp, _vp]),
     "gf_block_from_tiles_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_uint32, C.c_size_t, _vp, _vp, _vp, _vp]),
     "gf_tiles_from_block_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_uint32, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp]),
     "gf_block_read_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_int, _vp,

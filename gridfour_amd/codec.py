@@ -878,6 +878,72 @@ class CodecMasterHip:
                                                       _ptr(status)), "gf_tile_record_decode_batch_elems")
         return idx, out, status
 
+    # ---- records of several elements written (gf_tile_record_encode_batch_elems[_dev]) ----
+    def _elem_values(self, nRows, nCols, values_per_element, elems, fills):
+        """(gf_elem_spec array, [values [nt, cells] per element in the type the call takes: int32 (int, icf codes) / int16 / float32 bits])"""
+        specs, dtypes = self._elem_specs(elems)
+        vals = []
+        for e, el in enumerate(elems):
+            kind = el if isinstance(el, str) else el[0]
+            dt = {"int": np.int32, "short": np.int16, "icf": np.int32}.get(kind, np.float32)
+            vals.append(np.ascontiguousarray(values_per_element[e], dtype=dt).reshape(-1, nRows * nCols))
+            if kind == "short":
+                specs[e]["fill_i"] = -32768 if fills is None or fills[e] is None else fills[e]
+        assert len({v.shape[0] for v in vals}) == 1
+        return specs, vals
+
+    def tile_records_elems(self, nRows, nCols, tile_indices, values_per_element, elems, checksums=True, fills=None):
+        """gf_tile_record_encode_batch_elems, the host-memory form, for tiles of len(elems) elements (see _elem_specs; an "icf"
+        element's values are its int32 codes; fills: per "short" element its fill value, default -32768).  Returns (records:
+        list[bytes] exactly as RecordManager appends them to the file, codec index used [n_elems, nt] (255 = standard form))."""
+        specs, vals = self._elem_values(nRows, nCols, values_per_element, elems, fills)
+        nt, ne = vals[0].shape[0], len(vals)
+        idx = np.ascontiguousarray(tile_indices, dtype=np.int32)
+        assert idx.size == nt
+        cap = nt * int(lib().gf_tile_record_max_bytes_elems(_ptr(specs), ne, nRows, nCols))
+        blob = np.empty(max(cap, 16), np.uint8)
+        offsets = np.zeros(nt + 1, np.uint64)
+        used = np.zeros((ne, nt), np.uint8)
+        ptrs = (C.c_void_p * ne)(*[a.ctypes.data for a in vals])
+        check(lib().gf_tile_record_encode_batch_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, nRows,
+                                                      nCols, nt, _ptr(idx), ptrs, int(bool(checksums)), _ptr(blob), cap, _ptr(offsets),
+                                                      _ptr(used)), "gf_tile_record_encode_batch_elems")
+        return [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(nt)], used
+
+    def tile_records_elems_dev(self, nRows, nCols, tile_indices, values_per_element, elems, checksums=True, fills=None, blob_cap=None,
+                               raw=False):
+        """gf_tile_record_encode_batch_elems_dev: uploads the tiles, calls the device form, synchronises and downloads.  Returns
+        (records, codec index used [n_elems, nt], status per tile); with raw=True (blob, offsets, used, status) instead of the list
+        of records: the whole blob of blob_cap bytes (default: room for every record in standard form) pre-filled with 0xA5."""
+        specs, vals = self._elem_values(nRows, nCols, values_per_element, elems, fills)
+        nt, ne = vals[0].shape[0], len(vals)
+        idx = np.ascontiguousarray(tile_indices, dtype=np.int32)
+        assert idx.size == nt
+        full = nt * int(lib().gf_tile_record_max_bytes_elems(_ptr(specs), ne, nRows, nCols))
+        cap = full if blob_cap is None else int(blob_cap)
+        d_val = [DeviceBuffer(self.ctx, v.nbytes + 16).upload(v) for v in vals]
+        d_idx = DeviceBuffer(self.ctx, nt * 4 + 16).upload(idx)
+        d_blob = DeviceBuffer(self.ctx, max(cap, full) + 64).fill(0xA5)
+        d_off = DeviceBuffer(self.ctx, (nt + 1) * 8 + 16).fill(0xff)
+        d_used = DeviceBuffer(self.ctx, ne * nt + 16).fill(0)
+        d_st = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0x7f)
+        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_val])
+        try:
+            check(lib().gf_tile_record_encode_batch_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs),
+                                                              ne, nRows, nCols, nt, d_idx.ptr, ptrs, int(bool(checksums)), d_blob.ptr, cap,
+                                                              d_off.ptr, d_used.ptr, d_st.ptr), "gf_tile_record_encode_batch_elems_dev")
+            self.ctx.synchronize()
+            offsets = d_off.download(np.uint64, nt + 1)
+            blob = d_blob.download(np.uint8, max(cap, full) + 64)
+            used = d_used.download(np.uint8, ne * nt).reshape(ne, nt)
+            status = d_st.download(np.int32, nt)
+        finally:
+            for b in [d_idx, d_blob, d_off, d_used, d_st] + d_val:
+                b.free()
+        if raw:
+            return blob, offsets, used, status
+        return [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(nt)], used, status
+
     # ---- grid blocks: GvrsElement.readBlock for a batch of records (gf_block_read_elems[_dev]) ----
     @staticmethod
     def _fill_specs(specs, elems, fills):

@@ -113,12 +113,14 @@ struct gf_context {
                                                 // gather's element table and the records' tile indices, the slot table of the block's tiles
     DevBuf dRecMeta, dRecSub, dRecTmp;          // records / mixed packings in device memory (gvrs_api_records_dev.hip): per-record framing
                                                 // results, the partition by codec, decoded tiles on their way to their place
+    DevBuf dEncSlots, dEncMeta, dEncWide;       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots, their
+                                                // lengths / statuses and the records' layout, SHORT cells widened for the codecs
     std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
-    std::array<DevBuf *, 28> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
+    std::array<DevBuf *, 31> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
     {
         return {&workspace, &trees, &flags, &packRecs, &dValues, &dSlots, &dBlob, &dLengths, &dPred, &dStatus, &dOffsets, &dPlanes,
                 &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta, &dRecMeta, &dRecSub, &dRecTmp,
-                &dBlockTmp, &dBlockIdx, &dBlockSlots};
+                &dBlockTmp, &dBlockIdx, &dBlockSlots, &dEncSlots, &dEncMeta, &dEncWide};
     }
     gf_context()
     {
@@ -256,6 +258,8 @@ size_t elemItemBytes(int type);
 gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
                            int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets,
                            const uint32_t *dLengths, int verifyChecksum, int32_t *dTileIndices, void *const *dValues, int32_t *dStatus);
+// gvrs_api_records.hip
+size_t elemStandardSize(int elemType, size_t cells);
 // gvrs_api_deflate.hip
 gf_status deflateDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
                            const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues, int32_t *dStatus);

@@ -46,11 +46,15 @@ uint32_t gf_crc32c(const uint8_t *data, size_t n)
     return crc ^ 0xffffffffu;
 }
 
-static size_t elemStandardSize(int elemType, size_t cells)
+}  // extern "C"
+
+size_t elemStandardSize(int elemType, size_t cells)
 {
     // TileElement.java:86-93: bytes per sample * cells, rounded up to a multiple of 4
     return elemType == GF_ELEM_SHORT ? ((cells * 2 + 3) & ~(size_t)3) : cells * 4;
 }
+
+extern "C" {
 
 size_t gf_tile_record_max_bytes(int elemType, int nRows, int nCols)
 {

@@ -524,3 +524,54 @@ struct GfGridCutArgs {
     GfBlockGeom g;
 };
 hipError_t gf_launch_grid_cut(const GfGridCutArgs &a, hipStream_t stream);
+
+// Tile records written in device memory (gvrs_records_enc.hip; driven by gvrs_api_records_enc.hip): the mirror image of the read
+// side above.  Every integer codec of the list has encoded every integer element of every tile into a slot of its own (a
+// CANDIDATE: candidate a of an element is the a-th integer codec of the list); k_record_plan picks the winners and lays the
+// records out, k_record_scan turns their sizes into offsets, k_record_write assembles the bytes and k_record_crc32c_write
+// checksums them.  Per-element arrays are element-major as on the read side (instance i = e * nTiles + t).
+struct GfRecEncElem {          // an element of the tile, in the kernel arguments (32 bytes)
+    const void *values;        // the caller's cells, nTiles * cells items: the source of the standard form
+    const uint8_t *slots;      // candidate a of tile t: slots + (a * nTiles + t) * slotStride; null: the element has no candidates
+    uint32_t stdSize;          // bytes of the standard form (TileElement.java:86-93)
+    uint32_t srcBytes;         // bytes of a tile's cells in `values`: stdSize, or stdSize - 2 for a SHORT tile with an odd cell count
+    uint32_t slotStride;       // multiple of 16, >= stdSize: a packing that overflowed its slot could not have won
+    uint32_t cand0;            // the element's candidates are entries cand0 .. cand0 + nAct - 1 of candLen / candStatus
+};
+struct GfRecordPlanArgs {
+    size_t nTiles;
+    int nElems;                // 1 .. GF_K_MAX_ELEMS
+    int nAct;                  // integer codecs in the list (0: everything is in standard form)
+    const uint32_t *candLen;   // per candidate array and tile [c * nTiles + t]: what the codec's encoder left in d_lengths ...
+    const int32_t *candStatus; // ... and in d_status
+    uint32_t *elemLen;         // per instance: n, the element's bytes in the record
+    uint32_t *elemPos;         // ... where its length word lies in the record
+    uint8_t *elemSrc;          // ... the winning candidate, or 255: the standard form
+    uint32_t *sizes;           // per record: its size, 0 for a record that is not written (an encoder failed)
+    int32_t *status;           // per record: GF_K_OK or the first negative encoder status (element order, then list order)
+    uint8_t *codecUsed;        // may be null; per instance: the winner's index in the codec list, or 255
+    uint8_t actIndex[256];     // candidate a is entry actIndex[a] of the codec list
+    GfRecEncElem elems[GF_K_MAX_ELEMS];
+};
+hipError_t gf_launch_record_plan(const GfRecordPlanArgs &a, hipStream_t stream);
+// offsets[0 .. nTiles] = exclusive 64-bit scan of sizes
+hipError_t gf_launch_record_scan(const uint32_t *sizes, uint64_t *offsets, size_t nTiles, hipStream_t stream);
+struct GfRecordWriteArgs {
+    size_t nTiles;
+    int nElems;
+    int checksum;              // != 0: the last word of a record is left to k_record_crc32c_write, else it is written as 0
+    const int32_t *tileIndices;
+    const uint32_t *elemLen, *elemPos;
+    const uint8_t *elemSrc;
+    const uint32_t *sizes;
+    const uint64_t *offsets;   // nTiles + 1 entries, multiples of 8
+    uint8_t *blob;             // 8-byte aligned
+    size_t blobCap;            // a record that would end behind it is skipped whole
+    GfRecEncElem elems[GF_K_MAX_ELEMS];
+};
+hipError_t gf_launch_record_write(const GfRecordWriteArgs &a, hipStream_t stream);
+// the CRC-32C of the first size - 4 bytes of every written record into its last word
+hipError_t gf_launch_record_crc32c_write(uint8_t *blob, size_t blobCap, const uint64_t *offsets, const uint32_t *sizes, size_t nTiles,
+                                         hipStream_t stream);
+// SHORT cells widened for the codecs: fill -> INT4_NULL_CODE (TileElementShort.java:211-219).  src 4-byte, dst 16-byte aligned
+hipError_t gf_launch_elem_widen(const int16_t *src, int32_t *dst, size_t nCells, int fill, hipStream_t stream);

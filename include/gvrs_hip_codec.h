@@ -485,7 +485,8 @@ gf_status gf_canon_analyze_batch(gf_context *ctx, int n_rows, int n_cols, size_t
 /* ---- tile records (gvrs/RecordManager.java:153-204, 217-262, 386-520; gvrs/TileElementInt.java:196-219,
  * gvrs/TileElementShort.java:211-250; util/GridfourCRC32C.java): what RecordManager.writeTile appends to the file for a
  * tile of one integer-coded element, for a whole batch of dirty tiles in one call (flush()) -- tiles of several elements and of
- * float / int-coded-float elements are read by gf_tile_record_decode_batch_elems[_dev] below:
+ * float / int-coded-float elements are read by gf_tile_record_decode_batch_elems[_dev] and written by
+ * gf_tile_record_encode_batch_elems[_dev] below:
  *   [int32 LE size, multiple of 8][type 2][0 0 0][int32 tileIndex][int32 n][n element bytes][zeros][CRC-32C | 0]
  * element bytes = CodecMaster packing, or the standard (raw little-endian) form when no codec is listed / produced a
  * packing / it is not shorter (codec_used[t] = 255).  GF_ELEM_SHORT: values are int16, widened with fill_value mapped to
@@ -583,6 +584,60 @@ gf_status gf_tile_record_decode_batch_elems(gf_context *ctx, const int *codecs, 
                                             int n_elems, int n_rows, int n_cols, size_t n_tiles, const uint8_t *blob,
                                             const uint64_t *offsets, int verify_checksum, int32_t *tile_indices,
                                             void *const *values, int32_t *status);
+
+/* ---- tile records of several elements WRITTEN, in device memory: framing and CRC-32C on the GPU -----------------------------
+ * (gvrs/RecordManager.java:386-490 writeTile, gvrs/RasterTile.java:234-256 getCompressedPacking, gvrs/TileElementInt.java:196-206,
+ * gvrs/TileElementShort.java:100-110, 211-229, gvrs/TileElementFloat.java:209-219, gvrs/CodecMaster.java:150-169, 261-280)
+ * What RecordManager.writeTile appends to the file for tiles of n_elems elements, the inverse of gf_tile_record_decode_batch_elems[_dev]:
+ *   [int32 LE size, multiple of 8][type 2][0 0 0][int32 tileIndex] { [int32 n][n bytes] per element, no padding between } [zeros][CRC-32C | 0]
+ *   size = multipleOf8(4 + sum(4 + n_e) + 12).  Element bytes = the CodecMaster packing (the strictly shortest non-null packing over
+ *   the list, list order on ties) or, when no codec produced one or it is not shorter than the standard size, the standard form:
+ *   the little-endian cells, 4 * cells bytes for INT, FLOAT and ICF, 2 * cells rounded up to a multiple of 4 for SHORT (the two
+ *   extra bytes zero).  A SHORT element goes to the codecs as int32 with cells equal to (int16)fill_i mapped to INT4_NULL_CODE.
+ *   hasValidData() and the free-space list are the record manager's business: the caller lists the tiles it wants written.
+ *   elems, codecs and the array d_values itself (n_elems pointers) are HOST memory; d_values[e] points to n_tiles * cells items of
+ *   element e in device memory, 4-byte aligned: int32 for INT, int16 for SHORT, float32 for FLOAT (cells move as bits) and, for
+ *   ICF, the int32 CODES the tile holds -- the float-to-code conversion is TileElementIntCodedFloat.setValue, a tile-cache
+ *   operation with range checks that throw, not part of writeTile.  The d_values[e] of a SHORT element must be readable to the
+ *   end of the aligned 4-byte word that holds its last cell (the kernels read whole aligned words).
+ *   d_offsets[n_tiles + 1]: record t is d_blob[d_offsets[t] .. d_offsets[t+1]), d_offsets[0] = 0.  d_blob is 8-byte aligned.
+ *   d_codec_used (may be NULL) is element-major, d_codec_used[e * n_tiles + t]: the winning list index, or 255 for the standard
+ *   form.  d_status[t]: GF_OK, or the first negative status of an encoder that failed on one of the tile's elements (the Java
+ *   encoder would throw; unlike gf_codec_master_encode_batch_i32 the failure is not forgiven when another codec packs the
+ *   tile): such a record has length 0 and nothing of it is written.  A candidate that is GF_DECLINED, GF_OVERFLOW (the slots are
+ *   at least as long as the standard form) or not shorter than the standard size simply loses.
+ *   Capacity as for gf_compact_dev: a record that would end behind blob_cap is skipped whole, d_offsets[n_tiles] > blob_cap tells
+ *   the caller; no byte at or behind blob_cap is written, and every byte of a written record is written exactly once per call.
+ * The device form takes lists of GF_CODEC_HUFFMAN and GF_CODEC_CANON_HUFFMAN entries, and GF_CODEC_NONE entries as long as no
+ * element is FLOAT; n_codecs == 0 is "compression disabled": everything in standard form.  GF_ERR_UNSUPPORTED, from the arguments
+ * alone: a list with GF_CODEC_DEFLATE or GF_CODEC_LSOP12 (its reference default carries a Deflate alternative), a GF_CODEC_NONE
+ * entry together with a FLOAT element (CodecFloat's zlib streams); and for both forms n_elems * n_tiles > 0x7fffffff, 2^28 or more
+ * cells in a tile, a record that could exceed 0x7fffffff bytes (gf_tile_record_max_bytes_elems).
+ * GF_ERR_ARG, before the device is touched: null pointers (ctx, codecs with n_codecs > 0, elems, tile indices, d_values or one of
+ * its entries, d_blob, d_offsets, d_status), n_elems < 1 or > GF_MAX_ELEMS, a type outside 0..3, an ICF scale that is 0 or NaN, a
+ * SHORT fill_i outside int16, a codec kind outside GF_CODEC_NONE .. GF_CODEC_LSOP12, n_codecs > 255, n_rows < 1, n_cols < 1, a
+ * d_blob that is not 8-byte or a d_values[e] that is not 4-byte aligned.  n_tiles == 0 is GF_OK.
+ * The device form ONLY ENQUEUES on `stream` and never synchronises it: every codec runs on every tile and the layout is a scan, so
+ * nothing has to come back to the host.  It grows buffers of the context on demand (candidate slots, their lengths and statuses,
+ * widened SHORT cells: hipMalloc / hipFree); a second call with the same or smaller arguments allocates nothing.  Whether it can be
+ * captured into a hipGraph after such a warm-up call has NOT been tested and is not claimed.
+ * gf_tile_record_encode_batch_elems is the call for host memory and takes any list.  A list the device form accepts is staged into
+ * buffers of the context and sent through the device form (not pipelined); any other list is encoded element by element with the
+ * host entry points (gf_codec_master_encode_batch_i32; gf_float_encode_batch_f32 under the index of the list's first GF_CODEC_NONE
+ * entry, zlib level 6 as the reference's sample files were written) and framed on host threads.  It returns the first negative
+ * per-tile status as its own, and GF_ERR_CAPACITY with offsets[n_tiles] filled in when blob_cap is too small, as
+ * gf_tile_record_encode_batch does.  gf_tile_record_max_bytes_elems: the size of a record whose elements are all in standard form
+ * (0 for arguments the calls refuse).                                                                                          */
+size_t gf_tile_record_max_bytes_elems(const gf_elem_spec *elems, int n_elems, int n_rows, int n_cols);
+gf_status gf_tile_record_encode_batch_elems_dev(gf_context *ctx, void *stream, const int *codecs, int n_codecs,
+                                                const gf_elem_spec *elems, int n_elems, int n_rows, int n_cols, size_t n_tiles,
+                                                const int32_t *d_tile_indices, const void *const *d_values, int checksum_enabled,
+                                                uint8_t *d_blob, size_t blob_cap, uint64_t *d_offsets, uint8_t *d_codec_used,
+                                                int32_t *d_status);
+gf_status gf_tile_record_encode_batch_elems(gf_context *ctx, const int *codecs, int n_codecs, const gf_elem_spec *elems,
+                                            int n_elems, int n_rows, int n_cols, size_t n_tiles, const int32_t *tile_indices,
+                                            const void *const *values, int checksum_enabled, uint8_t *blob, size_t blob_cap,
+                                            uint64_t *offsets, uint8_t *codec_used);
 
 /* ---- grid blocks: a rectangle of the raster read from tiles, and a raster cut into tiles, in device memory ------------------
  * (gvrs/GvrsElement.java:298-404 readBlock / readBlockInt, gvrs/TileAccessIndices.java:79-88, gvrs/GvrsFileSpecification.java:423-424)
