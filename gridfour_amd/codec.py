@@ -687,6 +687,7 @@ STANDARD_CODEC_LIST = (CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_NONE, CODEC_CANON_HUF
 ELEM_TYPES = {"int": 0, "short": 1, "float": 2, "icf": 3}                                 # GF_ELEM_*
 _ELEM_SPEC = np.dtype([("type", np.int32), ("fill_i", np.int32), ("scale", np.float32), ("offset", np.float32),
                        ("fill_f", np.float32)])                                           # gf_elem_spec
+_ELEM_RANGE = np.dtype([("min_i", np.int32), ("max_i", np.int32), ("min_f", np.float32), ("max_f", np.float32)])   # gf_elem_range
 
 
 class CodecMasterHip:
@@ -1004,6 +1005,112 @@ class CodecMasterHip:
         check(lib().gf_block_read_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, _ptr(grid), _ptr(rect), nt,
                                         _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), ptrs, _ptr(status)), "gf_block_read_elems")
         return out, status
+
+    # ---- grid blocks written: raster in, tile records out (gf_block_write_elems[_dev]) ----
+    @staticmethod
+    def _range_specs(specs, elems, ranges):
+        """ranges: None (the library's defaults: NULL is passed) or per element None | (min, max) -> gf_elem_range array or None"""
+        if ranges is None:
+            return None
+        out = np.zeros(len(elems), _ELEM_RANGE)
+        for e, el in enumerate(elems):
+            kind = el if isinstance(el, str) else el[0]
+            r = ranges[e]
+            if kind in ("int", "short"):
+                out[e]["min_i"], out[e]["max_i"] = ((INT4_NULL_CODE + 1, 2 ** 31 - 1) if kind == "int" else (-32767, 32767)) if r is None else r
+            elif kind == "float":
+                out[e]["min_f"], out[e]["max_f"] = (-np.inf, np.inf) if r is None else r
+            else:
+                scale, offset = np.float32(specs[e]["scale"]), np.float32(specs[e]["offset"])
+                default = (np.float32(INT4_NULL_CODE + 1) / scale + offset, np.float32(2 ** 31 - 2) / scale + offset)
+                out[e]["min_f"], out[e]["max_f"] = default if r is None else r
+        return out
+
+    def _block_write_args(self, nRows, nCols, grid_shape, rect, blocks, elems, fills, ranges, old):
+        specs, dtypes = self._elem_specs(elems)
+        self._fill_specs(specs, elems, fills)
+        rng = self._range_specs(specs, elems, ranges)
+        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
+        rect = np.ascontiguousarray(rect, np.int32)
+        n_block = int(rect[2]) * int(rect[3])
+        blocks = [np.ascontiguousarray(b, dtype=dt).reshape(-1) for b, dt in zip(blocks, dtypes)]
+        assert len(blocks) == len(dtypes) and all(b.size == n_block for b in blocks)
+        tr = tuple(C.c_int32() for _ in range(4))
+        check(lib().gf_block_tile_rect(_ptr(grid), _ptr(rect), *[C.byref(x) for x in tr]), "gf_block_tile_rect")
+        n_out = tr[2].value * tr[3].value
+        if old is None:
+            old_blob, old_off = np.zeros(16, np.uint8), np.zeros(1, np.uint64)
+        else:
+            old_blob = np.ascontiguousarray(old[0], dtype=np.uint8)
+            old_off = np.ascontiguousarray(old[1], dtype=np.uint64)
+        full = n_out * int(lib().gf_tile_record_max_bytes_elems(_ptr(specs), len(dtypes), nRows, nCols))
+        return specs, rng, grid, rect, blocks, n_out, old_blob, old_off, full
+
+    def write_block_dev(self, nRows, nCols, grid_shape, rect, blocks, elems, fills=None, ranges=None, old=None, checksums=True,
+                        verify_old_checksums=True, blob_cap=None, raw=False):
+        """gf_block_write_elems_dev: the rectangle rect = (row0, col0, n_rows, n_cols) of a grid of grid_shape cells cut into nRows x
+        nCols tiles is written from blocks (per element [n_rows, n_cols]: int32 / int16 / float32, an "icf" element's float VALUES)
+        as tile records.  fills as read_block_dev; ranges: None or per element None | (min, max); old = (blob, offsets): records the
+        file already holds, merged into partly covered tiles.  Uploads, calls, synchronises, downloads: (tile indices [n_out],
+        records: list[bytes], b"" for a tile without one, codec used [n_elems, n_out], status [n_out]); raw=True: (tile indices,
+        blob, offsets, codec used, status) with the whole blob of blob_cap bytes + 64 pre-filled with 0xA5."""
+        specs, rng, grid, rect, blocks, n_out, old_blob, old_off, full = self._block_write_args(nRows, nCols, grid_shape, rect, blocks, elems,
+                                                                                                fills, ranges, old)
+        ne, n_old = len(blocks), old_off.size - 1
+        cap = full if blob_cap is None else int(blob_cap)
+        d_blk = [DeviceBuffer(self.ctx, b.nbytes + 16).upload(b) for b in blocks]
+        d_oblob = DeviceBuffer(self.ctx, old_blob.size + 32).fill(0).upload(old_blob)
+        d_ooff = DeviceBuffer(self.ctx, old_off.nbytes + 16).upload(old_off)
+        d_blob = DeviceBuffer(self.ctx, max(cap, full) + 64).fill(0xA5)
+        d_off = DeviceBuffer(self.ctx, (n_out + 1) * 8 + 16).fill(0xff)
+        d_idx = DeviceBuffer(self.ctx, n_out * 4 + 16).fill(0x7f)
+        d_used = DeviceBuffer(self.ctx, ne * n_out + 16).fill(0)
+        d_st = DeviceBuffer(self.ctx, n_out * 4 + 16).fill(0x7f)
+        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_blk])
+        try:
+            check(lib().gf_block_write_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs),
+                                                 None if rng is None else _ptr(rng), ne, _ptr(grid), _ptr(rect), ptrs, n_old,
+                                                 d_oblob.ptr if n_old else None, int(old_off[-1]) if n_old else 0, d_ooff.ptr if n_old else None,
+                                                 int(bool(verify_old_checksums)), int(bool(checksums)), d_blob.ptr, cap, d_off.ptr, d_idx.ptr,
+                                                 d_used.ptr, d_st.ptr), "gf_block_write_elems_dev")
+            self.ctx.synchronize()
+            offsets = d_off.download(np.uint64, n_out + 1)
+            blob = d_blob.download(np.uint8, max(cap, full) + 64)
+            idx = d_idx.download(np.int32, n_out)
+            used = d_used.download(np.uint8, ne * n_out).reshape(ne, n_out)
+            status = d_st.download(np.int32, n_out)
+        finally:
+            for b in [d_oblob, d_ooff, d_blob, d_off, d_idx, d_used, d_st] + d_blk:
+                b.free()
+        if raw:
+            return idx, blob, offsets, used, status
+        return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
+
+    def write_block(self, nRows, nCols, grid_shape, rect, blocks, elems, fills=None, ranges=None, old=None, checksums=True,
+                    verify_old_checksums=True, blob_cap=None, return_code=False):
+        """The same through gf_block_write_elems, the host-memory form, which takes any codec list.  Returns (tile indices, records,
+        codec used, status); a negative per-tile status or too small a blob_cap raises as the library returns it, unless
+        return_code is set: then (the call's return value, tile indices, records, codec used, status, offsets) come back."""
+        specs, rng, grid, rect, blocks, n_out, old_blob, old_off, full = self._block_write_args(nRows, nCols, grid_shape, rect, blocks, elems,
+                                                                                                fills, ranges, old)
+        ne, n_old = len(blocks), old_off.size - 1
+        cap = full if blob_cap is None else int(blob_cap)
+        old_blob = np.concatenate([old_blob, np.zeros(16, np.uint8)])
+        blob = np.empty(max(cap, 16), np.uint8)
+        offsets = np.zeros(n_out + 1, np.uint64)
+        idx = np.full(n_out, -1, np.int32)
+        used = np.zeros((ne, n_out), np.uint8)
+        status = np.full(n_out, 0x7f7f7f7f, np.int32)
+        ptrs = (C.c_void_p * ne)(*[b.ctypes.data for b in blocks])
+        rc = lib().gf_block_write_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs),
+                                        None if rng is None else _ptr(rng), ne, _ptr(grid), _ptr(rect), ptrs, n_old,
+                                        _ptr(old_blob) if n_old else None, _ptr(old_off) if n_old else None, int(bool(verify_old_checksums)),
+                                        int(bool(checksums)), _ptr(blob), cap, _ptr(offsets), _ptr(idx), _ptr(used), _ptr(status))
+        if return_code:
+            fits = int(offsets[-1]) <= cap
+            return rc, idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) if fits else None for t in range(n_out)], used, status, offsets
+        check(rc, "gf_block_write_elems")
+        return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
 
     def packing_blob_dev(self, nRows, nCols, blob, offsets, lengths):
         """gf_codec_master_decode_batch_i32_dev: packing t = blob[offsets[t]:offsets[t]+lengths[t]].  Returns (values, status)."""

@@ -6,8 +6,6 @@
 
 #include "gvrs_api_internal.h"
 
-namespace {
-
 // what the host can check of the geometry; fills g
 gf_status blockGeom(const gf_grid_spec *grid, const gf_rect *rect, GfBlockGeom &g)
 {
@@ -35,6 +33,8 @@ gf_status firstOf(gf_status a, gf_status b)
     return a != GF_OK ? a : b;
 }
 
+namespace {
+
 // slot table pre-set to -1, k_block_slots over the records' tile indices, k_block_gather; elems: the device table of nElems
 // entries, or null for the one element `one`.  Enqueues only (the slot table grows before the first launch).
 gf_status gatherDev(gf_context *c, hipStream_t st, const GfBlockGeom &g, size_t nRecords, const int32_t *dTileIndices, const GfBlockElem *dElems,
@@ -60,6 +60,8 @@ gf_status gatherDev(gf_context *c, hipStream_t st, const GfBlockGeom &g, size_t 
     return GF_OK;
 }
 
+}  // namespace
+
 // the fill value's bits per element; a SHORT's must be an int16
 gf_status elemFills(const gf_elem_spec *elems, int nElems, uint32_t *fill)
 {
@@ -73,6 +75,8 @@ gf_status elemFills(const gf_elem_spec *elems, int nElems, uint32_t *fill)
     }
     return GF_OK;
 }
+
+namespace {
 
 gf_status blockReadArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const gf_grid_spec *grid,
                         const gf_rect *rect, size_t nRecords, const uint8_t *blob, bool blobOnDevice, const uint64_t *offsets,

@@ -113,14 +113,16 @@ struct gf_context {
                                                 // gather's element table and the records' tile indices, the slot table of the block's tiles
     DevBuf dRecMeta, dRecSub, dRecTmp;          // records / mixed packings in device memory (gvrs_api_records_dev.hip): per-record framing
                                                 // results, the partition by codec, decoded tiles on their way to their place
+    DevBuf dBwTiles, dBwMeta, dBwStage;         // a block written (gvrs_api_blocks_write.hip): the elements' cut tiles, the tiles' flags and pre-status
+                                                // (the host form: its results too), the host form's blocks, old records and records
     DevBuf dEncSlots, dEncMeta, dEncWide;       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots, their
                                                 // lengths / statuses and the records' layout, SHORT cells widened for the codecs
     std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
-    std::array<DevBuf *, 31> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
+    std::array<DevBuf *, 34> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
     {
         return {&workspace, &trees, &flags, &packRecs, &dValues, &dSlots, &dBlob, &dLengths, &dPred, &dStatus, &dOffsets, &dPlanes,
                 &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta, &dRecMeta, &dRecSub, &dRecTmp,
-                &dBlockTmp, &dBlockIdx, &dBlockSlots, &dEncSlots, &dEncMeta, &dEncWide};
+                &dBlockTmp, &dBlockIdx, &dBlockSlots, &dEncSlots, &dEncMeta, &dEncWide, &dBwTiles, &dBwMeta, &dBwStage};
     }
     gf_context()
     {
@@ -258,6 +260,23 @@ size_t elemItemBytes(int type);
 gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
                            int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets,
                            const uint32_t *dLengths, int verifyChecksum, int32_t *dTileIndices, void *const *dValues, int32_t *dStatus);
+// gvrs_api_records_enc.hip: the argument checks of the record writer, "this list needs nothing from the host", the one device
+// pipeline (dPreStatus, may be null: per tile a non-zero status that replaces the record) and the host encoders' path
+gf_status encArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows, int nCols,
+                  size_t nTiles, const int32_t *tileIndices, const void *const *values, const uint8_t *blob, size_t blobCap,
+                  const uint64_t *offsets, bool onDevice, const int32_t *dStatus);
+bool deviceList(const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems);
+gf_status recordsEncodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
+                           int nCols, size_t nTiles, const int32_t *dTileIndices, const void *const *dValues, int checksumEnabled,
+                           uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets, uint8_t *dCodecUsed, int32_t *dStatus,
+                           const int32_t *dPreStatus = nullptr);
+gf_status recordsEncodeHost(gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows, int nCols,
+                            size_t nTiles, const int32_t *tileIndices, const void *const *values, int checksumEnabled, uint8_t *blob,
+                            size_t blobCap, uint64_t *offsets, uint8_t *codecUsed);
+// gvrs_api_blocks.hip: the geometry of a block call (what the host can check; fills g), ARG before UNSUPPORTED, the fills' bits
+gf_status blockGeom(const gf_grid_spec *grid, const gf_rect *rect, GfBlockGeom &g);
+gf_status firstOf(gf_status a, gf_status b);
+gf_status elemFills(const gf_elem_spec *elems, int nElems, uint32_t *fill);
 // gvrs_api_records.hip
 size_t elemStandardSize(int elemType, size_t cells);
 // gvrs_api_deflate.hip

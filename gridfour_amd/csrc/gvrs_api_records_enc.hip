@@ -11,6 +11,8 @@ namespace {
 
 bool isIntElem(int type) { return type != GF_ELEM_FLOAT; }
 
+}  // namespace
+
 // what the host can check without a device; values / blob / offsets: device or host pointers, only looked at for null and alignment
 gf_status encArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows, int nCols,
                   size_t nTiles, const int32_t *tileIndices, const void *const *values, const uint8_t *blob, size_t blobCap,
@@ -47,10 +49,12 @@ bool deviceList(const int *codecs, int nCodecs, const gf_elem_spec *elems, int n
 }
 
 // the one device pipeline (no lock taken, no argument checked).  Enqueues only: every codec runs on every tile and the layout is a
-// scan, so nothing has to come back to the host.
+// scan, so nothing has to come back to the host.  dPreStatus (may be null), per tile: a non-zero entry is the tile's status and the
+// tile gets no record (k_record_plan); the encoders run on such a tile all the same.
 gf_status recordsEncodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
                            int nCols, size_t nTiles, const int32_t *dTileIndices, const void *const *dValues, int checksumEnabled,
-                           uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets, uint8_t *dCodecUsed, int32_t *dStatus)
+                           uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets, uint8_t *dCodecUsed, int32_t *dStatus,
+                           const int32_t *dPreStatus)
 {
     if (nCodecs < 0) nCodecs = 0;
     const size_t cells = (size_t)nRows * (size_t)nCols, n = nTiles, nInst = (size_t)nElems * n;
@@ -121,6 +125,7 @@ gf_status recordsEncodeDev(gf_context *c, void *stream, const int *codecs, int n
     p.sizes = sizes;
     p.status = dStatus;
     p.codecUsed = dCodecUsed;
+    p.preStatus = dPreStatus;
     GF_HIP(gf_launch_record_plan(p, st));
     GF_HIP(gf_launch_record_scan(sizes, dOffsets, n, st));
     GfRecordWriteArgs w{};
@@ -245,8 +250,6 @@ gf_status recordsEncodeHost(gf_context *c, const int *codecs, int nCodecs, const
     });
     return GF_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -525,6 +525,41 @@ struct GfGridCutArgs {
 };
 hipError_t gf_launch_grid_cut(const GfGridCutArgs &a, hipStream_t stream);
 
+// A block WRITTEN (gvrs_blocks_write.hip; driven by gvrs_api_blocks_write.hip): the rectangle's cells of every element cut into the
+// tiles of the rectangle of tiles in the type the record writer takes (k_block_cut_elems: TileElement*.setValue with its range
+// checks, RasterTile.hasValidData), and the per-tile verdict the record writer receives as its pre-status (k_block_write_verdict).
+constexpr uint32_t GF_BW_FLAG_BOUNDS = 1u, GF_BW_FLAG_VALID = 2u;   // a tile's flags word: a cell out of range; a cell that is not fill
+struct GfBlockCutElem {        // an element of the block, in the kernel arguments (56 bytes): nothing is uploaded, so the call only enqueues
+    const void *block;         // nRows * nCols items, row-major: int32 (INT), int16 (SHORT), float32 (FLOAT and the VALUES of an ICF)
+    void *tiles;               // tile k of the rectangle of tiles at tiles + k * cells items: int32, int16, float bits, int32 codes
+    const void *oldTiles;      // may be null; decoded tiles of the old records in the tiles' type, record j at oldTiles + j * cells items
+    int32_t type;              // GF_K_ELEM_*
+    uint32_t fillBits;         // what a tile holds where nothing was written: fill_i (SHORT: the low 16 bits; ICF: the code), fill_f's bits
+    uint32_t fillFBits;        // ICF: fill_f's bits, the VALUE that converts to the code fillBits
+    uint32_t minBits, maxBits; // the accepted range: int32 for INT and SHORT, float bits for FLOAT and ICF
+    float scale, offset;       // ICF: code = floor((v - offset) * scale + 0.5)
+    uint32_t pad_;
+};
+struct GfBlockCutElemsArgs {
+    int nElems;
+    const int32_t *slots;         // may be null (no old records); per tile of the rectangle of tiles: the winning old record or -1
+    uint32_t *flags;              // per tile of the rectangle of tiles, pre-zeroed: GF_BW_FLAG_* of all elements, by atomicOr
+    GfBlockGeom g;
+    GfBlockCutElem elems[GF_K_MAX_ELEMS];
+};
+hipError_t gf_launch_block_cut_elems(const GfBlockCutElemsArgs &a, hipStream_t stream);
+struct GfBlockWriteVerdictArgs {
+    const uint32_t *flags;
+    const int32_t *slots;         // may be null
+    const int32_t *oldStatus;     // with slots: the old records' statuses, element-major [e * nOld + record]
+    size_t nOld;
+    int nElems;
+    int32_t *preStatus;           // per tile: 0, or what the tile gets in place of a record (old-record failure, ERR_BOUNDS, DECLINED)
+    int32_t *tileIndices;         // per tile: its index on the grid
+    GfBlockGeom g;
+};
+hipError_t gf_launch_block_write_verdict(const GfBlockWriteVerdictArgs &a, hipStream_t stream);
+
 // Tile records written in device memory (gvrs_records_enc.hip; driven by gvrs_api_records_enc.hip): the mirror image of the read
 // side above.  Every integer codec of the list has encoded every integer element of every tile into a slot of its own (a
 // CANDIDATE: candidate a of an element is the a-th integer codec of the list); k_record_plan picks the winners and lays the
@@ -550,6 +585,8 @@ struct GfRecordPlanArgs {
     uint32_t *sizes;           // per record: its size, 0 for a record that is not written (an encoder failed)
     int32_t *status;           // per record: GF_K_OK or the first negative encoder status (element order, then list order)
     uint8_t *codecUsed;        // may be null; per instance: the winner's index in the codec list, or 255
+    const int32_t *preStatus;  // may be null; per record, non-zero: the record is not written (size 0), its status is this value and
+                               // its codecUsed entries are 255, whatever the encoders said (a block write's verdict on the tile)
     uint8_t actIndex[256];     // candidate a is entry actIndex[a] of the codec list
     GfRecEncElem elems[GF_K_MAX_ELEMS];
 };

@@ -47,8 +47,9 @@ __global__ __launch_bounds__(256) void k_elem_widen(const int16_t *__restrict__ 
 // shortest non-null packing, list order on ties -- as gf_codec_master_encode_batch_i32 decides) and the per-element rule "not
 // shorter than the standard form -> the standard form" (TileElementInt.java:198-204): a candidate that declined, overflowed its
 // slot (the slot is at least as long as the standard form) or measures >= the standard size loses.  An encoder that failed (a
-// negative status: the Java encoder would throw) fails the record: size 0, nothing of it is written.  The element descriptions
-// are kernel arguments (scalar loads).
+// negative status: the Java encoder would throw) fails the record: size 0, nothing of it is written; a non-zero pre-status (a block
+// write's verdict: an unreadable old record, a cell out of range, no valid data) does the same and is the record's status.  The
+// element descriptions are kernel arguments (scalar loads).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_record_plan(const GfRecordPlanArgs a)
 {
@@ -80,6 +81,12 @@ __global__ __launch_bounds__(256) void k_record_plan(const GfRecordPlanArgs a)
         a.elemSrc[i] = (uint8_t)best;
         if (a.codecUsed) a.codecUsed[i] = best == 255u ? (uint8_t)255u : a.actIndex[best];
         pos += 4u + n;
+    }
+    const int32_t pre = a.preStatus ? a.preStatus[t] : 0;                   // the caller's verdict comes before the encoders'
+    if (pre != 0) {
+        st = pre;
+        if (a.codecUsed)
+            for (int e = 0; e < a.nElems; e++) a.codecUsed[(size_t)e * a.nTiles + t] = (uint8_t)255u;
     }
     a.sizes[t] = st == GF_K_OK ? ((pos + 4u + 7u) & ~7u) : 0u;               // multipleOf8(4 + content + RECORD_OVERHEAD_SIZE)
     a.status[t] = st;

@@ -598,7 +598,7 @@ gf_status gf_tile_record_decode_batch_elems(gf_context *ctx, const int *codecs, 
  *   elems, codecs and the array d_values itself (n_elems pointers) are HOST memory; d_values[e] points to n_tiles * cells items of
  *   element e in device memory, 4-byte aligned: int32 for INT, int16 for SHORT, float32 for FLOAT (cells move as bits) and, for
  *   ICF, the int32 CODES the tile holds -- the float-to-code conversion is TileElementIntCodedFloat.setValue, a tile-cache
- *   operation with range checks that throw, not part of writeTile.  The d_values[e] of a SHORT element must be readable to the
+ *   operation with range checks that throw, not part of writeTile (gf_block_write_elems_dev below does it).  The d_values[e] of a SHORT element must be readable to the
  *   end of the aligned 4-byte word that holds its last cell (the kernels read whole aligned words).
  *   d_offsets[n_tiles + 1]: record t is d_blob[d_offsets[t] .. d_offsets[t+1]), d_offsets[0] = 0.  d_blob is 8-byte aligned.
  *   d_codec_used (may be NULL) is element-major, d_codec_used[e * n_tiles + t]: the winning list index, or 255 for the standard
@@ -688,6 +688,74 @@ gf_status gf_block_read_elems_dev(gf_context *ctx, void *stream, const int *code
 gf_status gf_block_read_elems(gf_context *ctx, const int *codecs, int n_codecs, const gf_elem_spec *elems, int n_elems,
                               const gf_grid_spec *grid, const gf_rect *rect, size_t n_records, const uint8_t *blob,
                               const uint64_t *offsets, int verify_checksum, void *const *blocks, int32_t *status);
+
+/* ---- a grid block WRITTEN: raster in, tile records out, in device memory ------------------------------------------------------
+ * (gvrs/TileElementInt.java:118-126, TileElementShort.java:136-143, TileElementFloat.java:133-149, TileElementIntCodedFloat.java:152-169
+ * setValue / setIntValue; TileElement*.hasValidData, gvrs/RasterTile.java:215-222; gvrs/RecordManager.java:386-490 writeTile, :413-419)
+ * What the reference's tile cache and record manager produce when a rectangle of the raster is stored: the composition of the cut
+ * (gf_tiles_from_block_dev), the tile cache's range checks and float-to-code conversion, its "has valid data" verdict, the merge
+ * with what the file already holds, and gf_tile_record_encode_batch_elems_dev.
+ *   gf_block_tile_rect: the rectangle of tiles a rect touches, first tile row / column and the counts (host arithmetic only).
+ *   OUTPUT: one entry per tile of that rectangle of tiles, n_out = n_tile_rows * n_tile_cols, row-major.  d_tile_indices[j]: the
+ *   tile's index on the grid.  Record j is d_blob[d_offsets[j] .. d_offsets[j+1]), n_out + 1 offsets, d_offsets[0] = 0; d_codec_used
+ *   (may be NULL, element-major) and d_status[j] (per tile) as gf_tile_record_encode_batch_elems_dev defines them, the same capacity
+ *   rule (a record that would end behind blob_cap is skipped whole), d_blob 8-byte aligned.  A tile that gets no record (a status
+ *   other than GF_OK) has length 0 and 255 in its d_codec_used entries.
+ *   INPUT: d_blocks (a HOST array of n_elems device pointers, each 4-byte aligned): the rectangle's cells, row-major, in the type a
+ *   user writes: int32 (INT), int16 (SHORT), float32 (FLOAT) and float32 VALUES for ICF, not codes.  A cell whose grid coordinate
+ *   lies in the rectangle takes the block's value; every other cell of a tile, those beyond the grid included, takes the element's
+ *   fill: fill_i for INT and SHORT, the code fill_i for ICF, fill_f for FLOAT -- unless the tile has an old record, see below.
+ *   ICF, per cell, as setValue: bits equal to fill_f's (any NaN matches a NaN fill, +0.0 and -0.0 differ: Float.equals) -> the code
+ *   fill_i; else min_f <= v <= max_f -> (int) Math.floor((double)((v - offset) * scale) + 0.5), the subtraction and the product each
+ *   rounded once in float32, the cast saturating as Java's; else out of range.
+ *   RANGES (ranges[e]; NULL: the reference's default constructors): INT [INT_MIN + 1, INT_MAX] and SHORT [-32767, 32767]: a cell
+ *   passes when it is in [min_i, max_i] or equals the fill; FLOAT [-inf, +inf]: in [min_f, max_f] or its bits equal the fill's as
+ *   above (a NaN with a non-NaN fill is out of range); ICF min_f = (float)(INT_MIN + 1) / scale + offset, max_f = (float)(INT_MAX - 1)
+ *   / scale + offset in float32 (min_i / max_i are not consulted).  Any out-of-range cell of any element gives the tile
+ *   GF_ERR_BOUNDS and no record (the reference throws IllegalArgumentException).
+ *   NO VALID DATA: a tile in which every element is all fill after the merge (INT, SHORT: v != fill; ICF: code != fill_i; FLOAT with
+ *   a NaN fill: !isnan(v), with another fill the float comparison v != fill) gets GF_DECLINED and no record: writeTile writes
+ *   nothing for it and frees its old record, which the caller learns from the status.
+ *   OLD RECORDS (n_old may be 0, the three arguments then NULL): records the file already holds, in any order, decoded with
+ *   gf_tile_record_decode_batch_elems_dev's pipeline (ICF elements as their codes) into a temporary of the context.  Of two records
+ *   of one tile the later wins.  A partly covered tile with an old record keeps the old cells outside the rectangle; without one
+ *   it is a new tile and takes fill there.  If the winning old record of a partly covered tile has an element whose status is not
+ *   GF_OK, the tile gets that status (the first such element) and no record.  OLD RECORDS OF WHOLLY COVERED TILES, AND OF TILES
+ *   OUTSIDE THE RECTANGLE, ARE DECODED AND IGNORED, as in the block read.
+ *   LIMITATION: an old record whose HEADER cannot be read (its size field too small, too large or no multiple of 8, a record type
+ *   other than a tile's) names no tile, as in the block read, and the old records' statuses are not returned: a partly covered
+ *   tile whose only, or later, old record is damaged in this way is treated as a tile the file does not hold yet -- written with
+ *   fill outside the rectangle, status GF_OK -- and the earlier of two records wins when the later one's header is damaged.  A
+ *   caller that cannot trust its record headers decodes them first (gf_tile_record_decode_batch_elems_dev reports every record).
+ *   A tile's status, first match: old-record failure, GF_ERR_BOUNDS, GF_DECLINED, the record writer's own verdict.
+ * With n_old == 0 the device form ONLY ENQUEUES on `stream` and never synchronises; with old records it synchronises `stream` once,
+ * as the decode does.  Graph capture is not claimed for either.  It grows buffers of the context on demand (cut tiles, flags, and
+ * the block read's temporaries and slot table for the old records): a context's block reads, gathers and block writes belong on ONE
+ * stream, or are ordered by the caller.
+ * The device form takes the codec lists gf_tile_record_encode_batch_elems_dev takes (GF_ERR_UNSUPPORTED otherwise, from the arguments
+ * alone).  GF_ERR_ARG, before the context or a device is looked at: whatever the block calls above reject of grid and rect,
+ * whatever gf_tile_record_encode_batch_elems[_dev] rejects (n_rows, n_cols: the tile's; d_values: d_blocks) and, with n_old > 0,
+ * gf_tile_record_decode_batch_elems[_dev]; a NULL d_status / status; a ranges[e] with min > max or a NaN float bound.
+ * gf_block_write_elems is the same for host memory (no stream; old_offsets[n_old] bytes of old_blob are read) and takes any list:
+ * it stages blocks and old records into buffers of the context and runs the same decode and cut; a list the device form accepts goes
+ * through the device pipeline, any other list (one with CodecDeflate, as every standard list) brings the cut tiles and verdicts back
+ * and sends the tiles that get a record through the host encoders of gf_tile_record_encode_batch_elems.  Every array is filled in;
+ * it returns the first negative per-tile status as its own (GF_DECLINED is not an error), else GF_ERR_CAPACITY with
+ * offsets[n_out] filled in when blob_cap is too small.                                                                          */
+typedef struct gf_elem_range { int32_t min_i, max_i; float min_f, max_f; } gf_elem_range;
+gf_status gf_block_tile_rect(const gf_grid_spec *grid, const gf_rect *rect, int32_t *tile_row0, int32_t *tile_col0,
+                             int32_t *n_tile_rows, int32_t *n_tile_cols);
+gf_status gf_block_write_elems_dev(gf_context *ctx, void *stream, const int *codecs, int n_codecs, const gf_elem_spec *elems,
+                                   const gf_elem_range *ranges, int n_elems, const gf_grid_spec *grid, const gf_rect *rect,
+                                   const void *const *d_blocks, size_t n_old, const uint8_t *d_old_blob, size_t old_blob_bytes,
+                                   const uint64_t *d_old_offsets, int verify_old_checksum, int checksum_enabled, uint8_t *d_blob,
+                                   size_t blob_cap, uint64_t *d_offsets, int32_t *d_tile_indices, uint8_t *d_codec_used,
+                                   int32_t *d_status);
+gf_status gf_block_write_elems(gf_context *ctx, const int *codecs, int n_codecs, const gf_elem_spec *elems,
+                               const gf_elem_range *ranges, int n_elems, const gf_grid_spec *grid, const gf_rect *rect,
+                               const void *const *blocks, size_t n_old, const uint8_t *old_blob, const uint64_t *old_offsets,
+                               int verify_old_checksum, int checksum_enabled, uint8_t *blob, size_t blob_cap, uint64_t *offsets,
+                               int32_t *tile_indices, uint8_t *codec_used, int32_t *status);
 
 /* ---- CodecFloat (compress/CodecFloat.java:328-458): float32 tiles ---------------------------
  * The five byte planes (sign bits, exponent, three byte-delta coded mantissa bytes) are split and
