@@ -67,6 +67,53 @@ class GvrsHipContext:
                                             int(fill_bits) & 0xffffffff, int(bool(keep_outside)), d_block, int(n_tiles), d_tile_indices,
                                             d_tiles, d_status), "gf_tiles_from_block_dev")
 
+    # ---- a grid block interpolated: B-spline value, derivatives, unit normal (gf_block_interp_*) ----
+    @staticmethod
+    def _interp_out(out):
+        o = np.zeros(1, _INTERP_OUT)
+        for k, v in out.items():
+            o[k] = 0 if v is None else (v.value if isinstance(v, C.c_void_p) else int(v)) or 0
+        return o
+
+    def interp_points_dev(self, spec, d_block, n_points, d_rows, d_cols, out, d_col_spacing=None, stream=None):
+        """gf_block_interp_points_dev on device pointers: spec from interp_spec(), out a dict of device pointers under the names
+        z, zx, zy, zxx, zxy, zyy, normal (3 doubles per point), status (int32); all but z may be missing.  Enqueues only."""
+        o = self._interp_out(out)
+        check(lib().gf_block_interp_points_dev(self._h, stream, _ptr(spec), d_block, int(n_points), d_rows, d_cols, d_col_spacing, _ptr(o)),
+              "gf_block_interp_points_dev")
+
+    def interp_lattice_dev(self, spec, d_block, lattice, out, d_col_spacing_rows=None, stream=None):
+        """gf_block_interp_lattice_dev: lattice = (row0, col0, row_step, col_step, n_rows, n_cols); point (i, j) is row0 + i *
+        row_step, col0 + j * col_step; outputs row-major n_rows x n_cols; d_col_spacing_rows: one spacing per lattice row.
+        Enqueues only."""
+        lat = np.zeros(1, _INTERP_LATTICE)
+        lat["row0"], lat["col0"], lat["row_step"], lat["col_step"], lat["n_rows"], lat["n_cols"] = lattice
+        o = self._interp_out(out)
+        check(lib().gf_block_interp_lattice_dev(self._h, stream, _ptr(spec), d_block, _ptr(lat), d_col_spacing_rows, _ptr(o)),
+              "gf_block_interp_lattice_dev")
+
+    def interp_points(self, spec, block, rows, cols, col_spacing=None):
+        """gf_block_interp_points, the host-memory form (staged by the library): block is the rectangle spec["block"] of the raster
+        in the element's delivered dtype, rows / cols grid coordinates.  Returns a dict: z and status [n] always; zx, zy and normal
+        [n, 3] with target >= INTERP_FIRST; zxx, zxy, zyy with INTERP_SECOND.  A point whose status is not 0 is NaN throughout."""
+        rows, cols = np.ascontiguousarray(rows, np.float64).ravel(), np.ascontiguousarray(cols, np.float64).ravel()
+        assert rows.size == cols.size
+        n, target = rows.size, int(spec["target"][0])
+        dt = {0: np.int32, 1: np.int16, 2: np.float32, 3: np.float32}[int(spec["elem_type"][0])]
+        block = np.ascontiguousarray(block, dt)
+        assert block.size == int(spec["block"][0][2]) * int(spec["block"][0][3])
+        names = ["z"] + (["zx", "zy"] if target >= INTERP_FIRST else []) + (["zxx", "zxy", "zyy"] if target >= INTERP_SECOND else [])
+        res = {k: np.zeros(n, np.float64) for k in names}
+        if target >= INTERP_FIRST:
+            res["normal"] = np.zeros((n, 3), np.float64)
+        res["status"] = np.zeros(n, np.int32)
+        cs = None if col_spacing is None else np.ascontiguousarray(col_spacing, np.float64).ravel()
+        assert cs is None or cs.size == n
+        o = self._interp_out({k: a.ctypes.data for k, a in res.items()})
+        check(lib().gf_block_interp_points(self._h, _ptr(spec), _ptr(block), n, _ptr(rows), _ptr(cols), None if cs is None else _ptr(cs),
+                                           _ptr(o)), "gf_block_interp_points")
+        return res
+
     def close(self):
         if self._h:
             lib().gf_context_destroy(self._h)
@@ -77,6 +124,33 @@ class GvrsHipContext:
             self.close()
         except Exception:
             pass
+
+
+INTERP_VALUE, INTERP_FIRST, INTERP_SECOND = 0, 1, 2                      # GF_INTERP_*
+_INTERP_SPEC = np.dtype([("n_rows_grid", np.int32), ("n_cols_grid", np.int32), ("block", np.int32, 4), ("elem_type", np.int32),
+                         ("fill_i", np.int32), ("wrap", np.int32), ("target", np.int32), ("row_spacing", np.float64),
+                         ("col_spacing", np.float64), ("row_fringe0", np.float64), ("row_fringe1", np.float64),
+                         ("col_fringe0", np.float64), ("col_fringe1", np.float64)], align=True)                      # gf_interp_spec
+_INTERP_OUT = np.dtype([(k, np.uint64) for k in ("z", "zx", "zy", "zxx", "zxy", "zyy", "normal", "status")])        # gf_interp_out
+_INTERP_LATTICE = np.dtype([("row0", np.float64), ("col0", np.float64), ("row_step", np.float64), ("col_step", np.float64),
+                            ("n_rows", np.int64), ("n_cols", np.int64)])                                            # gf_interp_lattice
+
+
+def interp_spec(n_rows_grid, n_cols_grid, block=None, elem_type="float", fill_i=0, wrap=0, target=INTERP_VALUE, row_spacing=1.0,
+                col_spacing=1.0, row_fringe=None, col_fringe=None):
+    """A gf_interp_spec: the raster's size, the rectangle block = (row0, col0, n_rows, n_cols) of it that the block holds (None:
+    all of it), the element ("int", "short", "float", "icf" or GF_ELEM_*; fill_i: the cell of an int / short element that reads as
+    NaN), wrap (0; 1 the longitudes wrap; 2 they wrap and bracket), the target and the spacings dv, du of the derivatives.
+    The default fringe is (-0.5, n - 0.5) per axis: the reference widens it by 4 ulp of the MODEL coordinates at the raster's
+    edge (GvrsFileSpecification.java:437-440), which the library does not know -- a caller that has them passes the fringes."""
+    s = np.zeros(1, _INTERP_SPEC)
+    s["n_rows_grid"], s["n_cols_grid"] = n_rows_grid, n_cols_grid
+    s["block"] = (0, 0, n_rows_grid, n_cols_grid) if block is None else block
+    s["elem_type"] = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else elem_type
+    s["fill_i"], s["wrap"], s["target"], s["row_spacing"], s["col_spacing"] = fill_i, wrap, target, row_spacing, col_spacing
+    s["row_fringe0"], s["row_fringe1"] = (-0.5, n_rows_grid - 0.5) if row_fringe is None else row_fringe
+    s["col_fringe0"], s["col_fringe1"] = (-0.5, n_cols_grid - 0.5) if col_fringe is None else col_fringe
+    return s
 
 
 # struct gf_codec_stats (include/gvrs_hip_codec.h) = the sums of compress/CodecStats.java

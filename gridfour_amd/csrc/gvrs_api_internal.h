@@ -117,12 +117,13 @@ struct gf_context {
                                                 // (the host form: its results too), the host form's blocks, old records and records
     DevBuf dEncSlots, dEncMeta, dEncWide;       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots, their
                                                 // lengths / statuses and the records' layout, SHORT cells widened for the codecs
+    DevBuf dInterp;                             // interpolation, host form (gvrs_api_interp.hip): block, coordinates, spacings and outputs
     std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
-    std::array<DevBuf *, 34> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
+    std::array<DevBuf *, 35> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
     {
         return {&workspace, &trees, &flags, &packRecs, &dValues, &dSlots, &dBlob, &dLengths, &dPred, &dStatus, &dOffsets, &dPlanes,
                 &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta, &dRecMeta, &dRecSub, &dRecTmp,
-                &dBlockTmp, &dBlockIdx, &dBlockSlots, &dEncSlots, &dEncMeta, &dEncWide, &dBwTiles, &dBwMeta, &dBwStage};
+                &dBlockTmp, &dBlockIdx, &dBlockSlots, &dEncSlots, &dEncMeta, &dEncWide, &dBwTiles, &dBwMeta, &dBwStage, &dInterp};
     }
     gf_context()
     {

@@ -7,6 +7,8 @@
 
 #include <mutex>
 
+#include "gvrs_interp_common.h"
+
 // per-tile status values written by the kernels; identical to gf_status in
 // include/gvrs_hip_codec.h
 #define GF_K_OK 0
@@ -612,3 +614,21 @@ hipError_t gf_launch_record_crc32c_write(uint8_t *blob, size_t blobCap, const ui
                                          hipStream_t stream);
 // SHORT cells widened for the codecs: fill -> INT4_NULL_CODE (TileElementShort.java:211-219).  src 4-byte, dst 16-byte aligned
 hipError_t gf_launch_elem_widen(const int16_t *src, int32_t *dst, size_t nCells, int fill, hipStream_t stream);
+
+// B-spline interpolation over a grid block in device memory (gvrs_interp.hip; driven by gvrs_api_interp.hip): a lane per point.
+// Points form: rows / cols (and colSpacing, may be null: g.colSpacing) per point.  Lattice form (rows == null): point t is
+// (i, j) = (t / latCols, t % latCols), row = latRow0 + (double)i * latRowStep, col = latCol0 + (double)j * latColStep, each one
+// product and one sum, and colSpacing (may be null) is per lattice ROW.  Every output pointer may be null except z; normal holds 3
+// items per point.  Every output item of every point is written exactly once.  gf_launch_interp sends a lattice with one column
+// spacing to k_interp_lattice (a workgroup per patch of the output), everything else to k_interp_points.
+struct GfInterpArgs {
+    GfInterpGeom g;
+    const void *block;
+    size_t nPoints;
+    const double *rows, *cols, *colSpacing;
+    double latRow0, latCol0, latRowStep, latColStep;
+    uint64_t latRows, latCols;
+    double *z, *zx, *zy, *zxx, *zxy, *zyy, *normal;
+    int32_t *status;
+};
+hipError_t gf_launch_interp(const GfInterpArgs &a, hipStream_t stream);

@@ -689,6 +689,68 @@ gf_status gf_block_read_elems(gf_context *ctx, const int *codecs, int n_codecs, 
                               const gf_grid_spec *grid, const gf_rect *rect, size_t n_records, const uint8_t *blob,
                               const uint64_t *offsets, int verify_checksum, void *const *blocks, int32_t *status);
 
+/* ---- a grid block INTERPOLATED: B-spline value, derivatives and unit normal at a batch of grid coordinates ---------------------
+ * (gvrs/GvrsInterpolatorBSpline.java:327-334 zInterpGrid, :283-304 zNormalGrid, :374-445 loadSamples, :447-484 loadWrappingSamples,
+ * :307-314 blockLimit; interpolation/InterpolatorBSpline.java:159-379 interpolate; InterpolationResult.java:129-139 getUnitNormal)
+ * For every query point (row, column), doubles in GRID coordinates, the reference reads the 4 x 4 block of cells around it and
+ * evaluates a bicubic B-spline on the 16 samples.  These calls do the same for a batch of points over a block that lies in device
+ * memory (what gf_block_read_elems_dev delivers: d_block holds the rectangle spec->block, row-major, in the element's delivered
+ * type, aligned to its item size), BIT FOR BIT: the window is chosen as loadSamples / loadWrappingSamples choose it, the evaluation is
+ * interpolate(1.0 + v, 1.0 + u, 4, 4, z, row_spacing, column_spacing, target) with its own floor and outer-band adjustments, every
+ * operation in the reference's order, in double, without fused multiply-add.
+ *   z is what zInterpGrid returns; with target GF_INTERP_FIRST zx, zy and normal are what zNormalGrid's result holds (normal:
+ *   getUnitNormal, 3 doubles per point, interleaved); with GF_INTERP_SECOND zxx, zxy (= zyx), zyy as well.  An output array the
+ *   target does not compute is filled with NaN, as the reference sets those fields (InterpolatorBSpline.java:295-300, :372-375).
+ *   SAMPLES: FLOAT and ICF cells are used as they are; an INT or SHORT cell equal to fill_i reads as NaN, any other as (float) cell
+ *   (TileElementInt.java:150-156, TileElementShort.java:167-173), widened to double (InterpolatorBSpline.java:231-249).
+ *   wrap: 0, or what GvrsFileSpecification reports: 1 doGeographicCoordinatesWrapLongitude, 2 ... and ...BracketLongitude
+ *   (nColsForWrap = n_cols_grid - 1, GvrsInterpolatorBSpline.java:139-143).  The fringes are GvrsFileSpecification.java:437-440.
+ *   NOT DONE HERE, left to the caller: mapModelToGridPoint / mapGeographicToGridPoint, and zNormal's column spacing
+ *   cos(latitude) * du with its dx < 1 -> 1 clamp (:291-299; libm's cosine does not reproduce bit for bit): pass the resulting
+ *   column spacing per point (d_col_spacing) or per lattice row (d_col_spacing_rows); NULL: spec->col_spacing for all.
+ *   LATTICE FORM: point (i, j), 0 <= i < n_rows, 0 <= j < n_cols, has row = row0 + (double)i * row_step, col = col0 + (double)j *
+ *   col_step, one product and one sum, each rounded once; outputs are row-major n_rows x n_cols.  It gives the bits the points
+ *   form gives for those coordinates (one kernel serves both).
+ *   PER-POINT STATUS (out->status, may be NULL), first match: GF_ERR_ARG a NaN coordinate (interpolate throws); GF_DECLINED outside
+ *   the fringe (the reference returns NaN / a nullified result); GF_ERR_ARG a wrapped window the reference's readBlock rejects
+ *   (n1 < 1 or n2 < 1, GvrsElement.java:457-460); GF_ERR_BOUNDS the 4 x 4 window, or either part of a wrapped one, is not wholly
+ *   inside spec->block; GF_ERR_ARG a zero column spacing for the point with target >= GF_INTERP_FIRST (:304-307); else GF_OK.
+ *   With any status other than GF_OK every output array passed receives NaN for that point.  Every output item is written
+ *   exactly once.
+ * The device forms ONLY ENQUEUE on `stream` (NULL: the context's), allocate nothing, never synchronise and are safe for hipGraph
+ * capture.  gf_block_interp_points is the same for block, coordinates and outputs in host memory, staged through a buffer of the
+ * context: a convenience, not a rate.
+ * GF_ERR_ARG, before the context or a device is looked at: a NULL ctx, spec, block, out or out->z; NULL coordinate arrays with
+ * n_points > 0; a grid under 4 x 4 (the reference's constructor throws, :113-116); a block not wholly inside the grid or under
+ * 4 x 4; an elem_type, wrap or target out of range; a SHORT fill_i outside int16; with target >= GF_INTERP_FIRST a zero
+ * row_spacing, or a zero col_spacing without per-point / per-row spacings; normal with target GF_INTERP_VALUE; a NULL lattice
+ * or a lattice count below 1.  GF_ERR_UNSUPPORTED: a lattice of 2^63 or more points.  n_points == 0: GF_OK.                      */
+#define GF_INTERP_VALUE 0
+#define GF_INTERP_FIRST 1
+#define GF_INTERP_SECOND 2
+typedef struct gf_interp_spec {
+    int32_t n_rows_grid, n_cols_grid;   /* the raster; each >= 4                                                       */
+    gf_rect block;                      /* the rectangle of the raster that d_block holds, inside the grid, >= 4 x 4   */
+    int32_t elem_type, fill_i;          /* GF_ELEM_*; INT, SHORT: a cell equal to fill_i reads as NaN                  */
+    int32_t wrap;                       /* 0 none; 1 wraps longitude; 2 wraps and brackets longitude                   */
+    int32_t target;                     /* GF_INTERP_*                                                                 */
+    double row_spacing, col_spacing;    /* dv, du; non-zero when target >= GF_INTERP_FIRST                             */
+    double row_fringe0, row_fringe1, col_fringe0, col_fringe1;
+} gf_interp_spec;
+typedef struct gf_interp_out {          /* arrays of one item per point; any may be NULL except z                      */
+    double *z, *zx, *zy, *zxx, *zxy, *zyy;
+    double *normal;                     /* 3 per point, interleaved; needs target >= GF_INTERP_FIRST                   */
+    int32_t *status;
+} gf_interp_out;
+typedef struct gf_interp_lattice { double row0, col0, row_step, col_step; int64_t n_rows, n_cols; } gf_interp_lattice;
+gf_status gf_block_interp_points_dev(gf_context *ctx, void *stream, const gf_interp_spec *spec, const void *d_block, size_t n_points,
+                                     const double *d_rows, const double *d_cols, const double *d_col_spacing,
+                                     const gf_interp_out *out);
+gf_status gf_block_interp_lattice_dev(gf_context *ctx, void *stream, const gf_interp_spec *spec, const void *d_block,
+                                      const gf_interp_lattice *lattice, const double *d_col_spacing_rows, const gf_interp_out *out);
+gf_status gf_block_interp_points(gf_context *ctx, const gf_interp_spec *spec, const void *block, size_t n_points, const double *rows,
+                                 const double *cols, const double *col_spacing, const gf_interp_out *out);
+
 /* ---- a grid block WRITTEN: raster in, tile records out, in device memory ------------------------------------------------------
  * (gvrs/TileElementInt.java:118-126, TileElementShort.java:136-143, TileElementFloat.java:133-149, TileElementIntCodedFloat.java:152-169
  * setValue / setIntValue; TileElement*.hasValidData, gvrs/RasterTile.java:215-222; gvrs/RecordManager.java:386-490 writeTile, :413-419)
