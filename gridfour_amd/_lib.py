@@ -118,6 +118,12 @@ SIGNATURES = {
     "gf_block_interp_points_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "gf_block_interp_lattice_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gf_block_interp_points": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "gf_block_downsample_rect": (C.c_int, [_vp, C.c_int, _vp]),
+    "gf_block_downsample_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "gf_block_downsample_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "gf_block_read_downsampled_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_size_t, _vp, C.c_size_t, _vp,
+                                                      C.c_int, _vp, _vp]),
+    "gf_block_read_downsampled_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_size_t, _vp, _vp, C.c_int, _vp, _vp]),
     "gf_compact_dev":(C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
     "gf_float_planes_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "gf_float_planes_encode_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp, C.c_size_t]),

@@ -114,6 +114,52 @@ class GvrsHipContext:
                                            _ptr(o)), "gf_block_interp_points")
         return res
 
+    # ---- a grid block downsampled: the box average by an integer factor (gf_block_downsample_*) ----
+    @staticmethod
+    def downsample_rect(block, factor):
+        """gf_block_downsample_rect: block = (row0, col0, n_rows, n_cols) on the source grid -> the rectangle of the coarse grid
+        whose cells' whole factor x factor windows lie inside block (n_rows or n_cols may be 0)."""
+        block, out = np.ascontiguousarray(block, np.int32), np.zeros(4, np.int32)
+        assert block.size == 4
+        check(lib().gf_block_downsample_rect(_ptr(block), int(factor), _ptr(out)), "gf_block_downsample_rect")
+        return tuple(int(x) for x in out)
+
+    @staticmethod
+    def _downsample_specs(elems, fills):
+        """elems: a gf_elem_spec array as it is, or per element "int" | "short" | "float" with fills as read_block_dev takes them"""
+        if isinstance(elems, np.ndarray):
+            assert elems.dtype == _ELEM_SPEC and fills is None
+            return elems, [{0: np.int32, 1: np.int16}.get(int(t), np.float32) for t in elems["type"]]
+        specs, dtypes = CodecMasterHip._elem_specs(elems)
+        return CodecMasterHip._fill_specs(specs, elems, fills), dtypes
+
+    def downsample_dev(self, elems, block, factor, d_blocks, d_out, stream=None, fills=None):
+        """gf_block_downsample_elems_dev on device pointers: d_blocks[e] holds the rectangle block of element e (int32 / int16 /
+        float32, row-major), d_out[e] receives the cells of downsample_rect(block, factor).  Enqueues only."""
+        specs, _ = self._downsample_specs(elems, fills)
+        ne = len(specs)
+        assert len(d_blocks) == ne and len(d_out) == ne
+        val = lambda p: p.value if isinstance(p, C.c_void_p) else p
+        block = np.ascontiguousarray(block, np.int32)
+        check(lib().gf_block_downsample_elems_dev(self._h, stream, _ptr(specs), ne, _ptr(block), int(factor),
+                                                  (C.c_void_p * ne)(*[val(p) for p in d_blocks]), (C.c_void_p * ne)(*[val(p) for p in d_out])),
+              "gf_block_downsample_elems_dev")
+
+    def downsample(self, elems, block, factor, blocks, fills=None):
+        """gf_block_downsample_elems, the host-memory form (staged by the library): blocks[e] is the rectangle block of element e.
+        Returns one array [n_rows', n_cols'] per element in the element's dtype, for downsample_rect(block, factor)."""
+        specs, dtypes = self._downsample_specs(elems, fills)
+        ne = len(specs)
+        block = np.ascontiguousarray(block, np.int32)
+        blocks = [np.ascontiguousarray(b, dt) for b, dt in zip(blocks, dtypes)]
+        assert len(blocks) == ne and all(b.size == int(block[2]) * int(block[3]) for b in blocks)
+        _, _, n_rows, n_cols = self.downsample_rect(block, factor)
+        out = [np.zeros((n_rows, n_cols), dt) for dt in dtypes]
+        check(lib().gf_block_downsample_elems(self._h, _ptr(specs), ne, _ptr(block), int(factor),
+                                              (C.c_void_p * ne)(*[b.ctypes.data for b in blocks]),
+                                              (C.c_void_p * ne)(*[o.ctypes.data for o in out])), "gf_block_downsample_elems")
+        return out
+
     def close(self):
         if self._h:
             lib().gf_context_destroy(self._h)
@@ -1079,6 +1125,61 @@ class CodecMasterHip:
         check(lib().gf_block_read_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, _ptr(grid), _ptr(rect), nt,
                                         _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), ptrs, _ptr(status)), "gf_block_read_elems")
         return out, status
+
+    # ---- grid blocks read and downsampled: records in, one coarse block per element out (gf_block_read_downsampled_elems[_dev]) ----
+    @staticmethod
+    def _coarse_dtypes(elems, dtypes):
+        """an int-coded-float element comes back as its int32 codes"""
+        return [np.int32 if (el if isinstance(el, str) else el[0]) == "icf" else dt for el, dt in zip(elems, dtypes)]
+
+    def read_block_downsampled_dev(self, nRows, nCols, grid_shape, rect, factor, blob, offsets, elems, fills=None, verify_checksums=True):
+        """gf_block_read_downsampled_elems_dev: read_block_dev's arguments plus factor.  Returns ([coarse block [n_rows', n_cols'] per
+        element for downsample_rect(rect, factor): int32 / int16 / float32, an "icf" element as int32 codes], status [n_elems, nt]);
+        the blocks are good iff every status is 0."""
+        specs, dtypes = self._elem_specs(elems)
+        self._fill_specs(specs, elems, fills)
+        dtypes = self._coarse_dtypes(elems, dtypes)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nt, ne = offsets.size - 1, len(dtypes)
+        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
+        rect = np.ascontiguousarray(rect, np.int32)
+        _, _, n_rows, n_cols = GvrsHipContext.downsample_rect(rect, factor)
+        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
+        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
+        d_out = [DeviceBuffer(self.ctx, n_rows * n_cols * np.dtype(dt).itemsize + 16).fill(0) for dt in dtypes]
+        d_st = DeviceBuffer(self.ctx, ne * nt * 4 + 16).fill(0)
+        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_out])
+        try:
+            check(lib().gf_block_read_downsampled_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne,
+                                                            _ptr(grid), _ptr(rect), int(factor), nt, d_blob.ptr, blob.size, d_off.ptr,
+                                                            int(bool(verify_checksums)), ptrs, d_st.ptr), "gf_block_read_downsampled_elems_dev")
+            self.ctx.synchronize()
+            out = [b.download(dt, n_rows * n_cols).reshape(n_rows, n_cols) for b, dt in zip(d_out, dtypes)]
+            status = d_st.download(np.int32, ne * nt).reshape(ne, nt)
+        finally:
+            for b in [d_blob, d_off, d_st] + d_out:
+                b.free()
+        return out, status
+
+    def read_block_downsampled(self, nRows, nCols, grid_shape, rect, factor, blob, offsets, elems, fills=None, verify_checksums=True):
+        """The same through gf_block_read_downsampled_elems, the host-memory form; offsets[-1] bytes of blob are read."""
+        specs, dtypes = self._elem_specs(elems)
+        self._fill_specs(specs, elems, fills)
+        dtypes = self._coarse_dtypes(elems, dtypes)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        blob = np.concatenate([np.ascontiguousarray(blob, dtype=np.uint8), np.zeros(16, np.uint8)])
+        nt, ne = offsets.size - 1, len(dtypes)
+        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
+        rect = np.ascontiguousarray(rect, np.int32)
+        _, _, n_rows, n_cols = GvrsHipContext.downsample_rect(rect, factor)
+        out = [np.zeros(max(n_rows * n_cols, 1), dt) for dt in dtypes]
+        status = np.zeros((ne, nt), np.int32)
+        ptrs = (C.c_void_p * ne)(*[a.ctypes.data for a in out])
+        check(lib().gf_block_read_downsampled_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, _ptr(grid),
+                                                    _ptr(rect), int(factor), nt, _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), ptrs,
+                                                    _ptr(status)), "gf_block_read_downsampled_elems")
+        return [a[:n_rows * n_cols].reshape(n_rows, n_cols) for a in out], status
 
     # ---- grid blocks written: raster in, tile records out (gf_block_write_elems[_dev]) ----
     @staticmethod

@@ -76,8 +76,7 @@ gf_status elemFills(const gf_elem_spec *elems, int nElems, uint32_t *fill)
     return GF_OK;
 }
 
-namespace {
-
+// what the host can check of a block read's arguments (gvrs_api_downsample.hip shares it); fills g and fill
 gf_status blockReadArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const gf_grid_spec *grid,
                         const gf_rect *rect, size_t nRecords, const uint8_t *blob, bool blobOnDevice, const uint64_t *offsets,
                         void *const *blocks, const int32_t *status, GfBlockGeom &g, uint32_t *fill)
@@ -132,8 +131,6 @@ gf_status blockReadDev(gf_context *c, void *stream, const int *codecs, int nCode
     if (!n) GF_HIP(hipStreamSynchronize(st));                                    // (the call's one synchronisation, which the driver did not make)
     return GF_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

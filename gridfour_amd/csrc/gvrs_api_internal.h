@@ -118,12 +118,14 @@ struct gf_context {
     DevBuf dEncSlots, dEncMeta, dEncWide;       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots, their
                                                 // lengths / statuses and the records' layout, SHORT cells widened for the codecs
     DevBuf dInterp;                             // interpolation, host form (gvrs_api_interp.hip): block, coordinates, spacings and outputs
+    DevBuf dDsBlocks, dDsStage;                 // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks; the host
+                                                // forms' blocks and coarse blocks
     std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
-    std::array<DevBuf *, 35> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
+    std::array<DevBuf *, 37> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
     {
         return {&workspace, &trees, &flags, &packRecs, &dValues, &dSlots, &dBlob, &dLengths, &dPred, &dStatus, &dOffsets, &dPlanes,
                 &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta, &dRecMeta, &dRecSub, &dRecTmp,
-                &dBlockTmp, &dBlockIdx, &dBlockSlots, &dEncSlots, &dEncMeta, &dEncWide, &dBwTiles, &dBwMeta, &dBwStage, &dInterp};
+                &dBlockTmp, &dBlockIdx, &dBlockSlots, &dEncSlots, &dEncMeta, &dEncWide, &dBwTiles, &dBwMeta, &dBwStage, &dInterp, &dDsBlocks, &dDsStage};
     }
     gf_context()
     {
@@ -278,6 +280,14 @@ gf_status recordsEncodeHost(gf_context *c, const int *codecs, int nCodecs, const
 gf_status blockGeom(const gf_grid_spec *grid, const gf_rect *rect, GfBlockGeom &g);
 gf_status firstOf(gf_status a, gf_status b);
 gf_status elemFills(const gf_elem_spec *elems, int nElems, uint32_t *fill);
+// ... a block read's argument checks (fills g and fill), and records in device memory -> one block per element in device memory
+// (no lock taken, no argument checked)
+gf_status blockReadArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const gf_grid_spec *grid,
+                        const gf_rect *rect, size_t nRecords, const uint8_t *blob, bool blobOnDevice, const uint64_t *offsets,
+                        void *const *blocks, const int32_t *status, GfBlockGeom &g, uint32_t *fill);
+gf_status blockReadDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
+                       const uint32_t *fill, size_t n, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets, int verifyChecksum,
+                       void *const *dBlocks, int32_t *dStatus);
 // gvrs_api_records.hip
 size_t elemStandardSize(int elemType, size_t cells);
 // gvrs_api_deflate.hip

@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "gvrs_interp_common.h"
+#include "gvrs_downsample_common.h"
 
 // per-tile status values written by the kernels; identical to gf_status in
 // include/gvrs_hip_codec.h
@@ -632,3 +633,18 @@ struct GfInterpArgs {
     int32_t *status;
 };
 hipError_t gf_launch_interp(const GfInterpArgs &a, hipStream_t stream);
+
+// A grid block in device memory averaged down by an integer factor (gvrs_downsample.hip; driven by gvrs_api_downsample.hip): block
+// and out hold int32 / int16 / float32 cells as g.elemType says, out g.outRows x g.outCols of them, each written exactly once.
+// path: GF_DS_AUTO takes what gf_downsample_path chooses -- k_downsample_direct up to GF_DS_DIRECT_MAX_FACTOR, k_downsample_staged
+// above it (the measurements behind the bound: DESIGN.md section 4) -- GF_DS_DIRECT / GF_DS_STAGED force one; both serve every
+// factor and every geometry, bit for bit alike.
+enum { GF_DS_AUTO = 0, GF_DS_DIRECT = 1, GF_DS_STAGED = 2 };
+constexpr int32_t GF_DS_DIRECT_MAX_FACTOR = 8;
+struct GfDownsampleArgs {
+    GfDsGeom g;
+    const void *block;
+    void *out;
+};
+int gf_downsample_path(const GfDownsampleArgs &a);
+hipError_t gf_launch_downsample(const GfDownsampleArgs &a, int path, hipStream_t stream);

@@ -751,6 +751,57 @@ gf_status gf_block_interp_lattice_dev(gf_context *ctx, void *stream, const gf_in
 gf_status gf_block_interp_points(gf_context *ctx, const gf_interp_spec *spec, const void *block, size_t n_points, const double *rows,
                                  const double *cols, const double *col_spacing, const gf_interp_out *out);
 
+/* ---- a grid block DOWNSAMPLED: the box average by an integer factor, in device memory -------------------------------------------
+ * (demo/src/main/java/org/gridfour/demo/globalDEM/ExampleDownsample.java:164-210 the loop, :228-239 makeSpec's grid size)
+ * The coarser copy of a raster that the reference's ExampleDownsample writes -- an overview or pyramid level -- computed over a block
+ * that lies in device memory, bit for bit: output cell (i, j) of the coarse grid covers source rows i * f .. i * f + f - 1 and
+ * columns j * f .. j * f + f - 1, visited in row-major order; the coarse grid has floor(rows / f) x floor(cols / f) cells.
+ *   INT, SHORT: a window with ANY cell equal to fill_i gives fill_i (the reference leaves the cell unpopulated); else the cells are
+ *   summed as Java ints (wrap-around), avg = (double) sum / (f * f), the result (int) Math.floor(avg + 0.5).  No range check is made
+ *   (that is gf_block_write_elems[_dev]'s part); a SHORT's result always fits int16.
+ *   FLOAT: float sum = 0; sum += cell, one float32 rounding per addition in row-major order; the result sum / (float)(f * f).  The
+ *   fill gets no special treatment: a NaN fill propagates, any other is averaged in.  f = 1 turns -0.0 into +0.0, +inf and -inf in
+ *   one window give NaN, subnormals are not flushed.
+ *   ICF: the reference averages the CODES of an int-coded float (readBlockInt, fillValueI), never the float values, and a block read
+ *   under GF_ELEM_ICF holds float values: the two plain forms refuse GF_ELEM_ICF with GF_ERR_UNSUPPORTED.  Read the element as
+ *   GF_ELEM_INT with fill_i = fillValueI and downsample that; gf_block_read_downsampled_elems[_dev] does so by itself.
+ *   gf_block_downsample_rect (host arithmetic only): block is the rectangle of the SOURCE grid an input block holds; out is the
+ *   rectangle, in the COARSE grid's coordinates, of the output cells whose whole window lies inside block: row0' = ceil(row0 / f),
+ *   n_rows' = floor((row0 + n_rows) / f) - row0', the same for columns.  An empty result has n_rows' = 0 or n_cols' = 0 and is GF_OK.
+ *   A block need not start on a multiple of f: a caller working through a raster in strips gets the cells of one call on the whole.
+ *   gf_block_downsample_elems_dev: elems[n_elems] (type and fill_i are looked at); d_blocks and d_out are HOST arrays of n_elems
+ *   device pointers, each 4-byte aligned.  d_blocks[e] is the block `block` of element e as gf_block_read_elems_dev delivers it:
+ *   row-major, int32 / int16 / float32 (a SHORT block must be readable to the end of the aligned 4-byte word that holds its last
+ *   cell; otherwise nothing outside the blocks is read).  d_out[e] receives n_rows' x n_cols' items of the same type, row-major:
+ *   every item is written exactly once and nothing else is written.  An empty output rectangle is GF_OK and touches nothing.  The
+ *   call ONLY ENQUEUES on `stream` (NULL: the context's), one launch per element: it never synchronises, never allocates, and is
+ *   safe for hipGraph capture.  gf_block_downsample_elems is the same for blocks and outputs in host memory, staged through a
+ *   buffer of the context on the context's stream; it synchronises.
+ *   gf_block_read_downsampled_elems_dev: gf_block_read_elems_dev's arguments plus factor: tile records in, one COARSE block per
+ *   element out, for the rectangle gf_block_downsample_rect(rect, factor) gives.  The full-resolution blocks live in a temporary
+ *   of the context that grows on demand; then the kernels above run.  d_status is exactly the block read's: the result is good iff
+ *   every status is GF_OK (a missing tile and a failed record read as fill).  A GF_ELEM_ICF element IS accepted here: it is read
+ *   as INT on fill_i, averaged on its codes and delivered as int32 codes -- written back as a GF_ELEM_INT element these are the
+ *   bytes of an ICF element's records.  Synchronises `stream` once, as the block read does; not capture-safe.
+ *   gf_block_read_downsampled_elems is the same for bytes, coarse blocks and statuses in host memory.
+ * GF_ERR_ARG, before the context or a device is looked at: null pointers or a null entry of either pointer array, n_elems < 1 or
+ * > GF_MAX_ELEMS, a type outside 0..3, factor < 1, block.n_rows < 1, block.n_cols < 1, row0 < 0 or col0 < 0, a SHORT fill_i outside
+ * int16, a block or output pointer that is not 4-byte aligned, and for the record forms whatever gf_block_read_elems[_dev] rejects.
+ * GF_ERR_UNSUPPORTED: factor > 46340 (f * f leaves Java's int: the reference's new int[nRows * nColumns] fails; the rectangle rule
+ * answers the same), GF_ELEM_ICF in the two plain forms.                                                                         */
+gf_status gf_block_downsample_rect(const gf_rect *block, int factor, gf_rect *out);
+gf_status gf_block_downsample_elems_dev(gf_context *ctx, void *stream, const gf_elem_spec *elems, int n_elems, const gf_rect *block,
+                                        int factor, const void *const *d_blocks, void *const *d_out);
+gf_status gf_block_downsample_elems(gf_context *ctx, const gf_elem_spec *elems, int n_elems, const gf_rect *block, int factor,
+                                    const void *const *blocks, void *const *out);
+gf_status gf_block_read_downsampled_elems_dev(gf_context *ctx, void *stream, const int *codecs, int n_codecs, const gf_elem_spec *elems,
+                                              int n_elems, const gf_grid_spec *grid, const gf_rect *rect, int factor, size_t n_records,
+                                              const uint8_t *d_blob, size_t blob_bytes, const uint64_t *d_offsets, int verify_checksum,
+                                              void *const *d_out, int32_t *d_status);
+gf_status gf_block_read_downsampled_elems(gf_context *ctx, const int *codecs, int n_codecs, const gf_elem_spec *elems, int n_elems,
+                                          const gf_grid_spec *grid, const gf_rect *rect, int factor, size_t n_records, const uint8_t *blob,
+                                          const uint64_t *offsets, int verify_checksum, void *const *out, int32_t *status);
+
 /* ---- a grid block WRITTEN: raster in, tile records out, in device memory ------------------------------------------------------
  * (gvrs/TileElementInt.java:118-126, TileElementShort.java:136-143, TileElementFloat.java:133-149, TileElementIntCodedFloat.java:152-169
  * setValue / setIntValue; TileElement*.hasValidData, gvrs/RasterTile.java:215-222; gvrs/RecordManager.java:386-490 writeTile, :413-419)
