@@ -45,13 +45,15 @@ def test_planes_and_packings_match_oracle(fcodec, shape):
     L = lib()
     stride = (int(L.gf_float_planes_bytes(n_rows, n_cols)) + 15) // 16 * 16
     d_vals = DeviceBuffer(fcodec.ctx, tiles.nbytes).upload(tiles)
-    d_planes = DeviceBuffer(fcodec.ctx, nt * stride).fill(0xAB)
+    d_planes = DeviceBuffer(fcodec.ctx, nt * stride + 64).fill(0xAB)
     gridfour_amd.codec.check(L.gf_float_planes_encode_dev(fcodec.ctx.handle, None, n_rows, n_cols, nt, d_vals.ptr, d_planes.ptr, stride))
     fcodec.ctx.synchronize()
     planes = d_planes.download(np.uint8, nt * stride).reshape(nt, stride)
     for t in range(nt):
         ref = oracle.float_planes_encode(n_rows, n_cols, tiles[t].view(np.uint32))
         assert np.array_equal(planes[t, :ref.size], ref), (shape, t)
+        assert (planes[t, ref.size:] == 0xAB).all(), (shape, t)            # the padding between two tiles' planes is left alone
+    assert (d_planes.download(np.uint8, 64, nt * stride) == 0xAB).all()    # ... and what lies behind the last tile's
     # planes -> raw bits on the device
     d_back = DeviceBuffer(fcodec.ctx, tiles.nbytes).fill(0)
     gridfour_amd.codec.check(L.gf_float_planes_decode_dev(fcodec.ctx.handle, None, n_rows, n_cols, nt, d_planes.ptr, stride, d_back.ptr))
