@@ -590,7 +590,8 @@ __device__ void fast_sync_pass(DecShared &S, const FastHuff H, const uint16_t *c
     uint16_t *list = reinterpret_cast<uint16_t *>(S.qdirty);      // subsequences to redo (the flags themselves are not used here)
     constexpr uint32_t LIST_CAP = MAXQ / 2;                        // what does not fit waits for the next round
 #ifdef GF_DIAG
-    uint32_t rounds = 0;
+    uint32_t rounds = 0, listed = 0;                               // listed: subsequences redone, summed over the rounds
+    constexpr int DBG_LISTED = 9 - 11;                             // dbg points at word 11 of the tile's 16-word record: word 9, free of stamps
 #else
     (void)dbg;
 #endif
@@ -652,7 +653,11 @@ __device__ void fast_sync_pass(DecShared &S, const FastHuff H, const uint16_t *c
             for (int i = 0; i < NCUR; i++) any = any || a[i] < border[i];
             return __any(any) != 0;
         };
-        while (anyBefore(bA)) step(bA, std::false_type{});
+        if (anyBefore(bA)) {                                                    // (bottom-tested: no copies of the loop's registers at its head)
+            do {
+                step(bA, std::false_type{});
+            } while (anyBefore(bA));
+        }
 #pragma unroll
         for (int i = 0; i < NCUR; i++) sPos[i] = a[i] - sh0;                    // the first code at or beyond the boundary
         if (!pool) {
@@ -661,15 +666,26 @@ __device__ void fast_sync_pass(DecShared &S, const FastHuff H, const uint16_t *c
             // the subsequence itself, symbols kept: one or two codes per step (the second one only if it STARTS before the
             // border: the same rule as above, so positions and counts are the same), bytes gathered in a register pair and
             // stored a word at a time
-            // (the word being filled is stored after EVERY step, complete or not -- a later store of the same word only adds bytes --
-            // so there is no "word full?" branch and no epilogue; word-major addresses: the lanes of a wave are at about the same
-            // word, their stores fall into a line or two; a cursor that has filled its share, or overrun it, stores to the
-            // dump row behind the pool: an idle step of a cursor with exactly 4 poolWords symbols must not touch its last word)
-            uint32_t lo[NCUR];
+            // (round 7: a turn of the loop is TWO such steps -- the second one idle for a cursor that has arrived -- with one exit
+            // test and one store: two steps give four bytes at most, so a turn completes one word at most.  The turn's store goes
+            // to the word's slot if the turn completed it and to the dump row behind the pool otherwise, by address select -- no
+            // "word full?" branch; the word left partly filled is written behind the loop.  Word-major addresses: the lanes of
+            // a wave are at about the same word, their stores fall into a line or two.  The slot is kept as a byte offset from
+            // the pool's (wave-uniform) base that moves on by a row per completed word and stops at the dump row: a cursor that
+            // has filled its share, or overrun it, stores there, and an idle turn of a cursor with exactly 4 poolWords symbols
+            // completes nothing, so it does not touch its last word.  A lane without a subsequence never completes a word: it
+            // needs no exec mask, its stores go to the dump row)
+            uint32_t lo[NCUR], slot[NCUR], dumpAt[NCUR];
+            const uint32_t rowBytes = 4u * Q;
+            uint8_t *const poolB = reinterpret_cast<uint8_t *>(pool);
 #pragma unroll
-            for (int i = 0; i < NCUR; i++) lo[i] = 0;
-            const uint32_t dumpRow = poolWords;
-            while (anyBefore(limA)) {
+            for (int i = 0; i < NCUR; i++) {
+                lo[i] = 0;
+                slot[i] = d[i] ? 4u * qv[i] : 0u;
+                dumpAt[i] = poolWords * rowBytes + slot[i];
+                if (!d[i]) slot[i] = dumpAt[i];
+            }
+            auto poolStep = [&](uint32_t (&syms)[NCUR], uint32_t (&bits)[NCUR]) {
                 uint32_t x[NCUR], e[NCUR], anyLong = 0;
 #pragma unroll
                 for (int i = 0; i < NCUR; i++) {
@@ -691,20 +707,38 @@ __device__ void fast_sync_pass(DecShared &S, const FastHuff H, const uint16_t *c
                     const bool live = a[i] < limA[i];
                     const uint32_t a1 = (e[i] >> 16) & 63u, t2 = e[i] >> 22;
                     const bool two = t2 != a1 && a[i] + a1 < limA[i];
-                    const uint32_t k = live ? (two ? 2u : 1u) : 0u;
-                    const uint32_t syms = live ? (two ? e[i] & 0xffffu : e[i] & 0xffu) : 0u;
-                    const uint32_t at = cnt[i] & 3u;
-                    lo[i] |= syms << (8u * at);                                 // (a second byte behind byte 3 drops out: it opens the next word)
-                    if (d[i]) pool[min(cnt[i] >> 2, dumpRow) * Q + qv[i]] = lo[i];
-                    lo[i] = at + k >= 4u ? (at == 3u ? syms >> 8 : 0u) : lo[i];
-                    cnt[i] += k;
+                    const uint32_t m = live ? (two ? 0xffffu : 0xffu) : 0u;   // the bytes taken: their mask says how many (v_bcnt adds on)
+                    syms[i] = e[i] & m;
+                    bits[i] = (uint32_t)__builtin_popcount(m);
                     a[i] += live ? (two ? t2 : a1) : 0u;
                 }
+            };
+            uint32_t nb[NCUR];                                                  // symbols so far, in bits: 8 cnt
+#pragma unroll
+            for (int i = 0; i < NCUR; i++) nb[i] = 0;
+            if (anyBefore(limA)) {
+                do {
+                    uint32_t s0[NCUR], b0[NCUR], s1[NCUR], b1[NCUR];
+                    poolStep(s0, b0);
+                    poolStep(s1, b1);
+#pragma unroll
+                    for (int i = 0; i < NCUR; i++) {
+                        const uint32_t at = nb[i] & 24u, fill = at + b0[i] + b1[i];    // fill <= 24 + 32: bit 5 = the word is complete
+                        // the turn's bytes behind those of the word being filled; what does not fit opens the next word
+                        const uint64_t w = ((uint64_t)(s0[i] | (s1[i] << b0[i])) << at) | lo[i];
+                        const bool full = fill >= 32u;
+                        *reinterpret_cast<uint32_t *>(poolB + (full ? slot[i] : dumpAt[i])) = (uint32_t)w;
+                        lo[i] = full ? (uint32_t)(w >> 32) : (uint32_t)w;
+                        slot[i] = min(slot[i] + __umul24(fill >> 5, rowBytes), dumpAt[i]);    // (rowBytes = 4 Q: a few KB)
+                        nb[i] += b0[i] + b1[i];
+                    }
+                } while (anyBefore(limA));
             }
 #pragma unroll
             for (int i = 0; i < NCUR; i++) {
-                // (the word a second byte may have opened in the very last step)
-                if (d[i] && (cnt[i] & 3u)) pool[min(cnt[i] >> 2, dumpRow) * Q + qv[i]] = lo[i];
+                cnt[i] = nb[i] >> 3;
+                // the word left partly filled (a lane without a subsequence has counted nothing)
+                if (cnt[i] & 3u) *reinterpret_cast<uint32_t *>(poolB + slot[i]) = lo[i];
                 if (d[i] && cnt[i] > 4u * poolWords) S.poolOverflow = 1u;
             }
         }
@@ -742,6 +776,9 @@ __device__ void fast_sync_pass(DecShared &S, const FastHuff H, const uint16_t *c
         __syncthreads();
         const uint32_t nList = min(S.nRedo[round & 1u], LIST_CAP);
         if (nList == 0) break;
+#ifdef GF_DIAG
+        listed += nList;
+#endif
         uint32_t qv[NCUR];
 #pragma unroll
         for (int i = 0; i < NCUR; i++) {
@@ -768,7 +805,7 @@ __device__ void fast_sync_pass(DecShared &S, const FastHuff H, const uint16_t *c
     }
     if (tid == 0) S.chainTotal = tot;
 #ifdef GF_DIAG
-    if (dbg && tid == 0) { dbg[0] = rounds; dbg[4] = (uint32_t)__builtin_amdgcn_s_memtime() - tBegin; }   // the whole pass
+    if (dbg && tid == 0) { dbg[0] = rounds; dbg[DBG_LISTED] = listed; dbg[4] = (uint32_t)__builtin_amdgcn_s_memtime() - tBegin; }   // the whole pass
 #endif
     __syncthreads();
 }
