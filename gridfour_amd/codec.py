@@ -22,6 +22,14 @@ from ._lib import check, lib
 INT4_NULL_CODE = -(2 ** 31)   # util/GridfourConstants.java:61
 
 
+def _blob_of(packings):
+    """(blob, offsets[n + 1]) of packings laid back to back, with 16 zero bytes behind the last: the kernels read whole aligned
+    words past a packing's end."""
+    offsets = np.zeros(len(packings) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(p) for p in packings])
+    return np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8), offsets
+
+
 def _ptr(a):
     return C.c_void_p(a.ctypes.data)
 
@@ -278,9 +286,7 @@ class CodecHuffmanHip:
         if getattr(self, "_stats", None) is None:
             self._stats = np.zeros(6, dtype=CODEC_STATS_DTYPE)
         nt = len(packings)
-        offsets = np.zeros(nt + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in packings])
-        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)
+        blob, offsets = _blob_of(packings)
         status = np.zeros(nt, np.int32)
         if getattr(self, "_pairs", None) is None:
             self._pairs = np.zeros((6, 65536), np.int64)          # sB of the six CodecStats (CodecStats.java:64)
@@ -353,9 +359,7 @@ class CodecHuffmanHip:
     def decode_batch(self, nRows, nCols, packings):
         """packings: list of bytes.  Returns (values int32 [nTiles, cells], status)."""
         nt = len(packings)
-        offsets = np.zeros(nt + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in packings])
-        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)
+        blob, offsets = _blob_of(packings)
         out = np.empty((nt, nRows * nCols), np.int32)
         status = np.zeros(nt, np.int32)
         check(self._fn("decode_batch_i32")(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out),
@@ -398,9 +402,7 @@ class CodecCanonHuffmanHip(CodecHuffmanHip):
         if getattr(self, "_stats", None) is None:
             self._stats = np.zeros(6, dtype=CANON_STATS_DTYPE)
             self._escapes = np.zeros(6, np.int64)
-        offsets = np.zeros(nt + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in packings])
-        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)
+        blob, offsets = _blob_of(packings)
         check(lib().gf_canon_analyze_batch(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(self._stats),
                                            _ptr(self._escapes), _ptr(status)), "gf_canon_analyze_batch")
         return status
@@ -676,9 +678,7 @@ class CodecFloatHip:
 
     def decode_floats_batch(self, nRows, nCols, packings):
         nt = len(packings)
-        offsets = np.zeros(nt + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in packings])
-        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)
+        blob, offsets = _blob_of(packings)
         out = np.empty((nt, nRows * nCols), np.float32)
         status = np.zeros(nt, np.int32)
         check(lib().gf_float_decode_batch_f32(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out),
@@ -749,9 +749,7 @@ class LsCodecHip:
 
     def decode_batch(self, nRows, nCols, packings):
         nt = len(packings)
-        offsets = np.zeros(nt + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in packings])
-        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)
+        blob, offsets = _blob_of(packings)
         out = np.zeros((nt, nRows * nCols), np.int32)
         status = np.zeros(nt, np.int32)
         check(lib().gf_lsop12_decode_batch_i32(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out),
@@ -840,9 +838,7 @@ class CodecMasterHip:
 
     def decode_batch(self, nRows, nCols, packings):
         nt = len(packings)
-        offsets = np.zeros(nt + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in packings])
-        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)
+        blob, offsets = _blob_of(packings)
         out = np.zeros((nt, nRows * nCols), np.int32)
         status = np.zeros(nt, np.int32)
         check(lib().gf_codec_master_decode_batch_i32(self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt,
@@ -886,9 +882,7 @@ class CodecMasterHip:
         """Returns (tile indices, values [nt, cells] int32 / int16, status per record)."""
         short = element == "short"
         nt = len(records)
-        offsets = np.zeros(nt + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in records])
-        blob = np.frombuffer(b"".join(records) + b"\0" * 16, dtype=np.uint8)
+        blob, offsets = _blob_of(records)
         out = np.zeros((nt, nRows * nCols), np.int16 if short else np.int32)
         idx = np.full(nt, -1, np.int32)
         status = np.zeros(nt, np.int32)
@@ -934,9 +928,8 @@ class CodecMasterHip:
 
     def tiles_from_records_dev(self, nRows, nCols, records, element="int", verify_checksums=True):
         """tiles_from_records with the records decoded where they lie in device memory (gf_tile_record_decode_batch_dev)."""
-        offsets = np.zeros(len(records) + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in records])
-        blob = np.frombuffer(b"".join(records) + b"\0" * 16, dtype=np.uint8)[:int(offsets[-1])]
+        blob, offsets = _blob_of(records)
+        blob = blob[:int(offsets[-1])]
         return self.record_blob_dev(nRows, nCols, blob, offsets, element=element, verify_checksums=verify_checksums)
 
     # ---- records of several elements, float and int-coded-float elements (gf_tile_record_decode_batch_elems[_dev]) ----
@@ -1315,17 +1308,12 @@ class CodecMasterHip:
     def decode_batch_dev(self, nRows, nCols, packings):
         """decode_batch with the packings decoded where they lie in device memory (gf_codec_master_decode_batch_i32_dev)."""
         lengths = np.array([len(p) for p in packings], np.uint32)
-        offsets = np.zeros(len(packings), np.uint64)
-        if len(packings):
-            offsets[1:] = np.cumsum(lengths[:-1], dtype=np.uint64)
-        blob = np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8)[:int(lengths.sum())]
-        return self.packing_blob_dev(nRows, nCols, blob, offsets, lengths)
+        blob, offsets = _blob_of(packings)
+        return self.packing_blob_dev(nRows, nCols, blob[:int(offsets[-1])], offsets[:-1], lengths)
 
     def tiles_from_payloads(self, nRows, nCols, payloads):
         nt = len(payloads)
-        offsets = np.zeros(nt + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(p) for p in payloads])
-        blob = np.frombuffer(b"".join(payloads) + b"\0" * 16, dtype=np.uint8)
+        blob, offsets = _blob_of(payloads)
         out = np.zeros((nt, nRows * nCols), np.int32)
         status = np.zeros(nt, np.int32)
         check(lib().gf_tile_payload_decode_batch_i32(self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt,

@@ -144,9 +144,9 @@ void gf_context_destroy(gf_context *c)
     (void)hipStreamSynchronize(c->stream);
     gf_single_destroy(c->single);
     c->single = nullptr;
-    for (DevBuf *b : c->buffers()) b->release();
+    for (DevBuf *b = c->bufs; b; b = b->next) b->release();
     gf_host_pipe_destroy(c->pipe);
-    gf_rec_counts_destroy(c->hRecCounts);
+    c->hRecCounts.release();
     if (c->hRoomySeen) (void)hipHostFree(c->hRoomySeen);
     if (c->side.stream) {
         (void)hipStreamSynchronize(c->side.stream);
@@ -174,13 +174,23 @@ gf_status gf_context_reserve(gf_context *c, int nRows, int nCols, size_t nTiles)
     GF_CTX_LOCK(c);
     if (!c || nRows < 1 || nCols < 1) return GF_ERR_ARG;
     GF_HIP(hipSetDevice(c->device));
-    const unsigned grid = gf_huffman_decode_grid(nTiles);
-    // (the legacy decoder's leaf records + its roomy list; the canonical decoder's length records + the slack of its fast run)
-    gf_status s = c->trees.ensure(std::max(nTiles * (size_t)GF_TREE_REC_WORDS * 4 + 16 + nTiles * 4,
-                                           nTiles * (size_t)GF_CANON_REC_WORDS * 4 + 16 + 4096));
+    uint64_t need[3];
+    scratchReserve(nRows, nCols, nTiles, need);
+    gf_status s = c->trees.ensure(need[1]);
     if (s != GF_OK) return s;
-    if ((s = c->packRecs.ensure(encRecordBytes(nRows, nCols, nTiles))) != GF_OK) return s;
-    return c->workspace.ensure((size_t)grid * decodeWorkspaceStride(nRows, nCols));
+    if ((s = c->packRecs.ensure(need[2])) != GF_OK) return s;
+    return c->workspace.ensure(need[0]);
+}
+
+// Not part of the public ABI (tests load it by name): bytes held of workspace, trees, packRecs and of all the context's buffers; their moves
+gf_status gf_internal_context_scratch(gf_context *c, uint64_t out[5])
+{
+    GF_CTX_LOCK(c);
+    if (!c || !out) return GF_ERR_ARG;
+    out[0] = c->workspace.bytes, out[1] = c->trees.bytes, out[2] = c->packRecs.bytes, out[3] = 0;
+    for (const DevBuf *b = c->bufs; b; b = b->next) out[3] += b->bytes;
+    out[4] = c->bufMoves.load(std::memory_order_relaxed);
+    return GF_OK;
 }
 
 size_t gf_huffman_default_stride(int nRows, int nCols)

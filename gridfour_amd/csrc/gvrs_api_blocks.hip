@@ -97,22 +97,17 @@ gf_status blockReadDev(gf_context *c, void *stream, const int *codecs, int nCode
     GF_HIP(hipSetDevice(c->device));
     const hipStream_t st = streamOf(c, stream);
     const size_t cells = (size_t)g.nRowsTile * (size_t)g.nColsTile;
-    // the temporary: n_elems arrays of n_records * cells items, each a multiple of 16 bytes
-    size_t tmpBytes = 0, at[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        at[e] = tmpBytes;
-        tmpBytes += roundUp(n * cells * elemItemBytes(elems[e].type), 16);
-    }
-    const size_t tableBytes = GF_MAX_ELEMS * sizeof(GfBlockElem);
-    gf_status s;
-    if ((s = c->dBlockTmp.ensure(tmpBytes + 16)) != GF_OK) return s;
-    if ((s = c->dBlockIdx.ensure(tableBytes + n * 4 + 16)) != GF_OK) return s;
-    GfBlockElem *dElems = (GfBlockElem *)c->dBlockIdx.p;
-    int32_t *dIndices = (int32_t *)((uint8_t *)c->dBlockIdx.p + tableBytes);
+    // the temporary: n_elems arrays of n_records * cells items; the gather's element table and the records' tile indices
+    Carve idx;
     void *dValues[GF_MAX_ELEMS];
+    const size_t tableAt = idx.add(GF_MAX_ELEMS * sizeof(GfBlockElem)), indicesAt = idx.add(n * 4);
+    gf_status s;
+    if ((s = elemArrays(c->dBlockTmp, elems, nElems, n * cells, dValues)) != GF_OK) return s;
+    if ((s = c->dBlockIdx.ensure(idx)) != GF_OK) return s;
+    GfBlockElem *dElems = c->dBlockIdx.at<GfBlockElem>(tableAt);
+    int32_t *dIndices = c->dBlockIdx.at<int32_t>(indicesAt);
     GfBlockElem table[GF_MAX_ELEMS] = {};
     for (int e = 0; e < nElems; e++) {
-        dValues[e] = (uint8_t *)c->dBlockTmp.p + at[e];
         table[e].tiles = dValues[e];
         table[e].block = dBlocks[e];
         table[e].status = dStatus + (size_t)e * n;
@@ -202,19 +197,13 @@ gf_status gf_block_read_elems(gf_context *c, const int *codecs, int nCodecs, con
     GF_HIP(hipSetDevice(c->device));
     const size_t blobBytes = nRecords ? (size_t)offsets[nRecords] : 0, nInst = (size_t)nElems * nRecords;
     const size_t blockCells = (size_t)g.nRows * (size_t)g.nCols;
-    // staging: blob | offsets | the block of element 0, 1, ... (each part a multiple of 16 bytes) | statuses
-    size_t blockBytes = 0, at[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        at[e] = blockBytes;
-        blockBytes += roundUp(blockCells * elemItemBytes(elems[e].type), 16);
-    }
+    // staging: blob | offsets | the block of element 0, 1, ... | statuses
     if ((s = c->dBlob.ensure(blobBytes + 32)) != GF_OK) return s;
     if ((s = c->dOffsets.ensure((nRecords + 1) * 8 + 16)) != GF_OK) return s;
-    if ((s = c->dValues.ensure(blockBytes + 16)) != GF_OK) return s;
+    void *dBlocks[GF_MAX_ELEMS];
+    if ((s = elemArrays(c->dValues, elems, nElems, blockCells, dBlocks)) != GF_OK) return s;
     if ((s = c->dStatus.ensure(nInst * 4 + 16)) != GF_OK) return s;
     int32_t *dStatus = (int32_t *)c->dStatus.p;
-    void *dBlocks[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) dBlocks[e] = (uint8_t *)c->dValues.p + at[e];
     if (nRecords) {
         GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, blobBytes, hipMemcpyHostToDevice, c->stream));
         GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nRecords + 1) * 8, hipMemcpyHostToDevice, c->stream));

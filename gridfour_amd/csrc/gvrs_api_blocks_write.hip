@@ -80,12 +80,12 @@ gf_status blockWriteArgs(const gf_context *c, const int *codecs, int nCodecs, co
 // the layout of the small per-tile results in dBwMeta: flags | pre-status, then -- the host form only -- offsets | indices | statuses |
 // codec used
 struct BwMeta {
-    size_t flags, pre, offsets, indices, status, used, bytes;
+    Carve k;
+    size_t flags, pre, offsets, indices, status, used;
     BwMeta(size_t nOut, int nElems)
+        : flags(k.add(nOut * 4)), pre(k.add(nOut * 4)), offsets(k.add((nOut + 1) * 8)), indices(k.add(nOut * 4)), status(k.add(nOut * 4)),
+          used(k.add((size_t)nElems * nOut))
     {
-        const size_t w = roundUp(nOut, 4) * 4;
-        flags = 0, pre = w, offsets = 2 * w, indices = offsets + roundUp((nOut + 1) * 8, 16), status = indices + w, used = status + w;
-        bytes = used + roundUp((size_t)nElems * nOut, 16);
     }
 };
 
@@ -99,17 +99,11 @@ gf_status blockCutDev(gf_context *c, void *stream, const int *codecs, int nCodec
     const hipStream_t st = streamOf(c, stream);
     const size_t cells = (size_t)g.nRowsTile * (size_t)g.nColsTile, nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
     const BwMeta m(nOut, nElems);
-    // the cut tiles: n_elems arrays of n_out * cells items, each a multiple of 16 bytes with room behind a SHORT array's last word
-    size_t tileBytes = 0, at[GF_MAX_ELEMS], oldBytesTmp = 0, oldAt[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        at[e] = tileBytes;
-        tileBytes += roundUp(nOut * cells * elemItemBytes(elems[e].type) + 4, 16);
-        oldAt[e] = oldBytesTmp;
-        oldBytesTmp += roundUp(nOld * cells * elemItemBytes(elems[e].type), 16);
-    }
+    // the cut tiles: n_elems arrays of n_out * cells items with room behind a SHORT array's last word; the old records' tiles
+    void *cutTiles[GF_MAX_ELEMS], *dOld[GF_MAX_ELEMS];
     gf_status s;
-    if ((s = c->dBwTiles.ensure(tileBytes + 16)) != GF_OK) return s;
-    if ((s = c->dBwMeta.ensure(m.bytes + 16)) != GF_OK) return s;
+    if ((s = elemArrays(c->dBwTiles, elems, nElems, nOut * cells, cutTiles, 4)) != GF_OK) return s;
+    if ((s = c->dBwMeta.ensure(m.k)) != GF_OK) return s;
     uint8_t *meta = (uint8_t *)c->dBwMeta.p;
     GfBlockCutElemsArgs q{};
     q.nElems = nElems;
@@ -118,23 +112,22 @@ gf_status blockCutDev(gf_context *c, void *stream, const int *codecs, int nCodec
     for (int e = 0; e < nElems; e++) {
         q.elems[e] = cut[e];
         q.elems[e].block = dBlocks[e];
-        q.elems[e].tiles = (uint8_t *)c->dBwTiles.p + at[e];
-        dTiles[e] = q.elems[e].tiles;
+        q.elems[e].tiles = cutTiles[e];
+        dTiles[e] = cutTiles[e];
     }
     GfBlockWriteVerdictArgs v{};
     if (nOld) {
         // the old records, decoded into the block read's temporaries; an ICF element as INT: its codes come back, not floats
-        const size_t idxBytes = roundUp(nOld, 4) * 4;
-        if ((s = c->dBlockTmp.ensure(oldBytesTmp + 16)) != GF_OK) return s;
-        if ((s = c->dBlockIdx.ensure(idxBytes + (size_t)nElems * nOld * 4 + 16)) != GF_OK) return s;
+        Carve idx;
+        const size_t idxAt = idx.add(nOld * 4), statusAt = idx.add((size_t)nElems * nOld * 4);
+        if ((s = elemArrays(c->dBlockTmp, elems, nElems, nOld * cells, dOld)) != GF_OK) return s;
+        if ((s = c->dBlockIdx.ensure(idx)) != GF_OK) return s;
         if ((s = c->dBlockSlots.ensure(nOut * 4 + 16)) != GF_OK) return s;
-        int32_t *dOldIdx = (int32_t *)c->dBlockIdx.p, *dOldStatus = (int32_t *)((uint8_t *)c->dBlockIdx.p + idxBytes);
+        int32_t *dOldIdx = c->dBlockIdx.at<int32_t>(idxAt), *dOldStatus = c->dBlockIdx.at<int32_t>(statusAt);
         gf_elem_spec asInt[GF_MAX_ELEMS];
-        void *dOld[GF_MAX_ELEMS];
         for (int e = 0; e < nElems; e++) {
             asInt[e] = elems[e];
             if (asInt[e].type == GF_ELEM_ICF) asInt[e].type = GF_ELEM_INT;
-            dOld[e] = (uint8_t *)c->dBlockTmp.p + oldAt[e];
             q.elems[e].oldTiles = dOld[e];
         }
         GF_HIP(hipMemsetAsync(dOldIdx, 0xff, nOld * 4, st));                    // (the driver leaves a failed record's entry alone: -1 places nothing)
@@ -239,15 +232,12 @@ gf_status gf_block_write_elems(gf_context *c, const int *codecs, int nCodecs, co
     const size_t cells = (size_t)g.nRowsTile * (size_t)g.nColsTile, nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
     const size_t blockCells = (size_t)g.nRows * (size_t)g.nCols, oldBytes = nOld ? (size_t)oldOffsets[nOld] : 0;
     const size_t maxBlob = onDevice ? nOut * gf_tile_record_max_bytes_elems(elems, nElems, g.nRowsTile, g.nColsTile) : 0;
-    // staging: the block of element 0, 1, ... | old blob | old offsets | the records at their largest (each part a multiple of 16 bytes)
-    size_t stage = 0, at[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        at[e] = stage;
-        stage += roundUp(blockCells * elemItemBytes(elems[e].type), 16);
-    }
-    const size_t oldAt = stage, oldOffAt = oldAt + roundUp(oldBytes + 32, 16), outAt = oldOffAt + roundUp((nOld + 1) * 8, 16);
-    stage = outAt + roundUp(maxBlob, 16);
-    if ((s = c->dBwStage.ensure(stage + 16)) != GF_OK) return s;
+    // staging: the block of element 0, 1, ... | old blob | old offsets | the records at their largest
+    Carve stage;
+    size_t at[GF_MAX_ELEMS];
+    carveElems(stage, elems, nElems, blockCells, at);
+    const size_t oldAt = stage.add(oldBytes + 32), oldOffAt = stage.add((nOld + 1) * 8), outAt = stage.add(maxBlob);
+    if ((s = c->dBwStage.ensure(stage)) != GF_OK) return s;
     uint8_t *base = (uint8_t *)c->dBwStage.p;
     const void *dBlocks[GF_MAX_ELEMS];
     for (int e = 0; e < nElems; e++) {
@@ -259,7 +249,7 @@ gf_status gf_block_write_elems(gf_context *c, const int *codecs, int nCodecs, co
         GF_HIP(hipMemcpyAsync(base + oldOffAt, oldOffsets, (nOld + 1) * 8, hipMemcpyHostToDevice, c->stream));
     }
     const BwMeta m(nOut, nElems);
-    if ((s = c->dBwMeta.ensure(m.bytes + 16)) != GF_OK) return s;              // (before its addresses are taken: blockCutDev asks for no more)
+    if ((s = c->dBwMeta.ensure(m.k)) != GF_OK) return s;                       // (before its addresses are taken: blockCutDev asks for no more)
     uint8_t *meta = (uint8_t *)c->dBwMeta.p;
     const void *dTiles[GF_MAX_ELEMS];
     s = blockCutDev(c, c->stream, codecs, nCodecs, elems, nElems, g, cut, dBlocks, nOld, base + oldAt, oldBytes, (const uint64_t *)(base + oldOffAt),

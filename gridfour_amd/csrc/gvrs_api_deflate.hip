@@ -17,11 +17,14 @@ gf_status deflateDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, 
     gf_status s;
     if ((s = c->dInflOut.ensure(chunk * rawStride + 64)) != GF_OK) return s;
     if ((s = c->dInflate.ensure(chunk * sizeof(GfInflateStream) + 64)) != GF_OK) return s;
-    if ((s = c->dInflMeta.ensure(chunk * 20 + 256)) != GF_OK) return s;
+    Carve k;
+    size_t at[5];                                                        // per stream: produced, M32 length, status of inflate, walk, decode
+    for (size_t &x : at) x = k.add(chunk * 4);
+    if ((s = c->dInflMeta.ensure(k, 256)) != GF_OK) return s;
     uint8_t *raw = (uint8_t *)c->dInflOut.p;
     GfInflateStream *desc = (GfInflateStream *)c->dInflate.p;
-    uint32_t *produced = (uint32_t *)c->dInflMeta.p, *rawLengths = produced + chunk;
-    int32_t *inflStatus = (int32_t *)(rawLengths + chunk), *pre = inflStatus + chunk, *decStatus = pre + chunk;
+    uint32_t *produced = c->dInflMeta.at<uint32_t>(at[0]), *rawLengths = c->dInflMeta.at<uint32_t>(at[1]);
+    int32_t *inflStatus = c->dInflMeta.at<int32_t>(at[2]), *pre = c->dInflMeta.at<int32_t>(at[3]), *decStatus = c->dInflMeta.at<int32_t>(at[4]);
     for (size_t t0 = 0; t0 < nTiles; t0 += chunk) {
         const size_t n = std::min(chunk, nTiles - t0);
         GF_HIP(gf_launch_deflate_streams(dBlob, blobBytes, dOffsets, slotStride, dLengths, t0, n, (uint32_t)cells, raw, rawStride, desc, pre, st));

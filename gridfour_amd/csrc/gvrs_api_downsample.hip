@@ -67,20 +67,6 @@ gf_status dsLaunch(gf_context *c, hipStream_t st, const gf_elem_spec *elems, int
     return GF_OK;
 }
 
-// the record forms' temporary: one full-resolution block per element, each a multiple of 16 bytes
-gf_status dsFullBlocks(gf_context *c, const gf_elem_spec *elems, int nElems, const gf_rect &rect, void **dFull)
-{
-    size_t bytes = 0, at[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        at[e] = bytes;
-        bytes += roundUp((size_t)rect.n_rows * (size_t)rect.n_cols * elemItemBytes(elems[e].type), 16);
-    }
-    const gf_status s = c->dDsBlocks.ensure(bytes + 16);
-    if (s != GF_OK) return s;
-    for (int e = 0; e < nElems; e++) dFull[e] = (uint8_t *)c->dDsBlocks.p + at[e];
-    return GF_OK;
-}
-
 // the record forms' argument checks: the block read's on the elements as given, then the factor; asCodes: the elements with ICF
 // turned into INT on fill_i, fill: their fills' bits
 gf_status dsReadArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const gf_grid_spec *grid,
@@ -135,20 +121,17 @@ gf_status gf_block_downsample_elems(gf_context *c, const gf_elem_spec *elems, in
     if (outRect.n_rows == 0 || outRect.n_cols == 0) return GF_OK;
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
-    // staging: per element its block, then its coarse block, each part a multiple of 16 bytes
+    // staging: the elements' blocks, then their coarse blocks
     const size_t inCells = (size_t)block->n_rows * (size_t)block->n_cols, outCells = (size_t)outRect.n_rows * (size_t)outRect.n_cols;
-    size_t bytes = 0, atIn[GF_MAX_ELEMS], atOut[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        atIn[e] = bytes;
-        bytes += roundUp(inCells * elemItemBytes(elems[e].type), 16);
-        atOut[e] = bytes;
-        bytes += roundUp(outCells * elemItemBytes(elems[e].type), 16);
-    }
-    if ((s = c->dDsStage.ensure(bytes + 16)) != GF_OK) return s;
+    Carve k;
+    size_t atIn[GF_MAX_ELEMS], atOut[GF_MAX_ELEMS];
+    carveElems(k, elems, nElems, inCells, atIn);
+    carveElems(k, elems, nElems, outCells, atOut);
+    if ((s = c->dDsStage.ensure(k)) != GF_OK) return s;
     const void *dBlocks[GF_MAX_ELEMS];
     void *dOut[GF_MAX_ELEMS];
     for (int e = 0; e < nElems; e++) {
-        dBlocks[e] = (uint8_t *)c->dDsStage.p + atIn[e], dOut[e] = (uint8_t *)c->dDsStage.p + atOut[e];
+        dBlocks[e] = c->dDsStage.at<void>(atIn[e]), dOut[e] = c->dDsStage.at<void>(atOut[e]);
         GF_HIP(hipMemcpyAsync((void *)dBlocks[e], blocks[e], inCells * elemItemBytes(elems[e].type), hipMemcpyHostToDevice, c->stream));
     }
     if ((s = dsLaunch(c, c->stream, elems, nElems, *block, factor, outRect, dBlocks, dOut)) != GF_OK) return s;
@@ -172,7 +155,7 @@ gf_status gf_block_read_downsampled_elems_dev(gf_context *c, void *stream, const
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
     void *dFull[GF_MAX_ELEMS];
-    if ((s = dsFullBlocks(c, asCodes, nElems, *rect, dFull)) != GF_OK) return s;
+    if ((s = elemArrays(c->dDsBlocks, asCodes, nElems, (size_t)rect->n_rows * (size_t)rect->n_cols, dFull)) != GF_OK) return s;   // at full resolution
     s = blockReadDev(c, stream, codecs, nCodecs, asCodes, nElems, g, fill, nRecords, dBlob, blobBytes, dOffsets, verifyChecksum, dFull, dStatus);
     if (s != GF_OK || outRect.n_rows == 0 || outRect.n_cols == 0) return s;
     return dsLaunch(c, streamOf(c, stream), asCodes, nElems, *rect, factor, outRect, dFull, dOut);
@@ -193,19 +176,13 @@ gf_status gf_block_read_downsampled_elems(gf_context *c, const int *codecs, int 
     GF_HIP(hipSetDevice(c->device));
     const size_t blobBytes = nRecords ? (size_t)offsets[nRecords] : 0, nInst = (size_t)nElems * nRecords;
     const size_t outCells = (size_t)outRect.n_rows * (size_t)outRect.n_cols;
-    // staging: blob | offsets | statuses | the coarse block of element 0, 1, ... (each a multiple of 16 bytes)
-    size_t outBytes = 0, at[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        at[e] = outBytes;
-        outBytes += roundUp(outCells * elemItemBytes(asCodes[e].type), 16);
-    }
+    // staging: blob | offsets | statuses | the coarse block of element 0, 1, ...
     if ((s = c->dBlob.ensure(blobBytes + 32)) != GF_OK) return s;
     if ((s = c->dOffsets.ensure((nRecords + 1) * 8 + 16)) != GF_OK) return s;
     if ((s = c->dStatus.ensure(nInst * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dDsStage.ensure(outBytes + 16)) != GF_OK) return s;
     void *dFull[GF_MAX_ELEMS], *dOut[GF_MAX_ELEMS];
-    if ((s = dsFullBlocks(c, asCodes, nElems, *rect, dFull)) != GF_OK) return s;
-    for (int e = 0; e < nElems; e++) dOut[e] = (uint8_t *)c->dDsStage.p + at[e];
+    if ((s = elemArrays(c->dDsStage, asCodes, nElems, outCells, dOut)) != GF_OK) return s;
+    if ((s = elemArrays(c->dDsBlocks, asCodes, nElems, (size_t)rect->n_rows * (size_t)rect->n_cols, dFull)) != GF_OK) return s;   // at full resolution
     int32_t *dStatus = (int32_t *)c->dStatus.p;
     if (nRecords) {
         GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, blobBytes, hipMemcpyHostToDevice, c->stream));

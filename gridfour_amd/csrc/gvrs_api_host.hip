@@ -97,21 +97,20 @@ static void parallelCopy(void *dst, const void *src, size_t bytes)
 // The pinned meta record of a chunk (HostSlot::hMeta): offsets[chunk + 1], lengths[chunk], statuses[chunk] and -- the encoder's only --
 // predictors[chunk], each from a 64-byte boundary.
 struct HostMeta {
-    uint64_t *off;
-    uint32_t *len;
-    int32_t *st;
-    uint8_t *pred;
-    HostMeta(const HostSlot &S, size_t chunk)
+    Carve k;
+    const size_t offAt, lenAt, stAt, predAt;
+    uint64_t *off = nullptr;
+    uint32_t *len = nullptr;
+    int32_t *st = nullptr;
+    uint8_t *pred = nullptr;
+    HostMeta(size_t chunk, bool predictors)
+        : offAt(k.add((chunk + 1) * 8, 64)), lenAt(k.add(chunk * 4, 64)), stAt(k.add(chunk * 4, 64)), predAt(k.add(predictors ? chunk : 0, 64))
     {
-        uint8_t *b = (uint8_t *)S.hMeta.p;
-        off = (uint64_t *)b;
-        len = (uint32_t *)(b + roundUp((chunk + 1) * 8, 64));
-        st = (int32_t *)((uint8_t *)len + roundUp(chunk * 4, 64));
-        pred = (uint8_t *)st + roundUp(chunk * 4, 64);
     }
-    static size_t bytes(size_t chunk, bool predictors)
+    // the parts in a slot's record (which holds at least this layout: the encoder's has the predictors behind the decoder's)
+    HostMeta(const HostSlot &S, size_t chunk) : HostMeta(chunk, true)
     {
-        return roundUp((chunk + 1) * 8, 64) + 2 * roundUp(chunk * 4, 64) + (predictors ? roundUp(chunk, 64) : 0) + 64;
+        off = S.hMeta.at<uint64_t>(offAt), len = S.hMeta.at<uint32_t>(lenAt), st = S.hMeta.at<int32_t>(stAt), pred = S.hMeta.at<uint8_t>(predAt);
     }
 };
 
@@ -152,7 +151,7 @@ static gf_status encodeBatchHost(int kind, gf_context *c, int codecIndex, int nR
         if ((s = S.dOffsets.ensure((chunk + 1) * 8 + 16)) != GF_OK) return s;
         if (!pinnedIn && (s = S.hIn.ensure(chunk * cells * 4)) != GF_OK) return s;
         if ((s = S.hOut.ensure(chunk * stride)) != GF_OK) return s;
-        if ((s = S.hMeta.ensure(HostMeta::bytes(chunk, true))) != GF_OK) return s;
+        if ((s = S.hMeta.ensure(HostMeta(chunk, true).k, 64)) != GF_OK) return s;
     }
 
     uint64_t total = 0;                            // bytes of the packings placed so far
@@ -311,7 +310,7 @@ gf_status decodeBatchHostG(int kind, gf_context *c, int nRows, int nCols, size_t
         if ((s = S.dOffsets.ensure((chunk + 1) * 8 + 16)) != GF_OK) return s;
         if ((s = S.hIn.ensure(maxSlice + 64)) != GF_OK) return s;
         if (!pinnedOut && (s = S.hOut.ensure(chunk * cells * 4)) != GF_OK) return s;
-        if ((s = S.hMeta.ensure(HostMeta::bytes(chunk, false))) != GF_OK) return s;
+        if ((s = S.hMeta.ensure(HostMeta(chunk, false).k, 64)) != GF_OK) return s;
     }
     auto finish = [&](size_t k) -> gf_status {
         HostSlot &S = P->slot[k % HOST_SLOTS];

@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <atomic>
 #include <memory>
 #include <cmath>
@@ -24,6 +23,7 @@
 #include "../../include/gvrs_hip_codec.h"
 #include "gvrs_kernels.h"
 #include "gvrs_encode_layout.h"
+#include "gvrs_carve.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -64,17 +64,22 @@ inline bool offsetsValid(const uint64_t *offsets, size_t nTiles)
 }
 
 // Counts the device buffers that moved (a move is rare: buffers only grow).  A recorded hipGraph holds the addresses it was
-// captured with: the one-tile graphs (gf_single) remember the count they were recorded at and are dropped when it has changed --
-// a batch that grew the context's tree / selection records between two replays used to leave them pointing at freed memory.
-// Round 6 (advice): a context's buffers count on the CONTEXT's counter (gf_context::bufMoves) -- with one counter for the process
-// another GPU's shard or another thread's batch made every context drop and re-record its graphs; this one is what is left for
-// buffers that belong to no context.
+// captured with: the one-tile graphs (gf_single) remember the count they were recorded at and are dropped when it has changed.
+// A context's buffers count on the CONTEXT's counter (gf_context::bufMoves): another GPU's shard or another thread's batch must
+// not make every context re-record its graphs.  This one is for the buffers that belong to no context.
 inline std::atomic<uint64_t> g_devBufMoves{0};
 
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
     std::atomic<uint64_t> *moves = &g_devBufMoves;
+    DevBuf *next = nullptr;                         // the owner's list (gf_context::bufs)
+    DevBuf() = default;
+    explicit DevBuf(gf_context *owner);             // a context's buffer: links itself in and counts on the context's counter
+    DevBuf(const DevBuf &) = delete;
+    // a laid-out buffer: the Carve's parts + slack bytes; at<T>(offset) is a part
+    gf_status ensure(const Carve &k, size_t slack = 16) { return ensure(k.total + slack); }
+    template <class T> T *at(size_t offset) const { return (T *)((uint8_t *)p + offset); }
     gf_status ensure(size_t need)
     {
         if (need <= bytes) return GF_OK;
@@ -96,67 +101,12 @@ struct DevBuf {
     }
 };
 
-struct gf_context {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    DevBuf workspace;      // decode spill: grid * 6*cells
-    DevBuf trees;          // leaf records of the tree pre-pass: GF_TREE_REC_WORDS per tile
-    DevBuf flags;          // one word: tiles the fast decode kernel left to the general one (GfDecodeArgs::retryFlag)
-    DevBuf packRecs;       // encoder: selection records between k_huffman_encode and k_huffman_pack
-    // staging for the host-memory entry points
-    DevBuf dValues, dSlots, dBlob, dLengths, dPred, dStatus, dOffsets;
-    DevBuf dPlanes;        // CodecFloat plane staging
-    DevBuf dResiduals, dCoefs, dStatus2;   // LSOP staging
-    DevBuf dM32, dM32Len, dM32Models, dSeeds;   // CodecDeflate staging
-    DevBuf dInflate, dInflOut, dInflMeta;       // GPU inflate: stream descriptors, inflated bytes, produced / status
-    DevBuf dBlockTmp, dBlockIdx, dBlockSlots;   // grid blocks (gvrs_api_blocks.hip): the records' decoded tiles on their way into a block, the
-                                                // gather's element table and the records' tile indices, the slot table of the block's tiles
-    DevBuf dRecMeta, dRecSub, dRecTmp;          // records / mixed packings in device memory (gvrs_api_records_dev.hip): per-record framing
-                                                // results, the partition by codec, decoded tiles on their way to their place
-    DevBuf dBwTiles, dBwMeta, dBwStage;         // a block written (gvrs_api_blocks_write.hip): the elements' cut tiles, the tiles' flags and pre-status
-                                                // (the host form: its results too), the host form's blocks, old records and records
-    DevBuf dEncSlots, dEncMeta, dEncWide;       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots, their
-                                                // lengths / statuses and the records' layout, SHORT cells widened for the codecs
-    DevBuf dInterp;                             // interpolation, host form (gvrs_api_interp.hip): block, coordinates, spacings and outputs
-    DevBuf dDsBlocks, dDsStage;                 // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks; the host
-                                                // forms' blocks and coarse blocks
-    std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
-    std::array<DevBuf *, 37> buffers()              // every one of them: counted by the constructor, released by gf_context_destroy
-    {
-        return {&workspace, &trees, &flags, &packRecs, &dValues, &dSlots, &dBlob, &dLengths, &dPred, &dStatus, &dOffsets, &dPlanes,
-                &dResiduals, &dCoefs, &dStatus2, &dM32, &dM32Len, &dM32Models, &dSeeds, &dInflate, &dInflOut, &dInflMeta, &dRecMeta, &dRecSub, &dRecTmp,
-                &dBlockTmp, &dBlockIdx, &dBlockSlots, &dEncSlots, &dEncMeta, &dEncWide, &dBwTiles, &dBwMeta, &dBwStage, &dInterp, &dDsBlocks, &dDsStage};
-    }
-    gf_context()
-    {
-        for (DevBuf *b : buffers()) b->moves = &bufMoves;
-    }
-    // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
-    // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
-    // scratch buffers, staging slots and recorded graphs are one set.  Recursive: entry points call each other.
-    std::recursive_mutex mu;
-    GfSideStream side{nullptr, nullptr, nullptr};   // second stream + fork / join events: the fast decode kernel's roomy run (gvrs_kernels.h)
-    uint32_t *hRoomySeen = nullptr;                 // page-locked word: GfDecodeArgs::roomySeenHost
-    struct PinBuf *hRecCounts = nullptr;            // page-locked: the partition's counts on their way to the host (created on first use)
-    // what the last encode and the last decode batch launched (host side only: gf_internal_route_report)
-    uint32_t routeEnc = 0, routeDec = 0;            // GF_RT_* bits
-    int routeEncKind = -1, routeDecKind = -1, routeRoomy = GF_ROOMY_NONE, routePrepass = 0;
-    struct gf_host_pipe *pipe = nullptr;        // pipelined staging of the host-memory batch entry points (created on first use)
-    struct gf_single *single = nullptr;         // one tile per call: page-locked buffers and replayed graphs (created on first use)
-};
-void gf_host_pipe_destroy(struct gf_host_pipe *p);   // (gvrs_api_host.hip, as the next)
-void gf_single_destroy(struct gf_single *s);
-#define GF_CTX_LOCK(c)                                       \
-    std::unique_lock<std::recursive_mutex> gfCtxLock_;       \
-    if (c) gfCtxLock_ = std::unique_lock<std::recursive_mutex>((c)->mu)
-
-// the caller's stream, or the context's own
-inline hipStream_t streamOf(const gf_context *c, void *stream) { return stream ? (hipStream_t)stream : c->stream; }
-
 // page-locked host memory that grows on demand (the staging slots of gvrs_api_host.hip)
 struct PinBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    gf_status ensure(const Carve &k, size_t slack = 0) { return ensure(k.total + slack); }
+    template <class T> T *at(size_t offset) const { return (T *)((uint8_t *)p + offset); }
     gf_status ensure(size_t need)
     {
         if (need <= bytes) return GF_OK;
@@ -174,26 +124,75 @@ struct PinBuf {
     }
 };
 
-void gf_rec_counts_destroy(PinBuf *p);             // (gvrs_api_records_dev.hip)
+// A DevBuf is one line here: it links itself into bufs.  One DevBuf per owner: the host forms call one another while the caller's staging
+// is live (gf_block_write_elems -> recordsEncodeHost -> the float and LSOP host encoders; codecMasterDecodeScattered -> LSOP's host decode).
+struct gf_context {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::atomic<uint64_t> bufMoves{0};          // moves of THIS context's device buffers (DevBuf::moves): what its recorded graphs watch
+    DevBuf *bufs = nullptr;                     // every DevBuf below (declared before them: they link themselves in)
+    // scratch of the device forms, laid out by scratchPlan and sized ahead by gf_context_reserve
+    DevBuf workspace{this};      // decode spill: grid * 6*cells
+    DevBuf trees{this};          // leaf records of the tree pre-pass: GF_TREE_REC_WORDS per tile
+    DevBuf packRecs{this};       // encoder: selection records between k_huffman_encode and k_huffman_pack
+    DevBuf flags{this};          // one word: tiles the fast decode kernel left to the general one (GfDecodeArgs::retryFlag)
+    // staging of the host-memory entry points: whichever host form is called owns these for the call (the nested ones use their own)
+    DevBuf dValues{this}, dSlots{this}, dBlob{this}, dLengths{this}, dPred{this}, dStatus{this}, dOffsets{this};
+    DevBuf dPlanes{this};        // CodecFloat plane staging
+    DevBuf dResiduals{this}, dCoefs{this}, dStatus2{this};   // LSOP staging
+    DevBuf dM32{this}, dM32Len{this}, dM32Models{this}, dSeeds{this};   // CodecDeflate staging
+    DevBuf dInflate{this}, dInflOut{this}, dInflMeta{this};  // GPU inflate: stream descriptors, inflated bytes, produced / status
+    DevBuf dBlockTmp{this}, dBlockIdx{this}, dBlockSlots{this};   // grid blocks (gvrs_api_blocks.hip): the records' decoded tiles on their way into a block,
+                                                // the gather's element table and the records' tile indices, the slot table of the block's tiles
+    DevBuf dRecMeta{this}, dRecSub{this}, dRecTmp{this};          // records / mixed packings in device memory (gvrs_api_records_dev.hip): per-record framing
+                                                // results, the partition by codec, decoded tiles on their way to their place
+    DevBuf dBwTiles{this}, dBwMeta{this}, dBwStage{this};         // a block written (gvrs_api_blocks_write.hip): the elements' cut tiles, the tiles' flags and
+                                                // pre-status (the host form: its results too), the host form's blocks, old records and records
+    DevBuf dEncSlots{this}, dEncMeta{this}, dEncWide{this};       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots,
+                                                // their lengths / statuses and the records' layout, SHORT cells widened for the codecs
+    DevBuf dInterp{this};                       // interpolation, host form (gvrs_api_interp.hip): block, coordinates, spacings and outputs
+    DevBuf dDsBlocks{this}, dDsStage{this};     // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks; the host
+                                                // forms' blocks and coarse blocks
+    // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
+    // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
+    // scratch buffers, staging slots and recorded graphs are one set.  Recursive: entry points call each other.
+    std::recursive_mutex mu;
+    GfSideStream side{nullptr, nullptr, nullptr};   // second stream + fork / join events: the fast decode kernel's roomy run (gvrs_kernels.h)
+    uint32_t *hRoomySeen = nullptr;                 // page-locked word: GfDecodeArgs::roomySeenHost
+    PinBuf hRecCounts;                              // page-locked: the partition's counts on their way to the host
+    // what the last encode and the last decode batch launched (host side only: gf_internal_route_report)
+    uint32_t routeEnc = 0, routeDec = 0;            // GF_RT_* bits
+    int routeEncKind = -1, routeDecKind = -1, routeRoomy = GF_ROOMY_NONE, routePrepass = 0;
+    struct gf_host_pipe *pipe = nullptr;        // pipelined staging of the host-memory batch entry points (created on first use)
+    struct gf_single *single = nullptr;         // one tile per call: page-locked buffers and replayed graphs (created on first use)
+};
+void gf_host_pipe_destroy(struct gf_host_pipe *p);   // (gvrs_api_host.hip, as the next)
+void gf_single_destroy(struct gf_single *s);
+inline DevBuf::DevBuf(gf_context *owner) : moves(&owner->bufMoves), next(owner->bufs) { owner->bufs = this; }
+#define GF_CTX_LOCK(c)                                       \
+    std::unique_lock<std::recursive_mutex> gfCtxLock_;       \
+    if (c) gfCtxLock_ = std::unique_lock<std::recursive_mutex>((c)->mu)
+
+// the caller's stream, or the context's own
+inline hipStream_t streamOf(const gf_context *c, void *stream) { return stream ? (hipStream_t)stream : c->stream; }
 
 // codec kinds behind the shared batch plumbing
 enum { KIND_HUFFMAN = 0, KIND_CANON = 1, KIND_RAW_M32 = 2, KIND_DEFLATE = 3, KIND_FLOAT = 4 };
 
-inline size_t decodeWorkspaceStride(int nRows, int nCols)
-{
-    // spill layout of the decode kernel: M32 bytes (6 per cell, rounded to 32), start bitmap, rank bases
-    const size_t cap = roundUp((size_t)6 * (size_t)nRows * (size_t)nCols, 32);
-    return roundUp(cap + 2 * ((cap >> 5) + 2) * 4 + 64, 16);
-}
-
-// the encoders' per-tile records between their kernels (selection records, statistics) and, behind them, the legacy encoder's byte
-// plane of raw row differences (GfEncodeArgs::plane): one allocation of the context
-inline size_t encPlaneStride(int nRows, int nCols) { return roundUp((size_t)nRows * (size_t)nCols, 16); }
-inline size_t encRecordBytes(int nRows, int nCols, size_t nTiles)
-{
-    const size_t recs = nTiles * std::max((size_t)GF_PACK_REC_WORDS + GF_ENC_STAT_WORDS, gf_canon_pack_rec_words() + gf_canon_stat_words()) * 4 + 16;
-    return roundUp(recs, 256) + nTiles * encPlaneStride(nRows, nCols) + 256;
-}
+// ---- the scratch plan (gvrs_api_route.hip): what a batch of a kind needs of workspace, trees and packRecs, and where the parts lie.
+// The launch sites take sizes and offsets from it and gf_context_reserve allocates its maximum over the kinds: no _dev call after it allocates.
+enum { KIND_LSOP_DEC = 5, KIND_LSOP_ENC = 6 };      // LSOP12's needs, beside the KIND_* of the route plan
+struct gf_scratch_part { uint64_t at, bytes; };
+struct gf_scratch_plan {
+    uint64_t workspace, trees, packRecs;            // bytes needed
+    uint64_t wsStride, planeStride;                 // bytes per workgroup of the decode grid in workspace, per tile of the byte plane (0: none)
+    gf_scratch_part leaf, spare, roomy;             // trees, CodecHuffman decode: leaf records, four spare words, the roomy run's tile list
+    gf_scratch_part lengths, slack;                 // trees, CodecCanonHuffman decode: length records, the slack behind them (the fast run's where viaFast)
+    gf_scratch_part lsop0, lsop1;                   // trees, LSOP12 decode: the length records of the two streams
+    gf_scratch_part sel, stats, plane, hist;        // packRecs: selection records, statistics, byte plane (not lean); LSOP12 encode: histogram records
+};
+gf_status scratchPlan(int kind, int nRows, int nCols, size_t nTiles, int lean, int viaFast, gf_scratch_plan &p);
+void scratchReserve(int nRows, int nCols, size_t nTiles, uint64_t need[3]);       // workspace, trees, packRecs: the maximum over the kinds
 
 constexpr size_t INFLATE_SCRATCH_BYTES = (size_t)1 << 30;     // thousands of streams per launch: a stream is one serial chain
 
@@ -260,6 +259,23 @@ gf_status elemsArgs(const gf_context *c, const int *codecs, int nCodecs, const g
                     size_t nTiles, const uint8_t *blob, bool blobOnDevice, const uint64_t *offsets, void *const *values,
                     const int32_t *status);
 size_t elemItemBytes(int type);
+// one array of `count` cells per element in a Carve (+ extra bytes behind each): at[e] is element e's offset
+inline void carveElems(Carve &k, const gf_elem_spec *elems, int nElems, size_t count, size_t *at, size_t extra = 0)
+{
+    size_t item[GF_MAX_ELEMS];
+    for (int e = 0; e < nElems; e++) item[e] = elemItemBytes(elems[e].type);
+    k.each(nElems, count, item, at, extra);
+}
+// ... and a buffer that holds those arrays alone: ensured, arrays[e] is element e's
+inline gf_status elemArrays(DevBuf &b, const gf_elem_spec *elems, int nElems, size_t count, void **arrays, size_t extra = 0)
+{
+    Carve k;
+    size_t at[GF_MAX_ELEMS];
+    carveElems(k, elems, nElems, count, at, extra);
+    const gf_status s = b.ensure(k);
+    for (int e = 0; e < nElems && s == GF_OK; e++) arrays[e] = b.at<void>(at[e]);
+    return s;
+}
 gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
                            int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets,
                            const uint32_t *dLengths, int verifyChecksum, int32_t *dTileIndices, void *const *dValues, int32_t *dStatus);

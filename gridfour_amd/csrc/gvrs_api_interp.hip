@@ -89,22 +89,23 @@ gf_status gf_block_interp_points(gf_context *c, const gf_interp_spec *spec, cons
     if (nPoints == 0) return GF_OK;
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
-    // staging: block | rows | cols | spacings | z zx zy zxx zxy zyy | normal | status, each part a multiple of 16 bytes
+    // staging: block | rows | cols | spacings | z zx zy zxx zxy zyy | normal | status, the parts that the call has
     const size_t blockBytes = (size_t)a.g.bRows * (size_t)a.g.bCols * (a.g.elemType == GF_ELEM_SHORT ? 2 : 4);
     const size_t arr = roundUp(nPoints * 8, 16);
     double *const host[6] = {out->z, out->zx, out->zy, out->zxx, out->zxy, out->zyy};
-    size_t need = roundUp(blockBytes, 16) + 2 * arr + (colSpacing ? arr : 0);
-    for (double *h : host) need += h ? arr : 0;
-    need += (out->normal ? 3 * arr : 0) + (out->status ? roundUp(nPoints * 4, 16) : 0);
-    if ((s = c->dInterp.ensure(need + 16)) != GF_OK) return s;
-    uint8_t *p = (uint8_t *)c->dInterp.p;
-    auto take = [&p](size_t bytes) { uint8_t *q = p; p += bytes; return q; };
-    uint8_t *dBlock = take(roundUp(blockBytes, 16));
-    double *dRows = (double *)take(arr), *dCols = (double *)take(arr), *dCs = colSpacing ? (double *)take(arr) : nullptr;
+    Carve lay;
+    const size_t blockAt = lay.add(blockBytes), rowsAt = lay.add(arr), colsAt = lay.add(arr), csAt = lay.add(colSpacing ? arr : 0);
+    size_t devAt[6];
+    for (int k = 0; k < 6; k++) devAt[k] = lay.add(host[k] ? arr : 0);
+    const size_t normalAt = lay.add(out->normal ? 3 * arr : 0), statusAt = lay.add(out->status ? nPoints * 4 : 0);
+    if ((s = c->dInterp.ensure(lay)) != GF_OK) return s;
+    const DevBuf &B = c->dInterp;
+    uint8_t *dBlock = B.at<uint8_t>(blockAt);
+    double *dRows = B.at<double>(rowsAt), *dCols = B.at<double>(colsAt), *dCs = colSpacing ? B.at<double>(csAt) : nullptr;
     double *dev[6];
-    for (int k = 0; k < 6; k++) dev[k] = host[k] ? (double *)take(arr) : nullptr;
-    double *dNormal = out->normal ? (double *)take(3 * arr) : nullptr;
-    int32_t *dStatus = out->status ? (int32_t *)take(roundUp(nPoints * 4, 16)) : nullptr;
+    for (int k = 0; k < 6; k++) dev[k] = host[k] ? B.at<double>(devAt[k]) : nullptr;
+    double *dNormal = out->normal ? B.at<double>(normalAt) : nullptr;
+    int32_t *dStatus = out->status ? B.at<int32_t>(statusAt) : nullptr;
     GF_HIP(hipMemcpyAsync(dBlock, block, blockBytes, hipMemcpyHostToDevice, c->stream));
     GF_HIP(hipMemcpyAsync(dRows, rows, nPoints * 8, hipMemcpyHostToDevice, c->stream));
     GF_HIP(hipMemcpyAsync(dCols, cols, nPoints * 8, hipMemcpyHostToDevice, c->stream));

@@ -2,18 +2,13 @@
 
 #include "gvrs_api_internal.h"
 
-// code-length pre-pass for the first stream of LSOP12 containers of the canonical type
+// code-length pre-pass for the first stream of LSOP12 containers of the canonical type (the caller has checked c and set its device)
 static gf_status lsopParseLengths(gf_context *c, hipStream_t st, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
-                                  const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths)
+                                  const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, gf_scratch_plan &sp)
 {
-    if (!c) return GF_ERR_ARG;
-    GF_HIP(hipSetDevice(c->device));                        // launches and copies below go to the context's device
-    const size_t need = 2 * nTiles * (size_t)GF_CANON_REC_WORDS * 4 + 16;     // (both streams' records: k_lsop_head)
-    if (c->trees.bytes < need) {                           // not capture-safe: gf_context_reserve sizes this too
-        gf_status s = c->trees.ensure(need);
-        if (s != GF_OK) return s;
-    }
-    GF_HIP(gf_launch_canon_parse_lengths(dBlob, blobBytes, dOffsets, slotStride, dLengths, (uint32_t *)c->trees.p, nTiles, 1, st));
+    gf_status s = scratchPlan(KIND_LSOP_DEC, 1, 1, nTiles, 0, 0, sp);             // (the records do not depend on the tile shape)
+    if (s != GF_OK || (s = c->trees.ensure(sp.trees)) != GF_OK) return s;
+    GF_HIP(gf_launch_canon_parse_lengths(dBlob, blobBytes, dOffsets, slotStride, dLengths, c->trees.at<uint32_t>(sp.lsop0.at), nTiles, 1, st));
     return GF_OK;
 }
 
@@ -25,15 +20,10 @@ static gf_status lsopUnpackM32(gf_context *c, hipStream_t st, int nRows, int nCo
                                const uint8_t *rawSide = nullptr, size_t rawSideStride = 0, const int32_t *sideStatus = nullptr,
                                const uint32_t *produced2 = nullptr, const int32_t *inflStatus2 = nullptr)
 {
-    if (!c) return GF_ERR_ARG;
-    GF_HIP(hipSetDevice(c->device));                        // launches and copies below go to the context's device
     const unsigned grid = gf_huffman_decode_grid(nTiles);
-    const size_t wsStride = decodeWorkspaceStride(nRows, nCols);
-    if (c->workspace.bytes < (size_t)grid * wsStride) {
-        // not capture-safe: callers that capture graphs call gf_context_reserve first
-        gf_status s = c->workspace.ensure((size_t)grid * wsStride);
-        if (s != GF_OK) return s;
-    }
+    gf_scratch_plan sp;
+    gf_status s = scratchPlan(KIND_LSOP_DEC, nRows, nCols, nTiles, 0, 0, sp);
+    if (s != GF_OK || (s = c->workspace.ensure(sp.workspace)) != GF_OK) return s;
     GfLsopM32Args a;
     a.blob = dBlob;
     a.blobBytes = blobBytes;
@@ -45,7 +35,7 @@ static gf_status lsopUnpackM32(gf_context *c, hipStream_t st, int nRows, int nCo
     a.coefs = dCoefs;
     a.status = dScratchStatus;
     a.workspace = (uint8_t *)c->workspace.p;
-    a.workspaceStride = wsStride;
+    a.workspaceStride = sp.wsStride;
     a.nTiles = nTiles;
     a.nRows = nRows;
     a.nCols = nCols;
@@ -79,12 +69,16 @@ static gf_status lsopUnpackM32Deflate(gf_context *c, hipStream_t st, int nRows, 
     gf_status s;
     if ((s = c->dInflOut.ensure(chunk * rawStride + 64)) != GF_OK) return s;
     if ((s = c->dInflate.ensure(chunk * sizeof(GfInflateStream))) != GF_OK) return s;
-    if ((s = c->dInflMeta.ensure(chunk * 7 * 4 + 128)) != GF_OK) return s;
+    Carve k;
+    size_t at[6];                            // per stream: produced, consumed, produced (second stream), the two statuses, the side table
+    for (size_t &x : at) x = k.add(chunk * 4);
+    const size_t gateAt = k.add(4);
+    if ((s = c->dInflMeta.ensure(k, chunk * 4 + 112)) != GF_OK) return s;
     uint8_t *raw = (uint8_t *)c->dInflOut.p;
     GfInflateStream *desc = (GfInflateStream *)c->dInflate.p;
-    uint32_t *produced1 = (uint32_t *)c->dInflMeta.p, *consumed1 = produced1 + chunk, *produced2 = consumed1 + chunk;
-    int32_t *status1 = (int32_t *)(produced2 + chunk), *status2 = status1 + chunk, *side = status2 + chunk;
-    uint32_t *gate = (uint32_t *)(side + chunk);                   // number of Deflate containers in the chunk
+    uint32_t *produced1 = c->dInflMeta.at<uint32_t>(at[0]), *consumed1 = c->dInflMeta.at<uint32_t>(at[1]), *produced2 = c->dInflMeta.at<uint32_t>(at[2]);
+    int32_t *status1 = c->dInflMeta.at<int32_t>(at[3]), *status2 = c->dInflMeta.at<int32_t>(at[4]), *side = c->dInflMeta.at<int32_t>(at[5]);
+    uint32_t *gate = c->dInflMeta.at<uint32_t>(gateAt);            // number of Deflate containers in the chunk
     for (size_t t0 = 0; t0 < nTiles; t0 += chunk) {
         const size_t n = std::min(chunk, nTiles - t0);
         GF_HIP(hipMemsetAsync(gate, 0, 4, st));
@@ -140,11 +134,9 @@ static gf_status lsopEncodeBatchDev(gf_context *c, void *stream, int codecIndex,
     uint32_t *hist16 = nullptr;
     gf_status s;
     if (fast16) {
-        const size_t need = nTiles * gf_lsop_hist_rec_words() * 4 + 16;
-        if (c->packRecs.bytes < need) {                    // not capture-safe: gf_context_reserve sizes this too
-            if ((s = c->packRecs.ensure(need)) != GF_OK) return s;
-        }
-        hist16 = (uint32_t *)c->packRecs.p;
+        gf_scratch_plan sp;
+        if ((s = scratchPlan(KIND_LSOP_ENC, nRows, nCols, nTiles, 0, 0, sp)) != GF_OK || (s = c->packRecs.ensure(sp.packRecs)) != GF_OK) return s;
+        hist16 = c->packRecs.at<uint32_t>(sp.hist.at);
         GF_HIP(gf_launch_lsop_predict16(dValues, dResiduals, resStride, dCoefs, dScratchStatus, hist16, nTiles, nRows, nCols, st));
     } else {
         s = gf_lsop12_predict_dev(c, stream, nRows, nCols, nTiles, dValues, dResiduals, resStride, dCoefs, dScratchStatus);
@@ -261,14 +253,15 @@ gf_status gf_lsop12_decode_batch_i32_dev(gf_context *c, void *stream, int nRows,
     }
     if (resStride < gf_lsop12_residual_count(nRows, nCols)) return GF_ERR_ARG;
     const unsigned grid = gf_huffman_decode_grid(nTiles);
-    gf_status s = lsopParseLengths(c, st, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths);
+    gf_scratch_plan sp;
+    gf_status s = lsopParseLengths(c, st, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths, sp);
     if (s != GF_OK) return s;
     // (round 6) interior residuals as byte planes in the reconstruction's order where a tile's values allow (gvrs_kernels.h)
     GF_HIP(gf_launch_lsop_unpack2(dBlob, blobBytes, dOffsets, slotStride, dLengths, dResiduals, resStride, dCoefs,
                                   dScratchStatus, nTiles, nRows, nCols, gf_lsop_unpack_lds_text(nRows, nCols), grid, st,
-                                  (const uint32_t *)c->trees.p, g_decodeDebug,
+                                  c->trees.at<const uint32_t>(sp.lsop0.at), g_decodeDebug,
                                   // (the serial walk of a lane pays where sixty-four tiles share a wave: large batches)
-                                  gf_prepass_tiles_per_wave(nTiles) == 64u ? (uint32_t *)c->trees.p + nTiles * (size_t)GF_CANON_REC_WORDS : nullptr,
+                                  gf_prepass_tiles_per_wave(nTiles) == 64u ? c->trees.at<uint32_t>(sp.lsop1.at) : nullptr,
                                   true));
     s = lsopUnpackM32Deflate(c, st, nRows, nCols, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths, dResiduals, resStride,
                              dCoefs, dScratchStatus);

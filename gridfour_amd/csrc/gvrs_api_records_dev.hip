@@ -10,13 +10,6 @@
 
 #include "gvrs_api_internal.h"
 
-void gf_rec_counts_destroy(PinBuf *p)
-{
-    if (!p) return;
-    p->release();
-    delete p;
-}
-
 namespace {
 
 // one codec's share of the batch through its device decoder: packing j = lengths[j] bytes at dBlob + offsets[j]; the entry that is
@@ -77,24 +70,23 @@ gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int n
     GF_HIP(hipSetDevice(c->device));
     const hipStream_t st = streamOf(c, stream);
     const int nSeg = nCodecs + 1;                                                 // the codecs, then the standard form
-    const size_t nPad = roundUp(nInst, 4), nRecPad = roundUp(n, 4);
+    // per instance (a multiple of 4 of them): start, length, class; per record: size.  The partition: per instance offset, length,
+    // destination, status; the segments' counts; the element table
+    const size_t nPad = roundUp(nInst, 4);
+    Carve meta, sub;
+    const size_t startsAt = meta.add(nPad * 8), lensAt = meta.add(nPad * 4), clsAt = meta.add(nPad * 4), sizesAt = meta.add(n * 4);
+    const size_t subOffAt = sub.add(nPad * 8), subLenAt = sub.add(nPad * 4), subDstAt = sub.add(nPad * 4), subStatusAt = sub.add(nPad * 4);
+    const size_t countsAt = sub.add(256 * 4), elemsAt = sub.add(GF_MAX_ELEMS * sizeof(GfElemDesc));
     gf_status s;
-    if ((s = c->dRecMeta.ensure(nPad * 16 + nRecPad * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dRecSub.ensure(nPad * 20 + 256 * 4 + GF_MAX_ELEMS * sizeof(GfElemDesc) + 16)) != GF_OK) return s;
-    if (!c->hRecCounts) {
-        c->hRecCounts = new (std::nothrow) PinBuf();
-        if (!c->hRecCounts) return GF_ERR_HIP;
-    }
-    if ((s = c->hRecCounts->ensure(256 * 4)) != GF_OK) return s;
-    uint64_t *starts = (uint64_t *)c->dRecMeta.p;
-    uint32_t *lens = (uint32_t *)(starts + nPad);
-    int32_t *cls = (int32_t *)(lens + nPad);
-    uint32_t *sizes = (uint32_t *)(cls + nPad);
-    uint64_t *subOffsets = (uint64_t *)c->dRecSub.p;
-    uint32_t *subLengths = (uint32_t *)(subOffsets + nPad), *subDst = subLengths + nPad;
-    int32_t *subStatus = (int32_t *)(subDst + nPad);
-    uint32_t *dCounts = (uint32_t *)(subStatus + nPad);
-    GfElemDesc *dElems = (GfElemDesc *)(dCounts + 256);                            // (16-byte aligned: every part is a multiple of 16)
+    if ((s = c->dRecMeta.ensure(meta)) != GF_OK) return s;
+    if ((s = c->dRecSub.ensure(sub)) != GF_OK) return s;
+    if ((s = c->hRecCounts.ensure(256 * 4)) != GF_OK) return s;
+    const DevBuf &M = c->dRecMeta, &S = c->dRecSub;
+    uint64_t *starts = M.at<uint64_t>(startsAt), *subOffsets = S.at<uint64_t>(subOffAt);
+    uint32_t *lens = M.at<uint32_t>(lensAt), *sizes = M.at<uint32_t>(sizesAt), *subLengths = S.at<uint32_t>(subLenAt), *subDst = S.at<uint32_t>(subDstAt);
+    int32_t *cls = M.at<int32_t>(clsAt), *subStatus = S.at<int32_t>(subStatusAt);
+    uint32_t *dCounts = S.at<uint32_t>(countsAt);
+    GfElemDesc *dElems = S.at<GfElemDesc>(elemsAt);
 
     // the element table for k_elem_scatter; the walk takes the types as a packed word.  (A pageable source: the runtime has
     // staged the copy when the call returns, and the table outlives the synchronisation below anyway.)
@@ -145,8 +137,8 @@ gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int n
     q.counts = dCounts;
     GF_HIP(gf_launch_codec_partition(q, st));
     // the one synchronisation of the call: the host has to know which decoders to launch, and for how many instances
-    const uint32_t *counts = (const uint32_t *)c->hRecCounts->p;
-    GF_HIP(hipMemcpyAsync(c->hRecCounts->p, dCounts, (size_t)nSeg * 4, hipMemcpyDeviceToHost, st));
+    const uint32_t *counts = (const uint32_t *)c->hRecCounts.p;
+    GF_HIP(hipMemcpyAsync(c->hRecCounts.p, dCounts, (size_t)nSeg * 4, hipMemcpyDeviceToHost, st));
     GF_HIP(hipStreamSynchronize(st));
     size_t nPacked = 0;
     for (int k = 0; k < nCodecs; k++) nPacked += counts[k];
@@ -245,19 +237,18 @@ gf_status gf_tile_record_decode_batch_elems(gf_context *c, const int *codecs, in
     if (cells >= (1ull << 28)) return GF_ERR_UNSUPPORTED;
     GF_HIP(hipSetDevice(c->device));
     const size_t blobBytes = (size_t)offsets[nTiles];
-    // staging: blob | offsets | values of element 0, 1, ... (each part a multiple of 16 bytes) | statuses, tile indices
-    size_t valueBytes = 0, at[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        at[e] = valueBytes;
-        valueBytes += roundUp(nTiles * cells * elemItemBytes(elems[e].type), 16);
-    }
+    // staging: blob | offsets | values of element 0, 1, ... | statuses, tile indices
+    Carve vals, stat;
+    size_t at[GF_MAX_ELEMS];
+    carveElems(vals, elems, nElems, nTiles * cells, at);
+    const size_t valueBytes = vals.total, statusAt = stat.add(nInst * 4), indicesAt = stat.add(nTiles * 4);
     if ((s = c->dBlob.ensure(blobBytes + 32)) != GF_OK) return s;
     if ((s = c->dOffsets.ensure((nTiles + 1) * 8 + 16)) != GF_OK) return s;
-    if ((s = c->dValues.ensure(valueBytes + 16)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure((nInst + nTiles) * 4 + 16)) != GF_OK) return s;
-    int32_t *dStatus = (int32_t *)c->dStatus.p, *dIndices = dStatus + nInst;
+    if ((s = c->dValues.ensure(vals)) != GF_OK) return s;
+    if ((s = c->dStatus.ensure(stat)) != GF_OK) return s;
+    int32_t *dStatus = c->dStatus.at<int32_t>(statusAt), *dIndices = c->dStatus.at<int32_t>(indicesAt);
     void *dValues[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) dValues[e] = (uint8_t *)c->dValues.p + at[e];
+    for (int e = 0; e < nElems; e++) dValues[e] = c->dValues.at<void>(at[e]);
     GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, blobBytes, hipMemcpyHostToDevice, c->stream));
     GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nTiles + 1) * 8, hipMemcpyHostToDevice, c->stream));
     if (tileIndices) GF_HIP(hipMemcpyAsync(dIndices, tileIndices, nTiles * 4, hipMemcpyHostToDevice, c->stream));   // (a failed record keeps the caller's entry)

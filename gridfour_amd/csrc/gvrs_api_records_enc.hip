@@ -68,7 +68,8 @@ gf_status recordsEncodeDev(gf_context *c, void *stream, const int *codecs, int n
             act[nAct++] = k;
         }
     // sizes of the temporaries ("records written on the device")
-    size_t slotBytes = 0, wideBytes = 0, nCandArrays = 0, slotAt[GF_MAX_ELEMS] = {}, wideAt[GF_MAX_ELEMS] = {};
+    Carve slots, wide, meta;
+    size_t nCandArrays = 0, slotAt[GF_MAX_ELEMS] = {}, wideAt[GF_MAX_ELEMS] = {};
     for (int e = 0; e < nElems; e++) {
         const size_t stdSize = elemStandardSize(elems[e].type == GF_ELEM_SHORT ? GF_ELEM_SHORT : GF_ELEM_INT, cells);
         p.elems[e].values = dValues[e];
@@ -77,39 +78,38 @@ gf_status recordsEncodeDev(gf_context *c, void *stream, const int *codecs, int n
         if (isIntElem(elems[e].type) && nAct > 0) {
             p.elems[e].slotStride = (uint32_t)roundUp(stdSize, 16);
             p.elems[e].cand0 = (uint32_t)nCandArrays;
-            slotAt[e] = slotBytes;
-            slotBytes += (size_t)nAct * n * p.elems[e].slotStride;
+            slotAt[e] = slots.add((size_t)nAct * n * p.elems[e].slotStride);
             nCandArrays += (size_t)nAct;
-            if (elems[e].type == GF_ELEM_SHORT) {
-                wideAt[e] = wideBytes;
-                wideBytes += roundUp(n * cells * 4, 16);
-            }
+            if (elems[e].type == GF_ELEM_SHORT) wideAt[e] = wide.add(n * cells * 4);
         }
     }
-    const size_t nCand = nCandArrays * n, candPad = roundUp(nCand, 4), instPad = roundUp(nInst, 16), recPad = roundUp(n, 4);
+    // per candidate length and status; per instance (a multiple of 16 of them) length and position; per record its size; per instance its source
+    const size_t nCand = nCandArrays * n, instPad = roundUp(nInst, 16);
+    const size_t candLenAt = meta.add(nCand * 4), candStatusAt = meta.add(nCand * 4), elemLenAt = meta.add(instPad * 4), elemPosAt = meta.add(instPad * 4);
+    const size_t sizesAt = meta.add(n * 4), elemSrcAt = meta.add(instPad);
     gf_status s;
-    if ((s = c->dEncMeta.ensure(candPad * 8 + instPad * 9 + recPad * 4 + 64)) != GF_OK) return s;
-    if (slotBytes && (s = c->dEncSlots.ensure(slotBytes + 16)) != GF_OK) return s;
-    if (wideBytes && (s = c->dEncWide.ensure(wideBytes + 16)) != GF_OK) return s;
-    uint32_t *candLen = (uint32_t *)c->dEncMeta.p;
-    int32_t *candStatus = (int32_t *)(candLen + candPad);
-    uint32_t *elemLen = (uint32_t *)(candStatus + candPad), *elemPos = elemLen + instPad, *sizes = elemPos + instPad;
-    uint8_t *elemSrc = (uint8_t *)(sizes + recPad);
+    if ((s = c->dEncMeta.ensure(meta, 64)) != GF_OK) return s;
+    if (slots.total && (s = c->dEncSlots.ensure(slots)) != GF_OK) return s;
+    if (wide.total && (s = c->dEncWide.ensure(wide)) != GF_OK) return s;
+    const DevBuf &m = c->dEncMeta;
+    uint32_t *candLen = m.at<uint32_t>(candLenAt), *elemLen = m.at<uint32_t>(elemLenAt), *elemPos = m.at<uint32_t>(elemPosAt), *sizes = m.at<uint32_t>(sizesAt);
+    int32_t *candStatus = m.at<int32_t>(candStatusAt);
+    uint8_t *elemSrc = m.at<uint8_t>(elemSrcAt);
 
     // the codecs: every integer codec of the list on every integer element, in element order, then list order
     for (int e = 0; e < nElems; e++) {
         if (!p.elems[e].slotStride) continue;
-        p.elems[e].slots = (const uint8_t *)c->dEncSlots.p + slotAt[e];
+        p.elems[e].slots = c->dEncSlots.at<const uint8_t>(slotAt[e]);
         const int32_t *iv = (const int32_t *)dValues[e];                            // INT, and the codes of an ICF element, in place
         if (elems[e].type == GF_ELEM_SHORT) {
-            int32_t *wide = (int32_t *)((uint8_t *)c->dEncWide.p + wideAt[e]);
-            GF_HIP(gf_launch_elem_widen((const int16_t *)dValues[e], wide, n * cells, elems[e].fill_i, st));
-            iv = wide;
+            int32_t *widened = c->dEncWide.at<int32_t>(wideAt[e]);
+            GF_HIP(gf_launch_elem_widen((const int16_t *)dValues[e], widened, n * cells, elems[e].fill_i, st));
+            iv = widened;
         }
         for (int a = 0; a < nAct; a++) {
             const size_t cand = ((size_t)p.elems[e].cand0 + a) * n;
-            uint8_t *slots = (uint8_t *)c->dEncSlots.p + slotAt[e] + (size_t)a * n * p.elems[e].slotStride;
-            s = encodeBatchDev(codecs[act[a]] == GF_CODEC_HUFFMAN ? KIND_HUFFMAN : KIND_CANON, c, st, act[a], nRows, nCols, n, iv, slots,
+            uint8_t *slotsOf = c->dEncSlots.at<uint8_t>(slotAt[e] + (size_t)a * n * p.elems[e].slotStride);
+            s = encodeBatchDev(codecs[act[a]] == GF_CODEC_HUFFMAN ? KIND_HUFFMAN : KIND_CANON, c, st, act[a], nRows, nCols, n, iv, slotsOf,
                                p.elems[e].slotStride, candLen + cand, nullptr, candStatus + cand, GF_PM_ALL, 0);
             if (s != GF_OK) return s;
         }
@@ -291,27 +291,22 @@ gf_status gf_tile_record_encode_batch_elems(gf_context *c, const int *codecs, in
     if (!deviceList(codecs, nCodecs, elems, nElems))
         return recordsEncodeHost(c, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, tileIndices, values, checksumEnabled, blob, blobCap,
                                  offsets, codecUsed);
-    // staged through buffers of the context and sent through the device form: values of element 0, 1, ... (each part a multiple of 16
-    // bytes, four spare bytes behind the last) | the blob at its largest | offsets | tile indices, statuses | codec_used
+    // staged through buffers of the context and sent through the device form: values of element 0, 1, ... (four spare bytes behind
+    // each) | the blob at its largest | offsets | tile indices, statuses | codec_used
     GF_HIP(hipSetDevice(c->device));
     const size_t cells = (size_t)nRows * (size_t)nCols, nInst = (size_t)nElems * nTiles;
-    size_t valueBytes = 0, at[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        at[e] = valueBytes;
-        valueBytes += roundUp(nTiles * cells * elemItemBytes(elems[e].type) + 4, 16);
-    }
+    Carve stat;
+    void *dValues[GF_MAX_ELEMS];
+    const size_t indicesAt = stat.add(nTiles * 4), statusAt = stat.add(nTiles * 4);
     const size_t maxBlob = nTiles * gf_tile_record_max_bytes_elems(elems, nElems, nRows, nCols);
-    if ((s = c->dValues.ensure(valueBytes + 16)) != GF_OK) return s;
+    if ((s = elemArrays(c->dValues, elems, nElems, nTiles * cells, dValues, 4)) != GF_OK) return s;
     if ((s = c->dBlob.ensure(maxBlob + 32)) != GF_OK) return s;
     if ((s = c->dOffsets.ensure((nTiles + 1) * 8 + 16)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure(nTiles * 8 + 32)) != GF_OK) return s;
+    if ((s = c->dStatus.ensure(stat, 32)) != GF_OK) return s;
     if ((s = c->dPred.ensure(nInst + 16)) != GF_OK) return s;
-    int32_t *dIndices = (int32_t *)c->dStatus.p, *dStatus = dIndices + roundUp(nTiles, 4);
-    const void *dValues[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        dValues[e] = (uint8_t *)c->dValues.p + at[e];
-        GF_HIP(hipMemcpyAsync((void *)dValues[e], values[e], nTiles * cells * elemItemBytes(elems[e].type), hipMemcpyHostToDevice, c->stream));
-    }
+    int32_t *dIndices = c->dStatus.at<int32_t>(indicesAt), *dStatus = c->dStatus.at<int32_t>(statusAt);
+    for (int e = 0; e < nElems; e++)
+        GF_HIP(hipMemcpyAsync(dValues[e], values[e], nTiles * cells * elemItemBytes(elems[e].type), hipMemcpyHostToDevice, c->stream));
     GF_HIP(hipMemcpyAsync(dIndices, tileIndices, nTiles * 4, hipMemcpyHostToDevice, c->stream));
     s = recordsEncodeDev(c, c->stream, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, dIndices, dValues, checksumEnabled,
                          (uint8_t *)c->dBlob.p, maxBlob, (uint64_t *)c->dOffsets.p, (uint8_t *)c->dPred.p, dStatus);

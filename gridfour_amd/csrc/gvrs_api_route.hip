@@ -165,6 +165,47 @@ static gf_status routePlan(int kind, int nRows, int nCols, size_t nTiles, int le
     return GF_OK;
 }
 
+// ------------------------------------------------------------------ scratch plan
+// What a batch needs of the context's three scratch buffers and where the parts lie (gvrs_api_internal.h).  No device, no HIP call.
+// Exported for the tests as gf_internal_scratch_plan / gf_internal_scratch_reserve (loaded by name, like gf_internal_route_plan).
+gf_status scratchPlan(int kind, int nRows, int nCols, size_t nTiles, int lean, int viaFast, gf_scratch_plan &p)
+{
+    p = gf_scratch_plan{};
+    if (nRows < 1 || nCols < 1 || kind < KIND_HUFFMAN || kind > KIND_LSOP_ENC || kind == KIND_DEFLATE || kind == KIND_FLOAT) return GF_ERR_ARG;
+    const size_t n = nTiles, cells = (size_t)nRows * (size_t)nCols, lengthBytes = n * GF_CANON_REC_WORDS * 4;
+    if (kind != KIND_CANON && kind != KIND_LSOP_ENC) {
+        // spill layout of the decode kernel: M32 bytes (6 per cell, rounded to 32), start bitmap, rank bases
+        const size_t cap = roundUp(6 * cells, 32);
+        p.wsStride = roundUp(cap + 2 * ((cap >> 5) + 2) * 4 + 64, 16);
+        p.workspace = gf_huffman_decode_grid(n) * p.wsStride;
+    }
+    if (kind == KIND_HUFFMAN) p.leaf = {0, n * GF_TREE_REC_WORDS * 4}, p.spare = {p.leaf.bytes, 16}, p.roomy = {p.leaf.bytes + 16, n * 4};
+    if (kind == KIND_CANON) p.lengths = {0, lengthBytes}, p.slack = {lengthBytes, 16 + (viaFast ? 4096u : 0u)};
+    if (kind == KIND_LSOP_DEC) p.lsop0 = {0, lengthBytes}, p.lsop1 = {lengthBytes, lengthBytes};      // (both streams' records: k_lsop_head)
+    p.trees = kind == KIND_LSOP_DEC ? 2 * lengthBytes + 16 : p.roomy.at + p.roomy.bytes + p.slack.at + p.slack.bytes;     // (one of the two at most)
+    if (kind == KIND_LSOP_ENC) p.hist = {0, n * gf_lsop_hist_rec_words() * 4}, p.packRecs = p.hist.bytes + 16;
+    if (kind == KIND_LSOP_ENC || kind == KIND_LSOP_DEC) return GF_OK;
+    // the encoders' per-tile records between their kernels: selection records, behind them the statistics (CodecHuffman: what
+    // k_huffman_encode hands to k_huffman_trees) and, at the next multiple of 256 bytes, the byte plane of raw row differences
+    // (GfEncodeArgs::plane, round 6).  One size for both encoders: a context that writes with both never moves the buffer.
+    const size_t huff = (size_t)GF_PACK_REC_WORDS + GF_ENC_STAT_WORDS, canon = gf_canon_pack_rec_words() + gf_canon_stat_words();
+    const size_t planeStride = roundUp(cells, 16), selWords = kind == KIND_CANON ? gf_canon_pack_rec_words() : (size_t)GF_PACK_REC_WORDS;
+    p.sel = {0, n * selWords * 4};
+    p.stats = {p.sel.bytes, n * ((kind == KIND_CANON ? canon : huff) - selWords) * 4};
+    if (!lean && kind != KIND_RAW_M32) p.planeStride = planeStride, p.plane = {roundUp(p.stats.at + p.stats.bytes + 16, 256), n * planeStride};
+    p.packRecs = roundUp(n * std::max(huff, canon) * 4 + 16, 256) + n * planeStride + 256;
+    return GF_OK;
+}
+
+void scratchReserve(int nRows, int nCols, size_t nTiles, uint64_t need[3])
+{
+    need[0] = need[1] = need[2] = 0;
+    gf_scratch_plan p;
+    for (int kind = KIND_HUFFMAN; kind <= KIND_LSOP_ENC; kind++)
+        if (scratchPlan(kind, nRows, nCols, nTiles, 0, 1, p) == GF_OK)                // (viaFast: the larger of the two)
+            need[0] = std::max(need[0], p.workspace), need[1] = std::max(need[1], p.trees), need[2] = std::max(need[2], p.packRecs);
+}
+
 // the launchers' report against the plan: a difference is a bug of this file, not of the data
 static gf_status routeCheck(const char *what, uint32_t ran, uint32_t planned)
 {
@@ -202,27 +243,14 @@ gf_status encodeBatchDev(int kind, gf_context *c, void *stream, int codecIndex, 
     a.predictorMask = predictorMask & GF_PM_ALL;
     a.debug = g_encodeDebug;
     a.phaseLimit = g_encPhaseLimit;
-    a.packRecs = nullptr;
     a.retryFlag = kind == KIND_HUFFMAN ? (uint32_t *)c->flags.p + 4 : nullptr;      // (word 0 belongs to the decoder)
-    {
-        // (CodecHuffman: the selection records, and behind them the statistics k_huffman_encode hands to k_huffman_trees)
-        const size_t need = nTiles * (kind == KIND_CANON ? gf_canon_pack_rec_words() + gf_canon_stat_words() : (size_t)GF_PACK_REC_WORDS + GF_ENC_STAT_WORDS) * 4 + 16;
-        const size_t needAll = encRecordBytes(nRows, nCols, nTiles);
-        if (c->packRecs.bytes < needAll) {                 // not capture-safe: gf_context_reserve sizes this too
-            gf_status s = c->packRecs.ensure(needAll);
-            if (s != GF_OK) return s;
-        }
-        a.packRecs = (uint32_t *)c->packRecs.p;
-        a.lean = lean;
-        a.encStats = a.packRecs + nTiles * (kind == KIND_CANON ? gf_canon_pack_rec_words() : (size_t)GF_PACK_REC_WORDS);
-        // (round 6) the byte plane of raw row differences between phase A and the packer (GfEncodeArgs::plane), behind the records
-        a.plane = nullptr;
-        a.planeStride = 0;
-        if ((kind == KIND_HUFFMAN || kind == KIND_CANON) && !a.lean) {
-            a.planeStride = encPlaneStride(nRows, nCols);
-            a.plane = (uint8_t *)c->packRecs.p + roundUp(need, 256);
-        }
-    }
+    gf_scratch_plan sp;
+    if (gf_status s = scratchPlan(kind, nRows, nCols, nTiles, lean, 0, sp); s != GF_OK || (s = c->packRecs.ensure(sp.packRecs)) != GF_OK) return s;
+    a.packRecs = c->packRecs.at<uint32_t>(sp.sel.at);
+    a.lean = lean;
+    a.encStats = c->packRecs.at<uint32_t>(sp.stats.at);
+    a.planeStride = sp.planeStride;                        // (0 and no plane on the lean path)
+    a.plane = sp.planeStride ? c->packRecs.at<uint8_t>(sp.plane.at) : nullptr;
     const hipStream_t st = streamOf(c, stream);
     uint32_t ran = 0;
     if (kind == KIND_CANON) GF_HIP(gf_launch_canon_encode(a, st, &ran));
@@ -261,12 +289,11 @@ gf_status decodeBatchDev(int kind, gf_context *c, void *stream, int nRows, int n
     const hipStream_t st = streamOf(c, stream);
     uint32_t ran = 0;
     const unsigned grid = gf_huffman_decode_grid(nTiles);
-    const size_t wsStride = kind == KIND_CANON ? 0 : decodeWorkspaceStride(nRows, nCols);
-    if (c->workspace.bytes < (size_t)grid * wsStride) {
-        // not capture-safe: callers that capture graphs call gf_context_reserve first
-        gf_status s = c->workspace.ensure((size_t)grid * wsStride);
-        if (s != GF_OK) return s;
-    }
+    // (neither ensure is capture-safe: callers that capture graphs call gf_context_reserve first)
+    gf_scratch_plan sp;
+    if (gf_status s = scratchPlan(kind, nRows, nCols, nTiles, lean, plan.viaFast, sp);
+        s != GF_OK || (s = c->workspace.ensure(sp.workspace)) != GF_OK || (s = c->trees.ensure(sp.trees)) != GF_OK)
+        return s;
     GfDecodeArgs a{};
     a.blob = dBlob;
     a.blobBytes = blobBytes;
@@ -276,7 +303,7 @@ gf_status decodeBatchDev(int kind, gf_context *c, void *stream, int nRows, int n
     a.values = dValues;
     a.status = dStatus;
     a.workspace = (uint8_t *)c->workspace.p;
-    a.workspaceStride = wsStride;
+    a.workspaceStride = sp.wsStride;
     a.nTiles = nTiles;
     a.nRows = nRows;
     a.nCols = nCols;
@@ -285,17 +312,10 @@ gf_status decodeBatchDev(int kind, gf_context *c, void *stream, int nRows, int n
     a.rawM32 = kind == KIND_RAW_M32 ? 1 : 0;
     a.analysis = analysis;
     a.pairCounts = pairCounts;
-    a.trees = nullptr;
-    a.retryFlag = nullptr;
     a.lean = lean;
     if (kind == KIND_HUFFMAN) {
         // tree pre-pass: one lane per tile walks the serialised tree; the decode kernel starts from the leaf records
-        const size_t need = nTiles * (size_t)GF_TREE_REC_WORDS * 4 + 16 + nTiles * 4;      // (+ the roomy run's tile list)
-        if (c->trees.bytes < need) {                       // not capture-safe either: gf_context_reserve sizes this too
-            gf_status s = c->trees.ensure(need);
-            if (s != GF_OK) return s;
-        }
-        uint32_t *roomyList = (uint32_t *)c->trees.p + nTiles * (size_t)GF_TREE_REC_WORDS + 4;
+        uint32_t *roomyList = c->trees.at<uint32_t>(sp.roomy.at);
         if (!analysis) a.retryFlag = (uint32_t *)c->flags.p;
         // (the fast kernel runs twice where the plan gives it a roomy run: the pre-pass sorts the tiles)
         const uint32_t roomyBytes = plan.ldsM32Roomy, fastBytes = roomyBytes ? plan.fastM32 : 0u;
@@ -310,21 +330,14 @@ gf_status decodeBatchDev(int kind, gf_context *c, void *stream, int nRows, int n
     }
     if (kind == KIND_CANON) {
         // the same for the canonical decoder's code lengths, behind the canonical run of the fast kernel where the plan has one
-        const bool viaFast = plan.viaFast;
-        const uint32_t fastM32 = plan.fastM32;
-        if (viaFast) a.retryFlag = (uint32_t *)c->flags.p;
-        const size_t need = nTiles * (size_t)GF_CANON_REC_WORDS * 4 + 16 + (viaFast ? 4096 : 0);
-        if (c->trees.bytes < need) {
-            gf_status s = c->trees.ensure(need);
-            if (s != GF_OK) return s;
-        }
+        if (plan.viaFast) a.retryFlag = (uint32_t *)c->flags.p;
         GF_HIP(gf_launch_canon_parse_lengths(dBlob, blobBytes, dOffsets, slotStride, dLengths, (uint32_t *)c->trees.p, nTiles, 0,
                                              st, a.retryFlag));
         if (nTiles) ran |= gf_prepass_tiles_per_wave(nTiles) == 1u ? GF_RT_LENGTHS_1 : GF_RT_LENGTHS_64;
         a.trees = (const uint32_t *)c->trees.p;
-        if (viaFast) {
+        if (plan.viaFast) {
             GfDecodeArgs f = a;
-            f.ldsM32Bytes = fastM32;
+            f.ldsM32Bytes = plan.fastM32;
             f.ldsTextBytes = 0;
             f.ldsM32Roomy = 0;
             const int threads = plan.decThreads;
@@ -385,6 +398,18 @@ gf_status gf_internal_route_plan(int kind, int nRows, int nCols, size_t nTiles, 
     return routePlan(kind, nRows, nCols, nTiles, lean, analysis, roomySeen, 1, *out);
 }
 size_t gf_internal_route_plan_bytes(void) { return sizeof(gf_route_plan); }
+// scratchPlan and scratchReserve (need: workspace, trees, packRecs).  No device is needed.
+gf_status gf_internal_scratch_plan(int kind, int nRows, int nCols, size_t nTiles, int lean, int viaFast, gf_scratch_plan *out)
+{
+    return out ? scratchPlan(kind, nRows, nCols, nTiles, lean, viaFast, *out) : GF_ERR_ARG;
+}
+size_t gf_internal_scratch_plan_bytes(void) { return sizeof(gf_scratch_plan); }
+gf_status gf_internal_scratch_reserve(int nRows, int nCols, size_t nTiles, uint64_t need[3])
+{
+    if (!need || nRows < 1 || nCols < 1) return GF_ERR_ARG;
+    scratchReserve(nRows, nCols, nTiles, need);
+    return GF_OK;
+}
 // LDS bytes per workgroup (static + dynamic) that the plan weighs: build 0, 1, 2 = k_huffman_decode with 256, 512, 1024 threads
 // at the given M32 and text capacities; 3, 4 = k_canon_decode with 256, 512 threads at its own sizes for the tile shape
 size_t gf_internal_decode_lds_per_wg(int build, int nRows, int nCols, uint32_t ldsM32, uint32_t ldsText)
