@@ -118,6 +118,12 @@ SIGNATURES = {
     "gf_block_interp_points_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "gf_block_interp_lattice_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gf_block_interp_points": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "gf_palette_create": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "gf_palette_destroy": (None, [_vp]),
+    "gf_block_render_cells_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int32, _vp, C.c_size_t, _vp, _vp]),
+    "gf_block_render_lattice_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "gf_block_render_points_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "gf_block_render_lattice": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "gf_block_downsample_rect": (C.c_int, [_vp, C.c_int, _vp]),
     "gf_block_downsample_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "gf_block_downsample_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),

@@ -122,6 +122,57 @@ class GvrsHipContext:
                                            _ptr(o)), "gf_block_interp_points")
         return res
 
+    # ---- a grid block rendered to ARGB: colour palette and shaded relief (gf_block_render_*) ----
+    @staticmethod
+    def _render_args(lattice, light, out):
+        lat = None
+        if lattice is not None:
+            lat = np.zeros(1, _INTERP_LATTICE)
+            lat["row0"], lat["col0"], lat["row_step"], lat["col_step"], lat["n_rows"], lat["n_cols"] = lattice
+        o = np.zeros(1, _RENDER_OUT)
+        for k, v in out.items():
+            o[k] = 0 if v is None else (v.value if isinstance(v, C.c_void_p) else int(v)) or 0
+        return lat, (None if light is None else np.ascontiguousarray(light, _RENDER_LIGHT).reshape(1)), o
+
+    def render_cells_dev(self, palette, elem_type, d_cells, n_cells, d_argb, d_shade=None, fill_i=0, unlimited=False, stream=None):
+        """gf_block_render_cells_dev on device pointers: n_cells cells of the element ("int", "short", "float", "icf", GF_ELEM_*, or
+        "z" / RENDER_Z: doubles) -> d_argb [n_cells] int32; d_shade: one double per cell (the WithShade lookups).  Enqueues only."""
+        et = RENDER_Z if elem_type == "z" else ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
+        check(lib().gf_block_render_cells_dev(self._h, stream, palette.handle, RENDER_UNLIMITED if unlimited else 0, et, int(fill_i), d_cells,
+                                              int(n_cells), d_shade, d_argb), "gf_block_render_cells_dev")
+
+    def render_lattice_dev(self, spec, d_block, lattice, palette, out, light=None, unlimited=False, stream=None):
+        """gf_block_render_lattice_dev: spec and lattice as interp_lattice_dev takes them, light from render_light() (None: the
+        value alone, no shade), out a dict of device pointers under the names argb (int32), shade (double), status (int32), each
+        one item per pixel; argb or shade must be there.  Enqueues only."""
+        lat, li, o = self._render_args(lattice, light, out)
+        check(lib().gf_block_render_lattice_dev(self._h, stream, _ptr(spec), d_block, _ptr(lat), palette.handle, None if li is None else _ptr(li),
+                                                RENDER_UNLIMITED if unlimited else 0, _ptr(o)), "gf_block_render_lattice_dev")
+
+    def render_points_dev(self, spec, d_block, palette, out, lattice=None, n_points=0, d_rows=None, d_cols=None, d_col_spacing=None,
+                          light=None, unlimited=False, stream=None):
+        """gf_block_render_points_dev: with lattice, a lattice whose column spacing differs per row (d_col_spacing: one per lattice
+        row); without, n_points points d_rows, d_cols (d_col_spacing: one per point).  Enqueues only."""
+        lat, li, o = self._render_args(lattice, light, out)
+        check(lib().gf_block_render_points_dev(self._h, stream, _ptr(spec), d_block, None if lat is None else _ptr(lat), int(n_points), d_rows,
+                                               d_cols, d_col_spacing, palette.handle, None if li is None else _ptr(li),
+                                               RENDER_UNLIMITED if unlimited else 0, _ptr(o)), "gf_block_render_points_dev")
+
+    def render_lattice(self, spec, block, lattice, palette, light=None, unlimited=False):
+        """gf_block_render_lattice, the host-memory form (staged by the library): returns a dict argb [n_rows, n_cols] int32, status
+        the same, and shade (float64) with a light."""
+        dt = {0: np.int32, 1: np.int16, 2: np.float32, 3: np.float32}[int(spec["elem_type"][0])]
+        block = np.ascontiguousarray(block, dt)
+        assert block.size == int(spec["block"][0][2]) * int(spec["block"][0][3])
+        shape = (int(lattice[4]), int(lattice[5]))
+        res = {"argb": np.zeros(shape, np.int32), "status": np.zeros(shape, np.int32)}
+        if light is not None:
+            res["shade"] = np.zeros(shape, np.float64)
+        lat, li, o = self._render_args(lattice, light, {k: a.ctypes.data for k, a in res.items()})
+        check(lib().gf_block_render_lattice(self._h, _ptr(spec), _ptr(block), _ptr(lat), palette.handle, None if li is None else _ptr(li),
+                                            RENDER_UNLIMITED if unlimited else 0, _ptr(o)), "gf_block_render_lattice")
+        return res
+
     # ---- a grid block downsampled: the box average by an integer factor (gf_block_downsample_*) ----
     @staticmethod
     def downsample_rect(block, factor):
@@ -205,6 +256,73 @@ def interp_spec(n_rows_grid, n_cols_grid, block=None, elem_type="float", fill_i=
     s["row_fringe0"], s["row_fringe1"] = (-0.5, n_rows_grid - 0.5) if row_fringe is None else row_fringe
     s["col_fringe0"], s["col_fringe1"] = (-0.5, n_cols_grid - 0.5) if col_fringe is None else col_fringe
     return s
+
+
+PALETTE_RGB, PALETTE_HSV, PALETTE_MAX_RECORDS, RENDER_UNLIMITED, RENDER_Z = 0, 1, 256, 1, 4                                     # GF_PALETTE_*, GF_RENDER_*
+_PALETTE_RECORD = np.dtype([("range0", np.float64), ("range1", np.float64), ("model", np.int32), ("rgb0", np.int32, 3), ("rgb1", np.int32, 3),
+                            ("reserved", np.int32), ("hsv0", np.float64, 3), ("hsv1", np.float64, 3)])               # gf_palette_record
+_PALETTE_SPEC = np.dtype([("records", np.uint64), ("n_records", np.int32), ("argb_for_null", np.uint32), ("normalized", np.int32),
+                          ("hinge", np.int32), ("range_min", np.float64), ("range_max", np.float64), ("hinge_value", np.float64)])  # gf_palette_spec
+_RENDER_LIGHT = np.dtype([("x_gain", np.float64), ("y_gain", np.float64), ("sun", np.float64, 3), ("ambient", np.float64)])  # gf_render_light
+_RENDER_OUT = np.dtype([(k, np.uint64) for k in ("argb", "shade", "status")])                                       # gf_render_out
+
+
+def palette_records(records):
+    """A gf_palette_record array from tuples (range0, range1, "rgb", (r, g, b), (r, g, b)) or (range0, range1, "hsv", (h, s, v),
+    (h, s, v)); an array of that dtype passes through."""
+    if isinstance(records, np.ndarray) and records.dtype == _PALETTE_RECORD:
+        return np.ascontiguousarray(records)
+    out = np.zeros(len(records), _PALETTE_RECORD)
+    for o, (range0, range1, model, c0, c1) in zip(out, records):
+        o["range0"], o["range1"] = range0, range1
+        if model in ("rgb", PALETTE_RGB):
+            o["model"], o["rgb0"], o["rgb1"] = PALETTE_RGB, c0, c1
+        else:
+            o["model"], o["hsv0"], o["hsv1"] = (PALETTE_HSV if model == "hsv" else model), c0, c1
+    return out
+
+
+def palette_spec(records, argb_for_null=0, normalized=False, range_min=0.0, range_max=0.0, hinge=False, hinge_value=0.0):
+    """(gf_palette_spec, the record array it points to)"""
+    recs = palette_records(records)
+    s = np.zeros(1, _PALETTE_SPEC)
+    s["records"], s["n_records"], s["argb_for_null"] = recs.ctypes.data, len(recs), int(argb_for_null) & 0xffffffff
+    s["normalized"], s["hinge"], s["range_min"], s["range_max"], s["hinge_value"] = bool(normalized), bool(hinge), range_min, range_max, hinge_value
+    return s, recs
+
+
+def render_light(x_gain, y_gain, sun, ambient):
+    """A gf_render_light: the gains on zx and zy (ExtractData: -steepen, +steepen; DemoCOG: both -steepen), the unit vector
+    towards the sun and the ambient level."""
+    li = np.zeros(1, _RENDER_LIGHT)
+    li["x_gain"], li["y_gain"], li["sun"], li["ambient"] = x_gain, y_gain, sun, ambient
+    return li
+
+
+class Palette:
+    """A colour palette on a context's device (gf_palette_create): what the reference's ColorPaletteTable holds.  records as
+    palette_records() takes them; the other arguments are the table constructor's."""
+
+    def __init__(self, ctx, records, argb_for_null=0, normalized=False, range_min=0.0, range_max=0.0, hinge=False, hinge_value=0.0):
+        self._h = C.c_void_p()
+        spec, recs = palette_spec(records, argb_for_null, normalized, range_min, range_max, hinge, hinge_value)
+        check(lib().gf_palette_create(ctx.handle, _ptr(spec), C.byref(self._h)), "gf_palette_create")
+        self.ctx, self.n_records = ctx, len(recs)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            lib().gf_palette_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # struct gf_codec_stats (include/gvrs_hip_codec.h) = the sums of compress/CodecStats.java

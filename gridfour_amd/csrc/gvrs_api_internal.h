@@ -151,6 +151,7 @@ struct gf_context {
     DevBuf dEncSlots{this}, dEncMeta{this}, dEncWide{this};       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots,
                                                 // their lengths / statuses and the records' layout, SHORT cells widened for the codecs
     DevBuf dInterp{this};                       // interpolation, host form (gvrs_api_interp.hip): block, coordinates, spacings and outputs
+    DevBuf dRender{this};                       // rendering, host form (gvrs_api_render.hip): block and outputs
     DevBuf dDsBlocks{this}, dDsStage{this};     // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks; the host
                                                 // forms' blocks and coarse blocks
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
@@ -304,6 +305,8 @@ gf_status blockReadArgs(const gf_context *c, const int *codecs, int nCodecs, con
 gf_status blockReadDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
                        const uint32_t *fill, size_t n, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets, int verifyChecksum,
                        void *const *dBlocks, int32_t *dStatus);
+// gvrs_api_interp.hip: what the host can check of an interpolation spec (fills g)
+gf_status interpSpecArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, GfInterpGeom &g);
 // gvrs_api_records.hip
 size_t elemStandardSize(int elemType, size_t cells);
 // gvrs_api_deflate.hip

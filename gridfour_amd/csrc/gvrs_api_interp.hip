@@ -7,12 +7,10 @@
 
 #include "gvrs_api_internal.h"
 
-namespace {
-
-// what the host can check of a spec and the outputs; fills g
-gf_status interpArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, const gf_interp_out *out, GfInterpGeom &g)
+// what the host can check of a spec; fills g (the render calls of gvrs_api_render.hip check theirs with it too)
+gf_status interpSpecArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, GfInterpGeom &g)
 {
-    if (!c || !spec || !block || !out || !out->z) return GF_ERR_ARG;
+    if (!c || !spec || !block) return GF_ERR_ARG;
     if (spec->n_rows_grid < 4 || spec->n_cols_grid < 4) return GF_ERR_ARG;                         // (GvrsInterpolatorBSpline.java:113-116)
     const gf_rect &b = spec->block;
     if (b.row0 < 0 || b.col0 < 0 || b.n_rows < 4 || b.n_cols < 4) return GF_ERR_ARG;
@@ -21,12 +19,23 @@ gf_status interpArgs(const gf_context *c, const gf_interp_spec *spec, const void
     if (spec->wrap < 0 || spec->wrap > 2 || spec->target < GF_INTERP_VALUE || spec->target > GF_INTERP_SECOND) return GF_ERR_ARG;
     if (spec->elem_type == GF_ELEM_SHORT && (spec->fill_i < -32768 || spec->fill_i > 32767)) return GF_ERR_ARG;
     if (spec->target >= GF_INTERP_FIRST && (spec->row_spacing == 0 || (spec->col_spacing == 0 && !perPointSpacing))) return GF_ERR_ARG;
-    if (spec->target == GF_INTERP_VALUE && out->normal) return GF_ERR_ARG;
     g.nRowsGrid = spec->n_rows_grid, g.nColsGrid = spec->n_cols_grid;
     g.bRow0 = b.row0, g.bCol0 = b.col0, g.bRows = b.n_rows, g.bCols = b.n_cols;
     g.elemType = spec->elem_type, g.fillI = spec->fill_i, g.wrap = spec->wrap, g.target = spec->target;
     g.rowSpacing = spec->row_spacing, g.colSpacing = spec->col_spacing;
     g.rowFringe0 = spec->row_fringe0, g.rowFringe1 = spec->row_fringe1, g.colFringe0 = spec->col_fringe0, g.colFringe1 = spec->col_fringe1;
+    return GF_OK;
+}
+
+namespace {
+
+// ... and of the outputs
+gf_status interpArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, const gf_interp_out *out, GfInterpGeom &g)
+{
+    if (!c || !spec || !block || !out || !out->z) return GF_ERR_ARG;
+    const gf_status s = interpSpecArgs(c, spec, block, perPointSpacing, g);
+    if (s != GF_OK) return s;
+    if (spec->target == GF_INTERP_VALUE && out->normal) return GF_ERR_ARG;
     return GF_OK;
 }
 

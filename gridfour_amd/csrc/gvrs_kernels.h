@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "gvrs_interp_common.h"
+#include "gvrs_render_common.h"
 #include "gvrs_downsample_common.h"
 
 // per-tile status values written by the kernels; identical to gf_status in
@@ -633,6 +634,39 @@ struct GfInterpArgs {
     int32_t *status;
 };
 hipError_t gf_launch_interp(const GfInterpArgs &a, hipStream_t stream);
+
+// A grid block rendered to ARGB words (gvrs_render.hip; driven by gvrs_api_render.hip).  The palette is a packed table in device
+// memory (gvrs_render_common.h): head travels by value; table is what lies behind it, keys[n] | recs[n] as 10 n doubles, staged
+// in LDS by every workgroup (80 bytes a record).  unlimited: the UnlimitedRange forms of the lookup.
+struct GfRenderPal {
+    GfPalHead head;
+    const double *table;
+    int32_t unlimited;
+};
+// cells form: nCells cells of a block (int32 / int16 / float32 as elemType says; GF_RENDER_ELEM_Z: doubles; aligned to the item) -> argb; shade (may be null):
+// one double per cell, the WithShade forms.  Every argb item is written exactly once.
+struct GfRenderCellsArgs {
+    GfRenderPal pal;
+    int32_t elemType, fillI;
+    const void *cells;
+    const double *shade;
+    uint32_t *argb;
+    size_t nCells;
+};
+hipError_t gf_launch_render_cells(const GfRenderCellsArgs &a, hipStream_t stream);
+// interpolating forms: ip is what gf_launch_interp takes (its output pointers unused; g.target is GF_IP_FIRST with a light,
+// GF_IP_VALUE without); argb, shade and status may each be null.  A lattice with one column spacing goes to k_render_lattice,
+// everything else to k_render_points.
+struct GfRenderArgs {
+    GfInterpArgs ip;
+    GfRenderPal pal;
+    GfRenderLight light;
+    int32_t lit;                                    // != 0: light holds the illumination model; else the lookup without shade
+    uint32_t *argb;
+    double *shade;
+    int32_t *status;
+};
+hipError_t gf_launch_render(const GfRenderArgs &a, hipStream_t stream);
 
 // A grid block in device memory averaged down by an integer factor (gvrs_downsample.hip; driven by gvrs_api_downsample.hip): block
 // and out hold int32 / int16 / float32 cells as g.elemType says, out g.outRows x g.outCols of them, each written exactly once.

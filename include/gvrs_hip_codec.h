@@ -751,6 +751,101 @@ gf_status gf_block_interp_lattice_dev(gf_context *ctx, void *stream, const gf_in
 gf_status gf_block_interp_points(gf_context *ctx, const gf_interp_spec *spec, const void *block, size_t n_points, const double *rows,
                                  const double *cols, const double *col_spacing, const gf_interp_out *out);
 
+/* ---- a grid block RENDERED: one ARGB word per cell or per pixel, through a colour palette and a shaded relief ---------------------
+ * (imaging/palette/ColorPaletteTable.java:162-253 the constructor, :395-456 getArgb, :481-541 getArgbWithShade, :567-598
+ * getArgbUnlimitedRange[WithShade]; ColorPaletteRecord.java:176-182 compareTo; ColorPaletteRecordRGB.java:72-121;
+ * ColorPaletteRecordHSV.java:95-194; the illumination model of demo/src/main/java/org/gridfour/demo/globalDEM/ExtractData.java:
+ * 394-419 and demo/geoTiff/DemoCOG.java:405-441)
+ * What the reference's demos do per pixel after interpolating -- a shade from the surface's first derivatives, a colour from a
+ * palette, both in one int 0xAARRGGBB -- over a block that lies in device memory, BIT FOR BIT: doubles in the reference's operation
+ * order, no fused multiply-add, Java's (int) conversions, java.util.Arrays.binarySearch(double[], double) as the JDK walks it (with
+ * equal keys the probe sequence decides, -0.0 sorts below a key 0.0, NaN above everything), 32-bit shifts and ORs for the word (a
+ * shade outside 0..1 gives the bits Java gives), java.awt.Color.HSBtoRGB in float32 for HSV records.
+ *   PALETTE.  gf_palette_create does on the host what the table's constructor does: it sorts the records by (range0, range1) in
+ *   Double.compare's order (-0.0 < 0.0), stably; keys[i] = range0 of record i; hingeIndex = the first record whose range0 ==
+ *   hinge_value; per RGB record deltaR/G/B, per HSV record deltaS, deltaV, deltaH (|h1 - h0| < 1.0e-6 -> 0, else brought into
+ *   (-180, 180], 0 -> 360) and wrapAround.  It uploads one packed table, allocates and synchronises; rendering does neither.  The
+ *   palette belongs to the context's device, is read-only afterwards and may serve any number of calls; gf_palette_destroy frees
+ *   it (NULL is allowed).  normalized / range_min / range_max / hinge / hinge_value are the second constructor's arguments
+ *   (normalized == 0 and hinge == 0: the first constructor); argb_for_null is Color.getRGB() of colorForNull, 0 without one.
+ *   The library does not parse palette files.
+ *   DEVIATION: normalized && hinge with the hinge on the FIRST record is refused: the reference's constructor accepts it and then
+ *   indexes records[-1] on the first z below the hinge (:409).
+ *   gf_palette_create: GF_ERR_ARG, before the context or a device is looked at: a NULL spec, records, out or ctx; n_records < 1;
+ *   a record with !(range0 <= range1) (NaN included); a model other than GF_PALETTE_RGB / GF_PALETTE_HSV; an RGB channel outside
+ *   0..255; hinge with a hinge_value that equals no range0 (the constructor throws); the deviation above.  GF_ERR_UNSUPPORTED:
+ *   more than GF_PALETTE_MAX_RECORDS records.
+ *   LOOKUP.  z -> the normalised / hinge remapping as written (:405-420), the binary search on the keys, index == -1 -> the null
+ *   colour, else the record found or the one before the insertion point when its range1 >= z, else the null colour; the record
+ *   interpolates between its two colours (t clamped by the two comparisons; a NaN t, range0 == range1, yields channel 0).  NaN and
+ *   +-infinity give the null colour.  flags & GF_RENDER_UNLIMITED: getArgbUnlimitedRange (z clamped to records[0].range0 ..
+ *   records[n - 1].range1 first); with a shade the WithShade forms.
+ *   gf_block_render_cells_dev: n_cells cells (int32 / int16 / float32 as elem_type says, aligned to the item; INT and SHORT: a cell
+ *   equal to fill_i reads as NaN, any other as (float) cell, FLOAT and ICF as they are, widened to double: the interpolator's
+ *   samples) -> d_argb[n_cells] (4-byte aligned).  d_shade (may be NULL, 8-byte aligned): one double per cell.  elem_type
+ *   GF_RENDER_Z, this call alone: d_cells holds doubles, looked up as they are -- z as gf_block_interp_*_dev delivers it, with a
+ *   shade array of the caller's: the unfused form of the lattice call below, the same words.
+ *   gf_block_render_lattice_dev: spec, d_block and lattice as gf_block_interp_lattice_dev takes them; per pixel the sixteen samples
+ *   and the interpolator's own sums (the same functions: z, zx, zy are the bits gf_block_interp_lattice_dev delivers), then
+ *     nx = zx * x_gain; ny = zy * y_gain; s = sqrt(nx * nx + ny * ny + 1); nx /= s; ny /= s; nz = 1 / s;
+ *     dot = nx * sun[0] + ny * sun[1] + nz * sun[2]; shade = ambient; if (dot > 0) shade = dot * (1 - ambient) + ambient;
+ *   and the lookup of z with that shade.  ExtractData: x_gain = -steepen, y_gain = +steepen; DemoCOG: both -steepen.  The sun
+ *   vector comes from the caller (libm's sine and cosine do not reproduce bit for bit).  light == NULL: no shade, the value alone
+ *   is evaluated and looked up without shade.  spec->target is checked and otherwise ignored: first derivatives are evaluated
+ *   with a light, the value alone without.  out->argb [n], out->shade [n] (the shade, needs a light) and out->status [n] (the
+ *   interpolator's per-point status) may each be NULL, but not both argb and shade.  A pixel whose status is not GF_OK has NaN z,
+ *   zx and zy by the interpolator's rule and goes the same way: the null colour, the ambient shade.
+ *   gf_block_render_points_dev: the lane-per-point form.  lattice != NULL: a lattice whose column spacing differs per ROW
+ *   (d_col_spacing: n_rows entries; ExtractData's xScale = yScale * cos(latitude)); d_rows, d_cols must be NULL.  lattice == NULL:
+ *   n_points free points d_rows, d_cols, d_col_spacing per point.  d_col_spacing == NULL: spec->col_spacing.  A zero spacing gives
+ *   the pixel GF_ERR_ARG, as there.
+ *   gf_block_render_lattice: block and outputs in host memory, staged through a buffer of the context; it synchronises: a
+ *   convenience, not a rate.
+ * The device forms ONLY ENQUEUE on `stream` (NULL: the context's), allocate nothing, never synchronise and are safe for hipGraph
+ * capture.  Every output item is written exactly once and nothing else is written.
+ * GF_ERR_ARG, before the context or a device is looked at: what gf_block_interp_*_dev reject of ctx, spec, block, lattice and
+ * coordinate arrays (with a light: the zero-spacing rules of target GF_INTERP_FIRST); a NULL palette; a NULL out, or out->argb and
+ * out->shade both NULL; out->shade without a light; flags other than GF_RENDER_UNLIMITED; both a lattice and coordinate arrays;
+ * cells form: an elem_type outside GF_ELEM_INT .. GF_RENDER_Z, a SHORT fill_i outside int16, NULL d_cells or d_argb with n_cells > 0, a misaligned pointer.
+ * GF_ERR_UNSUPPORTED: a lattice of 2^63 or more points, more than 2^48 cells.  n_points == 0, n_cells == 0: GF_OK.  A palette of
+ * another device than the context's: GF_ERR_ARG.                                                                               */
+#define GF_PALETTE_RGB 0
+#define GF_PALETTE_HSV 1
+#define GF_PALETTE_MAX_RECORDS 256
+#define GF_RENDER_UNLIMITED 1
+#define GF_RENDER_Z 4                   /* gf_block_render_cells_dev: elem_type of double cells                        */
+typedef struct gf_palette gf_palette;
+typedef struct gf_palette_record {
+    double range0, range1;              /* range0 <= range1                                                            */
+    int32_t model;                      /* GF_PALETTE_RGB, GF_PALETTE_HSV                                              */
+    int32_t rgb0[3], rgb1[3];           /* RGB: red, green, blue at range0 / range1, each 0..255                       */
+    int32_t reserved;
+    double hsv0[3], hsv1[3];            /* HSV: hue (degrees), saturation, value at range0 / range1                    */
+} gf_palette_record;
+typedef struct gf_palette_spec {
+    const gf_palette_record *records;
+    int32_t n_records;                  /* 1 .. GF_PALETTE_MAX_RECORDS                                                 */
+    uint32_t argb_for_null;
+    int32_t normalized, hinge;          /* booleans                                                                    */
+    double range_min, range_max;        /* normalizedRangeMin / Max (normalized)                                       */
+    double hinge_value;                 /* (hinge) the range0 of a record                                              */
+} gf_palette_spec;
+typedef struct gf_render_light { double x_gain, y_gain, sun[3], ambient; } gf_render_light;
+typedef struct gf_render_out { int32_t *argb; double *shade; int32_t *status; } gf_render_out;
+gf_status gf_palette_create(gf_context *ctx, const gf_palette_spec *spec, gf_palette **out);
+void gf_palette_destroy(gf_palette *palette);
+gf_status gf_block_render_cells_dev(gf_context *ctx, void *stream, const gf_palette *palette, int flags, int elem_type, int32_t fill_i,
+                                    const void *d_cells, size_t n_cells, const double *d_shade, int32_t *d_argb);
+gf_status gf_block_render_lattice_dev(gf_context *ctx, void *stream, const gf_interp_spec *spec, const void *d_block,
+                                      const gf_interp_lattice *lattice, const gf_palette *palette, const gf_render_light *light,
+                                      int flags, const gf_render_out *out);
+gf_status gf_block_render_points_dev(gf_context *ctx, void *stream, const gf_interp_spec *spec, const void *d_block,
+                                     const gf_interp_lattice *lattice, size_t n_points, const double *d_rows, const double *d_cols,
+                                     const double *d_col_spacing, const gf_palette *palette, const gf_render_light *light, int flags,
+                                     const gf_render_out *out);
+gf_status gf_block_render_lattice(gf_context *ctx, const gf_interp_spec *spec, const void *block, const gf_interp_lattice *lattice,
+                                  const gf_palette *palette, const gf_render_light *light, int flags, const gf_render_out *out);
+
 /* ---- a grid block DOWNSAMPLED: the box average by an integer factor, in device memory -------------------------------------------
  * (demo/src/main/java/org/gridfour/demo/globalDEM/ExampleDownsample.java:164-210 the loop, :228-239 makeSpec's grid size)
  * The coarser copy of a raster that the reference's ExampleDownsample writes -- an overview or pyramid level -- computed over a block
