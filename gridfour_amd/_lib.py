@@ -130,6 +130,12 @@ SIGNATURES = {
     "gf_block_read_downsampled_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_size_t, _vp, C.c_size_t, _vp,
                                                       C.c_int, _vp, _vp]),
     "gf_block_read_downsampled_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_size_t, _vp, _vp, C.c_int, _vp, _vp]),
+    "gf_tab_dense_plan_of": (C.c_int, [_vp, _vp]),
+    "gf_block_tabulate_dense_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int32, C.c_int, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "gf_block_tabulate_dense": (C.c_int, [_vp, C.c_int, C.c_int32, C.c_int, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "gf_block_tabulate_symbols_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
+    "gf_block_tabulate_symbols": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
+    "gf_tab_entropy_counts": (C.c_int, [_vp, C.c_size_t, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
     "gf_compact_dev":(C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
     "gf_float_planes_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "gf_float_planes_encode_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp, C.c_size_t]),

@@ -219,6 +219,72 @@ class GvrsHipContext:
                                               (C.c_void_p * ne)(*[o.ctypes.data for o in out])), "gf_block_downsample_elems")
         return out
 
+    # ---- a grid block tabulated: value counts, range and entropy (gf_block_tabulate_*, gf_tab_*) ----
+    @staticmethod
+    def tab_dense_plan(def_min, def_max, scale):
+        """gf_tab_dense_plan_of: InputDataStatCollector's constructor -> dict n_counter, base, n_bins, scale_used"""
+        plan = np.zeros(1, _TAB_DENSE_PLAN)
+        check(lib().gf_tab_dense_plan_of(_ptr(_tab_dense_spec(def_min, def_max, scale)), _ptr(plan)), "gf_tab_dense_plan_of")
+        return {k: plan[k][0].item() for k in plan.dtype.names}
+
+    def tabulate_dense_dev(self, elem_type, d_block, n_cells, def_min, def_max, scale, d_counter, d_summary, fill_i=0, skip_fill=False,
+                           accumulate=False, first_cell=0, stream=None):
+        """gf_block_tabulate_dense_dev on device pointers: n_cells cells of the element ("int", "short", "float" or GF_ELEM_*) ->
+        d_counter [tab_dense_plan(...)["n_bins"]] int32 and d_summary, one gf_tab_summary (TAB_SUMMARY).  Enqueues only."""
+        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
+        flags = (TAB_ACCUMULATE if accumulate else 0) | (TAB_SKIP_FILL if skip_fill else 0)
+        check(lib().gf_block_tabulate_dense_dev(self._h, stream, et, int(fill_i), flags, d_block, int(n_cells), int(first_cell),
+                                                _ptr(_tab_dense_spec(def_min, def_max, scale)), d_counter, d_summary), "gf_block_tabulate_dense_dev")
+
+    def tabulate_dense(self, elem_type, block, def_min, def_max, scale, fill_i=0, skip_fill=False, first_cell=0, into=None):
+        """gf_block_tabulate_dense, the host-memory form (staged by the library): returns (counter [n_bins] int32, summary dict).
+        into = (counter, summary) of an earlier call: accumulate onto them (a raster in strips, first_cell the strip's first cell)."""
+        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
+        block = np.ascontiguousarray(block, {0: np.int32, 1: np.int16}.get(et, np.float32)).ravel()
+        flags = (TAB_ACCUMULATE if into is not None else 0) | (TAB_SKIP_FILL if skip_fill else 0)
+        summary = np.zeros(1, TAB_SUMMARY)
+        if into is not None:
+            counter = np.ascontiguousarray(into[0], np.int32).copy()
+            for k in TAB_SUMMARY.names:
+                summary[k] = into[1][k]
+            assert counter.size == self.tab_dense_plan(def_min, def_max, scale)["n_bins"]
+        else:
+            counter = np.zeros(self.tab_dense_plan(def_min, def_max, scale)["n_bins"], np.int32)
+        check(lib().gf_block_tabulate_dense(self._h, et, int(fill_i), flags, _ptr(block), block.size, int(first_cell),
+                                            _ptr(_tab_dense_spec(def_min, def_max, scale)), _ptr(counter), _ptr(summary)), "gf_block_tabulate_dense")
+        return counter, {k: summary[k][0].item() for k in TAB_SUMMARY.names}
+
+    def tabulate_symbols_dev(self, elem_type, d_block, n_cells, d_symbols, d_counts, table_cap, d_summary, stream=None):
+        """gf_block_tabulate_symbols_dev on device pointers: the distinct 32-bit symbols of n_cells cells in ascending unsigned order
+        -> d_symbols [table_cap] uint32, d_counts [table_cap] int32 (both None with table_cap 0) and d_summary, one gf_tab_symbols
+        (TAB_SYMBOLS).  Enqueues only."""
+        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
+        check(lib().gf_block_tabulate_symbols_dev(self._h, stream, et, d_block, int(n_cells), d_symbols, d_counts, int(table_cap), d_summary),
+              "gf_block_tabulate_symbols_dev")
+
+    def tabulate_symbols(self, elem_type, block, table_cap=None):
+        """gf_block_tabulate_symbols, the host-memory form: returns (symbols uint32, counts int32, summary dict); table_cap None:
+        room for every cell.  A table that does not hold every symbol comes back with its first table_cap entries (summary
+        ["n_written"] of summary["n_symbols"])."""
+        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
+        block = np.ascontiguousarray(block, {0: np.int32, 1: np.int16}.get(et, np.float32)).ravel()
+        cap = block.size if table_cap is None else int(table_cap)
+        symbols, counts, summary = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int32), np.zeros(1, TAB_SYMBOLS)
+        st = lib().gf_block_tabulate_symbols(self._h, et, _ptr(block), block.size, _ptr(symbols) if cap else None, _ptr(counts) if cap else None,
+                                             cap, _ptr(summary))
+        if st != _lib.ERR_CAPACITY:
+            check(st, "gf_block_tabulate_symbols")
+        n = int(summary["n_written"][0])
+        return symbols[:n], counts[:n], {k: summary[k][0].item() for k in TAB_SYMBOLS.names}
+
+    @staticmethod
+    def tab_entropy(counts, n_samples, kahan=True):
+        """gf_tab_entropy_counts: bits per sample of a table of counts in the order given; kahan: EntropyTabulator's sum, else
+        InputDataStatCollector.getEntropy's"""
+        counts, e = np.ascontiguousarray(counts, np.int32).ravel(), C.c_double()
+        check(lib().gf_tab_entropy_counts(_ptr(counts), counts.size, int(n_samples), int(bool(kahan)), C.byref(e)), "gf_tab_entropy_counts")
+        return e.value
+
     def close(self):
         if self._h:
             lib().gf_context_destroy(self._h)
@@ -229,6 +295,21 @@ class GvrsHipContext:
             self.close()
         except Exception:
             pass
+
+
+TAB_ACCUMULATE, TAB_SKIP_FILL = 1, 2                                      # GF_TAB_*
+_TAB_DENSE = np.dtype([("def_min", np.int32), ("def_max", np.int32), ("scale", np.float64)])                          # gf_tab_dense
+_TAB_DENSE_PLAN = np.dtype([("n_counter", np.int32), ("base", np.int32), ("n_bins", np.int64), ("scale_used", np.float64)])   # gf_tab_dense_plan
+TAB_SUMMARY = np.dtype([("n_cells", np.int64), ("n_skipped", np.int64), ("n_samples", np.int64), ("sum_samples", np.int64), ("sum_i", np.int64),
+                        ("min", np.float64), ("max", np.float64), ("min_at", np.int64), ("max_at", np.int64)])       # gf_tab_summary
+TAB_SYMBOLS = np.dtype([("n_samples", np.int64), ("n_symbols", np.int64), ("n_unique", np.int64), ("n_repeated", np.int64),
+                        ("n_written", np.int64), ("max_count", np.int32), ("reserved", np.int32)])                   # gf_tab_symbols
+
+
+def _tab_dense_spec(def_min, def_max, scale):
+    s = np.zeros(1, _TAB_DENSE)
+    s["def_min"], s["def_max"], s["scale"] = def_min, def_max, scale
+    return s
 
 
 INTERP_VALUE, INTERP_FIRST, INTERP_SECOND = 0, 1, 2                      # GF_INTERP_*

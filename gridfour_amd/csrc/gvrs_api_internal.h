@@ -154,6 +154,8 @@ struct gf_context {
     DevBuf dRender{this};                       // rendering, host form (gvrs_api_render.hip): block and outputs
     DevBuf dDsBlocks{this}, dDsStage{this};     // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks; the host
                                                 // forms' blocks and coarse blocks
+    DevBuf dTabPartials{this}, dTabSort{this}, dTabStage{this};   // tabulation (gvrs_api_tabulate.hip): k_tabulate_dense's partials (fixed size); the
+                                                // symbol form's keys, histograms and runs; the host forms' block, counters, tables and summary
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
     // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
     // scratch buffers, staging slots and recorded graphs are one set.  Recursive: entry points call each other.

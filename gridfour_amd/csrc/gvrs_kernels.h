@@ -10,6 +10,7 @@
 #include "gvrs_interp_common.h"
 #include "gvrs_render_common.h"
 #include "gvrs_downsample_common.h"
+#include "gvrs_tabulate_common.h"
 
 // per-tile status values written by the kernels; identical to gf_status in
 // include/gvrs_hip_codec.h
@@ -682,3 +683,40 @@ struct GfDownsampleArgs {
 };
 int gf_downsample_path(const GfDownsampleArgs &a);
 hipError_t gf_launch_downsample(const GfDownsampleArgs &a, int path, hipStream_t stream);
+
+// A grid block in device memory tabulated (gvrs_tabulate.hip; driven by gvrs_api_tabulate.hip; the arithmetic: gvrs_tabulate_common.h).
+// Dense form: counter[0 .. g.nCounter] are ADDED to (the caller zeroes them unless it accumulates), partials is room for
+// GF_TAB_MAX_GROUPS entries, and k_tabulate_finish writes *summary whole (accumulate: merged with what it held).
+struct GfTabPartial {          // what a workgroup of k_tabulate_dense leaves for k_tabulate_finish (64 bytes)
+    uint64_t nSkipped, nSamples, sumSamples, sumI;
+    double mn, mx;             // exact for every element type
+    int64_t mnAt, mxAt;        // -1: none
+};
+struct GfTabDenseArgs {
+    GfTabDenseGeom g;
+    const void *block;         // int32 / int16 / float32 cells as g.elemType says, 4-byte aligned
+    int32_t *counter;
+    GfTabPartial *partials;
+    GfTabSummary *summary;
+    int accumulate;
+};
+hipError_t gf_launch_tabulate_dense(const GfTabDenseArgs &a, hipStream_t stream);
+// Symbol form: the n >= 1 cells as 32-bit symbols, sorted (unsigned) and run-length counted.  keysA: n + 1 words, keysB: n words,
+// hist / sums / heads: gf_tab_sort_plan(n)'s histWords / sumWords / nRunBlocks words, nSym: one word; symbols / counts: cap
+// entries each (null with cap == 0); *summary is written whole.
+struct GfTabSortPlan {
+    uint32_t share, nWg;       // keys of a sort workgroup, sort workgroups
+    size_t histWords, sumWords, nRunBlocks;
+};
+GfTabSortPlan gf_tab_sort_plan(uint32_t n);
+struct GfTabSymbolsArgs {
+    int32_t elemType;
+    const void *block;
+    uint32_t n;
+    uint32_t *keysA, *keysB, *hist, *sums, *heads, *nSym;
+    uint32_t *symbols;
+    int32_t *counts;
+    size_t cap;
+    GfTabSymbols *summary;
+};
+hipError_t gf_launch_tab_symbols(const GfTabSymbolsArgs &a, hipStream_t stream);

@@ -897,6 +897,78 @@ gf_status gf_block_read_downsampled_elems(gf_context *ctx, const int *codecs, in
                                           const gf_grid_spec *grid, const gf_rect *rect, int factor, size_t n_records, const uint8_t *blob,
                                           const uint64_t *offsets, int verify_checksum, void *const *out, int32_t *status);
 
+/* ---- a grid block TABULATED: value counts, range and entropy, in device memory ----------------------------------------------------
+ * (demo/src/main/java/org/gridfour/demo/globalDEM/InputDataStatCollector.java:55-108, PackageData.java:445-448, :465-466, :504-533,
+ * ExtractData.java:306-317; demo/src/main/java/org/gridfour/demo/entropy/EntropyTabulator.java:227-297, util/KahanSummation.java:63-69)
+ * What the reference's data assessment says about a raster, over a block that lies in device memory: n_cells cells, row-major and
+ * contiguous as gf_block_read_elems_dev delivers them -- int32 (INT), int16 (SHORT), float32 (FLOAT), the pointer 4-byte aligned.
+ * GF_ELEM_ICF is refused with GF_ERR_UNSUPPORTED: read the element as INT codes, or tabulate the float block as FLOAT.  Everything
+ * delivered is integers or the result of a comparison with a definite tie rule: bit-exact whatever the order of evaluation.
+ *   DENSE FORM: InputDataStatCollector beside PackageData's zMin / zMax / zSum, quirks included.
+ *   gf_tab_dense_plan_of (host arithmetic only), the constructor: n_counter = (int)((def_max - def_min + 1) * scale), the difference a
+ *   Java int (it wraps), the product in double with the scale as given, the cast Java's (truncating, saturating, NaN -> 0); base =
+ *   (int)(def_min * scale); n_bins = n_counter + 1 counters; scale_used = (double)(float) scale -- the constructor stores the scale
+ *   through a float, so the plan and the samples see two different scales.  GF_ERR_ARG: n_counter < 0, a scale that is NaN or <= 0;
+ *   GF_ERR_UNSUPPORTED: n_bins > 2^28.
+ *   Per cell, the value taken as a double: a NaN is no sample, and under GF_TAB_SKIP_FILL an INT / SHORT cell equal to fill_i is none
+ *   either (both count in n_skipped).  A sample: sample = (int)(v * scale_used + 0.5) in FP64 without fma, index = sample - base with
+ *   int32 wrap; index < 0 or index > n_counter touches no counter and neither n_samples nor sum_samples, but still counts for min /
+ *   max / sum_i; else counter[index]++, sum_samples += sample, n_samples++.  (The cast truncates toward zero: at scale 1 the int -3
+ *   is sample -2.)  The reference's mean is sum_samples / n_samples / scale_used: the caller's arithmetic.
+ *   min / max are zMin / zMax: they start at +-infinity and are replaced on a strict < / >, so each is the value of the FIRST cell in
+ *   row-major order that compares equal to the extreme (which decides between +0.0 and -0.0), and min_at / max_at is first_cell +
+ *   that cell's index (-1: no sample).  sum_i is the exact int64 sum of all samples of an INT / SHORT block (0 for FLOAT); it equals
+ *   zSum wherever every partial sum stays below 2^53.  No float sum is offered: a sequential double sum of floats has an order.
+ *   Without GF_TAB_ACCUMULATE the call itself initialises d_counter[0 .. n_bins) and *d_summary; with it the call adds to what is
+ *   there -- a raster goes through in strips with first_cell as the reference's row loop does, and ties in min / max go to the smaller
+ *   global index.  n_cells == 0 is GF_OK: it initialises unless accumulating and reads nothing; more than 2^40 cells in one call is
+ *   GF_ERR_UNSUPPORTED (go through in strips).  The device form ONLY ENQUEUES on
+ *   `stream` (NULL: the context's) and writes exactly n_bins counters and the summary; a small fixed-size scratch of the context is
+ *   allocated on the first call.  gf_block_tabulate_dense is the same for block, counters and summary in host memory (accumulating, it
+ *   uploads what they hold), staged through a buffer of the context; it synchronises.
+ *   SYMBOL FORM: EntropyTabulator's count of every distinct 32-bit symbol -- an INT cell's bits, a SHORT cell sign-extended, a FLOAT
+ *   cell's RAW bits (-0.0 and +0.0 are two symbols, every NaN payload its own); every cell counts, the fill included.  The table is
+ *   what the reference's count file holds, compacted: the distinct symbols in ascending UNSIGNED order (negative ints behind the
+ *   positive ones), each with its count.  n_samples = n_cells, n_symbols the distinct symbols, n_unique those with count 1, n_repeated
+ *   the rest, max_count the largest count.  With n_symbols > table_cap the first table_cap entries are written, n_written = table_cap,
+ *   the scalars are complete, and the host form returns GF_ERR_CAPACITY; table_cap == 0 with NULL tables asks for the scalars alone.
+ *   n_cells > 2^31 - 1: GF_ERR_UNSUPPORTED (a count is a Java int).  There is no accumulate form.  The call grows a temporary of the
+ *   context on demand (9 bytes per cell) and only enqueues; it is not claimed safe for hipGraph capture.
+ *   gf_tab_entropy_counts (host only): bits per sample from counts in the order given, counts <= 0 skipped.  kahan = 1 is
+ *   EntropyTabulator's sum: p = count / (double) n_samples, s = -p * log(p), added with KahanSummation.add as written, the sum divided
+ *   by log(2.0).  kahan = 0 is InputDataStatCollector.getEntropy: sum += p * log(p), -sum / log(2.0), and 0 for n_samples == 0.
+ *   ORDER: every tabulation call of a context uses the same scratch of that context (the dense form's partials; the symbol form's
+ *   temporary, which a later, larger call frees and replaces).  The calls themselves are serialised by the context's lock, but what
+ *   they enqueue is not: tabulation calls on one context must all go to ONE stream, or the caller orders the streams (an event
+ *   between them) so that no two are in flight at once.  Contexts are independent of one another.
+ * GF_ERR_ARG, before the context or a device is looked at: a NULL ctx, block, spec, summary or counter array; NULL tables with
+ * table_cap > 0; an element type outside 0..3; a SHORT fill_i outside int16; n_cells < 0 or first_cell < 0; a block, counter or table
+ * pointer that is not 4-byte aligned, a summary pointer that is not 8-byte aligned; unknown flag bits; the plan's errors.  Then
+ * GF_ERR_UNSUPPORTED as listed.                                                                                                  */
+typedef struct gf_tab_dense { int32_t def_min, def_max; double scale; } gf_tab_dense;
+typedef struct gf_tab_dense_plan { int32_t n_counter, base; int64_t n_bins; double scale_used; } gf_tab_dense_plan;
+typedef struct gf_tab_summary {          /* device memory, 8-byte aligned */
+    int64_t n_cells, n_skipped;          /* cells looked at; cells that are no sample (NaN; the fill under GF_TAB_SKIP_FILL) */
+    int64_t n_samples, sum_samples;      /* the collector's nSamples and sumSamples (Java long, wraps)                       */
+    int64_t sum_i;                       /* INT, SHORT: exact sum of all samples; FLOAT: 0                                   */
+    double  min, max;                    /* zMin, zMax; +inf / -inf where there is no sample                                 */
+    int64_t min_at, max_at;              /* first_cell + row-major index of the cell that holds them; -1: none              */
+} gf_tab_summary;
+#define GF_TAB_ACCUMULATE 1
+#define GF_TAB_SKIP_FILL  2
+typedef struct gf_tab_symbols { int64_t n_samples, n_symbols, n_unique, n_repeated, n_written; int32_t max_count, reserved; } gf_tab_symbols;
+gf_status gf_tab_dense_plan_of(const gf_tab_dense *spec, gf_tab_dense_plan *plan);
+gf_status gf_block_tabulate_dense_dev(gf_context *ctx, void *stream, int elem_type, int32_t fill_i, int flags, const void *d_block,
+                                      int64_t n_cells, int64_t first_cell, const gf_tab_dense *spec, int32_t *d_counter,
+                                      gf_tab_summary *d_summary);
+gf_status gf_block_tabulate_dense(gf_context *ctx, int elem_type, int32_t fill_i, int flags, const void *block, int64_t n_cells,
+                                  int64_t first_cell, const gf_tab_dense *spec, int32_t *counter, gf_tab_summary *summary);
+gf_status gf_block_tabulate_symbols_dev(gf_context *ctx, void *stream, int elem_type, const void *d_block, int64_t n_cells,
+                                        uint32_t *d_symbols, int32_t *d_counts, size_t table_cap, gf_tab_symbols *d_summary);
+gf_status gf_block_tabulate_symbols(gf_context *ctx, int elem_type, const void *block, int64_t n_cells, uint32_t *symbols,
+                                    int32_t *counts, size_t table_cap, gf_tab_symbols *summary);
+gf_status gf_tab_entropy_counts(const int32_t *counts, size_t n, int64_t n_samples, int kahan, double *entropy);
+
 /* ---- a grid block WRITTEN: raster in, tile records out, in device memory ------------------------------------------------------
  * (gvrs/TileElementInt.java:118-126, TileElementShort.java:136-143, TileElementFloat.java:133-149, TileElementIntCodedFloat.java:152-169
  * setValue / setIntValue; TileElement*.hasValidData, gvrs/RasterTile.java:215-222; gvrs/RecordManager.java:386-490 writeTile, :413-419)
