@@ -124,6 +124,20 @@ SIGNATURES = {
     "gf_block_render_lattice_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "gf_block_render_points_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "gf_block_render_lattice": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "gf_image_split_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]),
+    "gf_image_join_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]),
+    "gf_image_reduce_size": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "gf_image_reduce_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "gf_image_split": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]),
+    "gf_image_join": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp]),
+    "gf_image_reduce": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "gf_image_write_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_int,
+                                     C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "gf_image_read_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_int, _vp,
+                                    _vp]),
+    "gf_image_write": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp,
+                                 C.c_size_t, _vp, _vp, _vp, _vp]),
+    "gf_image_read": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int32, _vp, _vp, C.c_size_t, _vp, _vp, C.c_int, _vp, _vp]),
     "gf_block_downsample_rect": (C.c_int, [_vp, C.c_int, _vp]),
     "gf_block_downsample_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "gf_block_downsample_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),

@@ -285,6 +285,69 @@ class GvrsHipContext:
         check(lib().gf_tab_entropy_counts(_ptr(counts), counts.size, int(n_samples), int(bool(kahan)), C.byref(e)), "gf_tab_entropy_counts")
         return e.value
 
+    # ---- ARGB images as element planes and as overviews (gf_image_split / _join / _reduce) ----
+    @staticmethod
+    def _image_kind(model, elem_type):
+        model = IMAGE_MODELS[model] if isinstance(model, str) else int(model)
+        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
+        return model, et, (np.int16 if et == 1 else np.int32)
+
+    def image_split_dev(self, model, elem_type, n_pixels, d_argb, d_planes):
+        """gf_image_split_dev on device pointers: n_pixels ARGB words -> three planes (model "rgb": r, g, b; "ycocg": Y, Co, Cg) of
+        int32 ("int") or int16 ("short").  Runs on the context's stream; enqueues only."""
+        model, et, _ = self._image_kind(model, elem_type)
+        val = lambda p: p.value if isinstance(p, C.c_void_p) else p
+        assert len(d_planes) == 3
+        check(lib().gf_image_split_dev(self._h, model, et, int(n_pixels), d_argb, (C.c_void_p * 3)(*[val(p) for p in d_planes])),
+              "gf_image_split_dev")
+
+    def image_join_dev(self, model, elem_type, n_pixels, d_planes, d_argb):
+        """gf_image_join_dev, the inverse: three planes of any ints -> n_pixels ARGB words.  Enqueues only."""
+        model, et, _ = self._image_kind(model, elem_type)
+        val = lambda p: p.value if isinstance(p, C.c_void_p) else p
+        assert len(d_planes) == 3
+        check(lib().gf_image_join_dev(self._h, model, et, int(n_pixels), (C.c_void_p * 3)(*[val(p) for p in d_planes]), d_argb),
+              "gf_image_join_dev")
+
+    @staticmethod
+    def image_reduce_size(width, height, factor):
+        """gf_image_reduce_size: (width // factor, height // factor)"""
+        w, h = C.c_int(), C.c_int()
+        check(lib().gf_image_reduce_size(int(width), int(height), int(factor), C.byref(w), C.byref(h)), "gf_image_reduce_size")
+        return w.value, h.value
+
+    def image_reduce_dev(self, width, height, factor, d_argb, d_out):
+        """gf_image_reduce_dev: height rows of width ARGB words -> the image of image_reduce_size(...), each word the per-channel
+        box average of factor x factor pixels as DemoCOG.makeReducedImage rounds it.  Enqueues only."""
+        check(lib().gf_image_reduce_dev(self._h, int(width), int(height), int(factor), d_argb, d_out), "gf_image_reduce_dev")
+
+    def image_split(self, argb, model="ycocg", elem_type="short"):
+        """gf_image_split, the host-memory form (staged by the library): three planes in the shape of argb"""
+        model, et, dt = self._image_kind(model, elem_type)
+        argb = np.ascontiguousarray(argb).view(np.int32) if np.asarray(argb).dtype == np.uint32 else np.ascontiguousarray(argb, np.int32)
+        planes = [np.zeros(argb.shape, dt) for _ in range(3)]
+        check(lib().gf_image_split(self._h, model, et, argb.size, _ptr(argb), (C.c_void_p * 3)(*[p.ctypes.data for p in planes])), "gf_image_split")
+        return planes
+
+    def image_join(self, planes, model="ycocg", elem_type="short"):
+        """gf_image_join, the host-memory form: ARGB words (int32) in the shape of the planes"""
+        model, et, dt = self._image_kind(model, elem_type)
+        planes = [np.ascontiguousarray(p, dt) for p in planes]
+        assert len(planes) == 3 and all(p.shape == planes[0].shape for p in planes)
+        argb = np.zeros(planes[0].shape, np.int32)
+        check(lib().gf_image_join(self._h, model, et, argb.size, (C.c_void_p * 3)(*[p.ctypes.data for p in planes]), _ptr(argb)), "gf_image_join")
+        return argb
+
+    def image_reduce(self, argb, factor):
+        """gf_image_reduce, the host-memory form: argb [height, width] -> int32 [height // factor, width // factor]"""
+        a = np.asarray(argb)
+        argb = np.ascontiguousarray(a).view(np.int32) if a.dtype == np.uint32 else np.ascontiguousarray(a, np.int32)
+        assert argb.ndim == 2
+        w, h = self.image_reduce_size(argb.shape[1], argb.shape[0], factor)
+        out = np.zeros((h, w), np.int32)
+        check(lib().gf_image_reduce(self._h, argb.shape[1], argb.shape[0], int(factor), _ptr(argb), C.c_void_p(out.ctypes.data)), "gf_image_reduce")
+        return out
+
     def close(self):
         if self._h:
             lib().gf_context_destroy(self._h)
@@ -297,6 +360,8 @@ class GvrsHipContext:
             pass
 
 
+IMAGE_RGB, IMAGE_YCOCG = 0, 1                                              # GF_IMAGE_*
+IMAGE_MODELS = {"rgb": IMAGE_RGB, "ycocg": IMAGE_YCOCG}
 TAB_ACCUMULATE, TAB_SKIP_FILL = 1, 2                                      # GF_TAB_*
 _TAB_DENSE = np.dtype([("def_min", np.int32), ("def_max", np.int32), ("scale", np.float64)])                          # gf_tab_dense
 _TAB_DENSE_PLAN = np.dtype([("n_counter", np.int32), ("base", np.int32), ("n_bins", np.int64), ("scale_used", np.float64)])   # gf_tab_dense_plan
@@ -1478,6 +1543,119 @@ class CodecMasterHip:
             return rc, idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) if fits else None for t in range(n_out)], used, status, offsets
         check(rc, "gf_block_write_elems")
         return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
+
+    # ---- ARGB images stored as tile records of three elements and read back (gf_image_write[_dev], gf_image_read[_dev]) ----
+    def _image_args(self, nRows, nCols, grid_shape, rect, model, elem_type, fill):
+        model, et, _ = GvrsHipContext._image_kind(model, elem_type)
+        fill = (INT4_NULL_CODE if et == 0 else -32768) if fill is None else int(fill)
+        specs = np.zeros(3, _ELEM_SPEC)
+        specs["type"], specs["fill_i"] = et, fill
+        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
+        rect = np.ascontiguousarray(rect, np.int32)
+        tr = tuple(C.c_int32() for _ in range(4))
+        check(lib().gf_block_tile_rect(_ptr(grid), _ptr(rect), *[C.byref(x) for x in tr]), "gf_block_tile_rect")
+        n_out = tr[2].value * tr[3].value
+        full = n_out * int(lib().gf_tile_record_max_bytes_elems(_ptr(specs), 3, nRows, nCols))
+        return model, et, fill, grid, rect, n_out, full
+
+    @staticmethod
+    def _image_words(argb, rect):
+        a = np.asarray(argb)
+        a = np.ascontiguousarray(a).view(np.int32) if a.dtype == np.uint32 else np.ascontiguousarray(a, np.int32)
+        assert a.size == int(rect[2]) * int(rect[3])
+        return a.reshape(-1)
+
+    def image_write_dev(self, nRows, nCols, grid_shape, rect, argb, model="ycocg", elem_type="short", fill=None, old=None, checksums=True,
+                        verify_old_checksums=True, blob_cap=None, raw=False):
+        """gf_image_write_dev: rect's pixels (argb [n_rows, n_cols] words) stored as tile records of three elements -- the planes r,
+        g, b ("rgb") or Y, Co, Cg ("ycocg") as "int" or "short" elements with fill `fill` -- as write_block_dev stores blocks, and
+        returning what it returns.  Uploads, calls, synchronises, downloads."""
+        model, et, fill, grid, rect, n_out, full = self._image_args(nRows, nCols, grid_shape, rect, model, elem_type, fill)
+        argb = self._image_words(argb, rect)
+        old_blob, old_off = (np.zeros(16, np.uint8), np.zeros(1, np.uint64)) if old is None else (
+            np.ascontiguousarray(old[0], dtype=np.uint8), np.ascontiguousarray(old[1], dtype=np.uint64))
+        n_old = old_off.size - 1
+        cap = full if blob_cap is None else int(blob_cap)
+        d_argb = DeviceBuffer(self.ctx, argb.nbytes + 16).upload(argb)
+        d_oblob = DeviceBuffer(self.ctx, old_blob.size + 32).fill(0).upload(old_blob)
+        d_ooff = DeviceBuffer(self.ctx, old_off.nbytes + 16).upload(old_off)
+        d_blob = DeviceBuffer(self.ctx, max(cap, full) + 64).fill(0xA5)
+        d_off = DeviceBuffer(self.ctx, (n_out + 1) * 8 + 16).fill(0xff)
+        d_idx = DeviceBuffer(self.ctx, n_out * 4 + 16).fill(0x7f)
+        d_used = DeviceBuffer(self.ctx, 3 * n_out + 16).fill(0)
+        d_st = DeviceBuffer(self.ctx, n_out * 4 + 16).fill(0x7f)
+        try:
+            check(lib().gf_image_write_dev(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, model, et, fill, _ptr(grid), _ptr(rect),
+                                           d_argb.ptr, n_old, d_oblob.ptr if n_old else None, int(old_off[-1]) if n_old else 0,
+                                           d_ooff.ptr if n_old else None, int(bool(verify_old_checksums)), int(bool(checksums)), d_blob.ptr, cap,
+                                           d_off.ptr, d_idx.ptr, d_used.ptr, d_st.ptr), "gf_image_write_dev")
+            self.ctx.synchronize()
+            offsets = d_off.download(np.uint64, n_out + 1)
+            blob = d_blob.download(np.uint8, max(cap, full) + 64)
+            idx = d_idx.download(np.int32, n_out)
+            used = d_used.download(np.uint8, 3 * n_out).reshape(3, n_out)
+            status = d_st.download(np.int32, n_out)
+        finally:
+            for b in (d_argb, d_oblob, d_ooff, d_blob, d_off, d_idx, d_used, d_st):
+                b.free()
+        if raw:
+            return idx, blob, offsets, used, status
+        return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
+
+    def image_write(self, nRows, nCols, grid_shape, rect, argb, model="ycocg", elem_type="short", fill=None, old=None, checksums=True,
+                    verify_old_checksums=True, blob_cap=None):
+        """The same through gf_image_write, the host-memory form, which takes any codec list: (tile indices, records, codec used,
+        status); a negative per-tile status or too small a blob_cap raises."""
+        model, et, fill, grid, rect, n_out, full = self._image_args(nRows, nCols, grid_shape, rect, model, elem_type, fill)
+        argb = self._image_words(argb, rect)
+        old_blob, old_off = (np.zeros(16, np.uint8), np.zeros(1, np.uint64)) if old is None else (
+            np.ascontiguousarray(old[0], dtype=np.uint8), np.ascontiguousarray(old[1], dtype=np.uint64))
+        n_old = old_off.size - 1
+        cap = full if blob_cap is None else int(blob_cap)
+        old_blob = np.concatenate([old_blob, np.zeros(16, np.uint8)])
+        blob = np.empty(max(cap, 16), np.uint8)
+        offsets = np.zeros(n_out + 1, np.uint64)
+        idx = np.full(n_out, -1, np.int32)
+        used = np.zeros((3, n_out), np.uint8)
+        status = np.full(n_out, 0x7f7f7f7f, np.int32)
+        check(lib().gf_image_write(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, model, et, fill, _ptr(grid), _ptr(rect), _ptr(argb),
+                                   n_old, _ptr(old_blob) if n_old else None, _ptr(old_off) if n_old else None, int(bool(verify_old_checksums)),
+                                   int(bool(checksums)), _ptr(blob), cap, _ptr(offsets), _ptr(idx), _ptr(used), _ptr(status)), "gf_image_write")
+        return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
+
+    def image_read_dev(self, nRows, nCols, grid_shape, rect, blob, offsets, model="ycocg", elem_type="short", fill=None, verify_checksums=True):
+        """gf_image_read_dev: rect's pixels read from tile records of three elements as image_write_dev writes them: (argb [n_rows,
+        n_cols] int32, status [3, n_records]).  The pixels of tiles the bytes do not hold are the join of three fills."""
+        model, et, fill, grid, rect, _, _ = self._image_args(nRows, nCols, grid_shape, rect, model, elem_type, fill)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nt, n_px = offsets.size - 1, int(rect[2]) * int(rect[3])
+        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
+        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
+        d_argb = DeviceBuffer(self.ctx, n_px * 4 + 16).fill(0)
+        d_st = DeviceBuffer(self.ctx, 3 * nt * 4 + 16).fill(0)
+        try:
+            check(lib().gf_image_read_dev(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, model, et, fill, _ptr(grid), _ptr(rect), nt,
+                                          d_blob.ptr, blob.size, d_off.ptr, int(bool(verify_checksums)), d_argb.ptr, d_st.ptr), "gf_image_read_dev")
+            self.ctx.synchronize()
+            argb = d_argb.download(np.int32, n_px).reshape(int(rect[2]), int(rect[3]))
+            status = d_st.download(np.int32, 3 * nt).reshape(3, nt)
+        finally:
+            for b in (d_blob, d_off, d_argb, d_st):
+                b.free()
+        return argb, status
+
+    def image_read(self, nRows, nCols, grid_shape, rect, blob, offsets, model="ycocg", elem_type="short", fill=None, verify_checksums=True):
+        """The same through gf_image_read, the host-memory form; offsets[-1] bytes of blob are read."""
+        model, et, fill, grid, rect, _, _ = self._image_args(nRows, nCols, grid_shape, rect, model, elem_type, fill)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        blob = np.concatenate([np.ascontiguousarray(blob, dtype=np.uint8), np.zeros(16, np.uint8)])
+        nt = offsets.size - 1
+        argb = np.zeros((int(rect[2]), int(rect[3])), np.int32)
+        status = np.zeros((3, nt), np.int32)
+        check(lib().gf_image_read(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, model, et, fill, _ptr(grid), _ptr(rect), nt,
+                                  _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), _ptr(argb), _ptr(status)), "gf_image_read")
+        return argb, status
 
     def packing_blob_dev(self, nRows, nCols, blob, offsets, lengths):
         """gf_codec_master_decode_batch_i32_dev: packing t = blob[offsets[t]:offsets[t]+lengths[t]].  Returns (values, status)."""

@@ -55,7 +55,10 @@ gf_status cutElems(const gf_elem_spec *elems, const gf_elem_range *ranges, int n
     return GF_OK;
 }
 
+}  // namespace
+
 // what the host can check, before the context or a device is looked at; fills g and the cut's element descriptions
+// (gvrs_api_image.hip shares it)
 gf_status blockWriteArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, const gf_elem_range *ranges, int nElems,
                          const gf_grid_spec *grid, const gf_rect *rect, const void *const *blocks, size_t nOld, const uint8_t *oldBlob,
                          const uint64_t *oldOffsets, const uint8_t *blob, size_t blobCap, const uint64_t *offsets, const int32_t *tileIndices,
@@ -76,6 +79,8 @@ gf_status blockWriteArgs(const gf_context *c, const int *codecs, int nCodecs, co
     if (cutElems(elems, ranges, nElems, cut) != GF_OK) return GF_ERR_ARG;
     return firstOf(sg, firstOf(se, so));
 }
+
+namespace {
 
 // the layout of the small per-tile results in dBwMeta: flags | pre-status, then -- the host form only -- offsets | indices | statuses |
 // codec used
@@ -158,6 +163,23 @@ gf_status blockCutDev(gf_context *c, void *stream, const int *codecs, int nCodec
 
 }  // namespace
 
+// blocks in device memory -> records in device memory: the cut, then the record writer with the cut's verdict as its pre-status (no
+// lock taken, no argument checked: its callers hold the context's lock)
+gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
+                        const GfBlockCutElem *cut, const void *const *dBlocks, size_t nOld, const uint8_t *dOldBlob, size_t oldBlobBytes,
+                        const uint64_t *dOldOffsets, int verifyOldChecksum, int checksumEnabled, uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets,
+                        int32_t *dTileIndices, uint8_t *dCodecUsed, int32_t *dStatus)
+{
+    const void *dTiles[GF_MAX_ELEMS];
+    const gf_status s = blockCutDev(c, stream, codecs, nCodecs, elems, nElems, g, cut, dBlocks, nOld, dOldBlob, oldBlobBytes, dOldOffsets,
+                                    verifyOldChecksum, dTileIndices, dTiles);
+    if (s != GF_OK) return s;
+    const size_t nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
+    const BwMeta m(nOut, nElems);
+    return recordsEncodeDev(c, stream, codecs, nCodecs, elems, nElems, g.nRowsTile, g.nColsTile, nOut, dTileIndices, dTiles, checksumEnabled, dBlob,
+                            blobCap, dOffsets, dCodecUsed, dStatus, (const int32_t *)((uint8_t *)c->dBwMeta.p + m.pre));
+}
+
 extern "C" {
 
 gf_status gf_block_tile_rect(const gf_grid_spec *grid, const gf_rect *rect, int32_t *tileRow0, int32_t *tileCol0, int32_t *nTileRows,
@@ -184,14 +206,8 @@ gf_status gf_block_write_elems_dev(gf_context *c, void *stream, const int *codec
     if (s != GF_OK) return s;
     if (!deviceList(codecs, nCodecs, elems, nElems)) return GF_ERR_UNSUPPORTED;
     GF_CTX_LOCK(c);
-    const void *dTiles[GF_MAX_ELEMS];
-    s = blockCutDev(c, stream, codecs, nCodecs, elems, nElems, g, cut, dBlocks, nOld, dOldBlob, oldBlobBytes, dOldOffsets, verifyOldChecksum,
-                    dTileIndices, dTiles);
-    if (s != GF_OK) return s;
-    const size_t nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
-    const BwMeta m(nOut, nElems);
-    return recordsEncodeDev(c, stream, codecs, nCodecs, elems, nElems, g.nRowsTile, g.nColsTile, nOut, dTileIndices, dTiles, checksumEnabled, dBlob,
-                            blobCap, dOffsets, dCodecUsed, dStatus, (const int32_t *)((uint8_t *)c->dBwMeta.p + m.pre));
+    return blockWriteDev(c, stream, codecs, nCodecs, elems, nElems, g, cut, dBlocks, nOld, dOldBlob, oldBlobBytes, dOldOffsets, verifyOldChecksum,
+                         checksumEnabled, dBlob, blobCap, dOffsets, dTileIndices, dCodecUsed, dStatus);
 }
 
 #ifdef GF_DIAG

@@ -154,6 +154,7 @@ struct gf_context {
     DevBuf dRender{this};                       // rendering, host form (gvrs_api_render.hip): block and outputs
     DevBuf dDsBlocks{this}, dDsStage{this};     // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks; the host
                                                 // forms' blocks and coarse blocks
+    DevBuf dImage{this}, dImageStage{this};     // images (gvrs_api_image.hip): the record forms' three planes; the host forms' words and planes
     DevBuf dTabPartials{this}, dTabSort{this}, dTabStage{this};   // tabulation (gvrs_api_tabulate.hip): k_tabulate_dense's partials (fixed size); the
                                                 // symbol form's keys, histograms and runs; the host forms' block, counters, tables and summary
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
@@ -307,6 +308,16 @@ gf_status blockReadArgs(const gf_context *c, const int *codecs, int nCodecs, con
 gf_status blockReadDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
                        const uint32_t *fill, size_t n, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets, int verifyChecksum,
                        void *const *dBlocks, int32_t *dStatus);
+// gvrs_api_blocks_write.hip: a block write's argument checks (fills g and the cut's element descriptions), and blocks in device
+// memory -> records in device memory (no lock taken, no argument checked)
+gf_status blockWriteArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, const gf_elem_range *ranges, int nElems,
+                         const gf_grid_spec *grid, const gf_rect *rect, const void *const *blocks, size_t nOld, const uint8_t *oldBlob,
+                         const uint64_t *oldOffsets, const uint8_t *blob, size_t blobCap, const uint64_t *offsets, const int32_t *tileIndices,
+                         const int32_t *status, bool onDevice, GfBlockGeom &g, GfBlockCutElem *cut);
+gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
+                        const GfBlockCutElem *cut, const void *const *dBlocks, size_t nOld, const uint8_t *dOldBlob, size_t oldBlobBytes,
+                        const uint64_t *dOldOffsets, int verifyOldChecksum, int checksumEnabled, uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets,
+                        int32_t *dTileIndices, uint8_t *dCodecUsed, int32_t *dStatus);
 // gvrs_api_interp.hip: what the host can check of an interpolation spec (fills g)
 gf_status interpSpecArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, GfInterpGeom &g);
 // gvrs_api_records.hip

@@ -24,6 +24,7 @@
 #include "gvrs_kernels.h"
 #include "gvrs_common.h"
 #include "gvrs_downsample_common.h"
+#include "gvrs_image_common.h"
 
 namespace {
 
@@ -47,17 +48,34 @@ struct DsAcc<float> {
     __device__ float finish(int32_t, int32_t n) const { return gf_ds_float_finish(sum, n); }
 };
 
+// a packed ARGB word as a cell type of its own (g.elemType GF_DS_ARGB): the channels are summed apart and the finish is
+// makeReducedImage's (gvrs_image_common.h); there is no fill
+struct DsArgb {
+    uint32_t w;
+    DsArgb() = default;
+    __device__ explicit DsArgb(uint32_t bits) : w(bits) {}
+};
+template <>
+struct DsAcc<DsArgb> {
+    GfImgAcc a;
+    __device__ void start() { gf_img_acc_start(a); }
+    __device__ void add(DsArgb v, int32_t) { gf_img_acc_add(a, v.w); }
+    __device__ DsArgb finish(int32_t, int32_t n) const { return DsArgb(gf_img_acc_finish(a, n)); }
+};
+
 // a cell as the dword an LDS stage holds, and back
 template <typename T>
 __device__ __forceinline__ uint32_t dsBits(T v)
 {
     if constexpr (std::is_same_v<T, float>) return __float_as_uint(v);
+    else if constexpr (std::is_same_v<T, DsArgb>) return v.w;
     else return (uint32_t)(int32_t)v;
 }
 template <typename T>
 __device__ __forceinline__ T dsCell(uint32_t bits)
 {
     if constexpr (std::is_same_v<T, float>) return __uint_as_float(bits);
+    else if constexpr (std::is_same_v<T, DsArgb>) return DsArgb(bits);
     else return (T)(int32_t)bits;
 }
 
@@ -260,6 +278,7 @@ hipError_t gf_launch_downsample(const GfDownsampleArgs &a, int path, hipStream_t
     case 0: return dsAny<int32_t>(a, path, stream);
     case 1: return dsAny<int16_t>(a, path, stream);
     case 2: return dsAny<float>(a, path, stream);
+    case GF_DS_ARGB: return dsAny<DsArgb>(a, path, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -49,12 +49,13 @@ GF_HD float gf_ds_float_finish(float sum, int32_t n) { return sum / (float)n; }
 
 // The geometry of one call, as the kernels and the harness take it.  The block holds pitch cells per row; output cell (i, j) of
 // outRows x outCols averages block rows rowOff + i * f .. + f - 1 and columns colOff + j * f .. + f - 1.
+#define GF_DS_ARGB 3
 struct GfDsGeom {
     int64_t pitch;                 // cells per block row (the block's n_cols)
     int64_t outRows, outCols;
     int32_t rowOff, colOff;        // the first window's corner inside the block, each in 0 .. f - 1
     int32_t f;                     // the factor, 1 .. 46340
-    int32_t elemType;              // GF_ELEM_*: 0 INT, 1 SHORT, 2 FLOAT
+    int32_t elemType;              // GF_ELEM_*: 0 INT, 1 SHORT, 2 FLOAT; GF_DS_ARGB: packed ARGB words (gvrs_image_common.h; fillI unused)
     int32_t fillI;
 };
 

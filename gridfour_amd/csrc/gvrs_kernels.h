@@ -10,6 +10,7 @@
 #include "gvrs_interp_common.h"
 #include "gvrs_render_common.h"
 #include "gvrs_downsample_common.h"
+#include "gvrs_image_common.h"
 #include "gvrs_tabulate_common.h"
 
 // per-tile status values written by the kernels; identical to gf_status in
@@ -683,6 +684,21 @@ struct GfDownsampleArgs {
 };
 int gf_downsample_path(const GfDownsampleArgs &a);
 hipError_t gf_launch_downsample(const GfDownsampleArgs &a, int path, hipStream_t stream);
+
+// Packed ARGB words split into three element planes and joined from them (gvrs_image.hip; driven by gvrs_api_image.hip; the
+// arithmetic: gvrs_image_common.h).  argb: nPixels words, 4-byte aligned; planes[k]: nPixels int32 (elemType 0, 4-byte aligned) or
+// int16 (elemType 1, 2-byte aligned).  Split reads argb and writes the planes, join the reverse; every output item is written
+// exactly once and nothing outside the nPixels items is touched.  The box average of packed words goes through
+// gf_launch_downsample with g.elemType = GF_DS_ARGB.
+struct GfImageArgs {
+    int32_t model;                 // GF_IMAGE_MODEL_*
+    int32_t elemType;              // 0 INT, 1 SHORT
+    size_t nPixels;
+    const void *argb;              // (join writes it)
+    const void *planes[3];         // (split writes them)
+};
+hipError_t gf_launch_image_split(const GfImageArgs &a, hipStream_t stream);
+hipError_t gf_launch_image_join(const GfImageArgs &a, hipStream_t stream);
 
 // A grid block in device memory tabulated (gvrs_tabulate.hip; driven by gvrs_api_tabulate.hip; the arithmetic: gvrs_tabulate_common.h).
 // Dense form: counter[0 .. g.nCounter] are ADDED to (the caller zeroes them unless it accumulates), partials is room for

@@ -1037,6 +1037,82 @@ gf_status gf_block_write_elems(gf_context *ctx, const int *codecs, int n_codecs,
                                int verify_old_checksum, int checksum_enabled, uint8_t *blob, size_t blob_cap, uint64_t *offsets,
                                int32_t *tile_indices, uint8_t *codec_used, int32_t *status);
 
+/* ---- ARGB IMAGES as element planes and as overviews, in device memory -----------------------------------------------------------
+ * (demo/src/main/java/org/gridfour/demo/imaging/ExperimentalImageStorage.java:203-213 elements r, g, b; :242-256 elements Y, Co, Cg
+ * after the reversible YCoCg-R transform; :275-286 the planes read back into words;
+ * demo/src/main/java/org/gridfour/demo/geoTiff/DemoCOG.java:735-770 makeReducedImage)
+ * What the reference does with an int[] argb, such as gf_block_render_* delivers: store it as three elements of a raster, read it
+ * back, and compute its overview levels.  All arithmetic is Java's wrapping 32-bit int, bit for bit.
+ *   SPLIT: r = (w >> 16) & 0xff, g = (w >> 8) & 0xff, b = w & 0xff; alpha is ignored.  GF_IMAGE_RGB: the planes are r, g, b.
+ *   GF_IMAGE_YCOCG: Co = r - b; tmp = b + (Co >> 1); Cg = g - tmp; Y = tmp + (Cg >> 1); the planes are Y, Co, Cg.  Every plane value
+ *   fits int16: elem_type GF_ELEM_INT writes int32 planes, GF_ELEM_SHORT int16 planes.
+ *   JOIN, of ANY three ints (planes may hold fill or damaged values; an int16 is sign-extended as TileElementShort.getValueInt):
+ *   YCoCg undoes the transform, tmp = Y - (Cg >> 1); g = Cg + tmp; b = tmp - (Co >> 1); r = b + Co; then both models give
+ *   word = (((0xff00 | r) << 8 | g) << 8) | b, without masks: r = 256 gives a red byte of 0, r = -1 gives 0xffff0000 | g << 8 | b.
+ *   The reference has no read loop of its own for r, g, b: the RGB join is its YCoCg loop without the transform.
+ *   With every plane INT_MIN (a missing tile under fill_i = INT_MIN) both models give 0xff000000.  RGB: 0xff00 | r = 0x8000ff00,
+ *   << 8 = 0x00ff0000, | g = 0x80ff0000, << 8 = 0xff000000, | b = 0xff000000.  YCoCg: Cg >> 1 = -2^30, tmp = -2^31 + 2^30 = -2^30,
+ *   g = -2^31 - 2^30 = 2^30 (wrapped), b = -2^30 + 2^30 = 0, r = INT_MIN; 0x00ff0000 | 2^30 = 0x40ff0000, << 8 = 0xff000000, | 0.
+ *   REDUCE by factor f: the reduced image has width / f x height / f words (gf_image_reduce_size, host arithmetic); word (i, j) is,
+ *   over the f x f window at (i * f, j * f), n = f * f: the channels summed, c = (cSum + n / 2) / n, 0xff000000 | r << 16 | g << 8 | b.
+ *   The rounding is not ExampleDownsample's: gf_block_downsample_* computes something else.  Rows and columns beyond the last whole
+ *   window are not looked at.
+ *   gf_image_split_dev / gf_image_join_dev: d_argb: n_pixels int32 in device memory, 4-byte aligned; d_planes: a HOST array of 3
+ *   device pointers, each to n_pixels items, 4-byte (INT) or 2-byte (SHORT) aligned.  gf_image_reduce_dev: d_argb: height rows of
+ *   width words, d_out: the reduced image, both 4-byte aligned.  Every output item is written exactly once; nothing outside the
+ *   arrays is read or written.  These three ONLY ENQUEUE, allocate nothing, never synchronise, and are safe to capture on the
+ *   context's stream.  gf_image_split / gf_image_join / gf_image_reduce are the same for host memory, staged through a buffer of the
+ *   context, synchronising: a convenience, not a rate.
+ *   gf_image_write_dev: rect's pixels (d_argb: rect.n_rows x rect.n_cols words, row-major) are split into three temporaries of the
+ *   context, which grow on demand; then exactly the block write of gf_block_write_elems_dev runs with three elements of elem_type,
+ *   fill fill_i and the type's whole range ([INT_MIN, INT_MAX], [-32768, 32767]: no cell is out of range).  Its outputs, statuses,
+ *   capacity rule, d_tile_indices, d_codec_used and accepted codec lists are the block write's; so is its stream class: it only
+ *   enqueues with n_old == 0 and synchronises once with old records.
+ *   gf_image_read_dev: gf_block_read_elems_dev into three temporaries, then the join.  d_status is element-major, 3 * n_records
+ *   entries, as the block read reports it.  The cells of absent or failed tiles are fill_i and go through the join like any other
+ *   int.  Synchronises once, as the block read does.
+ *   gf_image_write / gf_image_read: the same for host memory, as gf_block_write_elems / gf_block_read_elems stage; any codec list.
+ * THESE CALLS TAKE NO STREAM ARGUMENT.  They run on the context's stream, which gf_context_stream hands out.  A caller orders other
+ * work against that stream, or passes it (or NULL) to the other device forms of a chain.  The reason: tests/test_caller_stream_table.py
+ * requires a row in tests/caller_stream.py for every function of this header whose declaration has a `void *stream` parameter, so a
+ * stream parameter arrives in a later change.
+ * Each of the following is checked before the context or a device is looked at:
+ *   GF_ERR_ARG: a null pointer, or a null entry of a plane array;
+ *   GF_ERR_ARG: a model outside 0 .. 1;
+ *   GF_ERR_ARG: an elem_type other than GF_ELEM_INT / GF_ELEM_SHORT;
+ *   GF_ERR_ARG: a SHORT fill_i outside int16 (the record forms);
+ *   GF_ERR_ARG: a misaligned device pointer;
+ *   GF_ERR_ARG: width, height or factor < 1;
+ *   GF_ERR_UNSUPPORTED: factor > 2899 (2899^2 * 255 + 2899^2 / 2 = 2,147,273,355 still fits an int and 2900^2 does not: beyond it
+ *   the reference's sums wrap);
+ *   GF_ERR_UNSUPPORTED: more than 2^48 pixels;
+ *   GF_OK, nothing written: n_pixels == 0; an empty reduced image (factor > width or factor > height);
+ *   the record forms: whatever gf_block_write_elems[_dev] / gf_block_read_elems[_dev] reject, with the code they give.          */
+#define GF_IMAGE_RGB 0
+#define GF_IMAGE_YCOCG 1
+gf_status gf_image_split_dev(gf_context *ctx, int model, int elem_type, size_t n_pixels, const int32_t *d_argb, void *const *d_planes);
+gf_status gf_image_join_dev(gf_context *ctx, int model, int elem_type, size_t n_pixels, const void *const *d_planes, int32_t *d_argb);
+gf_status gf_image_reduce_size(int width, int height, int factor, int *out_width, int *out_height);
+gf_status gf_image_reduce_dev(gf_context *ctx, int width, int height, int factor, const int32_t *d_argb, int32_t *d_out);
+gf_status gf_image_split(gf_context *ctx, int model, int elem_type, size_t n_pixels, const int32_t *argb, void *const *planes);
+gf_status gf_image_join(gf_context *ctx, int model, int elem_type, size_t n_pixels, const void *const *planes, int32_t *argb);
+gf_status gf_image_reduce(gf_context *ctx, int width, int height, int factor, const int32_t *argb, int32_t *out);
+gf_status gf_image_write_dev(gf_context *ctx, const int *codecs, int n_codecs, int model, int elem_type, int32_t fill_i,
+                             const gf_grid_spec *grid, const gf_rect *rect, const int32_t *d_argb, size_t n_old,
+                             const uint8_t *d_old_blob, size_t old_blob_bytes, const uint64_t *d_old_offsets, int verify_old_checksum,
+                             int checksum_enabled, uint8_t *d_blob, size_t blob_cap, uint64_t *d_offsets, int32_t *d_tile_indices,
+                             uint8_t *d_codec_used, int32_t *d_status);
+gf_status gf_image_read_dev(gf_context *ctx, const int *codecs, int n_codecs, int model, int elem_type, int32_t fill_i,
+                            const gf_grid_spec *grid, const gf_rect *rect, size_t n_records, const uint8_t *d_blob, size_t blob_bytes,
+                            const uint64_t *d_offsets, int verify_checksum, int32_t *d_argb, int32_t *d_status);
+gf_status gf_image_write(gf_context *ctx, const int *codecs, int n_codecs, int model, int elem_type, int32_t fill_i,
+                         const gf_grid_spec *grid, const gf_rect *rect, const int32_t *argb, size_t n_old, const uint8_t *old_blob,
+                         const uint64_t *old_offsets, int verify_old_checksum, int checksum_enabled, uint8_t *blob, size_t blob_cap,
+                         uint64_t *offsets, int32_t *tile_indices, uint8_t *codec_used, int32_t *status);
+gf_status gf_image_read(gf_context *ctx, const int *codecs, int n_codecs, int model, int elem_type, int32_t fill_i,
+                        const gf_grid_spec *grid, const gf_rect *rect, size_t n_records, const uint8_t *blob, const uint64_t *offsets,
+                        int verify_checksum, int32_t *argb, int32_t *status);
+
 /* ---- CodecFloat (compress/CodecFloat.java:328-458): float32 tiles ---------------------------
  * The five byte planes (sign bits, exponent, three byte-delta coded mantissa bytes) are split and
  * merged on the GPU; the Deflate stage of each plane runs on the host's zlib (its bytes are defined
