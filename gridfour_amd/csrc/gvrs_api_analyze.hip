@@ -10,26 +10,19 @@
 // 100-141) are then accumulated here in tile order.  stats[p], p = 0..4 by predictor code (PredictorModelType ordinal),
 // stats[5] = "All Predictors"; counts ADD to what stats already holds (clearAnalysisData = zero the array).  The pair
 // counts behind CodecStats.getH2 (sA / sB) come from the same pass when the caller hands in tables for them.
-// The packings of an analysis batch to the device (c->dBlob, c->dOffsets, c->dLengths; c->dStatus sized), the lengths kept in
-// *lengths for the host's part.  Arguments as checked by the callers.
-static gf_status analyzeStage(gf_context *c, size_t nTiles, const uint8_t *blob, const uint64_t *offsets, std::vector<uint32_t> *lengths)
+// The packings of an analysis batch as a stage's inputs: blob | offsets | lengths (kept in *lengths for the host's part), and the
+// statuses that come back.  Arguments as checked by the callers.
+struct AnalyzeParts { int blob, offsets, lengths, status; };
+static AnalyzeParts analyzeStage(HostStage &sg, size_t nTiles, const uint8_t *blob, const uint64_t *offsets, std::vector<uint32_t> *lengths,
+                                 std::vector<int32_t> *st)
 {
-    GF_HIP(hipSetDevice(c->device));
-    const uint64_t total = offsets[nTiles];
-    gf_status s;
-    if ((s = c->dBlob.ensure(total + 32)) != GF_OK) return s;
-    if ((s = c->dLengths.ensure(nTiles * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure(nTiles * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dOffsets.ensure((nTiles + 1) * 8 + 16)) != GF_OK) return s;
     lengths->resize(nTiles);
-    for (size_t t = 0; t < nTiles; t++) {
-        if (offsets[t + 1] < offsets[t]) return GF_ERR_ARG;
-        (*lengths)[t] = (uint32_t)(offsets[t + 1] - offsets[t]);
-    }
-    GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, total, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nTiles + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(c->dLengths.p, lengths->data(), nTiles * 4, hipMemcpyHostToDevice, c->stream));
-    return GF_OK;
+    st->resize(nTiles);
+    for (size_t t = 0; t < nTiles; t++) (*lengths)[t] = (uint32_t)(offsets[t + 1] - offsets[t]);
+    AnalyzeParts p;
+    p.blob = sg.in(blob, (size_t)offsets[nTiles], 32), p.offsets = sg.in(offsets, (nTiles + 1) * 8);
+    p.lengths = sg.in(lengths->data(), nTiles * 4), p.status = sg.out(st->data(), nTiles * 4);
+    return p;
 }
 
 static gf_status analyzeBatch(gf_context *c, int nRows, int nCols, size_t nTiles, const uint8_t *blob, const uint64_t *offsets,
@@ -37,33 +30,21 @@ static gf_status analyzeBatch(gf_context *c, int nRows, int nCols, size_t nTiles
 {
     if (!c || nRows < 1 || nCols < 1 || !blob || !offsets || !stats) return GF_ERR_ARG;
     if (!offsetsValid(offsets, nTiles)) return GF_ERR_ARG;    // a bad array must not become an out-of-bounds read
-    const uint64_t total = offsets[nTiles];
-    std::vector<uint32_t> lengths;
-    gf_status s = analyzeStage(c, nTiles, blob, offsets, &lengths);
-    if (s != GF_OK) return s;
-    if ((s = c->dResiduals.ensure(nTiles * GF_ANALYSIS_WORDS * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dValues.ensure(16)) != GF_OK) return s;
-    uint32_t *dPairs = nullptr;
+    GF_HIP(hipSetDevice(c->device));
+    // staging: the packings | analysis records | a stand-in for the values, which an analysis does not write | the pair tables, zeroed
     const size_t pairWords = (size_t)GF_PAIR_TABLES * 65536;
-    if (pairCounts) {
-        if ((s = c->dCoefs.ensure(pairWords * 4)) != GF_OK) return s;
-        dPairs = (uint32_t *)c->dCoefs.p;
-        GF_HIP(hipMemsetAsync(dPairs, 0, pairWords * 4, c->stream));
-    }
-    s = decodeBatchDev(KIND_HUFFMAN, c, c->stream, nRows, nCols, nTiles, (const uint8_t *)c->dBlob.p, total,
-                       (const uint64_t *)c->dOffsets.p, 0, (const uint32_t *)c->dLengths.p, (int32_t *)c->dValues.p,
-                       (int32_t *)c->dStatus.p, 0, (uint32_t *)c->dResiduals.p, dPairs);
+    std::vector<uint32_t> lengths, rec(nTiles * GF_ANALYSIS_WORDS), pairs(pairCounts ? pairWords : 0);
+    std::vector<int32_t> st;
+    HostStage sg(c);
+    const AnalyzeParts in = analyzeStage(sg, nTiles, blob, offsets, &lengths, &st);
+    const int recP = sg.out(rec.data(), rec.size() * 4), valuesP = sg.local(16);
+    const int pairsP = sg.add(pairCounts ? pairs.data() : nullptr, pairWords * 4, STAGE_OUT | STAGE_ZERO);
+    gf_status s = sg.begin();
     if (s != GF_OK) return s;
-    std::vector<uint32_t> pairs;
-    if (pairCounts) {
-        pairs.resize(pairWords);
-        GF_HIP(hipMemcpyAsync(pairs.data(), dPairs, pairWords * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    std::vector<uint32_t> rec(nTiles * GF_ANALYSIS_WORDS);
-    std::vector<int32_t> st(nTiles);
-    GF_HIP(hipMemcpyAsync(rec.data(), c->dResiduals.p, rec.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(st.data(), c->dStatus.p, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
+    s = decodeBatchDev(KIND_HUFFMAN, c, c->stream, nRows, nCols, nTiles, sg.ptr<uint8_t>(in.blob), (size_t)offsets[nTiles],
+                       sg.ptr<uint64_t>(in.offsets), 0, sg.ptr<uint32_t>(in.lengths), sg.ptr<int32_t>(valuesP), sg.ptr<int32_t>(in.status), 0,
+                       sg.ptr<uint32_t>(recP), sg.ptr<uint32_t>(pairsP));
+    if (s != GF_OK || (s = sg.end()) != GF_OK) return s;
     const double LOG2 = std::log(2.0);
     const int64_t nValues = (int64_t)nRows * nCols;
     for (size_t t = 0; t < nTiles; t++) {
@@ -144,21 +125,19 @@ gf_status gf_canon_analyze_batch(gf_context *c, int nRows, int nCols, size_t nTi
     if (cells >= (1ull << 28)) return GF_ERR_UNSUPPORTED;
     GF_CTX_LOCK(c);
     if (nTiles == 0) return GF_OK;
-    std::vector<uint32_t> lengths;
-    gf_status s = analyzeStage(c, nTiles, blob, offsets, &lengths);
+    GF_HIP(hipSetDevice(c->device));
+    // staging: the packings | statistics records | the symbols of every tile
+    std::vector<uint32_t> lengths, rec(nTiles * GF_CANON_STAT_WORDS);
+    std::vector<int32_t> st;
+    HostStage sg(c);
+    const AnalyzeParts in = analyzeStage(sg, nTiles, blob, offsets, &lengths, &st);
+    const int recP = sg.out(rec.data(), rec.size() * 4), valuesP = sg.local(nTiles * gf_canon_stats_stride((uint32_t)cells) * 4);
+    gf_status s = sg.begin();
     if (s != GF_OK) return s;
-    const size_t stride = gf_canon_stats_stride((uint32_t)cells);
-    if ((s = c->dValues.ensure(nTiles * stride * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dResiduals.ensure(nTiles * GF_CANON_STAT_WORDS * 4 + 16)) != GF_OK) return s;
-    s = decodeBatchDev(KIND_CANON, c, c->stream, nRows, nCols, nTiles, (const uint8_t *)c->dBlob.p, offsets[nTiles],
-                       (const uint64_t *)c->dOffsets.p, 0, (const uint32_t *)c->dLengths.p, (int32_t *)c->dValues.p,
-                       (int32_t *)c->dStatus.p, 0, (uint32_t *)c->dResiduals.p);
-    if (s != GF_OK) return s;
-    std::vector<uint32_t> rec(nTiles * GF_CANON_STAT_WORDS);
-    std::vector<int32_t> st(nTiles);
-    GF_HIP(hipMemcpyAsync(rec.data(), c->dResiduals.p, rec.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(st.data(), c->dStatus.p, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
+    s = decodeBatchDev(KIND_CANON, c, c->stream, nRows, nCols, nTiles, sg.ptr<uint8_t>(in.blob), (size_t)offsets[nTiles],
+                       sg.ptr<uint64_t>(in.offsets), 0, sg.ptr<uint32_t>(in.lengths), sg.ptr<int32_t>(valuesP), sg.ptr<int32_t>(in.status), 0,
+                       sg.ptr<uint32_t>(recP));
+    if (s != GF_OK || (s = sg.end()) != GF_OK) return s;
     const int64_t n = (int64_t)cells;
     auto add = [&](gf_canon_stats &g, int64_t nBytes, int64_t bitsInCodeTable, int64_t observed, double entropy) {
         g.n_tiles++;                                                    // CanonHuffmanStats.addToCounts

@@ -195,27 +195,19 @@ gf_status gf_block_read_elems(gf_context *c, const int *codecs, int nCodecs, con
     if (s != GF_OK) return s;
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
-    const size_t blobBytes = nRecords ? (size_t)offsets[nRecords] : 0, nInst = (size_t)nElems * nRecords;
-    const size_t blockCells = (size_t)g.nRows * (size_t)g.nCols;
+    const size_t blobBytes = nRecords ? (size_t)offsets[nRecords] : 0;
     // staging: blob | offsets | the block of element 0, 1, ... | statuses
-    if ((s = c->dBlob.ensure(blobBytes + 32)) != GF_OK) return s;
-    if ((s = c->dOffsets.ensure((nRecords + 1) * 8 + 16)) != GF_OK) return s;
+    HostStage sg(c);
+    int blockP[GF_MAX_ELEMS];
+    const int blobP = sg.in(blob, blobBytes, 32), offsetsP = sg.in(offsets, nRecords ? (nRecords + 1) * 8 : 0);
+    stageElems(sg, STAGE_OUT, elems, nElems, (size_t)g.nRows * (size_t)g.nCols, blocks, blockP);
+    const int statusP = sg.out(status, (size_t)nElems * nRecords * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
     void *dBlocks[GF_MAX_ELEMS];
-    if ((s = elemArrays(c->dValues, elems, nElems, blockCells, dBlocks)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure(nInst * 4 + 16)) != GF_OK) return s;
-    int32_t *dStatus = (int32_t *)c->dStatus.p;
-    if (nRecords) {
-        GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, blobBytes, hipMemcpyHostToDevice, c->stream));
-        GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nRecords + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    s = blockReadDev(c, c->stream, codecs, nCodecs, elems, nElems, g, fill, nRecords, (const uint8_t *)c->dBlob.p, blobBytes,
-                     (const uint64_t *)c->dOffsets.p, verifyChecksum, dBlocks, dStatus);
-    if (s != GF_OK) return s;
-    for (int e = 0; e < nElems; e++)
-        GF_HIP(hipMemcpyAsync(blocks[e], dBlocks[e], blockCells * elemItemBytes(elems[e].type), hipMemcpyDeviceToHost, c->stream));
-    if (nInst) GF_HIP(hipMemcpyAsync(status, dStatus, nInst * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    sg.ptrs(blockP, nElems, dBlocks);
+    s = blockReadDev(c, c->stream, codecs, nCodecs, elems, nElems, g, fill, nRecords, sg.ptr<uint8_t>(blobP), blobBytes, sg.ptr<uint64_t>(offsetsP),
+                     verifyChecksum, dBlocks, sg.ptr<int32_t>(statusP));
+    return s != GF_OK ? s : sg.end();
 }
 
 }  // extern "C"

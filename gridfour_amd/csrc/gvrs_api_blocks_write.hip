@@ -82,16 +82,11 @@ gf_status blockWriteArgs(const gf_context *c, const int *codecs, int nCodecs, co
 
 namespace {
 
-// the layout of the small per-tile results in dBwMeta: flags | pre-status, then -- the host form only -- offsets | indices | statuses |
-// codec used
+// the layout of the small per-tile results in dBwMeta: flags | pre-status
 struct BwMeta {
     Carve k;
-    size_t flags, pre, offsets, indices, status, used;
-    BwMeta(size_t nOut, int nElems)
-        : flags(k.add(nOut * 4)), pre(k.add(nOut * 4)), offsets(k.add((nOut + 1) * 8)), indices(k.add(nOut * 4)), status(k.add(nOut * 4)),
-          used(k.add((size_t)nElems * nOut))
-    {
-    }
+    size_t flags, pre;
+    explicit BwMeta(size_t nOut) : flags(k.add(nOut * 4)), pre(k.add(nOut * 4)) {}
 };
 
 // blocks in device memory -> cut tiles in dBwTiles (dTiles[e]), pre-status in dBwMeta, tile indices in dTileIndices (the caller holds
@@ -103,7 +98,7 @@ gf_status blockCutDev(gf_context *c, void *stream, const int *codecs, int nCodec
     GF_HIP(hipSetDevice(c->device));
     const hipStream_t st = streamOf(c, stream);
     const size_t cells = (size_t)g.nRowsTile * (size_t)g.nColsTile, nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
-    const BwMeta m(nOut, nElems);
+    const BwMeta m(nOut);
     // the cut tiles: n_elems arrays of n_out * cells items with room behind a SHORT array's last word; the old records' tiles
     void *cutTiles[GF_MAX_ELEMS], *dOld[GF_MAX_ELEMS];
     gf_status s;
@@ -175,7 +170,7 @@ gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCod
                                     verifyOldChecksum, dTileIndices, dTiles);
     if (s != GF_OK) return s;
     const size_t nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
-    const BwMeta m(nOut, nElems);
+    const BwMeta m(nOut);
     return recordsEncodeDev(c, stream, codecs, nCodecs, elems, nElems, g.nRowsTile, g.nColsTile, nOut, dTileIndices, dTiles, checksumEnabled, dBlob,
                             blobCap, dOffsets, dCodecUsed, dStatus, (const int32_t *)((uint8_t *)c->dBwMeta.p + m.pre));
 }
@@ -247,59 +242,50 @@ gf_status gf_block_write_elems(gf_context *c, const int *codecs, int nCodecs, co
     const bool onDevice = deviceList(codecs, nCodecs, elems, nElems);
     const size_t cells = (size_t)g.nRowsTile * (size_t)g.nColsTile, nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
     const size_t blockCells = (size_t)g.nRows * (size_t)g.nCols, oldBytes = nOld ? (size_t)oldOffsets[nOld] : 0;
-    const size_t maxBlob = onDevice ? nOut * gf_tile_record_max_bytes_elems(elems, nElems, g.nRowsTile, g.nColsTile) : 0;
-    // staging: the block of element 0, 1, ... | old blob | old offsets | the records at their largest
-    Carve stage;
-    size_t at[GF_MAX_ELEMS];
-    carveElems(stage, elems, nElems, blockCells, at);
-    const size_t oldAt = stage.add(oldBytes + 32), oldOffAt = stage.add((nOld + 1) * 8), outAt = stage.add(maxBlob);
-    if ((s = c->dBwStage.ensure(stage)) != GF_OK) return s;
-    uint8_t *base = (uint8_t *)c->dBwStage.p;
-    const void *dBlocks[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        dBlocks[e] = base + at[e];
-        GF_HIP(hipMemcpyAsync(base + at[e], blocks[e], blockCells * elemItemBytes(elems[e].type), hipMemcpyHostToDevice, c->stream));
-    }
-    if (nOld) {
-        GF_HIP(hipMemcpyAsync(base + oldAt, oldBlob, oldBytes, hipMemcpyHostToDevice, c->stream));
-        GF_HIP(hipMemcpyAsync(base + oldOffAt, oldOffsets, (nOld + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    const BwMeta m(nOut, nElems);
-    if ((s = c->dBwMeta.ensure(m.k)) != GF_OK) return s;                       // (before its addresses are taken: blockCutDev asks for no more)
-    uint8_t *meta = (uint8_t *)c->dBwMeta.p;
-    const void *dTiles[GF_MAX_ELEMS];
-    s = blockCutDev(c, c->stream, codecs, nCodecs, elems, nElems, g, cut, dBlocks, nOld, base + oldAt, oldBytes, (const uint64_t *)(base + oldOffAt),
-                    verifyOldChecksum, (int32_t *)(meta + m.indices), dTiles);
-    if (s != GF_OK) return s;
     const size_t nInst = (size_t)nElems * nOut;
+    const size_t maxBlob = onDevice ? nOut * gf_tile_record_max_bytes_elems(elems, nElems, g.nRowsTile, g.nColsTile) : 0;
+    // staging: the block of element 0, 1, ... | old blob | old offsets | tile indices, and for a device list the records at their
+    // largest | offsets | statuses | codec used; the offsets say how much of the records counts
+    HostStage sg(c);
+    int blockP[GF_MAX_ELEMS];
+    stageElems(sg, STAGE_IN, elems, nElems, blockCells, blocks, blockP);
+    const int oldP = sg.in(nOld ? oldBlob : nullptr, oldBytes, 32), oldOffP = sg.in(nOld ? oldOffsets : nullptr, (nOld + 1) * 8);
+    const int indicesP = sg.out(tileIndices, nOut * 4);
+    const int blobP = sg.held(blob, maxBlob), offsetsP = sg.out(onDevice ? offsets : nullptr, (nOut + 1) * 8);
+    const int statusP = sg.out(onDevice ? status : nullptr, nOut * 4), usedP = sg.out(onDevice ? codecUsed : nullptr, nInst);
+    if ((s = sg.begin()) != GF_OK) return s;
+    void *dBlocks[GF_MAX_ELEMS];
+    sg.ptrs(blockP, nElems, dBlocks);
+    const BwMeta m(nOut);
+    if ((s = c->dBwMeta.ensure(m.k)) != GF_OK) return s;                       // (before its address is taken: blockCutDev asks for no more)
+    const int32_t *dPre = c->dBwMeta.at<int32_t>(m.pre);
+    const void *dTiles[GF_MAX_ELEMS];
+    s = blockCutDev(c, c->stream, codecs, nCodecs, elems, nElems, g, cut, dBlocks, nOld, sg.ptr<uint8_t>(oldP), oldBytes, sg.ptr<uint64_t>(oldOffP),
+                    verifyOldChecksum, sg.ptr<int32_t>(indicesP), dTiles);
+    if (s != GF_OK) return s;
     if (onDevice) {
-        s = recordsEncodeDev(c, c->stream, codecs, nCodecs, elems, nElems, g.nRowsTile, g.nColsTile, nOut, (const int32_t *)(meta + m.indices), dTiles,
-                             checksumEnabled, base + outAt, maxBlob, (uint64_t *)(meta + m.offsets), meta + m.used, (int32_t *)(meta + m.status),
-                             (const int32_t *)(meta + m.pre));
-        if (s != GF_OK) return s;
-        GF_HIP(hipMemcpyAsync(offsets, meta + m.offsets, (nOut + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        GF_HIP(hipMemcpyAsync(tileIndices, meta + m.indices, nOut * 4, hipMemcpyDeviceToHost, c->stream));
-        GF_HIP(hipMemcpyAsync(status, meta + m.status, nOut * 4, hipMemcpyDeviceToHost, c->stream));
-        if (codecUsed) GF_HIP(hipMemcpyAsync(codecUsed, meta + m.used, nInst, hipMemcpyDeviceToHost, c->stream));
-        GF_HIP(hipStreamSynchronize(c->stream));
+        s = recordsEncodeDev(c, c->stream, codecs, nCodecs, elems, nElems, g.nRowsTile, g.nColsTile, nOut, sg.ptr<int32_t>(indicesP), dTiles,
+                             checksumEnabled, sg.ptr<uint8_t>(blobP), maxBlob, sg.ptr<uint64_t>(offsetsP), sg.ptr<uint8_t>(usedP),
+                             sg.ptr<int32_t>(statusP), dPre);
+        if (s != GF_OK || (s = sg.flush()) != GF_OK) return s;
         gf_status first = GF_OK;
         for (size_t t = 0; t < nOut && first == GF_OK; t++)
             if (status[t] < 0) first = (gf_status)status[t];
         if (offsets[nOut] > blobCap) return first != GF_OK ? first : GF_ERR_CAPACITY;
-        if (offsets[nOut]) GF_HIP(hipMemcpy(blob, base + outAt, (size_t)offsets[nOut], hipMemcpyDeviceToHost));
+        if (offsets[nOut] && ((s = sg.fetch(blobP, (size_t)offsets[nOut])) != GF_OK || (s = sg.end()) != GF_OK)) return s;
         return first;
     }
-    // a list that needs the host's zlib: the cut tiles and the verdicts come back, the tiles that get a record go through the host
-    // encoders, and the records are laid out with zero-length records for the others
+    // a list that needs the host's zlib: the cut tiles and the verdicts come back from the device form's temporaries, the tiles that
+    // get a record go through the host encoders (which stage for themselves: this call's stage ends first), and the records are
+    // laid out with zero-length records for the others
     std::vector<std::vector<uint8_t>> tiles(nElems);
     for (int e = 0; e < nElems; e++) {
         const size_t tb = nOut * cells * elemItemBytes(elems[e].type);
         tiles[e].resize(tb + 4);                                                // (4 spare bytes: readable to the end of a SHORT array's last word)
         GF_HIP(hipMemcpyAsync(tiles[e].data(), dTiles[e], tb, hipMemcpyDeviceToHost, c->stream));
     }
-    GF_HIP(hipMemcpyAsync(tileIndices, meta + m.indices, nOut * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(status, meta + m.pre, nOut * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
+    GF_HIP(hipMemcpyAsync(status, dPre, nOut * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((s = sg.end()) != GF_OK) return s;
     std::vector<size_t> keep;
     gf_status first = GF_OK;
     for (size_t t = 0; t < nOut; t++) {

@@ -122,23 +122,14 @@ gf_status gf_block_downsample_elems(gf_context *c, const gf_elem_spec *elems, in
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
     // staging: the elements' blocks, then their coarse blocks
-    const size_t inCells = (size_t)block->n_rows * (size_t)block->n_cols, outCells = (size_t)outRect.n_rows * (size_t)outRect.n_cols;
-    Carve k;
-    size_t atIn[GF_MAX_ELEMS], atOut[GF_MAX_ELEMS];
-    carveElems(k, elems, nElems, inCells, atIn);
-    carveElems(k, elems, nElems, outCells, atOut);
-    if ((s = c->dDsStage.ensure(k)) != GF_OK) return s;
-    const void *dBlocks[GF_MAX_ELEMS];
-    void *dOut[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {
-        dBlocks[e] = c->dDsStage.at<void>(atIn[e]), dOut[e] = c->dDsStage.at<void>(atOut[e]);
-        GF_HIP(hipMemcpyAsync((void *)dBlocks[e], blocks[e], inCells * elemItemBytes(elems[e].type), hipMemcpyHostToDevice, c->stream));
-    }
-    if ((s = dsLaunch(c, c->stream, elems, nElems, *block, factor, outRect, dBlocks, dOut)) != GF_OK) return s;
-    for (int e = 0; e < nElems; e++)
-        GF_HIP(hipMemcpyAsync(out[e], dOut[e], outCells * elemItemBytes(elems[e].type), hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    HostStage sg(c);
+    int inP[GF_MAX_ELEMS], outP[GF_MAX_ELEMS];
+    stageElems(sg, STAGE_IN, elems, nElems, (size_t)block->n_rows * (size_t)block->n_cols, blocks, inP);
+    stageElems(sg, STAGE_OUT, elems, nElems, (size_t)outRect.n_rows * (size_t)outRect.n_cols, out, outP);
+    if ((s = sg.begin()) != GF_OK) return s;
+    void *dBlocks[GF_MAX_ELEMS], *dOut[GF_MAX_ELEMS];
+    sg.ptrs(inP, nElems, dBlocks), sg.ptrs(outP, nElems, dOut);
+    return (s = dsLaunch(c, c->stream, elems, nElems, *block, factor, outRect, dBlocks, dOut)) != GF_OK ? s : sg.end();
 }
 
 gf_status gf_block_read_downsampled_elems_dev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems,
@@ -174,31 +165,23 @@ gf_status gf_block_read_downsampled_elems(gf_context *c, const int *codecs, int 
     if (s != GF_OK) return s;
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
-    const size_t blobBytes = nRecords ? (size_t)offsets[nRecords] : 0, nInst = (size_t)nElems * nRecords;
+    const size_t blobBytes = nRecords ? (size_t)offsets[nRecords] : 0;
     const size_t outCells = (size_t)outRect.n_rows * (size_t)outRect.n_cols;
-    // staging: blob | offsets | statuses | the coarse block of element 0, 1, ...
-    if ((s = c->dBlob.ensure(blobBytes + 32)) != GF_OK) return s;
-    if ((s = c->dOffsets.ensure((nRecords + 1) * 8 + 16)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure(nInst * 4 + 16)) != GF_OK) return s;
+    // staging: blob | offsets | the coarse block of element 0, 1, ... | statuses
+    HostStage sg(c);
+    int outP[GF_MAX_ELEMS];
+    const int blobP = sg.in(blob, blobBytes, 32), offsetsP = sg.in(offsets, nRecords ? (nRecords + 1) * 8 : 0);
+    stageElems(sg, STAGE_OUT, asCodes, nElems, outCells, out, outP);
+    const int statusP = sg.out(status, (size_t)nElems * nRecords * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
     void *dFull[GF_MAX_ELEMS], *dOut[GF_MAX_ELEMS];
-    if ((s = elemArrays(c->dDsStage, asCodes, nElems, outCells, dOut)) != GF_OK) return s;
+    sg.ptrs(outP, nElems, dOut);
     if ((s = elemArrays(c->dDsBlocks, asCodes, nElems, (size_t)rect->n_rows * (size_t)rect->n_cols, dFull)) != GF_OK) return s;   // at full resolution
-    int32_t *dStatus = (int32_t *)c->dStatus.p;
-    if (nRecords) {
-        GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, blobBytes, hipMemcpyHostToDevice, c->stream));
-        GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nRecords + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    s = blockReadDev(c, c->stream, codecs, nCodecs, asCodes, nElems, g, fill, nRecords, (const uint8_t *)c->dBlob.p, blobBytes,
-                     (const uint64_t *)c->dOffsets.p, verifyChecksum, dFull, dStatus);
+    s = blockReadDev(c, c->stream, codecs, nCodecs, asCodes, nElems, g, fill, nRecords, sg.ptr<uint8_t>(blobP), blobBytes,
+                     sg.ptr<uint64_t>(offsetsP), verifyChecksum, dFull, sg.ptr<int32_t>(statusP));
     if (s != GF_OK) return s;
-    if (outCells) {
-        if ((s = dsLaunch(c, c->stream, asCodes, nElems, *rect, factor, outRect, dFull, dOut)) != GF_OK) return s;
-        for (int e = 0; e < nElems; e++)
-            GF_HIP(hipMemcpyAsync(out[e], dOut[e], outCells * elemItemBytes(asCodes[e].type), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (nInst) GF_HIP(hipMemcpyAsync(status, dStatus, nInst * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    if (outCells && (s = dsLaunch(c, c->stream, asCodes, nElems, *rect, factor, outRect, dFull, dOut)) != GF_OK) return s;
+    return sg.end();
 }
 
 }  // extern "C"

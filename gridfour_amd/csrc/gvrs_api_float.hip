@@ -120,15 +120,14 @@ gf_status gf_float_encode_batch_f32(gf_context *c, int codecIndex, int nRows, in
     GF_HIP(hipSetDevice(c->device));
     const size_t n = (size_t)nRows * (size_t)nCols, nSign = (n + 7) / 8;
     const size_t stride = roundUp(gf_float_planes_bytes(nRows, nCols), 16);
-    gf_status s;
-    if ((s = c->dValues.ensure(nTiles * n * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dPlanes.ensure(nTiles * stride + 16)) != GF_OK) return s;
-    GF_HIP(hipMemcpyAsync(c->dValues.p, values, nTiles * n * 4, hipMemcpyHostToDevice, c->stream));
-    s = gf_float_planes_encode_dev(c, c->stream, nRows, nCols, nTiles, (const float *)c->dValues.p, (uint8_t *)c->dPlanes.p, stride);
-    if (s != GF_OK) return s;
+    // staging: values | planes
     std::vector<uint8_t> planes(nTiles * stride);
-    GF_HIP(hipMemcpyAsync(planes.data(), c->dPlanes.p, nTiles * stride, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
+    HostStage sg(c);
+    const int valuesP = sg.in(values, nTiles * n * 4), planesP = sg.out(planes.data(), nTiles * stride);
+    gf_status s = sg.begin();
+    if (s != GF_OK) return s;
+    s = gf_float_planes_encode_dev(c, c->stream, nRows, nCols, nTiles, sg.ptr<float>(valuesP), sg.ptr<uint8_t>(planesP), stride);
+    if (s != GF_OK || (s = sg.end()) != GF_OK) return s;
     // framing, CodecFloat.java:371-391: codecIndex, 0, then five [int32 LE length, zlib stream]
     std::vector<std::vector<uint8_t>> packed(nTiles);
     std::vector<uint8_t> failed(nTiles, 0);

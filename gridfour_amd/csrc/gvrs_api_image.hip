@@ -102,12 +102,11 @@ gf_status recordFormArgs(int model, int elemType, int32_t fillI, const void *arg
 }
 
 // three planes of nPixels items in a buffer of the context
-gf_status planeArrays(DevBuf &b, int elemType, size_t nPixels, void **planes, size_t *wordsAt = nullptr)
+gf_status planeArrays(DevBuf &b, int elemType, size_t nPixels, void **planes)
 {
     Carve k;
     size_t at[3];
     for (int e = 0; e < 3; e++) at[e] = k.add(nPixels * itemBytes(elemType) + 4);
-    if (wordsAt) *wordsAt = k.add(nPixels * 4);
     const gf_status s = b.ensure(k);
     for (int e = 0; e < 3 && s == GF_OK; e++) planes[e] = b.at<void>(at[e]);
     return s;
@@ -160,16 +159,15 @@ gf_status gf_image_split(gf_context *c, int model, int elemType, size_t nPixels,
     if (s != GF_OK || nPixels == 0) return s;
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
-    // staging: the three planes | the words
+    // staging: the words | the three planes (four spare bytes behind each, as the record forms' planes have)
+    HostStage sg(c);
+    int planeP[3];
+    const int argbP = sg.in(argb, nPixels * 4);
+    for (int k = 0; k < 3; k++) planeP[k] = sg.add(planes[k], nPixels * itemBytes(elemType), STAGE_OUT, 4);
+    if ((s = sg.begin()) != GF_OK) return s;
     void *dPlanes[3];
-    size_t wordsAt = 0;
-    if ((s = planeArrays(c->dImageStage, elemType, nPixels, dPlanes, &wordsAt)) != GF_OK) return s;
-    int32_t *dArgb = c->dImageStage.at<int32_t>(wordsAt);
-    GF_HIP(hipMemcpyAsync(dArgb, argb, nPixels * 4, hipMemcpyHostToDevice, c->stream));
-    if ((s = splitLaunch(c->stream, model, elemType, nPixels, dArgb, dPlanes)) != GF_OK) return s;
-    for (int k = 0; k < 3; k++) GF_HIP(hipMemcpyAsync(planes[k], dPlanes[k], nPixels * itemBytes(elemType), hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    sg.ptrs(planeP, 3, dPlanes);
+    return (s = splitLaunch(c->stream, model, elemType, nPixels, sg.ptr<int32_t>(argbP), dPlanes)) != GF_OK ? s : sg.end();
 }
 
 gf_status gf_image_join(gf_context *c, int model, int elemType, size_t nPixels, const void *const *planes, int32_t *argb)
@@ -178,15 +176,15 @@ gf_status gf_image_join(gf_context *c, int model, int elemType, size_t nPixels, 
     if (s != GF_OK || nPixels == 0) return s;
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
+    // staging: the three planes (four spare bytes behind each) | the words
+    HostStage sg(c);
+    int planeP[3];
+    for (int k = 0; k < 3; k++) planeP[k] = sg.in(planes[k], nPixels * itemBytes(elemType), 4);
+    const int argbP = sg.out(argb, nPixels * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
     void *dPlanes[3];
-    size_t wordsAt = 0;
-    if ((s = planeArrays(c->dImageStage, elemType, nPixels, dPlanes, &wordsAt)) != GF_OK) return s;
-    int32_t *dArgb = c->dImageStage.at<int32_t>(wordsAt);
-    for (int k = 0; k < 3; k++) GF_HIP(hipMemcpyAsync(dPlanes[k], planes[k], nPixels * itemBytes(elemType), hipMemcpyHostToDevice, c->stream));
-    if ((s = joinLaunch(c->stream, model, elemType, nPixels, dPlanes, dArgb)) != GF_OK) return s;
-    GF_HIP(hipMemcpyAsync(argb, dArgb, nPixels * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    sg.ptrs(planeP, 3, dPlanes);
+    return (s = joinLaunch(c->stream, model, elemType, nPixels, dPlanes, sg.ptr<int32_t>(argbP))) != GF_OK ? s : sg.end();
 }
 
 gf_status gf_image_reduce(gf_context *c, int width, int height, int factor, const int32_t *argb, int32_t *out)
@@ -197,16 +195,10 @@ gf_status gf_image_reduce(gf_context *c, int width, int height, int factor, cons
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
     // staging: the image | the reduced image
-    const size_t nIn = (size_t)width * (size_t)height, nOut = (size_t)ow * (size_t)oh;
-    Carve k;
-    const size_t inAt = k.add(nIn * 4), outAt = k.add(nOut * 4);
-    if ((s = c->dImageStage.ensure(k)) != GF_OK) return s;
-    int32_t *dIn = c->dImageStage.at<int32_t>(inAt), *dOut = c->dImageStage.at<int32_t>(outAt);
-    GF_HIP(hipMemcpyAsync(dIn, argb, nIn * 4, hipMemcpyHostToDevice, c->stream));
-    if ((s = reduceLaunch(c->stream, width, factor, ow, oh, dIn, dOut)) != GF_OK) return s;
-    GF_HIP(hipMemcpyAsync(out, dOut, nOut * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    HostStage sg(c);
+    const int inP = sg.in(argb, (size_t)width * (size_t)height * 4), outP = sg.out(out, (size_t)ow * (size_t)oh * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
+    return (s = reduceLaunch(c->stream, width, factor, ow, oh, sg.ptr<int32_t>(inP), sg.ptr<int32_t>(outP))) != GF_OK ? s : sg.end();
 }
 
 gf_status gf_image_write_dev(gf_context *c, const int *codecs, int nCodecs, int model, int elemType, int32_t fillI, const gf_grid_spec *grid,

@@ -24,6 +24,7 @@
 #include "gvrs_kernels.h"
 #include "gvrs_encode_layout.h"
 #include "gvrs_carve.h"
+#include "gvrs_stage.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -74,6 +75,7 @@ struct DevBuf {
     size_t bytes = 0;
     std::atomic<uint64_t> *moves = &g_devBufMoves;
     DevBuf *next = nullptr;                         // the owner's list (gf_context::bufs)
+    bool staged = false;                            // a host form's Stage is live in it (gvrs_stage.h)
     DevBuf() = default;
     explicit DevBuf(gf_context *owner);             // a context's buffer: links itself in and counts on the context's counter
     DevBuf(const DevBuf &) = delete;
@@ -124,8 +126,7 @@ struct PinBuf {
     }
 };
 
-// A DevBuf is one line here: it links itself into bufs.  One DevBuf per owner: the host forms call one another while the caller's staging
-// is live (gf_block_write_elems -> recordsEncodeHost -> the float and LSOP host encoders; codecMasterDecodeScattered -> LSOP's host decode).
+// A DevBuf is one line here: it links itself into bufs.
 struct gf_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -136,27 +137,22 @@ struct gf_context {
     DevBuf trees{this};          // leaf records of the tree pre-pass: GF_TREE_REC_WORDS per tile
     DevBuf packRecs{this};       // encoder: selection records between k_huffman_encode and k_huffman_pack
     DevBuf flags{this};          // one word: tiles the fast decode kernel left to the general one (GfDecodeArgs::retryFlag)
-    // staging of the host-memory entry points: whichever host form is called owns these for the call (the nested ones use their own)
-    DevBuf dValues{this}, dSlots{this}, dBlob{this}, dLengths{this}, dPred{this}, dStatus{this}, dOffsets{this};
-    DevBuf dPlanes{this};        // CodecFloat plane staging
-    DevBuf dResiduals{this}, dCoefs{this}, dStatus2{this};   // LSOP staging
-    DevBuf dM32{this}, dM32Len{this}, dM32Models{this}, dSeeds{this};   // CodecDeflate staging
+    DevBuf dStage{this};         // the staging of the host-memory entry points: one Stage at a time (HostStage below)
+    DevBuf dValues{this}, dStatus{this}, dM32{this}, dM32Len{this}, dM32Models{this}, dSeeds{this};   // CodecDeflate's host encoder: a chunk's tiles,
+                                                // statuses and candidate streams (deflateEncodeBatchHost, which overlaps its chunks)
+    DevBuf dResiduals{this}, dCoefs{this}, dStatus2{this};   // LSOP12 under the records driver: residuals, coefficients, the second status
     DevBuf dInflate{this}, dInflOut{this}, dInflMeta{this};  // GPU inflate: stream descriptors, inflated bytes, produced / status
     DevBuf dBlockTmp{this}, dBlockIdx{this}, dBlockSlots{this};   // grid blocks (gvrs_api_blocks.hip): the records' decoded tiles on their way into a block,
                                                 // the gather's element table and the records' tile indices, the slot table of the block's tiles
     DevBuf dRecMeta{this}, dRecSub{this}, dRecTmp{this};          // records / mixed packings in device memory (gvrs_api_records_dev.hip): per-record framing
                                                 // results, the partition by codec, decoded tiles on their way to their place
-    DevBuf dBwTiles{this}, dBwMeta{this}, dBwStage{this};         // a block written (gvrs_api_blocks_write.hip): the elements' cut tiles, the tiles' flags and
-                                                // pre-status (the host form: its results too), the host form's blocks, old records and records
+    DevBuf dBwTiles{this}, dBwMeta{this};       // a block written (gvrs_api_blocks_write.hip): the elements' cut tiles, the tiles' flags and pre-status
     DevBuf dEncSlots{this}, dEncMeta{this}, dEncWide{this};       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots,
                                                 // their lengths / statuses and the records' layout, SHORT cells widened for the codecs
-    DevBuf dInterp{this};                       // interpolation, host form (gvrs_api_interp.hip): block, coordinates, spacings and outputs
-    DevBuf dRender{this};                       // rendering, host form (gvrs_api_render.hip): block and outputs
-    DevBuf dDsBlocks{this}, dDsStage{this};     // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks; the host
-                                                // forms' blocks and coarse blocks
-    DevBuf dImage{this}, dImageStage{this};     // images (gvrs_api_image.hip): the record forms' three planes; the host forms' words and planes
-    DevBuf dTabPartials{this}, dTabSort{this}, dTabStage{this};   // tabulation (gvrs_api_tabulate.hip): k_tabulate_dense's partials (fixed size); the
-                                                // symbol form's keys, histograms and runs; the host forms' block, counters, tables and summary
+    DevBuf dDsBlocks{this};                     // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks
+    DevBuf dImage{this};                        // images (gvrs_api_image.hip): the record forms' three planes
+    DevBuf dTabPartials{this}, dTabSort{this};  // tabulation (gvrs_api_tabulate.hip): k_tabulate_dense's partials (fixed size); the symbol form's
+                                                // keys, histograms and runs
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
     // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
     // scratch buffers, staging slots and recorded graphs are one set.  Recursive: entry points call each other.
@@ -176,6 +172,25 @@ inline DevBuf::DevBuf(gf_context *owner) : moves(&owner->bufMoves), next(owner->
 #define GF_CTX_LOCK(c)                                       \
     std::unique_lock<std::recursive_mutex> gfCtxLock_;       \
     if (c) gfCtxLock_ = std::unique_lock<std::recursive_mutex>((c)->mu)
+
+// The staging of a host form (gvrs_stage.h) in the context's dStage, on the context's stream.  One stage at a time: a host form that
+// began one ends it before it calls another host form, and begin() on a buffer in use fails the call (GF_ERR_HIP, gf_last_error).
+struct StageDev {
+    typedef gf_status Status;
+    DevBuf &buf;
+    hipStream_t st;
+    bool &busy() { return buf.staged; }
+    gf_status reserve(size_t bytes, unsigned char *&base) { const gf_status s = buf.ensure(bytes + 16); base = (unsigned char *)buf.p; return s; }
+    gf_status toDevice(void *d, const void *h, size_t n) { GF_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st)); return GF_OK; }
+    gf_status toHost(void *h, const void *d, size_t n) { GF_HIP(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, st)); return GF_OK; }
+    gf_status zero(void *d, size_t n) { GF_HIP(hipMemsetAsync(d, 0, n, st)); return GF_OK; }
+    gf_status sync() { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
+    gf_status refuse(const char *why) { g_lastError = why; return GF_ERR_HIP; }
+};
+struct HostStage : Stage<StageDev> {
+    explicit HostStage(gf_context *c) : Stage<StageDev>(StageDev{c->dStage, c->stream}) {}
+};
+static_assert(STAGE_MAX_PARTS >= 2 * GF_MAX_ELEMS + 12, "a stage holds every element's array twice and a dozen single parts");
 
 // the caller's stream, or the context's own
 inline hipStream_t streamOf(const gf_context *c, void *stream) { return stream ? (hipStream_t)stream : c->stream; }
@@ -263,19 +278,19 @@ gf_status elemsArgs(const gf_context *c, const int *codecs, int nCodecs, const g
                     size_t nTiles, const uint8_t *blob, bool blobOnDevice, const uint64_t *offsets, void *const *values,
                     const int32_t *status);
 size_t elemItemBytes(int type);
-// one array of `count` cells per element in a Carve (+ extra bytes behind each): at[e] is element e's offset
-inline void carveElems(Carve &k, const gf_elem_spec *elems, int nElems, size_t count, size_t *at, size_t extra = 0)
+// one array of `count` cells per element (+ slack bytes behind each) as parts of a stage: element e's lies at host[e], part[e] is its number
+inline void stageElems(HostStage &sg, unsigned flags, const gf_elem_spec *elems, int nElems, size_t count, const void *const *host, int *part,
+                       size_t slack = 0)
 {
-    size_t item[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) item[e] = elemItemBytes(elems[e].type);
-    k.each(nElems, count, item, at, extra);
+    for (int e = 0; e < nElems; e++) part[e] = sg.add(const_cast<void *>(host[e]), count * elemItemBytes(elems[e].type), flags, slack);
 }
-// ... and a buffer that holds those arrays alone: ensured, arrays[e] is element e's
+// ... and in a buffer that holds those arrays alone: ensured, arrays[e] is element e's
 inline gf_status elemArrays(DevBuf &b, const gf_elem_spec *elems, int nElems, size_t count, void **arrays, size_t extra = 0)
 {
     Carve k;
-    size_t at[GF_MAX_ELEMS];
-    carveElems(k, elems, nElems, count, at, extra);
+    size_t item[GF_MAX_ELEMS], at[GF_MAX_ELEMS];
+    for (int e = 0; e < nElems; e++) item[e] = elemItemBytes(elems[e].type);
+    k.each(nElems, count, item, at, extra);
     const gf_status s = b.ensure(k);
     for (int e = 0; e < nElems && s == GF_OK; e++) arrays[e] = b.at<void>(at[e]);
     return s;

@@ -99,38 +99,22 @@ gf_status gf_block_interp_points(gf_context *c, const gf_interp_spec *spec, cons
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
     // staging: block | rows | cols | spacings | z zx zy zxx zxy zyy | normal | status, the parts that the call has
-    const size_t blockBytes = (size_t)a.g.bRows * (size_t)a.g.bCols * (a.g.elemType == GF_ELEM_SHORT ? 2 : 4);
-    const size_t arr = roundUp(nPoints * 8, 16);
+    HostStage sg(c);
+    const int blockP = sg.in(block, (size_t)a.g.bRows * (size_t)a.g.bCols * (a.g.elemType == GF_ELEM_SHORT ? 2 : 4));
+    const int rowsP = sg.in(rows, nPoints * 8), colsP = sg.in(cols, nPoints * 8), csP = sg.in(colSpacing, nPoints * 8);
     double *const host[6] = {out->z, out->zx, out->zy, out->zxx, out->zxy, out->zyy};
-    Carve lay;
-    const size_t blockAt = lay.add(blockBytes), rowsAt = lay.add(arr), colsAt = lay.add(arr), csAt = lay.add(colSpacing ? arr : 0);
-    size_t devAt[6];
-    for (int k = 0; k < 6; k++) devAt[k] = lay.add(host[k] ? arr : 0);
-    const size_t normalAt = lay.add(out->normal ? 3 * arr : 0), statusAt = lay.add(out->status ? nPoints * 4 : 0);
-    if ((s = c->dInterp.ensure(lay)) != GF_OK) return s;
-    const DevBuf &B = c->dInterp;
-    uint8_t *dBlock = B.at<uint8_t>(blockAt);
-    double *dRows = B.at<double>(rowsAt), *dCols = B.at<double>(colsAt), *dCs = colSpacing ? B.at<double>(csAt) : nullptr;
-    double *dev[6];
-    for (int k = 0; k < 6; k++) dev[k] = host[k] ? B.at<double>(devAt[k]) : nullptr;
-    double *dNormal = out->normal ? B.at<double>(normalAt) : nullptr;
-    int32_t *dStatus = out->status ? B.at<int32_t>(statusAt) : nullptr;
-    GF_HIP(hipMemcpyAsync(dBlock, block, blockBytes, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(dRows, rows, nPoints * 8, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(dCols, cols, nPoints * 8, hipMemcpyHostToDevice, c->stream));
-    if (dCs) GF_HIP(hipMemcpyAsync(dCs, colSpacing, nPoints * 8, hipMemcpyHostToDevice, c->stream));
-    a.block = dBlock;
+    int devP[6];
+    for (int k = 0; k < 6; k++) devP[k] = sg.out(host[k], nPoints * 8);
+    const int normalP = sg.out(out->normal, nPoints * 24), statusP = sg.out(out->status, nPoints * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
+    a.block = sg.ptr<void>(blockP);
     a.nPoints = nPoints;
-    a.rows = dRows, a.cols = dCols, a.colSpacing = dCs;
-    a.z = dev[0], a.zx = dev[1], a.zy = dev[2], a.zxx = dev[3], a.zxy = dev[4], a.zyy = dev[5];
-    a.normal = dNormal, a.status = dStatus;
+    a.rows = sg.ptr<double>(rowsP), a.cols = sg.ptr<double>(colsP), a.colSpacing = sg.ptr<double>(csP);
+    a.z = sg.ptr<double>(devP[0]), a.zx = sg.ptr<double>(devP[1]), a.zy = sg.ptr<double>(devP[2]);
+    a.zxx = sg.ptr<double>(devP[3]), a.zxy = sg.ptr<double>(devP[4]), a.zyy = sg.ptr<double>(devP[5]);
+    a.normal = sg.ptr<double>(normalP), a.status = sg.ptr<int32_t>(statusP);
     GF_HIP(gf_launch_interp(a, c->stream));
-    for (int k = 0; k < 6; k++)
-        if (host[k]) GF_HIP(hipMemcpyAsync(host[k], dev[k], nPoints * 8, hipMemcpyDeviceToHost, c->stream));
-    if (dNormal) GF_HIP(hipMemcpyAsync(out->normal, dNormal, nPoints * 24, hipMemcpyDeviceToHost, c->stream));
-    if (dStatus) GF_HIP(hipMemcpyAsync(out->status, dStatus, nPoints * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    return sg.end();
 }
 
 }  // extern "C"

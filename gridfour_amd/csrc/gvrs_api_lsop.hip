@@ -291,40 +291,28 @@ gf_status gf_lsop12_encode_batch_i32(gf_context *c, int codecIndex, int nRows, i
     const size_t nRes = gf_lsop12_residual_count(nRows, nCols), resStride = roundUp(nRes, 4);
     const size_t nInit = (size_t)4 * nRows + 2 * nCols - 9, nInt = nRes - nInit;
     const size_t stride = gf_lsop12_max_packing(nRows, nCols);
-    gf_status s;
-    if ((s = c->dValues.ensure(nTiles * cells * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dSlots.ensure(nTiles * stride + 16)) != GF_OK) return s;
-    if ((s = c->dLengths.ensure(nTiles * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure(nTiles * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dStatus2.ensure(nTiles * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dResiduals.ensure(nTiles * resStride * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dCoefs.ensure(nTiles * 64 + 16)) != GF_OK) return s;
-    GF_HIP(hipMemcpyAsync(c->dValues.p, values, nTiles * cells * 4, hipMemcpyHostToDevice, c->stream));
     // deflateEnabled carries LsEncoder12's two switches as bits: GF_LSOP_DEFLATE (setDeflateEnabled) and GF_LSOP_VALUE_CHECKSUM
     // (setValueChecksumEnabled); any other bit was refused above
     const bool valueChecksum = (deflateEnabled & GF_LSOP_VALUE_CHECKSUM) != 0;
     deflateEnabled &= GF_LSOP_DEFLATE;
     const size_t hdrCanon = valueChecksum ? 59 : 55, hdrDeflate = valueChecksum ? 67 : 63;
-    s = lsopEncodeBatchDev(c, c->stream, codecIndex, nRows, nCols, nTiles, (const int32_t *)c->dValues.p,
-                           valueChecksum ? GF_LSOP_VALUE_CHECKSUM : 0, deflateEnabled != 0, (uint8_t *)c->dSlots.p, stride,
-                           (uint32_t *)c->dLengths.p, (int32_t *)c->dStatus.p, (int32_t *)c->dResiduals.p, resStride,
-                           (uint32_t *)c->dCoefs.p, (int32_t *)c->dStatus2.p);
-    if (s != GF_OK) return s;
-    std::vector<uint32_t> lengths(nTiles);
-    std::vector<int32_t> st(nTiles);
+    // staging: values | slots | lengths | statuses | residuals | coefficients (the two come home for the host's Deflate alone) | the
+    // second status
+    std::vector<uint32_t> lengths(nTiles), coefs(deflateEnabled ? nTiles * 16 : 0);
+    std::vector<int32_t> st(nTiles), res(deflateEnabled ? nTiles * resStride : 0);
     std::vector<uint8_t> slots(nTiles * stride);
-    GF_HIP(hipMemcpyAsync(lengths.data(), c->dLengths.p, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(st.data(), c->dStatus.p, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(slots.data(), c->dSlots.p, nTiles * stride, hipMemcpyDeviceToHost, c->stream));
-    std::vector<int32_t> res;
-    std::vector<uint32_t> coefs;
-    if (deflateEnabled) {
-        res.resize(nTiles * resStride);
-        coefs.resize(nTiles * 16);
-        GF_HIP(hipMemcpyAsync(res.data(), c->dResiduals.p, nTiles * resStride * 4, hipMemcpyDeviceToHost, c->stream));
-        GF_HIP(hipMemcpyAsync(coefs.data(), c->dCoefs.p, nTiles * 64, hipMemcpyDeviceToHost, c->stream));
-    }
-    GF_HIP(hipStreamSynchronize(c->stream));
+    HostStage sg(c);
+    const int valuesP = sg.in(values, nTiles * cells * 4), slotsP = sg.out(slots.data(), nTiles * stride);
+    const int lengthsP = sg.out(lengths.data(), nTiles * 4), statusP = sg.out(st.data(), nTiles * 4);
+    const int resP = deflateEnabled ? sg.out(res.data(), nTiles * resStride * 4) : sg.local(nTiles * resStride * 4);
+    const int coefsP = deflateEnabled ? sg.out(coefs.data(), nTiles * 64) : sg.local(nTiles * 64);
+    const int status2P = sg.local(nTiles * 4);
+    gf_status s = sg.begin();
+    if (s != GF_OK) return s;
+    s = lsopEncodeBatchDev(c, c->stream, codecIndex, nRows, nCols, nTiles, sg.ptr<int32_t>(valuesP), valueChecksum ? GF_LSOP_VALUE_CHECKSUM : 0,
+                           deflateEnabled != 0, sg.ptr<uint8_t>(slotsP), stride, sg.ptr<uint32_t>(lengthsP), sg.ptr<int32_t>(statusP),
+                           sg.ptr<int32_t>(resP), resStride, sg.ptr<uint32_t>(coefsP), sg.ptr<int32_t>(status2P));
+    if (s != GF_OK || (s = sg.end()) != GF_OK) return s;
 
     std::vector<std::vector<uint8_t>> alt(nTiles);          // Deflate container where it wins
     if (deflateEnabled) {
@@ -385,33 +373,21 @@ gf_status gf_lsop12_decode_batch_i32(gf_context *c, int nRows, int nCols, size_t
     }
     const size_t cells = (size_t)nRows * (size_t)nCols;
     const size_t nRes = gf_lsop12_residual_count(nRows, nCols), resStride = roundUp(nRes, 4);
+    // staging: blob | offsets | lengths | values | statuses | residuals | coefficients | the second status
     std::vector<uint32_t> lengths(nTiles);
-    for (size_t t = 0; t < nTiles; t++) lengths[t] = (uint32_t)(offsets[t + 1] - offsets[t]);
-    const uint8_t *gpuBlob = blob;
-    const uint64_t *gpuOffsets = offsets;
-    const uint64_t total = gpuOffsets[nTiles];
-
-    gf_status s;
-    if ((s = c->dBlob.ensure(total + 32)) != GF_OK) return s;
-    if ((s = c->dValues.ensure(nTiles * cells * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dLengths.ensure(nTiles * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure(nTiles * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dStatus2.ensure(nTiles * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dOffsets.ensure((nTiles + 1) * 8 + 16)) != GF_OK) return s;
-    if ((s = c->dResiduals.ensure(nTiles * resStride * 4 + 16)) != GF_OK) return s;
-    if ((s = c->dCoefs.ensure(nTiles * 64 + 16)) != GF_OK) return s;
-    GF_HIP(hipMemcpyAsync(c->dBlob.p, gpuBlob, total, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(c->dOffsets.p, gpuOffsets, (nTiles + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(c->dLengths.p, lengths.data(), nTiles * 4, hipMemcpyHostToDevice, c->stream));
-    s = gf_lsop12_decode_batch_i32_dev(c, c->stream, nRows, nCols, nTiles, (const uint8_t *)c->dBlob.p, total,
-                                       (const uint64_t *)c->dOffsets.p, 0, (const uint32_t *)c->dLengths.p, (int32_t *)c->dValues.p,
-                                       (int32_t *)c->dStatus.p, (int32_t *)c->dResiduals.p, resStride, (uint32_t *)c->dCoefs.p,
-                                       (int32_t *)c->dStatus2.p);
-    if (s != GF_OK) return s;
     std::vector<int32_t> st(nTiles);
-    GF_HIP(hipMemcpyAsync(values, c->dValues.p, nTiles * cells * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(st.data(), c->dStatus.p, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
+    for (size_t t = 0; t < nTiles; t++) lengths[t] = (uint32_t)(offsets[t + 1] - offsets[t]);
+    const size_t total = (size_t)offsets[nTiles];
+    HostStage sg(c);
+    const int blobP = sg.in(blob, total, 32), offsetsP = sg.in(offsets, (nTiles + 1) * 8), lengthsP = sg.in(lengths.data(), nTiles * 4);
+    const int valuesP = sg.out(values, nTiles * cells * 4), statusP = sg.out(st.data(), nTiles * 4);
+    const int resP = sg.local(nTiles * resStride * 4), coefsP = sg.local(nTiles * 64), status2P = sg.local(nTiles * 4);
+    gf_status s = sg.begin();
+    if (s != GF_OK) return s;
+    s = gf_lsop12_decode_batch_i32_dev(c, c->stream, nRows, nCols, nTiles, sg.ptr<uint8_t>(blobP), total, sg.ptr<uint64_t>(offsetsP), 0,
+                                       sg.ptr<uint32_t>(lengthsP), sg.ptr<int32_t>(valuesP), sg.ptr<int32_t>(statusP), sg.ptr<int32_t>(resP),
+                                       resStride, sg.ptr<uint32_t>(coefsP), sg.ptr<int32_t>(status2P));
+    if (s != GF_OK || (s = sg.end()) != GF_OK) return s;
     if (status) memcpy(status, st.data(), nTiles * 4);
     return GF_OK;
 }

@@ -233,35 +233,23 @@ gf_status gf_tile_record_decode_batch_elems(gf_context *c, const int *codecs, in
     gf_status s = elemsArgs(c, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, blob, false, offsets, values, status);
     if (s != GF_OK || nTiles == 0) return s;
     GF_CTX_LOCK(c);
-    const size_t cells = (size_t)nRows * (size_t)nCols, nInst = (size_t)nElems * nTiles;
+    const size_t cells = (size_t)nRows * (size_t)nCols;
     if (cells >= (1ull << 28)) return GF_ERR_UNSUPPORTED;
     GF_HIP(hipSetDevice(c->device));
     const size_t blobBytes = (size_t)offsets[nTiles];
-    // staging: blob | offsets | values of element 0, 1, ... | statuses, tile indices
-    Carve vals, stat;
-    size_t at[GF_MAX_ELEMS];
-    carveElems(vals, elems, nElems, nTiles * cells, at);
-    const size_t valueBytes = vals.total, statusAt = stat.add(nInst * 4), indicesAt = stat.add(nTiles * 4);
-    if ((s = c->dBlob.ensure(blobBytes + 32)) != GF_OK) return s;
-    if ((s = c->dOffsets.ensure((nTiles + 1) * 8 + 16)) != GF_OK) return s;
-    if ((s = c->dValues.ensure(vals)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure(stat)) != GF_OK) return s;
-    int32_t *dStatus = c->dStatus.at<int32_t>(statusAt), *dIndices = c->dStatus.at<int32_t>(indicesAt);
+    // staging: blob | offsets | values of element 0, 1, ..., zeroed (an element that fails reads as zeros, not as an earlier call) |
+    // statuses | tile indices (a failed record keeps the caller's entry)
+    HostStage sg(c);
+    int valueP[GF_MAX_ELEMS];
+    const int blobP = sg.in(blob, blobBytes, 32), offsetsP = sg.in(offsets, (nTiles + 1) * 8);
+    stageElems(sg, STAGE_OUT | STAGE_ZERO, elems, nElems, nTiles * cells, values, valueP);
+    const int statusP = sg.out(status, (size_t)nElems * nTiles * 4), indicesP = sg.inout(tileIndices, nTiles * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
     void *dValues[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) dValues[e] = c->dValues.at<void>(at[e]);
-    GF_HIP(hipMemcpyAsync(c->dBlob.p, blob, blobBytes, hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(c->dOffsets.p, offsets, (nTiles + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (tileIndices) GF_HIP(hipMemcpyAsync(dIndices, tileIndices, nTiles * 4, hipMemcpyHostToDevice, c->stream));   // (a failed record keeps the caller's entry)
-    GF_HIP(hipMemsetAsync(c->dValues.p, 0, valueBytes, c->stream));               // (an element that fails reads as zeros, not as an earlier batch)
-    s = recordsDecodeDev(c, c->stream, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, (const uint8_t *)c->dBlob.p, blobBytes,
-                         (const uint64_t *)c->dOffsets.p, nullptr, verifyChecksum, tileIndices ? dIndices : nullptr, dValues, dStatus);
-    if (s != GF_OK) return s;
-    for (int e = 0; e < nElems; e++)
-        GF_HIP(hipMemcpyAsync(values[e], dValues[e], nTiles * cells * elemItemBytes(elems[e].type), hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(status, dStatus, nInst * 4, hipMemcpyDeviceToHost, c->stream));
-    if (tileIndices) GF_HIP(hipMemcpyAsync(tileIndices, dIndices, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    sg.ptrs(valueP, nElems, dValues);
+    s = recordsDecodeDev(c, c->stream, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, sg.ptr<uint8_t>(blobP), blobBytes,
+                         sg.ptr<uint64_t>(offsetsP), nullptr, verifyChecksum, sg.ptr<int32_t>(indicesP), dValues, sg.ptr<int32_t>(statusP));
+    return s != GF_OK ? s : sg.end();
 }
 
 }  // extern "C"

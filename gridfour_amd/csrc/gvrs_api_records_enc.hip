@@ -291,36 +291,27 @@ gf_status gf_tile_record_encode_batch_elems(gf_context *c, const int *codecs, in
     if (!deviceList(codecs, nCodecs, elems, nElems))
         return recordsEncodeHost(c, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, tileIndices, values, checksumEnabled, blob, blobCap,
                                  offsets, codecUsed);
-    // staged through buffers of the context and sent through the device form: values of element 0, 1, ... (four spare bytes behind
-    // each) | the blob at its largest | offsets | tile indices, statuses | codec_used
+    // staged and sent through the device form: values of element 0, 1, ... (four spare bytes behind each) | tile indices | the blob at
+    // its largest | offsets | statuses | codec_used; the offsets say how much of the blob counts
     GF_HIP(hipSetDevice(c->device));
-    const size_t cells = (size_t)nRows * (size_t)nCols, nInst = (size_t)nElems * nTiles;
-    Carve stat;
-    void *dValues[GF_MAX_ELEMS];
-    const size_t indicesAt = stat.add(nTiles * 4), statusAt = stat.add(nTiles * 4);
+    const size_t cells = (size_t)nRows * (size_t)nCols;
     const size_t maxBlob = nTiles * gf_tile_record_max_bytes_elems(elems, nElems, nRows, nCols);
-    if ((s = elemArrays(c->dValues, elems, nElems, nTiles * cells, dValues, 4)) != GF_OK) return s;
-    if ((s = c->dBlob.ensure(maxBlob + 32)) != GF_OK) return s;
-    if ((s = c->dOffsets.ensure((nTiles + 1) * 8 + 16)) != GF_OK) return s;
-    if ((s = c->dStatus.ensure(stat, 32)) != GF_OK) return s;
-    if ((s = c->dPred.ensure(nInst + 16)) != GF_OK) return s;
-    int32_t *dIndices = c->dStatus.at<int32_t>(indicesAt), *dStatus = c->dStatus.at<int32_t>(statusAt);
-    for (int e = 0; e < nElems; e++)
-        GF_HIP(hipMemcpyAsync(dValues[e], values[e], nTiles * cells * elemItemBytes(elems[e].type), hipMemcpyHostToDevice, c->stream));
-    GF_HIP(hipMemcpyAsync(dIndices, tileIndices, nTiles * 4, hipMemcpyHostToDevice, c->stream));
-    s = recordsEncodeDev(c, c->stream, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, dIndices, dValues, checksumEnabled,
-                         (uint8_t *)c->dBlob.p, maxBlob, (uint64_t *)c->dOffsets.p, (uint8_t *)c->dPred.p, dStatus);
-    if (s != GF_OK) return s;
     std::vector<int32_t> status(nTiles);
-    GF_HIP(hipMemcpyAsync(offsets, c->dOffsets.p, (nTiles + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(status.data(), dStatus, nTiles * 4, hipMemcpyDeviceToHost, c->stream));
-    if (codecUsed) GF_HIP(hipMemcpyAsync(codecUsed, c->dPred.p, nInst, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
+    HostStage sg(c);
+    int valueP[GF_MAX_ELEMS];
+    stageElems(sg, STAGE_IN, elems, nElems, nTiles * cells, values, valueP, 4);
+    const int indicesP = sg.in(tileIndices, nTiles * 4), blobP = sg.held(blob, maxBlob), offsetsP = sg.out(offsets, (nTiles + 1) * 8);
+    const int statusP = sg.out(status.data(), nTiles * 4), usedP = sg.out(codecUsed, (size_t)nElems * nTiles);
+    if ((s = sg.begin()) != GF_OK) return s;
+    void *dValues[GF_MAX_ELEMS];
+    sg.ptrs(valueP, nElems, dValues);
+    s = recordsEncodeDev(c, c->stream, codecs, nCodecs, elems, nElems, nRows, nCols, nTiles, sg.ptr<int32_t>(indicesP), dValues, checksumEnabled,
+                         sg.ptr<uint8_t>(blobP), maxBlob, sg.ptr<uint64_t>(offsetsP), sg.ptr<uint8_t>(usedP), sg.ptr<int32_t>(statusP));
+    if (s != GF_OK || (s = sg.flush()) != GF_OK) return s;
     for (size_t t = 0; t < nTiles; t++)
         if (status[t] < 0) return (gf_status)status[t];                          // an encoder threw: the Java call fails as a whole
     if (offsets[nTiles] > blobCap) return GF_ERR_CAPACITY;
-    GF_HIP(hipMemcpy(blob, c->dBlob.p, (size_t)offsets[nTiles], hipMemcpyDeviceToHost));
-    return GF_OK;
+    return (s = sg.fetch(blobP, (size_t)offsets[nTiles])) != GF_OK ? s : sg.end();
 }
 
 }  // extern "C"

@@ -266,24 +266,15 @@ gf_status gf_block_render_lattice(gf_context *c, const gf_interp_spec *spec, con
     if (palette->device != c->device) return GF_ERR_ARG;
     // staging: block | argb | shade | status, the parts that the call has
     const size_t n = a.ip.nPoints;
-    const size_t blockBytes = (size_t)a.ip.g.bRows * (size_t)a.ip.g.bCols * (a.ip.g.elemType == GF_ELEM_SHORT ? 2 : 4);
-    Carve lay;
-    const size_t blockAt = lay.add(blockBytes), argbAt = lay.add(out->argb ? n * 4 : 0), shadeAt = lay.add(out->shade ? n * 8 : 0),
-                 statusAt = lay.add(out->status ? n * 4 : 0);
-    if ((s = c->dRender.ensure(lay)) != GF_OK) return s;
-    const DevBuf &B = c->dRender;
-    GF_HIP(hipMemcpyAsync(B.at<uint8_t>(blockAt), block, blockBytes, hipMemcpyHostToDevice, c->stream));
+    HostStage sg(c);
+    const int blockP = sg.in(block, (size_t)a.ip.g.bRows * (size_t)a.ip.g.bCols * (a.ip.g.elemType == GF_ELEM_SHORT ? 2 : 4));
+    const int argbP = sg.out(out->argb, n * 4), shadeP = sg.out(out->shade, n * 8), statusP = sg.out(out->status, n * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
     palOf(palette, flags, a.pal);
-    a.ip.block = B.at<uint8_t>(blockAt);
-    a.argb = out->argb ? B.at<uint32_t>(argbAt) : nullptr;
-    a.shade = out->shade ? B.at<double>(shadeAt) : nullptr;
-    a.status = out->status ? B.at<int32_t>(statusAt) : nullptr;
+    a.ip.block = sg.ptr<void>(blockP);
+    a.argb = sg.ptr<uint32_t>(argbP), a.shade = sg.ptr<double>(shadeP), a.status = sg.ptr<int32_t>(statusP);
     GF_HIP(gf_launch_render(a, c->stream));
-    if (a.argb) GF_HIP(hipMemcpyAsync(out->argb, a.argb, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (a.shade) GF_HIP(hipMemcpyAsync(out->shade, a.shade, n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (a.status) GF_HIP(hipMemcpyAsync(out->status, a.status, n * 4, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    return sg.end();
 }
 
 }  // extern "C"

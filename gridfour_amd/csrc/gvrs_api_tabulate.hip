@@ -146,24 +146,15 @@ gf_status gf_block_tabulate_dense(gf_context *c, int elemType, int32_t fillI, in
     if (s != GF_OK) return s;
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
-    // staging: block | counters | summary
-    const size_t blockBytes = (size_t)nCells * tabItemBytes(elemType), binBytes = (size_t)plan.n_bins * 4;
-    Carve k;
-    const size_t atBlock = k.add(blockBytes), atCounter = k.add(binBytes), atSummary = k.add(sizeof(gf_tab_summary));
-    if ((s = c->dTabStage.ensure(k)) != GF_OK) return s;
-    void *dBlock = c->dTabStage.at<void>(atBlock);
-    int32_t *dCounter = c->dTabStage.at<int32_t>(atCounter);
-    gf_tab_summary *dSummary = c->dTabStage.at<gf_tab_summary>(atSummary);
-    if (blockBytes) GF_HIP(hipMemcpyAsync(dBlock, block, blockBytes, hipMemcpyHostToDevice, c->stream));
-    if (flags & GF_TAB_ACCUMULATE) {
-        GF_HIP(hipMemcpyAsync(dCounter, counter, binBytes, hipMemcpyHostToDevice, c->stream));
-        GF_HIP(hipMemcpyAsync(dSummary, summary, sizeof(gf_tab_summary), hipMemcpyHostToDevice, c->stream));
-    }
-    if ((s = denseLaunch(c, c->stream, elemType, fillI, flags, dBlock, nCells, firstCell, plan, dCounter, dSummary)) != GF_OK) return s;
-    GF_HIP(hipMemcpyAsync(counter, dCounter, binBytes, hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipMemcpyAsync(summary, dSummary, sizeof(gf_tab_summary), hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
-    return GF_OK;
+    // staging: block | counters | summary (what an accumulating call adds to goes in first)
+    const unsigned both = (flags & GF_TAB_ACCUMULATE) ? STAGE_IN | STAGE_OUT : STAGE_OUT;
+    HostStage sg(c);
+    const int blockP = sg.in(block, (size_t)nCells * tabItemBytes(elemType));
+    const int counterP = sg.add(counter, (size_t)plan.n_bins * 4, both), summaryP = sg.add(summary, sizeof(gf_tab_summary), both);
+    if ((s = sg.begin()) != GF_OK) return s;
+    s = denseLaunch(c, c->stream, elemType, fillI, flags, sg.ptr<void>(blockP), nCells, firstCell, plan, sg.ptr<int32_t>(counterP),
+                    sg.ptr<gf_tab_summary>(summaryP));
+    return s != GF_OK ? s : sg.end();
 }
 
 gf_status gf_block_tabulate_symbols_dev(gf_context *c, void *stream, int elemType, const void *dBlock, int64_t nCells, uint32_t *dSymbols,
@@ -183,25 +174,20 @@ gf_status gf_block_tabulate_symbols(gf_context *c, int elemType, const void *blo
     if (s != GF_OK) return s;
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
-    // staging: block | symbols | counts | summary (a table holds n_cells entries at most)
-    const size_t blockBytes = (size_t)nCells * tabItemBytes(elemType), cap = std::min(tableCap, (size_t)nCells);
-    Carve k;
-    const size_t atBlock = k.add(blockBytes), atSymbols = k.add(cap * 4), atCounts = k.add(cap * 4), atSummary = k.add(sizeof(gf_tab_symbols));
-    if ((s = c->dTabStage.ensure(k)) != GF_OK) return s;
-    void *dBlock = c->dTabStage.at<void>(atBlock);
-    uint32_t *dSymbols = c->dTabStage.at<uint32_t>(atSymbols);
-    int32_t *dCounts = c->dTabStage.at<int32_t>(atCounts);
-    gf_tab_symbols *dSummary = c->dTabStage.at<gf_tab_symbols>(atSummary);
-    if (blockBytes) GF_HIP(hipMemcpyAsync(dBlock, block, blockBytes, hipMemcpyHostToDevice, c->stream));
-    if ((s = symbolsLaunch(c, c->stream, elemType, dBlock, nCells, dSymbols, dCounts, cap, dSummary)) != GF_OK) return s;
+    // staging: block | symbols | counts | summary (a table holds n_cells entries at most); the summary says how much of the table counts
+    const size_t cap = std::min(tableCap, (size_t)nCells);
     gf_tab_symbols got{};
-    GF_HIP(hipMemcpyAsync(&got, dSummary, sizeof(got), hipMemcpyDeviceToHost, c->stream));
-    GF_HIP(hipStreamSynchronize(c->stream));
+    HostStage sg(c);
+    const int blockP = sg.in(block, (size_t)nCells * tabItemBytes(elemType));
+    const int symbolsP = sg.held(symbols, cap * 4), countsP = sg.held(counts, cap * 4), summaryP = sg.out(&got, sizeof(got));
+    if ((s = sg.begin()) != GF_OK) return s;
+    s = symbolsLaunch(c, c->stream, elemType, sg.ptr<void>(blockP), nCells, sg.ptr<uint32_t>(symbolsP), sg.ptr<int32_t>(countsP), cap,
+                      sg.ptr<gf_tab_symbols>(summaryP));
+    if (s != GF_OK || (s = sg.flush()) != GF_OK) return s;
     got.n_written = std::min<int64_t>(got.n_symbols, (int64_t)tableCap);
     if (got.n_written > 0) {
-        GF_HIP(hipMemcpyAsync(symbols, dSymbols, (size_t)got.n_written * 4, hipMemcpyDeviceToHost, c->stream));
-        GF_HIP(hipMemcpyAsync(counts, dCounts, (size_t)got.n_written * 4, hipMemcpyDeviceToHost, c->stream));
-        GF_HIP(hipStreamSynchronize(c->stream));
+        if ((s = sg.fetch(symbolsP, (size_t)got.n_written * 4)) != GF_OK || (s = sg.fetch(countsP, (size_t)got.n_written * 4)) != GF_OK) return s;
+        if ((s = sg.end()) != GF_OK) return s;
     }
     *summary = got;
     return got.n_symbols > (int64_t)tableCap ? GF_ERR_CAPACITY : GF_OK;
