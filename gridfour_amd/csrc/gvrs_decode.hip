@@ -901,8 +901,16 @@ __device__ __forceinline__ void pool_to_m32(DecShared &S, const uint32_t *pool, 
     }
 }
 
+// The 512- and 1,024-thread builds take this into the kernel: a call there costs the callee's saved registers a scratch frame (the
+// inliner did so by itself until the unrolled rows of the byte path grew the kernel past its threshold); the 256-thread build, with
+// two cursors a thread, keeps the call it always had.
+#if GF_DEC_THREADS >= 512
+#define GF_FAST_INLINE __forceinline__
+#else
+#define GF_FAST_INLINE
+#endif
 template <int OWNER>
-__device__ int32_t huffman_to_m32_fast(DecShared &S, const uint32_t *__restrict__ base32, uint32_t nW, uint32_t sh0,
+__device__ GF_FAST_INLINE int32_t huffman_to_m32_fast(DecShared &S, const uint32_t *__restrict__ base32, uint32_t nW, uint32_t sh0,
                                        uint32_t *txt, uint32_t pkWords, const uint16_t *lut2, const unsigned long long *leafCodeG,
                                        uint32_t textStart, uint32_t endBit, uint32_t nM32, uint8_t *m32, uint32_t *dbg,
                                        const uint32_t warmBits, const int diagLimit = 0, uint32_t *pool = nullptr, uint32_t poolBytes = 0,
@@ -2156,13 +2164,26 @@ __device__ __forceinline__ int32_t m32_to_tile(DecShared &S, M32Ptr m32, uint32_
 //   Differencing  v(r,c) = C(r) + SUM(j = 1..c) res(r,j)                                C(r) = column 0, a running sum from the seed
 //   Linear        v(r,c) = C(r) + c d1(r) + SUM(k = 2..c) SUM(j = 2..k) res(r,j)        d1(r) = v(r,1) - v(r,0): a double prefix sum
 //   Triangle      v(r,c) = C(r) + SUM(i = 0..r) SUM(j = 1..c) res(i,j)                  four accumulators running down the rows; what
-//                 the blocks above a wave's own add up to comes from a pre-pass over the bytes (column sums per block as pairs
-//                 of 16-bit fields, then one row-wise prefix sum per block), through LDS
+//                 the blocks above a wave's own add up to comes from a pre-pass over the bytes (the lane's four prefixes summed
+//                 down the block, then one row-wise prefix sum per block), through LDS
 // Stream layouts (the order the encoders emit, see gf_stream_cell): Differencing -- cell i is byte i - 1; Linear -- byte 0 is
 // (0,1), bytes 2r - 1 / 2r are (r,0) / (r,1), the interior of row r starts at 2 nR - 1 + r (nC - 2); Triangle -- row 0, then
 // column 0, then the interior of row r >= 1 at nC + nR - 2 + (r - 1)(nC - 1).
 // Scratch (over the dead decode tables): C(r), d1(r), the block sums.
+//
+// The in-lane sums are dot products (v_dot4_i32_i8: SUM of the signed bytes of one word times the signed bytes of another, plus an
+// accumulator, exact modulo 2^32): with the weight bytes (1,0,0,0), (1,1,0,0), (1,1,1,0), (1,1,1,1) one instruction widens the
+// bytes, sums a prefix of them and adds it to what the third operand holds; Linear's second prefix has the weights (2,1,0,0),
+// (3,2,1,0), (4,3,2,1).  Triangle sums down the rows FIRST (four accumulators of lane-local prefixes) and over the lanes SECOND:
+// the sum over the rows of the rows' exclusive lane prefixes is the exclusive lane prefix of the accumulated lane totals.
 constexpr uint32_t BYTE_MAX_COLS = 256;
+constexpr uint32_t BYTE_KEEP_ROWS = 16;                           // Triangle: a block of up to so many rows stays in registers
+constexpr uint32_t DOT_P1 = 0x00000001u, DOT_P2 = 0x00000101u, DOT_P3 = 0x00010101u, DOT_P4 = 0x01010101u;
+constexpr uint32_t DOT_G2 = 0x00000102u, DOT_G3 = 0x00010203u, DOT_G4 = 0x01020304u;
+__device__ __forceinline__ uint32_t gf_dot4(uint32_t x, uint32_t w, uint32_t c)
+{
+    return (uint32_t)__builtin_amdgcn_sdot4((int)x, (int)w, (int)c, false);
+}
 __device__ __forceinline__ bool byte_path_eligible(int model, uint32_t nR, uint32_t nC, uint32_t ldsM32Bytes)
 {
     const uint32_t RB = (nR + DEC_WAVES - 1u) / DEC_WAVES;
@@ -2215,68 +2236,95 @@ __device__ __forceinline__ void m32_bytes_rows(DecShared &S, const uint8_t *m32,
     // row 0 of Differencing / Triangle starts at byte "-1": lane 0's first word does not exist (its byte would be column 0)
     auto fetchRow0 = [&]() -> uint32_t { return __builtin_amdgcn_alignbyte(m32w[lane], lane ? m32w[lane - 1u] : 0u, 3u); };
     const bool peel = MODEL != 2 && r0 == 0u && r1 > 0u;         // (wave-uniform: wave 0)
-    const uint32_t keep0 = lane == 0u ? 0u : 0xFFFFFFFFu;        // lane 0: the residuals of column 0 (Linear: and 1) count as zero
-    uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;              // Triangle: SUM over the rows so far of the row prefixes
+    // lane 0: the residuals of column 0 (Linear: and 1) count as zero
+    const uint32_t keep = lane != 0u ? 0xFFFFFFFFu : MODEL == 2 ? 0xFFFF0000u : 0xFFFFFF00u;
+    // Triangle: SUM over the rows so far of the lane's own prefixes; what the lanes before it add is a scan of acc3 (below)
+    uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+    // Triangle, a block of at most BYTE_KEEP_ROWS rows: the pre-pass keeps the words it fetched (masked) for the rows below
+    const bool keepWords = MODEL == 3 && RB <= BYTE_KEEP_ROWS;
+    uint32_t xs[BYTE_KEEP_ROWS];
     if (MODEL == 3) {
         // ---- pre-pass: T[b][j] = SUM(rows r of block b) SUM(m = 1..j) res(r,m); the last block's is not needed
-        if (wave + 1u < (uint32_t)DEC_WAVES && r1 > r0) {
-            uint32_t ev = 0, od = 0;                              // bytes + 128 of columns j0, j0 + 2 / j0 + 1, j0 + 3 as 16-bit fields
+        const bool wantT = wave + 1u < (uint32_t)DEC_WAVES && r1 > r0;
+        uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+        uint32_t a4 = rowAt(peel ? 1u : r0) + jf + 4u;
+        if (keepWords) {
+#pragma unroll
+            for (uint32_t i = 0; i < BYTE_KEEP_ROWS; i++) {
+                xs[i] = 0u;
+                if (r0 + i < r1) {                                // (wave-uniform)
+                    if (i == 0u && peel) xs[i] = fetchRow0() & keep;
+                    else {
+                        xs[i] = fetch(a4) & keep;
+                        a4 += rowStep;
+                    }
+                    if (wantT) {
+                        t0 = gf_dot4(xs[i], DOT_P1, t0); t1 = gf_dot4(xs[i], DOT_P2, t1);
+                        t2 = gf_dot4(xs[i], DOT_P3, t2); t3 = gf_dot4(xs[i], DOT_P4, t3);
+                    }
+                }
+            }
+        } else if (wantT) {
             uint32_t r = r0;
             if (peel) {
-                const uint32_t y = fetchRow0() ^ 0x80808080u;
-                ev = y & 0x00FF00FFu;
-                od = (y >> 8) & 0x00FF00FFu;
+                const uint32_t y = fetchRow0() & keep;
+                t0 = gf_dot4(y, DOT_P1, t0); t1 = gf_dot4(y, DOT_P2, t1); t2 = gf_dot4(y, DOT_P3, t2); t3 = gf_dot4(y, DOT_P4, t3);
                 r = 1u;
             }
-            uint32_t a4 = rowAt(r) + jf + 4u;
             for (; r < r1; r++) {
-                const uint32_t y = fetch(a4) ^ 0x80808080u;
-                ev += y & 0x00FF00FFu;
-                od += (y >> 8) & 0x00FF00FFu;
+                const uint32_t y = fetch(a4) & keep;
+                t0 = gf_dot4(y, DOT_P1, t0); t1 = gf_dot4(y, DOT_P2, t1); t2 = gf_dot4(y, DOT_P3, t2); t3 = gf_dot4(y, DOT_P4, t3);
                 a4 += rowStep;
             }
-            const uint32_t bias = 128u * (r1 - r0);
-            const uint32_t c0 = ((ev & 0xFFFFu) - bias) & keep0, c1 = (od & 0xFFFFu) - bias, c2 = (ev >> 16) - bias, c3 = (od >> 16) - bias;
-            const uint32_t p1 = c0 + c1, p2 = p1 + c2, p3 = p2 + c3;
-            const uint32_t ex = gf_wave_incl_scan(p3) - p3;
+        }
+        if (wantT) {
+            const uint32_t ex = gf_wave_incl_scan(t3) - t3;
             if (j0 < TS) {
                 uint32_t *Tw = T + wave * TS + j0;
-                Tw[0] = ex + c0; Tw[1] = ex + p1; Tw[2] = ex + p2; Tw[3] = ex + p3;
+                Tw[0] = ex + t0; Tw[1] = ex + t1; Tw[2] = ex + t2; Tw[3] = ex + t3;
             }
         }
     }
     __syncthreads();                                              // C(r), d1(r), T are in place
     if (MODEL == 3 && j0 < TS) {
+        // the blocks above: T holds their sums WITH what the lanes before this one add, the accumulators start without it (the
+        // scan of acc3 gives it back row by row) -- that share is the last column of the lane before, T[..][j0 - 1]
+        uint32_t before = 0;
+#pragma unroll 1                                                  // (four blocks a turn cost 20 more registers while xs is live)
         for (uint32_t w = 0; w < wave; w++) {
             const uint32_t *Tw = T + w * TS + j0;
             acc0 += Tw[0]; acc1 += Tw[1]; acc2 += Tw[2]; acc3 += Tw[3];
+            before += lane ? Tw[-1] : 0u;
         }
+        acc0 -= before; acc1 -= before; acc2 -= before; acc3 -= before;
     }
     // ---- the rows
     const uint32_t nFull = nC >> 2, rem = nC & 3u;               // lanes that store four cells; cells of the lane behind them
     const bool full = lane < nFull, part = lane == nFull && rem != 0u;
     struct Quad { uint32_t q0, q1, q2, q3; };
-    auto sums = [&](uint32_t x, uint32_t left, uint32_t d1) -> Quad {
-        const uint32_t v0 = sx(x) & keep0, v1 = MODEL == 2 ? sx(x >> 8) & keep0 : sx(x >> 8), v2 = sx(x >> 16), v3 = (uint32_t)((int32_t)x >> 24);
-        const uint32_t p1 = v0 + v1, p2 = p1 + v2, p3 = p2 + v3;
-        const uint32_t ex = gf_wave_incl_scan(p3) - p3;
+    auto sums = [&](uint32_t x, uint32_t left, uint32_t d1) -> Quad {     // x: the lane's four bytes, masked with keep
         Quad q;
+        if (MODEL == 3) {
+            acc0 = gf_dot4(x, DOT_P1, acc0); acc1 = gf_dot4(x, DOT_P2, acc1); acc2 = gf_dot4(x, DOT_P3, acc2); acc3 = gf_dot4(x, DOT_P4, acc3);
+            const uint32_t in = gf_wave_incl_scan(acc3), ex = in - acc3;
+            q.q0 = acc0 + ex + left; q.q1 = acc1 + ex + left; q.q2 = acc2 + ex + left; q.q3 = in + left;
+            return q;
+        }
+        const uint32_t p3 = gf_dot4(x, DOT_P4, 0u);
+        const uint32_t ex = gf_wave_incl_scan(p3) - p3;
         if (MODEL == 2) {
             // the second prefix sum: within the lane, then over the lanes (a lane before adds its own and four times what lay before it)
-            const uint32_t g1 = v0 + p1, g2 = g1 + p2, g3 = g2 + p3;
+            const uint32_t g3 = gf_dot4(x, DOT_G4, 0u);
             const uint32_t t = g3 + 4u * ex;
             const uint32_t gx = gf_wave_incl_scan(t) - t;
-            const uint32_t b = left + j0 * d1 + gx + ex;
-            q.q0 = b + v0;
-            q.q1 = b + d1 + ex + g1;
-            q.q2 = b + 2u * (d1 + ex) + g2;
-            q.q3 = b + 3u * (d1 + ex) + g3;
-        } else if (MODEL == 3) {
-            acc0 += ex + v0; acc1 += ex + p1; acc2 += ex + p2; acc3 += ex + p3;
-            q.q0 = acc0 + left; q.q1 = acc1 + left; q.q2 = acc2 + left; q.q3 = acc3 + left;
+            const uint32_t b = left + j0 * d1 + gx + ex, s = d1 + ex;
+            q.q0 = gf_dot4(x, DOT_P1, b);
+            q.q1 = gf_dot4(x, DOT_G2, b + s);
+            q.q2 = gf_dot4(x, DOT_G3, b + 2u * s);
+            q.q3 = b + 3u * s + g3;
         } else {
             const uint32_t b = left + ex;
-            q.q0 = b + v0; q.q1 = b + p1; q.q2 = b + p2; q.q3 = b + p3;
+            q.q0 = gf_dot4(x, DOT_P1, b); q.q1 = gf_dot4(x, DOT_P2, b); q.q2 = gf_dot4(x, DOT_P3, b); q.q3 = b + p3;
         }
         return q;
     };
@@ -2294,8 +2342,24 @@ __device__ __forceinline__ void m32_bytes_rows(DecShared &S, const uint8_t *m32,
         }
     };
     uint32_t r = r0;
-    if (peel) {
-        put(0u, sums(fetchRow0(), col0[0], 0u));
+    if (keepWords) {
+        // the block's words are in xs: two rows per turn as below, every turn predicated on its first row (wave-uniform)
+        const uint32_t last = r1 - 1u;
+#pragma unroll
+        for (uint32_t i = 0; i < BYTE_KEEP_ROWS; i += 2u) {
+            if (r0 + i < r1) {
+                const uint32_t rA = r0 + i, rB = min(rA + 1u, last);
+                const uint32_t lA = col0[rA], lB = col0[rB];
+                const Quad qa = sums(xs[i], lA, 0u);
+                const Quad qb = sums(xs[i + 1u], lB, 0u);         // (a zero word where the block has no row rA + 1)
+                put(rA, qa);
+                if (rA + 1u < r1) put(rA + 1u, qb);
+            }
+        }
+        r = r1;
+    }
+    if (peel && r < r1) {
+        put(0u, sums(fetchRow0() & keep, col0[0], 0u));
         r = 1u;
     }
     if (r < r1) {
@@ -2304,16 +2368,16 @@ __device__ __forceinline__ void m32_bytes_rows(DecShared &S, const uint8_t *m32,
         const uint32_t last = r1 - 1u;
         uint32_t a4 = rowAt(r) + jf + 4u, rB = min(r + 1u, last);
         uint32_t a4B = a4 + (rB - r) * rowStep;
-        uint32_t xA = fetch(a4), leftA = col0[r], dA = MODEL == 2 ? d1s[r] : 0u;
-        uint32_t xB = fetch(a4B), leftB = col0[rB], dB = MODEL == 2 ? d1s[rB] : 0u;
+        uint32_t xA = fetch(a4) & keep, leftA = col0[r], dA = MODEL == 2 ? d1s[r] : 0u;
+        uint32_t xB = fetch(a4B) & keep, leftB = col0[rB], dB = MODEL == 2 ? d1s[rB] : 0u;
         for (; r < r1; r += 2u) {
             const uint32_t x0 = xA, l0 = leftA, e0 = dA, x1 = xB, l1 = leftB, e1 = dB;
             const uint32_t nA = min(r + 2u, last), nB = min(r + 3u, last);
             a4 += (nA - r) * rowStep;
             a4B = a4 + (nB - nA) * rowStep;
-            xA = fetch(a4);
+            xA = fetch(a4) & keep;
             leftA = col0[nA];
-            xB = fetch(a4B);
+            xB = fetch(a4B) & keep;
             leftB = col0[nB];
             if (MODEL == 2) { dA = d1s[nA]; dB = d1s[nB]; }
             const Quad qa = sums(x0, l0, e0);

@@ -19,16 +19,16 @@
 #define REP4(x) x x x x
 #define REP16(x) REP4(x) REP4(x) REP4(x) REP4(x)
 
-enum { K_VADD = 0, K_VCMPSEL, K_VOP3, K_SADD, K_SCMP_NOT_TAKEN, K_SCMP_TAKEN, K_RFL_SALU, K_MIX_2V1S, K_MIX_1V1S, K_VDPP, K_COUNT };
+enum { K_VADD = 0, K_VCMPSEL, K_VOP3, K_SADD, K_SCMP_NOT_TAKEN, K_SCMP_TAKEN, K_RFL_SALU, K_MIX_2V1S, K_MIX_1V1S, K_VDPP, K_VDOT4, K_COUNT };
 static const char *kNames[K_COUNT] = {
     "v_add_u32 x8 independent",      "v_cmp_gt_u32 + v_cndmask_b32 pairs", "v_alignbit / v_bfe_u32 / v_lshl_or_b32 / v_mad_u32_u24",
     "s_add_u32 x8 independent",      "s_cmp_lg_u32 + s_cbranch_scc1 (not taken)", "s_cmp_eq_u32 + s_cbranch_scc1 (taken, to the next instruction)",
     "v_readfirstlane_b32 -> s_add_u32 (dependent)", "2 v_add_u32 : 1 s_add_u32 interleaved", "1 v_add_u32 : 1 s_add_u32 interleaved",
-    "v_add_u32_dpp row_shr:1 chain of 4 + s_nop 1 each"};
+    "v_add_u32_dpp row_shr:1 chain of 4 + s_nop 1 each", "v_dot4c_i32_i8 x8 independent"};
 // vector / scalar / branch instructions of ONE group of each kind
-static const int kVec[K_COUNT] = {8, 8, 8, 0, 0, 0, 4, 8, 4, 4};
-static const int kSca[K_COUNT] = {0, 0, 0, 8, 4, 4, 4, 4, 4, 4};
-static const int kBr[K_COUNT] = {0, 0, 0, 0, 4, 4, 0, 0, 0, 0};
+static const int kVec[K_COUNT] = {8, 8, 8, 0, 0, 0, 4, 8, 4, 4, 8};
+static const int kSca[K_COUNT] = {0, 0, 0, 8, 4, 4, 4, 4, 4, 4, 0};
+static const int kBr[K_COUNT] = {0, 0, 0, 0, 4, 4, 0, 0, 0, 0, 0};
 
 template <int KIND>
 __global__ __launch_bounds__(256) void k(uint32_t *out, int iters)
@@ -92,6 +92,10 @@ __global__ __launch_bounds__(256) void k(uint32_t *out, int iters)
                                "s_nop 1\n v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
                                "s_nop 1\n v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n")
                          : "+v"(a));
+        if (KIND == K_VDOT4)                 // the byte path's in-lane sums: the accumulating two-operand form the compiler emits
+            asm volatile(REP16("v_dot4c_i32_i8_e32 %0, %1, %1\n v_dot4c_i32_i8_e32 %2, %3, %3\n v_dot4c_i32_i8_e32 %4, %5, %5\n v_dot4c_i32_i8_e32 %6, %7, %7\n"
+                               "v_dot4c_i32_i8_e32 %1, %0, %0\n v_dot4c_i32_i8_e32 %3, %2, %2\n v_dot4c_i32_i8_e32 %5, %4, %4\n v_dot4c_i32_i8_e32 %7, %6, %6\n")
+                         : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
     }
     out[blockIdx.x * blockDim.x + threadIdx.x] = a + b + c + d + e + f + g + h + s0 + s1 + s2 + s3 + s4 + s5 + s6 + s7;
 }
@@ -144,7 +148,8 @@ int main()
             case K_RFL_SALU: ms = run<K_RFL_SALU>(d, blocks, iters); break;
             case K_MIX_2V1S: ms = run<K_MIX_2V1S>(d, blocks, iters); break;
             case K_MIX_1V1S: ms = run<K_MIX_1V1S>(d, blocks, iters); break;
-            default: ms = run<K_VDPP>(d, blocks, iters); break;
+            case K_VDPP: ms = run<K_VDPP>(d, blocks, iters); break;
+            default: ms = run<K_VDOT4>(d, blocks, iters); break;
             }
             // per wave: iters x (16 groups + the loop's s_add, s_cmp, s_cbranch)
             const double groups = (double)iters * 16.0;
