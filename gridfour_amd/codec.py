@@ -11,7 +11,11 @@ ICompressionDecoder.java:62-105, CodecHuffman.java:70-153):
 
 plus the batched forms the GPU needs (one launch per batch of tiles, not per tile).
 All compute happens in libgvrs_hip.so; nothing here has a CPU implementation.
+
+The module in order: constants and struct dtypes; helpers, DeviceBuffer and the device-call scope; GvrsHipContext and the objects
+made on one; the codec classes.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -19,346 +23,28 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 
+# ---- constants and struct dtypes (include/gvrs_hip_codec.h) ----
 INT4_NULL_CODE = -(2 ** 31)   # util/GridfourConstants.java:61
 
+CODEC_NONE, CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_CANON_HUFFMAN, CODEC_LSOP12 = 0, 1, 2, 3, 4
+STANDARD_CODEC_LIST = (CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_NONE, CODEC_CANON_HUFFMAN)    # GvrsFileSpecification.java:221-230
 
-def _blob_of(packings):
-    """(blob, offsets[n + 1]) of packings laid back to back, with 16 zero bytes behind the last: the kernels read whole aligned
-    words past a packing's end."""
-    offsets = np.zeros(len(packings) + 1, np.uint64)
-    offsets[1:] = np.cumsum([len(p) for p in packings])
-    return np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8), offsets
-
-
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-class GvrsHipContext:
-    """One device context (stream + workspace); one per process and GPU."""
-
-    def __init__(self, device=0):
-        self._h = C.c_void_p()
-        check(lib().gf_context_create(int(device), C.byref(self._h)), "gf_context_create")
-        self.device = int(device)
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def stream(self):
-        return lib().gf_context_stream(self._h)
-
-    def synchronize(self):
-        check(lib().gf_context_synchronize(self._h), "gf_context_synchronize")
-
-    def reserve(self, n_rows, n_cols, n_tiles):
-        check(lib().gf_context_reserve(self._h, n_rows, n_cols, n_tiles), "gf_context_reserve")
-
-    def block_from_tiles_dev(self, grid, rect, elem_type, fill_bits, n_tiles, d_tile_indices, d_tiles, d_block, d_tile_status=None,
-                             stream=None):
-        """gf_block_from_tiles_dev on device pointers: grid = (n_rows_grid, n_cols_grid, n_rows_tile, n_cols_tile), rect = (row0,
-        col0, n_rows, n_cols), elem_type one of ELEM_TYPES' values.  Enqueues only."""
-        grid, rect = np.ascontiguousarray(grid, np.int32), np.ascontiguousarray(rect, np.int32)
-        assert grid.size == 4 and rect.size == 4
-        check(lib().gf_block_from_tiles_dev(self._h, stream, _ptr(grid), _ptr(rect), int(elem_type),
-                                            int(fill_bits) & 0xffffffff, int(n_tiles), d_tile_indices, d_tile_status, d_tiles, d_block),
-              "gf_block_from_tiles_dev")
-
-    def tiles_from_block_dev(self, grid, rect, elem_type, fill_bits, d_block, n_tiles, d_tile_indices, d_tiles, d_status=None,
-                             keep_outside=False, stream=None):
-        """gf_tiles_from_block_dev on device pointers, the inverse of block_from_tiles_dev.  Enqueues only."""
-        grid, rect = np.ascontiguousarray(grid, np.int32), np.ascontiguousarray(rect, np.int32)
-        assert grid.size == 4 and rect.size == 4
-        check(lib().gf_tiles_from_block_dev(self._h, stream, _ptr(grid), _ptr(rect), int(elem_type),
-                                            int(fill_bits) & 0xffffffff, int(bool(keep_outside)), d_block, int(n_tiles), d_tile_indices,
-                                            d_tiles, d_status), "gf_tiles_from_block_dev")
-
-    # ---- a grid block interpolated: B-spline value, derivatives, unit normal (gf_block_interp_*) ----
-    @staticmethod
-    def _interp_out(out):
-        o = np.zeros(1, _INTERP_OUT)
-        for k, v in out.items():
-            o[k] = 0 if v is None else (v.value if isinstance(v, C.c_void_p) else int(v)) or 0
-        return o
-
-    def interp_points_dev(self, spec, d_block, n_points, d_rows, d_cols, out, d_col_spacing=None, stream=None):
-        """gf_block_interp_points_dev on device pointers: spec from interp_spec(), out a dict of device pointers under the names
-        z, zx, zy, zxx, zxy, zyy, normal (3 doubles per point), status (int32); all but z may be missing.  Enqueues only."""
-        o = self._interp_out(out)
-        check(lib().gf_block_interp_points_dev(self._h, stream, _ptr(spec), d_block, int(n_points), d_rows, d_cols, d_col_spacing, _ptr(o)),
-              "gf_block_interp_points_dev")
-
-    def interp_lattice_dev(self, spec, d_block, lattice, out, d_col_spacing_rows=None, stream=None):
-        """gf_block_interp_lattice_dev: lattice = (row0, col0, row_step, col_step, n_rows, n_cols); point (i, j) is row0 + i *
-        row_step, col0 + j * col_step; outputs row-major n_rows x n_cols; d_col_spacing_rows: one spacing per lattice row.
-        Enqueues only."""
-        lat = np.zeros(1, _INTERP_LATTICE)
-        lat["row0"], lat["col0"], lat["row_step"], lat["col_step"], lat["n_rows"], lat["n_cols"] = lattice
-        o = self._interp_out(out)
-        check(lib().gf_block_interp_lattice_dev(self._h, stream, _ptr(spec), d_block, _ptr(lat), d_col_spacing_rows, _ptr(o)),
-              "gf_block_interp_lattice_dev")
-
-    def interp_points(self, spec, block, rows, cols, col_spacing=None):
-        """gf_block_interp_points, the host-memory form (staged by the library): block is the rectangle spec["block"] of the raster
-        in the element's delivered dtype, rows / cols grid coordinates.  Returns a dict: z and status [n] always; zx, zy and normal
-        [n, 3] with target >= INTERP_FIRST; zxx, zxy, zyy with INTERP_SECOND.  A point whose status is not 0 is NaN throughout."""
-        rows, cols = np.ascontiguousarray(rows, np.float64).ravel(), np.ascontiguousarray(cols, np.float64).ravel()
-        assert rows.size == cols.size
-        n, target = rows.size, int(spec["target"][0])
-        dt = {0: np.int32, 1: np.int16, 2: np.float32, 3: np.float32}[int(spec["elem_type"][0])]
-        block = np.ascontiguousarray(block, dt)
-        assert block.size == int(spec["block"][0][2]) * int(spec["block"][0][3])
-        names = ["z"] + (["zx", "zy"] if target >= INTERP_FIRST else []) + (["zxx", "zxy", "zyy"] if target >= INTERP_SECOND else [])
-        res = {k: np.zeros(n, np.float64) for k in names}
-        if target >= INTERP_FIRST:
-            res["normal"] = np.zeros((n, 3), np.float64)
-        res["status"] = np.zeros(n, np.int32)
-        cs = None if col_spacing is None else np.ascontiguousarray(col_spacing, np.float64).ravel()
-        assert cs is None or cs.size == n
-        o = self._interp_out({k: a.ctypes.data for k, a in res.items()})
-        check(lib().gf_block_interp_points(self._h, _ptr(spec), _ptr(block), n, _ptr(rows), _ptr(cols), None if cs is None else _ptr(cs),
-                                           _ptr(o)), "gf_block_interp_points")
-        return res
-
-    # ---- a grid block rendered to ARGB: colour palette and shaded relief (gf_block_render_*) ----
-    @staticmethod
-    def _render_args(lattice, light, out):
-        lat = None
-        if lattice is not None:
-            lat = np.zeros(1, _INTERP_LATTICE)
-            lat["row0"], lat["col0"], lat["row_step"], lat["col_step"], lat["n_rows"], lat["n_cols"] = lattice
-        o = np.zeros(1, _RENDER_OUT)
-        for k, v in out.items():
-            o[k] = 0 if v is None else (v.value if isinstance(v, C.c_void_p) else int(v)) or 0
-        return lat, (None if light is None else np.ascontiguousarray(light, _RENDER_LIGHT).reshape(1)), o
-
-    def render_cells_dev(self, palette, elem_type, d_cells, n_cells, d_argb, d_shade=None, fill_i=0, unlimited=False, stream=None):
-        """gf_block_render_cells_dev on device pointers: n_cells cells of the element ("int", "short", "float", "icf", GF_ELEM_*, or
-        "z" / RENDER_Z: doubles) -> d_argb [n_cells] int32; d_shade: one double per cell (the WithShade lookups).  Enqueues only."""
-        et = RENDER_Z if elem_type == "z" else ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
-        check(lib().gf_block_render_cells_dev(self._h, stream, palette.handle, RENDER_UNLIMITED if unlimited else 0, et, int(fill_i), d_cells,
-                                              int(n_cells), d_shade, d_argb), "gf_block_render_cells_dev")
-
-    def render_lattice_dev(self, spec, d_block, lattice, palette, out, light=None, unlimited=False, stream=None):
-        """gf_block_render_lattice_dev: spec and lattice as interp_lattice_dev takes them, light from render_light() (None: the
-        value alone, no shade), out a dict of device pointers under the names argb (int32), shade (double), status (int32), each
-        one item per pixel; argb or shade must be there.  Enqueues only."""
-        lat, li, o = self._render_args(lattice, light, out)
-        check(lib().gf_block_render_lattice_dev(self._h, stream, _ptr(spec), d_block, _ptr(lat), palette.handle, None if li is None else _ptr(li),
-                                                RENDER_UNLIMITED if unlimited else 0, _ptr(o)), "gf_block_render_lattice_dev")
-
-    def render_points_dev(self, spec, d_block, palette, out, lattice=None, n_points=0, d_rows=None, d_cols=None, d_col_spacing=None,
-                          light=None, unlimited=False, stream=None):
-        """gf_block_render_points_dev: with lattice, a lattice whose column spacing differs per row (d_col_spacing: one per lattice
-        row); without, n_points points d_rows, d_cols (d_col_spacing: one per point).  Enqueues only."""
-        lat, li, o = self._render_args(lattice, light, out)
-        check(lib().gf_block_render_points_dev(self._h, stream, _ptr(spec), d_block, None if lat is None else _ptr(lat), int(n_points), d_rows,
-                                               d_cols, d_col_spacing, palette.handle, None if li is None else _ptr(li),
-                                               RENDER_UNLIMITED if unlimited else 0, _ptr(o)), "gf_block_render_points_dev")
-
-    def render_lattice(self, spec, block, lattice, palette, light=None, unlimited=False):
-        """gf_block_render_lattice, the host-memory form (staged by the library): returns a dict argb [n_rows, n_cols] int32, status
-        the same, and shade (float64) with a light."""
-        dt = {0: np.int32, 1: np.int16, 2: np.float32, 3: np.float32}[int(spec["elem_type"][0])]
-        block = np.ascontiguousarray(block, dt)
-        assert block.size == int(spec["block"][0][2]) * int(spec["block"][0][3])
-        shape = (int(lattice[4]), int(lattice[5]))
-        res = {"argb": np.zeros(shape, np.int32), "status": np.zeros(shape, np.int32)}
-        if light is not None:
-            res["shade"] = np.zeros(shape, np.float64)
-        lat, li, o = self._render_args(lattice, light, {k: a.ctypes.data for k, a in res.items()})
-        check(lib().gf_block_render_lattice(self._h, _ptr(spec), _ptr(block), _ptr(lat), palette.handle, None if li is None else _ptr(li),
-                                            RENDER_UNLIMITED if unlimited else 0, _ptr(o)), "gf_block_render_lattice")
-        return res
-
-    # ---- a grid block downsampled: the box average by an integer factor (gf_block_downsample_*) ----
-    @staticmethod
-    def downsample_rect(block, factor):
-        """gf_block_downsample_rect: block = (row0, col0, n_rows, n_cols) on the source grid -> the rectangle of the coarse grid
-        whose cells' whole factor x factor windows lie inside block (n_rows or n_cols may be 0)."""
-        block, out = np.ascontiguousarray(block, np.int32), np.zeros(4, np.int32)
-        assert block.size == 4
-        check(lib().gf_block_downsample_rect(_ptr(block), int(factor), _ptr(out)), "gf_block_downsample_rect")
-        return tuple(int(x) for x in out)
-
-    @staticmethod
-    def _downsample_specs(elems, fills):
-        """elems: a gf_elem_spec array as it is, or per element "int" | "short" | "float" with fills as read_block_dev takes them"""
-        if isinstance(elems, np.ndarray):
-            assert elems.dtype == _ELEM_SPEC and fills is None
-            return elems, [{0: np.int32, 1: np.int16}.get(int(t), np.float32) for t in elems["type"]]
-        specs, dtypes = CodecMasterHip._elem_specs(elems)
-        return CodecMasterHip._fill_specs(specs, elems, fills), dtypes
-
-    def downsample_dev(self, elems, block, factor, d_blocks, d_out, stream=None, fills=None):
-        """gf_block_downsample_elems_dev on device pointers: d_blocks[e] holds the rectangle block of element e (int32 / int16 /
-        float32, row-major), d_out[e] receives the cells of downsample_rect(block, factor).  Enqueues only."""
-        specs, _ = self._downsample_specs(elems, fills)
-        ne = len(specs)
-        assert len(d_blocks) == ne and len(d_out) == ne
-        val = lambda p: p.value if isinstance(p, C.c_void_p) else p
-        block = np.ascontiguousarray(block, np.int32)
-        check(lib().gf_block_downsample_elems_dev(self._h, stream, _ptr(specs), ne, _ptr(block), int(factor),
-                                                  (C.c_void_p * ne)(*[val(p) for p in d_blocks]), (C.c_void_p * ne)(*[val(p) for p in d_out])),
-              "gf_block_downsample_elems_dev")
-
-    def downsample(self, elems, block, factor, blocks, fills=None):
-        """gf_block_downsample_elems, the host-memory form (staged by the library): blocks[e] is the rectangle block of element e.
-        Returns one array [n_rows', n_cols'] per element in the element's dtype, for downsample_rect(block, factor)."""
-        specs, dtypes = self._downsample_specs(elems, fills)
-        ne = len(specs)
-        block = np.ascontiguousarray(block, np.int32)
-        blocks = [np.ascontiguousarray(b, dt) for b, dt in zip(blocks, dtypes)]
-        assert len(blocks) == ne and all(b.size == int(block[2]) * int(block[3]) for b in blocks)
-        _, _, n_rows, n_cols = self.downsample_rect(block, factor)
-        out = [np.zeros((n_rows, n_cols), dt) for dt in dtypes]
-        check(lib().gf_block_downsample_elems(self._h, _ptr(specs), ne, _ptr(block), int(factor),
-                                              (C.c_void_p * ne)(*[b.ctypes.data for b in blocks]),
-                                              (C.c_void_p * ne)(*[o.ctypes.data for o in out])), "gf_block_downsample_elems")
-        return out
-
-    # ---- a grid block tabulated: value counts, range and entropy (gf_block_tabulate_*, gf_tab_*) ----
-    @staticmethod
-    def tab_dense_plan(def_min, def_max, scale):
-        """gf_tab_dense_plan_of: InputDataStatCollector's constructor -> dict n_counter, base, n_bins, scale_used"""
-        plan = np.zeros(1, _TAB_DENSE_PLAN)
-        check(lib().gf_tab_dense_plan_of(_ptr(_tab_dense_spec(def_min, def_max, scale)), _ptr(plan)), "gf_tab_dense_plan_of")
-        return {k: plan[k][0].item() for k in plan.dtype.names}
-
-    def tabulate_dense_dev(self, elem_type, d_block, n_cells, def_min, def_max, scale, d_counter, d_summary, fill_i=0, skip_fill=False,
-                           accumulate=False, first_cell=0, stream=None):
-        """gf_block_tabulate_dense_dev on device pointers: n_cells cells of the element ("int", "short", "float" or GF_ELEM_*) ->
-        d_counter [tab_dense_plan(...)["n_bins"]] int32 and d_summary, one gf_tab_summary (TAB_SUMMARY).  Enqueues only."""
-        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
-        flags = (TAB_ACCUMULATE if accumulate else 0) | (TAB_SKIP_FILL if skip_fill else 0)
-        check(lib().gf_block_tabulate_dense_dev(self._h, stream, et, int(fill_i), flags, d_block, int(n_cells), int(first_cell),
-                                                _ptr(_tab_dense_spec(def_min, def_max, scale)), d_counter, d_summary), "gf_block_tabulate_dense_dev")
-
-    def tabulate_dense(self, elem_type, block, def_min, def_max, scale, fill_i=0, skip_fill=False, first_cell=0, into=None):
-        """gf_block_tabulate_dense, the host-memory form (staged by the library): returns (counter [n_bins] int32, summary dict).
-        into = (counter, summary) of an earlier call: accumulate onto them (a raster in strips, first_cell the strip's first cell)."""
-        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
-        block = np.ascontiguousarray(block, {0: np.int32, 1: np.int16}.get(et, np.float32)).ravel()
-        flags = (TAB_ACCUMULATE if into is not None else 0) | (TAB_SKIP_FILL if skip_fill else 0)
-        summary = np.zeros(1, TAB_SUMMARY)
-        if into is not None:
-            counter = np.ascontiguousarray(into[0], np.int32).copy()
-            for k in TAB_SUMMARY.names:
-                summary[k] = into[1][k]
-            assert counter.size == self.tab_dense_plan(def_min, def_max, scale)["n_bins"]
-        else:
-            counter = np.zeros(self.tab_dense_plan(def_min, def_max, scale)["n_bins"], np.int32)
-        check(lib().gf_block_tabulate_dense(self._h, et, int(fill_i), flags, _ptr(block), block.size, int(first_cell),
-                                            _ptr(_tab_dense_spec(def_min, def_max, scale)), _ptr(counter), _ptr(summary)), "gf_block_tabulate_dense")
-        return counter, {k: summary[k][0].item() for k in TAB_SUMMARY.names}
-
-    def tabulate_symbols_dev(self, elem_type, d_block, n_cells, d_symbols, d_counts, table_cap, d_summary, stream=None):
-        """gf_block_tabulate_symbols_dev on device pointers: the distinct 32-bit symbols of n_cells cells in ascending unsigned order
-        -> d_symbols [table_cap] uint32, d_counts [table_cap] int32 (both None with table_cap 0) and d_summary, one gf_tab_symbols
-        (TAB_SYMBOLS).  Enqueues only."""
-        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
-        check(lib().gf_block_tabulate_symbols_dev(self._h, stream, et, d_block, int(n_cells), d_symbols, d_counts, int(table_cap), d_summary),
-              "gf_block_tabulate_symbols_dev")
-
-    def tabulate_symbols(self, elem_type, block, table_cap=None):
-        """gf_block_tabulate_symbols, the host-memory form: returns (symbols uint32, counts int32, summary dict); table_cap None:
-        room for every cell.  A table that does not hold every symbol comes back with its first table_cap entries (summary
-        ["n_written"] of summary["n_symbols"])."""
-        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
-        block = np.ascontiguousarray(block, {0: np.int32, 1: np.int16}.get(et, np.float32)).ravel()
-        cap = block.size if table_cap is None else int(table_cap)
-        symbols, counts, summary = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int32), np.zeros(1, TAB_SYMBOLS)
-        st = lib().gf_block_tabulate_symbols(self._h, et, _ptr(block), block.size, _ptr(symbols) if cap else None, _ptr(counts) if cap else None,
-                                             cap, _ptr(summary))
-        if st != _lib.ERR_CAPACITY:
-            check(st, "gf_block_tabulate_symbols")
-        n = int(summary["n_written"][0])
-        return symbols[:n], counts[:n], {k: summary[k][0].item() for k in TAB_SYMBOLS.names}
-
-    @staticmethod
-    def tab_entropy(counts, n_samples, kahan=True):
-        """gf_tab_entropy_counts: bits per sample of a table of counts in the order given; kahan: EntropyTabulator's sum, else
-        InputDataStatCollector.getEntropy's"""
-        counts, e = np.ascontiguousarray(counts, np.int32).ravel(), C.c_double()
-        check(lib().gf_tab_entropy_counts(_ptr(counts), counts.size, int(n_samples), int(bool(kahan)), C.byref(e)), "gf_tab_entropy_counts")
-        return e.value
-
-    # ---- ARGB images as element planes and as overviews (gf_image_split / _join / _reduce) ----
-    @staticmethod
-    def _image_kind(model, elem_type):
-        model = IMAGE_MODELS[model] if isinstance(model, str) else int(model)
-        et = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else int(elem_type)
-        return model, et, (np.int16 if et == 1 else np.int32)
-
-    def image_split_dev(self, model, elem_type, n_pixels, d_argb, d_planes):
-        """gf_image_split_dev on device pointers: n_pixels ARGB words -> three planes (model "rgb": r, g, b; "ycocg": Y, Co, Cg) of
-        int32 ("int") or int16 ("short").  Runs on the context's stream; enqueues only."""
-        model, et, _ = self._image_kind(model, elem_type)
-        val = lambda p: p.value if isinstance(p, C.c_void_p) else p
-        assert len(d_planes) == 3
-        check(lib().gf_image_split_dev(self._h, model, et, int(n_pixels), d_argb, (C.c_void_p * 3)(*[val(p) for p in d_planes])),
-              "gf_image_split_dev")
-
-    def image_join_dev(self, model, elem_type, n_pixels, d_planes, d_argb):
-        """gf_image_join_dev, the inverse: three planes of any ints -> n_pixels ARGB words.  Enqueues only."""
-        model, et, _ = self._image_kind(model, elem_type)
-        val = lambda p: p.value if isinstance(p, C.c_void_p) else p
-        assert len(d_planes) == 3
-        check(lib().gf_image_join_dev(self._h, model, et, int(n_pixels), (C.c_void_p * 3)(*[val(p) for p in d_planes]), d_argb),
-              "gf_image_join_dev")
-
-    @staticmethod
-    def image_reduce_size(width, height, factor):
-        """gf_image_reduce_size: (width // factor, height // factor)"""
-        w, h = C.c_int(), C.c_int()
-        check(lib().gf_image_reduce_size(int(width), int(height), int(factor), C.byref(w), C.byref(h)), "gf_image_reduce_size")
-        return w.value, h.value
-
-    def image_reduce_dev(self, width, height, factor, d_argb, d_out):
-        """gf_image_reduce_dev: height rows of width ARGB words -> the image of image_reduce_size(...), each word the per-channel
-        box average of factor x factor pixels as DemoCOG.makeReducedImage rounds it.  Enqueues only."""
-        check(lib().gf_image_reduce_dev(self._h, int(width), int(height), int(factor), d_argb, d_out), "gf_image_reduce_dev")
-
-    def image_split(self, argb, model="ycocg", elem_type="short"):
-        """gf_image_split, the host-memory form (staged by the library): three planes in the shape of argb"""
-        model, et, dt = self._image_kind(model, elem_type)
-        argb = np.ascontiguousarray(argb).view(np.int32) if np.asarray(argb).dtype == np.uint32 else np.ascontiguousarray(argb, np.int32)
-        planes = [np.zeros(argb.shape, dt) for _ in range(3)]
-        check(lib().gf_image_split(self._h, model, et, argb.size, _ptr(argb), (C.c_void_p * 3)(*[p.ctypes.data for p in planes])), "gf_image_split")
-        return planes
-
-    def image_join(self, planes, model="ycocg", elem_type="short"):
-        """gf_image_join, the host-memory form: ARGB words (int32) in the shape of the planes"""
-        model, et, dt = self._image_kind(model, elem_type)
-        planes = [np.ascontiguousarray(p, dt) for p in planes]
-        assert len(planes) == 3 and all(p.shape == planes[0].shape for p in planes)
-        argb = np.zeros(planes[0].shape, np.int32)
-        check(lib().gf_image_join(self._h, model, et, argb.size, (C.c_void_p * 3)(*[p.ctypes.data for p in planes]), _ptr(argb)), "gf_image_join")
-        return argb
-
-    def image_reduce(self, argb, factor):
-        """gf_image_reduce, the host-memory form: argb [height, width] -> int32 [height // factor, width // factor]"""
-        a = np.asarray(argb)
-        argb = np.ascontiguousarray(a).view(np.int32) if a.dtype == np.uint32 else np.ascontiguousarray(a, np.int32)
-        assert argb.ndim == 2
-        w, h = self.image_reduce_size(argb.shape[1], argb.shape[0], factor)
-        out = np.zeros((h, w), np.int32)
-        check(lib().gf_image_reduce(self._h, argb.shape[1], argb.shape[0], int(factor), _ptr(argb), C.c_void_p(out.ctypes.data)), "gf_image_reduce")
-        return out
-
-    def close(self):
-        if self._h:
-            lib().gf_context_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
+# What an element kind means, in one place.  type: its GF_ELEM_* number; delivered: the dtype a reader hands out; written: the dtype
+# a record writer takes (an int-coded float's int32 codes); coarse: the dtype of a downsampled block; fill: the gf_elem_spec field
+# of a block's fill cell and its default (None: an int-coded float's is the fill_f of its description); range: the gf_elem_range
+# fields' suffix and the default range (an int-coded float's in codes, which its scale and offset turn into values).
+_ElemKind = collections.namedtuple("_ElemKind", "type delivered written coarse fill range")
+_ELEM_KINDS = {
+    "int": _ElemKind(0, np.int32, np.int32, np.int32, ("fill_i", INT4_NULL_CODE), ("i", INT4_NULL_CODE + 1, 2 ** 31 - 1)),
+    "short": _ElemKind(1, np.int16, np.int16, np.int16, ("fill_i", -32768), ("i", -32767, 32767)),
+    "float": _ElemKind(2, np.float32, np.float32, np.float32, ("fill_f", np.float32(np.nan)), ("f", -np.inf, np.inf)),
+    "icf": _ElemKind(3, np.float32, np.int32, np.int32, None, ("f", INT4_NULL_CODE + 1, 2 ** 31 - 2)),
+}
+ELEM_TYPES = {name: kind.type for name, kind in _ELEM_KINDS.items()}                       # GF_ELEM_*
+_DELIVERED = {kind.type: kind.delivered for kind in _ELEM_KINDS.values()}
+_ELEM_SPEC = np.dtype([("type", np.int32), ("fill_i", np.int32), ("scale", np.float32), ("offset", np.float32),
+                       ("fill_f", np.float32)])                                           # gf_elem_spec
+_ELEM_RANGE = np.dtype([("min_i", np.int32), ("max_i", np.int32), ("min_f", np.float32), ("max_f", np.float32)])   # gf_elem_range
 
 IMAGE_RGB, IMAGE_YCOCG = 0, 1                                              # GF_IMAGE_*
 IMAGE_MODELS = {"rgb": IMAGE_RGB, "ycocg": IMAGE_YCOCG}
@@ -370,13 +56,6 @@ TAB_SUMMARY = np.dtype([("n_cells", np.int64), ("n_skipped", np.int64), ("n_samp
 TAB_SYMBOLS = np.dtype([("n_samples", np.int64), ("n_symbols", np.int64), ("n_unique", np.int64), ("n_repeated", np.int64),
                         ("n_written", np.int64), ("max_count", np.int32), ("reserved", np.int32)])                   # gf_tab_symbols
 
-
-def _tab_dense_spec(def_min, def_max, scale):
-    s = np.zeros(1, _TAB_DENSE)
-    s["def_min"], s["def_max"], s["scale"] = def_min, def_max, scale
-    return s
-
-
 INTERP_VALUE, INTERP_FIRST, INTERP_SECOND = 0, 1, 2                      # GF_INTERP_*
 _INTERP_SPEC = np.dtype([("n_rows_grid", np.int32), ("n_cols_grid", np.int32), ("block", np.int32, 4), ("elem_type", np.int32),
                          ("fill_i", np.int32), ("wrap", np.int32), ("target", np.int32), ("row_spacing", np.float64),
@@ -385,6 +64,142 @@ _INTERP_SPEC = np.dtype([("n_rows_grid", np.int32), ("n_cols_grid", np.int32), (
 _INTERP_OUT = np.dtype([(k, np.uint64) for k in ("z", "zx", "zy", "zxx", "zxy", "zyy", "normal", "status")])        # gf_interp_out
 _INTERP_LATTICE = np.dtype([("row0", np.float64), ("col0", np.float64), ("row_step", np.float64), ("col_step", np.float64),
                             ("n_rows", np.int64), ("n_cols", np.int64)])                                            # gf_interp_lattice
+
+PALETTE_RGB, PALETTE_HSV, PALETTE_MAX_RECORDS, RENDER_UNLIMITED, RENDER_Z = 0, 1, 256, 1, 4                                     # GF_PALETTE_*, GF_RENDER_*
+_PALETTE_RECORD = np.dtype([("range0", np.float64), ("range1", np.float64), ("model", np.int32), ("rgb0", np.int32, 3), ("rgb1", np.int32, 3),
+                            ("reserved", np.int32), ("hsv0", np.float64, 3), ("hsv1", np.float64, 3)])               # gf_palette_record
+_PALETTE_SPEC = np.dtype([("records", np.uint64), ("n_records", np.int32), ("argb_for_null", np.uint32), ("normalized", np.int32),
+                          ("hinge", np.int32), ("range_min", np.float64), ("range_max", np.float64), ("hinge_value", np.float64)])  # gf_palette_spec
+_RENDER_LIGHT = np.dtype([("x_gain", np.float64), ("y_gain", np.float64), ("sun", np.float64, 3), ("ambient", np.float64)])  # gf_render_light
+_RENDER_OUT = np.dtype([(k, np.uint64) for k in ("argb", "shade", "status")])                                       # gf_render_out
+
+# struct gf_codec_stats (include/gvrs_hip_codec.h) = the sums of compress/CodecStats.java
+CODEC_STATS_DTYPE = np.dtype([("n_tiles", "<i8"), ("n_bytes", "<i8"), ("n_symbols", "<i8"), ("n_bits_overhead", "<i8"),
+                              ("n_m32_counted", "<i8"), ("sum_length_m32", "<i8"), ("sum_observed_m32", "<i8"),
+                              ("sum_entropy_m32", "<f8")])
+
+# struct gf_canon_stats (include/gvrs_hip_codec.h) = the sums of compress/canonicalHuffman/CanonHuffmanStats.java
+CANON_STATS_DTYPE = np.dtype([("n_tiles", "<i8"), ("n_bytes", "<i8"), ("n_symbols", "<i8"), ("n_bits_overhead", "<i8"),
+                              ("n_text_counted", "<i8"), ("sum_length", "<i8"), ("sum_observed", "<i8"), ("sum_entropy", "<f8"),
+                              ("sum_escape_bits", "<i8")])
+
+
+# ---- helpers ----
+def _call(name, *args):
+    """The entry point `name` of the library called and its status checked: raises GvrsHipError, else returns the status."""
+    return check(getattr(lib(), name)(*args), name)
+
+
+def _ptr(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def _ptrs(items):
+    """The c_void_p array of a per-element pointer table: items are DeviceBuffers, host arrays, c_void_p or plain addresses."""
+    def address(p):
+        if isinstance(p, DeviceBuffer):
+            return p.ptr.value
+        if isinstance(p, np.ndarray):
+            return p.ctypes.data
+        return p.value if isinstance(p, C.c_void_p) else p
+    return (C.c_void_p * len(items))(*[address(p) for p in items])
+
+
+def _blob_of(packings):
+    """(blob, offsets[n + 1]) of packings laid back to back, with 16 zero bytes behind the last: the kernels read whole aligned
+    words past a packing's end."""
+    offsets = np.zeros(len(packings) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(p) for p in packings])
+    return np.frombuffer(b"".join(packings) + b"\0" * 16, dtype=np.uint8), offsets
+
+
+def _records_in(blob, offsets, tail=False):
+    """Records as a caller hands them in -> (blob uint8, offsets uint64), both contiguous; tail: with the 16 zero bytes behind the
+    blob that a host form reads into."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    if tail:
+        blob = np.concatenate([blob, np.zeros(16, np.uint8)])
+    return blob, np.ascontiguousarray(offsets, dtype=np.uint64)
+
+
+def _records_out(blob, offsets, n, status=None):
+    """The n records blob[offsets[t]:offsets[t + 1]] as a list of bytes; with status, None for a record whose status is not OK."""
+    return [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) if status is None or status[t] == _lib.OK else None for t in range(n)]
+
+
+def _old_records(old):
+    """The old= argument of the writers, None or (blob, offsets) -> (blob, offsets, number of records); None: 16 bytes, no record."""
+    if old is None:
+        return np.zeros(16, np.uint8), np.zeros(1, np.uint64), 0
+    old_blob, old_off = _records_in(*old)
+    return old_blob, old_off, old_off.size - 1
+
+
+def _grown_blob(encode, cap, slack, offsets):
+    """The blob of a host-form batch encoder that answers ERR_CAPACITY with the bytes it needs in offsets[-1]: encode(blob, cap)
+    is called until the blob holds them.  Returns (the last call's status, unchecked; blob)."""
+    while True:
+        blob = np.empty(max(cap, 16), np.uint8)
+        st = encode(blob, cap)
+        if st != _lib.ERR_CAPACITY:
+            return st, blob
+        cap = int(offsets[-1]) + slack
+
+
+def _grid_rect(nRows, nCols, grid_shape, rect):
+    """(grid, rect) as the block entry points take them: (rows, columns of the grid, rows, columns of a tile), (row0, col0, n_rows, n_cols)"""
+    return np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32), np.ascontiguousarray(rect, np.int32)
+
+
+def _tiles_of_rect(grid, rect):
+    """gf_block_tile_rect: how many tiles rect touches"""
+    tr = tuple(C.c_int32() for _ in range(4))
+    _call("gf_block_tile_rect", _ptr(grid), _ptr(rect), *[C.byref(x) for x in tr])
+    return tr[2].value * tr[3].value
+
+
+def _argb_words(argb):
+    """ARGB words as int32: uint32 words keep their bits, anything else is converted"""
+    a = np.asarray(argb)
+    return np.ascontiguousarray(a).view(np.int32) if a.dtype == np.uint32 else np.ascontiguousarray(a, np.int32)
+
+
+def _out_struct(dtype, out):
+    """A struct of output addresses (gf_interp_out, gf_render_out) from a dict of c_void_p, addresses or None under its field names"""
+    o = np.zeros(1, dtype)
+    for k, v in out.items():
+        o[k] = 0 if v is None else (v.value if isinstance(v, C.c_void_p) else int(v)) or 0
+    return o
+
+
+def _lattice_struct(lattice):
+    """A gf_interp_lattice from (row0, col0, row_step, col_step, n_rows, n_cols)"""
+    lat = np.zeros(1, _INTERP_LATTICE)
+    lat["row0"], lat["col0"], lat["row_step"], lat["col_step"], lat["n_rows"], lat["n_cols"] = lattice
+    return lat
+
+
+def _elem_kind(el):
+    """An elems entry "int" | "short" | "float" | ("icf", scale, offset, fill_i, fill_f) -> (kind, its _ELEM_KINDS row, the
+    entry's parameters (scale, offset, fill_i, fill_f) or None)"""
+    kind = el if isinstance(el, str) else el[0]
+    return kind, _ELEM_KINDS[kind], (None if kind != "icf" else tuple(el[1:]))
+
+
+def _elem_type(x):
+    """GF_ELEM_* of an element's name or number"""
+    return ELEM_TYPES[x] if isinstance(x, str) else int(x)
+
+
+def _delivered_dtype(elem_type):
+    """The dtype of a GF_ELEM_* number's delivered cells; float32 for a number that is none (the library refuses it)"""
+    return _DELIVERED.get(int(elem_type), np.float32)
+
+
+def _tab_dense_spec(def_min, def_max, scale):
+    s = np.zeros(1, _TAB_DENSE)
+    s["def_min"], s["def_max"], s["scale"] = def_min, def_max, scale
+    return s
 
 
 def interp_spec(n_rows_grid, n_cols_grid, block=None, elem_type="float", fill_i=0, wrap=0, target=INTERP_VALUE, row_spacing=1.0,
@@ -397,20 +212,11 @@ def interp_spec(n_rows_grid, n_cols_grid, block=None, elem_type="float", fill_i=
     s = np.zeros(1, _INTERP_SPEC)
     s["n_rows_grid"], s["n_cols_grid"] = n_rows_grid, n_cols_grid
     s["block"] = (0, 0, n_rows_grid, n_cols_grid) if block is None else block
-    s["elem_type"] = ELEM_TYPES[elem_type] if isinstance(elem_type, str) else elem_type
+    s["elem_type"] = _elem_type(elem_type)
     s["fill_i"], s["wrap"], s["target"], s["row_spacing"], s["col_spacing"] = fill_i, wrap, target, row_spacing, col_spacing
     s["row_fringe0"], s["row_fringe1"] = (-0.5, n_rows_grid - 0.5) if row_fringe is None else row_fringe
     s["col_fringe0"], s["col_fringe1"] = (-0.5, n_cols_grid - 0.5) if col_fringe is None else col_fringe
     return s
-
-
-PALETTE_RGB, PALETTE_HSV, PALETTE_MAX_RECORDS, RENDER_UNLIMITED, RENDER_Z = 0, 1, 256, 1, 4                                     # GF_PALETTE_*, GF_RENDER_*
-_PALETTE_RECORD = np.dtype([("range0", np.float64), ("range1", np.float64), ("model", np.int32), ("rgb0", np.int32, 3), ("rgb1", np.int32, 3),
-                            ("reserved", np.int32), ("hsv0", np.float64, 3), ("hsv1", np.float64, 3)])               # gf_palette_record
-_PALETTE_SPEC = np.dtype([("records", np.uint64), ("n_records", np.int32), ("argb_for_null", np.uint32), ("normalized", np.int32),
-                          ("hinge", np.int32), ("range_min", np.float64), ("range_max", np.float64), ("hinge_value", np.float64)])  # gf_palette_spec
-_RENDER_LIGHT = np.dtype([("x_gain", np.float64), ("y_gain", np.float64), ("sun", np.float64, 3), ("ambient", np.float64)])  # gf_render_light
-_RENDER_OUT = np.dtype([(k, np.uint64) for k in ("argb", "shade", "status")])                                       # gf_render_out
 
 
 def palette_records(records):
@@ -445,6 +251,378 @@ def render_light(x_gain, y_gain, sun, ambient):
     return li
 
 
+# ---- device memory: one allocation, and the allocations of one call ----
+class DeviceBuffer:
+    """A raw device allocation owned through the C ABI (no torch needed)."""
+
+    def __init__(self, ctx, nbytes):
+        self.ctx = ctx
+        self.nbytes = int(nbytes)
+        p = C.c_void_p()
+        _call("gf_dev_malloc", ctx.handle, max(self.nbytes, 16), C.byref(p))
+        self.ptr = p
+
+    def upload(self, array, byte_offset=0):
+        a = np.ascontiguousarray(array)
+        assert byte_offset + a.nbytes <= max(self.nbytes, 16)
+        _call("gf_dev_upload", self.ctx.handle, C.c_void_p(self.ptr.value + byte_offset), _ptr(a), a.nbytes)
+        return self
+
+    def download(self, dtype, count, byte_offset=0):
+        out = np.empty(count, dtype)
+        assert byte_offset + out.nbytes <= max(self.nbytes, 16)
+        _call("gf_dev_download", self.ctx.handle, _ptr(out), C.c_void_p(self.ptr.value + byte_offset), out.nbytes)
+        return out
+
+    def fill(self, value=0):
+        _call("gf_dev_memset", self.ctx.handle, self.ptr, value, self.nbytes)
+        return self
+
+    def free(self):
+        if self.ptr:
+            lib().gf_dev_free(self.ctx.handle, self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class _DeviceScope:
+    """The device buffers of one call: `with _DeviceScope(ctx) as s:` owns every buffer made through s and frees them all when
+    the block ends, however it ends -- an allocation or an upload that raised half way included."""
+
+    def __init__(self, ctx):
+        self.ctx, self._buffers = ctx, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for b in self._buffers:
+            b.free()
+        return False
+
+    def alloc(self, nbytes, fill=None):
+        """A buffer of nbytes; fill: the byte it is set to"""
+        b = DeviceBuffer(self.ctx, nbytes)
+        self._buffers.append(b)
+        return b if fill is None else b.fill(fill)
+
+    def upload(self, array, slack=0, fill=None):
+        """A buffer that holds array and slack bytes behind it (fill: set to that byte first)"""
+        a = np.ascontiguousarray(array)
+        return self.alloc(a.nbytes + slack, fill).upload(a)
+
+    ptrs = staticmethod(_ptrs)
+
+    def run(self, name, *args):
+        """_call, then the context synchronised: after it the buffers may be downloaded"""
+        st = _call(name, *args)
+        self.ctx.synchronize()
+        return st
+
+
+# ---- the context and the objects made on one ----
+class GvrsHipContext:
+    """One device context (stream + workspace); one per process and GPU."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        _call("gf_context_create", int(device), C.byref(self._h))
+        self.device = int(device)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stream(self):
+        return lib().gf_context_stream(self._h)
+
+    def synchronize(self):
+        _call("gf_context_synchronize", self._h)
+
+    def reserve(self, n_rows, n_cols, n_tiles):
+        _call("gf_context_reserve", self._h, n_rows, n_cols, n_tiles)
+
+    def block_from_tiles_dev(self, grid, rect, elem_type, fill_bits, n_tiles, d_tile_indices, d_tiles, d_block, d_tile_status=None,
+                             stream=None):
+        """gf_block_from_tiles_dev on device pointers: grid = (n_rows_grid, n_cols_grid, n_rows_tile, n_cols_tile), rect = (row0,
+        col0, n_rows, n_cols), elem_type one of ELEM_TYPES' values.  Enqueues only."""
+        grid, rect = np.ascontiguousarray(grid, np.int32), np.ascontiguousarray(rect, np.int32)
+        assert grid.size == 4 and rect.size == 4
+        _call("gf_block_from_tiles_dev", self._h, stream, _ptr(grid), _ptr(rect), int(elem_type), int(fill_bits) & 0xffffffff, int(n_tiles),
+              d_tile_indices, d_tile_status, d_tiles, d_block)
+
+    def tiles_from_block_dev(self, grid, rect, elem_type, fill_bits, d_block, n_tiles, d_tile_indices, d_tiles, d_status=None,
+                             keep_outside=False, stream=None):
+        """gf_tiles_from_block_dev on device pointers, the inverse of block_from_tiles_dev.  Enqueues only."""
+        grid, rect = np.ascontiguousarray(grid, np.int32), np.ascontiguousarray(rect, np.int32)
+        assert grid.size == 4 and rect.size == 4
+        _call("gf_tiles_from_block_dev", self._h, stream, _ptr(grid), _ptr(rect), int(elem_type), int(fill_bits) & 0xffffffff,
+              int(bool(keep_outside)), d_block, int(n_tiles), d_tile_indices, d_tiles, d_status)
+
+    # ---- a grid block interpolated: B-spline value, derivatives, unit normal (gf_block_interp_*) ----
+    @staticmethod
+    def _interp_out(out):
+        return _out_struct(_INTERP_OUT, out)
+
+    def interp_points_dev(self, spec, d_block, n_points, d_rows, d_cols, out, d_col_spacing=None, stream=None):
+        """gf_block_interp_points_dev on device pointers: spec from interp_spec(), out a dict of device pointers under the names
+        z, zx, zy, zxx, zxy, zyy, normal (3 doubles per point), status (int32); all but z may be missing.  Enqueues only."""
+        o = self._interp_out(out)
+        _call("gf_block_interp_points_dev", self._h, stream, _ptr(spec), d_block, int(n_points), d_rows, d_cols, d_col_spacing, _ptr(o))
+
+    def interp_lattice_dev(self, spec, d_block, lattice, out, d_col_spacing_rows=None, stream=None):
+        """gf_block_interp_lattice_dev: lattice = (row0, col0, row_step, col_step, n_rows, n_cols); point (i, j) is row0 + i *
+        row_step, col0 + j * col_step; outputs row-major n_rows x n_cols; d_col_spacing_rows: one spacing per lattice row.
+        Enqueues only."""
+        lat, o = _lattice_struct(lattice), self._interp_out(out)
+        _call("gf_block_interp_lattice_dev", self._h, stream, _ptr(spec), d_block, _ptr(lat), d_col_spacing_rows, _ptr(o))
+
+    def interp_points(self, spec, block, rows, cols, col_spacing=None):
+        """gf_block_interp_points, the host-memory form (staged by the library): block is the rectangle spec["block"] of the raster
+        in the element's delivered dtype, rows / cols grid coordinates.  Returns a dict: z and status [n] always; zx, zy and normal
+        [n, 3] with target >= INTERP_FIRST; zxx, zxy, zyy with INTERP_SECOND.  A point whose status is not 0 is NaN throughout."""
+        rows, cols = np.ascontiguousarray(rows, np.float64).ravel(), np.ascontiguousarray(cols, np.float64).ravel()
+        assert rows.size == cols.size
+        n, target = rows.size, int(spec["target"][0])
+        block = np.ascontiguousarray(block, _delivered_dtype(spec["elem_type"][0]))
+        assert block.size == int(spec["block"][0][2]) * int(spec["block"][0][3])
+        names = ["z"] + (["zx", "zy"] if target >= INTERP_FIRST else []) + (["zxx", "zxy", "zyy"] if target >= INTERP_SECOND else [])
+        res = {k: np.zeros(n, np.float64) for k in names}
+        if target >= INTERP_FIRST:
+            res["normal"] = np.zeros((n, 3), np.float64)
+        res["status"] = np.zeros(n, np.int32)
+        cs = None if col_spacing is None else np.ascontiguousarray(col_spacing, np.float64).ravel()
+        assert cs is None or cs.size == n
+        o = self._interp_out({k: a.ctypes.data for k, a in res.items()})
+        _call("gf_block_interp_points", self._h, _ptr(spec), _ptr(block), n, _ptr(rows), _ptr(cols), None if cs is None else _ptr(cs), _ptr(o))
+        return res
+
+    # ---- a grid block rendered to ARGB: colour palette and shaded relief (gf_block_render_*) ----
+    @staticmethod
+    def _render_args(lattice, light, out):
+        lat = None if lattice is None else _lattice_struct(lattice)
+        return lat, (None if light is None else np.ascontiguousarray(light, _RENDER_LIGHT).reshape(1)), _out_struct(_RENDER_OUT, out)
+
+    def render_cells_dev(self, palette, elem_type, d_cells, n_cells, d_argb, d_shade=None, fill_i=0, unlimited=False, stream=None):
+        """gf_block_render_cells_dev on device pointers: n_cells cells of the element ("int", "short", "float", "icf", GF_ELEM_*, or
+        "z" / RENDER_Z: doubles) -> d_argb [n_cells] int32; d_shade: one double per cell (the WithShade lookups).  Enqueues only."""
+        et = RENDER_Z if elem_type == "z" else _elem_type(elem_type)
+        _call("gf_block_render_cells_dev", self._h, stream, palette.handle, RENDER_UNLIMITED if unlimited else 0, et, int(fill_i), d_cells,
+              int(n_cells), d_shade, d_argb)
+
+    def render_lattice_dev(self, spec, d_block, lattice, palette, out, light=None, unlimited=False, stream=None):
+        """gf_block_render_lattice_dev: spec and lattice as interp_lattice_dev takes them, light from render_light() (None: the
+        value alone, no shade), out a dict of device pointers under the names argb (int32), shade (double), status (int32), each
+        one item per pixel; argb or shade must be there.  Enqueues only."""
+        lat, li, o = self._render_args(lattice, light, out)
+        _call("gf_block_render_lattice_dev", self._h, stream, _ptr(spec), d_block, _ptr(lat), palette.handle, None if li is None else _ptr(li),
+              RENDER_UNLIMITED if unlimited else 0, _ptr(o))
+
+    def render_points_dev(self, spec, d_block, palette, out, lattice=None, n_points=0, d_rows=None, d_cols=None, d_col_spacing=None,
+                          light=None, unlimited=False, stream=None):
+        """gf_block_render_points_dev: with lattice, a lattice whose column spacing differs per row (d_col_spacing: one per lattice
+        row); without, n_points points d_rows, d_cols (d_col_spacing: one per point).  Enqueues only."""
+        lat, li, o = self._render_args(lattice, light, out)
+        _call("gf_block_render_points_dev", self._h, stream, _ptr(spec), d_block, None if lat is None else _ptr(lat), int(n_points), d_rows,
+              d_cols, d_col_spacing, palette.handle, None if li is None else _ptr(li), RENDER_UNLIMITED if unlimited else 0, _ptr(o))
+
+    def render_lattice(self, spec, block, lattice, palette, light=None, unlimited=False):
+        """gf_block_render_lattice, the host-memory form (staged by the library): returns a dict argb [n_rows, n_cols] int32, status
+        the same, and shade (float64) with a light."""
+        block = np.ascontiguousarray(block, _delivered_dtype(spec["elem_type"][0]))
+        assert block.size == int(spec["block"][0][2]) * int(spec["block"][0][3])
+        shape = (int(lattice[4]), int(lattice[5]))
+        res = {"argb": np.zeros(shape, np.int32), "status": np.zeros(shape, np.int32)}
+        if light is not None:
+            res["shade"] = np.zeros(shape, np.float64)
+        lat, li, o = self._render_args(lattice, light, {k: a.ctypes.data for k, a in res.items()})
+        _call("gf_block_render_lattice", self._h, _ptr(spec), _ptr(block), _ptr(lat), palette.handle, None if li is None else _ptr(li),
+              RENDER_UNLIMITED if unlimited else 0, _ptr(o))
+        return res
+
+    # ---- a grid block downsampled: the box average by an integer factor (gf_block_downsample_*) ----
+    @staticmethod
+    def downsample_rect(block, factor):
+        """gf_block_downsample_rect: block = (row0, col0, n_rows, n_cols) on the source grid -> the rectangle of the coarse grid
+        whose cells' whole factor x factor windows lie inside block (n_rows or n_cols may be 0)."""
+        block, out = np.ascontiguousarray(block, np.int32), np.zeros(4, np.int32)
+        assert block.size == 4
+        _call("gf_block_downsample_rect", _ptr(block), int(factor), _ptr(out))
+        return tuple(int(x) for x in out)
+
+    @staticmethod
+    def _downsample_specs(elems, fills):
+        """elems: a gf_elem_spec array as it is, or per element "int" | "short" | "float" with fills as read_block_dev takes them"""
+        if isinstance(elems, np.ndarray):
+            assert elems.dtype == _ELEM_SPEC and fills is None
+            return elems, [_delivered_dtype(t) for t in elems["type"]]
+        specs, dtypes = CodecMasterHip._elem_specs(elems)
+        return CodecMasterHip._fill_specs(specs, elems, fills), dtypes
+
+    def downsample_dev(self, elems, block, factor, d_blocks, d_out, stream=None, fills=None):
+        """gf_block_downsample_elems_dev on device pointers: d_blocks[e] holds the rectangle block of element e (int32 / int16 /
+        float32, row-major), d_out[e] receives the cells of downsample_rect(block, factor).  Enqueues only."""
+        specs, _ = self._downsample_specs(elems, fills)
+        ne = len(specs)
+        assert len(d_blocks) == ne and len(d_out) == ne
+        block = np.ascontiguousarray(block, np.int32)
+        _call("gf_block_downsample_elems_dev", self._h, stream, _ptr(specs), ne, _ptr(block), int(factor), _ptrs(d_blocks), _ptrs(d_out))
+
+    def downsample(self, elems, block, factor, blocks, fills=None):
+        """gf_block_downsample_elems, the host-memory form (staged by the library): blocks[e] is the rectangle block of element e.
+        Returns one array [n_rows', n_cols'] per element in the element's dtype, for downsample_rect(block, factor)."""
+        specs, dtypes = self._downsample_specs(elems, fills)
+        ne = len(specs)
+        block = np.ascontiguousarray(block, np.int32)
+        blocks = [np.ascontiguousarray(b, dt) for b, dt in zip(blocks, dtypes)]
+        assert len(blocks) == ne and all(b.size == int(block[2]) * int(block[3]) for b in blocks)
+        _, _, n_rows, n_cols = self.downsample_rect(block, factor)
+        out = [np.zeros((n_rows, n_cols), dt) for dt in dtypes]
+        _call("gf_block_downsample_elems", self._h, _ptr(specs), ne, _ptr(block), int(factor), _ptrs(blocks), _ptrs(out))
+        return out
+
+    # ---- a grid block tabulated: value counts, range and entropy (gf_block_tabulate_*, gf_tab_*) ----
+    @staticmethod
+    def tab_dense_plan(def_min, def_max, scale):
+        """gf_tab_dense_plan_of: InputDataStatCollector's constructor -> dict n_counter, base, n_bins, scale_used"""
+        spec, plan = _tab_dense_spec(def_min, def_max, scale), np.zeros(1, _TAB_DENSE_PLAN)
+        _call("gf_tab_dense_plan_of", _ptr(spec), _ptr(plan))
+        return {k: plan[k][0].item() for k in plan.dtype.names}
+
+    def tabulate_dense_dev(self, elem_type, d_block, n_cells, def_min, def_max, scale, d_counter, d_summary, fill_i=0, skip_fill=False,
+                           accumulate=False, first_cell=0, stream=None):
+        """gf_block_tabulate_dense_dev on device pointers: n_cells cells of the element ("int", "short", "float" or GF_ELEM_*) ->
+        d_counter [tab_dense_plan(...)["n_bins"]] int32 and d_summary, one gf_tab_summary (TAB_SUMMARY).  Enqueues only."""
+        flags = (TAB_ACCUMULATE if accumulate else 0) | (TAB_SKIP_FILL if skip_fill else 0)
+        spec = _tab_dense_spec(def_min, def_max, scale)
+        _call("gf_block_tabulate_dense_dev", self._h, stream, _elem_type(elem_type), int(fill_i), flags, d_block, int(n_cells), int(first_cell),
+              _ptr(spec), d_counter, d_summary)
+
+    def tabulate_dense(self, elem_type, block, def_min, def_max, scale, fill_i=0, skip_fill=False, first_cell=0, into=None):
+        """gf_block_tabulate_dense, the host-memory form (staged by the library): returns (counter [n_bins] int32, summary dict).
+        into = (counter, summary) of an earlier call: accumulate onto them (a raster in strips, first_cell the strip's first cell)."""
+        et = _elem_type(elem_type)
+        block = np.ascontiguousarray(block, _delivered_dtype(et)).ravel()
+        flags = (TAB_ACCUMULATE if into is not None else 0) | (TAB_SKIP_FILL if skip_fill else 0)
+        summary = np.zeros(1, TAB_SUMMARY)
+        if into is not None:
+            counter = np.ascontiguousarray(into[0], np.int32).copy()
+            for k in TAB_SUMMARY.names:
+                summary[k] = into[1][k]
+            assert counter.size == self.tab_dense_plan(def_min, def_max, scale)["n_bins"]
+        else:
+            counter = np.zeros(self.tab_dense_plan(def_min, def_max, scale)["n_bins"], np.int32)
+        spec = _tab_dense_spec(def_min, def_max, scale)
+        _call("gf_block_tabulate_dense", self._h, et, int(fill_i), flags, _ptr(block), block.size, int(first_cell), _ptr(spec), _ptr(counter),
+              _ptr(summary))
+        return counter, {k: summary[k][0].item() for k in TAB_SUMMARY.names}
+
+    def tabulate_symbols_dev(self, elem_type, d_block, n_cells, d_symbols, d_counts, table_cap, d_summary, stream=None):
+        """gf_block_tabulate_symbols_dev on device pointers: the distinct 32-bit symbols of n_cells cells in ascending unsigned order
+        -> d_symbols [table_cap] uint32, d_counts [table_cap] int32 (both None with table_cap 0) and d_summary, one gf_tab_symbols
+        (TAB_SYMBOLS).  Enqueues only."""
+        _call("gf_block_tabulate_symbols_dev", self._h, stream, _elem_type(elem_type), d_block, int(n_cells), d_symbols, d_counts, int(table_cap),
+              d_summary)
+
+    def tabulate_symbols(self, elem_type, block, table_cap=None):
+        """gf_block_tabulate_symbols, the host-memory form: returns (symbols uint32, counts int32, summary dict); table_cap None:
+        room for every cell.  A table that does not hold every symbol comes back with its first table_cap entries (summary
+        ["n_written"] of summary["n_symbols"])."""
+        et = _elem_type(elem_type)
+        block = np.ascontiguousarray(block, _delivered_dtype(et)).ravel()
+        cap = block.size if table_cap is None else int(table_cap)
+        symbols, counts, summary = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int32), np.zeros(1, TAB_SYMBOLS)
+        st = lib().gf_block_tabulate_symbols(self._h, et, _ptr(block), block.size, _ptr(symbols) if cap else None, _ptr(counts) if cap else None,
+                                             cap, _ptr(summary))
+        if st != _lib.ERR_CAPACITY:
+            check(st, "gf_block_tabulate_symbols")
+        n = int(summary["n_written"][0])
+        return symbols[:n], counts[:n], {k: summary[k][0].item() for k in TAB_SYMBOLS.names}
+
+    @staticmethod
+    def tab_entropy(counts, n_samples, kahan=True):
+        """gf_tab_entropy_counts: bits per sample of a table of counts in the order given; kahan: EntropyTabulator's sum, else
+        InputDataStatCollector.getEntropy's"""
+        counts, e = np.ascontiguousarray(counts, np.int32).ravel(), C.c_double()
+        _call("gf_tab_entropy_counts", _ptr(counts), counts.size, int(n_samples), int(bool(kahan)), C.byref(e))
+        return e.value
+
+    # ---- ARGB images as element planes and as overviews (gf_image_split / _join / _reduce) ----
+    @staticmethod
+    def _image_kind(model, elem_type):
+        """(GF_IMAGE_*, GF_ELEM_*, the planes' dtype) of a model's and an element's name or number; planes are "int" or "short" """
+        model, et = (IMAGE_MODELS[model] if isinstance(model, str) else int(model)), _elem_type(elem_type)
+        return model, et, _ELEM_KINDS["short" if et == ELEM_TYPES["short"] else "int"].delivered
+
+    def image_split_dev(self, model, elem_type, n_pixels, d_argb, d_planes):
+        """gf_image_split_dev on device pointers: n_pixels ARGB words -> three planes (model "rgb": r, g, b; "ycocg": Y, Co, Cg) of
+        int32 ("int") or int16 ("short").  Runs on the context's stream; enqueues only."""
+        model, et, _ = self._image_kind(model, elem_type)
+        assert len(d_planes) == 3
+        _call("gf_image_split_dev", self._h, model, et, int(n_pixels), d_argb, _ptrs(d_planes))
+
+    def image_join_dev(self, model, elem_type, n_pixels, d_planes, d_argb):
+        """gf_image_join_dev, the inverse: three planes of any ints -> n_pixels ARGB words.  Enqueues only."""
+        model, et, _ = self._image_kind(model, elem_type)
+        assert len(d_planes) == 3
+        _call("gf_image_join_dev", self._h, model, et, int(n_pixels), _ptrs(d_planes), d_argb)
+
+    @staticmethod
+    def image_reduce_size(width, height, factor):
+        """gf_image_reduce_size: (width // factor, height // factor)"""
+        w, h = C.c_int(), C.c_int()
+        _call("gf_image_reduce_size", int(width), int(height), int(factor), C.byref(w), C.byref(h))
+        return w.value, h.value
+
+    def image_reduce_dev(self, width, height, factor, d_argb, d_out):
+        """gf_image_reduce_dev: height rows of width ARGB words -> the image of image_reduce_size(...), each word the per-channel
+        box average of factor x factor pixels as DemoCOG.makeReducedImage rounds it.  Enqueues only."""
+        _call("gf_image_reduce_dev", self._h, int(width), int(height), int(factor), d_argb, d_out)
+
+    def image_split(self, argb, model="ycocg", elem_type="short"):
+        """gf_image_split, the host-memory form (staged by the library): three planes in the shape of argb"""
+        model, et, dt = self._image_kind(model, elem_type)
+        argb = _argb_words(argb)
+        planes = [np.zeros(argb.shape, dt) for _ in range(3)]
+        _call("gf_image_split", self._h, model, et, argb.size, _ptr(argb), _ptrs(planes))
+        return planes
+
+    def image_join(self, planes, model="ycocg", elem_type="short"):
+        """gf_image_join, the host-memory form: ARGB words (int32) in the shape of the planes"""
+        model, et, dt = self._image_kind(model, elem_type)
+        planes = [np.ascontiguousarray(p, dt) for p in planes]
+        assert len(planes) == 3 and all(p.shape == planes[0].shape for p in planes)
+        argb = np.zeros(planes[0].shape, np.int32)
+        _call("gf_image_join", self._h, model, et, argb.size, _ptrs(planes), _ptr(argb))
+        return argb
+
+    def image_reduce(self, argb, factor):
+        """gf_image_reduce, the host-memory form: argb [height, width] -> int32 [height // factor, width // factor]"""
+        argb = _argb_words(argb)
+        assert argb.ndim == 2
+        w, h = self.image_reduce_size(argb.shape[1], argb.shape[0], factor)
+        out = np.zeros((h, w), np.int32)
+        _call("gf_image_reduce", self._h, argb.shape[1], argb.shape[0], int(factor), _ptr(argb), _ptr(out))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().gf_context_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Palette:
     """A colour palette on a context's device (gf_palette_create): what the reference's ColorPaletteTable holds.  records as
     palette_records() takes them; the other arguments are the table constructor's."""
@@ -452,7 +630,7 @@ class Palette:
     def __init__(self, ctx, records, argb_for_null=0, normalized=False, range_min=0.0, range_max=0.0, hinge=False, hinge_value=0.0):
         self._h = C.c_void_p()
         spec, recs = palette_spec(records, argb_for_null, normalized, range_min, range_max, hinge, hinge_value)
-        check(lib().gf_palette_create(ctx.handle, _ptr(spec), C.byref(self._h)), "gf_palette_create")
+        _call("gf_palette_create", ctx.handle, _ptr(spec), C.byref(self._h))
         self.ctx, self.n_records = ctx, len(recs)
 
     @property
@@ -471,17 +649,127 @@ class Palette:
             pass
 
 
-# struct gf_codec_stats (include/gvrs_hip_codec.h) = the sums of compress/CodecStats.java
-CODEC_STATS_DTYPE = np.dtype([("n_tiles", "<i8"), ("n_bytes", "<i8"), ("n_symbols", "<i8"), ("n_bits_overhead", "<i8"),
-                              ("n_m32_counted", "<i8"), ("sum_length_m32", "<i8"), ("sum_observed_m32", "<i8"),
-                              ("sum_entropy_m32", "<f8")])
+class DeviceTileBatch:
+    """Device-resident batch of tiles and their packings: the measured hot path.
 
-# struct gf_canon_stats (include/gvrs_hip_codec.h) = the sums of compress/canonicalHuffman/CanonHuffmanStats.java
-CANON_STATS_DTYPE = np.dtype([("n_tiles", "<i8"), ("n_bytes", "<i8"), ("n_symbols", "<i8"), ("n_bits_overhead", "<i8"),
-                              ("n_text_counted", "<i8"), ("sum_length", "<i8"), ("sum_observed", "<i8"), ("sum_entropy", "<f8"),
-                              ("sum_escape_bits", "<i8")])
+    encode(): values -> slots/lengths/predictors/status   (gf_huffman_encode_batch_i32_dev)
+    decode(): slots/lengths -> decoded/status              (gf_huffman_decode_batch_i32_dev)
+    Nothing synchronises unless asked; everything is enqueued on `stream` (default: the
+    context's stream).
+    """
+
+    def __init__(self, ctx, n_rows, n_cols, n_tiles, slot_stride=None, codec="huffman"):
+        assert codec in ("huffman", "canon", "lsop")
+        self.codec = codec
+        self.ctx, self.n_rows, self.n_cols, self.n_tiles = ctx, int(n_rows), int(n_cols), int(n_tiles)
+        self.cells = self.n_rows * self.n_cols
+        self.stride = int(slot_stride or lib().gf_huffman_default_stride(n_rows, n_cols))
+        assert self.stride % 16 == 0
+        nt = self.n_tiles
+        self.values = DeviceBuffer(ctx, nt * self.cells * 4)
+        self.decoded = DeviceBuffer(ctx, nt * self.cells * 4)
+        self.slots = DeviceBuffer(ctx, nt * self.stride + 16)
+        self.lengths = DeviceBuffer(ctx, nt * 4)
+        self.predictors = DeviceBuffer(ctx, nt)
+        self.enc_status = DeviceBuffer(ctx, nt * 4)
+        self.dec_status = DeviceBuffer(ctx, nt * 4)
+        self._buffers = [self.values, self.decoded, self.slots, self.lengths, self.predictors, self.enc_status, self.dec_status]
+        ctx.reserve(n_rows, n_cols, nt)
+        if codec == "lsop":                          # work buffers of the LSOP stages
+            n = int(lib().gf_lsop12_residual_count(n_rows, n_cols))
+            self.res_stride = (n + 3) // 4 * 4
+            self.residuals = DeviceBuffer(ctx, nt * self.res_stride * 4 + 16)
+            self.coefs = DeviceBuffer(ctx, nt * 64)
+            self.scratch_status = DeviceBuffer(ctx, nt * 4)
+            self._buffers += [self.residuals, self.coefs, self.scratch_status]
+
+    def synth_dem(self, seed, tiles_per_row, tile0=0, stream=None, mask_per_mille=0, style=0):
+        head = (self.ctx.handle, stream, seed & (2 ** 64 - 1), self.n_rows, self.n_cols, tiles_per_row, tile0, self.n_tiles)
+        if style:
+            _call("gf_synth_dem_style_dev", *head, mask_per_mille, style, self.values.ptr)
+        elif mask_per_mille:
+            _call("gf_synth_dem_masked_dev", *head, mask_per_mille, self.values.ptr)
+        else:
+            _call("gf_synth_dem_dev", *head, self.values.ptr)
+
+    def encode(self, codec_index=0, predictor_mask=_lib.PM_ALL, stream=None, lsop_flags=0):
+        if self.codec == "lsop":
+            _call("gf_lsop12_encode_batch_i32_dev_ex", self.ctx.handle, stream, codec_index, self.n_rows, self.n_cols, self.n_tiles,
+                  self.values.ptr, lsop_flags, self.slots.ptr, self.stride, self.lengths.ptr, self.enc_status.ptr, self.residuals.ptr,
+                  self.res_stride, self.coefs.ptr, self.scratch_status.ptr)
+            return
+        _call("gf_%s_encode_batch_i32_dev" % self.codec, self.ctx.handle, stream, codec_index, self.n_rows, self.n_cols, self.n_tiles,
+              self.values.ptr, self.slots.ptr, self.stride, self.lengths.ptr, self.predictors.ptr, self.enc_status.ptr, predictor_mask)
+
+    def decode(self, stream=None):
+        if self.codec == "lsop":
+            _call("gf_lsop12_decode_batch_i32_dev", self.ctx.handle, stream, self.n_rows, self.n_cols, self.n_tiles, self.slots.ptr,
+                  self.n_tiles * self.stride, None, self.stride, self.lengths.ptr, self.decoded.ptr, self.dec_status.ptr,
+                  self.residuals.ptr, self.res_stride, self.coefs.ptr, self.scratch_status.ptr)
+            return
+        _call("gf_%s_decode_batch_i32_dev" % self.codec, self.ctx.handle, stream, self.n_rows, self.n_cols, self.n_tiles, self.slots.ptr,
+              self.n_tiles * self.stride, None, self.stride, self.lengths.ptr, self.decoded.ptr, self.dec_status.ptr)
+
+    # host views (synchronising copies)
+    def get_lengths(self):
+        return self.lengths.download(np.uint32, self.n_tiles)
+
+    def get_predictors(self):
+        return self.predictors.download(np.uint8, self.n_tiles)
+
+    def get_enc_status(self):
+        return self.enc_status.download(np.int32, self.n_tiles)
+
+    def get_dec_status(self):
+        return self.dec_status.download(np.int32, self.n_tiles)
+
+    def get_packing(self, t, length=None):
+        if length is None:
+            length = int(self.lengths.download(np.uint32, 1, 4 * t)[0])
+        return bytes(self.slots.download(np.uint8, length, t * self.stride))
+
+    def get_values(self, t0=0, n=None):
+        n = self.n_tiles - t0 if n is None else n
+        return self.values.download(np.int32, n * self.cells, t0 * self.cells * 4).reshape(n, self.cells)
+
+    def get_decoded(self, t0=0, n=None):
+        n = self.n_tiles - t0 if n is None else n
+        return self.decoded.download(np.int32, n * self.cells, t0 * self.cells * 4).reshape(n, self.cells)
+
+    def free(self):
+        """Frees every buffer of the batch, the LSOP work buffers included."""
+        for b in self._buffers:
+            b.free()
 
 
+class GpuTimer:
+    """HIP-event timer on the stream the kernels are launched on (gf_timer_*)."""
+
+    def __init__(self, ctx):
+        self._h = C.c_void_p()
+        _call("gf_timer_create", ctx.handle, C.byref(self._h))
+
+    def start(self, stream=None):
+        _call("gf_timer_start", self._h, stream)
+
+    def stop(self, stream=None):
+        _call("gf_timer_stop", self._h, stream)
+
+    def elapsed_ms(self):
+        ms = C.c_float(0)
+        _call("gf_timer_elapsed_ms", self._h, C.byref(ms))
+        return ms.value
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().gf_timer_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+
+# ---- the codec classes ----
 class CodecHuffmanHip:
     """Drop-in for org.gridfour.compress.CodecHuffman, computed on the MI355X."""
 
@@ -554,8 +842,8 @@ class CodecHuffmanHip:
         status = np.zeros(nt, np.int32)
         if getattr(self, "_pairs", None) is None:
             self._pairs = np.zeros((6, 65536), np.int64)          # sB of the six CodecStats (CodecStats.java:64)
-        check(lib().gf_huffman_analyze_batch_h2(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(self._stats),
-                                                _ptr(self._pairs), _ptr(status)), "gf_huffman_analyze_batch_h2")
+        _call("gf_huffman_analyze_batch_h2", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(self._stats), _ptr(self._pairs),
+              _ptr(status))
         return status
 
     def pair_counts(self):
@@ -599,26 +887,15 @@ class CodecHuffmanHip:
         """tiles: int32 [nTiles, nRows*nCols].  Returns (packings: list[bytes|None], predictors, status)."""
         v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
         nt = v.shape[0]
-        cap = nt * int(lib().gf_huffman_default_stride(nRows, nCols))
         offsets = np.zeros(nt + 1, np.uint64)
         preds = np.zeros(nt, np.uint8)
         status = np.zeros(nt, np.int32)
-        while True:
-            blob = np.empty(max(cap, 16), np.uint8)
-            st = self._fn("encode_batch_i32")(self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), _ptr(blob), cap,
-                                              _ptr(offsets), _ptr(preds), _ptr(status))
-            if st == _lib.ERR_CAPACITY:
-                cap = int(offsets[nt]) + 16
-                continue
-            check(st, self._PREFIX + "_encode_batch_i32")
-            break
-        packs = []
-        for t in range(nt):
-            if status[t] == _lib.OK:
-                packs.append(bytes(blob[int(offsets[t]):int(offsets[t + 1])]))
-            else:
-                packs.append(None)
-        return packs, preds, status
+        fn = self._fn("encode_batch_i32")
+        st, blob = _grown_blob(lambda blob, cap: fn(self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), _ptr(blob), cap, _ptr(offsets),
+                                                    _ptr(preds), _ptr(status)),
+                               nt * int(lib().gf_huffman_default_stride(nRows, nCols)), 16, offsets)
+        check(st, self._PREFIX + "_encode_batch_i32")
+        return _records_out(blob, offsets, nt, status), preds, status
 
     def decode_batch(self, nRows, nCols, packings):
         """packings: list of bytes.  Returns (values int32 [nTiles, cells], status)."""
@@ -626,8 +903,7 @@ class CodecHuffmanHip:
         blob, offsets = _blob_of(packings)
         out = np.empty((nt, nRows * nCols), np.int32)
         status = np.zeros(nt, np.int32)
-        check(self._fn("decode_batch_i32")(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out),
-                                           _ptr(status)), self._PREFIX + "_decode_batch_i32")
+        _call(self._PREFIX + "_decode_batch_i32", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status))
         return out, status
 
 
@@ -667,8 +943,8 @@ class CodecCanonHuffmanHip(CodecHuffmanHip):
             self._stats = np.zeros(6, dtype=CANON_STATS_DTYPE)
             self._escapes = np.zeros(6, np.int64)
         blob, offsets = _blob_of(packings)
-        check(lib().gf_canon_analyze_batch(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(self._stats),
-                                           _ptr(self._escapes), _ptr(status)), "gf_canon_analyze_batch")
+        _call("gf_canon_analyze_batch", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(self._stats), _ptr(self._escapes),
+              _ptr(status))
         return status
 
     def analysis_data(self):
@@ -713,177 +989,6 @@ class CodecCanonHuffmanHip(CodecHuffmanHip):
         self._escapes = None
 
 
-class DeviceBuffer:
-    """A raw device allocation owned through the C ABI (no torch needed)."""
-
-    def __init__(self, ctx, nbytes):
-        self.ctx = ctx
-        self.nbytes = int(nbytes)
-        p = C.c_void_p()
-        check(lib().gf_dev_malloc(ctx.handle, max(self.nbytes, 16), C.byref(p)), "gf_dev_malloc")
-        self.ptr = p
-
-    def upload(self, array, byte_offset=0):
-        a = np.ascontiguousarray(array)
-        assert byte_offset + a.nbytes <= max(self.nbytes, 16)
-        check(lib().gf_dev_upload(self.ctx.handle, C.c_void_p(self.ptr.value + byte_offset), _ptr(a), a.nbytes),
-              "gf_dev_upload")
-        return self
-
-    def download(self, dtype, count, byte_offset=0):
-        out = np.empty(count, dtype)
-        assert byte_offset + out.nbytes <= max(self.nbytes, 16)
-        check(lib().gf_dev_download(self.ctx.handle, _ptr(out), C.c_void_p(self.ptr.value + byte_offset),
-                                    out.nbytes), "gf_dev_download")
-        return out
-
-    def fill(self, value=0):
-        check(lib().gf_dev_memset(self.ctx.handle, self.ptr, value, self.nbytes), "gf_dev_memset")
-        return self
-
-    def free(self):
-        if self.ptr:
-            lib().gf_dev_free(self.ctx.handle, self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DeviceTileBatch:
-    """Device-resident batch of tiles and their packings: the measured hot path.
-
-    encode(): values -> slots/lengths/predictors/status   (gf_huffman_encode_batch_i32_dev)
-    decode(): slots/lengths -> decoded/status              (gf_huffman_decode_batch_i32_dev)
-    Nothing synchronises unless asked; everything is enqueued on `stream` (default: the
-    context's stream).
-    """
-
-    def __init__(self, ctx, n_rows, n_cols, n_tiles, slot_stride=None, codec="huffman"):
-        assert codec in ("huffman", "canon", "lsop")
-        self.codec = codec
-        self.ctx, self.n_rows, self.n_cols, self.n_tiles = ctx, int(n_rows), int(n_cols), int(n_tiles)
-        self.cells = self.n_rows * self.n_cols
-        self.stride = int(slot_stride or lib().gf_huffman_default_stride(n_rows, n_cols))
-        assert self.stride % 16 == 0
-        nt = self.n_tiles
-        self.values = DeviceBuffer(ctx, nt * self.cells * 4)
-        self.decoded = DeviceBuffer(ctx, nt * self.cells * 4)
-        self.slots = DeviceBuffer(ctx, nt * self.stride + 16)
-        self.lengths = DeviceBuffer(ctx, nt * 4)
-        self.predictors = DeviceBuffer(ctx, nt)
-        self.enc_status = DeviceBuffer(ctx, nt * 4)
-        self.dec_status = DeviceBuffer(ctx, nt * 4)
-        ctx.reserve(n_rows, n_cols, nt)
-        if codec == "lsop":                          # work buffers of the LSOP stages
-            n = int(lib().gf_lsop12_residual_count(n_rows, n_cols))
-            self.res_stride = (n + 3) // 4 * 4
-            self.residuals = DeviceBuffer(ctx, nt * self.res_stride * 4 + 16)
-            self.coefs = DeviceBuffer(ctx, nt * 64)
-            self.scratch_status = DeviceBuffer(ctx, nt * 4)
-
-    def synth_dem(self, seed, tiles_per_row, tile0=0, stream=None, mask_per_mille=0, style=0):
-        if style:
-            check(lib().gf_synth_dem_style_dev(self.ctx.handle, stream, seed & (2 ** 64 - 1), self.n_rows, self.n_cols,
-                                               tiles_per_row, tile0, self.n_tiles, mask_per_mille, style, self.values.ptr),
-                  "gf_synth_dem_style_dev")
-            return
-        if mask_per_mille:
-            check(lib().gf_synth_dem_masked_dev(self.ctx.handle, stream, seed & (2 ** 64 - 1), self.n_rows, self.n_cols,
-                                                tiles_per_row, tile0, self.n_tiles, mask_per_mille, self.values.ptr),
-                  "gf_synth_dem_masked_dev")
-            return
-        check(lib().gf_synth_dem_dev(self.ctx.handle, stream, seed & (2 ** 64 - 1), self.n_rows, self.n_cols,
-                                     tiles_per_row, tile0, self.n_tiles, self.values.ptr), "gf_synth_dem_dev")
-
-    def encode(self, codec_index=0, predictor_mask=_lib.PM_ALL, stream=None, lsop_flags=0):
-        if self.codec == "lsop":
-            check(lib().gf_lsop12_encode_batch_i32_dev_ex(self.ctx.handle, stream, codec_index, self.n_rows, self.n_cols,
-                                                          self.n_tiles, self.values.ptr, lsop_flags, self.slots.ptr, self.stride,
-                                                          self.lengths.ptr, self.enc_status.ptr, self.residuals.ptr,
-                                                          self.res_stride, self.coefs.ptr, self.scratch_status.ptr),
-                  "gf_lsop12_encode_batch_i32_dev_ex")
-            return
-        fn = getattr(lib(), "gf_%s_encode_batch_i32_dev" % self.codec)
-        check(fn(self.ctx.handle, stream, codec_index, self.n_rows, self.n_cols, self.n_tiles, self.values.ptr,
-                 self.slots.ptr, self.stride, self.lengths.ptr, self.predictors.ptr, self.enc_status.ptr,
-                 predictor_mask), "gf_%s_encode_batch_i32_dev" % self.codec)
-
-    def decode(self, stream=None):
-        if self.codec == "lsop":
-            check(lib().gf_lsop12_decode_batch_i32_dev(self.ctx.handle, stream, self.n_rows, self.n_cols, self.n_tiles,
-                                                       self.slots.ptr, self.n_tiles * self.stride, None, self.stride,
-                                                       self.lengths.ptr, self.decoded.ptr, self.dec_status.ptr,
-                                                       self.residuals.ptr, self.res_stride, self.coefs.ptr,
-                                                       self.scratch_status.ptr), "gf_lsop12_decode_batch_i32_dev")
-            return
-        fn = getattr(lib(), "gf_%s_decode_batch_i32_dev" % self.codec)
-        check(fn(self.ctx.handle, stream, self.n_rows, self.n_cols, self.n_tiles, self.slots.ptr,
-                 self.n_tiles * self.stride, None, self.stride, self.lengths.ptr, self.decoded.ptr,
-                 self.dec_status.ptr), "gf_%s_decode_batch_i32_dev" % self.codec)
-
-    # host views (synchronising copies)
-    def get_lengths(self):
-        return self.lengths.download(np.uint32, self.n_tiles)
-
-    def get_predictors(self):
-        return self.predictors.download(np.uint8, self.n_tiles)
-
-    def get_enc_status(self):
-        return self.enc_status.download(np.int32, self.n_tiles)
-
-    def get_dec_status(self):
-        return self.dec_status.download(np.int32, self.n_tiles)
-
-    def get_packing(self, t, length=None):
-        if length is None:
-            length = int(self.lengths.download(np.uint32, 1, 4 * t)[0])
-        return bytes(self.slots.download(np.uint8, length, t * self.stride))
-
-    def get_values(self, t0=0, n=None):
-        n = self.n_tiles - t0 if n is None else n
-        return self.values.download(np.int32, n * self.cells, t0 * self.cells * 4).reshape(n, self.cells)
-
-    def get_decoded(self, t0=0, n=None):
-        n = self.n_tiles - t0 if n is None else n
-        return self.decoded.download(np.int32, n * self.cells, t0 * self.cells * 4).reshape(n, self.cells)
-
-    def free(self):
-        for b in (self.values, self.decoded, self.slots, self.lengths, self.predictors, self.enc_status,
-                  self.dec_status):
-            b.free()
-
-
-class GpuTimer:
-    """HIP-event timer on the stream the kernels are launched on (gf_timer_*)."""
-
-    def __init__(self, ctx):
-        self._h = C.c_void_p()
-        check(lib().gf_timer_create(ctx.handle, C.byref(self._h)), "gf_timer_create")
-
-    def start(self, stream=None):
-        check(lib().gf_timer_start(self._h, stream), "gf_timer_start")
-
-    def stop(self, stream=None):
-        check(lib().gf_timer_stop(self._h, stream), "gf_timer_stop")
-
-    def elapsed_ms(self):
-        ms = C.c_float(0)
-        check(lib().gf_timer_elapsed_ms(self._h, C.byref(ms)), "gf_timer_elapsed_ms")
-        return ms.value
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().gf_timer_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-
 class CodecFloatHip:
     """Drop-in for org.gridfour.compress.CodecFloat (CodecFloat.java:328-458): float32 tiles as five
     byte planes (split/merged on the GPU) each compressed with zlib on the host.
@@ -906,8 +1011,7 @@ class CodecFloatHip:
         cap = 5 * v.size + 4096
         out = np.empty(cap, np.uint8)
         n = C.c_size_t(0)
-        check(lib().gf_float_encode_f32(self.ctx.handle, codecIndex, nRows, nCols, _ptr(v), self.level, _ptr(out), cap,
-                                        C.byref(n)), "gf_float_encode_f32")
+        _call("gf_float_encode_f32", self.ctx.handle, codecIndex, nRows, nCols, _ptr(v), self.level, _ptr(out), cap, C.byref(n))
         return bytes(out[:n.value])
 
     def implementsFloatingPointEncoding(self):
@@ -936,17 +1040,15 @@ class CodecFloatHip:
         cap = nt * (5 * nRows * nCols + 4096)
         blob = np.empty(cap, np.uint8)
         offsets = np.zeros(nt + 1, np.uint64)
-        check(lib().gf_float_encode_batch_f32(self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), self.level, _ptr(blob),
-                                              cap, _ptr(offsets)), "gf_float_encode_batch_f32")
-        return [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(nt)]
+        _call("gf_float_encode_batch_f32", self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), self.level, _ptr(blob), cap, _ptr(offsets))
+        return _records_out(blob, offsets, nt)
 
     def decode_floats_batch(self, nRows, nCols, packings):
         nt = len(packings)
         blob, offsets = _blob_of(packings)
         out = np.empty((nt, nRows * nCols), np.float32)
         status = np.zeros(nt, np.int32)
-        check(lib().gf_float_decode_batch_f32(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out),
-                                              _ptr(status)), "gf_float_decode_batch_f32")
+        _call("gf_float_decode_batch_f32", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status))
         return out, status
 
 
@@ -1003,21 +1105,17 @@ class LsCodecHip:
         offsets = np.zeros(nt + 1, np.uint64)
         types = np.zeros(nt, np.uint8)
         status = np.zeros(nt, np.int32)
-        check(lib().gf_lsop12_encode_batch_i32(self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v),
-                                               (_lib.LSOP_DEFLATE if self.deflate_enabled else 0) |
-                                               (_lib.LSOP_VALUE_CHECKSUM if self.value_checksum_enabled else 0),
-                                               _ptr(blob), cap, _ptr(offsets), _ptr(types),
-                                               _ptr(status)), "gf_lsop12_encode_batch_i32")
-        packs = [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) if status[t] == _lib.OK else None for t in range(nt)]
-        return packs, types, status
+        flags = (_lib.LSOP_DEFLATE if self.deflate_enabled else 0) | (_lib.LSOP_VALUE_CHECKSUM if self.value_checksum_enabled else 0)
+        _call("gf_lsop12_encode_batch_i32", self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), flags, _ptr(blob), cap, _ptr(offsets),
+              _ptr(types), _ptr(status))
+        return _records_out(blob, offsets, nt, status), types, status
 
     def decode_batch(self, nRows, nCols, packings):
         nt = len(packings)
         blob, offsets = _blob_of(packings)
         out = np.zeros((nt, nRows * nCols), np.int32)
         status = np.zeros(nt, np.int32)
-        check(lib().gf_lsop12_decode_batch_i32(self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out),
-                                               _ptr(status)), "gf_lsop12_decode_batch_i32")
+        _call("gf_lsop12_decode_batch_i32", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status))
         return out, status
 
     # ---- the predictor stage alone (device buffers handled here; used by tests and tools) ----
@@ -1027,17 +1125,13 @@ class LsCodecHip:
         nt = v.shape[0]
         n = int(lib().gf_lsop12_residual_count(nRows, nCols))
         stride = (n + 3) // 4 * 4
-        dv, dr, dc, ds = (DeviceBuffer(self.ctx, v.nbytes), DeviceBuffer(self.ctx, nt * stride * 4 + 16),
-                          DeviceBuffer(self.ctx, nt * 64), DeviceBuffer(self.ctx, nt * 4))
-        dv.upload(v)
-        check(lib().gf_lsop12_predict_dev(self.ctx.handle, None, nRows, nCols, nt, dv.ptr, dr.ptr, stride, dc.ptr, ds.ptr),
-              "gf_lsop12_predict_dev")
-        self.ctx.synchronize()
-        res = dr.download(np.int32, nt * stride).reshape(nt, stride)[:, :n]
-        coefs = dc.download(np.uint32, nt * 16).reshape(nt, 16)
-        status = ds.download(np.int32, nt)
-        for b in (dv, dr, dc, ds):
-            b.free()
+        with _DeviceScope(self.ctx) as s:
+            dv, dr, dc, ds = s.alloc(v.nbytes), s.alloc(nt * stride * 4 + 16), s.alloc(nt * 64), s.alloc(nt * 4)
+            dv.upload(v)
+            s.run("gf_lsop12_predict_dev", self.ctx.handle, None, nRows, nCols, nt, dv.ptr, dr.ptr, stride, dc.ptr, ds.ptr)
+            res = dr.download(np.int32, nt * stride).reshape(nt, stride)[:, :n]
+            coefs = dc.download(np.uint32, nt * 16).reshape(nt, 16)
+            status = ds.download(np.int32, nt)
         return coefs[:, 0].astype(np.int32), coefs[:, 1:13].copy().view(np.float32), res, status
 
     def reconstruct(self, nRows, nCols, seeds, coefficients, residuals):
@@ -1050,26 +1144,14 @@ class LsCodecHip:
         coefs = np.zeros((nt, 16), np.uint32)
         coefs[:, 0] = np.asarray(seeds, np.int32).view(np.uint32)
         coefs[:, 1:13] = np.ascontiguousarray(coefficients, np.float32).view(np.uint32).reshape(nt, 12)
-        dv, dr, dc, ds = (DeviceBuffer(self.ctx, nt * nRows * nCols * 4), DeviceBuffer(self.ctx, padded.nbytes + 16),
-                          DeviceBuffer(self.ctx, nt * 64), DeviceBuffer(self.ctx, nt * 4))
-        dr.upload(padded)
-        dc.upload(coefs)
-        check(lib().gf_lsop12_reconstruct_dev(self.ctx.handle, None, nRows, nCols, nt, dr.ptr, stride, dc.ptr, None, dv.ptr,
-                                              ds.ptr), "gf_lsop12_reconstruct_dev")
-        self.ctx.synchronize()
-        vals = dv.download(np.int32, nt * nRows * nCols).reshape(nt, nRows * nCols)
-        status = ds.download(np.int32, nt)
-        for b in (dv, dr, dc, ds):
-            b.free()
+        with _DeviceScope(self.ctx) as s:
+            dv, dr, dc, ds = s.alloc(nt * nRows * nCols * 4), s.alloc(padded.nbytes + 16), s.alloc(nt * 64), s.alloc(nt * 4)
+            dr.upload(padded)
+            dc.upload(coefs)
+            s.run("gf_lsop12_reconstruct_dev", self.ctx.handle, None, nRows, nCols, nt, dr.ptr, stride, dc.ptr, None, dv.ptr, ds.ptr)
+            vals = dv.download(np.int32, nt * nRows * nCols).reshape(nt, nRows * nCols)
+            status = ds.download(np.int32, nt)
         return vals, status
-
-
-CODEC_NONE, CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_CANON_HUFFMAN, CODEC_LSOP12 = 0, 1, 2, 3, 4
-STANDARD_CODEC_LIST = (CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_NONE, CODEC_CANON_HUFFMAN)    # GvrsFileSpecification.java:221-230
-ELEM_TYPES = {"int": 0, "short": 1, "float": 2, "icf": 3}                                 # GF_ELEM_*
-_ELEM_SPEC = np.dtype([("type", np.int32), ("fill_i", np.int32), ("scale", np.float32), ("offset", np.float32),
-                       ("fill_f", np.float32)])                                           # gf_elem_spec
-_ELEM_RANGE = np.dtype([("min_i", np.int32), ("max_i", np.int32), ("min_f", np.float32), ("max_f", np.float32)])   # gf_elem_range
 
 
 class CodecMasterHip:
@@ -1080,34 +1162,34 @@ class CodecMasterHip:
         self.ctx = context if context is not None else GvrsHipContext(device)
         self.codecs = np.asarray(codec_list, dtype=np.int32)
 
+    def _codecs_arg(self):
+        return self.codecs if self.codecs.size else np.zeros(1, np.int32)
+
+    def _head(self, stream=False):
+        """The arguments every entry point over a codec list begins with: the context, with stream the NULL stream, the list"""
+        return (self.ctx.handle,) + ((None,) if stream else ()) + (_ptr(self._codecs_arg()), self.codecs.size)
+
     def encode_batch(self, nRows, nCols, tiles):
         """Returns (packings: list[bytes|None], codec index used uint8 (255 = none), status)."""
         v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
         nt = v.shape[0]
-        cap = nt * (4 * nRows * nCols + 1024) + 64
         offsets = np.zeros(nt + 1, np.uint64)
         used = np.zeros(nt, np.uint8)
         status = np.zeros(nt, np.int32)
-        while True:
-            blob = np.empty(cap, np.uint8)
-            st = lib().gf_codec_master_encode_batch_i32(self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt,
-                                                        _ptr(v), _ptr(blob), cap, _ptr(offsets), _ptr(used), _ptr(status))
-            if st == _lib.ERR_CAPACITY:
-                cap = int(offsets[nt]) + 64
-                continue
-            check(st, "gf_codec_master_encode_batch_i32")
-            break
-        packs = [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) if status[t] == _lib.OK else None for t in range(nt)]
-        return packs, used, status
+        fn = lib().gf_codec_master_encode_batch_i32
+        st, blob = _grown_blob(lambda blob, cap: fn(self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt, _ptr(v), _ptr(blob),
+                                                    cap, _ptr(offsets), _ptr(used), _ptr(status)),
+                               nt * (4 * nRows * nCols + 1024) + 64, 64, offsets)
+        check(st, "gf_codec_master_encode_batch_i32")
+        return _records_out(blob, offsets, nt, status), used, status
 
     def decode_batch(self, nRows, nCols, packings):
         nt = len(packings)
         blob, offsets = _blob_of(packings)
         out = np.zeros((nt, nRows * nCols), np.int32)
         status = np.zeros(nt, np.int32)
-        check(lib().gf_codec_master_decode_batch_i32(self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt,
-                                                     _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status)),
-              "gf_codec_master_decode_batch_i32")
+        _call("gf_codec_master_decode_batch_i32", self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt, _ptr(blob),
+              _ptr(offsets), _ptr(out), _ptr(status))
         return out, status
 
     # ---- tile payloads: RasterTile.getCompressedPacking over TileElementInt.encode (one integer element per tile) ----
@@ -1119,10 +1201,18 @@ class CodecMasterHip:
         blob = np.empty(cap, np.uint8)
         offsets = np.zeros(nt + 1, np.uint64)
         used = np.zeros(nt, np.uint8)
-        check(lib().gf_tile_payload_encode_batch_i32(self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt,
-                                                     _ptr(v), _ptr(blob), cap, _ptr(offsets), _ptr(used)),
-              "gf_tile_payload_encode_batch_i32")
-        return [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(nt)], used
+        _call("gf_tile_payload_encode_batch_i32", self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt, _ptr(v), _ptr(blob),
+              cap, _ptr(offsets), _ptr(used))
+        return _records_out(blob, offsets, nt), used
+
+    def tiles_from_payloads(self, nRows, nCols, payloads):
+        nt = len(payloads)
+        blob, offsets = _blob_of(payloads)
+        out = np.zeros((nt, nRows * nCols), np.int32)
+        status = np.zeros(nt, np.int32)
+        _call("gf_tile_payload_decode_batch_i32", self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt, _ptr(blob),
+              _ptr(offsets), _ptr(out), _ptr(status))
+        return out, status
 
     # ---- tile records: RecordManager.writeTile / readTile for a batch of dirty tiles (one integer-coded element) ----
     def tile_records(self, nRows, nCols, tile_indices, tiles, element="int", fill_value=-32768, checksums=True):
@@ -1136,11 +1226,9 @@ class CodecMasterHip:
         blob = np.empty(max(cap, 16), np.uint8)
         offsets = np.zeros(nt + 1, np.uint64)
         used = np.zeros(nt, np.uint8)
-        codecs = self.codecs if self.codecs.size else np.zeros(1, np.int32)
-        check(lib().gf_tile_record_encode_batch(self.ctx.handle, _ptr(codecs), self.codecs.size, int(short), int(fill_value),
-                                                nRows, nCols, nt, _ptr(idx), _ptr(v), int(bool(checksums)), _ptr(blob), cap,
-                                                _ptr(offsets), _ptr(used)), "gf_tile_record_encode_batch")
-        return [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(nt)], used
+        _call("gf_tile_record_encode_batch", *self._head(), int(short), int(fill_value), nRows, nCols, nt, _ptr(idx), _ptr(v),
+              int(bool(checksums)), _ptr(blob), cap, _ptr(offsets), _ptr(used))
+        return _records_out(blob, offsets, nt), used
 
     def tiles_from_records(self, nRows, nCols, records, element="int", verify_checksums=True):
         """Returns (tile indices, values [nt, cells] int32 / int16, status per record)."""
@@ -1150,45 +1238,28 @@ class CodecMasterHip:
         out = np.zeros((nt, nRows * nCols), np.int16 if short else np.int32)
         idx = np.full(nt, -1, np.int32)
         status = np.zeros(nt, np.int32)
-        codecs = self.codecs if self.codecs.size else np.zeros(1, np.int32)
-        check(lib().gf_tile_record_decode_batch(self.ctx.handle, _ptr(codecs), self.codecs.size, int(short), nRows, nCols, nt,
-                                                _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), _ptr(idx), _ptr(out),
-                                                _ptr(status)), "gf_tile_record_decode_batch")
+        _call("gf_tile_record_decode_batch", *self._head(), int(short), nRows, nCols, nt, _ptr(blob), _ptr(offsets), int(bool(verify_checksums)),
+              _ptr(idx), _ptr(out), _ptr(status))
         return idx, out, status
 
     # ---- the same two readers for bytes in device memory: one upload of the bytes, everything else on the GPU ----
-    def _codecs_arg(self):
-        return self.codecs if self.codecs.size else np.zeros(1, np.int32)
-
     def record_blob_dev(self, nRows, nCols, blob, offsets, element="int", verify_checksums=True):
         """gf_tile_record_decode_batch_dev on records as they lie in a byte array: record t = blob[offsets[t]:offsets[t+1]]
         (any byte alignment, anything between and behind the records).  Uploads blob and offsets, downloads the results:
         (tile indices, values [nt, cells] int32 / int16, status per record).  A caller whose bytes or consumer are on the
         device calls the entry point itself, with DeviceBuffer pointers."""
         short = element == "short"
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        nt = offsets.size - 1
-        cells = nRows * nCols
-        item = 2 if short else 4
-        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
-        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
-        d_idx = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0xff)
-        d_val = DeviceBuffer(self.ctx, nt * cells * item + 16).fill(0)
-        d_st = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0)
-        try:
-            check(lib().gf_tile_record_decode_batch_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, int(short),
-                                                        nRows, nCols, nt, d_blob.ptr, blob.size, d_off.ptr,
-                                                        int(bool(verify_checksums)), d_idx.ptr, d_val.ptr, d_st.ptr),
-                  "gf_tile_record_decode_batch_dev")
-            self.ctx.synchronize()
-            idx = d_idx.download(np.int32, nt)
-            out = d_val.download(np.int16 if short else np.int32, nt * cells).reshape(nt, cells)
-            status = d_st.download(np.int32, nt)
-        finally:
-            for b in (d_blob, d_off, d_idx, d_val, d_st):
-                b.free()
-        return idx, out, status
+        blob, offsets = _records_in(blob, offsets)
+        nt, cells, dt = offsets.size - 1, nRows * nCols, np.dtype(np.int16 if short else np.int32)
+        with _DeviceScope(self.ctx) as s:
+            d_blob = s.upload(blob, slack=32, fill=0)
+            d_off = s.upload(offsets)
+            d_idx = s.alloc(nt * 4 + 16, fill=0xff)
+            d_val = s.alloc(nt * cells * dt.itemsize + 16, fill=0)
+            d_st = s.alloc(nt * 4 + 16, fill=0)
+            s.run("gf_tile_record_decode_batch_dev", *self._head(stream=True), int(short), nRows, nCols, nt, d_blob.ptr, blob.size, d_off.ptr,
+                  int(bool(verify_checksums)), d_idx.ptr, d_val.ptr, d_st.ptr)
+            return d_idx.download(np.int32, nt), d_val.download(dt, nt * cells).reshape(nt, cells), d_st.download(np.int32, nt)
 
     def tiles_from_records_dev(self, nRows, nCols, records, element="int", verify_checksums=True):
         """tiles_from_records with the records decoded where they lie in device memory (gf_tile_record_decode_batch_dev)."""
@@ -1203,13 +1274,11 @@ class CodecMasterHip:
         specs = np.zeros(len(elems), _ELEM_SPEC)
         dtypes = []
         for e, el in enumerate(elems):
-            kind = el if isinstance(el, str) else el[0]
-            specs[e]["type"] = ELEM_TYPES[kind]
-            specs[e]["scale"] = 1.0
-            if kind == "icf":
-                _, scale, offset, fill_i, fill_f = el
-                specs[e]["scale"], specs[e]["offset"], specs[e]["fill_i"], specs[e]["fill_f"] = scale, offset, fill_i, fill_f
-            dtypes.append({"int": np.int32, "short": np.int16}.get(kind, np.float32))
+            _, kind, params = _elem_kind(el)
+            specs[e]["type"], specs[e]["scale"] = kind.type, 1.0
+            if params is not None:
+                specs[e]["scale"], specs[e]["offset"], specs[e]["fill_i"], specs[e]["fill_f"] = params
+            dtypes.append(kind.delivered)
         return specs, dtypes
 
     def record_blob_elems_dev(self, nRows, nCols, blob, offsets, elems, verify_checksums=True):
@@ -1217,56 +1286,44 @@ class CodecMasterHip:
         len(elems) elements (see _elem_specs).  Uploads blob and offsets, downloads the results: (tile indices, [values
         [nt, cells] per element: int32 / int16 / float32], status [n_elems, nt]).  A tile is good iff all its statuses are 0."""
         specs, dtypes = self._elem_specs(elems)
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        blob, offsets = _records_in(blob, offsets)
         nt, ne, cells = offsets.size - 1, len(dtypes), nRows * nCols
-        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
-        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
-        d_idx = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0xff)
-        d_val = [DeviceBuffer(self.ctx, nt * cells * np.dtype(dt).itemsize + 16).fill(0) for dt in dtypes]
-        d_st = DeviceBuffer(self.ctx, ne * nt * 4 + 16).fill(0)
-        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_val])
-        try:
-            check(lib().gf_tile_record_decode_batch_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs),
-                                                              ne, nRows, nCols, nt, d_blob.ptr, blob.size, d_off.ptr,
-                                                              int(bool(verify_checksums)), d_idx.ptr, ptrs, d_st.ptr),
-                  "gf_tile_record_decode_batch_elems_dev")
-            self.ctx.synchronize()
+        with _DeviceScope(self.ctx) as s:
+            d_blob = s.upload(blob, slack=32, fill=0)
+            d_off = s.upload(offsets)
+            d_idx = s.alloc(nt * 4 + 16, fill=0xff)
+            d_val = [s.alloc(nt * cells * np.dtype(dt).itemsize + 16, fill=0) for dt in dtypes]
+            d_st = s.alloc(ne * nt * 4 + 16, fill=0)
+            s.run("gf_tile_record_decode_batch_elems_dev", *self._head(stream=True), _ptr(specs), ne, nRows, nCols, nt, d_blob.ptr, blob.size,
+                  d_off.ptr, int(bool(verify_checksums)), d_idx.ptr, s.ptrs(d_val), d_st.ptr)
             idx = d_idx.download(np.int32, nt)
             out = [b.download(dt, nt * cells).reshape(nt, cells) for b, dt in zip(d_val, dtypes)]
-            status = d_st.download(np.int32, ne * nt).reshape(ne, nt)
-        finally:
-            for b in [d_blob, d_off, d_idx, d_st] + d_val:
-                b.free()
-        return idx, out, status
+            return idx, out, d_st.download(np.int32, ne * nt).reshape(ne, nt)
 
     def record_blob_elems(self, nRows, nCols, blob, offsets, elems, verify_checksums=True):
         """The same through gf_tile_record_decode_batch_elems, the host-memory form (staged by the library, not pipelined);
         offsets[-1] bytes of blob are read."""
         specs, dtypes = self._elem_specs(elems)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        blob = np.concatenate([np.ascontiguousarray(blob, dtype=np.uint8), np.zeros(16, np.uint8)])
+        blob, offsets = _records_in(blob, offsets, tail=True)
         nt, ne, cells = offsets.size - 1, len(dtypes), nRows * nCols
         idx = np.full(nt, -1, np.int32)
         out = [np.zeros((nt, cells), dt) for dt in dtypes]
         status = np.zeros((ne, nt), np.int32)
-        ptrs = (C.c_void_p * ne)(*[a.ctypes.data for a in out])
-        check(lib().gf_tile_record_decode_batch_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, nRows,
-                                                      nCols, nt, _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), _ptr(idx), ptrs,
-                                                      _ptr(status)), "gf_tile_record_decode_batch_elems")
+        _call("gf_tile_record_decode_batch_elems", *self._head(), _ptr(specs), ne, nRows, nCols, nt, _ptr(blob), _ptr(offsets),
+              int(bool(verify_checksums)), _ptr(idx), _ptrs(out), _ptr(status))
         return idx, out, status
 
     # ---- records of several elements written (gf_tile_record_encode_batch_elems[_dev]) ----
-    def _elem_values(self, nRows, nCols, values_per_element, elems, fills):
+    @staticmethod
+    def _elem_values(nRows, nCols, values_per_element, elems, fills):
         """(gf_elem_spec array, [values [nt, cells] per element in the type the call takes: int32 (int, icf codes) / int16 / float32 bits])"""
-        specs, dtypes = self._elem_specs(elems)
+        specs, _ = CodecMasterHip._elem_specs(elems)
         vals = []
         for e, el in enumerate(elems):
-            kind = el if isinstance(el, str) else el[0]
-            dt = {"int": np.int32, "short": np.int16, "icf": np.int32}.get(kind, np.float32)
-            vals.append(np.ascontiguousarray(values_per_element[e], dtype=dt).reshape(-1, nRows * nCols))
-            if kind == "short":
-                specs[e]["fill_i"] = -32768 if fills is None or fills[e] is None else fills[e]
+            name, kind, _ = _elem_kind(el)
+            vals.append(np.ascontiguousarray(values_per_element[e], dtype=kind.written).reshape(-1, nRows * nCols))
+            if name == "short":
+                specs[e]["fill_i"] = kind.fill[1] if fills is None or fills[e] is None else fills[e]
         assert len({v.shape[0] for v in vals}) == 1
         return specs, vals
 
@@ -1282,11 +1339,9 @@ class CodecMasterHip:
         blob = np.empty(max(cap, 16), np.uint8)
         offsets = np.zeros(nt + 1, np.uint64)
         used = np.zeros((ne, nt), np.uint8)
-        ptrs = (C.c_void_p * ne)(*[a.ctypes.data for a in vals])
-        check(lib().gf_tile_record_encode_batch_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, nRows,
-                                                      nCols, nt, _ptr(idx), ptrs, int(bool(checksums)), _ptr(blob), cap, _ptr(offsets),
-                                                      _ptr(used)), "gf_tile_record_encode_batch_elems")
-        return [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(nt)], used
+        _call("gf_tile_record_encode_batch_elems", *self._head(), _ptr(specs), ne, nRows, nCols, nt, _ptr(idx), _ptrs(vals), int(bool(checksums)),
+              _ptr(blob), cap, _ptr(offsets), _ptr(used))
+        return _records_out(blob, offsets, nt), used
 
     def tile_records_elems_dev(self, nRows, nCols, tile_indices, values_per_element, elems, checksums=True, fills=None, blob_cap=None,
                                raw=False):
@@ -1299,143 +1354,101 @@ class CodecMasterHip:
         assert idx.size == nt
         full = nt * int(lib().gf_tile_record_max_bytes_elems(_ptr(specs), ne, nRows, nCols))
         cap = full if blob_cap is None else int(blob_cap)
-        d_val = [DeviceBuffer(self.ctx, v.nbytes + 16).upload(v) for v in vals]
-        d_idx = DeviceBuffer(self.ctx, nt * 4 + 16).upload(idx)
-        d_blob = DeviceBuffer(self.ctx, max(cap, full) + 64).fill(0xA5)
-        d_off = DeviceBuffer(self.ctx, (nt + 1) * 8 + 16).fill(0xff)
-        d_used = DeviceBuffer(self.ctx, ne * nt + 16).fill(0)
-        d_st = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0x7f)
-        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_val])
-        try:
-            check(lib().gf_tile_record_encode_batch_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs),
-                                                              ne, nRows, nCols, nt, d_idx.ptr, ptrs, int(bool(checksums)), d_blob.ptr, cap,
-                                                              d_off.ptr, d_used.ptr, d_st.ptr), "gf_tile_record_encode_batch_elems_dev")
-            self.ctx.synchronize()
+        with _DeviceScope(self.ctx) as s:
+            d_val = [s.upload(v, slack=16) for v in vals]
+            d_idx = s.upload(idx, slack=16)
+            d_blob = s.alloc(max(cap, full) + 64, fill=0xA5)
+            d_off = s.alloc((nt + 1) * 8 + 16, fill=0xff)
+            d_used = s.alloc(ne * nt + 16, fill=0)
+            d_st = s.alloc(nt * 4 + 16, fill=0x7f)
+            s.run("gf_tile_record_encode_batch_elems_dev", *self._head(stream=True), _ptr(specs), ne, nRows, nCols, nt, d_idx.ptr, s.ptrs(d_val),
+                  int(bool(checksums)), d_blob.ptr, cap, d_off.ptr, d_used.ptr, d_st.ptr)
             offsets = d_off.download(np.uint64, nt + 1)
             blob = d_blob.download(np.uint8, max(cap, full) + 64)
             used = d_used.download(np.uint8, ne * nt).reshape(ne, nt)
             status = d_st.download(np.int32, nt)
-        finally:
-            for b in [d_idx, d_blob, d_off, d_used, d_st] + d_val:
-                b.free()
         if raw:
             return blob, offsets, used, status
-        return [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(nt)], used, status
+        return _records_out(blob, offsets, nt), used, status
 
     # ---- grid blocks: GvrsElement.readBlock for a batch of records (gf_block_read_elems[_dev]) ----
     @staticmethod
     def _fill_specs(specs, elems, fills):
         """fills: per element None (INT4_NULL_CODE / -32768 / NaN) or the block's fill value; an ICF element's is its own fill_f"""
         for e, el in enumerate(elems):
-            kind = el if isinstance(el, str) else el[0]
+            _, kind, _ = _elem_kind(el)
             f = None if fills is None else fills[e]
-            if kind in ("int", "short"):
-                specs[e]["fill_i"] = (INT4_NULL_CODE if kind == "int" else -32768) if f is None else f
-            elif kind == "float":
-                specs[e]["fill_f"] = np.float32(np.nan) if f is None else f
-            else:
+            if kind.fill is None:
                 assert f is None, "an int-coded-float element is filled with the fill_f of its description"
+            else:
+                field, default = kind.fill
+                specs[e][field] = default if f is None else f
         return specs
+
+    def _read_args(self, nRows, nCols, grid_shape, rect, factor, blob, offsets, elems, fills, tail):
+        """What the block readers share.  factor None: the block itself in the delivered dtypes; else the block downsampled by it, in
+        the coarse dtypes.  -> (specs, dtypes, blob, offsets, grid, rect, the block's shape, (factor,) or ())"""
+        specs, dtypes = self._elem_specs(elems)
+        self._fill_specs(specs, elems, fills)
+        blob, offsets = _records_in(blob, offsets, tail=tail)
+        grid, rect = _grid_rect(nRows, nCols, grid_shape, rect)
+        if factor is None:
+            return specs, dtypes, blob, offsets, grid, rect, (int(rect[2]), int(rect[3])), ()
+        shape = GvrsHipContext.downsample_rect(rect, factor)[2:]
+        return specs, self._coarse_dtypes(elems, dtypes), blob, offsets, grid, rect, shape, (int(factor),)
+
+    def _read_blocks_dev(self, name, nRows, nCols, grid_shape, rect, factor, blob, offsets, elems, fills, verify_checksums):
+        specs, dtypes, blob, offsets, grid, rect, shape, factor = self._read_args(nRows, nCols, grid_shape, rect, factor, blob, offsets, elems,
+                                                                                  fills, False)
+        nt, ne, n_block = offsets.size - 1, len(dtypes), shape[0] * shape[1]
+        with _DeviceScope(self.ctx) as s:
+            d_blob = s.upload(blob, slack=32, fill=0)
+            d_off = s.upload(offsets)
+            d_blk = [s.alloc(n_block * np.dtype(dt).itemsize + 16, fill=0) for dt in dtypes]
+            d_st = s.alloc(ne * nt * 4 + 16, fill=0)
+            s.run(name, *self._head(stream=True), _ptr(specs), ne, _ptr(grid), _ptr(rect), *factor, nt, d_blob.ptr, blob.size, d_off.ptr,
+                  int(bool(verify_checksums)), s.ptrs(d_blk), d_st.ptr)
+            return [b.download(dt, n_block).reshape(shape) for b, dt in zip(d_blk, dtypes)], d_st.download(np.int32, ne * nt).reshape(ne, nt)
 
     def read_block_dev(self, nRows, nCols, grid_shape, rect, blob, offsets, elems, fills=None, verify_checksums=True):
         """gf_block_read_elems_dev: the rectangle rect = (row0, col0, n_rows, n_cols) of a grid of grid_shape = (rows, columns)
         cells cut into nRows x nCols tiles, read from tile records as they lie in a byte array (as record_blob_elems_dev; records
         in any order, tiles the bytes do not hold read as fill).  Uploads blob and offsets, downloads the results: ([block
         [n_rows, n_cols] per element: int32 / int16 / float32], status [n_elems, nt]).  The block is good iff every status is 0."""
-        specs, dtypes = self._elem_specs(elems)
-        self._fill_specs(specs, elems, fills)
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        nt, ne = offsets.size - 1, len(dtypes)
-        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
-        rect = np.ascontiguousarray(rect, np.int32)
-        n_block = int(rect[2]) * int(rect[3])
-        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
-        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
-        d_blk = [DeviceBuffer(self.ctx, n_block * np.dtype(dt).itemsize + 16).fill(0) for dt in dtypes]
-        d_st = DeviceBuffer(self.ctx, ne * nt * 4 + 16).fill(0)
-        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_blk])
-        try:
-            check(lib().gf_block_read_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, _ptr(grid),
-                                                _ptr(rect), nt, d_blob.ptr, blob.size, d_off.ptr, int(bool(verify_checksums)), ptrs, d_st.ptr),
-                  "gf_block_read_elems_dev")
-            self.ctx.synchronize()
-            out = [b.download(dt, n_block).reshape(int(rect[2]), int(rect[3])) for b, dt in zip(d_blk, dtypes)]
-            status = d_st.download(np.int32, ne * nt).reshape(ne, nt)
-        finally:
-            for b in [d_blob, d_off, d_st] + d_blk:
-                b.free()
-        return out, status
+        return self._read_blocks_dev("gf_block_read_elems_dev", nRows, nCols, grid_shape, rect, None, blob, offsets, elems, fills, verify_checksums)
 
     def read_block(self, nRows, nCols, grid_shape, rect, blob, offsets, elems, fills=None, verify_checksums=True):
         """The same through gf_block_read_elems, the host-memory form (staged by the library); offsets[-1] bytes of blob are read."""
-        specs, dtypes = self._elem_specs(elems)
-        self._fill_specs(specs, elems, fills)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        blob = np.concatenate([np.ascontiguousarray(blob, dtype=np.uint8), np.zeros(16, np.uint8)])
+        specs, dtypes, blob, offsets, grid, rect, shape, _ = self._read_args(nRows, nCols, grid_shape, rect, None, blob, offsets, elems, fills, True)
         nt, ne = offsets.size - 1, len(dtypes)
-        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
-        rect = np.ascontiguousarray(rect, np.int32)
-        out = [np.zeros((int(rect[2]), int(rect[3])), dt) for dt in dtypes]
+        out = [np.zeros(shape, dt) for dt in dtypes]
         status = np.zeros((ne, nt), np.int32)
-        ptrs = (C.c_void_p * ne)(*[a.ctypes.data for a in out])
-        check(lib().gf_block_read_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, _ptr(grid), _ptr(rect), nt,
-                                        _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), ptrs, _ptr(status)), "gf_block_read_elems")
+        _call("gf_block_read_elems", *self._head(), _ptr(specs), ne, _ptr(grid), _ptr(rect), nt, _ptr(blob), _ptr(offsets),
+              int(bool(verify_checksums)), _ptrs(out), _ptr(status))
         return out, status
 
     # ---- grid blocks read and downsampled: records in, one coarse block per element out (gf_block_read_downsampled_elems[_dev]) ----
     @staticmethod
     def _coarse_dtypes(elems, dtypes):
         """an int-coded-float element comes back as its int32 codes"""
-        return [np.int32 if (el if isinstance(el, str) else el[0]) == "icf" else dt for el, dt in zip(elems, dtypes)]
+        return [_elem_kind(el)[1].coarse for el in elems]
 
     def read_block_downsampled_dev(self, nRows, nCols, grid_shape, rect, factor, blob, offsets, elems, fills=None, verify_checksums=True):
         """gf_block_read_downsampled_elems_dev: read_block_dev's arguments plus factor.  Returns ([coarse block [n_rows', n_cols'] per
         element for downsample_rect(rect, factor): int32 / int16 / float32, an "icf" element as int32 codes], status [n_elems, nt]);
         the blocks are good iff every status is 0."""
-        specs, dtypes = self._elem_specs(elems)
-        self._fill_specs(specs, elems, fills)
-        dtypes = self._coarse_dtypes(elems, dtypes)
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        nt, ne = offsets.size - 1, len(dtypes)
-        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
-        rect = np.ascontiguousarray(rect, np.int32)
-        _, _, n_rows, n_cols = GvrsHipContext.downsample_rect(rect, factor)
-        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
-        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
-        d_out = [DeviceBuffer(self.ctx, n_rows * n_cols * np.dtype(dt).itemsize + 16).fill(0) for dt in dtypes]
-        d_st = DeviceBuffer(self.ctx, ne * nt * 4 + 16).fill(0)
-        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_out])
-        try:
-            check(lib().gf_block_read_downsampled_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne,
-                                                            _ptr(grid), _ptr(rect), int(factor), nt, d_blob.ptr, blob.size, d_off.ptr,
-                                                            int(bool(verify_checksums)), ptrs, d_st.ptr), "gf_block_read_downsampled_elems_dev")
-            self.ctx.synchronize()
-            out = [b.download(dt, n_rows * n_cols).reshape(n_rows, n_cols) for b, dt in zip(d_out, dtypes)]
-            status = d_st.download(np.int32, ne * nt).reshape(ne, nt)
-        finally:
-            for b in [d_blob, d_off, d_st] + d_out:
-                b.free()
-        return out, status
+        return self._read_blocks_dev("gf_block_read_downsampled_elems_dev", nRows, nCols, grid_shape, rect, factor, blob, offsets, elems, fills,
+                                     verify_checksums)
 
     def read_block_downsampled(self, nRows, nCols, grid_shape, rect, factor, blob, offsets, elems, fills=None, verify_checksums=True):
         """The same through gf_block_read_downsampled_elems, the host-memory form; offsets[-1] bytes of blob are read."""
-        specs, dtypes = self._elem_specs(elems)
-        self._fill_specs(specs, elems, fills)
-        dtypes = self._coarse_dtypes(elems, dtypes)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        blob = np.concatenate([np.ascontiguousarray(blob, dtype=np.uint8), np.zeros(16, np.uint8)])
+        specs, dtypes, blob, offsets, grid, rect, (n_rows, n_cols), factor = self._read_args(nRows, nCols, grid_shape, rect, factor, blob, offsets,
+                                                                                             elems, fills, True)
         nt, ne = offsets.size - 1, len(dtypes)
-        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
-        rect = np.ascontiguousarray(rect, np.int32)
-        _, _, n_rows, n_cols = GvrsHipContext.downsample_rect(rect, factor)
         out = [np.zeros(max(n_rows * n_cols, 1), dt) for dt in dtypes]
         status = np.zeros((ne, nt), np.int32)
-        ptrs = (C.c_void_p * ne)(*[a.ctypes.data for a in out])
-        check(lib().gf_block_read_downsampled_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs), ne, _ptr(grid),
-                                                    _ptr(rect), int(factor), nt, _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), ptrs,
-                                                    _ptr(status)), "gf_block_read_downsampled_elems")
+        _call("gf_block_read_downsampled_elems", *self._head(), _ptr(specs), ne, _ptr(grid), _ptr(rect), *factor, nt, _ptr(blob), _ptr(offsets),
+              int(bool(verify_checksums)), _ptrs(out), _ptr(status))
         return [a[:n_rows * n_cols].reshape(n_rows, n_cols) for a in out], status
 
     # ---- grid blocks written: raster in, tile records out (gf_block_write_elems[_dev]) ----
@@ -1446,37 +1459,72 @@ class CodecMasterHip:
             return None
         out = np.zeros(len(elems), _ELEM_RANGE)
         for e, el in enumerate(elems):
-            kind = el if isinstance(el, str) else el[0]
-            r = ranges[e]
-            if kind in ("int", "short"):
-                out[e]["min_i"], out[e]["max_i"] = ((INT4_NULL_CODE + 1, 2 ** 31 - 1) if kind == "int" else (-32767, 32767)) if r is None else r
-            elif kind == "float":
-                out[e]["min_f"], out[e]["max_f"] = (-np.inf, np.inf) if r is None else r
-            else:
+            name, kind, _ = _elem_kind(el)
+            suffix, lo, hi = kind.range
+            if name == "icf":                  # the codes' range as values
                 scale, offset = np.float32(specs[e]["scale"]), np.float32(specs[e]["offset"])
-                default = (np.float32(INT4_NULL_CODE + 1) / scale + offset, np.float32(2 ** 31 - 2) / scale + offset)
-                out[e]["min_f"], out[e]["max_f"] = default if r is None else r
+                lo, hi = np.float32(lo) / scale + offset, np.float32(hi) / scale + offset
+            out[e]["min_" + suffix], out[e]["max_" + suffix] = (lo, hi) if ranges[e] is None else ranges[e]
         return out
 
-    def _block_write_args(self, nRows, nCols, grid_shape, rect, blocks, elems, fills, ranges, old):
+    def _write_dev(self, name, head, source, n_elems, n_out, full, old, checksums, verify_old_checksums, blob_cap, raw):
+        """What write_block_dev and image_write_dev share: source (the arrays uploaded first, by the function that turns their buffers
+        into the call's arguments behind head), the old records, the output buffers, the call and what comes back."""
+        arrays, source_args = source
+        old_blob, old_off, n_old = _old_records(old)
+        cap = full if blob_cap is None else int(blob_cap)
+        with _DeviceScope(self.ctx) as s:
+            d_src = [s.upload(a, slack=16) for a in arrays]
+            d_oblob = s.upload(old_blob, slack=32, fill=0)
+            d_ooff = s.upload(old_off, slack=16)
+            d_blob = s.alloc(max(cap, full) + 64, fill=0xA5)
+            d_off = s.alloc((n_out + 1) * 8 + 16, fill=0xff)
+            d_idx = s.alloc(n_out * 4 + 16, fill=0x7f)
+            d_used = s.alloc(n_elems * n_out + 16, fill=0)
+            d_st = s.alloc(n_out * 4 + 16, fill=0x7f)
+            s.run(name, *head, source_args(d_src), n_old, d_oblob.ptr if n_old else None, int(old_off[-1]) if n_old else 0,
+                  d_ooff.ptr if n_old else None, int(bool(verify_old_checksums)), int(bool(checksums)), d_blob.ptr, cap, d_off.ptr, d_idx.ptr,
+                  d_used.ptr, d_st.ptr)
+            offsets = d_off.download(np.uint64, n_out + 1)
+            blob = d_blob.download(np.uint8, max(cap, full) + 64)
+            idx = d_idx.download(np.int32, n_out)
+            used = d_used.download(np.uint8, n_elems * n_out).reshape(n_elems, n_out)
+            status = d_st.download(np.int32, n_out)
+        if raw:
+            return idx, blob, offsets, used, status
+        return idx, _records_out(blob, offsets, n_out), used, status
+
+    def _write_host(self, name, head, source, n_elems, n_out, full, old, checksums, verify_old_checksums, blob_cap, checked=True):
+        """The same for write_block and image_write, the host forms -> (the call's return value, checked unless told otherwise; tile
+        indices, blob, offsets, codec used, status, the blob's capacity)"""
+        old_blob, old_off, n_old = _old_records(old)
+        old_blob, old_off = _records_in(old_blob, old_off, tail=True)
+        cap = full if blob_cap is None else int(blob_cap)
+        blob = np.empty(max(cap, 16), np.uint8)
+        offsets = np.zeros(n_out + 1, np.uint64)
+        idx = np.full(n_out, -1, np.int32)
+        used = np.zeros((n_elems, n_out), np.uint8)
+        status = np.full(n_out, 0x7f7f7f7f, np.int32)
+        rc = getattr(lib(), name)(*head, source, n_old, _ptr(old_blob) if n_old else None, _ptr(old_off) if n_old else None,
+                                  int(bool(verify_old_checksums)), int(bool(checksums)), _ptr(blob), cap, _ptr(offsets), _ptr(idx), _ptr(used),
+                                  _ptr(status))
+        if checked:
+            check(rc, name)
+        return rc, idx, blob, offsets, used, status, cap
+
+    def _block_write_args(self, nRows, nCols, grid_shape, rect, blocks, elems, fills, ranges):
+        """-> (the call's arguments from the element specs to rect; the arrays they point into, which the caller holds until the call is
+        over; the blocks flat in their dtypes; the number of tiles written; room for every record in standard form)"""
         specs, dtypes = self._elem_specs(elems)
         self._fill_specs(specs, elems, fills)
         rng = self._range_specs(specs, elems, ranges)
-        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
-        rect = np.ascontiguousarray(rect, np.int32)
+        grid, rect = _grid_rect(nRows, nCols, grid_shape, rect)
         n_block = int(rect[2]) * int(rect[3])
         blocks = [np.ascontiguousarray(b, dtype=dt).reshape(-1) for b, dt in zip(blocks, dtypes)]
         assert len(blocks) == len(dtypes) and all(b.size == n_block for b in blocks)
-        tr = tuple(C.c_int32() for _ in range(4))
-        check(lib().gf_block_tile_rect(_ptr(grid), _ptr(rect), *[C.byref(x) for x in tr]), "gf_block_tile_rect")
-        n_out = tr[2].value * tr[3].value
-        if old is None:
-            old_blob, old_off = np.zeros(16, np.uint8), np.zeros(1, np.uint64)
-        else:
-            old_blob = np.ascontiguousarray(old[0], dtype=np.uint8)
-            old_off = np.ascontiguousarray(old[1], dtype=np.uint64)
+        n_out = _tiles_of_rect(grid, rect)
         full = n_out * int(lib().gf_tile_record_max_bytes_elems(_ptr(specs), len(dtypes), nRows, nCols))
-        return specs, rng, grid, rect, blocks, n_out, old_blob, old_off, full
+        return (_ptr(specs), None if rng is None else _ptr(rng), len(blocks), _ptr(grid), _ptr(rect)), (specs, rng, grid, rect), blocks, n_out, full
 
     def write_block_dev(self, nRows, nCols, grid_shape, rect, blocks, elems, fills=None, ranges=None, old=None, checksums=True,
                         verify_old_checksums=True, blob_cap=None, raw=False):
@@ -1486,82 +1534,38 @@ class CodecMasterHip:
         file already holds, merged into partly covered tiles.  Uploads, calls, synchronises, downloads: (tile indices [n_out],
         records: list[bytes], b"" for a tile without one, codec used [n_elems, n_out], status [n_out]); raw=True: (tile indices,
         blob, offsets, codec used, status) with the whole blob of blob_cap bytes + 64 pre-filled with 0xA5."""
-        specs, rng, grid, rect, blocks, n_out, old_blob, old_off, full = self._block_write_args(nRows, nCols, grid_shape, rect, blocks, elems,
-                                                                                                fills, ranges, old)
-        ne, n_old = len(blocks), old_off.size - 1
-        cap = full if blob_cap is None else int(blob_cap)
-        d_blk = [DeviceBuffer(self.ctx, b.nbytes + 16).upload(b) for b in blocks]
-        d_oblob = DeviceBuffer(self.ctx, old_blob.size + 32).fill(0).upload(old_blob)
-        d_ooff = DeviceBuffer(self.ctx, old_off.nbytes + 16).upload(old_off)
-        d_blob = DeviceBuffer(self.ctx, max(cap, full) + 64).fill(0xA5)
-        d_off = DeviceBuffer(self.ctx, (n_out + 1) * 8 + 16).fill(0xff)
-        d_idx = DeviceBuffer(self.ctx, n_out * 4 + 16).fill(0x7f)
-        d_used = DeviceBuffer(self.ctx, ne * n_out + 16).fill(0)
-        d_st = DeviceBuffer(self.ctx, n_out * 4 + 16).fill(0x7f)
-        ptrs = (C.c_void_p * ne)(*[b.ptr.value for b in d_blk])
-        try:
-            check(lib().gf_block_write_elems_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs),
-                                                 None if rng is None else _ptr(rng), ne, _ptr(grid), _ptr(rect), ptrs, n_old,
-                                                 d_oblob.ptr if n_old else None, int(old_off[-1]) if n_old else 0, d_ooff.ptr if n_old else None,
-                                                 int(bool(verify_old_checksums)), int(bool(checksums)), d_blob.ptr, cap, d_off.ptr, d_idx.ptr,
-                                                 d_used.ptr, d_st.ptr), "gf_block_write_elems_dev")
-            self.ctx.synchronize()
-            offsets = d_off.download(np.uint64, n_out + 1)
-            blob = d_blob.download(np.uint8, max(cap, full) + 64)
-            idx = d_idx.download(np.int32, n_out)
-            used = d_used.download(np.uint8, ne * n_out).reshape(ne, n_out)
-            status = d_st.download(np.int32, n_out)
-        finally:
-            for b in [d_oblob, d_ooff, d_blob, d_off, d_idx, d_used, d_st] + d_blk:
-                b.free()
-        if raw:
-            return idx, blob, offsets, used, status
-        return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
+        args, _held, blocks, n_out, full = self._block_write_args(nRows, nCols, grid_shape, rect, blocks, elems, fills, ranges)
+        return self._write_dev("gf_block_write_elems_dev", self._head(stream=True) + args, (blocks, _ptrs), len(blocks), n_out, full, old,
+                               checksums, verify_old_checksums, blob_cap, raw)
 
     def write_block(self, nRows, nCols, grid_shape, rect, blocks, elems, fills=None, ranges=None, old=None, checksums=True,
                     verify_old_checksums=True, blob_cap=None, return_code=False):
         """The same through gf_block_write_elems, the host-memory form, which takes any codec list.  Returns (tile indices, records,
         codec used, status); a negative per-tile status or too small a blob_cap raises as the library returns it, unless
         return_code is set: then (the call's return value, tile indices, records, codec used, status, offsets) come back."""
-        specs, rng, grid, rect, blocks, n_out, old_blob, old_off, full = self._block_write_args(nRows, nCols, grid_shape, rect, blocks, elems,
-                                                                                                fills, ranges, old)
-        ne, n_old = len(blocks), old_off.size - 1
-        cap = full if blob_cap is None else int(blob_cap)
-        old_blob = np.concatenate([old_blob, np.zeros(16, np.uint8)])
-        blob = np.empty(max(cap, 16), np.uint8)
-        offsets = np.zeros(n_out + 1, np.uint64)
-        idx = np.full(n_out, -1, np.int32)
-        used = np.zeros((ne, n_out), np.uint8)
-        status = np.full(n_out, 0x7f7f7f7f, np.int32)
-        ptrs = (C.c_void_p * ne)(*[b.ctypes.data for b in blocks])
-        rc = lib().gf_block_write_elems(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, _ptr(specs),
-                                        None if rng is None else _ptr(rng), ne, _ptr(grid), _ptr(rect), ptrs, n_old,
-                                        _ptr(old_blob) if n_old else None, _ptr(old_off) if n_old else None, int(bool(verify_old_checksums)),
-                                        int(bool(checksums)), _ptr(blob), cap, _ptr(offsets), _ptr(idx), _ptr(used), _ptr(status))
+        args, _held, blocks, n_out, full = self._block_write_args(nRows, nCols, grid_shape, rect, blocks, elems, fills, ranges)
+        rc, idx, blob, offsets, used, status, cap = self._write_host("gf_block_write_elems", self._head() + args, _ptrs(blocks), len(blocks), n_out,
+                                                                     full, old, checksums, verify_old_checksums, blob_cap,
+                                                                     checked=not return_code)
         if return_code:
             fits = int(offsets[-1]) <= cap
-            return rc, idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) if fits else None for t in range(n_out)], used, status, offsets
-        check(rc, "gf_block_write_elems")
-        return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
+            return rc, idx, (_records_out(blob, offsets, n_out) if fits else [None] * n_out), used, status, offsets
+        return idx, _records_out(blob, offsets, n_out), used, status
 
     # ---- ARGB images stored as tile records of three elements and read back (gf_image_write[_dev], gf_image_read[_dev]) ----
     def _image_args(self, nRows, nCols, grid_shape, rect, model, elem_type, fill):
         model, et, _ = GvrsHipContext._image_kind(model, elem_type)
-        fill = (INT4_NULL_CODE if et == 0 else -32768) if fill is None else int(fill)
+        fill = _ELEM_KINDS["int" if et == ELEM_TYPES["int"] else "short"].fill[1] if fill is None else int(fill)
         specs = np.zeros(3, _ELEM_SPEC)
         specs["type"], specs["fill_i"] = et, fill
-        grid = np.array([grid_shape[0], grid_shape[1], nRows, nCols], np.int32)
-        rect = np.ascontiguousarray(rect, np.int32)
-        tr = tuple(C.c_int32() for _ in range(4))
-        check(lib().gf_block_tile_rect(_ptr(grid), _ptr(rect), *[C.byref(x) for x in tr]), "gf_block_tile_rect")
-        n_out = tr[2].value * tr[3].value
+        grid, rect = _grid_rect(nRows, nCols, grid_shape, rect)
+        n_out = _tiles_of_rect(grid, rect)
         full = n_out * int(lib().gf_tile_record_max_bytes_elems(_ptr(specs), 3, nRows, nCols))
         return model, et, fill, grid, rect, n_out, full
 
     @staticmethod
     def _image_words(argb, rect):
-        a = np.asarray(argb)
-        a = np.ascontiguousarray(a).view(np.int32) if a.dtype == np.uint32 else np.ascontiguousarray(a, np.int32)
+        a = _argb_words(argb)
         assert a.size == int(rect[2]) * int(rect[3])
         return a.reshape(-1)
 
@@ -1572,35 +1576,8 @@ class CodecMasterHip:
         returning what it returns.  Uploads, calls, synchronises, downloads."""
         model, et, fill, grid, rect, n_out, full = self._image_args(nRows, nCols, grid_shape, rect, model, elem_type, fill)
         argb = self._image_words(argb, rect)
-        old_blob, old_off = (np.zeros(16, np.uint8), np.zeros(1, np.uint64)) if old is None else (
-            np.ascontiguousarray(old[0], dtype=np.uint8), np.ascontiguousarray(old[1], dtype=np.uint64))
-        n_old = old_off.size - 1
-        cap = full if blob_cap is None else int(blob_cap)
-        d_argb = DeviceBuffer(self.ctx, argb.nbytes + 16).upload(argb)
-        d_oblob = DeviceBuffer(self.ctx, old_blob.size + 32).fill(0).upload(old_blob)
-        d_ooff = DeviceBuffer(self.ctx, old_off.nbytes + 16).upload(old_off)
-        d_blob = DeviceBuffer(self.ctx, max(cap, full) + 64).fill(0xA5)
-        d_off = DeviceBuffer(self.ctx, (n_out + 1) * 8 + 16).fill(0xff)
-        d_idx = DeviceBuffer(self.ctx, n_out * 4 + 16).fill(0x7f)
-        d_used = DeviceBuffer(self.ctx, 3 * n_out + 16).fill(0)
-        d_st = DeviceBuffer(self.ctx, n_out * 4 + 16).fill(0x7f)
-        try:
-            check(lib().gf_image_write_dev(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, model, et, fill, _ptr(grid), _ptr(rect),
-                                           d_argb.ptr, n_old, d_oblob.ptr if n_old else None, int(old_off[-1]) if n_old else 0,
-                                           d_ooff.ptr if n_old else None, int(bool(verify_old_checksums)), int(bool(checksums)), d_blob.ptr, cap,
-                                           d_off.ptr, d_idx.ptr, d_used.ptr, d_st.ptr), "gf_image_write_dev")
-            self.ctx.synchronize()
-            offsets = d_off.download(np.uint64, n_out + 1)
-            blob = d_blob.download(np.uint8, max(cap, full) + 64)
-            idx = d_idx.download(np.int32, n_out)
-            used = d_used.download(np.uint8, 3 * n_out).reshape(3, n_out)
-            status = d_st.download(np.int32, n_out)
-        finally:
-            for b in (d_argb, d_oblob, d_ooff, d_blob, d_off, d_idx, d_used, d_st):
-                b.free()
-        if raw:
-            return idx, blob, offsets, used, status
-        return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
+        return self._write_dev("gf_image_write_dev", self._head() + (model, et, fill, _ptr(grid), _ptr(rect)), ([argb], lambda d: d[0].ptr), 3,
+                               n_out, full, old, checksums, verify_old_checksums, blob_cap, raw)
 
     def image_write(self, nRows, nCols, grid_shape, rect, argb, model="ycocg", elem_type="short", fill=None, old=None, checksums=True,
                     verify_old_checksums=True, blob_cap=None):
@@ -1608,92 +1585,56 @@ class CodecMasterHip:
         status); a negative per-tile status or too small a blob_cap raises."""
         model, et, fill, grid, rect, n_out, full = self._image_args(nRows, nCols, grid_shape, rect, model, elem_type, fill)
         argb = self._image_words(argb, rect)
-        old_blob, old_off = (np.zeros(16, np.uint8), np.zeros(1, np.uint64)) if old is None else (
-            np.ascontiguousarray(old[0], dtype=np.uint8), np.ascontiguousarray(old[1], dtype=np.uint64))
-        n_old = old_off.size - 1
-        cap = full if blob_cap is None else int(blob_cap)
-        old_blob = np.concatenate([old_blob, np.zeros(16, np.uint8)])
-        blob = np.empty(max(cap, 16), np.uint8)
-        offsets = np.zeros(n_out + 1, np.uint64)
-        idx = np.full(n_out, -1, np.int32)
-        used = np.zeros((3, n_out), np.uint8)
-        status = np.full(n_out, 0x7f7f7f7f, np.int32)
-        check(lib().gf_image_write(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, model, et, fill, _ptr(grid), _ptr(rect), _ptr(argb),
-                                   n_old, _ptr(old_blob) if n_old else None, _ptr(old_off) if n_old else None, int(bool(verify_old_checksums)),
-                                   int(bool(checksums)), _ptr(blob), cap, _ptr(offsets), _ptr(idx), _ptr(used), _ptr(status)), "gf_image_write")
-        return idx, [bytes(blob[int(offsets[t]):int(offsets[t + 1])]) for t in range(n_out)], used, status
+        _, idx, blob, offsets, used, status, _ = self._write_host("gf_image_write", self._head() + (model, et, fill, _ptr(grid), _ptr(rect)),
+                                                                   _ptr(argb), 3, n_out, full, old, checksums, verify_old_checksums, blob_cap)
+        return idx, _records_out(blob, offsets, n_out), used, status
 
     def image_read_dev(self, nRows, nCols, grid_shape, rect, blob, offsets, model="ycocg", elem_type="short", fill=None, verify_checksums=True):
         """gf_image_read_dev: rect's pixels read from tile records of three elements as image_write_dev writes them: (argb [n_rows,
         n_cols] int32, status [3, n_records]).  The pixels of tiles the bytes do not hold are the join of three fills."""
         model, et, fill, grid, rect, _, _ = self._image_args(nRows, nCols, grid_shape, rect, model, elem_type, fill)
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        blob, offsets = _records_in(blob, offsets)
         nt, n_px = offsets.size - 1, int(rect[2]) * int(rect[3])
-        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
-        d_off = DeviceBuffer(self.ctx, offsets.nbytes).upload(offsets)
-        d_argb = DeviceBuffer(self.ctx, n_px * 4 + 16).fill(0)
-        d_st = DeviceBuffer(self.ctx, 3 * nt * 4 + 16).fill(0)
-        try:
-            check(lib().gf_image_read_dev(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, model, et, fill, _ptr(grid), _ptr(rect), nt,
-                                          d_blob.ptr, blob.size, d_off.ptr, int(bool(verify_checksums)), d_argb.ptr, d_st.ptr), "gf_image_read_dev")
-            self.ctx.synchronize()
-            argb = d_argb.download(np.int32, n_px).reshape(int(rect[2]), int(rect[3]))
-            status = d_st.download(np.int32, 3 * nt).reshape(3, nt)
-        finally:
-            for b in (d_blob, d_off, d_argb, d_st):
-                b.free()
-        return argb, status
+        with _DeviceScope(self.ctx) as s:
+            d_blob = s.upload(blob, slack=32, fill=0)
+            d_off = s.upload(offsets)
+            d_argb = s.alloc(n_px * 4 + 16, fill=0)
+            d_st = s.alloc(3 * nt * 4 + 16, fill=0)
+            s.run("gf_image_read_dev", *self._head(), model, et, fill, _ptr(grid), _ptr(rect), nt, d_blob.ptr, blob.size, d_off.ptr,
+                  int(bool(verify_checksums)), d_argb.ptr, d_st.ptr)
+            return d_argb.download(np.int32, n_px).reshape(int(rect[2]), int(rect[3])), d_st.download(np.int32, 3 * nt).reshape(3, nt)
 
     def image_read(self, nRows, nCols, grid_shape, rect, blob, offsets, model="ycocg", elem_type="short", fill=None, verify_checksums=True):
         """The same through gf_image_read, the host-memory form; offsets[-1] bytes of blob are read."""
         model, et, fill, grid, rect, _, _ = self._image_args(nRows, nCols, grid_shape, rect, model, elem_type, fill)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        blob = np.concatenate([np.ascontiguousarray(blob, dtype=np.uint8), np.zeros(16, np.uint8)])
+        blob, offsets = _records_in(blob, offsets, tail=True)
         nt = offsets.size - 1
         argb = np.zeros((int(rect[2]), int(rect[3])), np.int32)
         status = np.zeros((3, nt), np.int32)
-        check(lib().gf_image_read(self.ctx.handle, _ptr(self._codecs_arg()), self.codecs.size, model, et, fill, _ptr(grid), _ptr(rect), nt,
-                                  _ptr(blob), _ptr(offsets), int(bool(verify_checksums)), _ptr(argb), _ptr(status)), "gf_image_read")
+        _call("gf_image_read", *self._head(), model, et, fill, _ptr(grid), _ptr(rect), nt, _ptr(blob), _ptr(offsets), int(bool(verify_checksums)),
+              _ptr(argb), _ptr(status))
         return argb, status
 
+    # ---- packings in device memory (gf_codec_master_decode_batch_i32_dev) ----
     def packing_blob_dev(self, nRows, nCols, blob, offsets, lengths):
         """gf_codec_master_decode_batch_i32_dev: packing t = blob[offsets[t]:offsets[t]+lengths[t]].  Returns (values, status)."""
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        blob, offsets = _records_in(blob, offsets)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         nt = lengths.size
         assert offsets.size == nt
         cells = nRows * nCols
-        d_blob = DeviceBuffer(self.ctx, blob.size + 32).fill(0).upload(blob)
-        d_off = DeviceBuffer(self.ctx, offsets.nbytes + 16).upload(offsets)
-        d_len = DeviceBuffer(self.ctx, lengths.nbytes + 16).upload(lengths)
-        d_val = DeviceBuffer(self.ctx, nt * cells * 4 + 16).fill(0)
-        d_st = DeviceBuffer(self.ctx, nt * 4 + 16).fill(0)
-        try:
-            check(lib().gf_codec_master_decode_batch_i32_dev(self.ctx.handle, None, _ptr(self._codecs_arg()), self.codecs.size, nRows,
-                                                             nCols, nt, d_blob.ptr, blob.size, d_off.ptr, d_len.ptr, d_val.ptr,
-                                                             d_st.ptr), "gf_codec_master_decode_batch_i32_dev")
-            self.ctx.synchronize()
-            out = d_val.download(np.int32, nt * cells).reshape(nt, cells)
-            status = d_st.download(np.int32, nt)
-        finally:
-            for b in (d_blob, d_off, d_len, d_val, d_st):
-                b.free()
-        return out, status
+        with _DeviceScope(self.ctx) as s:
+            d_blob = s.upload(blob, slack=32, fill=0)
+            d_off = s.upload(offsets, slack=16)
+            d_len = s.upload(lengths, slack=16)
+            d_val = s.alloc(nt * cells * 4 + 16, fill=0)
+            d_st = s.alloc(nt * 4 + 16, fill=0)
+            s.run("gf_codec_master_decode_batch_i32_dev", *self._head(stream=True), nRows, nCols, nt, d_blob.ptr, blob.size, d_off.ptr, d_len.ptr,
+                  d_val.ptr, d_st.ptr)
+            return d_val.download(np.int32, nt * cells).reshape(nt, cells), d_st.download(np.int32, nt)
 
     def decode_batch_dev(self, nRows, nCols, packings):
         """decode_batch with the packings decoded where they lie in device memory (gf_codec_master_decode_batch_i32_dev)."""
         lengths = np.array([len(p) for p in packings], np.uint32)
         blob, offsets = _blob_of(packings)
         return self.packing_blob_dev(nRows, nCols, blob[:int(offsets[-1])], offsets[:-1], lengths)
-
-    def tiles_from_payloads(self, nRows, nCols, payloads):
-        nt = len(payloads)
-        blob, offsets = _blob_of(payloads)
-        out = np.zeros((nt, nRows * nCols), np.int32)
-        status = np.zeros(nt, np.int32)
-        check(lib().gf_tile_payload_decode_batch_i32(self.ctx.handle, _ptr(self.codecs), self.codecs.size, nRows, nCols, nt,
-                                                     _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status)),
-              "gf_tile_payload_decode_batch_i32")
-        return out, status
