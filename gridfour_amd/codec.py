@@ -1154,6 +1154,133 @@ class LsCodecHip:
         return vals, status
 
 
+class LsCodec08Hip:
+    """Drop-in for org.gridfour.lsop.LsEncoder08 + LsDecoder08 (codec id "LSOP08", the 3 x 3-neighbourhood sibling of LSOP12), computed
+    on the MI355X.  encode / encode_batch give the reference's choice between the Huffman and the Deflate container (the latter with
+    the host's zlib, as the reference uses the JDK's); encode_batch_dev is the device encoder, which writes the Huffman container."""
+
+    def __init__(self, context=None, device=0):
+        self.ctx = context if context is not None else GvrsHipContext(device)
+
+    # ---- ICompressionEncoder ----
+    def encode(self, codecIndex, nRows, nCols, values):
+        packs, _, status = self.encode_batch(codecIndex, nRows, nCols, np.asarray(values).reshape(1, -1))
+        if status[0] == _lib.DECLINED:
+            return None
+        check(int(status[0]), "gf_lsop08_encode_batch_i32")
+        return packs[0]
+
+    def encodeFloats(self, codecIndex, nRows, nCols, values):
+        return None                                             # LsEncoder08.java:140-142
+
+    def implementsFloatingPointEncoding(self):
+        return False
+
+    def implementsIntegerEncoding(self):
+        return True
+
+    # ---- ICompressionDecoder ----
+    def decode(self, nRows, nColumns, packing):
+        vals, status = self.decode_batch(nRows, nColumns, [packing])
+        if status[0] in (_lib.ERR_FORMAT, _lib.ERR_BOUNDS):
+            raise IOError(lib().gf_status_string(int(status[0])).decode())
+        check(int(status[0]), "gf_lsop08_decode_batch_i32")
+        return vals[0]
+
+    def decodeFloats(self, nRows, nColumns, packing):
+        return None
+
+    # ---- batched forms (host memory) ----
+    def encode_batch(self, codecIndex, nRows, nCols, tiles):
+        """Returns (packings: list[bytes|None], container types uint8, status int32)."""
+        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
+        nt = v.shape[0]
+        cap = nt * int(lib().gf_lsop08_max_packing(nRows, nCols)) + 64
+        blob = np.empty(cap, np.uint8)
+        offsets = np.zeros(nt + 1, np.uint64)
+        types = np.zeros(nt, np.uint8)
+        status = np.zeros(nt, np.int32)
+        _call("gf_lsop08_encode_batch_i32", self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), _ptr(blob), cap, _ptr(offsets),
+              _ptr(types), _ptr(status))
+        return _records_out(blob, offsets, nt, status), types, status
+
+    def decode_batch(self, nRows, nCols, packings):
+        nt = len(packings)
+        blob, offsets = _blob_of(packings)
+        out = np.zeros((nt, nRows * nCols), np.int32)
+        status = np.zeros(nt, np.int32)
+        _call("gf_lsop08_decode_batch_i32", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status))
+        return out, status
+
+    # ---- the device forms (device buffers handled here; used by tests and tools) ----
+    @staticmethod
+    def _strides(nRows, nCols):
+        n = int(lib().gf_lsop08_residual_count(nRows, nCols))
+        return n, max(4, (n + 3) // 4 * 4)
+
+    def encode_batch_dev(self, codecIndex, nRows, nCols, tiles):
+        """gf_lsop08_encode_batch_i32_dev: the Huffman container of every tile.  Returns (packings: list[bytes|None], status)."""
+        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
+        nt = v.shape[0]
+        _, stride = self._strides(nRows, nCols)
+        slot = max(64, int(lib().gf_lsop08_max_packing(nRows, nCols)))
+        with _DeviceScope(self.ctx) as s:
+            dv, do, dl, ds = s.upload(v), s.alloc(nt * slot + 16), s.alloc(nt * 4), s.alloc(nt * 4)
+            dr, dc, d2 = s.alloc(nt * stride * 4 + 16), s.alloc(nt * 64), s.alloc(nt * 4)
+            s.run("gf_lsop08_encode_batch_i32_dev", self.ctx.handle, codecIndex, nRows, nCols, nt, dv.ptr, do.ptr, slot, dl.ptr, ds.ptr,
+                  dr.ptr, stride, dc.ptr, d2.ptr)
+            status = ds.download(np.int32, nt)
+            lengths = dl.download(np.uint32, nt)
+            slots = do.download(np.uint8, nt * slot).reshape(nt, slot)
+        return [bytes(slots[t, :lengths[t]]) if status[t] == _lib.OK else None for t in range(nt)], status
+
+    def decode_batch_dev(self, nRows, nCols, packings):
+        """gf_lsop08_decode_batch_i32_dev on packings laid back to back in device memory.  Returns (values, status)."""
+        nt = len(packings)
+        blob, offsets = _blob_of(packings)
+        lengths = np.diff(offsets).astype(np.uint32)
+        _, stride = self._strides(nRows, nCols)
+        with _DeviceScope(self.ctx) as s:
+            db, dof, dl = s.upload(blob, slack=16), s.upload(offsets), s.upload(lengths)
+            dv, ds = s.alloc(nt * nRows * nCols * 4), s.alloc(nt * 4)
+            dr, dc, d2 = s.alloc(nt * stride * 4 + 16), s.alloc(nt * 64), s.alloc(nt * 4)
+            s.run("gf_lsop08_decode_batch_i32_dev", self.ctx.handle, nRows, nCols, nt, db.ptr, int(offsets[-1]), dof.ptr, 0, dl.ptr, dv.ptr,
+                  ds.ptr, dr.ptr, stride, dc.ptr, d2.ptr)
+            vals = dv.download(np.int32, nt * nRows * nCols).reshape(nt, nRows * nCols)
+            status = ds.download(np.int32, nt)
+        return vals, status
+
+    def predict(self, nRows, nCols, tiles):
+        """LsOptimalPredictor08.encode: returns (seed, coefficients float32[nt,8], residuals int32[nt,n], status)."""
+        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
+        nt = v.shape[0]
+        n, stride = self._strides(nRows, nCols)
+        with _DeviceScope(self.ctx) as s:
+            dv, dr, dc, ds = s.upload(v), s.alloc(nt * stride * 4 + 16), s.alloc(nt * 64, fill=0), s.alloc(nt * 4)
+            s.run("gf_lsop08_predict_dev", self.ctx.handle, nRows, nCols, nt, dv.ptr, dr.ptr, stride, dc.ptr, ds.ptr)
+            res = dr.download(np.int32, nt * stride).reshape(nt, stride)[:, :n]
+            coefs = dc.download(np.uint32, nt * 16).reshape(nt, 16)
+            status = ds.download(np.int32, nt)
+        return coefs[:, 0].astype(np.int32), coefs[:, 1:9].copy().view(np.float32), res, status
+
+    def reconstruct(self, nRows, nCols, seeds, coefficients, residuals):
+        """LsDecoder08.unpackInitializers/unpackInterior: returns (values int32[nt, cells], status)."""
+        res = np.ascontiguousarray(residuals, dtype=np.int32)
+        nt, n = res.shape
+        stride = max(4, (n + 3) // 4 * 4)
+        padded = np.zeros((nt, stride), np.int32)
+        padded[:, :n] = res
+        coefs = np.zeros((nt, 16), np.uint32)
+        coefs[:, 0] = np.asarray(seeds, np.int32).view(np.uint32)
+        coefs[:, 1:9] = np.ascontiguousarray(coefficients, np.float32).view(np.uint32).reshape(nt, 8)
+        with _DeviceScope(self.ctx) as s:
+            dv, dr, dc, ds = s.alloc(nt * nRows * nCols * 4), s.upload(padded, slack=16), s.upload(coefs), s.alloc(nt * 4)
+            s.run("gf_lsop08_reconstruct_dev", self.ctx.handle, nRows, nCols, nt, dr.ptr, stride, dc.ptr, None, dv.ptr, ds.ptr)
+            vals = dv.download(np.int32, nt * nRows * nCols).reshape(nt, nRows * nCols)
+            status = ds.download(np.int32, nt)
+        return vals, status
+
+
 class CodecMasterHip:
     """org.gridfour.gvrs.CodecMaster over a codec list, batched: the strictly shortest packing per tile (list order
     breaks ties), decode dispatch on packing[0]."""

@@ -1,4 +1,4 @@
-// gvrs_api_lsop.hip -- LSOP12: the device-resident and the host-memory entry points.
+// gvrs_api_lsop.hip -- LSOP12 and LSOP08: the device-resident and the host-memory entry points.
 
 #include "gvrs_api_internal.h"
 
@@ -14,7 +14,7 @@ static gf_status lsopParseLengths(gf_context *c, hipStream_t st, size_t nTiles, 
 
 // second entropy pass of the LSOP12 decode: containers k_lsop_unpack2 left marked GF_ERR_UNSUPPORTED (legacy Huffman of
 // M32; with rawM32 also the host-inflated Deflate ones)
-static gf_status lsopUnpackM32(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob,
+static gf_status lsopUnpackM32(gf_context *c, hipStream_t st, const GfLsopForm &form, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob,
                                size_t blobBytes, const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths,
                                int32_t *dResiduals, size_t resStride, uint32_t *dCoefs, int32_t *dScratchStatus, int rawM32,
                                const uint8_t *rawSide = nullptr, size_t rawSideStride = 0, const int32_t *sideStatus = nullptr,
@@ -46,6 +46,7 @@ static gf_status lsopUnpackM32(gf_context *c, hipStream_t st, int nRows, int nCo
     a.sideStatus = sideStatus;
     a.produced2 = produced2;
     a.inflStatus2 = inflStatus2;
+    a.form = form;
     GF_HIP(gf_launch_lsop_unpack_m32(a, st, grid));
     return GF_OK;
 }
@@ -56,11 +57,11 @@ constexpr size_t LSOP_INFLATE_SCRATCH_BYTES = (size_t)384 << 20;   // LSOP12's D
 // per chunk of tiles, k_lsop_streams describes the first zlib stream of every Deflate container, k_inflate runs, k_lsop_streams
 // places the second stream behind what the first one consumed, k_inflate runs again, and k_lsop_unpack_m32 reads the M32 bytes
 // of those tiles from the scratch (legacy Huffman containers are decoded as stored in the same launch).
-static gf_status lsopUnpackM32Deflate(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob,
+static gf_status lsopUnpackM32Deflate(gf_context *c, hipStream_t st, const GfLsopForm &form, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob,
                                       size_t blobBytes, const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths,
                                       int32_t *dResiduals, size_t resStride, uint32_t *dCoefs, int32_t *dScratchStatus)
 {
-    const size_t nInit = (size_t)4 * nRows + 2 * nCols - 9, nInt = (size_t)(nRows - 2) * (size_t)(nCols - 4);
+    const size_t nInit = form.nInit, nInt = form.nInt;
     const size_t rawStride = roundUp(6 * (nInit + nInt) + 192, 16);
     // The scratch of the Deflate containers: LSOP_INFLATE_SCRATCH_BYTES, not a share of HBM per tile of the batch -- the default
     // encoder output is the canonical container and pays these gated launches for nothing (the full gigabyte of the CodecDeflate /
@@ -87,7 +88,7 @@ static gf_status lsopUnpackM32Deflate(gf_context *c, hipStream_t st, int nRows, 
         const size_t blobBytesC = dOffsets ? blobBytes : blobBytes - t0 * slotStride;
         const uint64_t *offC = dOffsets ? dOffsets + t0 : nullptr;
         for (int pass = 0; pass < 2; pass++) {
-            GF_HIP(gf_launch_lsop_streams(blobC, blobBytesC, offC, slotStride, dLengths + t0, n, (uint32_t)nInit, (uint32_t)nInt, rawStride,
+            GF_HIP(gf_launch_lsop_streams(blobC, blobBytesC, offC, slotStride, dLengths + t0, n, form, rawStride,
                                           pass, produced1, status1, consumed1, desc, side, gate, st));
             GfInflateArgs a{};
             a.inBase = blobC;
@@ -101,7 +102,7 @@ static gf_status lsopUnpackM32Deflate(gf_context *c, hipStream_t st, int nRows, 
             a.window = gf_inflate_window(0);
             GF_HIP(gf_launch_inflate(a, st));
         }
-        s = lsopUnpackM32(c, st, nRows, nCols, n, blobC, blobBytesC, offC, slotStride, dLengths + t0, dResiduals + t0 * resStride, resStride,
+        s = lsopUnpackM32(c, st, form, nRows, nCols, n, blobC, blobBytesC, offC, slotStride, dLengths + t0, dResiduals + t0 * resStride, resStride,
                           dCoefs + t0 * 16, dScratchStatus + t0, 2, raw, rawStride, side, produced2, status2);
         if (s != GF_OK) return s;
     }
@@ -263,7 +264,7 @@ gf_status gf_lsop12_decode_batch_i32_dev(gf_context *c, void *stream, int nRows,
                                   // (the serial walk of a lane pays where sixty-four tiles share a wave: large batches)
                                   gf_prepass_tiles_per_wave(nTiles) == 64u ? c->trees.at<uint32_t>(sp.lsop1.at) : nullptr,
                                   true));
-    s = lsopUnpackM32Deflate(c, st, nRows, nCols, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths, dResiduals, resStride,
+    s = lsopUnpackM32Deflate(c, st, gf_lsop12_form(nRows, nCols), nRows, nCols, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths, dResiduals, resStride,
                              dCoefs, dScratchStatus);
     if (s != GF_OK) return s;
     GF_HIP(gf_launch_lsop_reconstruct(dResiduals, resStride, dCoefs, dScratchStatus, dValues, dStatus, nTiles, nRows, nCols, st,
@@ -406,6 +407,237 @@ gf_status gf_lsop12_decode_i32(gf_context *c, int nRows, int nCols, const uint8_
     GF_CTX_LOCK(c);
     return oneTileDecode(len, [&](const uint64_t *offsets, int32_t *st) {
         return gf_lsop12_decode_batch_i32(c, nRows, nCols, 1, packing, offsets, values, st);
+    });
+}
+
+// ------------------------------------------------------------------ LSOP08
+
+// the shapes the LSOP08 kernels take: LsOptimalPredictor08.java:62-64 declines fewer than 4 rows or columns (the callers answer
+// that themselves); k_lsop8_reconstruct keeps two rows of a tile in LDS; the packer counts a packing's bits in 32 bits
+static gf_status lsop08Shape(int nRows, int nCols)
+{
+    if (nCols > GF_LSOP8_MAX_COLS || (size_t)nRows * (size_t)nCols >= (1ull << 26)) return GF_ERR_UNSUPPORTED;
+    return GF_OK;
+}
+
+size_t gf_lsop08_residual_count(int nRows, int nCols)
+{
+    if (nRows < 4 || nCols < 4) return 0;
+    return (size_t)2 * nRows + (size_t)2 * nCols - 5 + (size_t)(nRows - 2) * (size_t)(nCols - 2);
+}
+
+size_t gf_lsop08_max_packing(int nRows, int nCols)
+{
+    // 47 header bytes + two bodies.  Huffman: a serialised tree is at most 8 + 10 * 256 - 1 bits and the text no longer than the M32
+    // bytes themselves (a Huffman code of at most 256 symbols is never longer than the fixed 8-bit one); Deflate: the reference
+    // gives each zlib stream its input's length + 128.  A value has at most 6 M32 bytes.
+    const size_t n = gf_lsop08_residual_count(nRows, nCols);
+    if (n == 0) return 0;
+    return roundUp(47 + 2 * 328 + 6 * n + 16, 16);
+}
+
+gf_status gf_lsop08_predict_dev(gf_context *c, int nRows, int nCols, size_t nTiles, const int32_t *dValues, int32_t *dResiduals,
+                                size_t resStride, uint32_t *dCoefs, int32_t *dStatus)
+{
+    GF_CTX_LOCK(c);
+    if (!c || !dValues || !dResiduals || !dCoefs || !dStatus || nRows < 1 || nCols < 1) return GF_ERR_ARG;
+    GF_HIP(hipSetDevice(c->device));
+    if (nRows < 4 || nCols < 4) {                       // LsOptimalPredictor08.java:62-64 -> null
+        if (nTiles) GF_HIP(hipMemsetD32Async((hipDeviceptr_t)dStatus, GF_DECLINED, nTiles, c->stream));
+        return GF_OK;
+    }
+    if (resStride < gf_lsop08_residual_count(nRows, nCols)) return GF_ERR_ARG;
+    const gf_status s = lsop08Shape(nRows, nCols);
+    if (s != GF_OK) return s;
+    GF_HIP(gf_launch_lsop8_predict(dValues, dResiduals, resStride, dCoefs, dStatus, nTiles, nRows, nCols, c->stream));
+    return GF_OK;
+}
+
+gf_status gf_lsop08_reconstruct_dev(gf_context *c, int nRows, int nCols, size_t nTiles, const int32_t *dResiduals, size_t resStride,
+                                    const uint32_t *dCoefs, const int32_t *dInStatus, int32_t *dValues, int32_t *dStatus)
+{
+    GF_CTX_LOCK(c);
+    if (!c || !dValues || !dResiduals || !dCoefs || !dStatus) return GF_ERR_ARG;
+    GF_HIP(hipSetDevice(c->device));
+    if (nRows < 4 || nCols < 4 || resStride < gf_lsop08_residual_count(nRows, nCols)) return GF_ERR_ARG;
+    const gf_status s = lsop08Shape(nRows, nCols);
+    if (s != GF_OK) return s;
+    GF_HIP(gf_launch_lsop8_reconstruct(dResiduals, resStride, dCoefs, dInStatus, dValues, dStatus, nTiles, nRows, nCols, c->stream));
+    return GF_OK;
+}
+
+gf_status gf_lsop08_encode_batch_i32_dev(gf_context *c, int codecIndex, int nRows, int nCols, size_t nTiles, const int32_t *dValues,
+                                         uint8_t *dOut, size_t slotStride, uint32_t *dLengths, int32_t *dStatus, int32_t *dResiduals,
+                                         size_t resStride, uint32_t *dCoefs, int32_t *dScratchStatus)
+{
+    GF_CTX_LOCK(c);
+    if (!c || !dValues || !dOut || !dLengths || !dStatus || !dResiduals || !dCoefs || !dScratchStatus || nRows < 1 || nCols < 1) return GF_ERR_ARG;
+    GF_HIP(hipSetDevice(c->device));
+    if (slotStride % 16 != 0 || ((uintptr_t)dOut & 15) != 0 || slotStride < 64) return GF_ERR_ARG;
+    if (nRows < 4 || nCols < 4) {
+        if (nTiles) {
+            GF_HIP(hipMemsetD32Async((hipDeviceptr_t)dStatus, GF_DECLINED, nTiles, c->stream));
+            GF_HIP(hipMemsetD32Async((hipDeviceptr_t)dLengths, 0, nTiles, c->stream));
+        }
+        return GF_OK;
+    }
+    const gf_status s = gf_lsop08_predict_dev(c, nRows, nCols, nTiles, dValues, dResiduals, resStride, dCoefs, dScratchStatus);
+    if (s != GF_OK) return s;
+    GF_HIP(gf_launch_lsop8_pack(dResiduals, resStride, dCoefs, dScratchStatus, dOut, slotStride, dLengths, dStatus, nTiles, nRows, nCols,
+                                codecIndex, c->stream));
+    return GF_OK;
+}
+
+gf_status gf_lsop08_decode_batch_i32_dev(gf_context *c, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
+                                         const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues,
+                                         int32_t *dStatus, int32_t *dResiduals, size_t resStride, uint32_t *dCoefs, int32_t *dScratchStatus)
+{
+    GF_CTX_LOCK(c);
+    if (!c || !dBlob || !dLengths || !dValues || !dStatus || !dResiduals || !dCoefs || !dScratchStatus || nRows < 1 || nCols < 1) return GF_ERR_ARG;
+    GF_HIP(hipSetDevice(c->device));
+    if (((uintptr_t)dBlob & 3) != 0) return GF_ERR_ARG;
+    const hipStream_t st = c->stream;
+    if (nRows < 4 || nCols < 4) {
+        if (nTiles) GF_HIP(hipMemsetD32Async((hipDeviceptr_t)dStatus, GF_ERR_BOUNDS, nTiles, st));
+        return GF_OK;
+    }
+    if (resStride < gf_lsop08_residual_count(nRows, nCols)) return GF_ERR_ARG;
+    gf_status s = lsop08Shape(nRows, nCols);
+    if (s != GF_OK || nTiles == 0) return s;
+    // every container is k_lsop_unpack_m32's (there is no canonical type): all tiles start out marked for it, the record's spare
+    // words as zero
+    GF_HIP(hipMemsetD32Async((hipDeviceptr_t)dScratchStatus, GF_ERR_UNSUPPORTED, nTiles, st));
+    GF_HIP(hipMemsetAsync(dCoefs, 0, nTiles * 64, st));
+    s = lsopUnpackM32Deflate(c, st, gf_lsop08_form(nRows, nCols), nRows, nCols, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths,
+                             dResiduals, resStride, dCoefs, dScratchStatus);
+    if (s != GF_OK) return s;
+    GF_HIP(gf_launch_lsop8_reconstruct(dResiduals, resStride, dCoefs, dScratchStatus, dValues, dStatus, nTiles, nRows, nCols, st));
+    return GF_OK;
+}
+
+// LsEncoder08.encode :66-137 for a batch in host memory: the Huffman body (type 0) comes from the GPU, the host's zlib (level 6)
+// compresses the two M32 streams, and the Huffman body is kept only where it is STRICTLY shorter (:118); otherwise the packing is the
+// Deflate one (type 1).  types[t] (may be null) = container type written.  A tile whose zlib stream would need more than its input's
+// length + 128 bytes -- the reference's buffer, which it would silently cut (:90-101) -- is GF_ERR_UNSUPPORTED.
+gf_status gf_lsop08_encode_batch_i32(gf_context *c, int codecIndex, int nRows, int nCols, size_t nTiles, const int32_t *values, uint8_t *blob,
+                                     size_t blobCap, uint64_t *offsets, uint8_t *types, int32_t *status)
+{
+    GF_CTX_LOCK(c);
+    if (!c || nRows < 1 || nCols < 1 || !values || !offsets || (!blob && blobCap)) return GF_ERR_ARG;
+    GF_HIP(hipSetDevice(c->device));
+    if (nRows < 4 || nCols < 4) {
+        for (size_t t = 0; t <= nTiles; t++) offsets[t] = 0;
+        for (size_t t = 0; t < nTiles; t++) { if (status) status[t] = GF_DECLINED; if (types) types[t] = 0; }
+        return GF_OK;
+    }
+    gf_status s = lsop08Shape(nRows, nCols);
+    if (s != GF_OK) return s;
+    const size_t cells = (size_t)nRows * (size_t)nCols;
+    const size_t nRes = gf_lsop08_residual_count(nRows, nCols), resStride = roundUp(nRes, 4);
+    const GfLsopForm form = gf_lsop08_form(nRows, nCols);
+    const size_t nInit = form.nInit, nInt = form.nInt, stride = gf_lsop08_max_packing(nRows, nCols), hdr = 47;
+    // staging: values | slots | lengths | statuses | residuals | coefficients | the second status
+    std::vector<uint32_t> lengths(nTiles), coefs(nTiles * 16);
+    std::vector<int32_t> st(nTiles), res(nTiles * resStride);
+    std::vector<uint8_t> slots(nTiles * stride);
+    HostStage sg(c);
+    const int valuesP = sg.in(values, nTiles * cells * 4), slotsP = sg.out(slots.data(), nTiles * stride);
+    const int lengthsP = sg.out(lengths.data(), nTiles * 4), statusP = sg.out(st.data(), nTiles * 4);
+    const int resP = sg.out(res.data(), nTiles * resStride * 4), coefsP = sg.out(coefs.data(), nTiles * 64), status2P = sg.local(nTiles * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
+    s = gf_lsop08_encode_batch_i32_dev(c, codecIndex, nRows, nCols, nTiles, sg.ptr<int32_t>(valuesP), sg.ptr<uint8_t>(slotsP), stride,
+                                       sg.ptr<uint32_t>(lengthsP), sg.ptr<int32_t>(statusP), sg.ptr<int32_t>(resP), resStride,
+                                       sg.ptr<uint32_t>(coefsP), sg.ptr<int32_t>(status2P));
+    if (s != GF_OK || (s = sg.end()) != GF_OK) return s;
+
+    std::vector<std::vector<uint8_t>> alt(nTiles);          // the Deflate container where the Huffman body is not strictly shorter
+    parallelFor(nTiles, [&](size_t t) {
+        if (st[t] != GF_OK) return;
+        const int32_t *r = res.data() + t * resStride;
+        std::vector<uint8_t> mInit, mInt, zInit, zInt;
+        const size_t nMI = m32Pack(r, nInit, mInit), nMX = m32Pack(r + nInit, nInt, mInt);
+        if (!zDeflate(mInit.data(), nMI, 6, zInit) || !zDeflate(mInt.data(), nMX, 6, zInt) || zInit.size() > nMI + 128 ||
+            zInt.size() > nMX + 128) {
+            st[t] = GF_ERR_UNSUPPORTED;
+            return;
+        }
+        if (lengths[t] - hdr < zInit.size() + zInt.size()) return;                  // :118
+        std::vector<uint8_t> &p = alt[t];
+        p.resize(hdr + zInit.size() + zInt.size());
+        p[0] = (uint8_t)codecIndex;
+        p[1] = 0x41;                                         // COMPRESSION_TYPE_DEFLATE | REVISION_FLAG
+        p[2] = 8;
+        for (int k = 0; k < 9; k++) putLE32(&p[3 + 4 * k], coefs[t * 16 + k]);
+        putLE32(&p[39], (uint32_t)nMI);
+        putLE32(&p[43], (uint32_t)nMX);
+        memcpy(&p[hdr], zInit.data(), zInit.size());
+        memcpy(&p[hdr + zInit.size()], zInt.data(), zInt.size());
+    });
+    uint64_t total = 0;
+    for (size_t t = 0; t < nTiles; t++) {
+        offsets[t] = total;
+        if (st[t] == GF_OK) total += alt[t].empty() ? lengths[t] : alt[t].size();
+        if (types) types[t] = st[t] == GF_OK && !alt[t].empty() ? 1 : 0;
+    }
+    offsets[nTiles] = total;
+    if (status) memcpy(status, st.data(), nTiles * 4);
+    if (total > blobCap) return GF_ERR_CAPACITY;
+    for (size_t t = 0; t < nTiles; t++) {
+        if (st[t] != GF_OK) continue;
+        if (alt[t].empty()) memcpy(blob + offsets[t], slots.data() + t * stride, lengths[t]);
+        else memcpy(blob + offsets[t], alt[t].data(), alt[t].size());
+    }
+    return GF_OK;
+}
+
+// LsDecoder08.decode :71-116 for a batch in host memory: both container types and both header revisions, decoded on the GPU as stored
+gf_status gf_lsop08_decode_batch_i32(gf_context *c, int nRows, int nCols, size_t nTiles, const uint8_t *blob, const uint64_t *offsets,
+                                     int32_t *values, int32_t *status)
+{
+    GF_CTX_LOCK(c);
+    if (!c || nRows < 1 || nCols < 1 || !blob || !offsets || !values) return GF_ERR_ARG;
+    if (!offsetsValid(offsets, nTiles)) return GF_ERR_ARG;
+    GF_HIP(hipSetDevice(c->device));
+    if (nRows < 4 || nCols < 4) {
+        for (size_t t = 0; t < nTiles && status; t++) status[t] = GF_ERR_BOUNDS;
+        return GF_OK;
+    }
+    gf_status s = lsop08Shape(nRows, nCols);
+    if (s != GF_OK) return s;
+    const size_t cells = (size_t)nRows * (size_t)nCols;
+    const size_t nRes = gf_lsop08_residual_count(nRows, nCols), resStride = roundUp(nRes, 4);
+    // staging: blob | offsets | lengths | values | statuses | residuals | coefficients | the second status
+    std::vector<uint32_t> lengths(nTiles);
+    std::vector<int32_t> st(nTiles);
+    for (size_t t = 0; t < nTiles; t++) lengths[t] = (uint32_t)(offsets[t + 1] - offsets[t]);
+    const size_t total = (size_t)offsets[nTiles];
+    HostStage sg(c);
+    const int blobP = sg.in(blob, total, 32), offsetsP = sg.in(offsets, (nTiles + 1) * 8), lengthsP = sg.in(lengths.data(), nTiles * 4);
+    const int valuesP = sg.out(values, nTiles * cells * 4), statusP = sg.out(st.data(), nTiles * 4);
+    const int resP = sg.local(nTiles * resStride * 4), coefsP = sg.local(nTiles * 64), status2P = sg.local(nTiles * 4);
+    if ((s = sg.begin()) != GF_OK) return s;
+    s = gf_lsop08_decode_batch_i32_dev(c, nRows, nCols, nTiles, sg.ptr<uint8_t>(blobP), total, sg.ptr<uint64_t>(offsetsP), 0,
+                                       sg.ptr<uint32_t>(lengthsP), sg.ptr<int32_t>(valuesP), sg.ptr<int32_t>(statusP), sg.ptr<int32_t>(resP),
+                                       resStride, sg.ptr<uint32_t>(coefsP), sg.ptr<int32_t>(status2P));
+    if (s != GF_OK || (s = sg.end()) != GF_OK) return s;
+    if (status) memcpy(status, st.data(), nTiles * 4);
+    return GF_OK;
+}
+
+gf_status gf_lsop08_encode_i32(gf_context *c, int codecIndex, int nRows, int nCols, const int32_t *values, uint8_t *out, size_t outCap,
+                               size_t *outLen)
+{
+    GF_CTX_LOCK(c);
+    return oneTileEncode(outLen, [&](uint64_t *offsets, int32_t *st) {
+        return gf_lsop08_encode_batch_i32(c, codecIndex, nRows, nCols, 1, values, out, outCap, offsets, nullptr, st);
+    });
+}
+
+gf_status gf_lsop08_decode_i32(gf_context *c, int nRows, int nCols, const uint8_t *packing, size_t len, int32_t *values)
+{
+    GF_CTX_LOCK(c);
+    return oneTileDecode(len, [&](const uint64_t *offsets, int32_t *st) {
+        return gf_lsop08_decode_batch_i32(c, nRows, nCols, 1, packing, offsets, values, st);
     });
 }
 

@@ -3080,7 +3080,7 @@ __global__ __launch_bounds__(DEC_THREADS, MODE >= 2 ? GF_DEC_WGS : GF_DEC_WGS_GE
 
 #ifndef GF_DEC_VARIANT
 // ---------------------------------------------------------------------------------------------------------------
-// LsDecoder12.decode for the containers that carry CodecM32 bytes (lsop/LsDecoder12.java:107-150): header (either
+// LsDecoder12.decode / LsDecoder08.decode (a.form) for the containers that carry CodecM32 bytes (lsop/LsDecoder12.java:107-150): header (either
 // revision, lsop/LsHeader.java:131-185), then the initialiser and interior M32 streams -- type 0: two legacy Huffman
 // segments back to back in one bit store, the second starting at the bit after the first one's last code
 // (LsDecoder12.java:116-124); type 1: two zlib streams, inflated by the host before the launch (rawM32).  Output:
@@ -3092,7 +3092,7 @@ __global__ __launch_bounds__(DEC_THREADS, 4) void k_lsop_unpack_m32(GfLsopM32Arg
 
     const int tid = threadIdx.x, wave = (int)gf_wave_id();
     const uint32_t nR = (uint32_t)a.nRows, nC = (uint32_t)a.nCols, nCells = nR * nC;
-    const uint32_t nInit = 4u * nR + 2u * nC - 9u, nInt = (nR - 2u) * (nC - 4u);
+    const uint32_t nInit = a.form.nInit, nInt = a.form.nInt, nCoef = a.form.nCoef;      // LSOP12 or LSOP08: gf_lsop12_form / gf_lsop08_form
     const uint32_t *__restrict__ w32 = reinterpret_cast<const uint32_t *>(a.blob);
     const uint64_t nWords = (a.blobBytes + 3) >> 2;
 
@@ -3106,7 +3106,7 @@ __global__ __launch_bounds__(DEC_THREADS, 4) void k_lsop_unpack_m32(GfLsopM32Arg
             return (uint32_t)pk[o] | ((uint32_t)pk[o + 1] << 8) | ((uint32_t)pk[o + 2] << 16) | ((uint32_t)pk[o + 3] << 24);
         };
 
-        // header: codec index, [type | flags], nCoef, seed, 12 floats, the two M32 byte counts, [type | flags]
+        // header: codec index, [type | flags], nCoef, seed, nCoef floats, the two M32 byte counts, [type | flags]
         int32_t early = GF_K_OK;
         uint32_t o = 1, type = 0, nMI = 0, nMX = 0;
         bool checksum = false;
@@ -3114,16 +3114,18 @@ __global__ __launch_bounds__(DEC_THREADS, 4) void k_lsop_unpack_m32(GfLsopM32Arg
         else {
             const bool revised = pk[1] & 0x40;
             if (revised) { type = pk[1] & 0x0fu; checksum = pk[1] & 0x80; o = 2; }
-            if (len < o + 1u + 52u + 8u + (revised ? 0u : 1u)) early = GF_K_ERR_BOUNDS;
-            else if (pk[o] != 12) early = GF_K_ERR_FORMAT;                // u[11] would index out of bounds
+            if (revised && a.form.strictTypes && type > 1u) early = GF_K_ERR_FORMAT;      // (no count follows a canonical header)
+            else if (len < o + 1u + 4u + 4u * nCoef + 8u + (revised ? 0u : 1u)) early = GF_K_ERR_BOUNDS;
+            else if (pk[o] != nCoef) early = GF_K_ERR_FORMAT;             // the predictor would index out of bounds
             else {
-                o += 53;
+                o += 5u + 4u * nCoef;
                 nMI = le32(o);
                 nMX = le32(o + 4);
                 o += 8;
                 if (!revised) { type = pk[o] & 0x0fu; checksum = pk[o] & 0x80; o++; }
                 if (checksum) o += 4;                                     // value checksum: skipped
                 if (o > len) early = GF_K_ERR_BOUNDS;
+                else if (a.form.strictTypes && type > 1u) early = GF_K_ERR_FORMAT;
                 else if (type == 2) early = GF_K_ERR_UNSUPPORTED;         // canonical text behind a legacy header: never written
                 else if (type != 0 && !a.rawM32) early = GF_K_ERR_UNSUPPORTED;   // Deflate: needs an inflate pass first
                 else if (nMI > 6u * nInit + 64u || nMX > 6u * nInt + 64u) early = GF_K_ERR_FORMAT;   // no encoder emits this
@@ -3141,7 +3143,7 @@ __global__ __launch_bounds__(DEC_THREADS, 4) void k_lsop_unpack_m32(GfLsopM32Arg
             __syncthreads();
             continue;
         }
-        if (tid < 13) a.coefs[t * 16 + tid] = le32((pk[1] & 0x40 ? 3u : 2u) + 4u * tid);
+        if (tid < (int)nCoef + 1) a.coefs[t * 16 + tid] = le32((pk[1] & 0x40 ? 3u : 2u) + 4u * tid);
 
         uint32_t startBit = o * 8u;                                       // type 0: where the next Huffman segment begins
         uint32_t rawAt = a.rawM32 == 2 ? 0u : o;                          // type 1: where the next M32 stream begins

@@ -596,14 +596,14 @@ __global__ void k_float_streams(const uint8_t *__restrict__ blob, size_t blobByt
     pre[i] = st;
 }
 
-// LSOP12 containers that carry Deflate (LsDecoder12.java:127-141): header (either revision, LsHeader.java:131-185) with the
+// LSOP12 / LSOP08 containers (form) that carry Deflate (LsDecoder12.java:127-141, LsDecoder08.java:91-110): header (either revision, LsHeader.java:131-185) with the
 // byte counts of the two M32 streams, then TWO zlib streams back to back -- the second one begins where the first one's
 // Inflater stopped reading (Inflater.getTotalIn()).  Two passes of one thread per tile around two k_inflate launches:
 // pass 0 describes stream one; pass 1 checks what came out of it and describes stream two.  Both streams of tile i go to
 // raw + i * rawStride: [initialiser M32 bytes][interior M32 bytes].  side[i]: 0 = a Deflate container on its way, 1 = not one
 // (or a header k_lsop_unpack_m32 rejects by itself), < 0 = the status of a failed first stream.
 __global__ void k_lsop_streams(const uint8_t *__restrict__ blob, size_t blobBytes, const uint64_t *__restrict__ offsets, size_t slotStride,
-                               const uint32_t *__restrict__ lengths, size_t nTiles, uint32_t nInit, uint32_t nInt, size_t rawStride,
+                               const uint32_t *__restrict__ lengths, size_t nTiles, GfLsopForm form, size_t rawStride,
                                int pass, const uint32_t *__restrict__ produced, const int32_t *__restrict__ inflStatus,
                                const uint32_t *__restrict__ consumed, GfInflateStream *__restrict__ desc, int32_t *__restrict__ side,
                                uint32_t *__restrict__ gate)
@@ -632,14 +632,15 @@ __global__ void k_lsop_streams(const uint8_t *__restrict__ blob, size_t blobByte
         const bool revised = pk[1] & 0x40;
         bool checksum = false;
         if (revised) { type = pk[1] & 0x0fu; checksum = pk[1] & 0x80; o = 2; }
-        if (len >= o + 1u + 52u + 8u + (revised ? 0u : 1u) && pk[o] == 12) {
-            o += 53;
+        if (len >= o + 1u + 4u + 4u * form.nCoef + 8u + (revised ? 0u : 1u) && pk[o] == form.nCoef) {
+            o += 5u + 4u * form.nCoef;
             nMI = le32(o);
             nMX = le32(o + 4);
             o += 8;
             if (!revised) { type = pk[o] & 0x0fu; checksum = pk[o] & 0x80; o++; }
             if (checksum) o += 4;
-            if (o <= len && type != 0 && type != 2 && nMI <= 6u * nInit + 64u && nMX <= 6u * nInt + 64u) sd = 0;
+            const bool deflate = form.strictTypes ? type == 1u : type != 0u && type != 2u;
+            if (o <= len && deflate && nMI <= 6u * form.nInit + 64u && nMX <= 6u * form.nInt + 64u) sd = 0;
         }
     }
     if (sd == 0) {
@@ -769,13 +770,13 @@ hipError_t gf_launch_float_short_planes(size_t nTiles, const int32_t *pre, const
 }
 
 hipError_t gf_launch_lsop_streams(const uint8_t *blob, size_t blobBytes, const uint64_t *offsets, size_t slotStride, const uint32_t *lengths,
-                                  size_t nTiles, uint32_t nInit, uint32_t nInt, size_t rawStride, int pass, const uint32_t *produced,
+                                  size_t nTiles, GfLsopForm form, size_t rawStride, int pass, const uint32_t *produced,
                                   const int32_t *inflStatus, const uint32_t *consumed, GfInflateStream *desc, int32_t *side, uint32_t *gate,
                                   hipStream_t stream)
 {
     if (nTiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_lsop_streams, dim3((unsigned)((nTiles + 255) / 256)), dim3(256), 0, stream, blob, blobBytes, offsets, slotStride,
-                       lengths, nTiles, nInit, nInt, rawStride, pass, produced, inflStatus, consumed, desc, side, gate);
+                       lengths, nTiles, form, rawStride, pass, produced, inflStatus, consumed, desc, side, gate);
     return hipGetLastError();
 }
 

@@ -170,7 +170,23 @@ struct GfSideStream {
     hipEvent_t fork, join;
 };
 
-// LSOP12 containers whose entropy stage is CodecM32 bytes: type 0 (legacy Huffman of the two M32 streams) and, with
+// What tells the two optimal-predictor codecs apart in a container of CodecM32 bytes (lsop/LsHeader.java:137-189): the number of
+// coefficients the header must state and the lengths of the two residual streams.  strictTypes: a container type other than 0 or 1
+// is GF_K_ERR_FORMAT (LSOP08); without it type 2 is left to the canonical unpacker and any other type reads as Deflate (LSOP12).
+struct GfLsopForm {
+    uint32_t nCoef, nInit, nInt;
+    int strictTypes;
+};
+inline GfLsopForm gf_lsop12_form(int nRows, int nCols)
+{
+    return GfLsopForm{12u, (uint32_t)(4 * nRows + 2 * nCols - 9), (uint32_t)(nRows - 2) * (uint32_t)(nCols - 4), 0};
+}
+inline GfLsopForm gf_lsop08_form(int nRows, int nCols)
+{
+    return GfLsopForm{8u, (uint32_t)(2 * nRows + 2 * nCols - 5), (uint32_t)(nRows - 2) * (uint32_t)(nCols - 2), 1};
+}
+
+// LSOP containers whose entropy stage is CodecM32 bytes: type 0 (legacy Huffman of the two M32 streams) and, with
 // rawM32 = 1, type 1 after the host inflated it (gvrs_decode.hip: k_lsop_unpack_m32)
 struct GfLsopM32Args {
     const uint8_t *blob;       // 4-byte aligned
@@ -180,7 +196,7 @@ struct GfLsopM32Args {
     const uint32_t *lengths;
     int32_t *residuals;        // nTiles * resStride ints: initialisers, then interior
     size_t resStride;
-    uint32_t *coefs;           // nTiles * 16 words: seed, 12 float bit patterns
+    uint32_t *coefs;           // nTiles * 16 words: seed, form.nCoef float bit patterns
     int32_t *status;           // in: only tiles marked GF_K_ERR_UNSUPPORTED are touched; out: their decode status
     uint8_t *workspace;        // gridDim.x * workspaceStride bytes (M32 spill)
     size_t workspaceStride;
@@ -194,6 +210,7 @@ struct GfLsopM32Args {
     const int32_t *sideStatus;     // mode 2, per tile (k_lsop_streams): 0 = inflated, < 0 = the first stream's failure
     const uint32_t *produced2;     // mode 2: bytes the second stream gave
     const int32_t *inflStatus2;    // mode 2: the second stream's status
+    GfLsopForm form;
 };
 
 hipError_t gf_launch_lsop_unpack_m32(const GfLsopM32Args &a, hipStream_t stream, unsigned grid);
@@ -314,6 +331,20 @@ hipError_t gf_launch_lsop_reconstruct(const int32_t *residuals, size_t resStride
                                       int32_t *values, int32_t *status, size_t nTiles, int nRows, int nCols,
                                       hipStream_t stream, bool planes = false);    // planes: word GF_LSOP_FMT_WORD of a tile's
                                                                                    // coefficient record says where its interior residuals are
+// LSOP08 (gvrs_lsop8.hip).  residuals: per tile resStride ints [2 nR + 2 nC - 5 initialisers | (nR - 2)(nC - 2) interior]; coefs: per
+// tile 16 words (seed, 8 float bit patterns, 7 words of 0).  The kernels walk the batch with at most GF_LSOP8_GRID_CAP workgroups;
+// k_lsop8_reconstruct keeps two rows of the tile in LDS, which bounds nCols.
+constexpr unsigned GF_LSOP8_GRID_CAP = 32768;
+constexpr int GF_LSOP8_MAX_COLS = 16384;
+hipError_t gf_launch_lsop8_predict(const int32_t *values, int32_t *residuals, size_t resStride, uint32_t *coefs, int32_t *status,
+                                   size_t nTiles, int nRows, int nCols, hipStream_t stream);
+// header + two legacy Huffman segments of the M32 bytes (container type 0); inStatus: k_lsop8_predict's
+hipError_t gf_launch_lsop8_pack(const int32_t *residuals, size_t resStride, const uint32_t *coefs, const int32_t *inStatus, uint8_t *out,
+                                size_t slotStride, uint32_t *lengths, int32_t *status, size_t nTiles, int nRows, int nCols, int codecIndex,
+                                hipStream_t stream);
+hipError_t gf_launch_lsop8_reconstruct(const int32_t *residuals, size_t resStride, const uint32_t *coefs, const int32_t *inStatus,
+                                       int32_t *values, int32_t *status, size_t nTiles, int nRows, int nCols, hipStream_t stream);
+
 // The interior residuals of a decoded tile as a BYTE PLANE in pipeline order (round 6).  k_lsop_reconstruct_plane walks a tile as
 // k_lsop_reconstruct_pipe does, with HALF a wave: lane l (0..31) takes rows 2 + l, 2 + 32 + l, ..., three steps behind lane l - 1, a
 // new row every P steps (two tiles share a wave) -- and at step s = 16 b + k a lane wants the residual of ITS cell of that step.
@@ -396,7 +427,7 @@ hipError_t gf_launch_merge_status(size_t nTiles, const int32_t *pre, const int32
 hipError_t gf_launch_float_streams(const uint8_t *blob, size_t blobBytes, const uint64_t *offsets, const uint32_t *lengths, size_t tile0,
                                    size_t nTiles, uint32_t cells, size_t planeStride, GfInflateStream *desc, int32_t *pre, hipStream_t stream);
 hipError_t gf_launch_lsop_streams(const uint8_t *blob, size_t blobBytes, const uint64_t *offsets, size_t slotStride, const uint32_t *lengths,
-                                  size_t nTiles, uint32_t nInit, uint32_t nInt, size_t rawStride, int pass, const uint32_t *produced,
+                                  size_t nTiles, GfLsopForm form, size_t rawStride, int pass, const uint32_t *produced,
                                   const int32_t *inflStatus, const uint32_t *consumed, GfInflateStream *desc, int32_t *side, uint32_t *gate,
                                   hipStream_t stream);
 hipError_t gf_launch_float_short_planes(size_t nTiles, const int32_t *pre, const int32_t *inflStatus, const uint32_t *produced,

@@ -32,6 +32,7 @@ namespace {
 #include "gvrs_encode_common.h"
 #include "gvrs_canon_common.h"
 #include "gvrs_crc32c.h"
+#include "gvrs_lsop_lu.h"
 
 // ------------------------------------------------------------------------------------------------
 // shared by predict and reconstruct
@@ -353,79 +354,6 @@ __device__ __forceinline__ void lsop_gram_mfma(const int32_t *__restrict__ v, in
     }
 }
 
-__device__ __forceinline__ double lsop_bcast(double x, int k)           // value of lane k (k wave-uniform)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), k), hi = __builtin_amdgcn_readlane(__double2hiint(x), k);
-    return __hiloint2double(hi, lo);
-}
-
-// JAMA's LU (LUDecomposition.java:70-134) and solve (:253-284) of the 13x13 system of
-// LsOptimalPredictor12.computeCoefficients :353-378 on one wave: lane i holds row i in registers.  The reference's
-// inner loop  s += LU[i][k] * LUcolj[k]  runs over k in the same order here, for all rows in lockstep (row i stops at
-// k = min(i, j)); the column value of row k is final exactly when step k needs it.  Every multiply and add is
-// rounded separately, as in Java.  Writes S.u / S.status.
-template <class Shared>                                // LsopShared / LsopShared16: G, u, status
-__device__ __forceinline__ void lsop_lu_solve_wave(Shared &S, int lane)
-{
-    auto Cij = [&](int i, int j) -> double {              // c[i][j], symmetric (:345-349)
-        if (i > j) { const int q = i; i = j; j = q; }
-        return S.G[i * 14 - (i * (i - 1)) / 2 + (j - i)];
-    };
-    auto Si = [&](int i) -> double { return S.G[i * 14 - (i * (i - 1)) / 2 + (13 - i)]; };
-    const int row = lane < 13 ? lane : 12;                // lanes >= 13 shadow row 12 (results unused)
-    double r[13], x;
-#pragma unroll
-    for (int j = 0; j < 12; j++) r[j] = row < 12 ? Cij(row + 1, j + 1) : Si(j + 1);
-    r[12] = row < 12 ? Si(row + 1) : 0.0;
-    x = row < 12 ? Cij(0, row + 1) : Si(0);               // right-hand side, permuted along with the rows
-    bool singular = false;
-#pragma unroll
-    for (int j = 0; j < 13; j++) {
-        double colv = r[j], s = 0.0;
-#pragma unroll
-        for (int k = 0; k < j; k++) {
-            const double ck = lsop_bcast(__dsub_rn(colv, s), k);      // LUcolj[k] after its own update
-            if (lane > k) s = __dadd_rn(s, __dmul_rn(r[k], ck));
-        }
-        colv = __dsub_rn(colv, s);
-        r[j] = colv;
-        // pivot: first row >= j with the largest |value| (strict > in scan order)
-        int p = j;
-        double ap = fabs(lsop_bcast(colv, j));
-#pragma unroll
-        for (int i = j + 1; i < 13; i++) {
-            const double ai = fabs(lsop_bcast(colv, i));
-            if (ai > ap) { p = i; ap = ai; }
-        }
-        p = __builtin_amdgcn_readfirstlane(p);
-        if (p != j) {
-            const int partner = lane == j ? p : lane == p ? j : lane;
-#pragma unroll
-            for (int c = 0; c < 13; c++) r[c] = __shfl(r[c], partner, 64);
-            x = __shfl(x, partner, 64);
-        }
-        const double djj = lsop_bcast(r[j], j);
-        if (djj != 0.0) { if (lane > j) r[j] = __ddiv_rn(r[j], djj); }
-        else singular = true;
-    }
-    if (singular) {
-        if (lane == 0) S.status = GF_K_DECLINED;          // "Matrix is singular." -> computeCoefficients returns null
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 13; k++) {                        // L y = b(piv)
-        const double xk = lsop_bcast(x, k);
-        if (lane > k) x = __dsub_rn(x, __dmul_rn(xk, r[k]));
-    }
-#pragma unroll
-    for (int k = 12; k >= 0; k--) {                       // U x = y
-        if (lane == k) x = __ddiv_rn(x, r[k]);
-        const double xk = lsop_bcast(x, k);
-        if (lane < k) x = __dsub_rn(x, __dmul_rn(xk, r[k]));
-    }
-    if (lane < 12) S.u[lane] = (float)x;
-}
-
 struct GfLsopPredictArgs {
     const int32_t *values;
     int32_t *residuals;        // per tile resStride ints: [initialisers | interior]
@@ -518,7 +446,7 @@ __global__ __launch_bounds__(256, GF_LSOP_PREDICT_WGS) void k_lsop_predict(GfLso
         __syncthreads();
 
         // 13x13 bordered system, LU, solve (:353-378; LUDecomposition.java:70-134, 253-284) by wave 0
-        if (wave == 0) lsop_lu_solve_wave(S, lane);
+        if (wave == 0) lsop_lu_solve_wave<13>(S, lane);
         __syncthreads();
         if (S.status != GF_K_OK) {
             if (tid == 0) a.status[t] = S.status;
@@ -784,7 +712,7 @@ __global__ __launch_bounds__(THREADS, GF_LSOP_PREDICT16_WGS) void k_lsop_predict
         // normal equations (:335-342) on the matrix pipe, 13 x 13 system (:353-378) by wave 0
         lsop_gram_mfma16<THREADS>(PL, S.C32, nR, nC, S.G, tid);
         __syncthreads();
-        if (wave == 0) lsop_lu_solve_wave(S, lane);
+        if (wave == 0) lsop_lu_solve_wave<13>(S, lane);
         __syncthreads();
 
         if (S.status != GF_K_OK) {

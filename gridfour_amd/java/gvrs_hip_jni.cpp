@@ -144,7 +144,9 @@ JNIEXPORT jintArray JNICALL Java_org_gridfour_hip_CodecHuffmanHip_decodeNative(J
 
 // ---- org.gridfour.hip.HipCodecNative: the same two calls for every integer codec of the library ----
 // kind 0 = CodecHuffman, 1 = CodecCanonHuffman, 2 = LSOP12 (Deflate alternative disabled), 3 = LSOP12 (reference default),
-// 4 = CodecDeflate, 5 / 6 = LSOP12 as 2 / 3 with the value checksum in the header (LsEncoder12.setValueChecksumEnabled)
+// 4 = CodecDeflate, 5 / 6 = LSOP12 as 2 / 3 with the value checksum in the header (LsEncoder12.setValueChecksumEnabled),
+// 7 = LSOP08 (HipCodecNative.KIND_LSOP08: LsEncoder08's choice between the Huffman and the Deflate container)
+constexpr int KIND_LSOP08 = 7;
 JNIEXPORT jlong JNICALL Java_org_gridfour_hip_HipCodecNative_create(JNIEnv *env, jclass cls, jint device)
 {
     return Java_org_gridfour_hip_CodecHuffmanHip_createNative(env, cls, device);
@@ -162,7 +164,8 @@ JNIEXPORT jbyteArray JNICALL Java_org_gridfour_hip_HipCodecNative_encode(JNIEnv 
     if (!h) return nullptr;
     const size_t cap = kind == 0 ? gf_huffman_max_packing(nRows, nCols)
                      : kind == 1 ? gf_canon_max_packing(nRows, nCols)
-                     : kind == 4 ? gf_m32_max_stream(nRows, nCols) + 256 : gf_lsop12_max_packing(nRows, nCols) + 64;
+                     : kind == 4 ? gf_m32_max_stream(nRows, nCols) + 256
+                     : kind == KIND_LSOP08 ? gf_lsop08_max_packing(nRows, nCols) + 64 : gf_lsop12_max_packing(nRows, nCols) + 64;
     jbyte *out = new jbyte[cap];
     size_t n = 0;
     gf_status s;
@@ -173,6 +176,7 @@ JNIEXPORT jbyteArray JNICALL Java_org_gridfour_hip_HipCodecNative_encode(JNIEnv 
         if (kind == 0) s = gf_huffman_encode_i32(h->ctx, codecIndex, nRows, nCols, v, (uint8_t *)out, cap, &n);
         else if (kind == 1) s = gf_canon_encode_i32(h->ctx, codecIndex, nRows, nCols, v, (uint8_t *)out, cap, &n);
         else if (kind == 4) s = gf_deflate_encode_i32(h->ctx, codecIndex, nRows, nCols, v, (uint8_t *)out, cap, &n);
+        else if (kind == KIND_LSOP08) s = gf_lsop08_encode_i32(h->ctx, codecIndex, nRows, nCols, v, (uint8_t *)out, cap, &n);
         else s = gf_lsop12_encode_i32(h->ctx, codecIndex, nRows, nCols, v,
                                       ((kind == 3 || kind == 6) ? GF_LSOP_DEFLATE : 0) | (kind >= 5 ? GF_LSOP_VALUE_CHECKSUM : 0),
                                       (uint8_t *)out, cap, &n);
@@ -211,6 +215,7 @@ JNIEXPORT jintArray JNICALL Java_org_gridfour_hip_HipCodecNative_decode(JNIEnv *
         if (kind == 0) s = gf_huffman_decode_i32(h->ctx, nRows, nCols, p, (size_t)len, o);
         else if (kind == 1) s = gf_canon_decode_i32(h->ctx, nRows, nCols, p, (size_t)len, o);
         else if (kind == 4) s = gf_deflate_decode_i32(h->ctx, nRows, nCols, p, (size_t)len, o);
+        else if (kind == KIND_LSOP08) s = gf_lsop08_decode_i32(h->ctx, nRows, nCols, p, (size_t)len, o);
         else s = gf_lsop12_decode_i32(h->ctx, nRows, nCols, p, (size_t)len, o);
     }
     if (s == GF_DECLINED) return nullptr;          // CodecDeflate.decode: the inflater gave nothing -> null (CodecDeflate.java:143-154)

@@ -1,7 +1,8 @@
 /*
  * Native entry points shared by the adapters of this package (JNI shim: gvrs_hip_jni.cpp; C ABI:
  * include/gvrs_hip_codec.h).  kind: 0 CodecHuffman, 1 CodecCanonHuffman, 2 LSOP12 without the Deflate
- * alternative, 3 LSOP12 with it (the reference's default), 4 CodecDeflate.  Not compiled in the build image (no JDK).
+ * alternative, 3 LSOP12 with it (the reference's default), 4 CodecDeflate, 5 / 6 LSOP12 as 2 / 3 with the value checksum,
+ * 7 LSOP08.  Not compiled in the build image (no JDK).
  */
 package org.gridfour.hip;
 
@@ -11,6 +12,9 @@ final class HipCodecNative {
   static {
     System.loadLibrary("gvrs_hip_jni");
   }
+
+  /** the kind of LsCodec08Hip: LsEncoder08 + LsDecoder08 (gf_lsop08_encode_i32 / gf_lsop08_decode_i32) */
+  static final int KIND_LSOP08 = 7;
 
   static native long create(int device);
   static native void destroy(long handle);

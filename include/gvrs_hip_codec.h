@@ -383,6 +383,57 @@ gf_status gf_lsop12_encode_i32(gf_context *ctx, int codec_index, int n_rows, int
 gf_status gf_lsop12_decode_i32(gf_context *ctx, int n_rows, int n_cols, const uint8_t *packing, size_t packing_len,
                                int32_t *values);
 
+/* ---- LSOP08 (lsop/LsEncoder08.java:66-137, lsop/LsDecoder08.java:71-163, lsop/LsOptimalPredictor08.java:56-246,
+ * lsop/LsHeader.java:137-265, util/jama/LUDecomposition.java:70-134, 253-284): the optimal 8-coefficient linear predictor over
+ * the 3 x 3 neighbourhood, codec id "LSOP08".  Tiles need at least 4 rows and 4 columns (else GF_DECLINED, Java null); a singular
+ * system is GF_DECLINED too (JAMA throws).  GF_ERR_UNSUPPORTED: more than 16,384 columns or 2^26 or more cells.
+ *   residuals: per tile res_stride ints (>= gf_lsop08_residual_count): [2R+2C-5 initialisers | (R-2)(C-2) interior]
+ *   coefs:     per tile 16 words: seed, the 8 float32 coefficients as bit patterns, 7 words of 0
+ * The container: a 47-byte header (LsHeader.packHeader, never a checksum), then the CodecM32 bytes of the two streams either as two
+ * legacy Huffman segments back to back in one bit store (type 0) or as two zlib streams (type 1).  The reference writes type 0
+ * only where its body is STRICTLY shorter than the Deflate one.
+ *   - gf_lsop08_encode_batch_i32_dev WRITES TYPE 0 ALWAYS: Deflate needs the host's zlib and is not a device-resident operation.  Its
+ *     output is the reference's output exactly for the tiles where Huffman is the strictly shorter body.
+ *   - the host forms (gf_lsop08_encode_batch_i32, gf_lsop08_encode_i32) give the reference's choice, with the host's zlib at level 6;
+ *     types[t] (may be NULL) receives the container type written.  The reference deflates each stream into a buffer of its length +
+ *     128 bytes and would write a truncated packing if zlib needed more; such a tile is GF_ERR_UNSUPPORTED here and nothing is written.
+ * The decoders take both types and both header revisions and skip a value checksum where bit 7 of the type byte announces one,
+ * entirely on the device (the zlib streams by k_inflate).  GF_ERR_FORMAT: a coefficient count other than 8, a type other than 0 or
+ * 1, byte counts no encoder can emit; streams that end early: GF_ERR_FORMAT or GF_ERR_BOUNDS.  Nothing outside a packing's bytes is
+ * read.  The _dev forms run on the context's stream (as the gf_image_*_dev calls do) and only enqueue; the _dev decode allocates
+ * inflate scratch inside the context on first use.                                                                         */
+size_t gf_lsop08_residual_count(int n_rows, int n_cols);
+size_t gf_lsop08_max_packing(int n_rows, int n_cols);
+/* LsOptimalPredictor08.encode: tile -> coefficients + residual streams (d_status: GF_OK / GF_DECLINED per tile) */
+gf_status gf_lsop08_predict_dev(gf_context *ctx, int n_rows, int n_cols, size_t n_tiles, const int32_t *d_values,
+                                int32_t *d_residuals, size_t res_stride, uint32_t *d_coefs, int32_t *d_status);
+/* LsDecoder08.unpackInitializers + unpackInterior: residual streams -> tile.  d_in_status (may be NULL): tiles whose entry is not
+ * GF_OK are skipped and keep that status                                                                                      */
+gf_status gf_lsop08_reconstruct_dev(gf_context *ctx, int n_rows, int n_cols, size_t n_tiles, const int32_t *d_residuals,
+                                    size_t res_stride, const uint32_t *d_coefs, const int32_t *d_in_status, int32_t *d_values,
+                                    int32_t *d_status);
+/* device-resident batches; d_residuals / d_coefs / d_scratch_status (n_tiles ints) are caller-provided work buffers; d_out: slots of
+ * slot_stride bytes (a multiple of 16, 16-byte aligned; gf_lsop08_max_packing always fits; a slot too small: GF_OVERFLOW per tile) */
+gf_status gf_lsop08_encode_batch_i32_dev(gf_context *ctx, int codec_index, int n_rows, int n_cols, size_t n_tiles,
+                                         const int32_t *d_values, uint8_t *d_out, size_t slot_stride, uint32_t *d_lengths,
+                                         int32_t *d_status, int32_t *d_residuals, size_t res_stride, uint32_t *d_coefs,
+                                         int32_t *d_scratch_status);
+/* d_offsets may be NULL (then packing t starts at t * slot_stride); d_blob 4-byte aligned */
+gf_status gf_lsop08_decode_batch_i32_dev(gf_context *ctx, int n_rows, int n_cols, size_t n_tiles, const uint8_t *d_blob,
+                                         size_t blob_bytes, const uint64_t *d_offsets, size_t slot_stride,
+                                         const uint32_t *d_lengths, int32_t *d_values, int32_t *d_status, int32_t *d_residuals,
+                                         size_t res_stride, uint32_t *d_coefs, int32_t *d_scratch_status);
+/* host memory */
+gf_status gf_lsop08_encode_batch_i32(gf_context *ctx, int codec_index, int n_rows, int n_cols, size_t n_tiles,
+                                     const int32_t *values, uint8_t *blob, size_t blob_cap, uint64_t *offsets, uint8_t *types,
+                                     int32_t *status);
+gf_status gf_lsop08_decode_batch_i32(gf_context *ctx, int n_rows, int n_cols, size_t n_tiles, const uint8_t *blob,
+                                     const uint64_t *offsets, int32_t *values, int32_t *status);
+gf_status gf_lsop08_encode_i32(gf_context *ctx, int codec_index, int n_rows, int n_cols, const int32_t *values, uint8_t *out,
+                               size_t out_cap, size_t *out_len);
+gf_status gf_lsop08_decode_i32(gf_context *ctx, int n_rows, int n_cols, const uint8_t *packing, size_t packing_len,
+                               int32_t *values);
+
 /* ---- CodecMaster (gvrs/CodecMaster.java:150-169, 195-203): a file's codec list in one batched call ------------------
  * codecs[k] names the k-th entry of the codec list (the standard list of gvrs/GvrsFileSpecification.java:221-230 is
  * {GF_CODEC_HUFFMAN, GF_CODEC_DEFLATE, GF_CODEC_NONE (CodecFloat), GF_CODEC_CANON_HUFFMAN}); k is the codec index written
