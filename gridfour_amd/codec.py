@@ -1052,12 +1052,114 @@ class CodecFloatHip:
         return out, status
 
 
-class LsCodecHip:
+class _LsCodecBase:
+    """What the two optimal-predictor codecs share: the ICompressionEncoder / ICompressionDecoder forms, the batched host forms and
+    the predictor stage alone.  A subclass names its entry points' prefix (_PREFIX), its coefficient count (_N_COEF), the arguments
+    its device forms take between the context and the shape (_DEV_HEAD).  The docstrings cite the reference classes of both:
+    org.gridfour.lsop.LsEncoder12 / LsDecoder12 / LsOptimalPredictor12 and their 08 siblings."""
+    _PREFIX, _N_COEF, _DEV_HEAD = None, 0, ()
+
+    def __init__(self, context=None, device=0):
+        self.ctx = context if context is not None else GvrsHipContext(device)
+
+    def _encode_flags(self):
+        """the arguments of <prefix>_encode_batch_i32 between the values and the blob"""
+        return ()
+
+    # ---- ICompressionEncoder ----
+    def encode(self, codecIndex, nRows, nCols, values):
+        packs, _, status = self.encode_batch(codecIndex, nRows, nCols, np.asarray(values).reshape(1, -1))
+        if status[0] == _lib.DECLINED:
+            return None
+        check(int(status[0]), self._PREFIX + "_encode_batch_i32")
+        return packs[0]
+
+    def encodeFloats(self, codecIndex, nRows, nCols, values):
+        return None                                             # LsEncoder12.java:222-224, LsEncoder08.java:140-142
+
+    def implementsFloatingPointEncoding(self):
+        return False
+
+    def implementsIntegerEncoding(self):
+        return True
+
+    # ---- ICompressionDecoder ----
+    def decode(self, nRows, nColumns, packing):
+        vals, status = self.decode_batch(nRows, nColumns, [packing])
+        if status[0] in (_lib.ERR_FORMAT, _lib.ERR_BOUNDS):
+            raise IOError(lib().gf_status_string(int(status[0])).decode())
+        check(int(status[0]), self._PREFIX + "_decode_batch_i32")
+        return vals[0]
+
+    def decodeFloats(self, nRows, nColumns, packing):
+        return None
+
+    # ---- batched forms (host memory) ----
+    def encode_batch(self, codecIndex, nRows, nCols, tiles):
+        """Returns (packings: list[bytes|None], container types uint8, status int32)."""
+        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
+        nt = v.shape[0]
+        cap = nt * int(getattr(lib(), self._PREFIX + "_max_packing")(nRows, nCols)) + 64
+        blob = np.empty(cap, np.uint8)
+        offsets = np.zeros(nt + 1, np.uint64)
+        types = np.zeros(nt, np.uint8)
+        status = np.zeros(nt, np.int32)
+        _call(self._PREFIX + "_encode_batch_i32", self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), *self._encode_flags(), _ptr(blob), cap,
+              _ptr(offsets), _ptr(types), _ptr(status))
+        return _records_out(blob, offsets, nt, status), types, status
+
+    def decode_batch(self, nRows, nCols, packings):
+        nt = len(packings)
+        blob, offsets = _blob_of(packings)
+        out = np.zeros((nt, nRows * nCols), np.int32)
+        status = np.zeros(nt, np.int32)
+        _call(self._PREFIX + "_decode_batch_i32", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status))
+        return out, status
+
+    # ---- the predictor stage alone (device buffers handled here; used by tests and tools) ----
+    def _strides(self, nRows, nCols):
+        n = int(getattr(lib(), self._PREFIX + "_residual_count")(nRows, nCols))
+        return n, max(4, (n + 3) // 4 * 4)
+
+    def predict(self, nRows, nCols, tiles):
+        """LsOptimalPredictor12 / 08.encode: returns (seed, coefficients float32[nt, 12 or 8], residuals int32[nt,n], status)."""
+        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
+        nt = v.shape[0]
+        n, stride = self._strides(nRows, nCols)
+        with _DeviceScope(self.ctx) as s:
+            dv, dr, dc, ds = s.upload(v), s.alloc(nt * stride * 4 + 16), s.alloc(nt * 64, fill=0), s.alloc(nt * 4)
+            s.run(self._PREFIX + "_predict_dev", self.ctx.handle, *self._DEV_HEAD, nRows, nCols, nt, dv.ptr, dr.ptr, stride, dc.ptr, ds.ptr)
+            res = dr.download(np.int32, nt * stride).reshape(nt, stride)[:, :n]
+            coefs = dc.download(np.uint32, nt * 16).reshape(nt, 16)
+            status = ds.download(np.int32, nt)
+        return coefs[:, 0].astype(np.int32), coefs[:, 1:1 + self._N_COEF].copy().view(np.float32), res, status
+
+    def reconstruct(self, nRows, nCols, seeds, coefficients, residuals):
+        """LsDecoder12 / 08.unpackInitializers/unpackInterior: returns (values int32[nt, cells], status)."""
+        res = np.ascontiguousarray(residuals, dtype=np.int32)
+        nt, n = res.shape
+        stride = max(4, (n + 3) // 4 * 4)
+        padded = np.zeros((nt, stride), np.int32)
+        padded[:, :n] = res
+        coefs = np.zeros((nt, 16), np.uint32)
+        coefs[:, 0] = np.asarray(seeds, np.int32).view(np.uint32)
+        coefs[:, 1:1 + self._N_COEF] = np.ascontiguousarray(coefficients, np.float32).view(np.uint32).reshape(nt, self._N_COEF)
+        with _DeviceScope(self.ctx) as s:
+            dv, dr, dc, ds = s.alloc(nt * nRows * nCols * 4), s.upload(padded, slack=16), s.upload(coefs), s.alloc(nt * 4)
+            s.run(self._PREFIX + "_reconstruct_dev", self.ctx.handle, *self._DEV_HEAD, nRows, nCols, nt, dr.ptr, stride, dc.ptr, None, dv.ptr,
+                  ds.ptr)
+            vals = dv.download(np.int32, nt * nRows * nCols).reshape(nt, nRows * nCols)
+            status = ds.download(np.int32, nt)
+        return vals, status
+
+
+class LsCodecHip(_LsCodecBase):
     """Drop-in for org.gridfour.lsop.LsEncoder12 + LsDecoder12 (codec id "LSOP12", LsCodecUtility.java:53),
     computed on the MI355X; the Deflate alternative container uses the host's zlib as the reference uses the JDK's."""
+    _PREFIX, _N_COEF, _DEV_HEAD = "gf_lsop12", 12, (None,)      # (its device forms take a stream: the context's own)
 
     def __init__(self, context=None, device=0, deflate_enabled=True, value_checksum_enabled=False):
-        self.ctx = context if context is not None else GvrsHipContext(device)
+        super().__init__(context, device)
         self.deflate_enabled = bool(deflate_enabled)           # LsEncoder12.setDeflateEnabled, default true
         self.value_checksum_enabled = bool(value_checksum_enabled)   # LsEncoder12.setValueChecksumEnabled, default false
 
@@ -1067,157 +1169,17 @@ class LsCodecHip:
     def setValueChecksumEnabled(self, enabled):
         self.value_checksum_enabled = bool(enabled)            # LsEncoder12.java:117-119
 
-    # ---- ICompressionEncoder ----
-    def encode(self, codecIndex, nRows, nCols, values):
-        packs, _, status = self.encode_batch(codecIndex, nRows, nCols, np.asarray(values).reshape(1, -1))
-        if status[0] == _lib.DECLINED:
-            return None
-        check(int(status[0]), "gf_lsop12_encode_batch_i32")
-        return packs[0]
-
-    def encodeFloats(self, codecIndex, nRows, nCols, values):
-        return None                                             # LsEncoder12.java:222-224
-
-    def implementsFloatingPointEncoding(self):
-        return False
-
-    def implementsIntegerEncoding(self):
-        return True
-
-    # ---- ICompressionDecoder ----
-    def decode(self, nRows, nColumns, packing):
-        vals, status = self.decode_batch(nRows, nColumns, [packing])
-        if status[0] in (_lib.ERR_FORMAT, _lib.ERR_BOUNDS):
-            raise IOError(lib().gf_status_string(int(status[0])).decode())
-        check(int(status[0]), "gf_lsop12_decode_batch_i32")
-        return vals[0]
-
-    def decodeFloats(self, nRows, nColumns, packing):
-        return None
-
-    # ---- batched forms (host memory) ----
-    def encode_batch(self, codecIndex, nRows, nCols, tiles):
-        """Returns (packings: list[bytes|None], container types uint8, status int32)."""
-        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
-        nt = v.shape[0]
-        cap = nt * int(lib().gf_lsop12_max_packing(nRows, nCols)) + 64
-        blob = np.empty(cap, np.uint8)
-        offsets = np.zeros(nt + 1, np.uint64)
-        types = np.zeros(nt, np.uint8)
-        status = np.zeros(nt, np.int32)
-        flags = (_lib.LSOP_DEFLATE if self.deflate_enabled else 0) | (_lib.LSOP_VALUE_CHECKSUM if self.value_checksum_enabled else 0)
-        _call("gf_lsop12_encode_batch_i32", self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), flags, _ptr(blob), cap, _ptr(offsets),
-              _ptr(types), _ptr(status))
-        return _records_out(blob, offsets, nt, status), types, status
-
-    def decode_batch(self, nRows, nCols, packings):
-        nt = len(packings)
-        blob, offsets = _blob_of(packings)
-        out = np.zeros((nt, nRows * nCols), np.int32)
-        status = np.zeros(nt, np.int32)
-        _call("gf_lsop12_decode_batch_i32", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status))
-        return out, status
-
-    # ---- the predictor stage alone (device buffers handled here; used by tests and tools) ----
-    def predict(self, nRows, nCols, tiles):
-        """LsOptimalPredictor12.encode: returns (seed, coefficients float32[nt,12], residuals int32[nt,n], status)."""
-        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
-        nt = v.shape[0]
-        n = int(lib().gf_lsop12_residual_count(nRows, nCols))
-        stride = (n + 3) // 4 * 4
-        with _DeviceScope(self.ctx) as s:
-            dv, dr, dc, ds = s.alloc(v.nbytes), s.alloc(nt * stride * 4 + 16), s.alloc(nt * 64), s.alloc(nt * 4)
-            dv.upload(v)
-            s.run("gf_lsop12_predict_dev", self.ctx.handle, None, nRows, nCols, nt, dv.ptr, dr.ptr, stride, dc.ptr, ds.ptr)
-            res = dr.download(np.int32, nt * stride).reshape(nt, stride)[:, :n]
-            coefs = dc.download(np.uint32, nt * 16).reshape(nt, 16)
-            status = ds.download(np.int32, nt)
-        return coefs[:, 0].astype(np.int32), coefs[:, 1:13].copy().view(np.float32), res, status
-
-    def reconstruct(self, nRows, nCols, seeds, coefficients, residuals):
-        """LsDecoder12.unpackInitializers/unpackInterior: returns (values int32[nt, cells], status)."""
-        res = np.ascontiguousarray(residuals, dtype=np.int32)
-        nt, n = res.shape
-        stride = (n + 3) // 4 * 4
-        padded = np.zeros((nt, stride), np.int32)
-        padded[:, :n] = res
-        coefs = np.zeros((nt, 16), np.uint32)
-        coefs[:, 0] = np.asarray(seeds, np.int32).view(np.uint32)
-        coefs[:, 1:13] = np.ascontiguousarray(coefficients, np.float32).view(np.uint32).reshape(nt, 12)
-        with _DeviceScope(self.ctx) as s:
-            dv, dr, dc, ds = s.alloc(nt * nRows * nCols * 4), s.alloc(padded.nbytes + 16), s.alloc(nt * 64), s.alloc(nt * 4)
-            dr.upload(padded)
-            dc.upload(coefs)
-            s.run("gf_lsop12_reconstruct_dev", self.ctx.handle, None, nRows, nCols, nt, dr.ptr, stride, dc.ptr, None, dv.ptr, ds.ptr)
-            vals = dv.download(np.int32, nt * nRows * nCols).reshape(nt, nRows * nCols)
-            status = ds.download(np.int32, nt)
-        return vals, status
+    def _encode_flags(self):
+        return ((_lib.LSOP_DEFLATE if self.deflate_enabled else 0) | (_lib.LSOP_VALUE_CHECKSUM if self.value_checksum_enabled else 0),)
 
 
-class LsCodec08Hip:
+class LsCodec08Hip(_LsCodecBase):
     """Drop-in for org.gridfour.lsop.LsEncoder08 + LsDecoder08 (codec id "LSOP08", the 3 x 3-neighbourhood sibling of LSOP12), computed
     on the MI355X.  encode / encode_batch give the reference's choice between the Huffman and the Deflate container (the latter with
     the host's zlib, as the reference uses the JDK's); encode_batch_dev is the device encoder, which writes the Huffman container."""
-
-    def __init__(self, context=None, device=0):
-        self.ctx = context if context is not None else GvrsHipContext(device)
-
-    # ---- ICompressionEncoder ----
-    def encode(self, codecIndex, nRows, nCols, values):
-        packs, _, status = self.encode_batch(codecIndex, nRows, nCols, np.asarray(values).reshape(1, -1))
-        if status[0] == _lib.DECLINED:
-            return None
-        check(int(status[0]), "gf_lsop08_encode_batch_i32")
-        return packs[0]
-
-    def encodeFloats(self, codecIndex, nRows, nCols, values):
-        return None                                             # LsEncoder08.java:140-142
-
-    def implementsFloatingPointEncoding(self):
-        return False
-
-    def implementsIntegerEncoding(self):
-        return True
-
-    # ---- ICompressionDecoder ----
-    def decode(self, nRows, nColumns, packing):
-        vals, status = self.decode_batch(nRows, nColumns, [packing])
-        if status[0] in (_lib.ERR_FORMAT, _lib.ERR_BOUNDS):
-            raise IOError(lib().gf_status_string(int(status[0])).decode())
-        check(int(status[0]), "gf_lsop08_decode_batch_i32")
-        return vals[0]
-
-    def decodeFloats(self, nRows, nColumns, packing):
-        return None
-
-    # ---- batched forms (host memory) ----
-    def encode_batch(self, codecIndex, nRows, nCols, tiles):
-        """Returns (packings: list[bytes|None], container types uint8, status int32)."""
-        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
-        nt = v.shape[0]
-        cap = nt * int(lib().gf_lsop08_max_packing(nRows, nCols)) + 64
-        blob = np.empty(cap, np.uint8)
-        offsets = np.zeros(nt + 1, np.uint64)
-        types = np.zeros(nt, np.uint8)
-        status = np.zeros(nt, np.int32)
-        _call("gf_lsop08_encode_batch_i32", self.ctx.handle, codecIndex, nRows, nCols, nt, _ptr(v), _ptr(blob), cap, _ptr(offsets),
-              _ptr(types), _ptr(status))
-        return _records_out(blob, offsets, nt, status), types, status
-
-    def decode_batch(self, nRows, nCols, packings):
-        nt = len(packings)
-        blob, offsets = _blob_of(packings)
-        out = np.zeros((nt, nRows * nCols), np.int32)
-        status = np.zeros(nt, np.int32)
-        _call("gf_lsop08_decode_batch_i32", self.ctx.handle, nRows, nCols, nt, _ptr(blob), _ptr(offsets), _ptr(out), _ptr(status))
-        return out, status
+    _PREFIX, _N_COEF = "gf_lsop08", 8
 
     # ---- the device forms (device buffers handled here; used by tests and tools) ----
-    @staticmethod
-    def _strides(nRows, nCols):
-        n = int(lib().gf_lsop08_residual_count(nRows, nCols))
-        return n, max(4, (n + 3) // 4 * 4)
-
     def encode_batch_dev(self, codecIndex, nRows, nCols, tiles):
         """gf_lsop08_encode_batch_i32_dev: the Huffman container of every tile.  Returns (packings: list[bytes|None], status)."""
         v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
@@ -1246,36 +1208,6 @@ class LsCodec08Hip:
             dr, dc, d2 = s.alloc(nt * stride * 4 + 16), s.alloc(nt * 64), s.alloc(nt * 4)
             s.run("gf_lsop08_decode_batch_i32_dev", self.ctx.handle, nRows, nCols, nt, db.ptr, int(offsets[-1]), dof.ptr, 0, dl.ptr, dv.ptr,
                   ds.ptr, dr.ptr, stride, dc.ptr, d2.ptr)
-            vals = dv.download(np.int32, nt * nRows * nCols).reshape(nt, nRows * nCols)
-            status = ds.download(np.int32, nt)
-        return vals, status
-
-    def predict(self, nRows, nCols, tiles):
-        """LsOptimalPredictor08.encode: returns (seed, coefficients float32[nt,8], residuals int32[nt,n], status)."""
-        v = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, nRows * nCols)
-        nt = v.shape[0]
-        n, stride = self._strides(nRows, nCols)
-        with _DeviceScope(self.ctx) as s:
-            dv, dr, dc, ds = s.upload(v), s.alloc(nt * stride * 4 + 16), s.alloc(nt * 64, fill=0), s.alloc(nt * 4)
-            s.run("gf_lsop08_predict_dev", self.ctx.handle, nRows, nCols, nt, dv.ptr, dr.ptr, stride, dc.ptr, ds.ptr)
-            res = dr.download(np.int32, nt * stride).reshape(nt, stride)[:, :n]
-            coefs = dc.download(np.uint32, nt * 16).reshape(nt, 16)
-            status = ds.download(np.int32, nt)
-        return coefs[:, 0].astype(np.int32), coefs[:, 1:9].copy().view(np.float32), res, status
-
-    def reconstruct(self, nRows, nCols, seeds, coefficients, residuals):
-        """LsDecoder08.unpackInitializers/unpackInterior: returns (values int32[nt, cells], status)."""
-        res = np.ascontiguousarray(residuals, dtype=np.int32)
-        nt, n = res.shape
-        stride = max(4, (n + 3) // 4 * 4)
-        padded = np.zeros((nt, stride), np.int32)
-        padded[:, :n] = res
-        coefs = np.zeros((nt, 16), np.uint32)
-        coefs[:, 0] = np.asarray(seeds, np.int32).view(np.uint32)
-        coefs[:, 1:9] = np.ascontiguousarray(coefficients, np.float32).view(np.uint32).reshape(nt, 8)
-        with _DeviceScope(self.ctx) as s:
-            dv, dr, dc, ds = s.alloc(nt * nRows * nCols * 4), s.upload(padded, slack=16), s.upload(coefs), s.alloc(nt * 4)
-            s.run("gf_lsop08_reconstruct_dev", self.ctx.handle, nRows, nCols, nt, dr.ptr, stride, dc.ptr, None, dv.ptr, ds.ptr)
             vals = dv.download(np.int32, nt * nRows * nCols).reshape(nt, nRows * nCols)
             status = ds.download(np.int32, nt)
         return vals, status

@@ -24,6 +24,7 @@
 #include "gvrs_kernels.h"
 #include "gvrs_encode_layout.h"
 #include "gvrs_carve.h"
+#include "gvrs_lsop_container.h"
 #include "gvrs_stage.h"
 
 #pragma GCC visibility push(hidden)
@@ -53,8 +54,6 @@ inline gf_status hipFail(hipError_t e, const char *what)
         hipError_t e_ = (call);                        \
         if (e_ != hipSuccess) return hipFail(e_, #call); \
     } while (0)
-
-inline size_t roundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // offsets[nTiles + 1] of a caller's blob: non-decreasing, every packing shorter than 4 GiB (lengths travel as uint32)
 inline bool offsetsValid(const uint64_t *offsets, size_t nTiles)
@@ -230,7 +229,7 @@ static void parallelFor(size_t n, F f)
     for (auto &x : th) x.join();
 }
 
-inline void putLE32(uint8_t *p, uint32_t x) { p[0] = (uint8_t)x; p[1] = (uint8_t)(x >> 8); p[2] = (uint8_t)(x >> 16); p[3] = (uint8_t)(x >> 24); }
+// (putLE32, roundUp and zDeflate: gvrs_lsop_container.h)
 inline uint32_t getLE32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
 // One tile through a codec's batch entry point (the ICompressionEncoder / ICompressionDecoder form): batch(offsets, &tileStatus) is
@@ -270,7 +269,6 @@ gf_status decodeBatchHost(int kind, gf_context *c, int nRows, int nCols, size_t 
 // gvrs_api_float.hip
 gf_status floatDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
                          const uint64_t *dOffsets, const uint32_t *dLengths, float *dValues, int32_t *dStatus);
-bool zDeflate(const uint8_t *in, size_t n, int level, std::vector<uint8_t> &out);
 bool zDeflateUpTo(const uint8_t *in, size_t n, int level, size_t limit, std::vector<uint8_t> &out);
 // gvrs_api_records_dev.hip: the argument checks of the elements calls, an element's bytes per cell, and the one device pipeline
 // (no lock taken, no argument checked: its callers hold the context's lock)

@@ -12,6 +12,7 @@
 #include "gvrs_downsample_common.h"
 #include "gvrs_image_common.h"
 #include "gvrs_tabulate_common.h"
+#include "gvrs_lsop_container.h"
 
 // per-tile status values written by the kernels; identical to gf_status in
 // include/gvrs_hip_codec.h
@@ -177,14 +178,12 @@ struct GfLsopForm {
     uint32_t nCoef, nInit, nInt;
     int strictTypes;
 };
-inline GfLsopForm gf_lsop12_form(int nRows, int nCols)
+inline GfLsopForm gf_lsop_form(const LsopFamily &F, int nRows, int nCols, int strictTypes)       // (the numbers: gvrs_lsop_container.h)
 {
-    return GfLsopForm{12u, (uint32_t)(4 * nRows + 2 * nCols - 9), (uint32_t)(nRows - 2) * (uint32_t)(nCols - 4), 0};
+    return GfLsopForm{F.nCoef, (uint32_t)F.nInit(nRows, nCols), (uint32_t)F.nInt(nRows, nCols), strictTypes};
 }
-inline GfLsopForm gf_lsop08_form(int nRows, int nCols)
-{
-    return GfLsopForm{8u, (uint32_t)(2 * nRows + 2 * nCols - 5), (uint32_t)(nRows - 2) * (uint32_t)(nCols - 2), 1};
-}
+inline GfLsopForm gf_lsop12_form(int nRows, int nCols) { return gf_lsop_form(GF_LSOP12, nRows, nCols, 0); }
+inline GfLsopForm gf_lsop08_form(int nRows, int nCols) { return gf_lsop_form(GF_LSOP08, nRows, nCols, 1); }
 
 // LSOP containers whose entropy stage is CodecM32 bytes: type 0 (legacy Huffman of the two M32 streams) and, with
 // rawM32 = 1, type 1 after the host inflated it (gvrs_decode.hip: k_lsop_unpack_m32)
