@@ -161,6 +161,14 @@ SIGNATURES = {
     "gf_block_tabulate_dense": (C.c_int, [_vp, C.c_int, C.c_int32, C.c_int, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "gf_block_tabulate_symbols_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
     "gf_block_tabulate_symbols": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
+    "gf_tab_symbols_merge_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "gf_tab_symbols_merge": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "gf_block_tabulate_symbols_acc_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "gf_block_tabulate_symbols_acc": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "gf_block_read_tabulated_symbols_elems_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_int,
+                                                            C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "gf_block_read_tabulated_symbols_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp, _vp,
+                                                        _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp]),
     "gf_tab_entropy_counts": (C.c_int, [_vp, C.c_size_t, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
     "gf_compact_dev":(C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
     "gf_float_planes_bytes": (C.c_size_t, [C.c_int, C.c_int]),

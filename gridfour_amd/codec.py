@@ -49,6 +49,7 @@ _ELEM_RANGE = np.dtype([("min_i", np.int32), ("max_i", np.int32), ("min_f", np.f
 IMAGE_RGB, IMAGE_YCOCG = 0, 1                                              # GF_IMAGE_*
 IMAGE_MODELS = {"rgb": IMAGE_RGB, "ycocg": IMAGE_YCOCG}
 TAB_ACCUMULATE, TAB_SKIP_FILL = 1, 2                                      # GF_TAB_*
+TAB_SYM_INPUT_TRUNCATED = 1                                               # GF_TAB_SYM_INPUT_TRUNCATED
 _TAB_DENSE = np.dtype([("def_min", np.int32), ("def_max", np.int32), ("scale", np.float64)])                          # gf_tab_dense
 _TAB_DENSE_PLAN = np.dtype([("n_counter", np.int32), ("base", np.int32), ("n_bins", np.int64), ("scale_used", np.float64)])   # gf_tab_dense_plan
 TAB_SUMMARY = np.dtype([("n_cells", np.int64), ("n_skipped", np.int64), ("n_samples", np.int64), ("sum_samples", np.int64), ("sum_i", np.int64),
@@ -200,6 +201,30 @@ def _tab_dense_spec(def_min, def_max, scale):
     s = np.zeros(1, _TAB_DENSE)
     s["def_min"], s["def_max"], s["scale"] = def_min, def_max, scale
     return s
+
+
+def _tab_table_in(table):
+    """A symbol table as the host forms take it in: None (empty) or (symbols, counts, summary dict) -> (symbols uint32, counts
+    int32, gf_tab_symbols [1] or None, the arguments: three pointers and the cap)"""
+    if table is None:
+        return None, None, None, (None, None, None, 0)
+    sym, cnt = np.ascontiguousarray(table[0], np.uint32).ravel(), np.ascontiguousarray(table[1], np.int32).ravel()
+    assert sym.size == cnt.size
+    summary = np.zeros(1, TAB_SYMBOLS)
+    for k in TAB_SYMBOLS.names:
+        summary[k] = table[2][k]
+    return sym, cnt, summary, (_ptr(sym) if sym.size else None, _ptr(cnt) if sym.size else None, _ptr(summary), sym.size)
+
+
+def _tab_table_out(name, cap, call):
+    """The out table of a host form: call(symbols pointer, counts pointer, cap, summary pointer) -> status; a table that does not
+    hold every symbol (ERR_CAPACITY) comes back with what it has -> (symbols, counts, summary dict)"""
+    symbols, counts, summary = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int32), np.zeros(1, TAB_SYMBOLS)
+    st = call(_ptr(symbols) if cap else None, _ptr(counts) if cap else None, cap, _ptr(summary))
+    if st != _lib.ERR_CAPACITY:
+        check(st, name)
+    n = int(summary["n_written"][0])
+    return symbols[:n], counts[:n], {k: summary[k][0].item() for k in TAB_SYMBOLS.names}
 
 
 def interp_spec(n_rows_grid, n_cols_grid, block=None, elem_type="float", fill_i=0, wrap=0, target=INTERP_VALUE, row_spacing=1.0,
@@ -544,6 +569,41 @@ class GvrsHipContext:
             check(st, "gf_block_tabulate_symbols")
         n = int(summary["n_written"][0])
         return symbols[:n], counts[:n], {k: summary[k][0].item() for k in TAB_SYMBOLS.names}
+
+    # ---- symbol tables merged, strips accumulated onto a table (gf_tab_symbols_merge[_dev], gf_block_tabulate_symbols_acc[_dev]) ----
+    def tab_symbols_merge_dev(self, d_sym_a, d_cnt_a, d_sum_a, cap_a, d_sym_b, d_cnt_b, d_sum_b, cap_b, d_sym_out, d_cnt_out, table_cap, d_sum_out):
+        """gf_tab_symbols_merge_dev on device pointers: tables A and B (their lengths are read on the device from their summaries:
+        min(n_written, cap)) -> the out table, which overlaps neither.  Enqueues on the context's stream."""
+        _call("gf_tab_symbols_merge_dev", self._h, d_sym_a, d_cnt_a, d_sum_a, int(cap_a), d_sym_b, d_cnt_b, d_sum_b, int(cap_b), d_sym_out,
+              d_cnt_out, int(table_cap), d_sum_out)
+
+    def tab_symbols_merge(self, a, b, table_cap=None):
+        """gf_tab_symbols_merge, the host-memory form: a, b = (symbols, counts, summary dict) as tabulate_symbols returns them ->
+        (symbols, counts, summary dict); table_cap None: room for every entry of both.  summary["reserved"] &
+        TAB_SYM_INPUT_TRUNCATED: an input did not hold all of its symbols."""
+        sa, ca, ua, arg_a = _tab_table_in(a)
+        sb, cb, ub, arg_b = _tab_table_in(b)
+        cap = sa.size + sb.size if table_cap is None else int(table_cap)
+        fn = lib().gf_tab_symbols_merge
+        return _tab_table_out("gf_tab_symbols_merge", cap, lambda sym, cnt, n, summ: fn(self._h, *arg_a, *arg_b, sym, cnt, n, summ))
+
+    def tabulate_symbols_acc_dev(self, elem_type, d_block, n_cells, d_sym_in, d_cnt_in, d_sum_in, cap_in, d_sym_out, d_cnt_out, cap_out, d_sum_out):
+        """gf_block_tabulate_symbols_acc_dev on device pointers: the symbols of n_cells cells (a strip of a raster) counted onto the
+        in-table (None / cap_in 0: empty) -> the out table, which does not overlap it.  Enqueues on the context's stream."""
+        _call("gf_block_tabulate_symbols_acc_dev", self._h, _elem_type(elem_type), d_block, int(n_cells), d_sym_in, d_cnt_in, d_sum_in, int(cap_in),
+              d_sym_out, d_cnt_out, int(cap_out), d_sum_out)
+
+    def tabulate_symbols_acc(self, elem_type, block, into=None, table_cap=None):
+        """gf_block_tabulate_symbols_acc, the host-memory form: the symbols of block counted onto the table into = (symbols, counts,
+        summary dict) of an earlier call (None: empty) -> (symbols, counts, summary dict); table_cap None: room for every cell."""
+        et = _elem_type(elem_type)
+        block = np.ascontiguousarray(block, _delivered_dtype(et)).ravel()
+        keep = block if block.size else np.zeros(1, block.dtype)
+        si, ci, ui, arg_in = _tab_table_in(into)
+        cap = arg_in[3] + block.size if table_cap is None else int(table_cap)
+        fn = lib().gf_block_tabulate_symbols_acc
+        return _tab_table_out("gf_block_tabulate_symbols_acc", cap,
+                              lambda sym, cnt, n, summ: fn(self._h, et, _ptr(keep), block.size, *arg_in, sym, cnt, n, summ))
 
     @staticmethod
     def tab_entropy(counts, n_samples, kahan=True):
@@ -1509,6 +1569,45 @@ class CodecMasterHip:
         _call("gf_block_read_downsampled_elems", *self._head(), _ptr(specs), ne, _ptr(grid), _ptr(rect), *factor, nt, _ptr(blob), _ptr(offsets),
               int(bool(verify_checksums)), _ptrs(out), _ptr(status))
         return [a[:n_rows * n_cols].reshape(n_rows, n_cols) for a in out], status
+
+    # ---- a rectangle read from tile records and its symbols counted onto a table (gf_block_read_tabulated_symbols_elems[_dev]) ----
+    def read_block_tabulated_symbols_dev(self, nRows, nCols, grid_shape, rect, blob, offsets, elems, which, into=None, fills=None,
+                                         verify_checksums=True, table_cap=None):
+        """gf_block_read_tabulated_symbols_elems_dev: read_block_dev's arguments, the element `which` whose symbols are counted (an
+        "icf" element as its int32 codes) and the table into = (symbols, counts, summary dict) they are counted onto (None: empty).
+        Uploads and downloads: ((symbols, counts, summary dict), status [n_elems, nt]); good iff every status is 0."""
+        specs, dtypes, blob, offsets, grid, rect, shape, _ = self._read_args(nRows, nCols, grid_shape, rect, None, blob, offsets, elems, fills, False)
+        nt, ne = offsets.size - 1, len(dtypes)
+        sym_in, cnt_in, sum_in, _ = _tab_table_in(into)
+        n_in = 0 if into is None else sym_in.size
+        cap = n_in + shape[0] * shape[1] if table_cap is None else int(table_cap)
+        with _DeviceScope(self.ctx) as s:
+            d_blob, d_off = s.upload(blob, slack=32, fill=0), s.upload(offsets)
+            d_in = [s.upload(a, slack=16) for a in (sym_in, cnt_in, sum_in)] if into is not None else None
+            d_sym, d_cnt, d_sum = s.alloc(cap * 4 + 16, fill=0), s.alloc(cap * 4 + 16, fill=0), s.alloc(TAB_SYMBOLS.itemsize, fill=0)
+            d_st = s.alloc(ne * nt * 4 + 16, fill=0)
+            in_args = (None, None, None, 0) if d_in is None else (d_in[0].ptr, d_in[1].ptr, d_in[2].ptr, n_in)
+            s.run("gf_block_read_tabulated_symbols_elems_dev", *self._head(), _ptr(specs), ne, _ptr(grid), _ptr(rect), nt, d_blob.ptr, blob.size,
+                  d_off.ptr, int(bool(verify_checksums)), int(which), *in_args, d_sym.ptr if cap else None, d_cnt.ptr if cap else None, cap,
+                  d_sum.ptr, d_st.ptr)
+            summary = d_sum.download(TAB_SYMBOLS, 1)
+            n = int(summary["n_written"][0])
+            table = (d_sym.download(np.uint32, n), d_cnt.download(np.int32, n), {k: summary[k][0].item() for k in TAB_SYMBOLS.names})
+            return table, d_st.download(np.int32, ne * nt).reshape(ne, nt)
+
+    def read_block_tabulated_symbols(self, nRows, nCols, grid_shape, rect, blob, offsets, elems, which, into=None, fills=None,
+                                     verify_checksums=True, table_cap=None):
+        """The same through gf_block_read_tabulated_symbols_elems, the host-memory form; offsets[-1] bytes of blob are read."""
+        specs, dtypes, blob, offsets, grid, rect, shape, _ = self._read_args(nRows, nCols, grid_shape, rect, None, blob, offsets, elems, fills, True)
+        nt, ne = offsets.size - 1, len(dtypes)
+        si, ci, ui, arg_in = _tab_table_in(into)
+        cap = arg_in[3] + shape[0] * shape[1] if table_cap is None else int(table_cap)
+        status = np.zeros((ne, nt), np.int32)
+        fn = lib().gf_block_read_tabulated_symbols_elems
+        table = _tab_table_out("gf_block_read_tabulated_symbols_elems", cap,
+                               lambda sym, cnt, n, summ: fn(*self._head(), _ptr(specs), ne, _ptr(grid), _ptr(rect), nt, _ptr(blob), _ptr(offsets),
+                                                            int(bool(verify_checksums)), int(which), *arg_in, sym, cnt, n, summ, _ptr(status)))
+        return table, status
 
     # ---- grid blocks written: raster in, tile records out (gf_block_write_elems[_dev]) ----
     @staticmethod

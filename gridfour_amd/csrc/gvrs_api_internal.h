@@ -151,7 +151,8 @@ struct gf_context {
     DevBuf dDsBlocks{this};                     // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks
     DevBuf dImage{this};                        // images (gvrs_api_image.hip): the record forms' three planes
     DevBuf dTabPartials{this}, dTabSort{this};  // tabulation (gvrs_api_tabulate.hip): k_tabulate_dense's partials (fixed size); the symbol form's
-                                                // keys, histograms and runs
+                                                // keys, histograms and runs, a strip's table and the merge's chunk counts
+    DevBuf dTabBlocks{this};                    // ... the composed read's blocks (gf_block_read_tabulated_symbols_elems[_dev])
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
     // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
     // scratch buffers, staging slots and recorded graphs are one set.  Recursive: entry points call each other.

@@ -766,3 +766,33 @@ struct GfTabSymbolsArgs {
     GfTabSymbols *summary;
 };
 hipError_t gf_launch_tab_symbols(const GfTabSymbolsArgs &a, hipStream_t stream);
+// Two symbol tables merged (gvrs_tabulate_common.h states the rule).  A table's length is read on the device: min(n_written of its
+// summary, its cap), 0 with a null summary (and, with its bit of noSamplesIsEmpty set -- 1: A, 2: B --, with n_samples == 0); caps
+// up to 2^31 - 1.  splits: gf_tab_merge_chunks(capA, capB) + 1 words, heads: one fewer, sums: that / GF_TAB_SCAN_BLOCK rounded up,
+// nSym: one word;
+// symbols / counts: cap entries each (null with cap == 0), disjoint from the inputs; *summary is written whole.
+struct GfTabMergeArgs {
+    const uint32_t *symA, *symB;
+    const int32_t *cntA, *cntB;
+    const GfTabSymbols *sumA, *sumB;
+    uint32_t capA, capB, noSamplesIsEmpty;
+    uint32_t *splits, *heads, *sums, *nSym;
+    uint32_t *symbols;
+    int32_t *counts;
+    size_t cap;
+    GfTabSymbols *summary;
+};
+size_t gf_tab_merge_chunks(uint32_t capA, uint32_t capB);
+hipError_t gf_launch_tab_merge(const GfTabMergeArgs &a, hipStream_t stream);
+// The symbol form of a SHORT block of n >= 1 cells (2-byte aligned) by 65,536 counters, without widening or sorting.  counter:
+// 65,536 words (zeroed here); symbols / counts: cap entries each (null with cap == 0); *summary is written whole.
+struct GfTabShortArgs {
+    const void *block;
+    uint32_t n;
+    int32_t *counter;
+    uint32_t *symbols;
+    int32_t *counts;
+    size_t cap;
+    GfTabSymbols *summary;
+};
+hipError_t gf_launch_tab_short(const GfTabShortArgs &a, hipStream_t stream);

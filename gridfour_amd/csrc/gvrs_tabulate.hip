@@ -18,6 +18,12 @@
 // k_tab_runs: phase 0 counts the run heads of GF_TAB_RUN_BLOCK sorted keys (scanned by k_tab_digit_scan), phase 1 writes every
 // head's position and symbol, phase 2 turns positions into counts and adds up the scalars.
 //
+// Two tables merged (gvrs_tabulate_common.h states the merged sequence and the pair rule): k_tab_merge_splits finds the split of
+// every chunk of GF_TAB_MERGE_BLOCK positions by binary search, k_tab_merge merges a chunk in LDS -- phase 0 counts its heads
+// (scanned by k_tab_digit_scan), k_tab_merge_head writes the summary, phase 1 writes symbols and summed counts and adds up the
+// scalars.  A SHORT block by counters: k_tab_short_counts (a window of the 65,536 counters in LDS, the rest by global atomics),
+// k_tab_short_compact (the counters that are not 0, in the symbols' order).
+//
 // Nothing outside the block is read; the counters, the summary, the tables up to their capacity and the context's temporaries
 // are all that is written.
 
@@ -443,6 +449,203 @@ hipError_t tabScan(uint32_t *data, size_t len, uint32_t *sums, uint32_t *total, 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- the symbol form: two tables merged
+
+constexpr uint32_t MERGE_PER = GF_TAB_MERGE_BLOCK / ST;
+constexpr uint32_t MERGE_WIN = GF_TAB_MERGE_BLOCK + 4;                            // gf_tab_merge_window's bound
+
+struct TabMergeIn {
+    const uint32_t *symA, *symB;
+    const int32_t *cntA, *cntB;
+    const GfTabSymbols *sumA, *sumB;
+    uint32_t capA, capB, noSamplesIsEmpty;
+};
+__device__ __forceinline__ uint32_t tabLenA(const TabMergeIn &in) { return gf_tab_table_len(in.sumA, in.capA, in.noSamplesIsEmpty & 1u); }
+__device__ __forceinline__ uint32_t tabLenB(const TabMergeIn &in) { return gf_tab_table_len(in.sumB, in.capB, in.noSamplesIsEmpty & 2u); }
+
+// splits[i] = the split of the merged sequence at position min(i * GF_TAB_MERGE_BLOCK, nA + nB), i = 0 .. nChunks: one lane each,
+// so that the searches through the tables, a chain of dependent loads each, all run at once and no workgroup of k_tab_merge waits
+// for its own
+__global__ __launch_bounds__(ST) void k_tab_merge_splits(const TabMergeIn in, uint32_t *__restrict__ splits, const size_t nChunks)
+{
+    const size_t i = tabGroup() * ST + threadIdx.x;
+    if (i > nChunks) return;
+    const uint32_t nA = tabLenA(in), nB = tabLenB(in);
+    const uint64_t n = (uint64_t)nA + nB, d = (uint64_t)i * GF_TAB_MERGE_BLOCK;
+    splits[i] = gf_tab_merge_split(in.symA, nA, in.symB, nB, d < n ? d : n);
+}
+
+// Workgroup b owns positions [b * GF_TAB_MERGE_BLOCK ..) of the merged sequence (gvrs_tabulate_common.h); the grid is laid out for
+// capA + capB positions and the workgroups behind the tables' real lengths, which only the device knows, have nothing to do.  With
+// the chunk's two splits from k_tab_merge_splits the workgroup brings the chunk's window into LDS, and every lane finds the
+// split of its own MERGE_PER positions there and walks them by the pair rule.  PHASE 0: heads[b] = the chunk's heads (scanned by
+// k_tab_digit_scan); PHASE 1: head j of the whole goes to symbols[j] / counts[j] while j < cap, and the scalars over the counts
+// > 0 are added to the summary by integer atomics (k_tab_merge_head has written the rest of it).
+template <int PHASE>
+__global__ __launch_bounds__(ST) void k_tab_merge(const TabMergeIn in, const uint32_t *__restrict__ splits, uint32_t *__restrict__ heads,
+                                                  uint32_t *__restrict__ symbols, int32_t *__restrict__ counts, const uint64_t cap,
+                                                  GfTabSymbols *__restrict__ summary, const size_t nChunks)
+{
+    __shared__ uint32_t sym[MERGE_WIN];
+    __shared__ int32_t cnt[MERGE_WIN];
+    __shared__ uint32_t waveTot[ST / 64];
+    const size_t b = tabGroup();
+    if (b >= nChunks) return;                                                      // (the grid's padding; workgroup-uniform)
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nA = tabLenA(in), nB = tabLenB(in);
+    const uint64_t n = (uint64_t)nA + nB, d0 = (uint64_t)b * GF_TAB_MERGE_BLOCK;
+    if (d0 >= n) {                                                                 // (workgroup-uniform)
+        if (PHASE == 0 && tid == 0) heads[b] = 0;
+        return;
+    }
+    const uint64_t d1 = n - d0 < GF_TAB_MERGE_BLOCK ? n : d0 + GF_TAB_MERGE_BLOCK;
+    const GfTabMergeWindow w = gf_tab_merge_window(nA, nB, d0, splits[b], d1, splits[b + 1]);
+    const uint32_t lA = w.a1 - w.a0, lB = w.b1 - w.b0;                             // lA + lB <= MERGE_WIN
+    for (uint32_t i = tid; i < lA + lB; i += ST) {
+        const bool isA = i < lA;
+        sym[i] = isA ? in.symA[w.a0 + i] : in.symB[w.b0 + (i - lA)];
+        cnt[i] = isA ? in.cntA[w.a0 + i] : in.cntB[w.b0 + (i - lA)];
+    }
+    __syncthreads();
+    const uint32_t len = (uint32_t)(d1 - d0), at = tid * MERGE_PER;                // the lane's positions: [at, at + steps) of the chunk
+    const uint32_t steps = at >= len ? 0u : len - at < MERGE_PER ? len - at : MERGE_PER;
+    uint32_t ia = 0, ib = 0;
+    if (steps) {
+        ia = gf_tab_merge_split(sym, lA, sym + lA, lB, (uint64_t)w.pre + at);
+        ib = w.pre + at - ia;
+    }
+    uint32_t hs[MERGE_PER];
+    int32_t hc[MERGE_PER];
+    const uint32_t nHeads = gf_tab_merge_run(sym, cnt, lA, sym + lA, cnt + lA, lB, ia, ib, steps, [&](uint32_t k, uint32_t s, int32_t c) {
+#pragma unroll
+        for (uint32_t q = 0; q < MERGE_PER; q++)
+            if (q == k) hs[q] = s, hc[q] = c;
+    });
+    uint32_t all;
+    uint64_t j = tabBlockExclScan(nHeads, waveTot, all);
+    if constexpr (PHASE == 0) {
+        if (tid == 0) heads[b] = all;
+    } else {
+        j += heads[b];
+        uint32_t unique = 0, repeated = 0;
+        int32_t most = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < MERGE_PER; q++)
+            if (q < nHeads) {
+                if (j < cap) symbols[j] = hs[q], counts[j] = hc[q];
+                gf_tab_count_scalars(hc[q], unique, repeated, most);
+                j++;
+            }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            unique += __shfl_down(unique, off, 64), repeated += __shfl_down(repeated, off, 64);
+            const int32_t m = __shfl_down(most, off, 64);
+            most = m > most ? m : most;
+        }
+        if ((tid & 63) == 0) {
+            if (unique) atomicAdd((unsigned long long *)&summary->nUnique, (unsigned long long)unique);
+            if (repeated) atomicAdd((unsigned long long *)&summary->nRepeated, (unsigned long long)repeated);
+            if (most) atomicMax(&summary->maxCount, most);
+        }
+    }
+}
+
+// one lane, behind the scan of the heads: the summary but for the scalars that phase 1 adds up
+__global__ void k_tab_merge_head(const TabMergeIn in, const uint32_t *__restrict__ nSym, const uint64_t cap, GfTabSymbols *__restrict__ summary)
+{
+    // (a table that is empty for want of samples gives nothing, its flag included)
+    const GfTabSymbols *a = (in.noSamplesIsEmpty & 1u) && in.sumA && in.sumA->nSamples == 0 ? nullptr : in.sumA;
+    const GfTabSymbols *b = (in.noSamplesIsEmpty & 2u) && in.sumB && in.sumB->nSamples == 0 ? nullptr : in.sumB;
+    GfTabSymbols out;
+    gf_tab_merge_summary(out, a, tabLenA(in), b, tabLenB(in), *nSym, cap);
+    *summary = out;
+}
+
+// ---------------------------------------------------------------- the symbol form: a SHORT block by counters
+
+// k_tabulate_dense's scheme on the 65,536 values a SHORT cell can take: persistent workgroups, 16-byte loads of 8 cells, the cells in
+// front of the first 16-byte boundary and behind the last whole load one a lane (the block need only be 2-byte aligned).  The
+// counters of the window GF_TAB_SHORT_WIN_LO .. _HI are private to the workgroup in LDS and the non-zero ones are flushed once; a
+// cell outside the window is one global atomic.  counter: 65,536 words, zeroed by the launcher, indexed by gf_tab_short_slot.
+__global__ __launch_bounds__(GF_TAB_THREADS) void k_tab_short_counts(const int16_t *__restrict__ block, int32_t *__restrict__ counter, const int64_t nCells,
+                                                                     const int64_t head, const int64_t nVec)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t tabWin[];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < (uint32_t)GF_TAB_SHORT_WIN; i += GF_TAB_THREADS) tabWin[i] = 0;
+    __syncthreads();
+    auto count = [&](int16_t v) {
+        const uint32_t ws = gf_tab_short_win_slot(v);
+        if (ws < (uint32_t)GF_TAB_SHORT_WIN) atomicAdd(&tabWin[ws], 1u);
+        else atomicAdd(&counter[gf_tab_short_slot(v)], 1);
+    };
+    const int64_t gid = (int64_t)blockIdx.x * GF_TAB_THREADS + tid, stride = (int64_t)gridDim.x * GF_TAB_THREADS;
+    if (gid < head) count(block[gid]);
+    const uint4 *vec = reinterpret_cast<const uint4 *>(block + head);
+    for (int64_t v = gid; v < nVec; v += stride) {
+        const uint4 x = vec[v];
+#pragma unroll
+        for (int c = 0; c < 8; c++) count(tabCellOf<int16_t>(x, c));
+    }
+    const int64_t tail0 = head + nVec * 8;
+    if (gid < nCells - tail0) count(block[tail0 + gid]);
+    __syncthreads();
+    for (uint32_t i = tid; i < (uint32_t)GF_TAB_SHORT_WIN; i += GF_TAB_THREADS) {
+        const uint32_t c = tabWin[i];
+        if (c) atomicAdd(&counter[gf_tab_short_slot(gf_tab_short_of_win_slot(i))], (int32_t)c);
+    }
+}
+
+// one workgroup: the table of the 65,536 counters -- slot s is the symbol of (int16) s sign-extended, the slots' order is the symbols'
+// ascending unsigned order, counters equal to 0 are left out -- and its summary, whole.  A lane owns 64 slots behind one another.
+__global__ __launch_bounds__(GF_TAB_COMPACT_THREADS) void k_tab_short_compact(const int32_t *__restrict__ counter, const int64_t nSamples,
+                                                                              uint32_t *__restrict__ symbols, int32_t *__restrict__ counts, const uint64_t cap,
+                                                                              GfTabSymbols *__restrict__ summary)
+{
+    constexpr uint32_t WAVES = GF_TAB_COMPACT_THREADS / 64, PER = 65536 / GF_TAB_COMPACT_THREADS;
+    __shared__ uint32_t waveTot[WAVES], waveUnique[WAVES], waveRepeated[WAVES];
+    __shared__ int32_t waveMost[WAVES];
+    const uint32_t tid = threadIdx.x, s0 = tid * PER;
+    uint32_t mine = 0, unique = 0, repeated = 0;
+    int32_t most = 0;
+    for (uint32_t k = 0; k < PER; k++) {
+        const int32_t c = counter[s0 + k];
+        mine += c != 0;
+        gf_tab_count_scalars(c, unique, repeated, most);
+    }
+    const uint32_t incl = gf_wave_incl_scan(mine);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        unique += __shfl_down(unique, off, 64), repeated += __shfl_down(repeated, off, 64);
+        const int32_t m = __shfl_down(most, off, 64);
+        most = m > most ? m : most;
+    }
+    if ((tid & 63) == 63) waveTot[tid >> 6] = incl;
+    if ((tid & 63) == 0) waveUnique[tid >> 6] = unique, waveRepeated[tid >> 6] = repeated, waveMost[tid >> 6] = most;
+    __syncthreads();
+    uint64_t j = incl - mine;
+    uint32_t total = 0;
+    for (uint32_t w = 0; w < WAVES; w++) {
+        if (w < (tid >> 6)) j += waveTot[w];
+        total += waveTot[w];
+    }
+    for (uint32_t k = 0; k < PER; k++) {
+        const int32_t c = counter[s0 + k];
+        if (c == 0) continue;
+        if (j < cap) symbols[j] = gf_tab_symbol_i16((int16_t)(uint16_t)(s0 + k)), counts[j] = c;
+        j++;
+    }
+    if (tid != 0) return;
+    GfTabSymbols out;
+    out.nSamples = nSamples, out.nSymbols = total, out.nUnique = 0, out.nRepeated = 0, out.maxCount = 0, out.reserved = 0;
+    out.nWritten = total < cap ? total : (int64_t)cap;
+    for (uint32_t w = 0; w < WAVES; w++) {
+        out.nUnique += waveUnique[w], out.nRepeated += waveRepeated[w];
+        out.maxCount = waveMost[w] > out.maxCount ? waveMost[w] : out.maxCount;
+    }
+    *summary = out;
+}
+
 }  // namespace
 
 hipError_t gf_launch_tabulate_dense(const GfTabDenseArgs &a, hipStream_t stream)
@@ -508,6 +711,59 @@ hipError_t gf_launch_tab_symbols(const GfTabSymbolsArgs &a, hipStream_t stream)
     TAB_LAUNCHED();
     const size_t groups = ((size_t)a.n + ST - 1) / ST;
     hipLaunchKernelGGL(k_tab_run_counts, dim3((unsigned)(groups < 2048 ? groups : 2048)), dim3(ST), 0, stream, a.nSym, a.keysA, a.counts, (uint64_t)a.cap,
+                       a.summary);
+    return hipGetLastError();
+}
+
+size_t gf_tab_merge_chunks(uint32_t capA, uint32_t capB)
+{
+    const size_t n = ((size_t)capA + capB + GF_TAB_MERGE_BLOCK - 1) / GF_TAB_MERGE_BLOCK;
+    return n ? n : 1;
+}
+
+hipError_t gf_launch_tab_merge(const GfTabMergeArgs &a, hipStream_t stream)
+{
+    if (!a.splits || !a.heads || !a.sums || !a.nSym || !a.summary || (a.cap && (!a.symbols || !a.counts)) || a.capA > 0x7fffffffu || a.capB > 0x7fffffffu ||
+        (a.capA && (!a.symA || !a.cntA)) || (a.capB && (!a.symB || !a.cntB)))
+        return hipErrorInvalidValue;
+    TabMergeIn in{};
+    in.symA = a.symA, in.cntA = a.cntA, in.sumA = a.sumA, in.capA = a.sumA ? a.capA : 0u;
+    in.symB = a.symB, in.cntB = a.cntB, in.sumB = a.sumB, in.capB = a.sumB ? a.capB : 0u;
+    in.noSamplesIsEmpty = a.noSamplesIsEmpty;
+    const size_t nChunks = gf_tab_merge_chunks(in.capA, in.capB);
+    hipLaunchKernelGGL(k_tab_merge_splits, gf_tile_grid((nChunks + 1 + ST - 1) / ST), dim3(ST), 0, stream, in, a.splits, nChunks);
+    TAB_LAUNCHED();
+    hipLaunchKernelGGL(k_tab_merge<0>, gf_tile_grid(nChunks), dim3(ST), 0, stream, in, a.splits, a.heads, a.symbols, a.counts, (uint64_t)a.cap,
+                       a.summary, nChunks);
+    TAB_LAUNCHED();
+    const hipError_t e = tabScan(a.heads, nChunks, a.sums, a.nSym, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_tab_merge_head, dim3(1), dim3(1), 0, stream, in, a.nSym, (uint64_t)a.cap, a.summary);
+    TAB_LAUNCHED();
+    hipLaunchKernelGGL(k_tab_merge<1>, gf_tile_grid(nChunks), dim3(ST), 0, stream, in, a.splits, a.heads, a.symbols, a.counts, (uint64_t)a.cap,
+                       a.summary, nChunks);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_tab_short(const GfTabShortArgs &a, hipStream_t stream)
+{
+    if (!a.block || a.n < 1 || a.n > 0x7fffffffu || ((uintptr_t)a.block & 1) != 0 || !a.counter || !a.summary || (a.cap && (!a.symbols || !a.counts)))
+        return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(a.counter, 0, 65536 * sizeof(int32_t), stream);
+    if (e != hipSuccess) return e;
+    const int64_t nCells = a.n;
+    int64_t head = (int64_t)(((16u - ((uintptr_t)a.block & 15u)) & 15u) / 2u);
+    if (head > nCells) head = nCells;
+    const int64_t nVec = (nCells - head) / 8;
+    const int64_t lanes = nVec > 8 ? nVec : 8;                                     // (head and tail: fewer than 8 cells each)
+    int64_t groups = (lanes + GF_TAB_THREADS - 1) / GF_TAB_THREADS;
+    if (groups > GF_TAB_SHORT_MAX_GROUPS) groups = GF_TAB_SHORT_MAX_GROUPS;
+    constexpr size_t dyn = (size_t)GF_TAB_SHORT_WIN * 4;
+    static GfDynLdsOptIn optIn;
+    if ((e = gf_opt_in_dyn_lds(k_tab_short_counts, dyn, optIn)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_tab_short_counts, dim3((unsigned)groups), dim3(GF_TAB_THREADS), dyn, stream, (const int16_t *)a.block, a.counter, nCells, head, nVec);
+    TAB_LAUNCHED();
+    hipLaunchKernelGGL(k_tab_short_compact, dim3(1), dim3(GF_TAB_COMPACT_THREADS), 0, stream, a.counter, nCells, a.symbols, a.counts, (uint64_t)a.cap,
                        a.summary);
     return hipGetLastError();
 }

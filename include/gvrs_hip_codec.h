@@ -983,19 +983,54 @@ gf_status gf_block_read_downsampled_elems(gf_context *ctx, const int *codecs, in
  *   positive ones), each with its count.  n_samples = n_cells, n_symbols the distinct symbols, n_unique those with count 1, n_repeated
  *   the rest, max_count the largest count.  With n_symbols > table_cap the first table_cap entries are written, n_written = table_cap,
  *   the scalars are complete, and the host form returns GF_ERR_CAPACITY; table_cap == 0 with NULL tables asks for the scalars alone.
- *   n_cells > 2^31 - 1: GF_ERR_UNSUPPORTED (a count is a Java int).  There is no accumulate form.  The call grows a temporary of the
- *   context on demand (9 bytes per cell) and only enqueues; it is not claimed safe for hipGraph capture.
+ *   n_cells > 2^31 - 1 in one call: GF_ERR_UNSUPPORTED (a count is a Java int); a larger raster goes through in strips with the
+ *   accumulate form below.  The call grows a temporary of the context on demand (9 bytes per cell) and only enqueues; it is not
+ *   claimed safe for hipGraph capture.  It always writes reserved = 0, and a SHORT block takes the same sort as the others.
+ *   TABLES MERGED, STRIPS ACCUMULATED: a TABLE is what the symbol form writes -- n symbols in strictly ascending unsigned order, each
+ *   with an int32 count, and a gf_tab_symbols summary; its entries that count are the first min(n_written, cap), which the device
+ *   forms read on the device (the host passes upper bounds only, so they only enqueue and never synchronise).
+ *   gf_tab_symbols_merge_dev: the union of the symbols of tables A and B in ascending unsigned order; the count of a symbol that both
+ *   hold is the sum with INT32 WRAP, as the reference's counter, a Java int, wraps on count + 1 (EntropyTabulator.java:239-240) --
+ *   addition mod 2^32 is associative, so any split of a raster into strips gives the counts of the one loop.  An entry whose count
+ *   wrapped to <= 0 stays in the table (it records a symbol that was seen; gf_tab_entropy_counts skips it).  n_samples is the int64
+ *   sum of the inputs', n_symbols the entries of the result, and n_unique, n_repeated and max_count are taken over the entries with
+ *   count > 0 alone, as the reference's last loop does (:278-292; max_count is 0 where there is none).  THE ONE DEVIATION: the
+ *   reference's nSymbols counts a symbol once more when its counter comes back to 0 after 2^32 occurrences; n_symbols here is the
+ *   number of distinct symbols.  Capacity as above: with more entries than table_cap the first table_cap are written, n_written =
+ *   table_cap, the scalars are complete, and the host form returns GF_ERR_CAPACITY.  An input that does not hold all of its symbols
+ *   (fewer entries that count than its n_symbols) cannot give a complete result: the merge takes the entries it has and sets
+ *   GF_TAB_SYM_INPUT_TRUNCATED (bit 0) in the result's reserved field; an input that carries the bit hands it on, and the host
+ *   form returns GF_ERR_CAPACITY.  Inputs that are not strictly ascending give an unspecified table, but never a write outside
+ *   [0, table_cap) or a read outside the inputs' entries.  The output arrays and summary must not overlap one another or any input
+ *   (the caller keeps two tables and alternates); an input table of more than 2^31 - 1 entries is GF_ERR_UNSUPPORTED.
+ *   gf_block_tabulate_symbols_acc_dev: the symbol form of one strip of n_cells <= 2^31 - 1 cells into a table of the context (INT,
+ *   FLOAT: the sort above; SHORT: 65,536 counters, no widening and no sort), merged with the caller's in-table into the out table.
+ *   The total over the calls is unbounded (n_samples is an int64).  No in-table -- NULL arrays, a NULL summary, cap_in == 0 -- or one
+ *   whose summary has n_samples == 0 is empty; n_cells == 0 copies the in-table through.  GF_ELEM_ICF is refused as above.  A SHORT
+ *   block need only be 2-byte aligned here, so strips with odd cell counts follow one another in one array.  Temporary of the
+ *   context: 17 bytes per cell of the strip (SHORT: 768 KiB) and 8 bytes per 2,048 entries of the tables.
+ *   gf_block_read_tabulated_symbols_elems[_dev]: gf_block_read_elems[_dev] of one rectangle into a temporary of the context, then
+ *   the accumulate form for element `which`; a GF_ELEM_ICF element is taken as its INT codes, which is what the reference's
+ *   readValueInt delivers for it (EntropyTabulator.java:230-235).  d_status as the block read defines it: the table is good iff
+ *   every status is 0.
+ *   gf_tab_symbols_merge, gf_block_tabulate_symbols_acc: the same for host memory, staged through a buffer of the context; an input
+ *   goes up with the entries that count.  They synchronise.
+ *   THESE DEVICE FORMS TAKE NO `void *stream`: like the gf_image_* and gf_lsop08_* calls they enqueue on the context's own stream.
  *   gf_tab_entropy_counts (host only): bits per sample from counts in the order given, counts <= 0 skipped.  kahan = 1 is
  *   EntropyTabulator's sum: p = count / (double) n_samples, s = -p * log(p), added with KahanSummation.add as written, the sum divided
  *   by log(2.0).  kahan = 0 is InputDataStatCollector.getEntropy: sum += p * log(p), -sum / log(2.0), and 0 for n_samples == 0.
- *   ORDER: every tabulation call of a context uses the same scratch of that context (the dense form's partials; the symbol form's
- *   temporary, which a later, larger call frees and replaces).  The calls themselves are serialised by the context's lock, but what
+ *   ORDER: every tabulation call of a context uses the same scratch of that context (the dense form's partials; the temporary of
+ *   the symbol form, of the merge and of the accumulate form, which a later, larger call frees and replaces).  The calls themselves are serialised by the context's lock, but what
  *   they enqueue is not: tabulation calls on one context must all go to ONE stream, or the caller orders the streams (an event
  *   between them) so that no two are in flight at once.  Contexts are independent of one another.
  * GF_ERR_ARG, before the context or a device is looked at: a NULL ctx, block, spec, summary or counter array; NULL tables with
  * table_cap > 0; an element type outside 0..3; a SHORT fill_i outside int16; n_cells < 0 or first_cell < 0; a block, counter or table
  * pointer that is not 4-byte aligned, a summary pointer that is not 8-byte aligned; unknown flag bits; the plan's errors.  Then
- * GF_ERR_UNSUPPORTED as listed.                                                                                                  */
+ * GF_ERR_UNSUPPORTED as listed.  The merge and the accumulate form, in this order: a NULL ctx, block or summary (the merge: any of
+ * the three; the accumulate form: the out summary); an element type outside 0..3, n_cells < 0; a block that is not 4-byte (SHORT:
+ * 2-byte) aligned; an in-table with one array and not the other; an out table with table_cap > 0 and a NULL array, or misaligned;
+ * an input table with cap > 0 and a NULL array (the merge), or misaligned; outputs that overlap one another or an input: all
+ * GF_ERR_ARG.  Then GF_ERR_UNSUPPORTED: GF_ELEM_ICF, n_cells > 2^31 - 1, an input cap > 2^31 - 1.                                */
 typedef struct gf_tab_dense { int32_t def_min, def_max; double scale; } gf_tab_dense;
 typedef struct gf_tab_dense_plan { int32_t n_counter, base; int64_t n_bins; double scale_used; } gf_tab_dense_plan;
 typedef struct gf_tab_summary {          /* device memory, 8-byte aligned */
@@ -1018,6 +1053,31 @@ gf_status gf_block_tabulate_symbols_dev(gf_context *ctx, void *stream, int elem_
                                         uint32_t *d_symbols, int32_t *d_counts, size_t table_cap, gf_tab_symbols *d_summary);
 gf_status gf_block_tabulate_symbols(gf_context *ctx, int elem_type, const void *block, int64_t n_cells, uint32_t *symbols,
                                     int32_t *counts, size_t table_cap, gf_tab_symbols *summary);
+#define GF_TAB_SYM_INPUT_TRUNCATED 1      /* gf_tab_symbols.reserved, bit 0: an input of a merge did not hold all of its symbols */
+gf_status gf_tab_symbols_merge_dev(gf_context *ctx, const uint32_t *d_sym_a, const int32_t *d_cnt_a, const gf_tab_symbols *d_sum_a,
+                                   size_t cap_a, const uint32_t *d_sym_b, const int32_t *d_cnt_b, const gf_tab_symbols *d_sum_b,
+                                   size_t cap_b, uint32_t *d_sym_out, int32_t *d_cnt_out, size_t table_cap, gf_tab_symbols *d_sum_out);
+gf_status gf_tab_symbols_merge(gf_context *ctx, const uint32_t *sym_a, const int32_t *cnt_a, const gf_tab_symbols *sum_a, size_t cap_a,
+                               const uint32_t *sym_b, const int32_t *cnt_b, const gf_tab_symbols *sum_b, size_t cap_b,
+                               uint32_t *sym_out, int32_t *cnt_out, size_t table_cap, gf_tab_symbols *sum_out);
+gf_status gf_block_tabulate_symbols_acc_dev(gf_context *ctx, int elem_type, const void *d_block, int64_t n_cells,
+                                            const uint32_t *d_sym_in, const int32_t *d_cnt_in, const gf_tab_symbols *d_sum_in,
+                                            size_t cap_in, uint32_t *d_sym_out, int32_t *d_cnt_out, size_t cap_out,
+                                            gf_tab_symbols *d_sum_out);
+gf_status gf_block_tabulate_symbols_acc(gf_context *ctx, int elem_type, const void *block, int64_t n_cells, const uint32_t *sym_in,
+                                        const int32_t *cnt_in, const gf_tab_symbols *sum_in, size_t cap_in, uint32_t *sym_out,
+                                        int32_t *cnt_out, size_t cap_out, gf_tab_symbols *sum_out);
+gf_status gf_block_read_tabulated_symbols_elems_dev(gf_context *ctx, const int *codecs, int n_codecs, const gf_elem_spec *elems, int n_elems,
+                                                    const gf_grid_spec *grid, const gf_rect *rect, size_t n_records, const uint8_t *d_blob,
+                                                    size_t blob_bytes, const uint64_t *d_offsets, int verify_checksum, int which,
+                                                    const uint32_t *d_sym_in, const int32_t *d_cnt_in, const gf_tab_symbols *d_sum_in,
+                                                    size_t cap_in, uint32_t *d_sym_out, int32_t *d_cnt_out, size_t cap_out,
+                                                    gf_tab_symbols *d_sum_out, int32_t *d_status);
+gf_status gf_block_read_tabulated_symbols_elems(gf_context *ctx, const int *codecs, int n_codecs, const gf_elem_spec *elems, int n_elems,
+                                                const gf_grid_spec *grid, const gf_rect *rect, size_t n_records, const uint8_t *blob,
+                                                const uint64_t *offsets, int verify_checksum, int which, const uint32_t *sym_in,
+                                                const int32_t *cnt_in, const gf_tab_symbols *sum_in, size_t cap_in, uint32_t *sym_out,
+                                                int32_t *cnt_out, size_t cap_out, gf_tab_symbols *sum_out, int32_t *status);
 gf_status gf_tab_entropy_counts(const int32_t *counts, size_t n, int64_t n_samples, int kahan, double *entropy);
 
 /* ---- a grid block WRITTEN: raster in, tile records out, in device memory ------------------------------------------------------
