@@ -123,6 +123,15 @@ SIGNATURES = {
                                           _vp]),
     "gf_block_read_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_int, _vp, _vp]),
     "gf_block_tile_rect": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "gf_file_open": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
+    "gf_file_close": (None, [_vp]),
+    "gf_file_get_info": (C.c_int, [_vp, _vp]),
+    "gf_file_elem_name": (C.c_char_p, [_vp, C.c_int]),
+    "gf_file_codec_id": (C.c_char_p, [_vp, C.c_int]),
+    "gf_file_product_label": (C.c_char_p, [_vp]),
+    "gf_file_tile_position": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),
+    "gf_file_read_block_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp]),
+    "gf_file_read_block_elems": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp]),
     "gf_block_write_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_int,
                                            C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "gf_block_write_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp,

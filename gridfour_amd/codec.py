@@ -26,7 +26,8 @@ from ._lib import check, lib
 # ---- constants and struct dtypes (include/gvrs_hip_codec.h) ----
 INT4_NULL_CODE = -(2 ** 31)   # util/GridfourConstants.java:61
 
-CODEC_NONE, CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_CANON_HUFFMAN, CODEC_LSOP12 = 0, 1, 2, 3, 4
+CODEC_NONE, CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_CANON_HUFFMAN, CODEC_LSOP12, CODEC_LSOP08 = 0, 1, 2, 3, 4, 5
+CODEC_UNKNOWN = -1             # GF_CODEC_UNKNOWN: a file's codec id the library has no decoder for
 STANDARD_CODEC_LIST = (CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_NONE, CODEC_CANON_HUFFMAN)    # GvrsFileSpecification.java:221-230
 
 # What an element kind means, in one place.  type: its GF_ELEM_* number; delivered: the dtype a reader hands out; written: the dtype
@@ -45,6 +46,13 @@ _DELIVERED = {kind.type: kind.delivered for kind in _ELEM_KINDS.values()}
 _ELEM_SPEC = np.dtype([("type", np.int32), ("fill_i", np.int32), ("scale", np.float32), ("offset", np.float32),
                        ("fill_f", np.float32)])                                           # gf_elem_spec
 _ELEM_RANGE = np.dtype([("min_i", np.int32), ("max_i", np.int32), ("min_f", np.float32), ("max_f", np.float32)])   # gf_elem_range
+_FILE_INFO = np.dtype([("version", np.int32), ("subversion", np.int32), ("checksum_enabled", np.int32), ("raster_space", np.int32),
+                       ("coordinate_system", np.int32), ("grid", np.int32, 4), ("n_elems", np.int32), ("elems", _ELEM_SPEC, 16),
+                       ("n_codecs", np.int32), ("codecs", np.int32, 255), ("content_pos", np.uint64), ("tile_dir_pos", np.uint64),
+                       ("metadata_dir_pos", np.uint64), ("freespace_dir_pos", np.uint64), ("dir_extended", np.int32), ("dir_row0", np.int32),
+                       ("dir_col0", np.int32), ("dir_n_rows", np.int32), ("dir_n_cols", np.int32), ("dir_entries_pos", np.uint64),
+                       ("x0", np.float64), ("y0", np.float64), ("x1", np.float64), ("y1", np.float64), ("cell_size_x", np.float64),
+                       ("cell_size_y", np.float64), ("m2r", np.float64, 6), ("r2m", np.float64, 6)], align=True)         # gf_file_info
 
 IMAGE_RGB, IMAGE_YCOCG = 0, 1                                              # GF_IMAGE_*
 IMAGE_MODELS = {"rgb": IMAGE_RGB, "ycocg": IMAGE_YCOCG}
@@ -1796,3 +1804,90 @@ class CodecMasterHip:
         lengths = np.array([len(p) for p in packings], np.uint32)
         blob, offsets = _blob_of(packings)
         return self.packing_blob_dev(nRows, nCols, blob[:int(offsets[-1])], offsets[:-1], lengths)
+
+
+# ---- GVRS files ----
+class GvrsFileHip:
+    """org.gridfour.gvrs.GvrsFile(file, "r") with GvrsElement.readBlock for all elements: a version 1.04 file opened from its path
+    or its bytes (gf_file_open: the header record and the tile directory's prefix, parsed on the host), blocks read from the file
+    image by gf_file_read_block_elems[_dev].  .info is the gf_file_info as a dict, with the elements' names, the codec ids and the
+    product label; .elems are the elements as the record calls of CodecMasterHip take them."""
+
+    _ELEM_NAMES = {kind.type: name for name, kind in _ELEM_KINDS.items()}
+
+    def __init__(self, path_or_bytes):
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview, np.ndarray)):
+            self.image = np.frombuffer(bytes(path_or_bytes), np.uint8)
+        else:
+            self.image = np.fromfile(path_or_bytes, np.uint8)
+        self._h = C.c_void_p()
+        _call("gf_file_open", _ptr(self.image), self.image.size, C.byref(self._h))
+        raw = np.zeros(1, _FILE_INFO)
+        _call("gf_file_get_info", self._h, _ptr(raw))
+        raw = raw[0]
+        L = lib()
+        self.n_elems, self.grid = int(raw["n_elems"]), tuple(int(x) for x in raw["grid"])
+        self._dtypes = [_delivered_dtype(raw["elems"][e]["type"]) for e in range(self.n_elems)]
+        self.elems = []
+        for e in range(self.n_elems):
+            el = raw["elems"][e]
+            name = self._ELEM_NAMES[int(el["type"])]
+            self.elems.append(name if name != "icf" else ("icf", float(el["scale"]), float(el["offset"]), int(el["fill_i"]), float(el["fill_f"])))
+        self.info = {k: (raw[k].tolist() if raw[k].ndim else raw[k].item()) for k in _FILE_INFO.names if k not in ("elems", "codecs", "grid")}
+        self.info["grid"] = self.grid
+        self.info["elems"] = [{k: raw["elems"][e][k].item() for k in _ELEM_SPEC.names} for e in range(self.n_elems)]
+        self.info["codecs"] = [int(k) for k in raw["codecs"][:int(raw["n_codecs"])]]
+        self.info["elem_names"] = [L.gf_file_elem_name(self._h, e).decode() for e in range(self.n_elems)]
+        self.info["codec_ids"] = [L.gf_file_codec_id(self._h, k).decode() for k in range(int(raw["n_codecs"]))]
+        self.info["product_label"] = L.gf_file_product_label(self._h).decode()
+
+    def tile_position(self, tile_index, image=None):
+        """gf_file_tile_position: the file position of the tile's record content, 0 for a tile the file does not hold; raises
+        GvrsHipError where the directory's entry or the record head is refused.  image: other bytes than the file's own."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        pos = C.c_uint64()
+        _call("gf_file_tile_position", self._h, _ptr(image), image.size, int(tile_index), C.byref(pos))
+        return pos.value
+
+    def _read_args(self, rect, image):
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        grid, rect = _grid_rect(self.grid[2], self.grid[3], self.grid[:2], rect)
+        nt = _tiles_of_rect(grid, rect)
+        return image, rect, nt, (int(rect[2]), int(rect[3]))
+
+    def read_block_dev(self, ctx, rect, verify_checksums=True, image=None):
+        """gf_file_read_block_elems_dev: rect = (row0, col0, n_rows, n_cols) of the grid read from the file image in device memory
+        (uploaded here; image: other bytes than the file's own, for a file that changed behind its header).  Returns ([block
+        [n_rows, n_cols] per element], status [n_elems, T], present [T]) over the T tiles the rectangle touches."""
+        image, rect, nt, shape = self._read_args(rect, image)
+        n_block = shape[0] * shape[1]
+        with _DeviceScope(ctx) as s:
+            d_image = s.upload(image, slack=32, fill=0)
+            d_blk = [s.alloc(n_block * np.dtype(dt).itemsize + 16, fill=0) for dt in self._dtypes]
+            d_st = s.alloc(self.n_elems * nt * 4 + 16, fill=0x7f)
+            d_pr = s.alloc(nt + 16, fill=0x7f)
+            s.run("gf_file_read_block_elems_dev", ctx.handle, self._h, d_image.ptr, image.size, _ptr(rect), int(bool(verify_checksums)),
+                  s.ptrs(d_blk), d_st.ptr, d_pr.ptr)
+            return ([b.download(dt, n_block).reshape(shape) for b, dt in zip(d_blk, self._dtypes)],
+                    d_st.download(np.int32, self.n_elems * nt).reshape(self.n_elems, nt), d_pr.download(np.uint8, nt))
+
+    def read_block(self, ctx, rect, verify_checksums=True, image=None):
+        """The same through gf_file_read_block_elems, the host-memory form: only the records of the rectangle's tiles are staged."""
+        image, rect, nt, shape = self._read_args(rect, image)
+        out = [np.zeros(shape, dt) for dt in self._dtypes]
+        status = np.full((self.n_elems, nt), 0x7f7f7f7f, np.int32)
+        present = np.full(nt, 0x7f, np.uint8)
+        _call("gf_file_read_block_elems", ctx.handle, self._h, _ptr(image), image.size, _ptr(rect), int(bool(verify_checksums)), _ptrs(out),
+              _ptr(status), _ptr(present))
+        return out, status, present
+
+    def close(self):
+        if self._h:
+            lib().gf_file_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -89,10 +89,12 @@ gf_status blockReadArgs(const gf_context *c, const int *codecs, int nCodecs, con
     return firstOf(sg, sa);
 }
 
-// records in device memory -> one block per element in device memory (the caller holds the lock and has checked the arguments)
+// records in device memory -> one block per element in device memory (the caller holds the lock and has checked the arguments).
+// dEnds, dVerdict (both null, or both given: a file image, gvrs_api_file.hip): record t = [dOffsets[t], dEnds[t]), and behind the
+// records' pipeline k_file_status puts the verdict of every slot that was not located into the statuses.
 gf_status blockReadDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
                        const uint32_t *fill, size_t n, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets, int verifyChecksum,
-                       void *const *dBlocks, int32_t *dStatus)
+                       void *const *dBlocks, int32_t *dStatus, const uint64_t *dEnds, const int32_t *dVerdict)
 {
     GF_HIP(hipSetDevice(c->device));
     const hipStream_t st = streamOf(c, stream);
@@ -119,8 +121,9 @@ gf_status blockReadDev(gf_context *c, void *stream, const int *codecs, int nCode
     if (n) {
         GF_HIP(hipMemsetAsync(dIndices, 0xff, n * 4, st));                      // (the driver leaves a failed record's entry alone: -1 places nothing)
         s = recordsDecodeDev(c, stream, codecs, nCodecs, elems, nElems, g.nRowsTile, g.nColsTile, n, dBlob, blobBytes, dOffsets, nullptr,
-                             verifyChecksum, dIndices, dValues, dStatus);
+                             verifyChecksum, dIndices, dValues, dStatus, dEnds);
         if (s != GF_OK) return s;
+        if (dVerdict) GF_HIP(gf_launch_file_status(dVerdict, dStatus, n, nElems, st));
     }
     if ((s = gatherDev(c, st, g, n, dIndices, dElems, table[0], nElems)) != GF_OK) return s;
     if (!n) GF_HIP(hipStreamSynchronize(st));                                    // (the call's one synchronisation, which the driver did not make)

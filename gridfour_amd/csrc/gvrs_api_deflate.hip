@@ -239,19 +239,20 @@ gf_status codecMasterDecodeScattered(gf_context *c, const int *codecs, int nCode
             i++;
         }
         gf_status s = GF_OK;
-        int kind = -1;                                    // of the batch decoders' shared plumbing; LSOP12 has none
+        int kind = -1;                                    // of the batch decoders' shared plumbing; the LSOP codecs have none
         switch (codecs[k]) {
         case GF_CODEC_HUFFMAN: kind = KIND_HUFFMAN; break;
         case GF_CODEC_DEFLATE: kind = KIND_DEFLATE; break;
         case GF_CODEC_CANON_HUFFMAN: kind = KIND_CANON; break;
-        case GF_CODEC_LSOP12: {
-            // (LSOP12's host path has stages of its own: its packings are gathered into one blob first, in parallel)
+        case GF_CODEC_LSOP12:
+        case GF_CODEC_LSOP08: {
+            // (the LSOP host paths have stages of their own: the packings are gathered into one blob first, in parallel)
             std::vector<uint64_t> off(i + 1, 0);
             for (size_t j = 0; j < i; j++) off[j + 1] = off[j] + kl[j];
             std::vector<uint8_t> sub((size_t)off[i] + 16);
             parallelFor(i, [&](size_t j) { memcpy(sub.data() + off[j], blob + ks[j], kl[j]); });
             std::vector<int32_t> out(i * cells), sst(i);
-            s = gf_lsop12_decode_batch_i32(c, nRows, nCols, i, sub.data(), off.data(), out.data(), sst.data());
+            s = (codecs[k] == GF_CODEC_LSOP12 ? gf_lsop12_decode_batch_i32 : gf_lsop08_decode_batch_i32)(c, nRows, nCols, i, sub.data(), off.data(), out.data(), sst.data());
             if (s != GF_OK) return s;
             parallelFor(i, [&](size_t j) {
                 st[kd[j]] = sst[j];
@@ -354,7 +355,7 @@ gf_status gf_codec_master_encode_batch_i32(gf_context *c, const int *codecs, int
     if (!c || !codecs || nCodecs < 1 || nCodecs > 255 || !values || !offsets || (!blob && blobCap)) return GF_ERR_ARG;
     const size_t cells = (size_t)nRows * (size_t)nCols;
     for (int k = 0; k < nCodecs; k++)
-        if (codecs[k] < GF_CODEC_NONE || codecs[k] > GF_CODEC_LSOP12) return GF_ERR_ARG;
+        if (codecs[k] < GF_CODEC_NONE || codecs[k] > GF_CODEC_LSOP08) return GF_ERR_ARG;
     // per codec of the list: its packings (Deflate: one vector per tile; the others: one blob + offsets) and statuses
     struct Entry {
         std::unique_ptr<uint8_t[]> blob;
@@ -397,6 +398,7 @@ gf_status gf_codec_master_encode_batch_i32(gf_context *c, const int *codecs, int
                     switch (kind) {
                     case GF_CODEC_HUFFMAN: s = gf_huffman_encode_batch_i32(c, k, nRows, nCols, nTiles, values, x.blob.get(), cap, x.off.data(), nullptr, x.st.data()); break;
                     case GF_CODEC_CANON_HUFFMAN: s = gf_canon_encode_batch_i32(c, k, nRows, nCols, nTiles, values, x.blob.get(), cap, x.off.data(), nullptr, x.st.data()); break;
+                    case GF_CODEC_LSOP08: s = gf_lsop08_encode_batch_i32(c, k, nRows, nCols, nTiles, values, x.blob.get(), cap, x.off.data(), nullptr, x.st.data()); break;
                     default: s = gf_lsop12_encode_batch_i32(c, k, nRows, nCols, nTiles, values, 1, x.blob.get(), cap, x.off.data(), nullptr, x.st.data()); break;
                     }
                     if (s != GF_ERR_CAPACITY) break;

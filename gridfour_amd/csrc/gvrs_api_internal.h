@@ -25,6 +25,7 @@
 #include "gvrs_encode_layout.h"
 #include "gvrs_carve.h"
 #include "gvrs_lsop_container.h"
+#include "gvrs_file_parse.h"
 #include "gvrs_stage.h"
 
 #pragma GCC visibility push(hidden)
@@ -152,6 +153,7 @@ struct gf_context {
     DevBuf dImage{this};                        // images (gvrs_api_image.hip): the record forms' three planes
     DevBuf dTabPartials{this}, dTabSort{this};  // tabulation (gvrs_api_tabulate.hip): k_tabulate_dense's partials (fixed size); the symbol form's
                                                 // keys, histograms and runs, a strip's table and the merge's chunk counts
+    DevBuf dFileLoc{this};                      // file images (gvrs_api_file.hip): the extents and verdicts of the rectangle's tiles
     DevBuf dTabBlocks{this};                    // ... the composed read's blocks (gf_block_read_tabulated_symbols_elems[_dev])
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
     // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
@@ -296,7 +298,8 @@ inline gf_status elemArrays(DevBuf &b, const gf_elem_spec *elems, int nElems, si
 }
 gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
                            int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets,
-                           const uint32_t *dLengths, int verifyChecksum, int32_t *dTileIndices, void *const *dValues, int32_t *dStatus);
+                           const uint32_t *dLengths, int verifyChecksum, int32_t *dTileIndices, void *const *dValues, int32_t *dStatus,
+                           const uint64_t *dEnds = nullptr);
 // gvrs_api_records_enc.hip: the argument checks of the record writer, "this list needs nothing from the host", the one device
 // pipeline (dPreStatus, may be null: per tile a non-zero status that replaces the record) and the host encoders' path
 gf_status encArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows, int nCols,
@@ -321,7 +324,7 @@ gf_status blockReadArgs(const gf_context *c, const int *codecs, int nCodecs, con
                         void *const *blocks, const int32_t *status, GfBlockGeom &g, uint32_t *fill);
 gf_status blockReadDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
                        const uint32_t *fill, size_t n, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets, int verifyChecksum,
-                       void *const *dBlocks, int32_t *dStatus);
+                       void *const *dBlocks, int32_t *dStatus, const uint64_t *dEnds = nullptr, const int32_t *dVerdict = nullptr);
 // gvrs_api_blocks_write.hip: a block write's argument checks (fills g and the cut's element descriptions), and blocks in device
 // memory -> records in device memory (no lock taken, no argument checked)
 gf_status blockWriteArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_elem_spec *elems, const gf_elem_range *ranges, int nElems,
@@ -336,6 +339,10 @@ gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCod
 gf_status interpSpecArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, GfInterpGeom &g);
 // gvrs_api_records.hip
 size_t elemStandardSize(int elemType, size_t cells);
+// gvrs_api_lsop.hip: gf_lsop08_decode_batch_i32_dev on a stream (the public form runs on the context's own)
+gf_status lsop08DecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
+                          const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues, int32_t *dStatus,
+                          int32_t *dResiduals, size_t resStride, uint32_t *dCoefs, int32_t *dScratchStatus);
 // gvrs_api_deflate.hip
 gf_status deflateDecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
                            const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues, int32_t *dStatus);

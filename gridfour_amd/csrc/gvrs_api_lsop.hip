@@ -439,11 +439,21 @@ gf_status gf_lsop08_decode_batch_i32_dev(gf_context *c, int nRows, int nCols, si
                                          const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues,
                                          int32_t *dStatus, int32_t *dResiduals, size_t resStride, uint32_t *dCoefs, int32_t *dScratchStatus)
 {
+    return lsop08DecodeDev(c, c ? c->stream : nullptr, nRows, nCols, nTiles, dBlob, blobBytes, dOffsets, slotStride, dLengths, dValues, dStatus,
+                           dResiduals, resStride, dCoefs, dScratchStatus);
+}
+
+}  // extern "C"
+
+// ... on a stream: the records' driver runs a list's LSOP08 entry on its caller's (gvrs_api_records_dev.hip)
+gf_status lsop08DecodeDev(gf_context *c, hipStream_t st, int nRows, int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes,
+                          const uint64_t *dOffsets, size_t slotStride, const uint32_t *dLengths, int32_t *dValues, int32_t *dStatus,
+                          int32_t *dResiduals, size_t resStride, uint32_t *dCoefs, int32_t *dScratchStatus)
+{
     GF_CTX_LOCK(c);
     if (!c || !dBlob || !dLengths || !dValues || !dStatus || !dResiduals || !dCoefs || !dScratchStatus || nRows < 1 || nCols < 1) return GF_ERR_ARG;
     GF_HIP(hipSetDevice(c->device));
     if (((uintptr_t)dBlob & 3) != 0) return GF_ERR_ARG;
-    const hipStream_t st = c->stream;
     if (GF_LSOP08.tooSmall(nRows, nCols)) {
         if (nTiles) GF_HIP(hipMemsetD32Async((hipDeviceptr_t)dStatus, GF_ERR_BOUNDS, nTiles, st));
         return GF_OK;
@@ -461,6 +471,8 @@ gf_status gf_lsop08_decode_batch_i32_dev(gf_context *c, int nRows, int nCols, si
     GF_HIP(gf_launch_lsop8_reconstruct(dResiduals, resStride, dCoefs, dScratchStatus, dValues, dStatus, nTiles, nRows, nCols, st));
     return GF_OK;
 }
+
+extern "C" {
 
 // LsEncoder08.encode for a batch in host memory: the Huffman container (type 0) comes from the GPU and is kept only where its body is
 // STRICTLY shorter than the two zlib streams (:118); otherwise the packing is the Deflate one (type 1).  types[t] (may be null) =

@@ -31,6 +31,15 @@ gf_status decodeSublist(gf_context *c, hipStream_t st, int codec, int nRows, int
         return gf_lsop12_decode_batch_i32_dev(c, st, nRows, nCols, n, dBlob, blobBytes, offsets, 0, lengths, values, status,
                                               (int32_t *)c->dResiduals.p, resStride, (uint32_t *)c->dCoefs.p, (int32_t *)c->dStatus2.p);
     }
+    case GF_CODEC_LSOP08: {
+        const size_t resStride = roundUp(GF_LSOP08.residualCount(nRows, nCols), 4);
+        gf_status s;
+        if ((s = c->dResiduals.ensure(n * resStride * 4 + 16)) != GF_OK) return s;
+        if ((s = c->dCoefs.ensure(n * 64 + 16)) != GF_OK) return s;
+        if ((s = c->dStatus2.ensure(n * 4 + 16)) != GF_OK) return s;
+        return lsop08DecodeDev(c, st, nRows, nCols, n, dBlob, blobBytes, offsets, 0, lengths, values, status, (int32_t *)c->dResiduals.p,
+                               resStride, (uint32_t *)c->dCoefs.p, (int32_t *)c->dStatus2.p);
+    }
     default: return GF_ERR_ARG;
     }
 }
@@ -51,18 +60,20 @@ gf_status elemsArgs(const gf_context *c, const int *codecs, int nCodecs, const g
         if (elems[e].type == GF_ELEM_ICF && (elems[e].scale == 0.0f || std::isnan(elems[e].scale))) return GF_ERR_ARG;
     }
     for (int k = 0; k < nCodecs; k++)
-        if (codecs[k] < GF_CODEC_NONE || codecs[k] > GF_CODEC_LSOP12) return GF_ERR_ARG;
+        if (codecs[k] < GF_CODEC_NONE || codecs[k] > GF_CODEC_LSOP08) return GF_ERR_ARG;
     if (nTiles > 0x7fffffffull / (size_t)nElems) return GF_ERR_UNSUPPORTED;         // instance numbers travel as 32 bits
     return GF_OK;
 }
 
 size_t elemItemBytes(int type) { return type == GF_ELEM_SHORT ? 2 : 4; }
 
-// the one device pipeline.  dLengths == nullptr: tile records, record t = [dOffsets[t], dOffsets[t + 1]).  Else packing mode: one INT
-// element, packing t = dLengths[t] bytes at dOffsets[t], no framing, no standard form, no checksum, no tile index.
+// the one device pipeline.  dLengths == nullptr: tile records, record t = [dOffsets[t], dOffsets[t + 1]), or [dOffsets[t], dEnds[t])
+// where dEnds is given (records anywhere in a file image: gvrs_api_file.hip).  Else packing mode: one INT element, packing t =
+// dLengths[t] bytes at dOffsets[t], no framing, no standard form, no checksum, no tile index.
 gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, int nRows,
                            int nCols, size_t nTiles, const uint8_t *dBlob, size_t blobBytes, const uint64_t *dOffsets,
-                           const uint32_t *dLengths, int verifyChecksum, int32_t *dTileIndices, void *const *dValues, int32_t *dStatus)
+                           const uint32_t *dLengths, int verifyChecksum, int32_t *dTileIndices, void *const *dValues, int32_t *dStatus,
+                           const uint64_t *dEnds)
 {
     if (nCodecs < 0) nCodecs = 0;
     const size_t cells = (size_t)nRows * (size_t)nCols, n = nTiles, nInst = (size_t)nElems * n;
@@ -107,6 +118,7 @@ gf_status recordsDecodeDev(gf_context *c, void *stream, const int *codecs, int n
     p.blob = dBlob;
     p.blobBytes = blobBytes;
     p.offsets = dOffsets;
+    p.ends = dLengths ? nullptr : dEnds;
     p.lengths = dLengths;
     p.nTiles = n;
     p.nElems = nElems;

@@ -28,7 +28,7 @@ gf_status encArgs(const gf_context *c, const int *codecs, int nCodecs, const gf_
         if (onDevice && ((uintptr_t)values[e] & 3) != 0) return GF_ERR_ARG;
     }
     for (int k = 0; k < nCodecs; k++)
-        if (codecs[k] < GF_CODEC_NONE || codecs[k] > GF_CODEC_LSOP12) return GF_ERR_ARG;
+        if (codecs[k] < GF_CODEC_NONE || codecs[k] > GF_CODEC_LSOP08) return GF_ERR_ARG;
     if (nTiles > 0x7fffffffull / (size_t)nElems) return GF_ERR_UNSUPPORTED;         // instance numbers travel as 32 bits
     if ((size_t)nRows * (size_t)nCols >= (1ull << 28)) return GF_ERR_UNSUPPORTED;
     if (gf_tile_record_max_bytes_elems(elems, nElems, nRows, nCols) > 0x7fffffffull) return GF_ERR_UNSUPPORTED;   // the size field is an int32
@@ -42,7 +42,7 @@ bool deviceList(const int *codecs, int nCodecs, const gf_elem_spec *elems, int n
     bool anyFloat = false;
     for (int e = 0; e < nElems; e++) anyFloat |= elems[e].type == GF_ELEM_FLOAT;
     for (int k = 0; k < nCodecs; k++) {
-        if (codecs[k] == GF_CODEC_DEFLATE || codecs[k] == GF_CODEC_LSOP12) return false;
+        if (codecs[k] == GF_CODEC_DEFLATE || codecs[k] == GF_CODEC_LSOP12 || codecs[k] == GF_CODEC_LSOP08) return false;
         if (codecs[k] == GF_CODEC_NONE && anyFloat) return false;
     }
     return true;

@@ -468,6 +468,8 @@ struct GfRecordParseElemsArgs {
     const uint8_t *blob;       // 4-byte aligned
     size_t blobBytes;
     const uint64_t *offsets;   // records: nTiles + 1 entries, record t = [offsets[t], offsets[t + 1]); packings: nTiles entries
+    const uint64_t *ends;      // records only, may be null; else nTiles entries and record t = [offsets[t], ends[t]): records that lie
+                               // anywhere in the blob (a file image), offsets[nTiles] is not read
     const uint32_t *lengths;   // null: tile records with their framing; else packing t = lengths[t] bytes at offsets[t]: no head, no
                                // standard form, no tile index, one INT element
     size_t nTiles;
@@ -560,6 +562,29 @@ struct GfGridCutArgs {
     GfBlockGeom g;
 };
 hipError_t gf_launch_grid_cut(const GfGridCutArgs &a, hipStream_t stream);
+
+// A file image (gvrs_file.hip; driven by gvrs_api_file.hip): the tile directory read in place for the tiles of a block's rectangle of
+// tiles (k_file_locate), and the verdicts put into the statuses behind the records' pipeline (k_file_status).  Slot j = the j-th
+// tile of the rectangle of tiles, row-major.  A slot's verdict: GF_K_OK for a tile the file does not hold (the directory's entry
+// is 0 or the tile lies outside the directory's rectangle), GF_K_ERR_BOUNDS / GF_K_ERR_FORMAT for an entry that is refused -- all
+// three with the empty extent [0, 0), which the framing walk refuses without reading anything -- or
+constexpr int32_t GF_FILE_LOCATED = 1;       // the record's extent is emitted: the pipeline's own statuses stand
+struct GfFileLocateArgs {
+    const uint8_t *image;      // 8-byte aligned
+    uint64_t imageBytes;
+    uint64_t entriesPos;       // the directory's first entry: a multiple of 8
+    uint64_t contentPos;       // where the records begin
+    int32_t extended;          // entries: int64 positions; else unsigned int32, position = entry * 8
+    int32_t dirRow0, dirCol0, dirNRows, dirNCols;       // the directory's rectangle of tiles
+    int32_t nColsOfTiles;
+    int32_t tileRow0, tileCol0, nTileRows, nTileCols;   // the block's rectangle of tiles: nTileRows * nTileCols <= 0x7fffffff slots
+    uint64_t *starts, *ends;   // per slot: the record's extent [position - 8, min(imageBytes, position - 8 + size))
+    int32_t *verdict;          // per slot
+    uint8_t *present;          // may be null; per slot: 1 where the directory's entry is not 0
+};
+hipError_t gf_launch_file_locate(const GfFileLocateArgs &a, hipStream_t stream);
+// status[e * nSlots + j] = verdict[j] wherever that is not GF_FILE_LOCATED
+hipError_t gf_launch_file_status(const int32_t *verdict, int32_t *status, size_t nSlots, int nElems, hipStream_t stream);
 
 // A block WRITTEN (gvrs_blocks_write.hip; driven by gvrs_api_blocks_write.hip): the rectangle's cells of every element cut into the
 // tiles of the rectangle of tiles in the type the record writer takes (k_block_cut_elems: TileElement*.setValue with its range

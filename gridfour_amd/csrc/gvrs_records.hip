@@ -36,7 +36,8 @@ __device__ __forceinline__ int32_t rec_packing_class(const GfRecordParseElemsArg
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_record_parse_elems: a lane per record.  Record mode (a.lengths == nullptr): record t is blob[offsets[t] .. offsets[t + 1]); the
+// k_record_parse_elems: a lane per record.  Record mode (a.lengths == nullptr): record t is blob[offsets[t] .. offsets[t + 1]), or
+// blob[offsets[t] .. ends[t]) where a list of ends is given (records that lie anywhere in a file image, gvrs_api_file.hip); the
 // framing rules of gf_tile_record_decode_batch in its order.  A record's first 20 bytes (the 16-byte head and the first byte of
 // element 0, which names the codec of a packing) are fetched in one go -- every record that reaches them spans 20 bytes -- so
 // that the checks behind them wait for memory once; a head that fails gives every element that status.  Then the short serial
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void k_record_parse_elems(const GfRecordParseE
         a.sizes[t] = 0u;
         return;
     }
-    const uint64_t o0 = a.offsets[t], o1 = a.offsets[t + 1];
+    const uint64_t o0 = a.offsets[t], o1 = a.ends ? a.ends[t] : a.offsets[t + 1];
     int32_t headSt = GF_K_OK;
     uint32_t size = 0, h3 = 0, h4 = 0;
     if (o0 > o1 || o1 > a.blobBytes || o1 - o0 < 20u) headSt = GF_K_ERR_BOUNDS;          // (nothing of such a record is read)

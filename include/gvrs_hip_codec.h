@@ -445,6 +445,7 @@ gf_status gf_lsop08_decode_i32(gf_context *ctx, int n_rows, int n_cols, const ui
 #define GF_CODEC_DEFLATE 2
 #define GF_CODEC_CANON_HUFFMAN 3
 #define GF_CODEC_LSOP12 4
+#define GF_CODEC_LSOP08 5   /* in a list: decoded by every call that takes one; encoded by the host forms */
 gf_status gf_codec_master_encode_batch_i32(gf_context *ctx, const int *codecs, int n_codecs, int n_rows, int n_cols,
                                            size_t n_tiles, const int32_t *values, uint8_t *blob, size_t blob_cap,
                                            uint64_t *offsets, uint8_t *codec_used, int32_t *status);
@@ -571,7 +572,7 @@ gf_status gf_tile_record_decode_batch(gf_context *ctx, const int *codecs, int n_
  * offsets array cannot fail the call as a whole -- a record with d_offsets[t] > d_offsets[t+1] or d_offsets[t+1] > blob_bytes,
  * or a packing with d_offsets[t] + d_lengths[t] > blob_bytes, gets GF_ERR_BOUNDS and nothing of it is read.
  * GF_ERR_ARG, before the device is touched: null pointers, another elem_type, n_rows < 1 or n_cols < 1, a codec kind outside
- * GF_CODEC_NONE .. GF_CODEC_LSOP12, n_codecs > 255 (and, for the codec-master form, n_codecs < 1).  n_tiles == 0 is GF_OK.
+ * GF_CODEC_NONE .. GF_CODEC_LSOP08, n_codecs > 255 (and, for the codec-master form, n_codecs < 1).  n_tiles == 0 is GF_OK.
  * NOT capture-safe, unlike the other _dev entry points: the host must learn how many tiles each codec has before it can launch
  * the decoders, so these calls SYNCHRONISE `stream` ONCE (a copy of the per-codec counts into page-locked memory) and grow
  * context-owned buffers on demand (the per-record tables; a temporary for the decoded tiles of a batch that mixes codecs,
@@ -610,7 +611,7 @@ gf_status gf_tile_record_decode_batch_dev(gf_context *ctx, void *stream, const i
  * STATUSES ARE GF_OK.  With n_elems == 1 and type INT or SHORT the call answers exactly as gf_tile_record_decode_batch_dev.
  * GF_ERR_ARG, before the device is touched: null pointers (ctx, codecs with n_codecs > 0, elems, d_blob, d_offsets, d_values or
  * one of its entries, d_status), n_elems < 1 or > GF_MAX_ELEMS, a type outside 0..3, an ICF scale that is 0 or NaN, a codec kind
- * outside GF_CODEC_NONE .. GF_CODEC_LSOP12, n_codecs > 255, n_rows < 1, n_cols < 1, an unaligned d_blob.  GF_ERR_UNSUPPORTED:
+ * outside GF_CODEC_NONE .. GF_CODEC_LSOP08, n_codecs > 255, n_rows < 1, n_cols < 1, an unaligned d_blob.  GF_ERR_UNSUPPORTED:
  * n_elems * n_tiles > 0x7fffffff.  n_tiles == 0 is GF_OK.
  * gf_tile_record_decode_batch_elems is the same call for bytes in host memory (values[e], tile_indices, status: host arrays;
  * offsets[n_tiles] bytes of blob are read): it stages blob and offsets into buffers of the context, calls the device form on
@@ -661,12 +662,12 @@ gf_status gf_tile_record_decode_batch_elems(gf_context *ctx, const int *codecs, 
  *   the caller; no byte at or behind blob_cap is written, and every byte of a written record is written exactly once per call.
  * The device form takes lists of GF_CODEC_HUFFMAN and GF_CODEC_CANON_HUFFMAN entries, and GF_CODEC_NONE entries as long as no
  * element is FLOAT; n_codecs == 0 is "compression disabled": everything in standard form.  GF_ERR_UNSUPPORTED, from the arguments
- * alone: a list with GF_CODEC_DEFLATE or GF_CODEC_LSOP12 (its reference default carries a Deflate alternative), a GF_CODEC_NONE
+ * alone: a list with GF_CODEC_DEFLATE, GF_CODEC_LSOP12 or GF_CODEC_LSOP08 (their containers' choice needs zlib), a GF_CODEC_NONE
  * entry together with a FLOAT element (CodecFloat's zlib streams); and for both forms n_elems * n_tiles > 0x7fffffff, 2^28 or more
  * cells in a tile, a record that could exceed 0x7fffffff bytes (gf_tile_record_max_bytes_elems).
  * GF_ERR_ARG, before the device is touched: null pointers (ctx, codecs with n_codecs > 0, elems, tile indices, d_values or one of
  * its entries, d_blob, d_offsets, d_status), n_elems < 1 or > GF_MAX_ELEMS, a type outside 0..3, an ICF scale that is 0 or NaN, a
- * SHORT fill_i outside int16, a codec kind outside GF_CODEC_NONE .. GF_CODEC_LSOP12, n_codecs > 255, n_rows < 1, n_cols < 1, a
+ * SHORT fill_i outside int16, a codec kind outside GF_CODEC_NONE .. GF_CODEC_LSOP08, n_codecs > 255, n_rows < 1, n_cols < 1, a
  * d_blob that is not 8-byte or a d_values[e] that is not 4-byte aligned.  n_tiles == 0 is GF_OK.
  * The device form ONLY ENQUEUES on `stream` and never synchronises it: every codec runs on every tile and the layout is a scan, so
  * nothing has to come back to the host.  It grows buffers of the context on demand (candidate slots, their lengths and statuses,
@@ -1268,6 +1269,77 @@ gf_status gf_synth_dem_masked_dev(gf_context *ctx, void *stream, uint64_t seed, 
 gf_status gf_synth_dem_style_dev(gf_context *ctx, void *stream, uint64_t seed, int n_rows, int n_cols,
                                  int64_t tiles_per_row, int64_t tile0, size_t n_tiles, int mask_per_mille, int style,
                                  int32_t *d_values);
+
+/* ---- GVRS files: the header record, the tile directory and block reads from a file image ------------------------------------
+ * (gvrs/GvrsFile.java:341-483 the constructor GvrsFile(File, "r"), gvrs/GvrsFileSpecification.java:856-1052, 1154-1160,
+ * gvrs/RecordManager.java:835-856 readTileDirectory, gvrs/TileDirectory.java:200-257, gvrs/TileDirectoryExtended.java,
+ * gvrs/GvrsElement.java:298-404 readBlock)
+ * A file IMAGE is the bytes of a .gvrs file, as read or mapped.  gf_file_open parses the header record -- the specification of
+ * grid, tiles, elements and codec list -- and the 24-byte prefix of the tile directory; the block reads then need nothing from
+ * the caller but the image and a rectangle.  Version 1.04 files; everything little-endian.
+ *   gf_file_open needs no device and no context (host arithmetic on bytes, not a compute entry point).  It reads only the header
+ *   record and the directory's prefix and never a byte at or behind image_bytes.  The handle keeps copies and holds no pointer into
+ *   the image: the image may be an mmap and may go away after the call.  GF_ERR_FORMAT: a wrong magic, a version the reference
+ *   rejects, a number of levels other than 1, a non-zero opened-for-writing time, an element type code outside 0..3, a header
+ *   checksum mismatch where the specification enables checksums (and a non-zero checksum word where it does not: the writer leaves
+ *   0 there, and a damaged flag byte must not switch the check off), a header record too small for its fields or a field that runs
+ *   past the header record, tile or grid sizes < 1, a tile-directory position that is 0, not a multiple of 8 or in front of the
+ *   content, a directory prefix that does not fit the image, a directory rectangle with a negative number or more entries than the
+ *   grid has tiles.  GF_ERR_BOUNDS: anything of the header record that would be read at or behind image_bytes (a truncated
+ *   image).  GF_ERR_UNSUPPORTED: versions 1.02 and 1.03 (another file head), more than GF_MAX_ELEMS elements or 255 codecs, 2^28 or more cells in a tile, more than 0x7fffffff tiles.  GF_ERR_ARG: null
+ *   pointers.  gf_file_info: element types are GF_ELEM_*; an ICF element's fill_i is its iFill, fill_f its fFill, scale and offset
+ *   the file's; SHORT and INTEGER take fill_i from their fill, FLOAT takes fill_f.  codecs[k] is the GF_CODEC_* kind of the k-th
+ *   codec id ("GvrsHuffman", "GvrsDeflate", "GvrsFloat" -> GF_CODEC_NONE, "GvrsCanonicalHuffman", "LSOP12", "LSOP08") or
+ *   GF_CODEC_UNKNOWN for an id the library has no decoder for: such a file opens, and its reads answer GF_ERR_UNSUPPORTED.
+ *   gf_file_elem_name / gf_file_codec_id: the strings of the specification (owned by the handle; NULL for a bad number).
+ *   gf_file_tile_position: the directory looked up in an image in HOST memory: *pos = the file position of the tile's record
+ *   content (the tile-index word; the record's size word is 8 bytes in front of it), 0 for a tile the file does not hold.  The
+ *   entry and the record head are judged as the device form judges them (below): GF_ERR_BOUNDS / GF_ERR_FORMAT, *pos = the entry's
+ *   position.  GF_ERR_ARG: a tile index outside the grid's tiles.
+ *   gf_file_read_block_elems_dev: GvrsElement.readBlock for every element of the file, the image in DEVICE memory.  d_image is
+ *   8-byte aligned and readable to the end of the aligned 16-byte piece that holds its last byte.  T = the tiles of the rectangle's
+ *   rectangle of tiles (gf_block_tile_rect), row-major; d_status is element-major, d_status[e * T + j]; d_present[j] (may be NULL)
+ *   is 1 where the directory names a record for tile j (a non-zero entry, whatever becomes of it).  A tile the directory does not
+ *   name -- an entry of 0, or a tile outside the directory's rectangle -- is GF_OK for every element and its cells are fill, as the
+ *   reference delivers them.  k_file_locate reads the directory in place in d_image (compact entries: unsigned int32 * 8; extended:
+ *   int64) and judges a position before it touches it: position >= content_pos + 8, a multiple of 8, position + 12 <= image_bytes,
+ *   and the entry itself inside the image -- else GF_ERR_BOUNDS and nothing of the tile is read; the record's tile-index word must
+ *   equal the slot's tile index, else GF_ERR_FORMAT (the check the reference left as a commented assertion,
+ *   RecordManager.java:746-748).  The record [position - 8, min(image_bytes, position - 8 + size)) then goes through the pipeline
+ *   of gf_block_read_elems_dev unchanged: framing, CRC-32C when verify_checksum (and the file's specification enables checksums: the
+ *   records of a file without them carry a 0 there, and the reference does not look), partition by codec, the decoders, scatter, gather.
+ *   Statuses, fill for failed elements and THE BLOCK IS GOOD IFF EVERY STATUS IS GF_OK are exactly as there.  Runs on the context's
+ *   stream (as the gf_lsop08_*_dev and gf_image_*_dev calls do) and synchronises it once, not capture-safe; d_blocks is a HOST array of n_elems device pointers.  GF_ERR_UNSUPPORTED: a codec list that holds
+ *   GF_CODEC_UNKNOWN.  GF_ERR_ARG: null pointers, an unaligned d_image, image_bytes < content_pos, a rectangle not wholly inside
+ *   the grid.
+ *   gf_file_read_block_elems: the same for an image, blocks, statuses and present flags in HOST memory: the rectangle's tiles are
+ *   looked up in the host image and only their records are staged, end to end, into the context's staging buffer -- never the
+ *   whole image -- and go through the contiguous path of gf_block_read_elems.
+ * Not here: versions <= 1.03, writing or updating files, the contents of the metadata and free-space directories (their positions
+ * are reported), the tile cache.                                                                                                */
+#define GF_CODEC_UNKNOWN (-1)   /* an id the library has no decoder for: reported, never accepted by a call */
+typedef struct gf_file gf_file;
+typedef struct gf_file_info {
+    int32_t version, subversion, checksum_enabled, raster_space, coordinate_system;
+    gf_grid_spec grid;
+    int32_t n_elems;  gf_elem_spec elems[GF_MAX_ELEMS];   /* GF_ELEM_* types; fill_i / fill_f / scale / offset from the file */
+    int32_t n_codecs; int32_t codecs[255];                /* GF_CODEC_* kinds in list order, GF_CODEC_UNKNOWN where unmapped */
+    uint64_t content_pos, tile_dir_pos, metadata_dir_pos, freespace_dir_pos;
+    int32_t dir_extended, dir_row0, dir_col0, dir_n_rows, dir_n_cols;  uint64_t dir_entries_pos;
+    double x0, y0, x1, y1, cell_size_x, cell_size_y, m2r[6], r2m[6];
+} gf_file_info;
+gf_status gf_file_open(const uint8_t *image, size_t image_bytes, gf_file **out);   /* host bytes; no device, no context */
+void      gf_file_close(gf_file *f);
+gf_status gf_file_get_info(const gf_file *f, gf_file_info *info);
+const char *gf_file_elem_name(const gf_file *f, int e);
+const char *gf_file_codec_id(const gf_file *f, int k);
+const char *gf_file_product_label(const gf_file *f);
+gf_status gf_file_tile_position(const gf_file *f, const uint8_t *image, size_t image_bytes, int32_t tile_index, uint64_t *pos);
+gf_status gf_file_read_block_elems_dev(gf_context *ctx, const gf_file *f, const uint8_t *d_image, size_t image_bytes,
+                                       const gf_rect *rect, int verify_checksum, void *const *d_blocks, int32_t *d_status,
+                                       uint8_t *d_present);
+gf_status gf_file_read_block_elems(gf_context *ctx, const gf_file *f, const uint8_t *image, size_t image_bytes,
+                                   const gf_rect *rect, int verify_checksum, void *const *blocks, int32_t *status, uint8_t *present);
 
 /* ---- thin device-memory helpers so that non-HIP hosts (JNI, ctypes) can
  *      stage data without linking the HIP runtime themselves --------------- */
