@@ -3,7 +3,9 @@ lsop/LsDecoder08.java:71-163, lsop/LsHeader.java:137-189, 210-265, util/jama/LUD
 the gf_lsop08_* entry points.  No reference-made LSOP08 file exists, so parity rests on reading the source and on the checks of
 tests/test_lsop08_ref.py.
 
-float32 arithmetic is done with numpy float32 scalars, FP64 with Python floats, the JAMA loops are written out.  The oracle supplies
+float32 arithmetic is done with numpy float32 scalars, FP64 with Python floats, the JAMA loops are written out.  The sums and the
+interior stream also have numpy array forms (gram_fast, interior_fast) that give the same bits, which tests/test_lsop08_ref.py
+checks; predict() and encode() use them, so that a tile of a million cells takes seconds.  The oracle supplies
 only what the reference fixtures already pin: CodecM32 (m32_encode_seq / m32_decode_seq) and the legacy Huffman coder
 (huffman_encode / huffman_decode with bit_pos / prefix).  Deflate is Python's zlib at level 6.
 """
@@ -250,12 +252,31 @@ def interior(nr, nc, v, u, rounding=estimate, trace=None):
     return out
 
 
+def interior_fast(nr, nc, v, u):
+    """interior() with numpy float32 arrays: the int -> float32 conversion of every neighbour, the eight float32 products summed left
+    to right (an elementwise numpy operation rounds once, as the scalar one does), + 0.5f, and Java's cast -- NaN -> 0, toward zero,
+    saturating -- on the float64 image of the float32 sum, which is exact.  tests/test_lsop08_ref.py holds it to interior()."""
+    g = np.asarray(v, np.int32).reshape(nr, nc)
+    offs = [(0, -1), (-1, -1), (-1, 0), (0, -2), (-1, -2), (-2, -2), (-2, -1), (-2, 0)]          # neighbours(), as (row, column) steps
+    uf = np.asarray(u, np.float32)
+    with np.errstate(all="ignore"):
+        p = None
+        for i, (dr, dc) in enumerate(offs):
+            t = uf[i] * g[2 + dr:nr + dr, 2 + dc:nc + dc].astype(np.float32)
+            p = t if p is None else p + t
+        assert p.dtype == np.float32
+        q = (p + F32(0.5)).astype(np.float64)
+        est = np.clip(np.trunc(np.where(np.isnan(q), 0.0, q)), float(I32_MIN), float(I32_MAX)).astype(np.int64)
+    res = g[2:, 2:].astype(np.int64) - est
+    return ((res + 2 ** 31) % 2 ** 32 - 2 ** 31).ravel().tolist()
+
+
 def predict(nr, nc, v):
     """LsOptimalPredictor08.encode: (seed, u float32[8], initialisers, interior) or None (declined)."""
     u = coefficients(nr, nc, v)
     if u is None:
         return None
-    return int(v[0]), u, initialisers(nr, nc, v), interior(nr, nc, v, u)
+    return int(v[0]), u, initialisers(nr, nc, v), interior_fast(nr, nc, v, u)
 
 
 def reconstruct(nr, nc, seed, init, inter, u, rounding=estimate, trace=None):
@@ -315,22 +336,50 @@ def deflate_body(m_init, m_int):
     return z0 + z1
 
 
+def m32_seq(values):
+    """oracle.m32_encode_seq, with the oracle asked once per distinct value (a stream of a million values has a few thousand)."""
+    vals = [int(x) for x in values]
+    code = {x: oracle.m32_encode(x) for x in set(vals)}
+    return b"".join([code[x] for x in vals])
+
+
+def container(codec_index, seed, u, init, inter, ctype=None):
+    """LsEncoder08.encode :85-134 from the two streams on: (packing, type).  ctype None: the reference's choice, Huffman only where
+    its body is strictly shorter; 0 / 1: that container whatever its size (the device encoder writes type 0 always)."""
+    m_init, m_int = m32_seq(init), m32_seq(inter)
+    body_h = huffman_body(m_init, m_int)
+    if ctype is None:
+        body_d = deflate_body(m_init, m_int)
+        ctype = TYPE_DEFLATE if len(body_h) >= len(body_d) else TYPE_HUFFMAN
+    body = body_h if ctype == TYPE_HUFFMAN else deflate_body(m_init, m_int)
+    return pack_header(codec_index, ctype, seed, u, len(m_init), len(m_int)) + body, ctype
+
+
 def encode(codec_index, nr, nc, v, force_type=None):
-    """LsEncoder08.encode: (packing, type) or (None, None).  force_type: that container whatever its size (the device encoder
-    writes type 0 always)."""
+    """LsEncoder08.encode: (packing, type) or (None, None).  force_type: see container()."""
     pr = predict(nr, nc, v)
     if pr is None:
         return None, None
-    seed, u, init, inter = pr
-    m_init, m_int = oracle.m32_encode_seq(init), oracle.m32_encode_seq(inter)
-    body_h = huffman_body(m_init, m_int)
-    if force_type == TYPE_HUFFMAN:
-        ctype = TYPE_HUFFMAN
-    else:
-        body_d = deflate_body(m_init, m_int)
-        ctype = TYPE_DEFLATE if force_type == TYPE_DEFLATE or len(body_h) >= len(body_d) else TYPE_HUFFMAN
-    body = body_h if ctype == TYPE_HUFFMAN else body_d
-    return pack_header(codec_index, ctype, seed, u, len(m_init), len(m_int)) + body, ctype
+    return container(codec_index, *pr, ctype=force_type)
+
+
+CHUNK = 1024                      # values of a chunk of k_lsop8_pack (L8_THREADS * P8_VPT)
+
+
+def segment_code_lengths(stream):
+    """(code_lengths[256] of HuffmanEncoder for the stream's M32 bytes, number of distinct bytes); the single-symbol form has no
+    text: every length is 0"""
+    m = np.frombuffer(m32_seq(stream), np.uint8)
+    return oracle.huffman_encode(m)[2].astype(np.int64), int(np.unique(m).size)
+
+
+def chunk_bits(stream, code_lengths):
+    """code bits of each run of CHUNK consecutive values of a stream: for every value the code lengths of its M32 bytes, summed"""
+    vals = np.asarray([int(x) for x in stream], np.int64)
+    uniq, inv = np.unique(vals, return_inverse=True)
+    cl = np.asarray(code_lengths, np.int64)
+    per = np.array([int(cl[np.frombuffer(oracle.m32_encode(int(x)), np.uint8)].sum()) for x in uniq], np.int64)[inv]
+    return [int(per[i:i + CHUNK].sum()) for i in range(0, len(per), CHUNK)]
 
 
 def parse_header(pack):

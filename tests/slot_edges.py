@@ -19,6 +19,8 @@ test_slot_edges_oracle.test_content_selects_the_packer), for the tiles that fit 
   canon plain-m*, nulls k_canon_pack without escapes;  canon escape: every escape kind 1..6 (value_edges.canon_kind)
   lsop 16 / 32          k_canon_pack2 with and without the 16-bit histogram records (gf_lsop_predict16_eligible, restated in
                         lsop16_eligible), each with and without GF_LSOP_VALUE_CHECKSUM (header 55 / 59 bytes)
+  lsop08                k_lsop8_pack (gvrs_lsop8.hip; lengths from the restatement tests/lsop08_ref.py, type 0 as the device encoder
+                        writes it): a shape whose cell count is no multiple of 4 and LSOP_WIDE
   m32                   k_m32_streams: three candidates per tile, written when length + 8 <= sub_stride
   canon uniform         the uniform form (6 bytes, predictor 0) at the smallest legal stride, 16: the only tiles that fit
 (The canonical encoder also has an overflow branch for a uniform tile at strides below 8 (gvrs_canon_encode.hip, "early =
@@ -27,6 +29,7 @@ import functools
 
 import numpy as np
 
+import lsop08_ref
 import oracle
 import value_edges as ve
 
@@ -119,6 +122,8 @@ def encode_one(codec, nr, nc, tile, mask=0xF, lsop_flags=0):
     if codec == "lsop":
         pk, _ = oracle.lsop12_encode(0, nr, nc, tile, False, bool(lsop_flags & LSOP_CHECKSUM))
         return pk, 0
+    if codec == "lsop08":
+        return lsop08_ref.encode(0, nr, nc, tile, force_type=lsop08_ref.TYPE_HUFFMAN)[0], 0
     raise ValueError(codec)
 
 
@@ -427,6 +432,16 @@ def lsop(wide, checksum):
                         _all_k(nr * nc), lsop_flags=LSOP_CHECKSUM if checksum else 0, lo=64)
 
 
+LSOP08_ODD = (15, 41)                            # 615 cells: tile t of a batch starts 12 t bytes past a 16-byte boundary
+
+
+@functools.lru_cache(maxsize=None)
+def lsop08(wide):
+    nr, nc = LSOP_WIDE if wide else LSOP08_ODD
+    assert (nr * nc) % 4 != 0
+    return build_family("lsop08-%s" % ("wide" if wide else "odd"), "lsop08", nr, nc, ladder(nr, nc), _all_k(nr * nc), lo=64)
+
+
 @functools.lru_cache(maxsize=None)
 def m32(edge=0):
     """sub_stride S such that the lengths S - 11 .. S - 7 occur among the streams of candidate `edge` (0 Differencing, 1 Linear;
@@ -465,7 +480,7 @@ def m32(edge=0):
 SMALL_FAMILIES = ([(huffman_plane, (m,)) for m in (1, 2, 3)] + [(huffman_flatplain, (m,)) for m in (1, 2, 3)]
                   + [(huffman_wide, (m,)) for m in (1, 2, 3)] + [(huffman_nulls, ()), (huffman_rare, ())]
                   + [(canon_plain, (m,)) for m in (1, 2, 3)] + [(canon_nulls, ()), (canon_escape, ())]
-                  + [(lsop, (w, c)) for w in (False, True) for c in (False, True)])
+                  + [(lsop, (w, c)) for w in (False, True) for c in (False, True)] + [(lsop08, (w,)) for w in (False, True)])
 
 
 def family_id(entry):

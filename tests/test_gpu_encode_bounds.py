@@ -1,9 +1,9 @@
-"""Where the encoders write.  Every packer path of the slot-writing encoders (gf_huffman_*, gf_canon_*, gf_lsop12_*,
+"""Where the encoders write.  Every packer path of the slot-writing encoders (gf_huffman_*, gf_canon_*, gf_lsop12_*, gf_lsop08_*,
 gf_m32_encode_batch_i32_dev) gets packings of S - 3 .. S + 1 bytes around its slot stride S (tests/slot_edges.py; the CPU test
 tests/test_slot_edges_oracle.py proves that every family reaches them), in a slot array that lies inside a larger allocation filled
 with a sentinel byte: lengths, predictors and statuses are the oracle's, a packing that fits is the oracle's byte for byte, a tile
 reported GF_OVERFLOW or GF_DECLINED leaves its whole slot untouched (the contract of include/gvrs_hip_codec.h), and nothing outside
-the slot array is written.  Then gf_compact_dev on what the encoders leave behind -- tiles with d_lengths[t] > slot_stride take no
+the slot array is written (LSOP08: nor outside the caller's residuals, coefficient records and scratch statuses).  Then gf_compact_dev on what the encoders leave behind -- tiles with d_lengths[t] > slot_stride take no
 room -- on hand-made slots at every alignment and at blob_cap's edges, and the out_cap / blob_cap rule of the host-memory encoders.
 
 No test here depends on an access outside an allocation: guards are sized from the oracle's lengths before any kernel runs."""
@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lsop08_ref
 import oracle
 import route_plan as rp
 import slot_edges as se
@@ -19,6 +20,7 @@ from slot_edges import DECLINED, OK, SENTINEL
 
 pytestmark = pytest.mark.gpu
 META_GUARD = 64
+LSOP = ("lsop", "lsop08")
 ERR_CAPACITY = -3
 
 
@@ -74,7 +76,8 @@ def _encode(ctx, f, tiles=None, index=None):
     e.values = DeviceBuffer(ctx, vals.nbytes).upload(vals)
     e.slots = Guarded(ctx, nt * sub * S, f.guard())
     e.lengths = Guarded(ctx, nt * sub * 4, META_GUARD)
-    e.preds = Guarded(ctx, nt * sub, META_GUARD) if f.codec != "lsop" else None     # (the LSOP12 encoders report no predictor)
+    e.preds = Guarded(ctx, nt * sub, META_GUARD) if f.codec not in LSOP else None   # (the LSOP encoders report no predictor)
+    e.work_ok = True
     e.status = Guarded(ctx, nt * 4, META_GUARD)
     ctx.reserve(f.nr, f.nc, nt)
     if f.codec in ("huffman", "canon"):
@@ -94,6 +97,15 @@ def _encode(ctx, f, tiles=None, index=None):
             check(L.gf_lsop12_encode_batch_i32_dev(ctx.handle, None, 0, f.nr, f.nc, nt, e.values.ptr, e.slots.ptr, S, e.lengths.ptr,
                                                    e.status.ptr, e.residuals.ptr, e.res_stride, e.coefs.ptr, e.scratch.ptr),
                   "lsop encode")
+    elif f.codec == "lsop08":            # the caller's work buffers lie between guards too: residuals, coefficient records, statuses
+        n = int(L.gf_lsop08_residual_count(f.nr, f.nc))
+        e.res_stride = (n + 3) // 4 * 4
+        e.residuals, e.coefs = Guarded(ctx, nt * e.res_stride * 4, META_GUARD), Guarded(ctx, nt * 64, META_GUARD)
+        e.scratch = Guarded(ctx, nt * 4, META_GUARD)
+        check(L.gf_lsop08_encode_batch_i32_dev(ctx.handle, 0, f.nr, f.nc, nt, e.values.ptr, e.slots.ptr, S, e.lengths.ptr, e.status.ptr,
+                                               e.residuals.ptr, e.res_stride, e.coefs.ptr, e.scratch.ptr), "lsop08 encode")
+        ctx.synchronize()
+        e.work_ok = all(g.download()[1] for g in (e.residuals, e.coefs, e.scratch))
     else:
         e.seeds = Guarded(ctx, nt * 4, META_GUARD)
         check(L.gf_m32_encode_batch_i32_dev(ctx.handle, None, f.nr, f.nc, nt, e.values.ptr, e.slots.ptr, S, e.lengths.ptr,
@@ -110,8 +122,8 @@ def _encode(ctx, f, tiles=None, index=None):
 def _check(f, e):
     """the assertions of the module's docstring on one encode call; every mismatch is collected before the test fails"""
     S, bad = f.stride, []
-    if not (e.slots_ok and e.lengths_ok and e.status_ok and e.preds_ok):
-        bad.append(("guards", e.slots_ok, e.lengths_ok, e.preds_ok, e.status_ok))
+    if not (e.slots_ok and e.lengths_ok and e.status_ok and e.preds_ok and e.work_ok):
+        bad.append(("guards", e.slots_ok, e.lengths_ok, e.preds_ok, e.status_ok, e.work_ok))
     for i, t in enumerate(e.index):
         want = f.expected_status(t)
         if e.h_status[i] != want:
@@ -132,7 +144,7 @@ def _check(f, e):
             continue
         if int(e.h_lengths[i]) != f.lengths[t]:
             bad.append(("length", i, t, int(e.h_lengths[i]), f.lengths[t]))
-        if f.codec != "lsop" and want != DECLINED and int(e.h_preds[i]) != f.preds[t]:
+        if f.codec not in LSOP and want != DECLINED and int(e.h_preds[i]) != f.preds[t]:
             bad.append(("predictor", i, t, int(e.h_preds[i]), f.preds[t]))
         if want == OK:
             if e.h_slots[i, :f.lengths[t]].tobytes() != f.packs[t]:
@@ -178,6 +190,9 @@ def _decode(ctx, f, e):
     if f.codec == "lsop":
         check(L.gf_lsop12_decode_batch_i32_dev(ctx.handle, None, f.nr, f.nc, nt, e.slots.ptr, nt * S, None, S, d_len.ptr, d_vals.ptr,
                                                d_st.ptr, e.residuals.ptr, e.res_stride, e.coefs.ptr, e.scratch.ptr), "lsop decode")
+    elif f.codec == "lsop08":
+        check(L.gf_lsop08_decode_batch_i32_dev(ctx.handle, f.nr, f.nc, nt, e.slots.ptr, nt * S, None, S, d_len.ptr, d_vals.ptr, d_st.ptr,
+                                               e.residuals.ptr, e.res_stride, e.coefs.ptr, e.scratch.ptr), "lsop08 decode")
     else:
         fn = getattr(L, "gf_%s_decode_batch_i32_dev" % f.codec)
         check(fn(ctx.handle, None, f.nr, f.nc, nt, e.slots.ptr, nt * S, None, S, d_len.ptr, d_vals.ptr, d_st.ptr), "decode")
@@ -207,7 +222,7 @@ def _assert_route(ctx, f, e):
         p = rp.plan(rp.KIND_CANON, f.nr, f.nc, e.nt)
         assert rep.encKind == rp.KIND_CANON and rep.encBits == p.encBits, (hex(rep.encBits), hex(p.encBits))
         assert rep.encBits & rp.CANON_ENC_1 and rep.encBits & rp.CANON_PACK
-    # (the LSOP12 and the M32 kernels are not in the route report: slot_edges.lsop16_eligible restates what selects k_canon_pack2's
+    # (the LSOP12, the LSOP08 and the M32 kernels are not in the route report: slot_edges.lsop16_eligible restates what selects k_canon_pack2's
     # histogram form, and gf_m32_encode_batch_i32_dev has one kernel)
 
 
@@ -257,7 +272,7 @@ def _shuffled(f, n_min):
     return index
 
 
-@pytest.mark.parametrize("entry", [(se.huffman_plane, (1,)), (se.canon_plain, (1,))], ids=se.family_id)
+@pytest.mark.parametrize("entry", [(se.huffman_plane, (1,)), (se.canon_plain, (1,)), (se.lsop08, (False,))], ids=se.family_id)
 def test_large_batch(entry):
     """the family repeated to 2,100 tiles and more in a shuffled order: several tiles per workgroup, the tile loop's `continue`
     paths between tiles that are written"""
@@ -384,7 +399,8 @@ def _host_tile(kind):
         f = (v.astype(np.float32) * np.float32(0.1)).astype(np.float32)
         return f, oracle.codec_float_encode(0, nr, nc, f.view(np.uint32), 6)
     enc = {"huffman": lambda: oracle.codec_huffman_encode(0, nr, nc, v)[0], "canon": lambda: oracle.codec_canon_encode(0, nr, nc, v)[0],
-           "deflate": lambda: oracle.codec_deflate_encode(0, nr, nc, v)[0], "lsop12": lambda: oracle.lsop12_encode(0, nr, nc, v, True)[0]}
+           "deflate": lambda: oracle.codec_deflate_encode(0, nr, nc, v)[0], "lsop12": lambda: oracle.lsop12_encode(0, nr, nc, v, True)[0],
+           "lsop08": lambda: lsop08_ref.encode(0, nr, nc, v)[0]}
     return v, enc[kind]()
 
 
@@ -395,10 +411,12 @@ def _call_one(L, ctx, kind, v, out, cap, n):
         return L.gf_float_encode_f32(ctx.handle, 0, nr, nc, _ptr(v), 6, _ptr(out), cap, C.byref(n))
     if kind == "lsop12":
         return L.gf_lsop12_encode_i32(ctx.handle, 0, nr, nc, _ptr(v), 1, _ptr(out), cap, C.byref(n))
+    if kind == "lsop08":
+        return L.gf_lsop08_encode_i32(ctx.handle, 0, nr, nc, _ptr(v), _ptr(out), cap, C.byref(n))
     return getattr(L, "gf_%s_encode_i32" % kind)(ctx.handle, 0, nr, nc, _ptr(v), _ptr(out), cap, C.byref(n))
 
 
-@pytest.mark.parametrize("kind", ["huffman", "canon", "deflate", "lsop12", "float"])
+@pytest.mark.parametrize("kind", ["huffman", "canon", "deflate", "lsop12", "lsop08", "float"])
 def test_one_tile_out_cap_edges(kind):
     """out_cap = L - 1, L, L + 1: GF_ERR_CAPACITY with *out_len == L ("out_len = needed") and nothing written behind out_cap, or
     GF_OK with the oracle's bytes.  The Huffman and the canonical calls are made twice each: the second one replays the captured
@@ -421,7 +439,7 @@ def test_one_tile_out_cap_edges(kind):
                 assert rc == 0 and out[:need].tobytes() == ref, (kind, cap, call, rc)
 
 
-@pytest.mark.parametrize("kind", ["huffman", "canon", "deflate", "lsop12", "float"])
+@pytest.mark.parametrize("kind", ["huffman", "canon", "deflate", "lsop12", "lsop08", "float"])
 def test_batch_blob_cap_edges(kind):
     """blob_cap = total - 1 and total: GF_ERR_CAPACITY with offsets complete and nothing written behind blob_cap, or the exact blob"""
     from gridfour_amd import lib
@@ -437,7 +455,8 @@ def test_batch_blob_cap_edges(kind):
     else:
         vals = ints
         enc = {"huffman": lambda x: oracle.codec_huffman_encode(0, nr, nc, x)[0], "canon": lambda x: oracle.codec_canon_encode(0, nr, nc, x)[0],
-               "deflate": lambda x: oracle.codec_deflate_encode(0, nr, nc, x)[0], "lsop12": lambda x: oracle.lsop12_encode(0, nr, nc, x, True)[0]}[kind]
+               "deflate": lambda x: oracle.codec_deflate_encode(0, nr, nc, x)[0], "lsop12": lambda x: oracle.lsop12_encode(0, nr, nc, x, True)[0],
+               "lsop08": lambda x: lsop08_ref.encode(0, nr, nc, x)[0]}[kind]
         refs = [enc(x) or b"" for x in vals]
     cat = b"".join(refs)
     total = len(cat)
@@ -450,6 +469,8 @@ def test_batch_blob_cap_edges(kind):
             rc = L.gf_float_encode_batch_f32(ctx.handle, 0, nr, nc, nt, _ptr(vals), 6, _ptr(blob), cap, _ptr(off))
         elif kind == "lsop12":
             rc = L.gf_lsop12_encode_batch_i32(ctx.handle, 0, nr, nc, nt, _ptr(vals), 1, _ptr(blob), cap, _ptr(off), None, None)
+        elif kind == "lsop08":
+            rc = L.gf_lsop08_encode_batch_i32(ctx.handle, 0, nr, nc, nt, _ptr(vals), _ptr(blob), cap, _ptr(off), None, None)
         else:
             rc = getattr(L, "gf_%s_encode_batch_i32" % kind)(ctx.handle, 0, nr, nc, nt, _ptr(vals), _ptr(blob), cap, _ptr(off), None, None)
         assert off.tolist() == want_off, (kind, cap, rc, off.tolist(), want_off)

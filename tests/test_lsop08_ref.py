@@ -1,6 +1,7 @@
 """CPU-only: the Python restatement of LSOP08 (tests/lsop08_ref.py) holds together -- it round-trips, its LU agrees with an exact
-rational solve, its rounding is told apart from LSOP12's -- and what of the gf_lsop08_* family can be checked without a device: the
-size functions, the argument refusals, the Java adapter and its shim kind (as text)."""
+rational solve, its rounding is told apart from LSOP12's, its numpy forms give the scalar forms' bits -- and what of the gf_lsop08_*
+family can be checked without a device: the size functions, the argument refusals, the Java adapter and its shim kind (as text).
+Then the tiles of tests/lsop08_cases.py: each has the property the GPU tests use it for."""
 import ctypes as C
 import os
 import re
@@ -10,6 +11,7 @@ import zlib
 import numpy as np
 import pytest
 
+import lsop08_cases as K
 import lsop08_ref as R
 import oracle
 from gvrs_walk import tile_packings
@@ -86,6 +88,132 @@ def test_single_symbol_segment():
 def test_numpy_sums_are_the_scan_order_sums():
     for v, nr, nc in ((R.terrain(16, 16), 16, 16), (make_tile("noise32", 16, 16), 16, 16), (make_tile("sparse_big", 7, 9), 7, 9)):
         assert R.gram(nr, nc, v) == R.gram_fast(nr, nc, v)
+
+
+def test_numpy_interior_is_the_scalar_interior():
+    """interior_fast against interior(): every coefficient set of COEF_SETS (Inf, NaN, saturation at both limits, the half-way cases
+    of p + 0.5f, negative predictions) on a smooth tile and on 32-bit noise, and each tile's own coefficients"""
+    tiles = [(16, 16, R.terrain(16, 16)), (9, 11, make_tile("noise32", 9, 11)), (7, 70, make_tile("smooth", 7, 70)),
+             (12, 9, np.random.default_rng(8).integers(-2 ** 31, 2 ** 31, 108).astype(np.int32))]
+    for nr, nc, v in tiles:
+        sets = dict(R.COEF_SETS, own=R.coefficients(nr, nc, v))
+        for name, u in sets.items():
+            tr = []
+            slow = R.interior(nr, nc, v, u, trace=tr)
+            assert slow == R.interior_fast(nr, nc, v, u), (nr, nc, name)
+        assert len(slow) == R.n_interior(nr, nc)
+    # ... and the sets still reach the edges they are there for, on the tile the comparison ran on
+    v = tiles[1][2]
+    with np.errstate(all="ignore"):
+        tr = []
+        R.interior(9, 11, v, R.COEF_SETS["inf_pair"], trace=tr)
+        assert np.isnan(np.array(tr, np.float32)).any()
+        tr = []
+        R.interior(9, 11, v, R.COEF_SETS["sat_pos"], trace=tr)
+        assert (np.array(tr, np.float32) > 3e9).any() and (np.array(tr, np.float32) < -3e9).any()
+
+
+def test_container_from_streams_round_trips():
+    """container() is what encode() writes, and a packing built from arbitrary streams and coefficients decodes to what
+    reconstruct() makes of them, in both types"""
+    nr, nc = 7, 9
+    v = R.terrain(nr, nc, 0)
+    seed, u, init, inter = R.predict(nr, nc, v)
+    for t in (None, 0, 1):
+        assert R.container(5, seed, u, init, inter, t) == R.encode(5, nr, nc, v, force_type=t)
+    rng = np.random.default_rng(4)
+    init = rng.integers(-2 ** 31, 2 ** 31, R.n_init(nr, nc)).tolist()
+    inter = rng.integers(-70000, 70000, R.n_interior(nr, nc)).tolist()
+    want = R.reconstruct(nr, nc, -12345, init, inter, R.COEF_SETS["dense"])
+    for t in (0, 1):
+        p, ctype = R.container(9, -12345, R.COEF_SETS["dense"], init, inter, t)
+        assert ctype == t and p[:3] == bytes([9, 0x40 | t, 8]) and np.array_equal(R.decode(nr, nc, p), want)
+    assert R.m32_seq(init) == oracle.m32_encode_seq(init)
+
+
+def test_chunk_bits_add_up_to_the_text():
+    """the chunks' code bits are the segment's text: the bit store's growth less the serialised tree"""
+    v = make_tile("sparse_big", 40, 60)
+    _, _, init, inter = R.predict(40, 60, v)
+    for stream in (init, inter):
+        m = R.m32_seq(stream)
+        _, end, cl, tree_bits = oracle.huffman_encode(m)
+        bits = R.chunk_bits(stream, cl)
+        assert len(bits) == -(-len(stream) // R.CHUNK) and sum(bits) == end - tree_bits
+        assert bits[0] == sum(int(cl[b]) for x in stream[:R.CHUNK] for b in oracle.m32_encode(x))
+    assert R.segment_code_lengths([3, 3, 3])[1] == 1 and R.segment_code_lengths(init)[1] > 1
+
+
+# ---- the tiles of tests/lsop08_cases.py have the properties the GPU tests need
+@pytest.mark.parametrize("shape", [(4, 4), (66, 66)], ids=lambda s: "%dx%d" % s)
+def test_threshold_tiles_lie_either_side_of_two_to_the_53(shape):
+    nr, nc = shape
+    n_int = R.n_interior(nr, nc)
+    m = K.largest_exact_magnitude(n_int)
+    assert m * m * n_int < 2 ** 53 <= (m + 1) ** 2 * n_int
+    tiles = K.threshold_tiles(nr, nc)
+    assert sorted(tiles) == sorted(["at-mid", "at-row0", "at-last", "over-mid", "over-row0", "over-last", "int32min"])
+    for name, v in tiles.items():
+        assert (K.bound(nr, nc, v) < 2 ** 53) == name.startswith("at-"), name
+        assert R.predict(nr, nc, v) is not None, name
+        # on the exact side every sum of the normal equations is an integer the scan-order FP64 sums hold exactly
+        if name.startswith("at-") and n_int <= 16:
+            s, c = R.gram(nr, nc, v)
+            es, ec = R.gram_exact(nr, nc, v)
+            assert [int(x) for x in s] == es and all(int(c[a][b]) == ec[a][b] for a in range(9) for b in range(a, 9))
+    for where in ("mid", "row0", "last"):
+        a, b = tiles["at-" + where].astype(np.int64), tiles["over-" + where].astype(np.int64)
+        assert (a != b).sum() == 1 and (b - a).max() == 1 and a.max() == m and b.max() == m + 1
+    assert tiles["at-row0"][:nc].max() == m and tiles["at-last"][-1] == m and int(tiles["int32min"].min()) == R.I32_MIN
+
+
+def test_single_symbol_tiles():
+    nr, nc, v = K.single_symbol_first()
+    seed, u, init, inter = R.predict(nr, nc, v)
+    assert set(init) == {0} and K.distinct_bytes(init) == 1 and K.distinct_bytes(inter) > 1
+    assert oracle.huffman_encode(R.m32_seq(init))[1] == 17            # the whole first segment: 17 tree bits, no text
+    found = K.single_symbol_second()
+    assert found is not None, "no all-equal interior within %d seeds a shape" % K.SECOND_SEARCH_SEEDS
+    nr, nc, v, seed_no = found
+    print("all-equal interior: %d x %d, seed %d" % (nr, nc, seed_no))
+    _, _, init, inter = R.predict(nr, nc, v)
+    assert K.distinct_bytes(inter) == 1 and K.distinct_bytes(init) > 1
+    b0, end0, _, _ = oracle.huffman_encode(R.m32_seq(init))
+    assert oracle.huffman_encode(R.m32_seq(inter), end0, b0)[1] == end0 + 17        # ... and the second one behind a first with text
+    for name, p, want in K.single_symbol_containers():
+        assert np.array_equal(R.decode(6, 7, p), want), name
+    # the forms' sizes: 17 tree bits and no text for a segment of one symbol
+    both = [p for name, p, _ in K.single_symbol_containers() if name == "both"][0]
+    assert len(both) == R.HEADER_BYTES + (17 + 17 + 7) // 8
+
+
+@pytest.mark.parametrize("shape", K.MAX_BODY_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_max_packing_holds_the_longest_bodies(shape):
+    """gf_lsop08_max_packing "always fits": 32-bit noise makes every residual five or six M32 bytes, and the tiles with the most
+    distinct bytes make the serialised trees as large as the shape allows; either container type"""
+    import gridfour_amd
+    nr, nc = shape
+    cap = gridfour_amd.lib().gf_lsop08_max_packing(nr, nc)
+    for name, v in K.max_body_tiles(nr, nc).items():
+        seed, u, init, inter = R.predict(nr, nc, v)
+        assert np.median([len(oracle.m32_encode(x)) for x in init + inter]) >= 5, name
+        if name == "bytes" and shape in ((33, 65), (6, 257)):
+            assert K.distinct_bytes(inter) == 256 and (K.distinct_bytes(init) == 256 or shape == (33, 65))
+        for t in (0, 1):
+            assert len(R.container(0, seed, u, init, inter, t)[0]) <= cap, (name, t)
+
+
+def test_window_overflow_tile():
+    """the tile of the packer's direct route: one chunk of the interior stream beyond the 2,048-word window by the margin of
+    lsop08_cases.OVERFLOW_MARGIN_BITS, another inside it, no code longer than 56 bits (about 6 s: tiles of more than a million cells)"""
+    o = K.overflow_tile()
+    print("side %d, %d noise row(s), largest chunk %d bits, smallest %d, chunks beyond the window %d of %d, longest codes %r, tried %r" %
+          (o.side, o.rows, max(o.chunk_bits), min(o.chunk_bits), sum(b > K.WINDOW_BITS for b in o.chunk_bits), len(o.chunk_bits), o.max_code,
+           o.tried))
+    assert o.side * o.side <= K.OVERFLOW_MAX_CELLS and o.tried[0][:2] == (1024, 4)
+    assert max(o.chunk_bits) > K.WINDOW_BITS + K.OVERFLOW_MARGIN_BITS and min(o.chunk_bits) < K.WINDOW_BITS - 31
+    assert max(o.max_code) <= K.MAX_CODE_BITS
+    assert o.pack[:3] == bytes([6, 0x40, 8]) and len(o.pack) > R.HEADER_BYTES + sum(o.chunk_bits) // 8
 
 
 def _sample14(golden_dir):

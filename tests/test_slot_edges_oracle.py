@@ -21,7 +21,7 @@ def family(request):
 def test_stride_is_legal_and_lengths_reach_its_edges(family):
     f = family
     S = f.stride
-    assert S % 16 == 0 and S >= (64 if f.codec == "lsop" else 16)
+    assert S % 16 == 0 and S >= (64 if f.codec in ("lsop", "lsop08") else 16)
     have = set(f.all_lengths)
     if f.relaxed:                         # huffman general: one packing within 16 bytes under S, one within 16 bytes over
         assert any(S - 16 <= L <= S for L in f.lengths if L) and any(S < L <= S + 16 for L in f.lengths)
@@ -125,6 +125,23 @@ def test_content_selects_the_packer():
         a, b = se.lsop(wide, False), se.lsop(wide, True)
         assert min(x for x in b.all_lengths) - min(x for x in a.all_lengths) == 4          # the checksum: header 55 -> 59 bytes
         assert all(p is None or (p[1] & 0x80) for p in b.packs) and all(p is None or not (p[1] & 0x80) for p in a.packs)
+
+
+def test_lsop08_families():
+    """the LSOP08 families: tiles of a batch start at every alignment a cell count that is no multiple of 4 gives, every packing is
+    the Huffman container (type 0, what the device encoder writes) and decodes to its tile by the restatement, and no slot is
+    larger than gf_lsop08_max_packing needs it (the stride lies below it: a slot that is too small is a caller's choice)"""
+    import gridfour_amd
+    import lsop08_ref as R
+    for wide in (False, True):
+        f = se.lsop08(wide)
+        assert f.cells % 4 != 0 and (f.nr, f.nc) == (se.LSOP_WIDE if wide else se.LSOP08_ODD)
+        assert 64 <= f.stride < gridfour_amd.lib().gf_lsop08_max_packing(f.nr, f.nc)
+        for t in range(f.n):
+            if f.packs[t] is not None:
+                assert f.packs[t][:3] == bytes([0, 0x40, 8])
+        for t in (0, f.n - 1):
+            assert np.array_equal(R.decode(f.nr, f.nc, f.packs[t]), f.tiles[t])
 
 
 def test_uniform_family_at_the_smallest_stride():
