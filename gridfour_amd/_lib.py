@@ -132,6 +132,10 @@ SIGNATURES = {
     "gf_file_tile_position": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),
     "gf_file_read_block_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp]),
     "gf_file_read_block_elems": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp]),
+    "gf_file_write_plan": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gf_file_assemble": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "gf_file_write_block_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "gf_file_write_block_elems": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_uint64), _vp, _vp, _vp]),
     "gf_block_write_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_int,
                                            C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "gf_block_write_elems": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp,

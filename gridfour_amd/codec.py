@@ -54,6 +54,17 @@ _FILE_INFO = np.dtype([("version", np.int32), ("subversion", np.int32), ("checks
                        ("x0", np.float64), ("y0", np.float64), ("x1", np.float64), ("y1", np.float64), ("cell_size_x", np.float64),
                        ("cell_size_y", np.float64), ("m2r", np.float64, 6), ("r2m", np.float64, 6)], align=True)         # gf_file_info
 
+_FILE_ELEM_FACTS = np.dtype([("name", np.uint64), ("label", np.uint64), ("description", np.uint64), ("unit", np.uint64), ("continuous", np.int32),
+                             ("has_range", np.int32), ("range", _ELEM_RANGE)], align=True)                             # gf_file_elem_facts
+_FILE_FACTS = np.dtype([("grid", np.int32, 4), ("n_elems", np.int32), ("n_codecs", np.int32), ("elems", np.uint64), ("elem_facts", np.uint64),
+                        ("codec_ids", np.uint64), ("product_label", np.uint64), ("checksum_enabled", np.int32), ("raster_space", np.int32),
+                        ("coordinate_system", np.int32), ("reserved", np.int32), ("x0", np.float64), ("y0", np.float64), ("x1", np.float64),
+                        ("y1", np.float64), ("cell_size_x", np.float64), ("cell_size_y", np.float64), ("m2r", np.float64, 6),
+                        ("r2m", np.float64, 6), ("uuid", np.uint8, 16), ("time_modified", np.int64)], align=True)           # gf_file_facts
+_FILE_METADATA = np.dtype([("name", np.uint64), ("description", np.uint64), ("content", np.uint64), ("content_bytes", np.uint64),
+                           ("record_id", np.int32), ("type", np.int32)], align=True)                                     # gf_file_metadata
+FILE_DIR_EXTENDED = 1                                                      # GF_FILE_DIR_EXTENDED
+
 IMAGE_RGB, IMAGE_YCOCG = 0, 1                                              # GF_IMAGE_*
 IMAGE_MODELS = {"rgb": IMAGE_RGB, "ycocg": IMAGE_YCOCG}
 TAB_ACCUMULATE, TAB_SKIP_FILL = 1, 2                                      # GF_TAB_*
@@ -1807,10 +1818,99 @@ class CodecMasterHip:
 
 
 # ---- GVRS files ----
+class GvrsFileFacts:
+    """What a file is written from (gf_file_facts, gf_file_metadata), held together with every buffer the structs point into.
+    grid = (rows, columns of the grid, rows, columns of a tile); elems as the record calls take them ("int" | "short" | "float" |
+    ("icf", scale, offset, fill_i, fill_f)), fills as read_block_dev; elem_facts: None (elements "e0", "e1", ... with the default
+    ranges) or per element a dict of name, label, description, unit, continuous and range -- None, (min, max), or for an "icf"
+    element (min_f, max_f, min_i, max_i); codec_ids: the specification's strings; bounds = (x0, y0, x1, y1), default the grid's
+    cell indices; metadata: (name, record id, type code, content bytes, description) per record, laid in this order."""
+
+    def __init__(self, grid, elems, fills=None, elem_facts=None, codec_ids=(), checksums=True, raster_space=0, coordinate_system=0, bounds=None,
+                 cell_size=(1.0, 1.0), m2r=(1.0, 0.0, -0.0, 0.0, 1.0, -0.0), r2m=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0), product_label="", uuid=bytes(16),
+                 time_modified=0, metadata=()):
+        self.grid, self.elems = tuple(int(x) for x in grid), list(elems)
+        self._held = []
+        self.specs, self.dtypes = CodecMasterHip._elem_specs(self.elems)
+        CodecMasterHip._fill_specs(self.specs, self.elems, fills)
+        self._written = [_elem_kind(el)[1].delivered for el in self.elems]
+        f = np.zeros(1, _FILE_FACTS)
+        f["grid"], f["n_elems"], f["n_codecs"] = self.grid, len(self.elems), len(codec_ids)
+        f["elems"] = self.specs.ctypes.data
+        if elem_facts is not None:
+            assert len(elem_facts) == len(self.elems)
+            x = np.zeros(len(self.elems), _FILE_ELEM_FACTS)
+            for e, d in enumerate(elem_facts):
+                for k in ("name", "label", "description", "unit"):
+                    x[e][k] = self._str(d.get(k))
+                x[e]["continuous"] = int(bool(d.get("continuous", False)))
+                r = d.get("range")
+                if r is not None:
+                    kind = _elem_kind(self.elems[e])[0]
+                    x[e]["has_range"] = 1
+                    if kind == "icf":
+                        x[e]["range"]["min_f"], x[e]["range"]["max_f"], x[e]["range"]["min_i"], x[e]["range"]["max_i"] = r
+                    else:
+                        suffix = _ELEM_KINDS[kind].range[0]
+                        x[e]["range"]["min_" + suffix], x[e]["range"]["max_" + suffix] = r
+            self._held.append(x)
+            f["elem_facts"] = x.ctypes.data
+        ids = (C.c_char_p * max(len(codec_ids), 1))(*[c.encode() for c in codec_ids])
+        self._held.append(ids)
+        f["codec_ids"] = C.addressof(ids)
+        f["product_label"] = self._str(product_label)
+        f["checksum_enabled"], f["raster_space"], f["coordinate_system"] = int(bool(checksums)), raster_space, coordinate_system
+        f["x0"], f["y0"], f["x1"], f["y1"] = (0.0, 0.0, float(self.grid[1] - 1), float(self.grid[0] - 1)) if bounds is None else bounds
+        f["cell_size_x"], f["cell_size_y"] = cell_size
+        f["m2r"], f["r2m"] = m2r, r2m
+        f["uuid"] = np.frombuffer(bytes(uuid), np.uint8)
+        f["time_modified"] = time_modified
+        self.facts, self.checksums = f, bool(checksums)
+        m = np.zeros(max(len(metadata), 1), _FILE_METADATA)
+        for k, (name, record_id, type_code, content, description) in enumerate(metadata):
+            content = np.frombuffer(bytes(content), np.uint8)
+            self._held.append(content)
+            m[k]["name"], m[k]["description"] = self._str(name), self._str(description)
+            m[k]["content"], m[k]["content_bytes"] = (content.ctypes.data if content.size else 0), content.size
+            m[k]["record_id"], m[k]["type"] = record_id, type_code
+        self.metadata, self.n_metadata = m, len(metadata)
+
+    def _str(self, s):
+        """The address of a held 0-terminated copy of s; 0 (NULL) for None"""
+        if s is None:
+            return 0
+        b = C.create_string_buffer(s if isinstance(s, bytes) else s.encode())
+        self._held.append(b)
+        return C.addressof(b)
+
+    def args(self):
+        """(facts, metadata, n_metadata) as the entry points take them"""
+        return _ptr(self.facts), (_ptr(self.metadata) if self.n_metadata else None), self.n_metadata
+
+    def rect_args(self, rect):
+        """-> (rect array, number of tiles it touches); None: the whole grid"""
+        grid, rect = _grid_rect(self.grid[2], self.grid[3], self.grid[:2], (0, 0, self.grid[0], self.grid[1]) if rect is None else rect)
+        return rect, _tiles_of_rect(grid, rect)
+
+    def blocks_in(self, rect, blocks):
+        n_block = int(rect[2]) * int(rect[3])
+        blocks = [np.ascontiguousarray(b, dtype=dt).reshape(-1) for b, dt in zip(blocks, self._written)]
+        assert len(blocks) == len(self.elems) and all(b.size == n_block for b in blocks)
+        return blocks
+
+    def plan(self, rect=None, flags=0):
+        """gf_file_write_plan: (the first tile record's position, the largest image the rectangle can need)"""
+        r = None if rect is None else self.rect_args(rect)[0]
+        first, most = C.c_uint64(), C.c_uint64()
+        _call("gf_file_write_plan", *self.args(), None if r is None else _ptr(r), int(flags), C.byref(first), C.byref(most))
+        return first.value, most.value
+
+
 class GvrsFileHip:
     """org.gridfour.gvrs.GvrsFile(file, "r") with GvrsElement.readBlock for all elements: a version 1.04 file opened from its path
     or its bytes (gf_file_open: the header record and the tile directory's prefix, parsed on the host), blocks read from the file
-    image by gf_file_read_block_elems[_dev].  .info is the gf_file_info as a dict, with the elements' names, the codec ids and the
+    image by gf_file_read_block_elems[_dev]; and, as static methods, new file images written: assemble (tile records in, host
+    memory), write_image (blocks in device memory in, the image out) and write_image_host.  .info is the gf_file_info as a dict, with the elements' names, the codec ids and the
     product label; .elems are the elements as the record calls of CodecMasterHip take them."""
 
     _ELEM_NAMES = {kind.type: name for name, kind in _ELEM_KINDS.items()}
@@ -1880,6 +1980,80 @@ class GvrsFileHip:
         _call("gf_file_read_block_elems", ctx.handle, self._h, _ptr(image), image.size, _ptr(rect), int(bool(verify_checksums)), _ptrs(out),
               _ptr(status), _ptr(present))
         return out, status, present
+
+    # ---- files written (gf_file_assemble, gf_file_write_block_elems[_dev]) ----
+    @staticmethod
+    def assemble(facts, records, tile_indices, flags=0, image_cap=None, return_code=False):
+        """gf_file_assemble: the image of a new file from facts (a GvrsFileFacts) and tile records (list[bytes], b"" for none) of the
+        tiles tile_indices, laid in that order -> bytes.  return_code (with image_cap, the room given): (status, image bytes as far
+        as the room reaches, the size the image has or needs)."""
+        blob, offsets = _blob_of([bytes(r) for r in records])
+        idx = np.ascontiguousarray(tile_indices, np.int32)
+        assert idx.size == len(records)
+        need = C.c_uint64()
+        fn = lib().gf_file_assemble
+        a = facts.args() + (int(flags), _ptr(blob), _ptr(offsets), _ptr(idx), idx.size)
+        if image_cap is None:
+            st = fn(*a, None, 0, C.byref(need))
+            if st != _lib.ERR_CAPACITY:
+                check(st, "gf_file_assemble")
+            image_cap = need.value
+        image = np.full(max(int(image_cap), 1), 0xA5, np.uint8)
+        st = fn(*a, _ptr(image), int(image_cap), C.byref(need))
+        if return_code:
+            return st, image[:int(image_cap)].tobytes(), need.value
+        check(st, "gf_file_assemble")
+        return image[:need.value].tobytes()
+
+    @staticmethod
+    def write_image(ctx, facts, blocks, rect=None, flags=0, image_cap=None, raw=False):
+        """gf_file_write_block_elems_dev: the image of a new file whose rectangle rect (None: the whole grid) holds blocks (per
+        element [n_rows, n_cols]: int32 / int16 / float32, an "icf" element's float VALUES), written in device memory.  Uploads,
+        calls, synchronises, downloads: (image bytes, tile indices [n_out], status [n_out], codec used [n_elems, n_out]); raw: (file
+        status, the size the image has or needs, the whole buffer of image_cap + 64 bytes pre-filled with 0xA5, tile indices,
+        status, codec used) and a file status of ERR_CAPACITY does not raise."""
+        rect, n_out = facts.rect_args(rect)
+        blocks = facts.blocks_in(rect, blocks)
+        cap = facts.plan(rect, flags)[1] if image_cap is None else int(image_cap)
+        ne = len(blocks)
+        with _DeviceScope(ctx) as s:
+            d_blk = [s.upload(b, slack=16) for b in blocks]
+            d_image = s.alloc(cap + 64, fill=0xA5)
+            d_bytes = s.alloc(16, fill=0x7f)
+            d_fst = s.alloc(16, fill=0x7f)
+            d_idx = s.alloc(n_out * 4 + 16, fill=0x7f)
+            d_st = s.alloc(n_out * 4 + 16, fill=0x7f)
+            d_used = s.alloc(ne * n_out + 16, fill=0)
+            s.run("gf_file_write_block_elems_dev", ctx.handle, *facts.args(), _ptr(rect), s.ptrs(d_blk), int(flags), d_image.ptr, cap, d_bytes.ptr,
+                  d_fst.ptr, d_idx.ptr, d_st.ptr, d_used.ptr)
+            n_bytes, fst = int(d_bytes.download(np.uint64, 1)[0]), int(d_fst.download(np.int32, 1)[0])
+            image = d_image.download(np.uint8, cap + 64)
+            idx, status = d_idx.download(np.int32, n_out), d_st.download(np.int32, n_out)
+            used = d_used.download(np.uint8, ne * n_out).reshape(ne, n_out)
+        if raw:
+            return fst, n_bytes, image, idx, status, used
+        check(fst, "gf_file_write_block_elems_dev")
+        return image[:n_bytes].tobytes(), idx, status, used
+
+    @staticmethod
+    def write_image_host(ctx, facts, blocks, rect=None, flags=0, image_cap=None, return_code=False):
+        """The same through gf_file_write_block_elems, the host-memory form, which takes any codec list -> (image bytes, tile indices,
+        status, codec used); a negative per-tile status or too small an image_cap raises unless return_code is set: then (the call's
+        return value, the size the image has or needs) come first."""
+        rect, n_out = facts.rect_args(rect)
+        blocks = facts.blocks_in(rect, blocks)
+        cap = facts.plan(rect, flags)[1] if image_cap is None else int(image_cap)
+        image = np.full(max(cap, 1), 0xA5, np.uint8)
+        idx, status = np.full(n_out, -1, np.int32), np.full(n_out, 0x7f7f7f7f, np.int32)
+        used = np.zeros((len(blocks), n_out), np.uint8)
+        need = C.c_uint64()
+        rc = lib().gf_file_write_block_elems(ctx.handle, *facts.args(), _ptr(rect), _ptrs(blocks), int(flags), _ptr(image), cap, C.byref(need),
+                                             _ptr(idx), _ptr(status), _ptr(used))
+        n = min(need.value, cap)
+        if return_code:
+            return rc, need.value, image[:n].tobytes(), idx, status, used
+        check(rc, "gf_file_write_block_elems")
+        return image[:n].tobytes(), idx, status, used
 
     def close(self):
         if self._h:

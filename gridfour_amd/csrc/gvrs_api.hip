@@ -147,6 +147,8 @@ void gf_context_destroy(gf_context *c)
     for (DevBuf *b = c->bufs; b; b = b->next) b->release();
     gf_host_pipe_destroy(c->pipe);
     c->hRecCounts.release();
+    c->hFileFront.release();
+    if (c->fileFrontDone) (void)hipEventDestroy(c->fileFrontDone);
     if (c->hRoomySeen) (void)hipHostFree(c->hRoomySeen);
     if (c->side.stream) {
         (void)hipStreamSynchronize(c->side.stream);

@@ -154,6 +154,8 @@ struct gf_context {
     DevBuf dTabPartials{this}, dTabSort{this};  // tabulation (gvrs_api_tabulate.hip): k_tabulate_dense's partials (fixed size); the symbol form's
                                                 // keys, histograms and runs, a strip's table and the merge's chunk counts
     DevBuf dFileLoc{this};                      // file images (gvrs_api_file.hip): the extents and verdicts of the rectangle's tiles
+    DevBuf dFileWrite{this};                    // file images written (gvrs_api_file_write.hip): the kernels' state, the records' offsets, the
+                                                // metadata directory on its way to its place, the tile directory's chunk checksums
     DevBuf dTabBlocks{this};                    // ... the composed read's blocks (gf_block_read_tabulated_symbols_elems[_dev])
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
     // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
@@ -162,6 +164,8 @@ struct gf_context {
     GfSideStream side{nullptr, nullptr, nullptr};   // second stream + fork / join events: the fast decode kernel's roomy run (gvrs_kernels.h)
     uint32_t *hRoomySeen = nullptr;                 // page-locked word: GfDecodeArgs::roomySeenHost
     PinBuf hRecCounts;                              // page-locked: the partition's counts on their way to the host
+    PinBuf hFileFront;                              // page-locked: a written file's header, metadata records and metadata directory on their
+    hipEvent_t fileFrontDone = nullptr;             // way to the device; recorded behind their copies (gvrs_api_file_write.hip)
     // what the last encode and the last decode batch launched (host side only: gf_internal_route_report)
     uint32_t routeEnc = 0, routeDec = 0;            // GF_RT_* bits
     int routeEncKind = -1, routeDecKind = -1, routeRoomy = GF_ROOMY_NONE, routePrepass = 0;

@@ -586,6 +586,44 @@ hipError_t gf_launch_file_locate(const GfFileLocateArgs &a, hipStream_t stream);
 // status[e * nSlots + j] = verdict[j] wherever that is not GF_FILE_LOCATED
 hipError_t gf_launch_file_status(const int32_t *verdict, int32_t *status, size_t nSlots, int nElems, hipStream_t stream);
 
+// A file image WRITTEN (gvrs_file_write.hip; driven by gvrs_api_file_write.hip): behind the record writer, which has laid the records
+// of the rectangle's tiles into the image from firstRecordPos on and left their offsets, the kernels find the bounding rectangle of
+// the tiles with a record (k_file_dir_rect), write the tile directory (k_file_dir_entries), checksum it in chunks (k_file_dir_crc)
+// and finish the image (k_file_finish).  Slot j = the j-th tile of the rectangle of tiles, row-major; record j is
+// image[firstRecordPos + offsets[j] .. firstRecordPos + offsets[j + 1]).
+struct GfFileWriteState {      // zeroed before k_file_dir_rect; 0 in the first four words = no tile has a record
+    uint32_t invRow0, invCol0; // max of ~row, ~col over the tiles with a record
+    uint32_t row1p, col1p;     // max of row + 1, col + 1
+    uint32_t extended;         // a record's content position exceeds 1 << 35
+    uint32_t pad_[3];
+};
+struct GfFileWriteArgs {
+    uint8_t *image;            // 8-byte aligned
+    uint64_t imageCap;
+    uint64_t firstRecordPos;   // a multiple of 8
+    uint64_t contentPos;       // the header record's end: its checksum word lies 4 bytes in front of it
+    const uint64_t *offsets;   // nTileRows * nTileCols + 1
+    const uint8_t *metaDir;    // the metadata directory's record, whole (8-byte aligned), metaDirBytes (a multiple of 8, may be 0)
+    uint32_t metaDirBytes;
+    int32_t checksums, forceExtended;
+    int32_t tileRow0, tileCol0, nTileRows, nTileCols;   // the block's rectangle of tiles
+    GfFileWriteState *state;
+    uint32_t *chunkCrc;        // one word per GF_FILE_CRC_CHUNK bytes of the largest directory the rectangle of tiles can give
+    uint64_t *imageBytes;      // out: the image's size, or the size it needs
+    int32_t *fileStatus;       // out: GF_K_OK or GF_K_ERR_CAPACITY
+};
+#define GF_K_ERR_CAPACITY (-3)
+// A front of up to this many bytes -- the image's bytes [16, firstRecordPos) and behind them the metadata directory's record --
+// travels in k_file_finish's ARGUMENTS: nothing is uploaded and the call waits for nothing.  A longer one (large metadata) is
+// copied to the image and to metaDir from a page-locked buffer before the kernels.
+constexpr uint32_t GF_FILE_FRONT_ARG_BYTES = 3072;
+struct GfFileFinishArgs {
+    GfFileWriteArgs a;         // (a.metaDir is not read)
+    uint32_t front[GF_FILE_FRONT_ARG_BYTES / 4];
+};
+// the four kernels, in order; front: null, or the (firstRecordPos - 16 + metaDirBytes) bytes that travel as arguments
+hipError_t gf_launch_file_write(const GfFileWriteArgs &a, const uint8_t *front, hipStream_t stream);
+
 // A block WRITTEN (gvrs_blocks_write.hip; driven by gvrs_api_blocks_write.hip): the rectangle's cells of every element cut into the
 // tiles of the rectangle of tiles in the type the record writer takes (k_block_cut_elems: TileElement*.setValue with its range
 // checks, RasterTile.hasValidData), and the per-tile verdict the record writer receives as its pre-status (k_block_write_verdict).

@@ -1315,8 +1315,8 @@ gf_status gf_synth_dem_style_dev(gf_context *ctx, void *stream, uint64_t seed, i
  *   gf_file_read_block_elems: the same for an image, blocks, statuses and present flags in HOST memory: the rectangle's tiles are
  *   looked up in the host image and only their records are staged, end to end, into the context's staging buffer -- never the
  *   whole image -- and go through the contiguous path of gf_block_read_elems.
- * Not here: versions <= 1.03, writing or updating files, the contents of the metadata and free-space directories (their positions
- * are reported), the tile cache.                                                                                                */
+ * Not here: versions <= 1.03, updating files (writing a new one: below), the contents of the metadata and free-space directories
+ * (their positions are reported), the tile cache.                                                                                                */
 #define GF_CODEC_UNKNOWN (-1)   /* an id the library has no decoder for: reported, never accepted by a call */
 typedef struct gf_file gf_file;
 typedef struct gf_file_info {
@@ -1340,6 +1340,109 @@ gf_status gf_file_read_block_elems_dev(gf_context *ctx, const gf_file *f, const 
                                        uint8_t *d_present);
 gf_status gf_file_read_block_elems(gf_context *ctx, const gf_file *f, const uint8_t *image, size_t image_bytes,
                                    const gf_rect *rect, int verify_checksum, void *const *blocks, int32_t *status, uint8_t *present);
+
+/* ---- GVRS files WRITTEN: a new file image from a rectangle of the raster, in one call ------------------------------------------
+ * (gvrs/GvrsFile.java:239-300 the constructor that writes the header, :584-616 close; gvrs/GvrsFileSpecification.java:1170-1285
+ * write; gvrs/GvrsMetadata.java:217-234 write; gvrs/RecordManager.java:161-204, 218-219 a record's frame and size, :670-719
+ * writeMetadata, :864-883 writeTileDirectory, :991-1017 writeMetadataDirectory, :87, 451-454 the extended directory;
+ * gvrs/TileDirectory.java:266-290, gvrs/TileDirectoryExtended.java writeTilePositions / getStorageSize)
+ * The inverse of gf_file_open and the file reads: the image of a NEW version 1.04 file, laid out as every finished file of the
+ * reference is,
+ *     file head | header record | metadata records | tile records | metadata directory | tile directory
+ * with no free-space directory (its header word is 0).  Every record: [int32 size, a multiple of 8][type 0 0 0][content][zeros]
+ * [CRC-32C of all bytes in front of it, or 0 in a file without checksums], size = multipleOf8(content + 12).  Given the facts a
+ * reference file was written from, its metadata records' fields and its tile records in file order, gf_file_assemble returns the
+ * reference's file byte for byte.
+ *   THE FACTS (gf_file_facts; strings are 0-terminated bytes, NULL reads as "", at most 65535 bytes each): grid and tile sizes; per
+ *   element its gf_elem_spec (type, fill_i / fill_f, scale, offset) and a gf_file_elem_facts: name, label, description, unit, the
+ *   continuous flag and the range the header states -- has_range 0: the defaults of the reference's constructors, as ranges ==
+ *   NULL in gf_block_write_elems (an ICF's min_i / max_i are then INT_MIN + 1 / INT_MAX - 1 and its min_f / max_f their values);
+ *   INT and SHORT state min_i / max_i, FLOAT min_f / max_f, ICF all four.  THE RANGE OF AN ELEMENT IS ALSO WHAT THE FILE WRITES
+ *   CHECK CELLS AGAINST.  elem_facts == NULL: elements named "e0", "e1", ... with defaults.  codec_ids: the strings of the
+ *   specification's codec list; the kinds follow from them as gf_file_open maps them ("GvrsFloat" -> GF_CODEC_NONE), an id that
+ *   maps to nothing is GF_ERR_UNSUPPORTED.  checksum_enabled, raster_space, coordinate_system, the six bounds and cell sizes,
+ *   m2r[6] and r2m[6] are written as given (nothing is computed from coordinates); product label, UUID (the 16 bytes in file
+ *   order), time modified.  Opened-for-writing is 0 and the number of levels 1.  The header record's size is the reference's:
+ *   multipleOf8 of its fields + 8 reserved bytes + the checksum word.
+ *   METADATA (gf_file_metadata, n_metadata of them, may be 0): name, record id, type code (GvrsMetadataType), content bytes and
+ *   description; record content [utf name][int32 id][type 0 0 0][int32 n][n bytes][utf description], record type 1, laid in the
+ *   caller's order directly behind the header record.  The metadata directory (record type 4: int32 count, then per record int64
+ *   content position, utf name, int32 id, type byte, in order of position) follows the tile records; with n_metadata == 0 there is
+ *   none and the header's word is 0.
+ *   THE TILE DIRECTORY (record type 5): 8 prefix bytes (byte 1: the extended flag), int32 row0 col0 nRows nCols, the entries
+ *   row-major.  The rectangle is the BOUNDING rectangle of the tiles that got a record; a tile inside it without one has entry 0.
+ *   With no record at all the four numbers are 0, there are no entries and the record is 40 bytes.  Compact entries: content
+ *   position / 8 as uint32; extended: int64 positions.  Extended when a record's content position exceeds 1 << 35, as the
+ *   reference decides, or when flags holds GF_FILE_DIR_EXTENDED (any size; the readers take either form at any size).
+ *   gf_file_write_plan (host arithmetic): *first_record_pos = where the first tile record goes (behind the metadata records, a
+ *   multiple of 8); *max_image_bytes = the largest image the rectangle of tiles rect touches (NULL: the whole grid) can need: every
+ *   tile's record at gf_tile_record_max_bytes_elems plus both directories.  Either pointer may be NULL.
+ *   gf_file_assemble needs no device and no context.  Records as gf_tile_record_encode_batch_elems and gf_block_write_elems hand
+ *   them out: record r = blob[offsets[r] .. offsets[r + 1]) belongs to tile tile_indices[r].  The image holds them IN THE CALLER'S
+ *   ORDER (the reference's sample files lay their tiles 3, 2, 1, 0); a record of length 0 gets no place and its tile the entry 0.
+ *   *image_bytes = the image's size, also when it does not fit: GF_ERR_CAPACITY, and nothing is written to image (may be NULL with
+ *   image_cap 0).  GF_ERR_ARG: null pointers, a tile index outside the grid's tiles, two non-empty records of one tile, a
+ *   non-empty record whose length is no multiple of 8 or below 24, decreasing offsets, facts gf_file_open would refuse (sizes
+ *   < 1, n_elems < 1, an element type outside 0..3), a string of more than 65535 bytes; GF_ERR_UNSUPPORTED: n_elems > GF_MAX_ELEMS,
+ *   n_codecs > 255, an unknown codec id, more than 0x7fffffff tiles.
+ *   gf_file_write_block_elems_dev: blocks in DEVICE memory in (d_blocks, a HOST array of n_elems device pointers, rect, the types
+ *   and rules of gf_block_write_elems_dev with n_old == 0), the file image out in device memory at d_image (8-byte aligned,
+ *   image_cap bytes).  Runs on the context's stream (as gf_file_read_block_elems_dev does), ONLY ENQUEUES and never synchronises.
+ *   The host emits the header record (directory positions and checksum still 0), the metadata records and the metadata directory;
+ *   up to 3,072 bytes of them travel in k_file_finish's arguments, which writes them; more (large metadata) is copied to the image's
+ *   front, bytes 16 and up, from a page-locked buffer of the context before the kernels (the one wait on the host, and only then: an
+ *   EARLIER call's copy must have left that buffer, an event behind it); the block write's pipeline writes the records STRAIGHT INTO the image from first_record_pos
+ *   on, in row-major order of the rectangle's tiles (no copy of the records); then k_file_dir_rect (bounding rectangle and the
+ *   extended decision), k_file_dir_entries (the tile directory, every byte once), k_file_dir_crc (a wave per chunk of
+ *   GF_FILE_CRC_CHUNK bytes) and k_file_finish (one wave: the metadata directory -- emitted whole on the host, checksum included,
+ *   because its records lie in front of the tile records and their positions are known there -- copied to its place, the chunks'
+ *   checksums folded in order, both positions patched into the header record, its checksum, and LAST the 16 bytes of the file
+ *   head).  *d_image_bytes = the image's size, *d_file_status = GF_OK -- or, when the image does not fit image_cap (the record
+ *   writer skipped a record whole, or a directory has no room), the size it needs and GF_ERR_CAPACITY: then no directory is
+ *   written, bytes 0..15 are ZERO, and the image does not open.  No byte at or behind image_cap is ever written.  d_tile_indices,
+ *   d_status (per tile of the rectangle of tiles) and d_codec_used (may be NULL) are the block write's; a tile with GF_ERR_BOUNDS
+ *   or GF_DECLINED gets no record and the entry 0, and the file is valid without it.  The codec ids must map to a list the device
+ *   record writer takes (GF_ERR_UNSUPPORTED otherwise, from the arguments alone).  GF_ERR_ARG: what gf_file_assemble and
+ *   gf_block_write_elems_dev refuse, an unaligned d_image, NULL d_image_bytes / d_file_status.
+ *   gf_file_write_block_elems: the same for host memory and any codec list: gf_block_write_elems, then gf_file_assemble in row-major
+ *   order; for a list the device form takes, the same bytes.  Returns the first negative per-tile status, else the assembler's.
+ * Not here: updating an existing file (old records, the free-space list), versions <= 1.03, the tile cache.                     */
+#define GF_FILE_DIR_EXTENDED 1  /* flags: the tile directory in its extended form whatever the positions */
+typedef struct gf_file_elem_facts {
+    const char *name, *label, *description, *unit;
+    int32_t continuous, has_range;
+    gf_elem_range range;
+} gf_file_elem_facts;
+typedef struct gf_file_facts {
+    gf_grid_spec grid;
+    int32_t n_elems, n_codecs;
+    const gf_elem_spec *elems;                 /* n_elems */
+    const gf_file_elem_facts *elem_facts;      /* n_elems, or NULL */
+    const char *const *codec_ids;              /* n_codecs */
+    const char *product_label;
+    int32_t checksum_enabled, raster_space, coordinate_system, reserved;
+    double x0, y0, x1, y1, cell_size_x, cell_size_y, m2r[6], r2m[6];
+    uint8_t uuid[16];
+    int64_t time_modified;
+} gf_file_facts;
+typedef struct gf_file_metadata {
+    const char *name, *description;
+    const uint8_t *content;
+    uint64_t content_bytes;
+    int32_t record_id, type;
+} gf_file_metadata;
+gf_status gf_file_write_plan(const gf_file_facts *facts, const gf_file_metadata *metadata, int n_metadata, const gf_rect *rect,
+                             int flags, uint64_t *first_record_pos, uint64_t *max_image_bytes);
+gf_status gf_file_assemble(const gf_file_facts *facts, const gf_file_metadata *metadata, int n_metadata, int flags,
+                           const uint8_t *blob, const uint64_t *offsets, const int32_t *tile_indices, size_t n_records,
+                           uint8_t *image, size_t image_cap, uint64_t *image_bytes);
+gf_status gf_file_write_block_elems_dev(gf_context *ctx, const gf_file_facts *facts, const gf_file_metadata *metadata,
+                                        int n_metadata, const gf_rect *rect, const void *const *d_blocks, int flags,
+                                        uint8_t *d_image, size_t image_cap, uint64_t *d_image_bytes, int32_t *d_file_status,
+                                        int32_t *d_tile_indices, int32_t *d_status, uint8_t *d_codec_used);
+gf_status gf_file_write_block_elems(gf_context *ctx, const gf_file_facts *facts, const gf_file_metadata *metadata, int n_metadata,
+                                    const gf_rect *rect, const void *const *blocks, int flags, uint8_t *image, size_t image_cap,
+                                    uint64_t *image_bytes, int32_t *tile_indices, int32_t *status, uint8_t *codec_used);
 
 /* ---- thin device-memory helpers so that non-HIP hosts (JNI, ctypes) can
  *      stage data without linking the HIP runtime themselves --------------- */
