@@ -2055,6 +2055,109 @@ class GvrsFileHip:
         check(rc, "gf_file_write_block_elems")
         return image[:n].tobytes(), idx, status, used
 
+    # ---- files updated in place (gf_file_update_*) ----
+    def update_begin(self, image=None):
+        """gf_file_update_begin: the file opened for an update -> a GvrsFileUpdate (the free list after opening, the plan).  image:
+        other bytes than the file's own.  A handle serves one image state: after an update, open the new image and begin again."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        return GvrsFileUpdate(self, image)
+
+    def update_assemble(self, upd, records, tile_indices, time_modified, status=None, flags=0, image_cap=None, return_code=False):
+        """gf_file_update_assemble: tile records (list[bytes], b"" for none) of the tiles tile_indices applied to the image upd was
+        begun on, in that order -> the updated image's bytes.  status: per record, a negative one leaves its tile untouched.
+        image_cap: the room given (default: the plan's bound for the whole grid).  return_code: (status, the buffer of image_cap
+        bytes -- unchanged behind the old image's bytes, 0xA5, when the call refuses -- and the size the image has or needs)."""
+        blob, offsets = _blob_of([bytes(r) for r in records])
+        idx = np.ascontiguousarray(tile_indices, np.int32)
+        assert idx.size == len(records)
+        st = None if status is None else np.ascontiguousarray(status, np.int32)
+        cap = upd.plan()[0] if image_cap is None else int(image_cap)
+        image = np.full(max(cap, 1), 0xA5, np.uint8)
+        image[:min(cap, upd.image.size)] = upd.image[:min(cap, upd.image.size)]
+        need = C.c_uint64()
+        rc = lib().gf_file_update_assemble(upd.handle, _ptr(image), cap, _ptr(blob), _ptr(offsets), _ptr(idx), None if st is None else _ptr(st),
+                                           idx.size, int(time_modified), int(flags), C.byref(need))
+        if return_code:
+            return rc, image[:cap].tobytes(), need.value
+        check(rc, "gf_file_update_assemble")
+        return image[:need.value].tobytes()
+
+    def update_records_dev(self, ctx, upd, records, tile_indices, time_modified, status=None, flags=0, image_cap=None, list_capacity=0):
+        """gf_file_update_records_dev: update_assemble's device counterpart.  Uploads the image upd was begun on and the records,
+        calls, synchronises, downloads -> (file status, the size the image has or needs, the whole buffer of image_cap + 64
+        bytes: the old image, then 0xA5).  list_capacity: the room of the allocator's list (0: what the call needs); a list of
+        more than 2048 nodes' capacity is worked in the context's scratch, a smaller one in LDS."""
+        blob, offsets = _blob_of([bytes(r) for r in records])
+        idx = np.ascontiguousarray(tile_indices, np.int32)
+        assert idx.size == len(records)
+        cap = upd.plan()[0] if image_cap is None else int(image_cap)
+        buf = np.full(cap + 64, 0xA5, np.uint8)
+        buf[:min(cap, upd.image.size)] = upd.image[:min(cap, upd.image.size)]
+        with _DeviceScope(ctx) as s:
+            d_image = s.upload(buf)
+            d_blob = s.upload(blob, slack=16)
+            d_off = s.upload(offsets, slack=16)
+            d_idx = s.upload(idx, slack=16)
+            d_st = None if status is None else s.upload(np.ascontiguousarray(status, np.int32), slack=16)
+            d_bytes = s.alloc(16, fill=0x7f)
+            d_fst = s.alloc(16, fill=0x7f)
+            s.run("gf_file_update_records_dev", ctx.handle, upd.handle, d_image.ptr, cap, d_blob.ptr, d_off.ptr, d_idx.ptr,
+                  None if d_st is None else d_st.ptr, idx.size, int(offsets[-1]), int(time_modified), int(flags), int(list_capacity), d_bytes.ptr,
+                  d_fst.ptr)
+            return int(d_fst.download(np.int32, 1)[0]), int(d_bytes.download(np.uint64, 1)[0]), d_image.download(np.uint8, cap + 64).tobytes()
+
+    def update_image(self, ctx, upd, rect, blocks, time_modified, flags=0, image_cap=None, raw=False):
+        """gf_file_update_block_elems_dev: blocks (as update_image_host takes them) stored into rect of the image upd was begun on,
+        in device memory.  Uploads, calls, synchronises, downloads: (image bytes, tile indices, status, codec used); raw: (file
+        status, the size the image has or needs, the whole buffer of image_cap + 64 bytes -- the old image, then 0xA5 --, tile
+        indices, status, codec used), and no file status raises."""
+        image0, rect, nt, shape = self._read_args(rect, upd.image)
+        blocks = [np.ascontiguousarray(b, dt).reshape(shape) for b, dt in zip(blocks, self._dtypes)]
+        assert len(blocks) == self.n_elems
+        cap = upd.plan(rect)[0] if image_cap is None else int(image_cap)
+        buf = np.full(cap + 64, 0xA5, np.uint8)
+        buf[:min(cap, image0.size)] = image0[:min(cap, image0.size)]
+        with _DeviceScope(ctx) as s:
+            d_blk = [s.upload(b, slack=16) for b in blocks]
+            d_image = s.upload(buf)
+            d_bytes = s.alloc(16, fill=0x7f)
+            d_fst = s.alloc(16, fill=0x7f)
+            d_idx = s.alloc(nt * 4 + 16, fill=0x7f)
+            d_st = s.alloc(nt * 4 + 16, fill=0x7f)
+            d_used = s.alloc(self.n_elems * nt + 16, fill=0)
+            s.run("gf_file_update_block_elems_dev", ctx.handle, upd.handle, _ptr(rect), s.ptrs(d_blk), int(flags), int(time_modified), d_image.ptr,
+                  cap, d_bytes.ptr, d_fst.ptr, d_idx.ptr, d_st.ptr, d_used.ptr)
+            n_bytes, fst = int(d_bytes.download(np.uint64, 1)[0]), int(d_fst.download(np.int32, 1)[0])
+            image = d_image.download(np.uint8, cap + 64)
+            idx, status = d_idx.download(np.int32, nt), d_st.download(np.int32, nt)
+            used = d_used.download(np.uint8, self.n_elems * nt).reshape(self.n_elems, nt)
+        if raw:
+            return fst, n_bytes, image.tobytes(), idx, status, used
+        check(fst, "gf_file_update_block_elems_dev")
+        return image[:n_bytes].tobytes(), idx, status, used
+
+    def update_image_host(self, ctx, upd, rect, blocks, time_modified, flags=0, image_cap=None, return_code=False):
+        """gf_file_update_block_elems: blocks (per element [n_rows, n_cols]: int32 / int16 / float32, an "icf" element's float
+        VALUES) stored into rect = (row0, col0, n_rows, n_cols) of the image upd was begun on, in host memory, any codec list ->
+        (image bytes, tile indices, status, codec used); a negative per-tile status raises unless return_code is set: then (the
+        call's return value, the size the image has or needs) come first."""
+        image0, rect, nt, shape = self._read_args(rect, upd.image)
+        blocks = [np.ascontiguousarray(b, dt).reshape(shape) for b, dt in zip(blocks, self._dtypes)]
+        assert len(blocks) == self.n_elems
+        cap = upd.plan(rect)[0] if image_cap is None else int(image_cap)
+        image = np.full(max(cap, 1), 0xA5, np.uint8)
+        image[:min(cap, image0.size)] = image0[:min(cap, image0.size)]
+        idx, status = np.full(nt, -1, np.int32), np.full(nt, 0x7f7f7f7f, np.int32)
+        used = np.zeros((self.n_elems, nt), np.uint8)
+        need = C.c_uint64()
+        rc = lib().gf_file_update_block_elems(ctx.handle, upd.handle, _ptr(rect), _ptrs(blocks), int(flags), int(time_modified), _ptr(image), cap,
+                                              C.byref(need), _ptr(idx), _ptr(status), _ptr(used))
+        n = min(need.value, cap) if rc != _lib.ERR_CAPACITY else min(image0.size, cap)
+        if return_code:
+            return rc, need.value, image[:n].tobytes(), idx, status, used
+        check(rc, "gf_file_update_block_elems")
+        return image[:n].tobytes(), idx, status, used
+
     def close(self):
         if self._h:
             lib().gf_file_close(self._h)
@@ -2063,5 +2166,39 @@ class GvrsFileHip:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class GvrsFileUpdate:
+    """A file opened for an update (gf_file_update_begin): .free_list = [(position, size)] after the three deallocations of
+    opening, plan(rect) = (the largest image an update of the rectangle's tiles can need, the free list's capacity for it)."""
+
+    def __init__(self, file, image):
+        self.file, self.image = file, image
+        self.handle = C.c_void_p()
+        _call("gf_file_update_begin", file._h, _ptr(image), image.size, C.byref(self.handle))
+        n = C.c_size_t()
+        rc = lib().gf_file_update_free_list(self.handle, None, None, 0, C.byref(n))
+        if rc != _lib.ERR_CAPACITY:
+            check(rc, "gf_file_update_free_list")
+        pos, size = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.uint64)
+        _call("gf_file_update_free_list", self.handle, _ptr(pos), _ptr(size), n.value, C.byref(n))
+        self.free_list = [(int(p), int(z)) for p, z in zip(pos[:n.value], size[:n.value])]
+
+    def plan(self, rect=None):
+        r = None if rect is None else np.ascontiguousarray(rect, np.int32)
+        most, cap = C.c_uint64(), C.c_uint64()
+        _call("gf_file_update_plan", self.handle, None if r is None else _ptr(r), C.byref(most), C.byref(cap))
+        return most.value, cap.value
+
+    def end(self):
+        if self.handle:
+            lib().gf_file_update_end(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.end()
         except Exception:
             pass

@@ -93,7 +93,7 @@ struct BwMeta {
 // the lock and has checked the arguments).  With old records it synchronises the stream once (the records driver does).
 gf_status blockCutDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
                       const GfBlockCutElem *cut, const void *const *dBlocks, size_t nOld, const uint8_t *dOldBlob, size_t oldBytes,
-                      const uint64_t *dOldOffsets, int verifyOld, int32_t *dTileIndices, const void **dTiles)
+                      const uint64_t *dOldOffsets, int verifyOld, int32_t *dTileIndices, const void **dTiles, const uint64_t *dOldEnds = nullptr)
 {
     GF_HIP(hipSetDevice(c->device));
     const hipStream_t st = streamOf(c, stream);
@@ -132,7 +132,7 @@ gf_status blockCutDev(gf_context *c, void *stream, const int *codecs, int nCodec
         }
         GF_HIP(hipMemsetAsync(dOldIdx, 0xff, nOld * 4, st));                    // (the driver leaves a failed record's entry alone: -1 places nothing)
         s = recordsDecodeDev(c, stream, codecs, nCodecs, asInt, nElems, g.nRowsTile, g.nColsTile, nOld, dOldBlob, oldBytes, dOldOffsets, nullptr,
-                             verifyOld, dOldIdx, dOld, dOldStatus);
+                             verifyOld, dOldIdx, dOld, dOldStatus, dOldEnds);
         if (s != GF_OK) return s;
         GF_HIP(hipMemsetAsync(c->dBlockSlots.p, 0xff, nOut * 4, st));
         GfBlockSlotsArgs p{};
@@ -159,15 +159,16 @@ gf_status blockCutDev(gf_context *c, void *stream, const int *codecs, int nCodec
 }  // namespace
 
 // blocks in device memory -> records in device memory: the cut, then the record writer with the cut's verdict as its pre-status (no
-// lock taken, no argument checked: its callers hold the context's lock)
+// lock taken, no argument checked: its callers hold the context's lock).  dOldEnds (may be null): an explicit end per old record, as the
+// records driver takes it: the old records of a file image, where they lie (gvrs_api_file_update.hip)
 gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
                         const GfBlockCutElem *cut, const void *const *dBlocks, size_t nOld, const uint8_t *dOldBlob, size_t oldBlobBytes,
                         const uint64_t *dOldOffsets, int verifyOldChecksum, int checksumEnabled, uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets,
-                        int32_t *dTileIndices, uint8_t *dCodecUsed, int32_t *dStatus)
+                        int32_t *dTileIndices, uint8_t *dCodecUsed, int32_t *dStatus, const uint64_t *dOldEnds)
 {
     const void *dTiles[GF_MAX_ELEMS];
     const gf_status s = blockCutDev(c, stream, codecs, nCodecs, elems, nElems, g, cut, dBlocks, nOld, dOldBlob, oldBlobBytes, dOldOffsets,
-                                    verifyOldChecksum, dTileIndices, dTiles);
+                                    verifyOldChecksum, dTileIndices, dTiles, dOldEnds);
     if (s != GF_OK) return s;
     const size_t nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
     const BwMeta m(nOut);

@@ -156,6 +156,8 @@ struct gf_context {
     DevBuf dFileLoc{this};                      // file images (gvrs_api_file.hip): the extents and verdicts of the rectangle's tiles
     DevBuf dFileWrite{this};                    // file images written (gvrs_api_file_write.hip): the kernels' state, the records' offsets, the
                                                 // metadata directory on its way to its place, the tile directory's chunk checksums
+    DevBuf dFileUpdateBlob{this};               // ... the records of a rectangle on their way into the image, and their offsets
+    DevBuf dFileUpdate{this};                   // file images updated (gvrs_api_file_update.hip): state, positions, the free list, the old entries
     DevBuf dTabBlocks{this};                    // ... the composed read's blocks (gf_block_read_tabulated_symbols_elems[_dev])
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
     // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
@@ -338,7 +340,7 @@ gf_status blockWriteArgs(const gf_context *c, const int *codecs, int nCodecs, co
 gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCodecs, const gf_elem_spec *elems, int nElems, const GfBlockGeom &g,
                         const GfBlockCutElem *cut, const void *const *dBlocks, size_t nOld, const uint8_t *dOldBlob, size_t oldBlobBytes,
                         const uint64_t *dOldOffsets, int verifyOldChecksum, int checksumEnabled, uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets,
-                        int32_t *dTileIndices, uint8_t *dCodecUsed, int32_t *dStatus);
+                        int32_t *dTileIndices, uint8_t *dCodecUsed, int32_t *dStatus, const uint64_t *dOldEnds = nullptr);
 // gvrs_api_interp.hip: what the host can check of an interpolation spec (fills g)
 gf_status interpSpecArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, GfInterpGeom &g);
 // gvrs_api_records.hip

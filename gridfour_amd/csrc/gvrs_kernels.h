@@ -624,6 +624,45 @@ struct GfFileFinishArgs {
 // the four kernels, in order; front: null, or the (firstRecordPos - 16 + metaDirBytes) bytes that travel as arguments
 hipError_t gf_launch_file_write(const GfFileWriteArgs &a, const uint8_t *front, hipStream_t stream);
 
+// A file image UPDATED IN PLACE (gvrs_file_update.hip; driven by gvrs_api_file_update.hip): records in device memory placed into an
+// image that holds the old file.  k_update_snapshot copies the old directory's entries aside, k_update_alloc (one wave) runs the
+// allocator of gvrs_file_update.h over the records in order and the close sequence's three allocations and writes NOTHING into
+// the image; every kernel behind it reads its verdict and writes only when it is GF_K_OK.
+struct GfFileUpdateState {     // k_update_alloc's result
+    int32_t verdict;           // GF_K_OK, GF_K_ERR_CAPACITY (total = the size needed) or what refused the call (total 0)
+    uint32_t extended, row0, col0, nRows, nCols;   // the new directory
+    uint32_t nFinal, hasFreeDir;                   // the final list's nodes; the file gets a free-space directory
+    uint64_t total, metaDirAt, tileDirAt, tileDirSize, freeDirAt, freeDirSize;   // record positions (not content positions)
+};
+constexpr uint64_t GF_UPDATE_UNTOUCHED = ~0ull;   // recPos of a record that changes nothing
+constexpr uint32_t GF_UPDATE_LDS_NODES = 2048;    // a list of up to this capacity lives in LDS (32 KiB), a larger one in scratch
+struct GfFileUpdateArgs {
+    uint8_t *image;            // 8-byte aligned; the old image in its first oldBytes bytes
+    uint64_t imageCap, oldBytes, contentPos;
+    uint64_t entriesPos;       // the old tile directory: its entries and rectangle
+    int32_t oldExtended, dirRow0, dirCol0, dirNRows, dirNCols;
+    int32_t nColsOfTiles, nTilesGrid;
+    int32_t checksums, compression, forceExtended;
+    int64_t timeModified;
+    const uint8_t *blob;       // 8-byte aligned
+    const uint64_t *offsets;   // nRecords + 1
+    const int32_t *tiles, *status;   // status may be null
+    int32_t *tileStatus;       // may be null; else (the block form) a refused old record gives its tile that status and the tile stays
+    uint64_t nRecords, blobBytes;
+    GfFileUpdateState *state;
+    uint64_t *recPos;          // nRecords: the content position a record got, 0 for a tile freed, GF_UPDATE_UNTOUCHED
+    uint64_t *listPos, *listSize, *listPrefix;   // listCap (+ 1 for the prefix sums of the final sizes); the opened list on entry
+    uint32_t listCap, nOpened;
+    uint64_t *grid;            // nTilesGrid: the old entry of every tile of the grid, then patched with recPos
+    uint32_t *seen;            // nTilesGrid, zeroed: how many records name a tile
+    const uint8_t *metaDir;    // the old metadata directory's record (8-byte aligned), metaDirBytes (a multiple of 8, may be 0)
+    uint32_t metaDirBytes;
+    uint32_t *chunkCrc;        // one word per GF_FILE_CRC_CHUNK bytes of the largest directory the grid can give
+    uint64_t *imageBytes;      // out
+    int32_t *fileStatus;       // out
+};
+hipError_t gf_launch_file_update(const GfFileUpdateArgs &a, hipStream_t stream);
+
 // A block WRITTEN (gvrs_blocks_write.hip; driven by gvrs_api_blocks_write.hip): the rectangle's cells of every element cut into the
 // tiles of the rectangle of tiles in the type the record writer takes (k_block_cut_elems: TileElement*.setValue with its range
 // checks, RasterTile.hasValidData), and the per-tile verdict the record writer receives as its pre-status (k_block_write_verdict).

@@ -1315,8 +1315,8 @@ gf_status gf_synth_dem_style_dev(gf_context *ctx, void *stream, uint64_t seed, i
  *   gf_file_read_block_elems: the same for an image, blocks, statuses and present flags in HOST memory: the rectangle's tiles are
  *   looked up in the host image and only their records are staged, end to end, into the context's staging buffer -- never the
  *   whole image -- and go through the contiguous path of gf_block_read_elems.
- * Not here: versions <= 1.03, updating files (writing a new one: below), the contents of the metadata and free-space directories
- * (their positions are reported), the tile cache.                                                                                                */
+ * Not here: versions <= 1.03, the contents of the metadata directory (its position is reported; writing a new file and updating
+ * one: below), the tile cache.                                                                                                */
 #define GF_CODEC_UNKNOWN (-1)   /* an id the library has no decoder for: reported, never accepted by a call */
 typedef struct gf_file gf_file;
 typedef struct gf_file_info {
@@ -1406,7 +1406,7 @@ gf_status gf_file_read_block_elems(gf_context *ctx, const gf_file *f, const uint
  *   gf_block_write_elems_dev refuse, an unaligned d_image, NULL d_image_bytes / d_file_status.
  *   gf_file_write_block_elems: the same for host memory and any codec list: gf_block_write_elems, then gf_file_assemble in row-major
  *   order; for a list the device form takes, the same bytes.  Returns the first negative per-tile status, else the assembler's.
- * Not here: updating an existing file (old records, the free-space list), versions <= 1.03, the tile cache.                     */
+ * Not here: updating an existing file (below), versions <= 1.03, the tile cache.                                                */
 #define GF_FILE_DIR_EXTENDED 1  /* flags: the tile directory in its extended form whatever the positions */
 typedef struct gf_file_elem_facts {
     const char *name, *label, *description, *unit;
@@ -1443,6 +1443,106 @@ gf_status gf_file_write_block_elems_dev(gf_context *ctx, const gf_file_facts *fa
 gf_status gf_file_write_block_elems(gf_context *ctx, const gf_file_facts *facts, const gf_file_metadata *metadata, int n_metadata,
                                     const gf_rect *rect, const void *const *blocks, int flags, uint8_t *image, size_t image_cap,
                                     uint64_t *image_bytes, int32_t *tile_indices, int32_t *status, uint8_t *codec_used);
+
+/* ---- GVRS files UPDATED IN PLACE: the record allocator, the free-space list, the three directories ---------------------------------
+ * (gvrs/GvrsFile.java:443-483 opening for writing, :584-616 close; gvrs/RecordManager.java:218-312 fileSpaceAlloc, :314-384
+ * fileSpaceDealloc, :386-490 writeTile, :864-883 writeTileDirectory, :885-903 readFreespaceDirectory, :905-989
+ * writeFreeSpaceDirectory, :991-1017 writeMetadataDirectory, :451-454 the sticky extended form; gvrs/TileDirectory.java:121-191)
+ * What GvrsFile(file, "rw") ... close() does: tile records stored into a file that exists.  The finished image is a pure function
+ * of the old image, the records, their order and the modification time, and is the reference's byte for byte: every byte lies in
+ * a live record or in a free node of the final list.
+ *   THE ALLOCATOR.  A record of content c has sizeToStore = multipleOf8(c + 12) bytes.  fileSpaceAlloc takes the FIRST node in
+ *   order of position whose size is exactly sizeToStore or at least sizeToStore + 32; a larger node is split and its surplus
+ *   listed at position + sizeToStore.  With no such node, a last node that ends at the file's end and is smaller than sizeToStore
+ *   is overwritten and the file extended; otherwise the record is appended.  fileSpaceDealloc lists the freed record by position:
+ *   merged with the prior node where they touch (and then with the next, if they now touch), else with the next, else inserted.
+ *   gf_file_update_begin needs no device and no context.  It takes the image gf_file_open opened, reads the free-space directory
+ *   (record type 3: int32 count, per node int64 position and int32 size), the size words of the three directory records and the
+ *   metadata directory record, keeps copies and holds no pointer into the image, and then frees the free-space directory record,
+ *   the metadata directory record and the tile directory record in its own list, in that order, as opening for writing does.
+ *   Judged before trusted: nodes ascend, neither overlap nor touch, positions and sizes are multiples of 8, a size is at least 24
+ *   (NOT MIN_FREE_BLOCK_SIZE, 32: that bounds only the surplus of a split; a freed record of any size is listed, and the smallest
+ *   record that can be freed is a tile record of 24 bytes), a node lies in [content_pos, image_bytes) and its own head in the
+ *   image states the same size and type 0; the directory records have types 3 / 4 / 5, sizes that are multiples of 8 and end
+ *   inside the image, and overlap no node; the tile directory record holds its entries; the count is one the record can hold;
+ *   image_bytes is a multiple of 8.  GF_ERR_FORMAT: any of these; GF_ERR_BOUNDS: a position or size that reaches to or behind
+ *   image_bytes (a truncated image); GF_ERR_ARG: null pointers, an image whose header record has another size than the opened
+ *   one's.  No byte at or behind image_bytes is read.  A handle serves ONE image state: after an update, open and begin again.
+ *   gf_file_update_free_list: the list after opening, positions[k] and sizes[k] of *n_nodes nodes (GF_ERR_CAPACITY with *n_nodes
+ *   set when cap is smaller).
+ *   gf_file_update_plan (rect NULL: the whole grid): *max_image_bytes = the old size + every tile the rectangle touches at
+ *   gf_tile_record_max_bytes_elems + the three directories at their largest; *free_list_capacity = the nodes after opening + the
+ *   tiles written + 3, the room a call's list needs.  Either pointer may be NULL.
+ *   gf_file_update_assemble needs no device and no context.  image holds the old image in its first bytes and has image_cap
+ *   bytes; records as gf_block_write_elems hands them out, applied IN THE CALLER'S ORDER as writeTile applies them: a non-empty
+ *   record frees the tile's old record FIRST and is then allocated (in a file without compression, n_codecs == 0, an old record
+ *   is rewritten at its place and nothing is allocated; the new record must have its size); length 0 with status GF_DECLINED
+ *   (or status == NULL) frees the old record and sets the entry 0; a negative status leaves the tile untouched, record and entry.
+ *   An old record is found as gf_file_tile_position finds it and its head judged (type 2, a size >= 24 that is a multiple of 8
+ *   inside the image) before it is freed: else that verdict is returned.  Then close: time_modified, opened-for-writing 0, the
+ *   metadata directory (the old record, allocated anew: no metadata is added or moved, so its bytes are the old ones), the tile
+ *   directory over the bounding rectangle of the OLD rectangle and every tile that got a position (it only grows; an old extended
+ *   directory stays extended, flags GF_FILE_DIR_EXTENDED or a content position above 1 << 35 make it so), the free-space directory
+ *   (allocated for the count of nodes; counted AGAIN behind the allocation, which may have consumed one: the record is then 12
+ *   bytes roomier; no node before the allocation: no record, the word is 0), every remaining node as [size][0 0 0 0][zeros]
+ *   [CRC-32C of its first 8 bytes | 0], the three header words and the header checksum.  ALL OR NOTHING: *image_bytes = the size
+ *   the image has or needs; with image_cap smaller it returns GF_ERR_CAPACITY and not one byte of the image is changed, as for
+ *   every other refusal.  GF_ERR_ARG: what gf_file_assemble refuses of records and indices, two records for one tile, image_cap
+ *   below the old size, blob inside image.  GF_ERR_UNSUPPORTED: a directory or a node of 2^31 bytes or more.
+ *   DEVIATION from the reference: with compression enabled, an old record, and a new record that is not smaller than the standard
+ *   form, writeTile has freed the old record and zeroed its entry (:429-432) and then writes the standard form into the freed
+ *   block (:476-480) without restoring the entry: the tile is lost.  Here such a record is freed and allocated like any other.
+ *   gf_file_update_records_dev: the assembler's device counterpart.  The records lie in device memory (d_blob, d_offsets
+ *   [n_records + 1], d_tile_indices, d_status or NULL) and are placed into d_image (8-byte aligned, image_cap bytes, the old
+ *   image in its first bytes).  Runs on the context's stream and ONLY ENQUEUES; the one wait on the host, as in
+ *   gf_file_write_block_elems_dev with a long front: an EARLIER call's copies must have left the context's page-locked buffer, through
+ *   which the opened list and the metadata directory travel (an event behind them).  k_update_alloc, one wave,
+ *   runs the serial rules above over a position-sorted list (first fit by ballot over 64 nodes a turn, insert and delete as
+ *   wave-wide shifts), in LDS where list_capacity nodes fit and in the context's scratch otherwise (list_capacity 0: the plan's
+ *   number; a caller may pass a larger one), and writes nothing into the image; k_update_snapshot has copied the old directory
+ *   entries aside before.  When the size needed exceeds image_cap, or an old record is refused, every later kernel sees the verdict
+ *   and writes nothing: *d_file_status = GF_ERR_CAPACITY and *d_image_bytes = the size needed (or the verdict and 0), the image byte for
+ *   byte as it was.  Otherwise k_update_copy lays the records in 8-byte words, k_update_dir the tile directory over the new
+ *   rectangle, k_update_dir_crc its chunked checksum, k_update_fill every free node (a lane per 8-byte word across all nodes) and
+ *   k_update_finish the metadata directory, the free-space directory and the header.  GF_ERR_ARG as the assembler, as far as the
+ *   host can tell (device contents are judged on the device and reported in *d_file_status), an unaligned d_image.
+ *   gf_file_update_block_elems_dev: a rectangle of the raster (d_blocks, rect, the types and rules of gf_block_write_elems_dev, the
+ *   default ranges) into an image in DEVICE memory; tiles are written in row-major order of the rectangle's tiles; d_tile_indices,
+ *   d_status and d_codec_used (may be NULL) are the block write's.  A rectangle whose four sides lie on tile seams (a side at a grid
+ *   edge that cuts a tile is none: such a tile keeps its old cells beyond the grid) decodes nothing and the call only enqueues, as the records
+ *   form.  Otherwise k_file_locate finds the old records of the rectangle's tiles in the image and the block write's merge takes
+ *   them where they lie, an explicit end per record (a tile without a record, or with a refused entry, is an empty extent and a new
+ *   tile to the merge): the call then synchronises once, as gf_block_write_elems_dev with old records does.  The records are
+ *   written to a buffer of the context and laid by k_update_copy.  k_update_alloc judges the head of EVERY old record itself before
+ *   it frees it (type 2, a size >= 24 that is a multiple of 8 inside the image): a wholly covered tile with a damaged body is
+ *   overwritten; a tile whose entry or head is refused gets that status in d_status and stays, record and entry; a partly covered
+ *   tile whose old record fails keeps the merge's status and stays.  The codec list must be one the device record writer takes
+ *   (GF_ERR_UNSUPPORTED otherwise, from the arguments alone).  *d_file_status and *d_image_bytes as the records form.
+ *   gf_file_update_block_elems: a rectangle of the raster into an image in HOST memory, any codec list: the old records of the
+ *   rectangle's tiles are looked up and their heads judged on the host (a refused one gives its tile that status, and the tile
+ *   stays), gf_block_write_elems merges the old cells of partly covered tiles, then gf_file_update_assemble in row-major order of
+ *   the rectangle's tiles.  Cells are checked against the default ranges (the handle does not keep the header's).  Returns the
+ *   assembler's status when it refuses the update (GF_ERR_CAPACITY: *image_bytes = the need), else the first negative per-tile status.
+ * Not here: adding, changing or removing metadata, versions <= 1.03, the tile cache and its
+ * flush order, truncating a file whose last record became free (the reference does not either).                                 */
+typedef struct gf_file_update gf_file_update;
+gf_status gf_file_update_begin(const gf_file *f, const uint8_t *image, size_t image_bytes, gf_file_update **out);   /* host bytes */
+void      gf_file_update_end(gf_file_update *u);
+gf_status gf_file_update_free_list(const gf_file_update *u, uint64_t *positions, uint64_t *sizes, size_t cap, size_t *n_nodes);
+gf_status gf_file_update_plan(const gf_file_update *u, const gf_rect *rect, uint64_t *max_image_bytes, uint64_t *free_list_capacity);
+gf_status gf_file_update_assemble(const gf_file_update *u, uint8_t *image, size_t image_cap, const uint8_t *blob,
+                                  const uint64_t *offsets, const int32_t *tile_indices, const int32_t *status, size_t n_records,
+                                  int64_t time_modified, int flags, uint64_t *image_bytes);
+gf_status gf_file_update_records_dev(gf_context *ctx, const gf_file_update *u, uint8_t *d_image, size_t image_cap,
+                                     const uint8_t *d_blob, const uint64_t *d_offsets, const int32_t *d_tile_indices,
+                                     const int32_t *d_status, size_t n_records, size_t blob_bytes, int64_t time_modified, int flags,
+                                     size_t list_capacity, uint64_t *d_image_bytes, int32_t *d_file_status);
+gf_status gf_file_update_block_elems_dev(gf_context *ctx, const gf_file_update *u, const gf_rect *rect, const void *const *d_blocks,
+                                         int flags, int64_t time_modified, uint8_t *d_image, size_t image_cap, uint64_t *d_image_bytes,
+                                         int32_t *d_file_status, int32_t *d_tile_indices, int32_t *d_status, uint8_t *d_codec_used);
+gf_status gf_file_update_block_elems(gf_context *ctx, const gf_file_update *u, const gf_rect *rect, const void *const *blocks,
+                                     int flags, int64_t time_modified, uint8_t *image, size_t image_cap, uint64_t *image_bytes,
+                                     int32_t *tile_indices, int32_t *status, uint8_t *codec_used);
 
 /* ---- thin device-memory helpers so that non-HIP hosts (JNI, ctypes) can
  *      stage data without linking the HIP runtime themselves --------------- */
