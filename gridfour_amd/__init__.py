@@ -8,12 +8,12 @@ the reference interface used by tests, bench.py and Python callers.
 """
 from ._lib import (GvrsHipError, OK, DECLINED, OVERFLOW, ERR_FORMAT, ERR_BOUNDS, ERR_CAPACITY,  # noqa: F401
                    ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, PM_ALL, lib, lib_path)
-from .codec import (CodecMasterHip, STANDARD_CODEC_LIST, CodecHuffmanHip, CodecDeflateHip, CodecCanonHuffmanHip, CodecFloatHip, LsCodecHip, LsCodec08Hip, GvrsFileHip, GvrsFileFacts, GvrsFileUpdate, FILE_DIR_EXTENDED, GvrsHipContext, DeviceBuffer, DeviceTileBatch, GpuTimer,  # noqa: F401
+from .codec import (CodecMasterHip, STANDARD_CODEC_LIST, CodecHuffmanHip, CodecDeflateHip, CodecCanonHuffmanHip, CodecFloatHip, LsCodecHip, LsCodec08Hip, GvrsFileHip, GvrsFileFacts, GvrsFileUpdate, GvrsInspection, INSPECT_STOPS, FILE_DIR_EXTENDED, GvrsHipContext, DeviceBuffer, DeviceTileBatch, GpuTimer,  # noqa: F401
                     INT4_NULL_CODE, CODEC_STATS_DTYPE, CANON_STATS_DTYPE, interp_spec, INTERP_VALUE, INTERP_FIRST, INTERP_SECOND, ELEM_TYPES,
                     Palette, palette_records, palette_spec, render_light, PALETTE_RGB, PALETTE_HSV, PALETTE_MAX_RECORDS, RENDER_UNLIMITED, RENDER_Z,
                     IMAGE_RGB, IMAGE_YCOCG, IMAGE_MODELS, CODEC_NONE, CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_CANON_HUFFMAN, CODEC_LSOP12,
                     CODEC_LSOP08, CODEC_UNKNOWN)
 from .sharding import shard_range, GvrsHipMulti, PinnedArray, TileReadAhead  # noqa: F401
 
-__all__ = ["CodecHuffmanHip", "CodecCanonHuffmanHip", "CodecDeflateHip", "CodecFloatHip", "LsCodecHip", "LsCodec08Hip", "GvrsFileHip", "GvrsFileFacts", "GvrsFileUpdate", "GvrsHipContext", "GvrsHipError", "INT4_NULL_CODE", "lib", "lib_path",
+__all__ = ["CodecHuffmanHip", "CodecCanonHuffmanHip", "CodecDeflateHip", "CodecFloatHip", "LsCodecHip", "LsCodec08Hip", "GvrsFileHip", "GvrsFileFacts", "GvrsFileUpdate", "GvrsInspection", "GvrsHipContext", "GvrsHipError", "INT4_NULL_CODE", "lib", "lib_path",
            "shard_range", "GvrsHipMulti", "PinnedArray", "TileReadAhead", "Palette", "render_light"]

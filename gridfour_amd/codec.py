@@ -53,6 +53,14 @@ _FILE_INFO = np.dtype([("version", np.int32), ("subversion", np.int32), ("checks
                        ("dir_col0", np.int32), ("dir_n_rows", np.int32), ("dir_n_cols", np.int32), ("dir_entries_pos", np.uint64),
                        ("x0", np.float64), ("y0", np.float64), ("x1", np.float64), ("y1", np.float64), ("cell_size_x", np.float64),
                        ("cell_size_y", np.float64), ("m2r", np.float64, 6), ("r2m", np.float64, 6)], align=True)         # gf_file_info
+_FILE_RECORD = np.dtype([("pos", np.uint64), ("size", np.uint32), ("type", np.int32), ("tile_index", np.int32), ("checksum", np.int32)],
+                        align=True)                                                       # gf_file_record
+_FILE_INSPECT_REPORT = np.dtype([("status", np.int32), ("failed", np.int32), ("complete", np.int32), ("stop", np.int32),
+                                 ("bad_tile_index", np.int32), ("invalid_record_size", np.int32), ("tile_dir_located", np.int32),
+                                 ("tile_dir_passed", np.int32), ("termination_pos", np.uint64), ("n_records", np.uint64),
+                                 ("n_by_type", np.uint64, 7), ("n_checksum_failures", np.uint64), ("n_bad_tiles", np.uint64)],
+                                align=True)                                               # gf_file_inspect_report
+INSPECT_STOPS = ("end", "bad_tile_index", "tile_too_large", "two_checksum_failures", "bad_record_type", "bad_record_size", "truncated")
 
 _FILE_ELEM_FACTS = np.dtype([("name", np.uint64), ("label", np.uint64), ("description", np.uint64), ("unit", np.uint64), ("continuous", np.int32),
                              ("has_range", np.int32), ("range", _ELEM_RANGE)], align=True)                             # gf_file_elem_facts
@@ -2158,6 +2166,63 @@ class GvrsFileHip:
         check(rc, "gf_file_update_block_elems")
         return image[:n].tobytes(), idx, status, used
 
+    # ---- files inspected (gf_file_inspect[_dev]) ----
+    def inspect_plan(self, image_bytes=None):
+        """gf_file_inspect_plan -> (segment bytes, CRC chunk bytes, the default room for records) of the device form"""
+        seg, chunk, most = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _call("gf_file_inspect_plan", self._h, self.image.size if image_bytes is None else int(image_bytes), C.byref(seg), C.byref(chunk), C.byref(most))
+        return seg.value, chunk.value, most.value
+
+    def inspect(self, image=None, bad_cap=None, records_cap=None, return_code=False):
+        """gf_file_inspect: GvrsInspector's walk over the image in host memory -> a GvrsInspection.  image: other bytes than the
+        file's own.  bad_cap / records_cap: the room given (default: what the image needs, found by a first call without
+        records); return_code: (status, GvrsInspection) and GF_ERR_CAPACITY does not raise."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        report = np.zeros(1, _FILE_INSPECT_REPORT)
+        if bad_cap is None or records_cap is None:
+            _call("gf_file_inspect", self._h, _ptr(image), image.size, _ptr(report), None, 0, None, 0)
+            bad_cap = int(report[0]["n_bad_tiles"]) if bad_cap is None else bad_cap
+            records_cap = int(report[0]["n_records"]) if records_cap is None else records_cap
+        bad = np.full(int(bad_cap) + 4, 0x7f7f7f7f, np.int32)
+        records = np.full((int(records_cap) + 2) * _FILE_RECORD.itemsize, 0x7f, np.uint8).view(_FILE_RECORD)
+        rc = lib().gf_file_inspect(self._h, _ptr(image), image.size, _ptr(report), _ptr(bad), int(bad_cap), _ptr(records), int(records_cap))
+        out = GvrsInspection(report[0], bad, int(bad_cap), records, int(records_cap))
+        if return_code:
+            return rc, out
+        check(rc, "gf_file_inspect")
+        return out
+
+    def inspect_dev(self, ctx, image=None, max_records=None, bad_cap=None, with_records=True, return_code=False):
+        """gf_file_inspect_dev: the same in device memory.  Uploads the image, calls, synchronises, downloads -> a GvrsInspection.
+        max_records: the room of the record list (default: the plan's); on GF_ERR_CAPACITY the call is made once more with the
+        count the report names, unless return_code: then (the report's status, GvrsInspection) come back as they are.
+        bad_cap: the room for bad tiles (default: the grid's tiles)."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        room = self.inspect_plan(image.size)[2] if max_records is None else int(max_records)
+        room = max(room, 1)
+        n_tiles = -(-self.grid[0] // self.grid[2]) * -(-self.grid[1] // self.grid[3])
+        bad_cap = n_tiles if bad_cap is None else int(bad_cap)
+        for attempt in range(2):
+            with _DeviceScope(ctx) as s:
+                d_image = s.upload(image, slack=32, fill=0)
+                d_report = s.alloc(_FILE_INSPECT_REPORT.itemsize + 16, fill=0x7f)
+                d_bad = s.alloc((bad_cap + 4) * 4, fill=0x7f)
+                d_rec = s.alloc((room + 2) * _FILE_RECORD.itemsize, fill=0x7f) if with_records else None
+                s.run("gf_file_inspect_dev", ctx.handle, self._h, d_image.ptr, image.size, room, d_report.ptr, d_bad.ptr, bad_cap,
+                      None if d_rec is None else d_rec.ptr)
+                report = d_report.download(np.uint8, _FILE_INSPECT_REPORT.itemsize + 16)
+                bad = d_bad.download(np.int32, bad_cap + 4)
+                records = None if d_rec is None else d_rec.download(np.uint8, (room + 2) * _FILE_RECORD.itemsize).view(_FILE_RECORD)
+            assert bytes(report[_FILE_INSPECT_REPORT.itemsize:]) == b"\x7f" * 16, "gf_file_inspect_dev wrote behind its report"
+            out = GvrsInspection(report[:_FILE_INSPECT_REPORT.itemsize].view(_FILE_INSPECT_REPORT)[0], bad, bad_cap, records, room)
+            if return_code or out.status != _lib.ERR_CAPACITY or attempt == 1:
+                break
+            room = out.n_records
+        if return_code:
+            return out.status, out
+        check(out.status, "gf_file_inspect_dev")
+        return out
+
     def close(self):
         if self._h:
             lib().gf_file_close(self._h)
@@ -2168,6 +2233,36 @@ class GvrsFileHip:
             self.close()
         except Exception:
             pass
+
+
+class GvrsInspection:
+    """What gf_file_inspect[_dev] answered: the report's fields as attributes (status, failed, complete, stop, stop_name,
+    bad_tile_index, invalid_record_size, tile_dir_located, tile_dir_passed, termination_pos, n_records, n_by_type,
+    n_checksum_failures, n_bad_tiles), .bad_tiles (the first bad_cap of them, in file order), .records ([(pos, size, type, tile
+    index, checksum)], None where none were asked for or the room was too small) and .guards_intact: the entries behind
+    bad_cap and records_cap are as they were."""
+
+    def __init__(self, report, bad, bad_cap, records, records_cap):
+        for k in _FILE_INSPECT_REPORT.names:
+            v = report[k]
+            setattr(self, k, [int(x) for x in v] if v.ndim else int(v))
+        self.stop_name = INSPECT_STOPS[self.stop] if 0 <= self.stop < len(INSPECT_STOPS) else None
+        self.passed = self.status == 0 and not self.failed
+        n_bad = min(self.n_bad_tiles, bad_cap)
+        self.bad_tiles = [int(t) for t in bad[:n_bad]]
+        guard = np.full(1, 0x7f7f7f7f, np.int32)[0]
+        self.guards_intact = bool((bad[n_bad:] == guard).all())
+        self.records = self.records_raw = None
+        if records is not None:
+            n = min(self.n_records, records_cap)                  # (the host form fills the room it has)
+            raw = records.view(np.uint8).reshape(-1, _FILE_RECORD.itemsize)
+            self.records_raw = raw
+            self.guards_intact = self.guards_intact and bool((raw[n:] == 0x7f).all())
+            if self.status == 0 and self.n_records <= records_cap:
+                self.records = [tuple(int(records[k][f]) for f in _FILE_RECORD.names) for k in range(n)]
+
+    def report(self):
+        return {k: getattr(self, k) for k in _FILE_INSPECT_REPORT.names}
 
 
 class GvrsFileUpdate:

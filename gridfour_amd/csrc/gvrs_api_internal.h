@@ -158,7 +158,8 @@ struct gf_context {
                                                 // metadata directory on its way to its place, the tile directory's chunk checksums
     DevBuf dFileUpdateBlob{this};               // ... the records of a rectangle on their way into the image, and their offsets
     DevBuf dFileUpdate{this};                   // file images updated (gvrs_api_file_update.hip): state, positions, the free list, the old entries
-    DevBuf dTabBlocks{this};                    // ... the composed read's blocks (gf_block_read_tabulated_symbols_elems[_dev])
+    DevBuf dFileInspect{this};                  // file images inspected (gvrs_api_file_inspect.hip): state, the segments' anchors and walks, the record list
+    DevBuf dTabBlocks{this};                   // ... the composed read's blocks (gf_block_read_tabulated_symbols_elems[_dev])
     // Every entry point that takes the context holds this lock for its duration (GF_CTX_LOCK): the reference calls ONE decoder
     // instance from several threads (gvrs/RasterTileCache.java:418-421, TileDecompressionAssistant.java:68-73), and a context's
     // scratch buffers, staging slots and recorded graphs are one set.  Recursive: entry points call each other.

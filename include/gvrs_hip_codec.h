@@ -1544,6 +1544,71 @@ gf_status gf_file_update_block_elems(gf_context *ctx, const gf_file_update *u, c
                                      int flags, int64_t time_modified, uint8_t *image, size_t image_cap, uint64_t *image_bytes,
                                      int32_t *tile_indices, int32_t *status, uint8_t *codec_used);
 
+/* ---- GVRS files INSPECTED: every record walked and checksummed, as the file is laid out ----------------------------------------
+ * (gvrs/GvrsInspector.java:213-312 inspectContent, :314-337 testRecordChecksum)
+ * The one reader that goes record by record from the first byte of content to the image's end -- metadata, directories, free
+ * nodes and tile records the directory no longer names included -- and answers whether the image, as a whole, is a file the
+ * reference would accept.  The header has passed: the calls take an opened gf_file (gf_file_open refuses what the inspector's
+ * constructor refuses); image may be other bytes than the ones opened (an updated image), with the same header record size.
+ *   THE WALK: from content_pos, while fewer than image_bytes - 12 bytes lie in front of the position.  At one record, in this
+ *   order: a size word of 0 ends the walk cleanly (complete); a type code outside 0..6 stops it (GF_INSPECT_BAD_RECORD_TYPE); a
+ *   size word below 16 or no multiple of 8 stops it (_BAD_RECORD_SIZE); a tile record (type 2) whose index lies outside the grid's
+ *   tiles stops it (_BAD_TILE_INDEX, bad_tile_index) and one larger than the standard form, (4 + 4 * n_elems + the standard tile
+ *   bytes + 12 + 7) & ~7, is listed as bad and stops it (_TILE_TOO_LARGE, invalid_record_size); a record that ends behind the image
+ *   stops it (_TRUNCATED); and, ONLY WHERE THE SPECIFICATION ENABLES CHECKSUMS, the CRC-32C of the record's first size - 4 bytes
+ *   (a free node, type 0: of its first 8 bytes, whatever its body holds) is compared with its last word: a mismatch fails the file,
+ *   lists a tile, and directly behind another mismatch stops the walk at this record (_TWO_CHECKSUM_FAILURES).  A stop fails the
+ *   file, leaves complete 0 and termination_pos at the record; else termination_pos is where the walk ended.  tile_dir_passed: the
+ *   CRC-32C of the record at the header's tile directory position, taken in every file (0 in a file without checksums, whose
+ *   word is 0), or any tile directory record (type 5) the walk met that matched.
+ *   DEVIATIONS from the reference, where it is undefined: _BAD_RECORD_SIZE (there an exception, a backward walk or one off the
+ *   8-byte grid); _TRUNCATED in both modes (there EOFException with checksums, a walk past the end reported as complete
+ *   without); termination_pos after a bad type code is the record's position (there it stays 16).
+ *   No byte at or behind image_bytes is read.  The report counts the records up to and including the one the walk stopped at;
+ *   bad_tiles is the reference's list, in file order, a tile twice where two of its records fail: the first bad_cap entries are
+ *   written, n_bad_tiles is the true count.
+ *   gf_file_inspect (host bytes; no device, no context): records may be NULL; with records_cap < n_records the call answers
+ *   GF_ERR_CAPACITY (also in status), n_records is the number needed and nothing is written behind the capacity.  GF_ERR_ARG: null
+ *   pointers, image_bytes < content_pos, a header record of another size than the opened one.  GF_ERR_FORMAT: a content_pos that
+ *   is no multiple of 8.
+ *   gf_file_inspect_dev: the image, the report, the list and the records in DEVICE memory; d_image is 8-byte aligned and readable
+ *   to the end of the aligned 16-byte piece that holds its last byte.  Runs on the context's stream, ONLY ENQUEUES and never
+ *   synchronises.  The result equals gf_file_inspect's on the same bytes, field for field.  The walk is cut at ANCHORS: the tile
+ *   directory's entries (judged as gf_file_read_block_elems_dev judges them) and the header's three directory positions give, per
+ *   segment of segment_bytes, the first record start known there; a lane per anchored segment walks to the next anchor.  THE CHAIN
+ *   FROM content_pos IS THE AUTHORITY: a segment's walk counts only if the walk in front of it landed exactly on its anchor, and
+ *   where a link does not close (a damaged size word, an entry that leads into the middle of a record) one lane walks the rest of
+ *   the image from the landing point -- slow and correct, for damaged files only.  Checksums: a wave per record of up to 8 chunks
+ *   of crc_chunk_bytes, a larger record chunk by chunk over many waves.  max_records: the room of the call's record list (0: the
+ *   plan's default_max_records); the list takes every record up to the first structural stop, so with more of them the REPORT
+ *   says status GF_ERR_CAPACITY and n_records = that count, and nothing else of it, the list or the records is valid.
+ *   d_records (may be NULL) has max_records entries.  GF_ERR_ARG as above and an unaligned d_image; GF_ERR_UNSUPPORTED: more than
+ *   2^31 - 2 records of room.
+ *   gf_file_inspect_plan: the device form's numbers for an image of image_bytes (each pointer may be NULL).
+ * Not here: versions <= 1.03, the tile records' payloads (the block reads decode them and report per tile), repairing a file,
+ * GvrsInspector.summarize's text.                                                                                               */
+enum { GF_INSPECT_END = 0, GF_INSPECT_BAD_TILE_INDEX = 1, GF_INSPECT_TILE_TOO_LARGE = 2, GF_INSPECT_TWO_CHECKSUM_FAILURES = 3,
+       GF_INSPECT_BAD_RECORD_TYPE = 4, GF_INSPECT_BAD_RECORD_SIZE = 5, GF_INSPECT_TRUNCATED = 6 };
+typedef struct gf_file_record {      /* one record as the walk met it */
+    uint64_t pos;                    /* of its size word */
+    uint32_t size;  int32_t type;    /* the size word; the type code (0..6 unless the walk stopped at it) */
+    int32_t tile_index;              /* -1 unless type 2 */
+    int32_t checksum;                /* 1 passed, 0 failed, -1 not checked (a file without checksums, a structural stop) */
+} gf_file_record;
+typedef struct gf_file_inspect_report {
+    int32_t status;                  /* GF_OK, or GF_ERR_CAPACITY: only n_records is valid */
+    int32_t failed, complete, stop;  /* stop: GF_INSPECT_* */
+    int32_t bad_tile_index, invalid_record_size, tile_dir_located, tile_dir_passed;
+    uint64_t termination_pos;
+    uint64_t n_records, n_by_type[7], n_checksum_failures, n_bad_tiles;
+} gf_file_inspect_report;
+gf_status gf_file_inspect_plan(const gf_file *f, size_t image_bytes, uint64_t *segment_bytes, uint64_t *crc_chunk_bytes,
+                               uint64_t *default_max_records);
+gf_status gf_file_inspect(const gf_file *f, const uint8_t *image, size_t image_bytes, gf_file_inspect_report *report,
+                          int32_t *bad_tiles, size_t bad_cap, gf_file_record *records, size_t records_cap);
+gf_status gf_file_inspect_dev(gf_context *ctx, const gf_file *f, const uint8_t *d_image, size_t image_bytes, size_t max_records,
+                              gf_file_inspect_report *d_report, int32_t *d_bad_tiles, size_t bad_cap, gf_file_record *d_records);
+
 /* ---- thin device-memory helpers so that non-HIP hosts (JNI, ctypes) can
  *      stage data without linking the HIP runtime themselves --------------- */
 gf_status gf_dev_malloc(gf_context *ctx, size_t bytes, void **d_ptr);
