@@ -70,7 +70,7 @@ gf_status gf_file_tile_position(const gf_file *f, const uint8_t *image, size_t i
     *pos = 0;
     const gf_grid_spec &g = f->p.info.grid;
     const GfFileDir d = gfFileDirOf(f->p.info);
-    const int64_t nTiles = (int64_t)d.nColsOfTiles * (((int64_t)g.n_rows_grid + g.n_rows_tile - 1) / g.n_rows_tile);
+    const int64_t nTiles = gfTilesOfGrid(g).count();
     if (tileIndex < 0 || tileIndex >= nTiles) return GF_ERR_ARG;
     uint32_t size;
     return gfFileLocate(d, image, imageBytes, tileIndex, pos, &size);

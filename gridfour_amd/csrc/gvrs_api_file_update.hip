@@ -78,7 +78,7 @@ static gf_status updateRecordsDev(gf_context *c, const GfFileUpdate &h, uint8_t 
     if (cap < need) return GF_ERR_ARG;
     if (nRecords > 0x7fffffffull || cap > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
     const GfFileDir d = gfFileDirOf(i);
-    const uint64_t nTilesGrid = (uint64_t)d.nColsOfTiles * (uint64_t)(((int64_t)i.grid.n_rows_grid + i.grid.n_rows_tile - 1) / i.grid.n_rows_tile);
+    const uint64_t nTilesGrid = (uint64_t)gfTilesOfGrid(i.grid).count();
     if (gfFileTileDirSize(nTilesGrid, true) > 0x7fffffffull) return GF_ERR_UNSUPPORTED;   // (a record's size is an int32)
     GF_HIP(hipSetDevice(c->device));
     const hipStream_t st = c->stream;

@@ -1,17 +1,14 @@
 // gvrs_api_records.hip -- CRC-32C and the tile records of RecordManager's framing.
 
 #include "gvrs_api_internal.h"
+#include "gvrs_crc32c.h"
 
 extern "C" {
 
 // ------------------------------------------------------------------ tile records (RecordManager framing)
 
-static uint32_t crc32cTable[256];
-static std::once_flag crc32cOnce;
-
-// CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) as util/GridfourCRC32C.java:330-338 applies it.  The host's crc32
-// instruction (SSE 4.2: eight bytes per step) where there is one, the byte-at-a-time table otherwise (round 3: the table loop
-// alone, ~1 byte per cycle over every record of a batch).
+// CRC-32C (Castagnoli) as util/GridfourCRC32C.java:330-338 applies it.  The host's crc32 instruction (SSE 4.2: eight bytes per
+// step) where there is one, the library's own gfCrc32c (gvrs_crc32c.h) otherwise.
 #if defined(__x86_64__)
 #define GF_HOST_HAS_CRC32_INSN 1
 __attribute__((target("sse4.2"))) static uint32_t crc32cHw(const uint8_t *data, size_t n)
@@ -34,16 +31,7 @@ uint32_t gf_crc32c(const uint8_t *data, size_t n)
     static const bool hw = __builtin_cpu_supports("sse4.2");
     if (hw) return crc32cHw(data, n);
 #endif
-    std::call_once(crc32cOnce, []() {
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t x = i;
-            for (int k = 0; k < 8; k++) x = (x >> 1) ^ ((x & 1u) ? 0x82F63B78u : 0u);
-            crc32cTable[i] = x;
-        }
-    });
-    uint32_t crc = 0xffffffffu;
-    for (size_t i = 0; i < n; i++) crc = crc32cTable[(crc ^ data[i]) & 0xffu] ^ (crc >> 8);
-    return crc ^ 0xffffffffu;
+    return gfCrc32c(data, n);
 }
 
 }  // extern "C"

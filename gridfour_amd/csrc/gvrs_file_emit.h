@@ -26,35 +26,13 @@ constexpr uint64_t GF_FILE_MAX_COMPACT_POS = 1ull << 35;         // RecordManage
 enum { GF_FILE_REC_METADATA = 1, GF_FILE_REC_TILE = 2, GF_FILE_REC_METADATA_DIR = 4, GF_FILE_REC_TILE_DIR = 5, GF_FILE_REC_HEADER = 6 };
 constexpr uint64_t GF_FILE_POS_METADATA_DIR = 64, GF_FILE_POS_TILE_DIR = 80;
 
-// ---- CRC-32C folded: crc(A || B) from crc(A), crc(B) and |B| (the arithmetic of zlib's crc32_combine in GF(2)[x] modulo the
-// reflected Castagnoli polynomial; gvrs_crc32c.h has the device's twin) ----
-inline uint32_t gfCrcMulmod(uint32_t a, uint32_t b)               // a * b mod P, operands and result bit-reflected
-{
-    uint32_t p = 0;
-    for (uint32_t m = 0x80000000u; m; m >>= 1) {
-        p ^= (a & m) ? b : 0u;
-        b = (b & 1u) ? (b >> 1) ^ 0x82F63B78u : b >> 1;
-    }
-    return p;
-}
-inline uint32_t gfCrcXpow8n(uint64_t nBytes)                      // x^(8 nBytes) mod P
-{
-    uint32_t p = 0x80000000u, sq = 0x00800000u;                   // x^0; x^8
-    for (uint64_t n = nBytes; n; n >>= 1) {
-        if (n & 1u) p = gfCrcMulmod(sq, p);
-        sq = gfCrcMulmod(sq, sq);
-    }
-    return p;
-}
-inline uint32_t gfCrc32cFold(uint32_t crcA, uint32_t crcB, uint32_t xpowB) { return gfCrcMulmod(xpowB, crcA) ^ crcB; }   // xpowB = gfCrcXpow8n(|B|)
-inline uint32_t gfCrc32cCombine(uint32_t crcA, uint32_t crcB, uint64_t lenB) { return gfCrc32cFold(crcA, crcB, gfCrcXpow8n(lenB)); }
-// the checksum of p[0, n) as the device computes a tile directory's: chunk by chunk, folded in order
+// the checksum of p[0, n) as the device computes a tile directory's: chunk by chunk, folded in order (gvrs_crc32c.h)
 inline uint32_t gfFileCrc32cChunked(const uint8_t *p, size_t n)
 {
     uint32_t crc = 0;                                             // (the checksum of no bytes)
     for (size_t at = 0; at < n; at += GF_FILE_CRC_CHUNK) {
         const size_t len = std::min<size_t>(GF_FILE_CRC_CHUNK, n - at);
-        crc = gfCrc32cCombine(crc, gfFileCrc32c(p + at, len), len);
+        crc = gfCrc32cCombine(crc, gfCrc32c(p + at, len), len);
     }
     return crc;
 }
@@ -78,7 +56,8 @@ struct GfFileOut {
 
 inline bool gfFileUtfOk(const char *s) { return !s || strlen(s) <= 65535; }
 inline size_t gfFileUtfBytes(const char *s) { return 2 + (s ? strlen(s) : 0); }
-inline uint64_t gfFileRecordSize(uint64_t content) { return (content + 12 + 7) & ~7ull; }       // RecordManager.java:219
+GF_HD uint64_t gfFileRecordSize(uint64_t content) { return (content + 12 + 7) & ~7ull; }        // RecordManager.java:219
+GF_HD uint64_t gfFileTileDirSize(uint64_t nEntries, bool extended) { return gfFileRecordSize(8 + 16 + nEntries * (extended ? 8 : 4)); }
 
 // the range the header states of an element, and the block write checks cells against: the caller's, or the default constructors'
 inline gf_elem_range gfFileElemRange(const gf_elem_spec &s, const gf_file_elem_facts *f)
@@ -117,8 +96,7 @@ inline gf_status gfFileFactsCheck(const gf_file_facts *f, int *kinds)
         if (kind == GF_CODEC_UNKNOWN) return GF_ERR_UNSUPPORTED;
         if (kinds) kinds[k] = kind;
     }
-    const uint64_t tr = ((uint64_t)g.n_rows_grid + g.n_rows_tile - 1) / g.n_rows_tile, tc = ((uint64_t)g.n_cols_grid + g.n_cols_tile - 1) / g.n_cols_tile;
-    if (tr * tc > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
+    if (gfTilesOfGrid(g).count() > 0x7fffffffll) return GF_ERR_UNSUPPORTED;
     return GF_OK;
 }
 
@@ -187,24 +165,19 @@ inline void gfFileEmitHeader(const gf_file_facts &f, uint64_t metadataDirPos, ui
     // 8 reserved bytes, the checksum word, padding to a multiple of 8 of the file position (GvrsFile.java:274-290)
     const size_t contentPos = (out.size() + 8 + 4 + 7) & ~(size_t)7, size = contentPos - 16;
     o.zeros(contentPos - out.size());
-    for (int i = 0; i < 4; i++) out[16 + i] = (uint8_t)(size >> (8 * i));
-    if (finished && f.checksum_enabled) {
-        const uint32_t crc = gfFileCrc32c(out.data() + 16, size - 4);
-        for (int i = 0; i < 4; i++) out[contentPos - 4 + i] = (uint8_t)(crc >> (8 * i));
-    }
+    gfPutLe(&out[16], size, 4);
+    if (finished && f.checksum_enabled) gfPutLe(&out[contentPos - 4], gfCrc32c(out.data() + 16, size - 4), 4);
 }
 
-// a record's frame around content that begins at out[start + 8] and ends at out's end: size and type words, padding, checksum
-inline void gfFileCloseRecord(std::vector<uint8_t> &out, size_t start, int type, bool checksums, bool chunked = false)
+// a record's frame around content that begins at out[start + 8] and ends at out's end: size and type words, padding, checksum.
+// size: the record's, where it is given (at least the content's need); else the smallest that holds the content
+inline void gfFileCloseRecord(std::vector<uint8_t> &out, size_t start, int type, bool checksums, bool chunked = false, size_t size = 0)
 {
-    const size_t size = (size_t)gfFileRecordSize(out.size() - start - 8);
+    if (size == 0) size = (size_t)gfFileRecordSize(out.size() - start - 8);
     out.resize(start + size, 0);
-    for (int i = 0; i < 4; i++) out[start + i] = (uint8_t)(size >> (8 * i));
-    out[start + 4] = (uint8_t)type, out[start + 5] = out[start + 6] = out[start + 7] = 0;
-    if (checksums) {
-        const uint32_t crc = chunked ? gfFileCrc32cChunked(out.data() + start, size - 4) : gfFileCrc32c(out.data() + start, size - 4);
-        for (int i = 0; i < 4; i++) out[start + size - 4 + i] = (uint8_t)(crc >> (8 * i));
-    }
+    gfPutLe(&out[start], size, 4);
+    gfPutLe(&out[start + 4], (uint64_t)type, 4);
+    if (checksums) gfPutLe(&out[start + size - 4], chunked ? gfFileCrc32cChunked(out.data() + start, size - 4) : gfCrc32c(out.data() + start, size - 4), 4);
 }
 
 // one metadata record appended (GvrsMetadata.write in RecordManager.writeMetadata's frame); returns its content position in out
@@ -239,8 +212,6 @@ inline void gfFileEmitMetadataDir(const gf_file_metadata *m, const uint64_t *pos
     }
     gfFileCloseRecord(out, start, GF_FILE_REC_METADATA_DIR, checksums);
 }
-
-inline uint64_t gfFileTileDirSize(uint64_t nEntries, bool extended) { return gfFileRecordSize(8 + 16 + nEntries * (extended ? 8 : 4)); }
 
 // the tile directory appended: positions[nRows * nCols] = the content position of each tile's record, or 0, row-major
 inline void gfFileEmitTileDir(bool extended, int32_t row0, int32_t col0, int32_t nRows, int32_t nCols, const uint64_t *positions, bool checksums,
@@ -280,14 +251,9 @@ inline void gfFileEmitFront(const gf_file_facts &f, const gf_file_metadata *m, i
 // the header record of front finished in place: the two positions and, where checksums are on, the record's checksum
 inline void gfFileFinishHeader(std::vector<uint8_t> &front, uint64_t contentPos, uint64_t metadataDirPos, uint64_t tileDirPos, bool checksums)
 {
-    for (int i = 0; i < 8; i++) {
-        front[GF_FILE_POS_METADATA_DIR + i] = (uint8_t)(metadataDirPos >> (8 * i));
-        front[GF_FILE_POS_TILE_DIR + i] = (uint8_t)(tileDirPos >> (8 * i));
-    }
-    if (checksums) {
-        const uint32_t crc = gfFileCrc32c(front.data() + 16, (size_t)contentPos - 16 - 4);
-        for (int i = 0; i < 4; i++) front[contentPos - 4 + i] = (uint8_t)(crc >> (8 * i));
-    }
+    gfPutLe(&front[GF_FILE_POS_METADATA_DIR], metadataDirPos, 8);
+    gfPutLe(&front[GF_FILE_POS_TILE_DIR], tileDirPos, 8);
+    if (checksums) gfPutLe(&front[contentPos - 4], gfCrc32c(front.data() + 16, (size_t)contentPos - 16 - 4), 4);
 }
 
 // gf_file_write_plan behind its argument checks: the tiles a write covers (nOut) -> the first record's position and the largest image
@@ -306,8 +272,7 @@ inline gf_status gfFileAssemble(const gf_file_facts &f, const gf_file_metadata *
     if (!imageBytes || (nRecords && (!offsets || !tileIndices)) || (!image && imageCap)) return GF_ERR_ARG;
     *imageBytes = 0;
     const gf_grid_spec &g = f.grid;
-    const int64_t nColsOfTiles = ((int64_t)g.n_cols_grid + g.n_cols_tile - 1) / g.n_cols_tile;
-    const int64_t nTiles = nColsOfTiles * (((int64_t)g.n_rows_grid + g.n_rows_tile - 1) / g.n_rows_tile);
+    const int64_t nColsOfTiles = gfTilesOfGrid(g).cols, nTiles = gfTilesOfGrid(g).count();
     GfFileFront w;
     gfFileEmitFront(f, m, nMeta, w);
     // the records' places, the bounding rectangle of their tiles and the extended decision

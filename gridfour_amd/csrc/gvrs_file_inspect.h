@@ -21,12 +21,6 @@
 
 #pragma GCC visibility push(hidden)
 
-#if defined(__HIPCC__)
-#define GF_INS_HD __host__ __device__
-#else
-#define GF_INS_HD
-#endif
-
 constexpr int GF_INSPECT_NEXT = -1;                               // gfInspectStep: the record's head passed, the walk goes on behind it
 constexpr uint64_t GF_INSPECT_MIN_SEGMENT = 1024;                 // gf_file_inspect_plan's numbers (the device form's; the host form has no use for them)
 constexpr uint64_t GF_INSPECT_MAX_SEGMENTS = 32768;
@@ -39,16 +33,11 @@ struct GfInspectParams {
     int32_t nTiles, checksums;
 };
 
-GF_INS_HD inline uint32_t gfInsLe32(const uint8_t *p)
-{
-    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
-
 // The head of the record at pos (a position the walk reached: pos <= bytes), judged without its checksum.  GF_INSPECT_END: the walk
 // ends in front of it (fewer than 13 bytes left, or a size word of 0) and r is untouched.  Else r = the record as the walk met it
 // (checksum -1) and the answer is GF_INSPECT_NEXT or the structural stop.
 template <class Word>
-GF_INS_HD inline int gfInspectStepWords(const GfInspectParams &p, uint64_t pos, gf_file_record &r, Word word)
+GF_HD int gfInspectStepWords(const GfInspectParams &p, uint64_t pos, gf_file_record &r, Word word)
 {
     if (p.bytes - pos <= 12) return GF_INSPECT_END;               // (the reference's filePos < fileSize - RECORD_OVERHEAD_SIZE)
     const uint32_t sizeWord = word(pos);
@@ -67,51 +56,21 @@ GF_INS_HD inline int gfInspectStepWords(const GfInspectParams &p, uint64_t pos, 
 }
 inline int gfInspectStep(const uint8_t *image, const GfInspectParams &p, uint64_t pos, gf_file_record &r)
 {
-    return gfInspectStepWords(p, pos, r, [image](uint64_t at) { return gfInsLe32(image + at); });
+    return gfInspectStepWords(p, pos, r, [image](uint64_t at) { return (uint32_t)gfLe(image + at, 4); });
 }
 
 // testRecordChecksum's judgement of the record whose content lies at P, in front of its checksum: true = *size is a size word the
 // checksum can be taken over.  P is the header's word: nothing about it is trusted.
-GF_INS_HD inline bool gfInspectDirHead(const GfInspectParams &p, uint64_t P, uint32_t sizeWord, uint32_t typeWord)
+GF_HD bool gfInspectDirHead(const GfInspectParams &p, uint64_t P, uint32_t sizeWord, uint32_t typeWord)
 {
     const int32_t size = (int32_t)sizeWord;
     if ((typeWord & 0xffu) > 6u) return false;
     if (size < 16 || (size & 7) != 0) return false;
     return (uint64_t)size <= p.bytes - (P - 8);
 }
-GF_INS_HD inline bool gfInspectDirPlace(const GfInspectParams &p, uint64_t P)   // may the 8 bytes in front of P be read?
+GF_HD bool gfInspectDirPlace(const GfInspectParams &p, uint64_t P)   // may the 8 bytes in front of P be read?
 {
     return P >= p.contentPos + 8 && (P & 7) == 0 && P <= p.bytes;
-}
-
-// CRC-32C eight bytes a step through eight byte tables (t[k][b]: byte b followed by k zero bytes): the walk checksums every byte
-// of the image, and the stand-alone test every byte of every truncation
-inline uint32_t gfInspectCrc32c(const uint8_t *p, size_t n)
-{
-    struct Table {
-        uint32_t t[8][256];
-        Table()
-        {
-            for (uint32_t i = 0; i < 256; i++) {
-                uint32_t c = i;
-                for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? 0x82F63B78u : 0u);
-                t[0][i] = c;
-            }
-            for (int k = 1; k < 8; k++)
-                for (uint32_t i = 0; i < 256; i++) t[k][i] = t[0][t[k - 1][i] & 0xffu] ^ (t[k - 1][i] >> 8);
-        }
-    };
-    static const Table table;
-    const uint32_t(*t)[256] = table.t;
-    uint32_t crc = 0xffffffffu;
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-        const uint32_t a = gfInsLe32(p + i) ^ crc, b = gfInsLe32(p + i + 4);
-        crc = t[7][a & 0xffu] ^ t[6][(a >> 8) & 0xffu] ^ t[5][(a >> 16) & 0xffu] ^ t[4][a >> 24] ^ t[3][b & 0xffu] ^ t[2][(b >> 8) & 0xffu] ^
-              t[1][(b >> 16) & 0xffu] ^ t[0][b >> 24];
-    }
-    for (; i < n; i++) crc = t[0][(crc ^ p[i]) & 0xffu] ^ (crc >> 8);
-    return ~crc;
 }
 
 inline GfInspectParams gfInspectParamsOf(const gf_file_info &f, uint64_t bytes)
@@ -122,8 +81,7 @@ inline GfInspectParams gfInspectParamsOf(const gf_file_info &f, uint64_t bytes)
     for (int e = 0; e < f.n_elems; e++) standard += f.elems[e].type == GF_ELEM_SHORT ? (cells * 2 + 3) & ~3ull : cells * 4;
     p.contentPos = f.content_pos, p.bytes = bytes, p.tileDirPos = f.tile_dir_pos;
     p.maxTileRecordSize = (int64_t)((4 + 4 * (uint64_t)f.n_elems + standard + 12 + 7) & ~7ull);
-    p.nTiles = (int32_t)((((int64_t)f.grid.n_rows_grid + f.grid.n_rows_tile - 1) / f.grid.n_rows_tile) *
-                         (((int64_t)f.grid.n_cols_grid + f.grid.n_cols_tile - 1) / f.grid.n_cols_tile));
+    p.nTiles = (int32_t)gfTilesOfGrid(f.grid).count();
     p.checksums = f.checksum_enabled != 0;
     return p;
 }
@@ -153,15 +111,15 @@ inline gf_status gfFileInspect(const gf_file_info &f, const uint8_t *image, uint
                                size_t badCap, gf_file_record *records, size_t recordsCap)
 {
     memset(report, 0, sizeof(*report));
-    gf_status s = bytes >= 20 ? gfInspectImageCheck(f, bytes, gfInsLe32(image + 16)) : GF_ERR_ARG;
+    gf_status s = bytes >= 20 ? gfInspectImageCheck(f, bytes, gfLe(image + 16, 4)) : GF_ERR_ARG;
     if (s != GF_OK) return s;
     const GfInspectParams p = gfInspectParamsOf(f, bytes);
     gf_file_inspect_report &o = *report;
     o.tile_dir_located = 1;
     const uint64_t T = p.tileDirPos;
-    if (gfInspectDirPlace(p, T) && gfInspectDirHead(p, T, gfInsLe32(image + T - 8), gfInsLe32(image + T - 4))) {
-        const uint32_t size = gfInsLe32(image + T - 8);
-        o.tile_dir_passed = gfInspectCrc32c(image + T - 8, size - 4) == gfInsLe32(image + T - 8 + size - 4);
+    if (gfInspectDirPlace(p, T) && gfInspectDirHead(p, T, gfLe(image + T - 8, 4), gfLe(image + T - 4, 4))) {
+        const uint32_t size = (uint32_t)gfLe(image + T - 8, 4);
+        o.tile_dir_passed = gfCrc32c(image + T - 8, size - 4) == gfLe(image + T - 8 + size - 4, 4);
     }
     auto list = [&](const gf_file_record &r) {
         if (records && o.n_records < recordsCap) records[o.n_records] = r;
@@ -190,8 +148,8 @@ inline gf_status gfFileInspect(const gf_file_info &f, const uint8_t *image, uint
         }
         if (p.checksums) {
             const bool freeNode = r.type == GF_FILE_REC_FREE;
-            const uint32_t crc = gfInspectCrc32c(image + pos, freeNode ? 8 : r.size - 4);
-            r.checksum = crc == gfInsLe32(image + pos + r.size - 4);
+            const uint32_t crc = gfCrc32c(image + pos, freeNode ? 8 : r.size - 4);
+            r.checksum = crc == gfLe(image + pos + r.size - 4, 4);
             if (!r.checksum) {
                 o.n_checksum_failures++;
                 if (r.type == GF_FILE_REC_TILE) bad(r.tile_index);
@@ -223,15 +181,6 @@ inline gf_status gfFileInspect(const gf_file_info &f, const uint8_t *image, uint
 // ends a multiple of 16 bytes in front of its record's last whole 16 bytes, the power comes from a table, and the up to 12 bytes
 // behind are run through the byte table at the end.  small[j] = x^(8 * 16 j) for every run of a record one wave takes;
 // two[i] = x^(8 * 16 * 2^i) for the chunks of a larger one (a product over the set bits of the distance).
-constexpr uint32_t gfInsMulmod(uint32_t a, uint32_t b)            // a * b mod P, operands and result bit-reflected (gfCrcMulmod)
-{
-    uint32_t p = 0;
-    for (uint32_t m = 0x80000000u; m; m >>= 1) {
-        p ^= (a & m) ? b : 0u;
-        b = (b & 1u) ? (b >> 1) ^ 0x82F63B78u : b >> 1;
-    }
-    return p;
-}
 constexpr uint32_t GF_INSPECT_SMALL_POWERS = GF_INSPECT_WAVE_CHUNKS * GF_INSPECT_CRC_CHUNK / 16 + 1;
 struct GfInspectPowers {
     uint32_t small[GF_INSPECT_SMALL_POWERS];
@@ -241,11 +190,11 @@ constexpr GfInspectPowers gfInspectMakePowers()
 {
     GfInspectPowers t{};
     uint32_t x128 = 0x00800000u;                                  // x^8 ...
-    for (int k = 0; k < 4; k++) x128 = gfInsMulmod(x128, x128);   // ... to the 16th: x^(8 * 16)
+    for (int k = 0; k < 4; k++) x128 = gfCrcMulmod(x128, x128);   // ... to the 16th: x^(8 * 16)
     t.small[0] = 0x80000000u;                                     // x^0
-    for (uint32_t j = 1; j < GF_INSPECT_SMALL_POWERS; j++) t.small[j] = gfInsMulmod(t.small[j - 1], x128);
+    for (uint32_t j = 1; j < GF_INSPECT_SMALL_POWERS; j++) t.small[j] = gfCrcMulmod(t.small[j - 1], x128);
     t.two[0] = x128;
-    for (int i = 1; i < 28; i++) t.two[i] = gfInsMulmod(t.two[i - 1], t.two[i - 1]);
+    for (int i = 1; i < 28; i++) t.two[i] = gfCrcMulmod(t.two[i - 1], t.two[i - 1]);
     return t;
 }
 

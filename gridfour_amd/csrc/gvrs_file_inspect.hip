@@ -198,41 +198,23 @@ __global__ __launch_bounds__(256) void k_inspect_list(const GfInspectArgs a)
     }
 }
 
-__device__ __forceinline__ uint32_t ins_crc_word(const uint32_t *table, uint32_t crc, uint32_t w)
-{
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        crc = table[(crc ^ w) & 0xffu] ^ (crc >> 8);
-        w >>= 8;
-    }
-    return crc;
-}
-
 // the powers of x (gvrs_file_inspect.h), made by the compiler: read through the cache, 4 KB and a few words
 __device__ const GfInspectPowers INS_POW = gfInspectMakePowers();
 
 // the CRC-32C of r[0, nBytes) by the whole wave, nBytes a multiple of 4 of at most GF_INSPECT_WAVE_CHUNKS chunks and r 8-byte
 // aligned: lane l takes the l-th of 64 runs (a multiple of 16 bytes each) of the whole 16-byte pieces, the runs are joined as
 // gvrs_crc32c.h says with powers from the table, and the up to 12 bytes behind them are run through the byte table by every
-// lane.  Every lane returns the checksum.
+// lane.  Every lane returns the checksum.  (Its own split, not wave_crc_bytes: the runs end on the table's powers.)
 __device__ __forceinline__ uint32_t ins_wave_crc(const uint32_t *table, const uint8_t *r, uint32_t nBytes, uint32_t lane)
 {
     const uint32_t nFull = nBytes & ~15u, per = ((nFull / 16u + 63u) / 64u) * 16u;
     const uint32_t begin = min(nFull, lane * per), end = min(nFull, begin + per);
-    uint32_t crc = 0xffffffffu;
-    for (uint32_t i = begin; i < end; i += 16u) {
-        const GfU4 q = *reinterpret_cast<const GfU4 *>(r + i);
-        crc = ins_crc_word(table, crc, q.x);
-        crc = ins_crc_word(table, crc, q.y);
-        crc = ins_crc_word(table, crc, q.z);
-        crc = ins_crc_word(table, crc, q.w);
-    }
-    crc ^= 0xffffffffu;                                           // the run's own checksum (an empty run: 0)
-    uint32_t part = crc_mulmod(INS_POW.small[(nFull - end) / 16u], crc);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
+    uint32_t at = begin;
+    __builtin_assume(((end - begin) & 15u) == 0u);                // (whole pieces only)
+    const uint32_t crc = ~crc_pieces16(table, 0xffffffffu, r, at, end);   // the run's own checksum (an empty run: 0)
+    uint32_t part = wave_xor(gfCrcMulmod(INS_POW.small[(nFull - end) / 16u], crc));
     part ^= 0xffffffffu;                                          // the checksum of the whole pieces goes on over the rest
-    for (uint32_t i = nFull; i < nBytes; i += 4u) part = ins_crc_word(table, part, *reinterpret_cast<const uint32_t *>(r + i));
+    for (uint32_t i = nFull; i < nBytes; i += 4u) part = crc_word(table, part, *reinterpret_cast<const uint32_t *>(r + i));
     return part ^ 0xffffffffu;
 }
 
@@ -258,8 +240,7 @@ __device__ __forceinline__ bool ins_crc_work(const GfInspectArgs &a, const GfIns
 __global__ __launch_bounds__(256) void k_inspect_crc(const GfInspectArgs a)
 {
     __shared__ uint32_t table[256];
-    table[threadIdx.x] = crc_table_entry(threadIdx.x);
-    __syncthreads();
+    crc_table_fill_256(table);
     const GfInspectState st = *a.state;
     if (st.status != GF_K_OK) return;
     const uint32_t lane = threadIdx.x & 63u;
@@ -285,8 +266,7 @@ __global__ __launch_bounds__(256) void k_inspect_crc(const GfInspectArgs a)
 __global__ __launch_bounds__(256) void k_inspect_crc_large(const GfInspectArgs a)
 {
     __shared__ uint32_t table[256];
-    table[threadIdx.x] = crc_table_entry(threadIdx.x);
-    __syncthreads();
+    crc_table_fill_256(table);
     const GfInspectState st = *a.state;
     if (st.status != GF_K_OK) return;
     const uint32_t lane = threadIdx.x & 63u;
@@ -300,7 +280,7 @@ __global__ __launch_bounds__(256) void k_inspect_crc_large(const GfInspectArgs a
             uint32_t crc = ins_wave_crc(table, a.image + r.pos + at, len, lane);
             // its weight x^(8 * bytes behind it): the product of the table's powers over the set bits of the distance in 16-byte pieces
             for (uint32_t e = (nWhole - at - len) / 16u, i = 0; e; e >>= 1, i++)
-                if (e & 1u) crc = crc_mulmod(INS_POW.two[i], crc);
+                if (e & 1u) crc = gfCrcMulmod(INS_POW.two[i], crc);
             if (lane == 0u) atomicXor(a.acc + idx, crc);
         }
     }
@@ -327,10 +307,8 @@ __global__ __launch_bounds__(INS_THREADS) void k_inspect_fold(const GfInspectArg
         const uint32_t idx = a.large[k];
         const gf_file_record r = a.recs[idx];
         uint32_t crc = ~a.acc[idx];                               // (the whole pieces' checksum goes on over the up to 12 bytes behind them)
-        for (uint32_t i = ins_large_whole(r.size - 4u); i < r.size - 4u; i += 4u) {
-            crc ^= *reinterpret_cast<const uint32_t *>(a.image + r.pos + i);
-            for (int b = 0; b < 32; b++) crc = (crc >> 1) ^ ((crc & 1u) ? CRC32C_POLY : 0u);
-        }
+        for (uint32_t i = ins_large_whole(r.size - 4u); i < r.size - 4u; i += 4u)
+            crc = gfCrcWordBits(crc, *reinterpret_cast<const uint32_t *>(a.image + r.pos + i));
         a.recs[idx].checksum = ~crc == *reinterpret_cast<const uint32_t *>(a.image + r.pos + r.size - 4u) ? 1 : 0;
     }
     __syncthreads();

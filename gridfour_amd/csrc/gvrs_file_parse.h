@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/gvrs_hip_codec.h"
+#include "gvrs_crc32c.h"
 
 #pragma GCC visibility push(hidden)          // nothing here is an export of the library
 
@@ -30,15 +31,23 @@ struct GfFileParsed {
     std::string productLabel;
 };
 
-// CRC-32C (util/GridfourCRC32C.java), bit by bit: a header record is a few hundred bytes
-inline uint32_t gfFileCrc32c(const uint8_t *p, size_t n)
+// little-endian get and put of n bytes, for every header of the chain
+GF_HD uint64_t gfLe(const uint8_t *p, int n)
 {
-    uint32_t crc = 0xffffffffu;
-    for (size_t i = 0; i < n; i++) {
-        crc ^= p[i];
-        for (int k = 0; k < 8; k++) crc = (crc >> 1) ^ ((crc & 1u) ? 0x82F63B78u : 0u);
-    }
-    return ~crc;
+    uint64_t v = 0;
+    for (int i = 0; i < n; i++) v |= (uint64_t)p[i] << (8 * i);
+    return v;
+}
+GF_HD void gfPutLe(uint8_t *p, uint64_t v, int n) { for (int i = 0; i < n; i++) p[i] = (uint8_t)(v >> (8 * i)); }
+
+// the tile rows and tile columns of a grid
+struct GfTilesOfGrid {
+    int64_t rows, cols;
+    int64_t count() const { return rows * cols; }
+};
+inline GfTilesOfGrid gfTilesOfGrid(const gf_grid_spec &g)
+{
+    return GfTilesOfGrid{((int64_t)g.n_rows_grid + g.n_rows_tile - 1) / g.n_rows_tile, ((int64_t)g.n_cols_grid + g.n_cols_tile - 1) / g.n_cols_tile};
 }
 
 // A cursor over image[0, limit), limit <= bytes.  A read that would pass the limit fails the cursor: GF_ERR_BOUNDS where the image
@@ -61,11 +70,9 @@ struct GfFileCursor {
     void alignTo4() { skip((4 - (pos & 3)) & 3); }             // (a multiple of 4 of the FILE position)
     uint64_t le(int n)
     {
-        uint64_t v = 0;
         if (!need((uint64_t)n)) return 0;
-        for (int i = 0; i < n; i++) v |= (uint64_t)image[pos + i] << (8 * i);
         pos += (uint64_t)n;
-        return v;
+        return gfLe(image + pos - n, n);
     }
     uint8_t u8() { return (uint8_t)le(1); }
     int16_t i16() { return (int16_t)(uint16_t)le(2); }
@@ -118,7 +125,7 @@ inline gf_status gfFileParse(const uint8_t *image, size_t bytes, GfFileParsed &o
     // that carries a checksum and says it has none is refused, so that no single damaged byte -- the flag's own included -- opens.
     uint32_t stored;
     memcpy(&stored, image + f.content_pos - 4, 4);                                         // (little-endian hosts, as the library's kernels)
-    if (image[GF_FILE_SPEC_POS + 24] != 0 ? gfFileCrc32c(image + 16, (size_t)size - 4) != stored : stored != 0u) return GF_ERR_FORMAT;
+    if (image[GF_FILE_SPEC_POS + 24] != 0 ? gfCrc32c(image + 16, (size_t)size - 4) != stored : stored != 0u) return GF_ERR_FORMAT;
     GfFileCursor c(image, bytes, f.content_pos - 4, 20);
     c.skip(4 + 16 + 8);                                                                    // record type + 3, UUID, time modified
     const uint64_t openedForWriting = c.u64();
@@ -191,9 +198,8 @@ inline gf_status gfFileParse(const uint8_t *image, size_t bytes, GfFileParsed &o
     }
     out.productLabel = c.utf();
     if (c.status != GF_OK) return c.status;
-    const uint64_t nRowsOfTiles = ((uint64_t)f.grid.n_rows_grid + f.grid.n_rows_tile - 1) / f.grid.n_rows_tile;
-    const uint64_t nColsOfTiles = ((uint64_t)f.grid.n_cols_grid + f.grid.n_cols_tile - 1) / f.grid.n_cols_tile;
-    if (nRowsOfTiles * nColsOfTiles > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
+    const uint64_t nTilesGrid = (uint64_t)gfTilesOfGrid(f.grid).count();
+    if (nTilesGrid > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
     if ((uint64_t)f.grid.n_rows_tile * (uint64_t)f.grid.n_cols_tile >= (1ull << 28)) return GF_ERR_UNSUPPORTED;
     // the tile directory's prefix
     const uint64_t P = f.tile_dir_pos;
@@ -207,7 +213,7 @@ inline gf_status gfFileParse(const uint8_t *image, size_t bytes, GfFileParsed &o
     if (d.status != GF_OK) return d.status;
     f.dir_entries_pos = P + GF_FILE_DIR_PREFIX;
     if (f.dir_row0 < 0 || f.dir_col0 < 0 || f.dir_n_rows < 0 || f.dir_n_cols < 0) return GF_ERR_FORMAT;
-    if ((uint64_t)f.dir_n_rows * (uint64_t)f.dir_n_cols > nRowsOfTiles * nColsOfTiles) return GF_ERR_FORMAT;
+    if ((uint64_t)f.dir_n_rows * (uint64_t)f.dir_n_cols > nTilesGrid) return GF_ERR_FORMAT;
     if (f.dir_n_cols == 0 || f.dir_n_rows == 0) f.dir_n_rows = f.dir_n_cols = 0;          // (no entries)
     return GF_OK;
 }
@@ -224,7 +230,7 @@ inline GfFileDir gfFileDirOf(const gf_file_info &f)
     GfFileDir d;
     d.entriesPos = f.dir_entries_pos, d.contentPos = f.content_pos;
     d.extended = f.dir_extended, d.row0 = f.dir_row0, d.col0 = f.dir_col0, d.nRows = f.dir_n_rows, d.nCols = f.dir_n_cols;
-    d.nColsOfTiles = (int32_t)(((int64_t)f.grid.n_cols_grid + f.grid.n_cols_tile - 1) / f.grid.n_cols_tile);
+    d.nColsOfTiles = (int32_t)gfTilesOfGrid(f.grid).cols;
     return d;
 }
 
@@ -237,9 +243,7 @@ inline gf_status gfFileLocate(const GfFileDir &d, const uint8_t *image, uint64_t
     if (tr < 0 || tr >= d.nRows || tc < 0 || tc >= d.nCols) return GF_OK;
     const uint64_t k = (uint64_t)tr * (uint64_t)d.nCols + (uint64_t)tc, w = d.extended ? 8 : 4, at = d.entriesPos + k * w;
     if (at > bytes || w > bytes - at) return GF_ERR_BOUNDS;
-    uint64_t p = 0;
-    for (uint64_t i = 0; i < w; i++) p |= (uint64_t)image[at + i] << (8 * i);
-    if (!d.extended) p *= 8;
+    const uint64_t p = d.extended ? gfLe(image + at, 8) : gfLe(image + at, 4) * 8;
     *pos = p;
     if (p == 0) return GF_OK;
     if (p < d.contentPos + 8 || (p & 7) != 0 || p > bytes || 12 > bytes - p) return GF_ERR_BOUNDS;

@@ -26,44 +26,38 @@
 
 #pragma GCC visibility push(hidden)
 
-#if defined(__HIPCC__)
-#define GF_FS_HD __host__ __device__
-#else
-#define GF_FS_HD
-#endif
-
 constexpr uint64_t GF_FS_MIN_SPLIT = 32;                          // RecordManager.MIN_FREE_BLOCK_SIZE
 constexpr uint64_t GF_FS_MIN_NODE = 24;                           // the smallest record that can be freed (above)
 enum { GF_FILE_REC_FREE = 0, GF_FILE_REC_FREE_DIR = 3 };
 constexpr uint64_t GF_FILE_POS_TIME_MODIFIED = 40, GF_FILE_POS_OPENED = 48, GF_FILE_POS_FREE_DIR = 56;
 
 // ---- the serial rules, on a list held as two arrays in order of position: pos[0, n), size[0, n), room for cap nodes ----
-GF_FS_HD inline void gfFsErase(uint64_t *pos, uint64_t *size, uint32_t &n, uint32_t k)
+GF_HD void gfFsErase(uint64_t *pos, uint64_t *size, uint32_t &n, uint32_t k)
 {
     for (uint32_t i = k + 1; i < n; i++) pos[i - 1] = pos[i], size[i - 1] = size[i];
     n--;
 }
-GF_FS_HD inline void gfFsInsert(uint64_t *pos, uint64_t *size, uint32_t &n, uint32_t k, uint64_t p, uint64_t s)
+GF_HD void gfFsInsert(uint64_t *pos, uint64_t *size, uint32_t &n, uint32_t k, uint64_t p, uint64_t s)
 {
     for (uint32_t i = n; i > k; i--) pos[i] = pos[i - 1], size[i] = size[i - 1];
     pos[k] = p, size[k] = s;
     n++;
 }
 // the first node behind position p
-GF_FS_HD inline uint32_t gfFsBehind(const uint64_t *pos, uint32_t n, uint64_t p)
+GF_HD uint32_t gfFsBehind(const uint64_t *pos, uint32_t n, uint64_t p)
 {
     uint32_t k = 0;
     while (k < n && pos[k] <= p) k++;
     return k;
 }
 // does [p, p + s) overlap a node?  (what a damaged file can ask the allocator to free)
-GF_FS_HD inline bool gfFsOverlaps(const uint64_t *pos, const uint64_t *size, uint32_t n, uint64_t p, uint64_t s)
+GF_HD bool gfFsOverlaps(const uint64_t *pos, const uint64_t *size, uint32_t n, uint64_t p, uint64_t s)
 {
     const uint32_t k = gfFsBehind(pos, n, p);
     return (k > 0 && pos[k - 1] + size[k - 1] > p) || (k < n && p + s > pos[k]);
 }
 // fileSpaceDealloc of the record [p, p + s): a case is tested only when no earlier one applies.  false: the list is full.
-GF_FS_HD inline bool gfFsDealloc(uint64_t *pos, uint64_t *size, uint32_t &n, uint32_t cap, uint64_t p, uint64_t s)
+GF_HD bool gfFsDealloc(uint64_t *pos, uint64_t *size, uint32_t &n, uint32_t cap, uint64_t p, uint64_t s)
 {
     const uint32_t k = gfFsBehind(pos, n, p);
     if (k > 0 && pos[k - 1] + size[k - 1] == p) {                 // merged with the prior node, and then with the next if they now touch
@@ -83,7 +77,7 @@ GF_FS_HD inline bool gfFsDealloc(uint64_t *pos, uint64_t *size, uint32_t &n, uin
     return true;
 }
 // fileSpaceAlloc of a record of sizeToStore bytes (a multiple of 8): its position; fileSize grows where the file does
-GF_FS_HD inline uint64_t gfFsAlloc(uint64_t *pos, uint64_t *size, uint32_t &n, uint64_t &fileSize, uint64_t sizeToStore)
+GF_HD uint64_t gfFsAlloc(uint64_t *pos, uint64_t *size, uint32_t &n, uint64_t &fileSize, uint64_t sizeToStore)
 {
     uint32_t k = 0;
     while (k < n && !(size[k] == sizeToStore || size[k] >= sizeToStore + GF_FS_MIN_SPLIT)) k++;
@@ -112,14 +106,6 @@ struct GfFileUpdate {
     std::vector<uint8_t> metaDir;                                 // the old metadata directory record, whole; empty: the file has none
 };
 
-inline uint64_t gfFsLe(const uint8_t *p, int n)
-{
-    uint64_t v = 0;
-    for (int i = 0; i < n; i++) v |= (uint64_t)p[i] << (8 * i);
-    return v;
-}
-inline void gfFsPut(uint8_t *p, uint64_t v, int n) { for (int i = 0; i < n; i++) p[i] = (uint8_t)(v >> (8 * i)); }
-
 // The head of the record whose content lies at P, judged before anything of it is trusted: P a multiple of 8 behind the header
 // record, the head inside the image, the type, a size that is a multiple of 8 of at least minSize and ends inside the image.
 inline gf_status gfFsRecordHead(const uint8_t *image, uint64_t bytes, uint64_t contentPos, uint64_t P, int type, uint64_t minSize, uint64_t *size)
@@ -127,8 +113,8 @@ inline gf_status gfFsRecordHead(const uint8_t *image, uint64_t bytes, uint64_t c
     *size = 0;
     if ((P & 7) != 0 || P < contentPos + 8 || P > (1ull << 62)) return GF_ERR_FORMAT;
     if (P > bytes) return GF_ERR_BOUNDS;
-    const int32_t s = (int32_t)(uint32_t)gfFsLe(image + P - 8, 4);
-    if (gfFsLe(image + P - 4, 4) != (uint64_t)type) return GF_ERR_FORMAT;
+    const int32_t s = (int32_t)(uint32_t)gfLe(image + P - 8, 4);
+    if (gfLe(image + P - 4, 4) != (uint64_t)type) return GF_ERR_FORMAT;
     if (s < (int64_t)minSize || (s & 7) != 0) return GF_ERR_FORMAT;
     if ((uint64_t)s > bytes - (P - 8)) return GF_ERR_BOUNDS;
     *size = (uint64_t)s;
@@ -142,7 +128,7 @@ inline gf_status gfFileUpdateBegin(const gf_file_info &info, const uint8_t *imag
     u.info = info;
     u.imageBytes = bytes;
     if (bytes < info.content_pos || info.content_pos < 20) return GF_ERR_ARG;
-    if (16 + gfFsLe(image + 16, 4) != info.content_pos) return GF_ERR_ARG;                   // (not the image that was opened)
+    if (16 + gfLe(image + 16, 4) != info.content_pos) return GF_ERR_ARG;                   // (not the image that was opened)
     if ((bytes & 7) != 0 || (info.content_pos & 7) != 0) return GF_ERR_FORMAT;               // (records are appended at the image's end)
     gf_status s;
     uint64_t size;
@@ -152,17 +138,17 @@ inline gf_status gfFileUpdateBegin(const gf_file_info &info, const uint8_t *imag
     uint64_t freeDirSize = 0;
     if (F != 0) {
         if ((s = gfFsRecordHead(image, bytes, info.content_pos, F, GF_FILE_REC_FREE_DIR, 16, &freeDirSize)) != GF_OK) return s;
-        const int32_t count = (int32_t)(uint32_t)gfFsLe(image + F, 4);                       // (16 bytes of record: the word is inside)
+        const int32_t count = (int32_t)(uint32_t)gfLe(image + F, 4);                       // (16 bytes of record: the word is inside)
         if (count < 0 || 4 + 12 * (uint64_t)count > freeDirSize - 12) return GF_ERR_FORMAT;  // (a count the record can hold)
         u.freePos.resize((size_t)count + 3), u.freeSize.resize((size_t)count + 3);
         uint64_t end = info.content_pos;
         for (int32_t k = 0; k < count; k++) {
-            const uint64_t p = gfFsLe(image + F + 4 + 12 * (uint64_t)k, 8);
-            const int32_t z = (int32_t)(uint32_t)gfFsLe(image + F + 12 + 12 * (uint64_t)k, 4);
+            const uint64_t p = gfLe(image + F + 4 + 12 * (uint64_t)k, 8);
+            const int32_t z = (int32_t)(uint32_t)gfLe(image + F + 12 + 12 * (uint64_t)k, 4);
             if ((p & 7) != 0 || (z & 7) != 0 || z < (int64_t)GF_FS_MIN_NODE) return GF_ERR_FORMAT;
             if (p < end || (k > 0 && p == end)) return GF_ERR_FORMAT;                        // ascending; no two nodes overlap or touch
             if (p > bytes || (uint64_t)z > bytes - p) return GF_ERR_BOUNDS;
-            if (gfFsLe(image + p, 4) != (uint64_t)z || gfFsLe(image + p + 4, 4) != GF_FILE_REC_FREE) return GF_ERR_FORMAT;
+            if (gfLe(image + p, 4) != (uint64_t)z || gfLe(image + p + 4, 4) != GF_FILE_REC_FREE) return GF_ERR_FORMAT;
             u.freePos[(size_t)k] = p, u.freeSize[(size_t)k] = (uint64_t)z;
             end = p + (uint64_t)z;
         }
@@ -184,9 +170,8 @@ inline gf_status gfFileUpdateBegin(const gf_file_info &info, const uint8_t *imag
     }
     if ((s = gfFsRecordHead(image, bytes, info.content_pos, T, GF_FILE_REC_TILE_DIR, 40, &size)) != GF_OK) return s;
     const uint64_t nEntries = (uint64_t)info.dir_n_rows * (uint64_t)info.dir_n_cols;
-    const int64_t nRowsOfTiles = ((int64_t)info.grid.n_rows_grid + info.grid.n_rows_tile - 1) / info.grid.n_rows_tile;
-    const int64_t nColsOfTiles = ((int64_t)info.grid.n_cols_grid + info.grid.n_cols_tile - 1) / info.grid.n_cols_tile;
-    if (nEntries != 0 && ((int64_t)info.dir_row0 + info.dir_n_rows > nRowsOfTiles || (int64_t)info.dir_col0 + info.dir_n_cols > nColsOfTiles))
+    const GfTilesOfGrid tiles = gfTilesOfGrid(info.grid);
+    if (nEntries != 0 && ((int64_t)info.dir_row0 + info.dir_n_rows > tiles.rows || (int64_t)info.dir_col0 + info.dir_n_cols > tiles.cols))
         return GF_ERR_FORMAT;                                                                // (a rectangle of tiles the grid does not have)
     if (gfFileTileDirSize(nEntries, info.dir_extended != 0) > size) return GF_ERR_FORMAT;    // (the entries lie inside the record)
     if (gfFsOverlaps(u.freePos.data(), u.freeSize.data(), n, T - 8, size)) return GF_ERR_FORMAT;
@@ -198,21 +183,11 @@ inline gf_status gfFileUpdateBegin(const gf_file_info &info, const uint8_t *imag
 // gf_file_update_plan's two numbers: nTiles = the tiles written, maxRecordBytes = gf_tile_record_max_bytes_elems of a tile
 inline void gfFileUpdatePlan(const GfFileUpdate &u, uint64_t nTiles, uint64_t maxRecordBytes, uint64_t *maxImageBytes, uint64_t *listCapacity)
 {
-    const gf_grid_spec &g = u.info.grid;
-    const uint64_t tilesOfGrid = (((uint64_t)g.n_rows_grid + g.n_rows_tile - 1) / g.n_rows_tile) * (((uint64_t)g.n_cols_grid + g.n_cols_tile - 1) / g.n_cols_tile);
+    const uint64_t tilesOfGrid = (uint64_t)gfTilesOfGrid(u.info.grid).count();
     const uint64_t cap = u.freePos.size() + nTiles + 3;
     if (listCapacity) *listCapacity = cap;
     if (maxImageBytes)
         *maxImageBytes = u.imageBytes + nTiles * maxRecordBytes + u.metaDir.size() + gfFileTileDirSize(tilesOfGrid, true) + gfFileRecordSize(4 + 12 * cap);
-}
-
-// a record of a given size (at least the content's need) closed in out, which holds 8 bytes of head and the content
-inline void gfFsCloseSized(std::vector<uint8_t> &out, size_t size, int type, bool checksums)
-{
-    out.resize(size, 0);
-    gfFsPut(out.data(), size, 4);
-    gfFsPut(out.data() + 4, (uint64_t)type, 4);
-    if (checksums) gfFsPut(out.data() + size - 4, gfFileCrc32c(out.data(), size - 4), 4);
 }
 
 // gf_file_update_assemble behind its null checks (gvrs_hip_codec.h has the contract).  Everything is decided before the first
@@ -226,7 +201,7 @@ inline gf_status gfFileUpdateAssemble(const GfFileUpdate &u, uint8_t *image, uin
     const gf_file_info &f = u.info;
     const GfFileDir d = gfFileDirOf(f);
     const int64_t nColsOfTiles = d.nColsOfTiles;
-    const int64_t nTiles = nColsOfTiles * (((int64_t)f.grid.n_rows_grid + f.grid.n_rows_tile - 1) / f.grid.n_rows_tile);
+    const int64_t nTiles = gfTilesOfGrid(f.grid).count();
     const bool compression = f.n_codecs > 0, checksums = f.checksum_enabled != 0;
     // the records: what gf_file_assemble refuses, and two records for one tile
     std::vector<int32_t> seen(tileIndices, tileIndices + nRecords);
@@ -307,7 +282,7 @@ inline gf_status gfFileUpdateAssemble(const GfFileUpdate &u, uint8_t *image, uin
     for (int64_t tr = 0; tr < d.nRows; tr++)
         for (int64_t tc = 0; tc < d.nCols; tc++) {
             const uint8_t *e = image + d.entriesPos + (uint64_t)(tr * d.nCols + tc) * (d.extended ? 8 : 4);
-            positions[(size_t)((tr + d.row0 - r0) * nCols + (tc + d.col0 - c0))] = d.extended ? gfFsLe(e, 8) : gfFsLe(e, 4) * 8;
+            positions[(size_t)((tr + d.row0 - r0) * nCols + (tc + d.col0 - c0))] = d.extended ? gfLe(e, 8) : gfLe(e, 4) * 8;
         }
     for (const Placed &p : placed) {
         positions[(size_t)((p.tile / nColsOfTiles - r0) * nCols + (p.tile % nColsOfTiles - c0))] = p.pos;
@@ -323,21 +298,21 @@ inline gf_status gfFileUpdateAssemble(const GfFileUpdate &u, uint8_t *image, uin
         o.zeros(8);
         o.i32((int32_t)n);
         for (uint32_t k = 0; k < n; k++) o.i64(pos[k]), o.i32((int32_t)size[k]);
-        gfFsCloseSized(rec, (size_t)freeDirSize, GF_FILE_REC_FREE_DIR, checksums);
+        gfFileCloseRecord(rec, 0, GF_FILE_REC_FREE_DIR, checksums, false, (size_t)freeDirSize);
         memcpy(image + freeDirAt, rec.data(), rec.size());
     }
     for (uint32_t k = 0; k < n; k++) {                                                   // every free node: head, zeros, checksum of the head
         uint8_t *p = image + pos[k];
         memset(p, 0, (size_t)size[k]);
-        gfFsPut(p, size[k], 4);
-        if (checksums) gfFsPut(p + size[k] - 4, gfFileCrc32c(p, 8), 4);
+        gfPutLe(p, size[k], 4);
+        if (checksums) gfPutLe(p + size[k] - 4, gfCrc32c(p, 8), 4);
     }
-    gfFsPut(image + GF_FILE_POS_TIME_MODIFIED, (uint64_t)timeModified, 8);
-    gfFsPut(image + GF_FILE_POS_OPENED, 0, 8);
-    gfFsPut(image + GF_FILE_POS_FREE_DIR, hasFreeDir ? freeDirAt + 8 : 0, 8);
-    gfFsPut(image + GF_FILE_POS_METADATA_DIR, u.metaDir.empty() ? 0 : metaDirAt + 8, 8);
-    gfFsPut(image + GF_FILE_POS_TILE_DIR, tileDirAt + 8, 8);
-    if (checksums) gfFsPut(image + f.content_pos - 4, gfFileCrc32c(image + 16, (size_t)f.content_pos - 16 - 4), 4);
+    gfPutLe(image + GF_FILE_POS_TIME_MODIFIED, (uint64_t)timeModified, 8);
+    gfPutLe(image + GF_FILE_POS_OPENED, 0, 8);
+    gfPutLe(image + GF_FILE_POS_FREE_DIR, hasFreeDir ? freeDirAt + 8 : 0, 8);
+    gfPutLe(image + GF_FILE_POS_METADATA_DIR, u.metaDir.empty() ? 0 : metaDirAt + 8, 8);
+    gfPutLe(image + GF_FILE_POS_TILE_DIR, tileDirAt + 8, 8);
+    if (checksums) gfPutLe(image + f.content_pos - 4, gfCrc32c(image + 16, (size_t)f.content_pos - 16 - 4), 4);
     return GF_OK;
 }
 

@@ -8,7 +8,7 @@
 //   k_update_patch      a lane per record: its tile's entry in the copy becomes its new position, or 0
 //   k_update_copy       a lane per 8-byte word of the records: to their positions
 //   k_update_dir        a lane per 8-byte word of the tile directory's record over the new rectangle, every byte once
-//   k_update_dir_crc    a wave per chunk of GF_FILE_CRC_CHUNK bytes of it (the scheme of k_file_dir_crc)
+//   k_update_dir_crc    a wave per chunk of GF_FILE_CRC_CHUNK bytes of it (both: gvrs_file_dir.h, shared with the write)
 //   k_update_fill       a lane per 8-byte word across ALL nodes of the final list: head, zeros, the head's checksum
 //   k_update_finish     ONE wave: status and size; the metadata directory, the free-space directory, the tile directory's
 //                       checksum folded, time modified, opened-for-writing 0, the three positions and the header's checksum
@@ -19,45 +19,10 @@
 
 #include "gvrs_kernels.h"
 #include "gvrs_common.h"
-#include "gvrs_crc32c.h"
+#include "gvrs_file_dir.h"
 #include "gvrs_file_update.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t upd_crc_word(const uint32_t *table, uint32_t crc, uint32_t w)
-{
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        crc = table[(crc ^ w) & 0xffu] ^ (crc >> 8);
-        w >>= 8;
-    }
-    return crc;
-}
-
-// the CRC-32C of n4 words that word(i) delivers, by the whole wave (the runs joined as gvrs_crc32c.h says); every lane returns it
-template <class Word>
-__device__ __forceinline__ uint32_t upd_wave_crc(const uint32_t *table, uint32_t n4, uint32_t lane, Word word)
-{
-    const uint32_t per = (n4 + 63u) / 64u, begin = min(n4, lane * per), end = min(n4, begin + per);
-    uint32_t crc = 0xffffffffu;
-    for (uint32_t i = begin; i < end; i++) crc = upd_crc_word(table, crc, word(i));
-    crc ^= 0xffffffffu;
-    uint32_t part = crc_mulmod(crc_xpow8n(4u * (n4 - end)), crc);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
-    return part;
-}
-
-// the CRC-32C of two words, without a table (a free node's head)
-__device__ __forceinline__ uint32_t upd_crc_head(uint32_t w0, uint32_t w1)
-{
-    uint32_t crc = 0xffffffffu;
-    for (int k = 0; k < 2; k++) {
-        crc ^= k ? w1 : w0;
-        for (int b = 0; b < 32; b++) crc = (crc >> 1) ^ ((crc & 1u) ? CRC32C_POLY : 0u);
-    }
-    return ~crc;
-}
 
 // ------------------------------------------------------------------------------------------------
 // k_update_snapshot: a lane per tile of the grid.  grid[t] = the old entry as a position, 0 outside the old rectangle.  The entries
@@ -192,8 +157,6 @@ __device__ __forceinline__ uint64_t wl_alloc(WaveList &l, uint64_t &fileSize, ui
     return p;
 }
 
-__device__ __forceinline__ uint64_t upd_record_size(uint64_t content) { return (content + 12u + 7u) & ~7ull; }
-
 // ------------------------------------------------------------------------------------------------
 // k_update_alloc: ONE wave.  Every value but the lane's share of a ballot or a shift is wave-uniform.
 // ------------------------------------------------------------------------------------------------
@@ -295,13 +258,13 @@ __global__ __launch_bounds__(64) void k_update_alloc(const GfFileUpdateArgs a)
         st.nRows = empty ? 0u : (uint32_t)(r1 - r0 + 1), st.nCols = empty ? 0u : (uint32_t)(c1 - c0 + 1);
         st.row0 = empty ? (uint32_t)a.dirRow0 : (uint32_t)r0, st.col0 = empty ? (uint32_t)a.dirCol0 : (uint32_t)c0;
         st.extended = extended;
-        st.tileDirSize = upd_record_size(8u + 16u + (uint64_t)st.nRows * st.nCols * (extended ? 8u : 4u));
+        st.tileDirSize = gfFileTileDirSize((uint64_t)st.nRows * st.nCols, extended != 0u);
         if (st.tileDirSize > 0x7fffffffull) verdict = GF_K_ERR_UNSUPPORTED;
         else {
             st.tileDirAt = wl_alloc(l, fileSize, st.tileDirSize, lane);
             st.hasFreeDir = l.n != 0u ? 1u : 0u;
             if (st.hasFreeDir) {
-                st.freeDirSize = upd_record_size(4u + 12u * (uint64_t)l.n);
+                st.freeDirSize = gfFileRecordSize(4u + 12u * (uint64_t)l.n);
                 if (st.freeDirSize > 0x7fffffffull) verdict = GF_K_ERR_UNSUPPORTED;
                 else st.freeDirAt = wl_alloc(l, fileSize, st.freeDirSize, lane);
             }
@@ -368,51 +331,30 @@ __global__ __launch_bounds__(256) void k_update_copy(const GfFileUpdateArgs a)
     *reinterpret_cast<uint2 *>(a.image + p - 8u + (b - a.offsets[lo])) = *reinterpret_cast<const uint2 *>(a.blob + b);
 }
 
-__device__ __forceinline__ uint64_t upd_entry(const GfFileUpdateArgs &a, const GfFileUpdateState &s, uint64_t k)
+__device__ __forceinline__ GfTileDirRec upd_dir(const GfFileUpdateState &s)
 {
-    if (k >= (uint64_t)s.nRows * s.nCols) return 0;
-    const uint32_t dr = (uint32_t)(k / s.nCols), dc = (uint32_t)(k - (uint64_t)dr * s.nCols);
-    return a.grid[(uint64_t)(s.row0 + dr) * (uint32_t)a.nColsOfTiles + s.col0 + dc];
+    return GfTileDirRec{s.tileDirAt, s.tileDirSize, s.extended, s.row0, s.col0, s.nRows, s.nCols};
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_update_dir: as k_file_dir_entries, over the new rectangle; the record's last 4 bytes are left to k_update_finish with checksums
+// k_update_dir, k_update_dir_crc: as k_file_dir_entries and k_file_dir_crc, over the new rectangle; a tile's entry: its word of
+// the grid.  The record's last 4 bytes are left to k_update_finish with checksums.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_update_dir(const GfFileUpdateArgs a)
 {
     const GfFileUpdateState s = *a.state;
-    const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x, nWords = s.tileDirSize / 8u;
-    if (s.verdict != GF_K_OK || w >= nWords) return;
-    uint32_t lo, hi;
-    if (w == 0u) lo = (uint32_t)s.tileDirSize, hi = (uint32_t)GF_FILE_REC_TILE_DIR;
-    else if (w == 1u) lo = s.extended << 8, hi = 0u;
-    else if (w == 2u) lo = s.row0, hi = s.col0;
-    else if (w == 3u) lo = s.nRows, hi = s.nCols;
-    else if (s.extended) {
-        const uint64_t p = upd_entry(a, s, w - 4u);
-        lo = (uint32_t)p, hi = (uint32_t)(p >> 32);
-    } else {
-        lo = (uint32_t)(upd_entry(a, s, 2u * (w - 4u)) >> 3);
-        hi = (uint32_t)(upd_entry(a, s, 2u * (w - 4u) + 1u) >> 3);
-    }
-    uint8_t *dst = a.image + s.tileDirAt + 8u * w;
-    if (w == nWords - 1u && a.checksums) *reinterpret_cast<uint32_t *>(dst) = lo;
-    else *reinterpret_cast<uint2 *>(dst) = make_uint2(lo, hi);
+    const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (s.verdict != GF_K_OK || w >= s.tileDirSize / 8u) return;
+    tile_dir_store_word(a.image, upd_dir(s), w, a.checksums != 0,
+                        [&](uint32_t row, uint32_t col) { return a.grid[(uint64_t)row * (uint32_t)a.nColsOfTiles + col]; });
 }
 
 __global__ __launch_bounds__(256) void k_update_dir_crc(const GfFileUpdateArgs a)
 {
     __shared__ uint32_t table[256];
-    table[threadIdx.x] = crc_table_entry(threadIdx.x);
-    __syncthreads();
+    crc_table_fill_256(table);
     const GfFileUpdateState s = *a.state;
-    const uint64_t nBytes = s.tileDirSize - 4u, c = (uint64_t)blockIdx.x * 4u + gf_wave_id();
-    if (s.verdict != GF_K_OK || c * GF_FILE_CRC_CHUNK >= nBytes) return;
-    const uint64_t left = nBytes - c * GF_FILE_CRC_CHUNK;
-    const uint32_t n4 = (uint32_t)(left < GF_FILE_CRC_CHUNK ? left : GF_FILE_CRC_CHUNK) / 4u, lane = threadIdx.x & 63u;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(a.image + s.tileDirAt + c * GF_FILE_CRC_CHUNK);
-    const uint32_t crc = upd_wave_crc(table, n4, lane, [&](uint32_t i) { return src[i]; });
-    if (lane == 0u) a.chunkCrc[c] = crc;
+    if (s.verdict == GF_K_OK) tile_dir_chunk_crc(table, a.image, upd_dir(s), (uint64_t)blockIdx.x * 4u + gf_wave_id(), threadIdx.x & 63u, a.chunkCrc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -435,7 +377,7 @@ __global__ __launch_bounds__(256) void k_update_fill(const GfFileUpdateArgs a)
         const uint64_t in = b - a.listPrefix[lo], size = a.listSize[lo];
         uint2 v = make_uint2(0u, 0u);
         if (in == 0u) v.x = (uint32_t)size;
-        else if (in == size - 8u && a.checksums) v.y = upd_crc_head((uint32_t)size, 0u);
+        else if (in == size - 8u && a.checksums) v.y = ~gfCrcWordBits(gfCrcWordBits(0xffffffffu, (uint32_t)size), 0u);   // (of its head)
         *reinterpret_cast<uint2 *>(a.image + a.listPos[lo] + in) = v;
     }
 }
@@ -447,9 +389,7 @@ __global__ __launch_bounds__(64) void k_update_finish(const GfFileUpdateArgs a)
 {
     __shared__ uint32_t table[256];
     const uint32_t lane = threadIdx.x;
-#pragma unroll
-    for (uint32_t i = 0; i < 4u; i++) table[lane + 64u * i] = crc_table_entry(lane + 64u * i);
-    __syncthreads();
+    crc_table_fill_wave(table, lane);
     const GfFileUpdateState s = *a.state;
     if (lane == 0u) {
         *a.imageBytes = s.total;
@@ -475,44 +415,24 @@ __global__ __launch_bounds__(64) void k_update_finish(const GfFileUpdateArgs a)
         };
         uint32_t *to = reinterpret_cast<uint32_t *>(a.image + s.freeDirAt);
         for (uint32_t i = lane; i < n4 - 1u; i += 64u) to[i] = word(i);
-        const uint32_t crc = a.checksums ? upd_wave_crc(table, n4 - 1u, lane, word) : 0u;
+        const uint32_t crc = a.checksums ? wave_crc_words(table, n4 - 1u, lane, word) : 0u;
         if (lane == 0u) to[n4 - 1u] = crc;
     }
-    const uint64_t freeDirPos = s.hasFreeDir ? s.freeDirAt + 8u : 0u, metaDirPos = a.metaDirBytes ? s.metaDirAt + 8u : 0u, tileDirPos = s.tileDirAt + 8u;
+    // the header record's fields this kernel computes, for its checksum and for the stores
+    const GfHeadField fields[5] = {{(uint32_t)GF_FILE_POS_TIME_MODIFIED, (uint64_t)a.timeModified},
+                                   {(uint32_t)GF_FILE_POS_OPENED, 0u},
+                                   {(uint32_t)GF_FILE_POS_FREE_DIR, s.hasFreeDir ? s.freeDirAt + 8u : 0u},
+                                   {(uint32_t)GF_FILE_POS_METADATA_DIR, a.metaDirBytes ? s.metaDirAt + 8u : 0u},
+                                   {(uint32_t)GF_FILE_POS_TILE_DIR, s.tileDirAt + 8u}};
     uint32_t headCrc = 0;
     if (a.checksums) {
-        // the tile directory's checksum: the chunks' folded in order
-        const uint64_t nBytes = s.tileDirSize - 4u, nChunks = (nBytes + GF_FILE_CRC_CHUNK - 1u) / GF_FILE_CRC_CHUNK;
-        uint32_t part = 0;
-        for (uint64_t c = lane; c < nChunks; c += 64u) {
-            const uint64_t end = min(nBytes, (c + 1u) * GF_FILE_CRC_CHUNK);
-            part ^= crc_mulmod(crc_xpow8n((uint32_t)(nBytes - end)), a.chunkCrc[c]);
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
-        if (lane == 0u) *reinterpret_cast<uint32_t *>(a.image + s.tileDirAt + nBytes) = part;
-        // the header record's: bytes [16, contentPos - 4) with the words this kernel writes in place
+        tile_dir_fold(a.image, upd_dir(s), a.chunkCrc, lane);
+        // the header record's checksum: bytes [16, contentPos - 4)
         const uint32_t *head = reinterpret_cast<const uint32_t *>(a.image + 16u);
-        headCrc = upd_wave_crc(table, (uint32_t)(a.contentPos - 16u - 4u) / 4u, lane, [&](uint32_t i) {
-            const uint32_t at = 16u + 4u * i;
-            if (at == GF_FILE_POS_TIME_MODIFIED) return (uint32_t)a.timeModified;
-            if (at == GF_FILE_POS_TIME_MODIFIED + 4u) return (uint32_t)((uint64_t)a.timeModified >> 32);
-            if (at == GF_FILE_POS_OPENED || at == GF_FILE_POS_OPENED + 4u) return 0u;
-            if (at == GF_FILE_POS_FREE_DIR) return (uint32_t)freeDirPos;
-            if (at == GF_FILE_POS_FREE_DIR + 4u) return (uint32_t)(freeDirPos >> 32);
-            if (at == GF_FILE_POS_METADATA_DIR) return (uint32_t)metaDirPos;
-            if (at == GF_FILE_POS_METADATA_DIR + 4u) return (uint32_t)(metaDirPos >> 32);
-            if (at == GF_FILE_POS_TILE_DIR) return (uint32_t)tileDirPos;
-            if (at == GF_FILE_POS_TILE_DIR + 4u) return (uint32_t)(tileDirPos >> 32);
-            return head[i];
-        });
+        headCrc = head_crc(table, (uint32_t)(a.contentPos - 16u - 4u) / 4u, lane, fields, [&](uint32_t i) { return head[i]; });
     }
     if (lane == 0u) {
-        *reinterpret_cast<uint64_t *>(a.image + GF_FILE_POS_TIME_MODIFIED) = (uint64_t)a.timeModified;
-        *reinterpret_cast<uint64_t *>(a.image + GF_FILE_POS_OPENED) = 0u;
-        *reinterpret_cast<uint64_t *>(a.image + GF_FILE_POS_FREE_DIR) = freeDirPos;
-        *reinterpret_cast<uint64_t *>(a.image + GF_FILE_POS_METADATA_DIR) = metaDirPos;
-        *reinterpret_cast<uint64_t *>(a.image + GF_FILE_POS_TILE_DIR) = tileDirPos;
+        head_store(a.image, fields);
         if (a.checksums) *reinterpret_cast<uint32_t *>(a.image + a.contentPos - 4u) = headCrc;
     }
 }

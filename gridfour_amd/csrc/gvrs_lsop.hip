@@ -26,12 +26,12 @@
 #include "gvrs_kernels.h"
 #include "gvrs_encode_layout.h"
 #include "huff_build.h"
+#include "gvrs_crc32c.h"
 
 namespace {
 
 #include "gvrs_encode_common.h"
 #include "gvrs_canon_common.h"
-#include "gvrs_crc32c.h"
 #include "gvrs_lsop_lu.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1036,42 +1036,19 @@ __device__ void p2_append_bits(const uint32_t *img, uint32_t nbits, uint32_t *wi
 // ------------------------------------------------------------------------------------------------
 // k_lsop_value_crc: LsHeader.computeChecksum (lsop/LsHeader.java:391-406) -- the CRC-32C (util/GridfourCRC32C.java:160-185) of a
 // tile's values as little-endian bytes, i.e. of the tile as it lies in memory -- for LsEncoder12.setValueChecksumEnabled
-// (:117-119, default off).  One wave per tile: lane l takes the l-th of 64 equal runs of cells byte by byte through the
-// polynomial's table (in LDS, made by the workgroup), and the runs' checksums are joined by the CRC's linearity:
-//   crc(A || B) = crc(A) * x^(8 |B|)  xor  crc(B)    in GF(2)[x] modulo the (reflected) polynomial,
-// so the tile's checksum is the XOR over the lanes of crc(run) * x^(8 bytes behind the run).  The multiplications are 32 steps
-// of shift-and-conditional-xor each, the powers by square and multiply (gvrs_crc32c.h, shared with the tile records' checksum).
-// Word 13 of the tile's coefficient record receives it.
+// (:117-119, default off).  One wave per tile around the byte table in LDS (wave_crc_words, gvrs_crc32c.h, shared with the tile
+// records' and the file kernels' checksums).  Word 13 of the tile's coefficient record receives it.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lsop_value_crc(const int32_t *__restrict__ values, uint32_t nCells, size_t nTiles,
                                                         const int32_t *__restrict__ inStatus, uint32_t *__restrict__ coefs)
 {
     __shared__ uint32_t table[256];
-    {
-        uint32_t c = threadIdx.x;
-#pragma unroll
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? CRC32C_POLY : 0u);
-        table[threadIdx.x] = c;
-    }
-    __syncthreads();
+    crc_table_fill_256(table);
     const uint32_t lane = threadIdx.x & 63u;
     const size_t t = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (t >= nTiles || (inStatus && inStatus[t] != GF_K_OK)) return;
     const uint32_t *__restrict__ v = reinterpret_cast<const uint32_t *>(values) + t * (size_t)nCells;
-    const uint32_t per = (nCells + 63u) / 64u, begin = min(nCells, lane * per), end = min(nCells, begin + per);
-    uint32_t crc = 0xffffffffu;
-    for (uint32_t i = begin; i < end; i++) {
-        uint32_t w = v[i];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            crc = table[(crc ^ w) & 0xffu] ^ (crc >> 8);
-            w >>= 8;
-        }
-    }
-    crc ^= 0xffffffffu;                                                       // the run's own checksum (an empty run: 0)
-    uint32_t part = crc_mulmod(crc_xpow8n((nCells - end) * 4u), crc);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
+    const uint32_t part = wave_crc_words(table, nCells, lane, [&](uint32_t i) { return v[i]; });
     if (lane == 0) coefs[t * 16 + 13] = part;
 }
 

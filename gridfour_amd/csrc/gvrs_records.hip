@@ -130,29 +130,17 @@ __global__ __launch_bounds__(256) void k_record_parse_elems(const GfRecordParseE
 
 // ------------------------------------------------------------------------------------------------
 // k_record_crc32c_elems: verification only.  A wave per record with sizes[t] != 0: the CRC-32C of its first size - 4 bytes against
-// the stored one in its last four.  Lane l takes the l-th of 64 runs (a multiple of 16 bytes each) through the byte table in
-// LDS; the runs are joined as gvrs_crc32c.h says.  A record that starts at a multiple of 4 (file records start at multiples of
-// 8) is read in 16-byte and 4-byte pieces, any other byte by byte.  Nothing outside [offsets[t], offsets[t] + size) is read.
+// the stored one in its last four (wave_crc_bytes, gvrs_crc32c.h).  A record that starts at a multiple of 4 (file records start at
+// multiples of 8) is read in 16-byte and 4-byte pieces, any other byte by byte.  Nothing outside [offsets[t], offsets[t] + size) is read.
 // A mismatch reaches all nElems instances of the record (lane e writes element e's): class failed -- out of the partition --
 // and GF_K_ERR_FORMAT, whatever the walk said about them.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t crc_word(const uint32_t *table, uint32_t crc, uint32_t w)
-{
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        crc = table[(crc ^ w) & 0xffu] ^ (crc >> 8);
-        w >>= 8;
-    }
-    return crc;
-}
-
 __global__ __launch_bounds__(256) void k_record_crc32c_elems(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets,
                                                              const uint32_t *__restrict__ sizes, int32_t *__restrict__ cls,
                                                              int32_t *__restrict__ status, size_t nTiles, int nElems)
 {
     __shared__ uint32_t table[256];
-    table[threadIdx.x] = crc_table_entry(threadIdx.x);
-    __syncthreads();
+    crc_table_fill_256(table);
     const uint32_t lane = threadIdx.x & 63u;
     const size_t t = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (t >= nTiles) return;
@@ -161,23 +149,7 @@ __global__ __launch_bounds__(256) void k_record_crc32c_elems(const uint8_t *__re
     const uint64_t o0 = offsets[t];
     const uint32_t nBytes = size - 4u;
     const uint8_t *__restrict__ r = blob + o0;
-    const uint32_t per = ((nBytes + 63u) / 64u + 15u) & ~15u, begin = min(nBytes, lane * per), end = min(nBytes, begin + per);
-    uint32_t crc = 0xffffffffu, i = begin;
-    if ((o0 & 3u) == 0u) {
-        for (; i + 16u <= end; i += 16u) {
-            const GfU4 q = *reinterpret_cast<const GfU4 *>(r + i);
-            crc = crc_word(table, crc, q.x);
-            crc = crc_word(table, crc, q.y);
-            crc = crc_word(table, crc, q.z);
-            crc = crc_word(table, crc, q.w);
-        }
-        for (; i + 4u <= end; i += 4u) crc = crc_word(table, crc, *reinterpret_cast<const uint32_t *>(r + i));
-    }
-    for (; i < end; i++) crc = table[(crc ^ r[i]) & 0xffu] ^ (crc >> 8);
-    crc ^= 0xffffffffu;                                                       // the run's own checksum (an empty run: 0)
-    uint32_t part = crc_mulmod(crc_xpow8n(nBytes - end), crc);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
+    const uint32_t part = wave_crc_bytes(table, r, nBytes, lane, (o0 & 3u) == 0u, true);
     if ((int)lane < nElems && part != rec_le32(r + nBytes)) {
         status[(size_t)lane * nTiles + t] = GF_K_ERR_FORMAT;
         cls[(size_t)lane * nTiles + t] = GF_REC_FAILED;

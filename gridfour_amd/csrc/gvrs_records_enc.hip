@@ -212,26 +212,15 @@ __global__ __launch_bounds__(256) void k_record_write(const GfRecordWriteArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_record_crc32c_write: a wave per written record, as k_record_crc32c_elems reads one: lane l takes the l-th of 64 runs (a multiple
-// of 16 bytes each) through the byte table in LDS, the runs are joined as gvrs_crc32c.h says, and lane 0 stores the checksum into
-// the record's last word (a vector store).  Records start at multiples of 8: 16-byte and 4-byte loads throughout.
+// k_record_crc32c_write: a wave per written record, as k_record_crc32c_elems reads one (wave_crc_bytes, gvrs_crc32c.h), and lane 0
+// stores the checksum into the record's last word (a vector store).  Records start at multiples of 8: 16-byte and 4-byte loads
+// throughout.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t enc_crc_word(const uint32_t *table, uint32_t crc, uint32_t w)
-{
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        crc = table[(crc ^ w) & 0xffu] ^ (crc >> 8);
-        w >>= 8;
-    }
-    return crc;
-}
-
 __global__ __launch_bounds__(256) void k_record_crc32c_write(uint8_t *__restrict__ blob, size_t blobCap, const uint64_t *__restrict__ offsets,
                                                              const uint32_t *__restrict__ sizes, size_t nTiles)
 {
     __shared__ uint32_t table[256];
-    table[threadIdx.x] = crc_table_entry(threadIdx.x);
-    __syncthreads();
+    crc_table_fill_256(table);
     const uint32_t lane = threadIdx.x & 63u;
     const size_t t = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (t >= nTiles) return;
@@ -241,20 +230,7 @@ __global__ __launch_bounds__(256) void k_record_crc32c_write(uint8_t *__restrict
     if (o0 + size > blobCap) return;
     const uint32_t nBytes = size - 4u;                                        // (a multiple of 4)
     uint8_t *r = blob + o0;
-    const uint32_t per = ((nBytes + 63u) / 64u + 15u) & ~15u, begin = min(nBytes, lane * per), end = min(nBytes, begin + per);
-    uint32_t crc = 0xffffffffu, i = begin;
-    for (; i + 16u <= end; i += 16u) {
-        const GfU4 q = *reinterpret_cast<const GfU4 *>(r + i);
-        crc = enc_crc_word(table, crc, q.x);
-        crc = enc_crc_word(table, crc, q.y);
-        crc = enc_crc_word(table, crc, q.z);
-        crc = enc_crc_word(table, crc, q.w);
-    }
-    for (; i + 4u <= end; i += 4u) crc = enc_crc_word(table, crc, *reinterpret_cast<const uint32_t *>(r + i));
-    crc ^= 0xffffffffu;                                                       // the run's own checksum (an empty run: 0)
-    uint32_t part = crc_mulmod(crc_xpow8n(nBytes - end), crc);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) part ^= gf_lane_xor(part, o);
+    const uint32_t part = wave_crc_bytes(table, r, nBytes, lane, true, false);
     if (lane == 0u) *reinterpret_cast<uint32_t *>(r + nBytes) = part;
 }
 

@@ -2,7 +2,7 @@
 // records' fields, tile records in file order) and assembled again, byte for byte; every image_cap from 0 to the need for the first
 // two of them, each in a heap block of exactly image_cap bytes and once more in front of a guard region; an empty directory; the
 // forced extended directory; metadata names and contents of length 0; and the CRC fold against the straight CRC for every pair of
-// lengths 0 .. 2 chunks + 1.
+// lengths 0 .. 2 chunks + 1, behind the host's CRC-32C itself against a bit-by-bit loop and the check value.
 //   file_emit_test FILE...      prints "chunk N", one line per file and "done"; exit 0, or 1 with a message
 #include <cstdio>
 #include <cstdlib>
@@ -23,7 +23,7 @@ static bool recordCrcBad(const std::vector<uint8_t> &d, uint64_t at, bool checks
 {
     const uint32_t size = le32(d, at);
     if (size < 16 || (size & 7) != 0 || at + size > d.size()) return true;
-    return le32(d, at + size - 4) != (checksums ? gfFileCrc32c(d.data() + at, size - 4) : 0u);
+    return le32(d, at + size - 4) != (checksums ? gfCrc32c(d.data() + at, size - 4) : 0u);
 }
 
 namespace {
@@ -142,6 +142,26 @@ static gf_status assemble(const Taken &t, int flags, size_t nRecords, uint8_t *i
 
 }  // namespace
 
+// the shared gfCrc32c (eight bytes a step) against a bit-by-bit loop: every length 0 .. 40 at every start offset 0 .. 7 of a buffer
+// (head, 8-byte body and tail), and the check value of the nine digits
+static int crcStraight()
+{
+    uint8_t bytes[48];
+    uint32_t x = 2463534242u;
+    for (uint8_t &b : bytes) x = x * 1664525u + 1013904223u, b = (uint8_t)(x >> 24);
+    for (size_t at = 0; at < 8; at++)
+        for (size_t n = 0; n <= 40; n++) {
+            uint32_t crc = 0xffffffffu;
+            for (size_t i = 0; i < n; i++) {
+                crc ^= bytes[at + i];
+                for (int k = 0; k < 8; k++) crc = (crc >> 1) ^ ((crc & 1u) ? 0x82F63B78u : 0u);
+            }
+            if (gfCrc32c(bytes + at, n) != ~crc) return fail("crc", "gfCrc32c differs from the bit-by-bit loop", (long)(at * 1000 + n));
+        }
+    if (gfCrc32c((const uint8_t *)"123456789", 9) != 0xE3069283u) return fail("crc", "gfCrc32c misses the check value", 0);
+    return 0;
+}
+
 static int crcFold()
 {
     const size_t top = 2 * GF_FILE_CRC_CHUNK + 1;
@@ -150,7 +170,7 @@ static int crcFold()
     for (uint8_t &b : bytes) x = x * 1664525u + 1013904223u, b = (uint8_t)(x >> 24);
     std::vector<uint32_t> xpow(top + 1), whole(2 * top + 1);
     for (size_t n = 0; n <= top; n++) xpow[n] = gfCrcXpow8n(n);
-    for (size_t n = 0; n <= 2 * top; n++) whole[n] = gfFileCrc32c(bytes.data(), n);              // the straight CRC of every prefix
+    for (size_t n = 0; n <= 2 * top; n++) whole[n] = gfCrc32c(bytes.data(), n);              // the straight CRC of every prefix
     for (size_t a = 0; a <= top; a++) {
         uint32_t run = 0xffffffffu;                                                              // crc of bytes[a, a + b), byte by byte
         for (size_t b = 0; b <= top; b++) {
@@ -162,7 +182,7 @@ static int crcFold()
         }
     }
     for (const size_t n : {(size_t)0, (size_t)1, (size_t)GF_FILE_CRC_CHUNK - 1, (size_t)GF_FILE_CRC_CHUNK, (size_t)GF_FILE_CRC_CHUNK + 1, 2 * top})
-        if (gfFileCrc32cChunked(bytes.data(), n) != whole[n] || gfCrc32cCombine(whole[n / 3], gfFileCrc32c(bytes.data() + n / 3, n - n / 3), n - n / 3) != whole[n])
+        if (gfFileCrc32cChunked(bytes.data(), n) != whole[n] || gfCrc32cCombine(whole[n / 3], gfCrc32c(bytes.data() + n / 3, n - n / 3), n - n / 3) != whole[n])
             return fail("crc", "the chunked CRC differs", (long)n);
     return 0;
 }
@@ -266,7 +286,7 @@ int main(int argc, char **argv)
         }
         if (nRec && first != expect) return fail(argv[a], "the records do not follow the metadata records end to end", (long)expect);
     }
-    if (crcFold()) return 1;
+    if (crcStraight() || crcFold()) return 1;
     printf("done\n");
     return 0;
 }

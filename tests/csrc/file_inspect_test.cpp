@@ -35,13 +35,23 @@ static bool sameRecord(const gf_file_record &a, const gf_file_record &b)
 // k_inspect_fold).  What is checked is the arithmetic and the tables, against the plain checksum.
 static const GfInspectPowers POWERS = gfInspectMakePowers();
 
+static uint32_t bitCrc(const uint8_t *p, size_t n)                 // the plain checksum, bit by bit
+{
+    uint32_t crc = 0xffffffffu;
+    for (size_t i = 0; i < n; i++) {
+        crc ^= p[i];
+        for (int b = 0; b < 8; b++) crc = (crc >> 1) ^ ((crc & 1u) ? 0x82F63B78u : 0u);
+    }
+    return ~crc;
+}
+
 static uint32_t waveCrc(const uint8_t *r, uint32_t nBytes)
 {
     const uint32_t nFull = nBytes & ~15u, per = ((nFull / 16u + 63u) / 64u) * 16u;
     uint32_t sum = 0;
     for (uint32_t lane = 0; lane < 64; lane++) {
         const uint32_t begin = std::min(nFull, lane * per), end = std::min(nFull, begin + per);
-        sum ^= gfCrcMulmod(POWERS.small[(nFull - end) / 16u], end > begin ? gfInspectCrc32c(r + begin, end - begin) : 0u);
+        sum ^= gfCrcMulmod(POWERS.small[(nFull - end) / 16u], end > begin ? gfCrc32c(r + begin, end - begin) : 0u);
     }
     uint32_t crc = ~sum;
     for (uint32_t i = nFull; i < nBytes; i++) {
@@ -79,12 +89,12 @@ static void checkPowers()
     uint32_t x = 12345;
     for (uint8_t &b : bytes) b = (uint8_t)((x = x * 1664525u + 1013904223u) >> 24);
     for (uint32_t n = 0; n < 70; n++)                              // the eight-table checksum against the bit-by-bit one, at every phase
-        for (uint32_t at = 0; at < 9; at++) CHECK(gfInspectCrc32c(bytes.data() + at, n) == gfFileCrc32c(bytes.data() + at, n));
-    CHECK(gfInspectCrc32c(bytes.data() + 3, 5001) == gfFileCrc32c(bytes.data() + 3, 5001));
+        for (uint32_t at = 0; at < 9; at++) CHECK(gfCrc32c(bytes.data() + at, n) == bitCrc(bytes.data() + at, n));
+    CHECK(gfCrc32c(bytes.data() + 3, 5001) == bitCrc(bytes.data() + 3, 5001));
     const uint32_t most = GF_INSPECT_WAVE_CHUNKS * GF_INSPECT_CRC_CHUNK;
-    for (uint32_t n = 0; n <= most; n += (n < 1100 || n + 40 > most ? 4 : 500)) CHECK(waveCrc(bytes.data(), n) == gfInspectCrc32c(bytes.data(), n));
+    for (uint32_t n = 0; n <= most; n += (n < 1100 || n + 40 > most ? 4 : 500)) CHECK(waveCrc(bytes.data(), n) == gfCrc32c(bytes.data(), n));
     for (uint32_t n : {most + 4, most + 12, most + 16, most + GF_INSPECT_CRC_CHUNK, most + GF_INSPECT_CRC_CHUNK + 4, 3 * most - 4, 3 * most, 3 * most + 60})
-        CHECK(largeCrc(bytes.data(), n) == gfInspectCrc32c(bytes.data(), n));
+        CHECK(largeCrc(bytes.data(), n) == gfCrc32c(bytes.data(), n));
 }
 
 int main(int argc, char **argv)

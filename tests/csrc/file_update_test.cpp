@@ -42,7 +42,7 @@ static bool tiles(const std::vector<uint8_t> &image, uint64_t contentPos)
     uint64_t at = contentPos;
     while (at < image.size()) {
         if (image.size() - at < 16) return false;
-        const uint64_t size = gfFsLe(image.data() + at, 4);
+        const uint64_t size = gfLe(image.data() + at, 4);
         if (size < 16 || (size & 7) != 0 || size > image.size() - at) return false;
         at += size;
     }
@@ -106,7 +106,7 @@ int main(int argc, char **argv)
             printf("FAILED to open %s\n", argv[a]);
             return 2;
         }
-        const int64_t time = (int64_t)gfFsLe(image.data() + GF_FILE_POS_TIME_MODIFIED, 8);
+        const int64_t time = (int64_t)gfLe(image.data() + GF_FILE_POS_TIME_MODIFIED, 8);
         std::vector<uint8_t> out, again;
         CHECK(update(image, {}, {}, time, out) == GF_OK && tiles(out, p.info.content_pos));
         if (p.info.freespace_dir_pos == 0) CHECK(out == image);   // (a file without free space closes as it was)

@@ -87,6 +87,43 @@ def test_chunk_size_is_printed(emit_exe):
     assert c >= 64 and c % 64 == 0
 
 
+@pytest.mark.parametrize("extended", [False, True], ids=["compact", "extended"])
+def test_directory_of_more_than_64_chunks(emit_exe, extended):
+    """The shape at which the device's fold gives a lane a second chunk (tests/dir_seams.py), on the host: the assembler's chunked
+    fold against the Python writer and against a Python CRC loop that is not the library's"""
+    import gvrs_file_update_ref as R
+    from dir_seams import SEAMS
+    w = 8 if extended else 4
+    n = dict(SEAMS)["65C+1"](crc_chunk(emit_exe), w)
+    s = W.spec((2, 2 * n, 2, 2), [B.element("z_int", "int")], [], uuid=bytes(16), time_modified=5)
+    recs = [B.frame_record(t, [struct.pack("<4i", t, t + 1, t + 2, t + 3)], True) for t in range(n)]
+    flags = FILE_DIR_EXTENDED if extended else 0
+    image = GvrsFileHip.assemble(W.lib_facts(s), recs, np.arange(n, dtype=np.int32), flags=flags)
+    assert image == W.ref_image(s, list(enumerate(recs)), extended=extended)
+    at = GvrsFileHip(image).info["tile_dir_pos"] - 8
+    (size,) = struct.unpack_from("<i", image, at)
+    assert at + size == len(image) and size == (8 + 8 + 16 + n * w + 4 + 7) // 8 * 8 and size - 4 > 64 * crc_chunk(emit_exe)
+    assert struct.unpack_from("<I", image, at + size - 4)[0] == R.crc32c(image[at:at + size - 4])
+
+
+def test_exported_crc32c_against_a_bit_by_bit_loop():
+    """gf_crc32c through the binding, as tests/csrc/file_emit_test.cpp holds the library's own gfCrc32c: every length 0 .. 40 at
+    every start offset 0 .. 7 of a buffer (head, 8-byte body and tail of an eight-byte step), and the check value"""
+    def bitwise(data):
+        crc = 0xffffffff
+        for x in data:
+            crc ^= x
+            for _ in range(8):
+                crc = (crc >> 1) ^ (0x82F63B78 if crc & 1 else 0)
+        return crc ^ 0xffffffff
+
+    buf = np.random.default_rng(40).integers(0, 256, 48, dtype=np.uint8).tobytes()
+    assert bitwise(b"123456789") == 0xE3069283 and B.crc32c(b"123456789") == 0xE3069283
+    for at in range(8):
+        for n in range(41):
+            assert B.crc32c(buf[at:at + n]) == bitwise(buf[at:at + n]), (at, n)
+
+
 def random_spec(rng, n_elems):
     kinds = ["int", "short", "float", "icf"]
     elements = []

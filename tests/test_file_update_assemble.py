@@ -39,6 +39,22 @@ def test_scenario_equals_the_model(name, checksums):
     both(image, records, tiles, status, flags, compression)
 
 
+@pytest.mark.parametrize("extended", [False, True], ids=["compact", "extended"])
+def test_directory_of_more_than_64_chunks(tmp_path_factory, extended):
+    """The shape at which the device's fold gives a lane a second chunk (tests/dir_seams.py), on the host: a grid of one row of n
+    tiles, a file with tile 0 alone, tile 0 written anew and the last tile written, against the model"""
+    from dir_seams import SEAMS, read_chunk
+    n = dict(SEAMS)["65C+1"](read_chunk(tmp_path_factory), 8 if extended else 4)
+    image = U.make_file([("t", 0, 40)], grid=(2, 2 * n, 2, 2))
+    records, tiles = U.writes_of([(0, 48), (n - 1, 24)])
+    want, opened, final, _, _ = U.model(image, records, tiles, flags=int(extended), n_tile_cols=n)
+    got, lib_opened = lib_update(image, records, tiles, None, int(extended))
+    assert lib_opened == opened and got == want
+    U.check_invariants(got, final, n_tile_cols=n)
+    td = struct.unpack_from("<q", got, 80)[0]
+    assert struct.unpack_from("<iiii", got, td + 8) == (0, 0, 1, n) and got[td + 1] == int(extended)
+
+
 def test_the_deviation_keeps_the_tile():
     """the reference would write the standard form into the block it freed and lose the entry: here the record is allocated"""
     image, records, tiles, *_ = U.scenario("the deviation")

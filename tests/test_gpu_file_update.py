@@ -2,7 +2,8 @@
 on tile-aligned rectangles (nothing decoded, only enqueued) and on rectangles with partly covered tiles (the old records found by
 k_file_locate and merged), with damaged old records, and both device forms are shown to return while a backlog still runs.  gf_file_update_records_dev is held to gf_file_update_assemble byte for byte (which
 tests/test_file_update_assemble.py holds to the model) on every scenario of tests/file_update_cases.py, at the seams of the
-allocator's 64-node turns in both of its routes (the list in LDS and in scratch, chosen by the capacity argument), and at one byte
+allocator's 64-node turns in both of its routes (the list in LDS and in scratch, chosen by the capacity argument), at the seams of
+the directory checksum's chunks (the table of tests/dir_seams.py, up to more than 64 chunks), and at one byte
 too little room, where the image must stay as it was.  gf_file_update_block_elems, the host-memory block form, is held to the
 model fed with its own records, and its images read back as the old raster with the rectangle replaced."""
 import functools
@@ -16,7 +17,9 @@ from gridfour_amd import GvrsFileHip, _lib
 
 import file_update_cases as U
 import gvrs_file_build as B
+import gvrs_file_update_ref as R
 import gvrs_file_write_ref as W
+from dir_seams import SEAMS, read_chunk
 
 pytestmark = pytest.mark.gpu
 CRC = pytest.mark.parametrize("checksums", [True, False], ids=["crc", "nocrc"])
@@ -51,6 +54,27 @@ def test_records_form_equals_the_assembler(ctx, name, checksums):
 def test_records_form_in_scratch_equals_the_assembler(ctx, name):
     image, records, tiles, status, flags, _, _ = U.scenario(name)
     dev_equals_host(ctx, image, records, tiles, status, flags, list_capacity=SCRATCH_ROUTE)
+
+
+@pytest.fixture(scope="module")
+def chunk(tmp_path_factory):
+    return read_chunk(tmp_path_factory)
+
+
+@pytest.mark.parametrize("extended", [False, True], ids=["compact", "extended"])
+@pytest.mark.parametrize("name,count", SEAMS, ids=[n for n, _ in SEAMS])
+def test_directory_checksum_at_chunk_seams(ctx, chunk, name, count, extended):
+    """The seam table of tests/dir_seams.py on the update's directory kernels: a grid of one row of n tiles, a file with
+    tile 0 alone, and an update that writes tile 0 anew and the last tile, so that the new directory has n entries"""
+    n = count(chunk, 8 if extended else 4)
+    assert n >= 1
+    image = U.make_file([("t", 0, 40)], grid=(2, 2 * n, 2, 2))
+    got = dev_equals_host(ctx, image, *U.writes_of([(0, 48), (n - 1, 24)][:n]), flags=int(extended))
+    td = struct.unpack_from("<q", got, 80)[0]
+    (size,) = struct.unpack_from("<i", got, td - 8)
+    assert struct.unpack_from("<iiii", got, td + 8) == (0, 0, 1, n) and got[td + 1] == int(extended)
+    assert size == (8 + 8 + 16 + n * (8 if extended else 4) + 4 + 7) // 8 * 8
+    assert struct.unpack_from("<I", got, td - 8 + size - 4)[0] == R.crc32c(got[td - 8:td - 8 + size - 4])    # (the Python loop, not the library's)
 
 
 @CRC

@@ -16,6 +16,7 @@ from gridfour_amd import _lib
 
 import gvrs_file_build as B
 import gvrs_file_write_ref as W
+from dir_seams import SEAMS, read_chunk
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -230,15 +231,7 @@ def test_a_tile_out_of_range_gets_no_record_and_the_file_reads(ctx):
 
 @pytest.fixture(scope="module")
 def chunk(tmp_path_factory):
-    """GF_FILE_CRC_CHUNK, read through the stand-alone program of tests/csrc/file_emit_test.cpp: no copy of it is kept here"""
-    from test_file_assemble import build_emit_test, crc_chunk
-    exe, err = build_emit_test(tmp_path_factory, False)
-    assert exe, err[-2000:]
-    return crc_chunk(exe)
-
-
-SEAMS = [("one", lambda c, w: 1), ("C-1", lambda c, w: c // w - 1), ("C", lambda c, w: c // w), ("C+1", lambda c, w: c // w + 1),
-         ("3C+5", lambda c, w: 3 * c // w + 5)]
+    return read_chunk(tmp_path_factory)
 
 
 @pytest.mark.parametrize("extended", [False, True], ids=["compact", "extended"])
