@@ -2,7 +2,8 @@
 model alone), tests/test_file_update_assemble.py (the library's host path against the model) and tests/test_gpu_file_update.py.
 No file the reference made has free space, so the images are built here: a LAYOUT is the file's content in file order,
 ("t", tile, size) a tile record of `size` bytes, ("f", size) a free node; the tile directory and, where there are nodes, the
-free-space directory follow.  After opening, the two directories at the file's end are one trailing free node."""
+free-space directory follow.  After opening, the two directories at the file's end are one trailing free node.
+tests/file_update_chains.py builds on make_file / writes_of / model: lists that are long AT OPEN, chains, and the launch seams."""
 import struct
 
 import gvrs_file_build as B

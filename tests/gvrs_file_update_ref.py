@@ -37,7 +37,10 @@ def multiple_of_8(v):
 
 
 class RefUpdate:
-    """A file opened for writing.  n_cols_of_tiles and compression (the specification has codecs) are the caller's knowledge."""
+    """A file opened for writing.  n_cols_of_tiles and compression (the specification has codecs) are the caller's knowledge.
+    .log: an event per dealloc and alloc, each ending with the node index k it found and the list's length n BEFORE the event:
+    ("free", "insert" | "prior" | "next" | "both", pos, size, k, n), ("alloc", "split" | "exact", pos, size, surplus, k, n) and
+    ("alloc", "overwrite-last" | "append", pos, size, n), where the search passed all n nodes."""
 
     def __init__(self, image, n_cols_of_tiles, compression):
         b = self.b = bytearray(image)
@@ -104,16 +107,17 @@ class RefUpdate:
             file_size = len(self.b)
             if self.free and self.free[-1][0] + self.free[-1][1] == file_size and self.free[-1][1] < size_to_store:
                 pos = self.free.pop()[0]
-                self.log.append(("alloc", "overwrite-last", pos, size_to_store))
+                self.log.append(("alloc", "overwrite-last", pos, size_to_store, k))
                 self.init_record(pos, size_to_store, rtype)
                 return pos + 8
-            self.log.append(("alloc", "append", file_size, size_to_store))
+            self.log.append(("alloc", "append", file_size, size_to_store, k))
             self.init_record(file_size, size_to_store, rtype)
             return file_size + 8
+        n_before = len(self.free)
         pos, _ = self.free.pop(k)
         (found,) = struct.unpack_from("<i", self.b, pos)
         surplus = found - size_to_store
-        self.log.append(("alloc", "split" if surplus > 0 else "exact", pos, size_to_store, surplus, k))
+        self.log.append(("alloc", "split" if surplus > 0 else "exact", pos, size_to_store, surplus, k, n_before))
         if surplus > 0:
             surplus_pos = pos + size_to_store
             self.init_record(surplus_pos, surplus, FREE)
@@ -131,6 +135,7 @@ class RefUpdate:
         k = 0
         while k < len(self.free) and self.free[k][0] <= release_pos:
             k += 1
+        n_before = len(self.free)
         prior = self.free[k - 1] if k > 0 else None
         nxt = self.free[k] if k < len(self.free) else None
         if prior is not None and prior[0] + prior[1] == release_pos:
@@ -138,19 +143,19 @@ class RefUpdate:
             if nxt is not None and prior[0] + prior[1] == nxt[0]:
                 prior[1] += nxt[1]
                 del self.free[k]
-                self.log.append(("free", "both", release_pos, release_size))
+                self.log.append(("free", "both", release_pos, release_size, k, n_before))
             else:
-                self.log.append(("free", "prior", release_pos, release_size))
+                self.log.append(("free", "prior", release_pos, release_size, k, n_before))
             struct.pack_into("<ii", self.b, prior[0], prior[1], FREE)
             return
         if nxt is not None and release_pos + release_size == nxt[0]:
             nxt[0] = release_pos
             nxt[1] += release_size
             struct.pack_into("<ii", self.b, nxt[0], nxt[1], FREE)
-            self.log.append(("free", "next", release_pos, release_size))
+            self.log.append(("free", "next", release_pos, release_size, k, n_before))
             return
         self.free.insert(k, [release_pos, release_size])
-        self.log.append(("free", "insert", release_pos, release_size))
+        self.log.append(("free", "insert", release_pos, release_size, k, n_before))
 
     # ---- TileDirectory ----
     def get_position(self, tile):
