@@ -2014,6 +2014,41 @@ class GvrsFileHip:
         return image[:need.value].tobytes()
 
     @staticmethod
+    def _image_dev(ctx, name, head, rect, blocks, mid, cap, n_out, old=None):
+        """The device scaffold of write_image and update_image.  Uploads the blocks and a buffer of cap + 64 bytes (old's bytes as
+        far as cap reaches, then 0xA5), calls name(ctx, *head, rect, blocks, *mid, image, cap, size, file status, tile indices,
+        status, codec used), synchronises, downloads -> (file status, the size the image has or needs, the whole buffer, tile
+        indices [n_out], status [n_out], codec used [n_elems, n_out])."""
+        ne = len(blocks)
+        buf = np.full(cap + 64, 0xA5, np.uint8)
+        if old is not None:
+            buf[:min(cap, old.size)] = old[:min(cap, old.size)]
+        with _DeviceScope(ctx) as s:
+            d_blk = [s.upload(b, slack=16) for b in blocks]
+            d_image = s.upload(buf)
+            d_bytes, d_fst = s.alloc(16, fill=0x7f), s.alloc(16, fill=0x7f)
+            d_idx, d_st = s.alloc(n_out * 4 + 16, fill=0x7f), s.alloc(n_out * 4 + 16, fill=0x7f)
+            d_used = s.alloc(ne * n_out + 16, fill=0)
+            s.run(name, ctx.handle, *head, _ptr(rect), s.ptrs(d_blk), *mid, d_image.ptr, cap, d_bytes.ptr, d_fst.ptr, d_idx.ptr, d_st.ptr, d_used.ptr)
+            return (int(d_fst.download(np.int32, 1)[0]), int(d_bytes.download(np.uint64, 1)[0]), d_image.download(np.uint8, cap + 64),
+                    d_idx.download(np.int32, n_out), d_st.download(np.int32, n_out), d_used.download(np.uint8, ne * n_out).reshape(ne, n_out))
+
+    @staticmethod
+    def _image_host(ctx, name, head, rect, blocks, mid, cap, n_out, old=None):
+        """The host scaffold of write_image_host and update_image_host: the image's room of cap bytes (old's bytes, then 0xA5),
+        name(ctx, *head, rect, blocks, *mid, image, cap, size, tile indices, status, codec used) -> (the call's return value, the
+        size the image has or needs, the room, tile indices, status, codec used)."""
+        image = np.full(max(cap, 1), 0xA5, np.uint8)
+        if old is not None:
+            image[:min(cap, old.size)] = old[:min(cap, old.size)]
+        idx, status = np.full(n_out, -1, np.int32), np.full(n_out, 0x7f7f7f7f, np.int32)
+        used = np.zeros((len(blocks), n_out), np.uint8)
+        need = C.c_uint64()
+        rc = getattr(lib(), name)(ctx.handle, *head, _ptr(rect), _ptrs(blocks), *mid, _ptr(image), cap, C.byref(need), _ptr(idx), _ptr(status),
+                                  _ptr(used))
+        return rc, need.value, image, idx, status, used
+
+    @staticmethod
     def write_image(ctx, facts, blocks, rect=None, flags=0, image_cap=None, raw=False):
         """gf_file_write_block_elems_dev: the image of a new file whose rectangle rect (None: the whole grid) holds blocks (per
         element [n_rows, n_cols]: int32 / int16 / float32, an "icf" element's float VALUES), written in device memory.  Uploads,
@@ -2021,23 +2056,9 @@ class GvrsFileHip:
         status, the size the image has or needs, the whole buffer of image_cap + 64 bytes pre-filled with 0xA5, tile indices,
         status, codec used) and a file status of ERR_CAPACITY does not raise."""
         rect, n_out = facts.rect_args(rect)
-        blocks = facts.blocks_in(rect, blocks)
         cap = facts.plan(rect, flags)[1] if image_cap is None else int(image_cap)
-        ne = len(blocks)
-        with _DeviceScope(ctx) as s:
-            d_blk = [s.upload(b, slack=16) for b in blocks]
-            d_image = s.alloc(cap + 64, fill=0xA5)
-            d_bytes = s.alloc(16, fill=0x7f)
-            d_fst = s.alloc(16, fill=0x7f)
-            d_idx = s.alloc(n_out * 4 + 16, fill=0x7f)
-            d_st = s.alloc(n_out * 4 + 16, fill=0x7f)
-            d_used = s.alloc(ne * n_out + 16, fill=0)
-            s.run("gf_file_write_block_elems_dev", ctx.handle, *facts.args(), _ptr(rect), s.ptrs(d_blk), int(flags), d_image.ptr, cap, d_bytes.ptr,
-                  d_fst.ptr, d_idx.ptr, d_st.ptr, d_used.ptr)
-            n_bytes, fst = int(d_bytes.download(np.uint64, 1)[0]), int(d_fst.download(np.int32, 1)[0])
-            image = d_image.download(np.uint8, cap + 64)
-            idx, status = d_idx.download(np.int32, n_out), d_st.download(np.int32, n_out)
-            used = d_used.download(np.uint8, ne * n_out).reshape(ne, n_out)
+        fst, n_bytes, image, idx, status, used = GvrsFileHip._image_dev(ctx, "gf_file_write_block_elems_dev", facts.args(), rect,
+                                                                        facts.blocks_in(rect, blocks), (int(flags),), cap, n_out)
         if raw:
             return fst, n_bytes, image, idx, status, used
         check(fst, "gf_file_write_block_elems_dev")
@@ -2049,17 +2070,12 @@ class GvrsFileHip:
         status, codec used); a negative per-tile status or too small an image_cap raises unless return_code is set: then (the call's
         return value, the size the image has or needs) come first."""
         rect, n_out = facts.rect_args(rect)
-        blocks = facts.blocks_in(rect, blocks)
         cap = facts.plan(rect, flags)[1] if image_cap is None else int(image_cap)
-        image = np.full(max(cap, 1), 0xA5, np.uint8)
-        idx, status = np.full(n_out, -1, np.int32), np.full(n_out, 0x7f7f7f7f, np.int32)
-        used = np.zeros((len(blocks), n_out), np.uint8)
-        need = C.c_uint64()
-        rc = lib().gf_file_write_block_elems(ctx.handle, *facts.args(), _ptr(rect), _ptrs(blocks), int(flags), _ptr(image), cap, C.byref(need),
-                                             _ptr(idx), _ptr(status), _ptr(used))
-        n = min(need.value, cap)
+        rc, need, image, idx, status, used = GvrsFileHip._image_host(ctx, "gf_file_write_block_elems", facts.args(), rect,
+                                                                     facts.blocks_in(rect, blocks), (int(flags),), cap, n_out)
+        n = min(need, cap)
         if return_code:
-            return rc, need.value, image[:n].tobytes(), idx, status, used
+            return rc, need, image[:n].tobytes(), idx, status, used
         check(rc, "gf_file_write_block_elems")
         return image[:n].tobytes(), idx, status, used
 
@@ -2114,31 +2130,20 @@ class GvrsFileHip:
                   d_fst.ptr)
             return int(d_fst.download(np.int32, 1)[0]), int(d_bytes.download(np.uint64, 1)[0]), d_image.download(np.uint8, cap + 64).tobytes()
 
+    def _update_args(self, upd, rect, blocks, image_cap):
+        image0, rect, nt, shape = self._read_args(rect, upd.image)
+        blocks = [np.ascontiguousarray(b, dt).reshape(shape) for b, dt in zip(blocks, self._dtypes)]
+        assert len(blocks) == self.n_elems
+        return image0, rect, nt, blocks, upd.plan(rect)[0] if image_cap is None else int(image_cap)
+
     def update_image(self, ctx, upd, rect, blocks, time_modified, flags=0, image_cap=None, raw=False):
         """gf_file_update_block_elems_dev: blocks (as update_image_host takes them) stored into rect of the image upd was begun on,
         in device memory.  Uploads, calls, synchronises, downloads: (image bytes, tile indices, status, codec used); raw: (file
         status, the size the image has or needs, the whole buffer of image_cap + 64 bytes -- the old image, then 0xA5 --, tile
         indices, status, codec used), and no file status raises."""
-        image0, rect, nt, shape = self._read_args(rect, upd.image)
-        blocks = [np.ascontiguousarray(b, dt).reshape(shape) for b, dt in zip(blocks, self._dtypes)]
-        assert len(blocks) == self.n_elems
-        cap = upd.plan(rect)[0] if image_cap is None else int(image_cap)
-        buf = np.full(cap + 64, 0xA5, np.uint8)
-        buf[:min(cap, image0.size)] = image0[:min(cap, image0.size)]
-        with _DeviceScope(ctx) as s:
-            d_blk = [s.upload(b, slack=16) for b in blocks]
-            d_image = s.upload(buf)
-            d_bytes = s.alloc(16, fill=0x7f)
-            d_fst = s.alloc(16, fill=0x7f)
-            d_idx = s.alloc(nt * 4 + 16, fill=0x7f)
-            d_st = s.alloc(nt * 4 + 16, fill=0x7f)
-            d_used = s.alloc(self.n_elems * nt + 16, fill=0)
-            s.run("gf_file_update_block_elems_dev", ctx.handle, upd.handle, _ptr(rect), s.ptrs(d_blk), int(flags), int(time_modified), d_image.ptr,
-                  cap, d_bytes.ptr, d_fst.ptr, d_idx.ptr, d_st.ptr, d_used.ptr)
-            n_bytes, fst = int(d_bytes.download(np.uint64, 1)[0]), int(d_fst.download(np.int32, 1)[0])
-            image = d_image.download(np.uint8, cap + 64)
-            idx, status = d_idx.download(np.int32, nt), d_st.download(np.int32, nt)
-            used = d_used.download(np.uint8, self.n_elems * nt).reshape(self.n_elems, nt)
+        image0, rect, nt, blocks, cap = self._update_args(upd, rect, blocks, image_cap)
+        fst, n_bytes, image, idx, status, used = self._image_dev(ctx, "gf_file_update_block_elems_dev", (upd.handle,), rect, blocks,
+                                                                 (int(flags), int(time_modified)), cap, nt, old=image0)
         if raw:
             return fst, n_bytes, image.tobytes(), idx, status, used
         check(fst, "gf_file_update_block_elems_dev")
@@ -2149,20 +2154,12 @@ class GvrsFileHip:
         VALUES) stored into rect = (row0, col0, n_rows, n_cols) of the image upd was begun on, in host memory, any codec list ->
         (image bytes, tile indices, status, codec used); a negative per-tile status raises unless return_code is set: then (the
         call's return value, the size the image has or needs) come first."""
-        image0, rect, nt, shape = self._read_args(rect, upd.image)
-        blocks = [np.ascontiguousarray(b, dt).reshape(shape) for b, dt in zip(blocks, self._dtypes)]
-        assert len(blocks) == self.n_elems
-        cap = upd.plan(rect)[0] if image_cap is None else int(image_cap)
-        image = np.full(max(cap, 1), 0xA5, np.uint8)
-        image[:min(cap, image0.size)] = image0[:min(cap, image0.size)]
-        idx, status = np.full(nt, -1, np.int32), np.full(nt, 0x7f7f7f7f, np.int32)
-        used = np.zeros((self.n_elems, nt), np.uint8)
-        need = C.c_uint64()
-        rc = lib().gf_file_update_block_elems(ctx.handle, upd.handle, _ptr(rect), _ptrs(blocks), int(flags), int(time_modified), _ptr(image), cap,
-                                              C.byref(need), _ptr(idx), _ptr(status), _ptr(used))
-        n = min(need.value, cap) if rc != _lib.ERR_CAPACITY else min(image0.size, cap)
+        image0, rect, nt, blocks, cap = self._update_args(upd, rect, blocks, image_cap)
+        rc, need, image, idx, status, used = self._image_host(ctx, "gf_file_update_block_elems", (upd.handle,), rect, blocks,
+                                                              (int(flags), int(time_modified)), cap, nt, old=image0)
+        n = min(need, cap) if rc != _lib.ERR_CAPACITY else min(image0.size, cap)
         if return_code:
-            return rc, need.value, image[:n].tobytes(), idx, status, used
+            return rc, need, image[:n].tobytes(), idx, status, used
         check(rc, "gf_file_update_block_elems")
         return image[:n].tobytes(), idx, status, used
 

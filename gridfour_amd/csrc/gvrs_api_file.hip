@@ -32,6 +32,20 @@ gf_status fileReadArgs(const gf_context *c, const gf_file *f, const uint8_t *ima
 
 }  // namespace
 
+gf_status fileLocateDev(gf_context *c, hipStream_t st, const gf_file_info &i, const uint8_t *dImage, size_t imageBytes, const GfBlockGeom &g,
+                        uint8_t *dPresent, GfFileLocateArgs &a)
+{
+    const size_t T = (size_t)g.nTileRows * (size_t)g.nTileCols;
+    Carve k;
+    const size_t startsAt = k.add(T * 8), endsAt = k.add(T * 8), verdictAt = k.add(T * 4);
+    const gf_status s = c->dFileLoc.ensure(k);
+    if (s != GF_OK) return s;
+    a = GfFileLocateArgs{dImage, imageBytes, gfFileDirOf(i), g.tileRow0, g.tileCol0, g.nTileRows, g.nTileCols, c->dFileLoc.at<uint64_t>(startsAt),
+                         c->dFileLoc.at<uint64_t>(endsAt), c->dFileLoc.at<int32_t>(verdictAt), dPresent};
+    GF_HIP(gf_launch_file_locate(a, st));
+    return GF_OK;
+}
+
 extern "C" {
 
 gf_status gf_file_open(const uint8_t *image, size_t imageBytes, gf_file **out)
@@ -68,12 +82,9 @@ gf_status gf_file_tile_position(const gf_file *f, const uint8_t *image, size_t i
 {
     if (!f || !image || !pos) return GF_ERR_ARG;
     *pos = 0;
-    const gf_grid_spec &g = f->p.info.grid;
-    const GfFileDir d = gfFileDirOf(f->p.info);
-    const int64_t nTiles = gfTilesOfGrid(g).count();
-    if (tileIndex < 0 || tileIndex >= nTiles) return GF_ERR_ARG;
+    if (tileIndex < 0 || tileIndex >= gfTilesOfGrid(f->p.info.grid).count()) return GF_ERR_ARG;
     uint32_t size;
-    return gfFileLocate(d, image, imageBytes, tileIndex, pos, &size);
+    return gfFileLocate(gfFileDirOf(f->p.info), image, imageBytes, tileIndex, pos, &size);
 }
 
 gf_status gf_file_read_block_elems_dev(gf_context *c, const gf_file *f, const uint8_t *dImage, size_t imageBytes,
@@ -91,22 +102,8 @@ gf_status gf_file_read_block_elems_dev(gf_context *c, const gf_file *f, const ui
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
     const hipStream_t st = c->stream;
-    // per slot of the rectangle of tiles: the record's extent and the verdict on its directory entry
-    Carve k;
-    const size_t startsAt = k.add(T * 8), endsAt = k.add(T * 8), verdictAt = k.add(T * 4);
-    if ((s = c->dFileLoc.ensure(k)) != GF_OK) return s;
-    const GfFileDir d = gfFileDirOf(i);
-    GfFileLocateArgs a{};
-    a.image = dImage;
-    a.imageBytes = imageBytes;
-    a.entriesPos = d.entriesPos, a.contentPos = d.contentPos;
-    a.extended = d.extended, a.dirRow0 = d.row0, a.dirCol0 = d.col0, a.dirNRows = d.nRows, a.dirNCols = d.nCols;
-    a.nColsOfTiles = d.nColsOfTiles;
-    a.tileRow0 = g.tileRow0, a.tileCol0 = g.tileCol0, a.nTileRows = g.nTileRows, a.nTileCols = g.nTileCols;
-    a.starts = c->dFileLoc.at<uint64_t>(startsAt), a.ends = c->dFileLoc.at<uint64_t>(endsAt);
-    a.verdict = c->dFileLoc.at<int32_t>(verdictAt);
-    a.present = dPresent;
-    GF_HIP(gf_launch_file_locate(a, st));
+    GfFileLocateArgs a;
+    if ((s = fileLocateDev(c, st, i, dImage, imageBytes, g, dPresent, a)) != GF_OK) return s;
     // the dense list: every slot is a record of the batch, the ones without a record as empty extents whose status k_file_status
     // puts right behind the pipeline -- the host need not know how many tiles are present, and the call synchronises once
     return blockReadDev(c, st, codecs, i.n_codecs, i.elems, i.n_elems, g, fill, T, dImage, imageBytes, a.starts, verifyChecksum, dBlocks,
@@ -125,16 +122,11 @@ gf_status gf_file_read_block_elems(gf_context *c, const gf_file *f, const uint8_
     if (!i.checksum_enabled) verifyChecksum = 0;
     const size_t T = (size_t)g.nTileRows * (size_t)g.nTileCols, nElems = (size_t)i.n_elems;
     if (T > 0x7fffffffull / nElems) return GF_ERR_UNSUPPORTED;
-    // The rectangle's tiles looked up in the host image, judged as k_file_locate and the framing walk judge them.  A record the
-    // walk would refuse for its size word is refused here, so that the staged records are whole, multiples of 8 and end to end.
-    const GfFileDir d = gfFileDirOf(i);
+    // The rectangle's tiles looked up in the host image.  A record the framing walk would refuse for its size word is refused
+    // here, so that the staged records are whole, multiples of 8 and end to end.
     std::vector<int32_t> verdict(T);
     std::vector<uint64_t> from, offsets(1, 0);
-    for (size_t j = 0; j < T; j++) {
-        const int32_t tileIndex = (g.tileRow0 + (int32_t)(j / (size_t)g.nTileCols)) * g.nColsOfTiles + g.tileCol0 + (int32_t)(j % (size_t)g.nTileCols);
-        uint64_t pos;
-        uint32_t size;
-        int32_t v = gfFileLocate(d, image, imageBytes, tileIndex, &pos, &size);
+    gfFileLocateRect(gfFileDirOf(i), image, imageBytes, g.tileRow0, g.tileCol0, g.nTileRows, g.nTileCols, [&](size_t j, int32_t v, uint64_t pos, uint32_t size) {
         if (present) present[j] = pos != 0;
         if (v == GF_OK && pos != 0) {
             if (size < 20u || (size & 7u) != 0u || (uint64_t)size > imageBytes - (pos - 8)) v = GF_ERR_BOUNDS;
@@ -145,7 +137,7 @@ gf_status gf_file_read_block_elems(gf_context *c, const gf_file *f, const uint8_
             }
         }
         verdict[j] = v;
-    }
+    });
     const size_t nRec = from.size(), blobBytes = (size_t)offsets.back();
     std::vector<uint8_t> blob(blobBytes + 16);
     for (size_t r = 0; r < nRec; r++) memcpy(blob.data() + offsets[r], image + from[r], (size_t)(offsets[r + 1] - offsets[r]));

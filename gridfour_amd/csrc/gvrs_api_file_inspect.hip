@@ -42,7 +42,6 @@ gf_status gf_file_inspect_dev(gf_context *c, const gf_file *f, const uint8_t *dI
     const uint64_t room = maxRecords ? maxRecords : std::max<uint64_t>(defaultMax, 1);
     if (room > 0x7ffffffeull) return GF_ERR_UNSUPPORTED;
     const uint64_t span = imageBytes - i.content_pos, nSeg = std::max<uint64_t>((span + segBytes - 1) / segBytes, 1);
-    const GfFileDir d = gfFileDirOf(i);
     GF_CTX_LOCK(c);
     GF_HIP(hipSetDevice(c->device));
     const hipStream_t st = c->stream;
@@ -55,8 +54,7 @@ gf_status gf_file_inspect_dev(gf_context *c, const gf_file *f, const uint8_t *dI
     GfInspectArgs a{};
     a.image = dImage;
     a.p = gfInspectParamsOf(i, imageBytes);
-    a.entriesPos = d.entriesPos, a.metaDirPos = i.metadata_dir_pos, a.freeDirPos = i.freespace_dir_pos;
-    a.extended = d.extended, a.dirRow0 = d.row0, a.dirCol0 = d.col0, a.dirNRows = d.nRows, a.dirNCols = d.nCols, a.nColsOfTiles = d.nColsOfTiles;
+    a.dir = gfFileDirOf(i), a.metaDirPos = i.metadata_dir_pos, a.freeDirPos = i.freespace_dir_pos;
     a.segBytes = segBytes, a.maxRecords = room, a.nSeg = (uint32_t)nSeg;
     a.state = c->dFileInspect.at<GfInspectState>(stateAt);
     a.acc = c->dFileInspect.at<uint32_t>(accAt);

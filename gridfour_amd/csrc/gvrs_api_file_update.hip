@@ -49,10 +49,10 @@ gf_status gf_file_update_plan(const gf_file_update *u, const gf_rect *rect, uint
     const gf_file_info &i = u->u.info;
     const gf_rect whole{0, 0, i.grid.n_rows_grid, i.grid.n_cols_grid};
     GfBlockGeom g{};
-    const gf_status s = blockGeom(&i.grid, rect ? rect : &whole, g);
+    gf_status s = blockGeom(&i.grid, rect ? rect : &whole, g);
     if (s != GF_OK) return s;
-    const size_t maxRecord = gf_tile_record_max_bytes_elems(i.elems, i.n_elems, g.nRowsTile, g.nColsTile);
-    if (maxRecord == 0 || maxRecord > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
+    size_t maxRecord;
+    if ((s = fileMaxRecord(i.elems, i.n_elems, g, maxRecord)) != GF_OK) return s;
     gfFileUpdatePlan(u->u, (uint64_t)g.nTileRows * (uint64_t)g.nTileCols, maxRecord, maxImageBytes, freeListCapacity);
     return GF_OK;
 }
@@ -77,7 +77,6 @@ static gf_status updateRecordsDev(gf_context *c, const GfFileUpdate &h, uint8_t 
     const size_t need = h.freePos.size() + nRecords + 3, cap = listCapacity ? listCapacity : need;
     if (cap < need) return GF_ERR_ARG;
     if (nRecords > 0x7fffffffull || cap > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
-    const GfFileDir d = gfFileDirOf(i);
     const uint64_t nTilesGrid = (uint64_t)gfTilesOfGrid(i.grid).count();
     if (gfFileTileDirSize(nTilesGrid, true) > 0x7fffffffull) return GF_ERR_UNSUPPORTED;   // (a record's size is an int32)
     GF_HIP(hipSetDevice(c->device));
@@ -93,10 +92,8 @@ static gf_status updateRecordsDev(gf_context *c, const GfFileUpdate &h, uint8_t 
     if (s != GF_OK) return s;
     GfFileUpdateArgs a{};
     a.image = dImage;
-    a.imageCap = imageCap, a.oldBytes = h.imageBytes, a.contentPos = i.content_pos;
-    a.entriesPos = d.entriesPos;
-    a.oldExtended = d.extended, a.dirRow0 = d.row0, a.dirCol0 = d.col0, a.dirNRows = d.nRows, a.dirNCols = d.nCols;
-    a.nColsOfTiles = d.nColsOfTiles, a.nTilesGrid = (int32_t)nTilesGrid;
+    a.imageCap = imageCap, a.oldBytes = h.imageBytes;
+    a.dir = gfFileDirOf(i), a.nTilesGrid = (int32_t)nTilesGrid;
     a.checksums = i.checksum_enabled ? 1 : 0, a.compression = i.n_codecs > 0 ? 1 : 0, a.forceExtended = (flags & GF_FILE_DIR_EXTENDED) ? 1 : 0;
     a.timeModified = timeModified;
     a.blob = dBlob, a.offsets = dOffsets, a.tiles = dTileIndices, a.status = dStatus, a.tileStatus = dTileStatus;
@@ -111,26 +108,9 @@ static gf_status updateRecordsDev(gf_context *c, const GfFileUpdate &h, uint8_t 
     a.metaDirBytes = (uint32_t)h.metaDir.size();
     a.chunkCrc = c->dFileUpdate.at<uint32_t>(chunksAt);
     a.imageBytes = dImageBytes, a.fileStatus = dFileStatus;
-    // The opened list and the metadata directory travel through the page-locked buffer that a written file's front uses, so that
-    // the copies are enqueued like the kernels; the one wait: an EARLIER call's copies must have left that buffer.
-    if (nOpened || !h.metaDir.empty()) {
-        if (!c->fileFrontDone) GF_HIP(hipEventCreateWithFlags(&c->fileFrontDone, hipEventDisableTiming));
-        GF_HIP(hipEventSynchronize(c->fileFrontDone));
-        Carve hc;
-        const size_t hPosAt = hc.add(nOpened * 8), hSizeAt = hc.add(nOpened * 8), hMetaAt = hc.add(h.metaDir.size());
-        if ((s = c->hFileFront.ensure(hc, 16)) != GF_OK) return s;
-        if (nOpened) {
-            memcpy(c->hFileFront.at<uint8_t>(hPosAt), h.freePos.data(), nOpened * 8);
-            memcpy(c->hFileFront.at<uint8_t>(hSizeAt), h.freeSize.data(), nOpened * 8);
-            GF_HIP(hipMemcpyAsync(a.listPos, c->hFileFront.at<uint8_t>(hPosAt), nOpened * 8, hipMemcpyHostToDevice, st));
-            GF_HIP(hipMemcpyAsync(a.listSize, c->hFileFront.at<uint8_t>(hSizeAt), nOpened * 8, hipMemcpyHostToDevice, st));
-        }
-        if (!h.metaDir.empty()) {
-            memcpy(c->hFileFront.at<uint8_t>(hMetaAt), h.metaDir.data(), h.metaDir.size());
-            GF_HIP(hipMemcpyAsync(const_cast<uint8_t *>(a.metaDir), c->hFileFront.at<uint8_t>(hMetaAt), h.metaDir.size(), hipMemcpyHostToDevice, st));
-        }
-        GF_HIP(hipEventRecord(c->fileFrontDone, st));
-    }
+    // the opened list and the metadata directory travel through the page-locked buffer that a written file's front uses
+    if ((s = fileFrontSend(c, st, {{h.freePos.data(), a.listPos, nOpened * 8}, {h.freeSize.data(), a.listSize, nOpened * 8},
+                                   {h.metaDir.data(), const_cast<uint8_t *>(a.metaDir), h.metaDir.size()}})) != GF_OK) return s;
     GF_HIP(hipMemsetAsync(a.seen, 0, nTilesGrid * 4, st));
     GF_HIP(gf_launch_file_update(a, st));
     return GF_OK;
@@ -166,8 +146,8 @@ gf_status gf_file_update_block_elems_dev(gf_context *c, const gf_file_update *u,
     if (s != GF_OK) return s;
     if (!deviceList(i.codecs, i.n_codecs, i.elems, i.n_elems)) return GF_ERR_UNSUPPORTED;
     const size_t T = (size_t)g.nTileRows * (size_t)g.nTileCols;
-    const size_t maxRecord = gf_tile_record_max_bytes_elems(i.elems, i.n_elems, g.nRowsTile, g.nColsTile);
-    if (maxRecord == 0 || maxRecord > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
+    size_t maxRecord;
+    if ((s = fileMaxRecord(i.elems, i.n_elems, g, maxRecord)) != GF_OK) return s;
     // Only a rectangle whose four sides lie on tile seams needs no old cell: it decodes nothing and never synchronises.  A tile that
     // the grid's edge cuts keeps its old cells beyond the grid, as the reference's tile does, so a rectangle that ends at such an edge
     // takes the old records' route.
@@ -185,21 +165,8 @@ gf_status gf_file_update_block_elems_dev(gf_context *c, const gf_file_update *u,
     if (!aligned) {
         // the old records of the rectangle's tiles where they lie in the image (k_file_locate): a dense list, a tile without a
         // record or with a refused entry as an empty extent, which names no tile and leaves its slot a new tile to the merge
-        Carve k;
-        const size_t startsAt = k.add(T * 8), endsAt = k.add(T * 8), verdictAt = k.add(T * 4);
-        if ((s = c->dFileLoc.ensure(k)) != GF_OK) return s;
-        const GfFileDir d = gfFileDirOf(i);
-        GfFileLocateArgs a{};
-        a.image = dImage;
-        a.imageBytes = h.imageBytes;
-        a.entriesPos = d.entriesPos, a.contentPos = d.contentPos;
-        a.extended = d.extended, a.dirRow0 = d.row0, a.dirCol0 = d.col0, a.dirNRows = d.nRows, a.dirNCols = d.nCols;
-        a.nColsOfTiles = d.nColsOfTiles;
-        a.tileRow0 = g.tileRow0, a.tileCol0 = g.tileCol0, a.nTileRows = g.nTileRows, a.nTileCols = g.nTileCols;
-        a.starts = c->dFileLoc.at<uint64_t>(startsAt), a.ends = c->dFileLoc.at<uint64_t>(endsAt);
-        a.verdict = c->dFileLoc.at<int32_t>(verdictAt);
-        a.present = nullptr;
-        GF_HIP(gf_launch_file_locate(a, st));
+        GfFileLocateArgs a;
+        if ((s = fileLocateDev(c, st, i, dImage, (size_t)h.imageBytes, g, nullptr, a)) != GF_OK) return s;
         dStarts = a.starts, dEnds = a.ends;
     }
     s = blockWriteDev(c, st, i.codecs, i.n_codecs, i.elems, i.n_elems, g, cut, dBlocks, aligned ? 0 : T, aligned ? nullptr : dImage,
@@ -226,27 +193,22 @@ gf_status gf_file_update_block_elems(gf_context *c, const gf_file_update *u, con
     gf_status s = blockGeom(&i.grid, rect, g);
     if (s != GF_OK) return s;
     const size_t T = (size_t)g.nTileRows * (size_t)g.nTileCols;
-    const size_t maxRecord = gf_tile_record_max_bytes_elems(i.elems, i.n_elems, g.nRowsTile, g.nColsTile);
-    if (maxRecord == 0 || maxRecord > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
-    // The old records of the rectangle's tiles, looked up and judged by their heads as the assembler will judge them: a tile whose
-    // entry or head is refused keeps its verdict and stays as it is.  The block write merges the old cells of partly covered tiles
-    // and decodes and ignores the others.
-    const GfFileDir d = gfFileDirOf(i);
+    size_t maxRecord;
+    if ((s = fileMaxRecord(i.elems, i.n_elems, g, maxRecord)) != GF_OK) return s;
+    // The old records of the rectangle's tiles, looked up and judged by their heads: a tile whose entry or head is refused keeps
+    // its verdict and stays as it is.  The block write merges the old cells of partly covered tiles and decodes and ignores the others.
     std::vector<int32_t> verdict(T, GF_OK);
     std::vector<uint8_t> oldBlob;
     std::vector<uint64_t> oldOffsets(1, 0);
-    for (size_t j = 0; j < T; j++) {
-        const int32_t tileIndex = (g.tileRow0 + (int32_t)(j / (size_t)g.nTileCols)) * g.nColsOfTiles + g.tileCol0 + (int32_t)(j % (size_t)g.nTileCols);
-        uint64_t pos, size = 0;
-        uint32_t sizeWord;
-        gf_status v = gfFileLocate(d, image, u->u.imageBytes, tileIndex, &pos, &sizeWord);
-        if (v == GF_OK && pos != 0) v = gfFsRecordHead(image, u->u.imageBytes, i.content_pos, pos, GF_FILE_REC_TILE, 24, &size);
+    gfFileLocateRect(gfFileDirOf(i), image, u->u.imageBytes, g.tileRow0, g.tileCol0, g.nTileRows, g.nTileCols, [&](size_t j, gf_status v, uint64_t pos, uint32_t) {
+        uint64_t size = 0;
+        if (v == GF_OK && pos != 0) v = gfFsRecordHead(u->u.imageBytes, i.content_pos, pos, GF_FILE_REC_TILE, 24, &size, GfLoadLe{image});
         verdict[j] = v;
         if (v == GF_OK && pos != 0) {
             oldBlob.insert(oldBlob.end(), image + pos - 8, image + pos - 8 + size);
             oldOffsets.push_back(oldBlob.size());
         }
-    }
+    });
     const size_t nOld = oldOffsets.size() - 1;
     std::vector<uint8_t> blob(T * maxRecord + 16);
     std::vector<uint64_t> offsets(T + 1, 0);

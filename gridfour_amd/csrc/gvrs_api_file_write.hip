@@ -27,6 +27,27 @@ gf_rect wholeGrid(const gf_grid_spec &g) { return gf_rect{0, 0, g.n_rows_grid, g
 
 }  // namespace
 
+// The parts are copied into the page-locked buffer and from there with hipMemcpyAsync.  The one wait of such a call: an EARLIER
+// call's copies must have left that buffer.
+gf_status fileFrontSend(gf_context *c, hipStream_t st, std::initializer_list<FileFrontPart> parts)
+{
+    Carve h, at;
+    for (const FileFrontPart &p : parts) h.add(p.bytes);
+    if (h.total == 0) return GF_OK;
+    if (!c->fileFrontDone) GF_HIP(hipEventCreateWithFlags(&c->fileFrontDone, hipEventDisableTiming));
+    GF_HIP(hipEventSynchronize(c->fileFrontDone));
+    const gf_status s = c->hFileFront.ensure(h, 16);
+    if (s != GF_OK) return s;
+    for (const FileFrontPart &p : parts) {
+        uint8_t *via = c->hFileFront.at<uint8_t>(at.add(p.bytes));
+        if (p.bytes == 0) continue;
+        memcpy(via, p.host, p.bytes);
+        GF_HIP(hipMemcpyAsync(p.dev, via, p.bytes, hipMemcpyHostToDevice, st));
+    }
+    GF_HIP(hipEventRecord(c->fileFrontDone, st));
+    return GF_OK;
+}
+
 extern "C" {
 
 gf_status gf_file_write_plan(const gf_file_facts *facts, const gf_file_metadata *metadata, int nMeta, const gf_rect *rect, int flags,
@@ -39,8 +60,8 @@ gf_status gf_file_write_plan(const gf_file_facts *facts, const gf_file_metadata 
     const gf_rect whole = wholeGrid(facts->grid);
     GfBlockGeom g{};
     if ((s = blockGeom(&facts->grid, rect ? rect : &whole, g)) != GF_OK) return s;
-    const size_t maxRecord = gf_tile_record_max_bytes_elems(facts->elems, facts->n_elems, g.nRowsTile, g.nColsTile);
-    if (maxRecord == 0 || maxRecord > 0x7fffffffull) return GF_ERR_UNSUPPORTED;
+    size_t maxRecord;
+    if ((s = fileMaxRecord(facts->elems, facts->n_elems, g, maxRecord)) != GF_OK) return s;
     GfFileFront w;
     gfFileEmitFront(*facts, metadata, nMeta, w);
     gfFilePlan(w, (uint64_t)g.nTileRows * (uint64_t)g.nTileCols, maxRecord, flags, firstRecordPos, maxImageBytes);
@@ -108,26 +129,16 @@ gf_status gf_file_write_block_elems_dev(gf_context *c, const gf_file_facts *fact
     GF_HIP(hipMemsetAsync(a.state, 0, sizeof(GfFileWriteState), st));
     // The front -- the header record and the metadata records without the file head (k_file_finish writes it, and only into an image
     // that fits), and the metadata directory.  A short one travels in k_file_finish's arguments.  A long one (large metadata) is
-    // copied now, as far as the image reaches, through a page-locked buffer of the context, so that the copies are enqueued like
-    // the kernels; the one wait of such a call: an EARLIER call's copies must have left that buffer.
+    // copied now, as far as the image reaches, through the context's page-locked buffer (fileFrontSend).
     const bool inArgs = p0 - 16 + w.metaDir.size() <= GF_FILE_FRONT_ARG_BYTES;
     std::vector<uint8_t> frontArg;
     if (inArgs) {
         frontArg.assign(w.front.begin() + 16, w.front.end());
         frontArg.insert(frontArg.end(), w.metaDir.begin(), w.metaDir.end());
     } else {
-        if (!c->fileFrontDone) GF_HIP(hipEventCreateWithFlags(&c->fileFrontDone, hipEventDisableTiming));
-        GF_HIP(hipEventSynchronize(c->fileFrontDone));
-        Carve h;
-        const size_t frontAt = h.add(w.front.size()), metaDirFrom = h.add(w.metaDir.size());
-        if ((s = c->hFileFront.ensure(h, 16)) != GF_OK) return s;
-        memcpy(c->hFileFront.at<uint8_t>(frontAt), w.front.data(), w.front.size());
-        if (!w.metaDir.empty()) memcpy(c->hFileFront.at<uint8_t>(metaDirFrom), w.metaDir.data(), w.metaDir.size());
         const size_t frontBytes = (size_t)std::min<uint64_t>(p0, imageCap);
-        if (frontBytes > 16) GF_HIP(hipMemcpyAsync(dImage + 16, c->hFileFront.at<uint8_t>(frontAt + 16), frontBytes - 16, hipMemcpyHostToDevice, st));
-        if (!w.metaDir.empty())
-            GF_HIP(hipMemcpyAsync(const_cast<uint8_t *>(a.metaDir), c->hFileFront.at<uint8_t>(metaDirFrom), w.metaDir.size(), hipMemcpyHostToDevice, st));
-        GF_HIP(hipEventRecord(c->fileFrontDone, st));
+        if ((s = fileFrontSend(c, st, {{w.front.data() + 16, dImage + 16, frontBytes > 16 ? frontBytes - 16 : 0},
+                                       {w.metaDir.data(), const_cast<uint8_t *>(a.metaDir), w.metaDir.size()}})) != GF_OK) return s;
     }
     s = blockWriteDev(c, st, kinds, facts->n_codecs, facts->elems, facts->n_elems, g, cut, dBlocks, 0, nullptr, 0, nullptr, 0, a.checksums, dImage + p0,
                       blobCap, dOffsets, dTileIndices, dCodecUsed, dStatus);

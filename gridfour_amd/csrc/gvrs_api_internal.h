@@ -342,6 +342,18 @@ gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCod
                         const GfBlockCutElem *cut, const void *const *dBlocks, size_t nOld, const uint8_t *dOldBlob, size_t oldBlobBytes,
                         const uint64_t *dOldOffsets, int verifyOldChecksum, int checksumEnabled, uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets,
                         int32_t *dTileIndices, uint8_t *dCodecUsed, int32_t *dStatus, const uint64_t *dOldEnds = nullptr);
+// gvrs_api_file.hip: k_file_locate for the rectangle's tiles on a stream (no lock taken): a.starts, a.ends, a.verdict lie in dFileLoc
+gf_status fileLocateDev(gf_context *c, hipStream_t st, const gf_file_info &i, const uint8_t *dImage, size_t imageBytes, const GfBlockGeom &g,
+                        uint8_t *dPresent, GfFileLocateArgs &a);
+// gvrs_api_file_write.hip: host bytes to device memory through the context's page-locked hFileFront, enqueued like the kernels
+struct FileFrontPart { const void *host; void *dev; size_t bytes; };   // (0 bytes: nothing travels)
+gf_status fileFrontSend(gf_context *c, hipStream_t st, std::initializer_list<FileFrontPart> parts);
+// the largest tile record of a file with these elements and tiles, refused where its size does not travel as an int32
+inline gf_status fileMaxRecord(const gf_elem_spec *elems, int nElems, const GfBlockGeom &g, size_t &maxRecord)
+{
+    maxRecord = gf_tile_record_max_bytes_elems(elems, nElems, g.nRowsTile, g.nColsTile);
+    return maxRecord == 0 || maxRecord > 0x7fffffffull ? GF_ERR_UNSUPPORTED : GF_OK;
+}
 // gvrs_api_interp.hip: what the host can check of an interpolation spec (fills g)
 gf_status interpSpecArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, GfInterpGeom &g);
 // gvrs_api_records.hip

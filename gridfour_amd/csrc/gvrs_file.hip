@@ -15,15 +15,11 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // k_file_locate: a lane per tile of the block's rectangle of tiles, slot j = row-major.  The lanes of a wave run along a tile row,
 // so their directory entries are neighbours: one coalesced 4- or 8-byte load each (the entries start at a multiple of 8 of an
-// 8-byte aligned image).  A position is judged BEFORE anything is read there: at least contentPos + 8 (a record's content lies
-// behind its 8-byte head, and no record lies in the header), a multiple of 8, and position + 12 <= imageBytes (size word, type,
-// tile index) -- else GF_K_ERR_BOUNDS and nothing of the tile is read.  An entry that itself lies outside the image is
-// GF_K_ERR_BOUNDS too.  Then the record head in one 16-byte load at position - 8 (8-byte aligned; it ends at position + 8, inside
-// the image): the tile-index word must be the slot's tile index, else GF_K_ERR_FORMAT -- a directory whose entry leads to another
-// tile's record, or to no record at all.  The size word is NOT judged here: the extent [position - 8, min(imageBytes, position
-// - 8 + size)) goes to the framing walk, which refuses a size that is too small, no multiple of 8 or longer than its extent, and
-// judges the type byte.  Every slot gets an extent (the empty one unless located), a verdict and its present flag: the list
-// stays dense, nothing is compacted and the host learns nothing from this kernel.
+// 8-byte aligned image).  The tile is looked up by gfFileLocateHead (gvrs_file_parse.h), the head in one 16-byte load; a tile
+// that is present and passes is GF_FILE_LOCATED.  The size word is not judged here: the extent [position - 8, min(imageBytes,
+// position - 8 + size)) goes to the framing walk, which refuses a size that is too small, no multiple of 8 or longer than its
+// extent, and judges the type byte.  Every slot gets an extent (the empty one unless located), a verdict and its present flag: the
+// list stays dense, nothing is compacted and the host learns nothing from this kernel.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_file_locate(const GfFileLocateArgs a)
 {
@@ -31,37 +27,20 @@ __global__ __launch_bounds__(256) void k_file_locate(const GfFileLocateArgs a)
     if (j >= (uint32_t)a.nTileRows * (uint32_t)a.nTileCols) return;
     const int32_t ty = (int32_t)(j / (uint32_t)a.nTileCols), tx = (int32_t)(j - (uint32_t)ty * (uint32_t)a.nTileCols);
     const int32_t tileRow = a.tileRow0 + ty, tileCol = a.tileCol0 + tx;
-    const int32_t tileIndex = tileRow * a.nColsOfTiles + tileCol;                     // (< the grid's tiles <= 0x7fffffff)
-    const int32_t dr = tileRow - a.dirRow0, dc = tileCol - a.dirCol0;
-    uint64_t start = 0, end = 0;
-    int32_t verdict = GF_K_OK;
-    uint8_t present = 0;
-    if (dr >= 0 && dr < a.dirNRows && dc >= 0 && dc < a.dirNCols) {
-        const uint64_t w = a.extended ? 8u : 4u, at = a.entriesPos + ((uint64_t)dr * (uint64_t)a.dirNCols + (uint64_t)dc) * w;
-        if (at > a.imageBytes || w > a.imageBytes - at) verdict = GF_K_ERR_BOUNDS;
-        else {
-            const uint64_t p = a.extended ? *reinterpret_cast<const uint64_t *>(a.image + at)
-                                          : (uint64_t) * reinterpret_cast<const uint32_t *>(a.image + at) * 8u;
-            if (p != 0) {
-                present = 1;
-                if (p < a.contentPos + 8u || (p & 7u) != 0u || p > a.imageBytes || a.imageBytes - p < 12u) verdict = GF_K_ERR_BOUNDS;
-                else {
-                    const GfU4 h = *reinterpret_cast<const GfU4 *>(a.image + (p - 8u));
-                    if ((int32_t)h.z != tileIndex) verdict = GF_K_ERR_FORMAT;
-                    else {
-                        const uint64_t e = (p - 8u) + (uint64_t)h.x;
-                        start = p - 8u;
-                        end = e < a.imageBytes ? e : a.imageBytes;
-                        verdict = GF_FILE_LOCATED;
-                    }
-                }
-            }
-        }
+    const int32_t tileIndex = tileRow * a.dir.nColsOfTiles + tileCol;                 // (< the grid's tiles <= 0x7fffffff)
+    uint64_t p, start = 0, end = 0;
+    GfU4 h;
+    int32_t verdict = gfFileLocateHead(a.dir, a.imageBytes, gfDirEntryAt(a.dir, tileRow, tileCol), tileIndex, &p, &h, GfLoadAligned{a.image});
+    if (verdict == GF_K_OK && p != 0) {
+        const uint64_t e = (p - 8u) + (uint64_t)h.x;
+        start = p - 8u;
+        end = e < a.imageBytes ? e : a.imageBytes;
+        verdict = GF_FILE_LOCATED;
     }
     a.starts[j] = start;
     a.ends[j] = end;
     a.verdict[j] = verdict;
-    if (a.present) a.present[j] = present;
+    if (a.present) a.present[j] = p != 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -82,8 +61,8 @@ __global__ __launch_bounds__(256) void k_file_status(const int32_t *__restrict__
 hipError_t gf_launch_file_locate(const GfFileLocateArgs &a, hipStream_t stream)
 {
     const uint64_t n = (uint64_t)a.nTileRows * (uint64_t)a.nTileCols;
-    if (a.nTileRows < 1 || a.nTileCols < 1 || n > 0x7fffffffull || a.nColsOfTiles < 1) return hipErrorInvalidValue;
-    if (((uintptr_t)a.image & 7u) != 0 || (a.entriesPos & 7u) != 0) return hipErrorInvalidValue;
+    if (a.nTileRows < 1 || a.nTileCols < 1 || n > 0x7fffffffull || a.dir.nColsOfTiles < 1) return hipErrorInvalidValue;
+    if (((uintptr_t)a.image & 7u) != 0 || !gfDirEntriesAligned(a.dir)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_file_locate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
     return hipGetLastError();
 }

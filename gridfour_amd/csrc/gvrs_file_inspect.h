@@ -2,7 +2,7 @@
 // first byte of content to the end, each judged by its head and, where the specification enables checksums, by its CRC-32C; the
 // verdict says whether the file is sound, which tiles are bad and where the walk had to stop.  Host arithmetic on bytes: no HIP
 // header, so that tests/csrc/file_inspect_test.cpp runs it under the sanitizers on any machine.  The judgement of ONE record's head
-// (gfInspectStep) is shared with the kernels of gvrs_file_inspect.hip, which hold to this loop field for field.
+// (gfInspectStepWords) is shared with the kernels of gvrs_file_inspect.hip, which hold to this loop field for field.
 // Reference (core/src/main/java/org/gridfour/gvrs/): GvrsInspector.java:213-312 inspectContent, :314-337 testRecordChecksum,
 // GvrsFileSpecification.java:546-556 getStandardTileSizeInBytes.  Version 1.04; everything little-endian.
 // The checks at one record, in this order (the reference's wherever the reference is defined): a size word of 0 (a clean end), the
@@ -21,7 +21,7 @@
 
 #pragma GCC visibility push(hidden)
 
-constexpr int GF_INSPECT_NEXT = -1;                               // gfInspectStep: the record's head passed, the walk goes on behind it
+constexpr int GF_INSPECT_NEXT = -1;                               // gfInspectStepWords: the record's head passed, the walk goes on behind it
 constexpr uint64_t GF_INSPECT_MIN_SEGMENT = 1024;                 // gf_file_inspect_plan's numbers (the device form's; the host form has no use for them)
 constexpr uint64_t GF_INSPECT_MAX_SEGMENTS = 32768;
 constexpr uint32_t GF_INSPECT_CRC_CHUNK = 2048;                   // a multiple of 256: 64 lanes, a multiple of 4 bytes each
@@ -36,41 +36,33 @@ struct GfInspectParams {
 // The head of the record at pos (a position the walk reached: pos <= bytes), judged without its checksum.  GF_INSPECT_END: the walk
 // ends in front of it (fewer than 13 bytes left, or a size word of 0) and r is untouched.  Else r = the record as the walk met it
 // (checksum -1) and the answer is GF_INSPECT_NEXT or the structural stop.
-template <class Word>
-GF_HD int gfInspectStepWords(const GfInspectParams &p, uint64_t pos, gf_file_record &r, Word word)
+template <class Load>
+GF_HD int gfInspectStepWords(const GfInspectParams &p, uint64_t pos, gf_file_record &r, Load load)
 {
     if (p.bytes - pos <= 12) return GF_INSPECT_END;               // (the reference's filePos < fileSize - RECORD_OVERHEAD_SIZE)
-    const uint32_t sizeWord = word(pos);
+    const uint32_t sizeWord = load.word(pos);
     if (sizeWord == 0u) return GF_INSPECT_END;
-    const int32_t size = (int32_t)sizeWord, type = (int32_t)(word(pos + 4) & 0xffu);
+    const int32_t size = (int32_t)sizeWord, type = (int32_t)(load.word(pos + 4) & 0xffu);
     r.pos = pos, r.size = sizeWord, r.type = type, r.tile_index = -1, r.checksum = -1;
     if (type > 6) return GF_INSPECT_BAD_RECORD_TYPE;
     if (size < 16 || (size & 7) != 0) return GF_INSPECT_BAD_RECORD_SIZE;
     if (type == GF_FILE_REC_TILE) {
-        r.tile_index = (int32_t)word(pos + 8);
+        r.tile_index = (int32_t)load.word(pos + 8);
         if (r.tile_index < 0 || r.tile_index >= p.nTiles) return GF_INSPECT_BAD_TILE_INDEX;
         if ((int64_t)size > p.maxTileRecordSize) return GF_INSPECT_TILE_TOO_LARGE;
     }
     if ((uint64_t)size > p.bytes - pos) return GF_INSPECT_TRUNCATED;
     return GF_INSPECT_NEXT;
 }
-inline int gfInspectStep(const uint8_t *image, const GfInspectParams &p, uint64_t pos, gf_file_record &r)
-{
-    return gfInspectStepWords(p, pos, r, [image](uint64_t at) { return (uint32_t)gfLe(image + at, 4); });
-}
 
 // testRecordChecksum's judgement of the record whose content lies at P, in front of its checksum: true = *size is a size word the
-// checksum can be taken over.  P is the header's word: nothing about it is trusted.
+// checksum can be taken over.  P is the header's word: nothing about it is trusted, so the place rule (behind = 0) comes first.
 GF_HD bool gfInspectDirHead(const GfInspectParams &p, uint64_t P, uint32_t sizeWord, uint32_t typeWord)
 {
     const int32_t size = (int32_t)sizeWord;
     if ((typeWord & 0xffu) > 6u) return false;
     if (size < 16 || (size & 7) != 0) return false;
     return (uint64_t)size <= p.bytes - (P - 8);
-}
-GF_HD bool gfInspectDirPlace(const GfInspectParams &p, uint64_t P)   // may the 8 bytes in front of P be read?
-{
-    return P >= p.contentPos + 8 && (P & 7) == 0 && P <= p.bytes;
 }
 
 inline GfInspectParams gfInspectParamsOf(const gf_file_info &f, uint64_t bytes)
@@ -117,7 +109,7 @@ inline gf_status gfFileInspect(const gf_file_info &f, const uint8_t *image, uint
     gf_file_inspect_report &o = *report;
     o.tile_dir_located = 1;
     const uint64_t T = p.tileDirPos;
-    if (gfInspectDirPlace(p, T) && gfInspectDirHead(p, T, gfLe(image + T - 8, 4), gfLe(image + T - 4, 4))) {
+    if (gfRecordPlace(p.contentPos, bytes, T, 0) == GF_PLACE_OK && gfInspectDirHead(p, T, gfLe(image + T - 8, 4), gfLe(image + T - 4, 4))) {
         const uint32_t size = (uint32_t)gfLe(image + T - 8, 4);
         o.tile_dir_passed = gfCrc32c(image + T - 8, size - 4) == gfLe(image + T - 8 + size - 4, 4);
     }
@@ -135,7 +127,7 @@ inline gf_status gfFileInspect(const gf_file_info &f, const uint8_t *image, uint
     o.stop = GF_INSPECT_END;
     for (;;) {
         gf_file_record r;
-        const int code = gfInspectStep(image, p, pos, r);
+        const int code = gfInspectStepWords(p, pos, r, GfLoadLe{image});
         if (code == GF_INSPECT_END) {
             o.complete = 1;
             break;
@@ -210,8 +202,8 @@ struct GfInspectState {            // zeroed before the kernels; k_inspect_chain
 struct GfInspectArgs {
     const uint8_t *image;          // 8-byte aligned
     GfInspectParams p;
-    uint64_t entriesPos, metaDirPos, freeDirPos;     // the tile directory's entries; the header's two other directory positions
-    int32_t extended, dirRow0, dirCol0, dirNRows, dirNCols, nColsOfTiles;
+    GfFileDir dir;                                   // the tile directory (gvrs_file_parse.h)
+    uint64_t metaDirPos, freeDirPos;                 // the header's two other directory positions
     uint64_t segBytes, maxRecords;
     uint32_t nSeg;
     // per segment

@@ -3,8 +3,8 @@
 // order of the checks and the deviations) and shares the judgement of one record's head, gfInspectStepWords, with the kernels here.
 // A record's position is the previous record's position plus its size: one lane walking 12,960 records pays a dependent load that
 // misses to HBM for every one of them.  So the walk is cut at ANCHORS, record starts known without walking:
-//   k_inspect_anchors   a lane per tile directory entry, judged as k_file_locate judges it (the position before it is touched, then
-//                       the record's type and tile index): atomicMin of position - 8 into the slot of the position's segment.
+//   k_inspect_anchors   a lane per tile directory entry (its position through the place rule before it is touched, then the record's
+//                       type and tile index, not its size): atomicMin of position - 8 into the slot of the position's segment.
 //                       Segment 0's anchor is the content position; the header's three directory positions are anchors too.
 //   k_inspect_walk      a lane per ANCHORED segment walks from its anchor until it reaches or passes the anchor of a later
 //                       segment, or stops.  A segment may have no anchor (a long free node spans it) and its anchor need not be
@@ -41,12 +41,6 @@ namespace {
 
 constexpr uint32_t INS_THREADS = 1024, INS_WAVES = INS_THREADS / 64;
 
-__device__ __forceinline__ int ins_step(const GfInspectArgs &a, uint64_t pos, gf_file_record &r)
-{
-    const uint8_t *image = a.image;
-    return gfInspectStepWords(a.p, pos, r, [image](uint64_t at) { return *reinterpret_cast<const uint32_t *>(image + at); });
-}
-
 __device__ __forceinline__ void ins_put_anchor(const GfInspectArgs &a, uint64_t q)        // q in [contentPos, bytes)
 {
     const uint64_t s = (q - a.p.contentPos) / a.segBytes;
@@ -60,16 +54,16 @@ __global__ __launch_bounds__(256) void k_inspect_anchors(const GfInspectArgs a)
         ins_put_anchor(a, a.p.contentPos);                        // (the smallest position there is: segment 0's anchor)
         const uint64_t dirs[3] = {a.p.tileDirPos, a.metaDirPos, a.freeDirPos};
         for (int i = 0; i < 3; i++)
-            if (dirs[i] != 0 && gfInspectDirPlace(a.p, dirs[i]) && dirs[i] - 8u < bytes) ins_put_anchor(a, dirs[i] - 8u);
+            if (dirs[i] != 0 && gfRecordPlace(a.p.contentPos, bytes, dirs[i], 0) == GF_PLACE_OK) ins_put_anchor(a, dirs[i] - 8u);
     }
-    if (k >= (uint64_t)a.dirNRows * (uint64_t)a.dirNCols) return;
-    const uint64_t w = a.extended ? 8u : 4u, at = a.entriesPos + k * w;
+    if (k >= (uint64_t)a.dir.nRows * (uint64_t)a.dir.nCols) return;
+    // (gfDirEntryPos and gfRecordPlace written out as before they were shared: with them the sound image measured 0.5 to 1 % slower)
+    const uint64_t w = a.dir.extended ? 8u : 4u, at = a.dir.entriesPos + k * w;
     if (at > bytes || w > bytes - at) return;
-    const uint64_t p = a.extended ? *reinterpret_cast<const uint64_t *>(a.image + at) : (uint64_t) * reinterpret_cast<const uint32_t *>(a.image + at) * 8u;
+    const uint64_t p = a.dir.extended ? *reinterpret_cast<const uint64_t *>(a.image + at) : (uint64_t) * reinterpret_cast<const uint32_t *>(a.image + at) * 8u;
     if (p == 0 || p < a.p.contentPos + 8u || (p & 7u) != 0u || p > bytes || bytes - p < 12u) return;
-    const int32_t tileIndex = (a.dirRow0 + (int32_t)(k / (uint64_t)a.dirNCols)) * a.nColsOfTiles + a.dirCol0 + (int32_t)(k % (uint64_t)a.dirNCols);
     const uint32_t *h = reinterpret_cast<const uint32_t *>(a.image + (p - 8u));          // (size, type, tile index: ends at p + 4)
-    if ((h[1] & 0xffu) != (uint32_t)GF_FILE_REC_TILE || (int32_t)h[2] != tileIndex) return;
+    if ((h[1] & 0xffu) != (uint32_t)GF_FILE_REC_TILE || (int32_t)h[2] != gfDirTileOfEntry(a.dir, k)) return;
     ins_put_anchor(a, p - 8u);
 }
 
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(256) void k_inspect_walk(const GfInspectArgs a)
     int code;
     for (;;) {
         gf_file_record r;
-        code = ins_step(a, pos, r);
+        code = gfInspectStepWords(a.p, pos, r, GfLoadAligned{a.image});
         if (code != GF_INSPECT_NEXT) {
             if (code != GF_INSPECT_END) cnt++;
             break;
@@ -160,7 +154,7 @@ __global__ __launch_bounds__(INS_THREADS) void k_inspect_chain(const GfInspectAr
     if (code == GF_INSPECT_OVERSHOOT) {                           // the link did not close: the rest of the image, serially
         for (;;) {
             gf_file_record r;
-            code = ins_step(a, pos, r);
+            code = gfInspectStepWords(a.p, pos, r, GfLoadAligned{a.image});
             if (code == GF_INSPECT_END) break;
             if (n < a.maxRecords) a.recs[n] = r;
             n++;
@@ -175,7 +169,7 @@ __global__ __launch_bounds__(INS_THREADS) void k_inspect_chain(const GfInspectAr
     // the record at the header's tile directory position: judged here, checksummed with the others
     gf_file_record d{};
     const uint64_t T = a.p.tileDirPos;
-    if (gfInspectDirPlace(a.p, T)) {
+    if (gfRecordPlace(a.p.contentPos, a.p.bytes, T, 0) == GF_PLACE_OK) {
         const uint32_t *h = reinterpret_cast<const uint32_t *>(a.image + (T - 8u));
         if (gfInspectDirHead(a.p, T, h[0], h[1])) d.pos = T - 8u, d.size = h[0], d.type = -1, d.checksum = -1;
     }
@@ -192,7 +186,7 @@ __global__ __launch_bounds__(256) void k_inspect_list(const GfInspectArgs a)
     const uint32_t cnt = a.count[s];
     for (uint32_t i = 0; i < cnt; i++) {
         gf_file_record r;
-        (void)ins_step(a, pos, r);
+        (void)gfInspectStepWords(a.p, pos, r, GfLoadAligned{a.image});
         a.recs[b + i] = r;
         pos += r.size;
     }
@@ -394,9 +388,9 @@ extern "C" int gf_internal_inspect_kernel_ms(float ms[7])
 
 hipError_t gf_launch_file_inspect(const GfInspectArgs &a, hipStream_t stream)
 {
-    const uint64_t nEntries = (uint64_t)a.dirNRows * (uint64_t)a.dirNCols;
-    if (a.nSeg < 1u || a.segBytes < 8u || a.dirNRows < 0 || a.dirNCols < 0 || nEntries > 0x7fffffffull || a.nColsOfTiles < 1) return hipErrorInvalidValue;
-    if (((uintptr_t)a.image & 7u) != 0 || (a.entriesPos & 7u) != 0 || (a.p.contentPos & 7u) != 0 || a.maxRecords > 0x7ffffffeull) return hipErrorInvalidValue;
+    const uint64_t nEntries = (uint64_t)a.dir.nRows * (uint64_t)a.dir.nCols;
+    if (a.nSeg < 1u || a.segBytes < 8u || a.dir.nRows < 0 || a.dir.nCols < 0 || nEntries > 0x7fffffffull || a.dir.nColsOfTiles < 1) return hipErrorInvalidValue;
+    if (((uintptr_t)a.image & 7u) != 0 || !gfDirEntriesAligned(a.dir) || (a.p.contentPos & 7u) != 0 || a.maxRecords > 0x7ffffffeull) return hipErrorInvalidValue;
     const unsigned segBlocks = (a.nSeg + 255u) / 256u;
     const unsigned crcBlocks = (unsigned)std::min<uint64_t>((a.maxRecords + 1u + 3u) / 4u, 8192u);
     INS_MARK(0);

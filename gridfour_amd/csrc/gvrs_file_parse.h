@@ -218,11 +218,12 @@ inline gf_status gfFileParse(const uint8_t *image, size_t bytes, GfFileParsed &o
     return GF_OK;
 }
 
-// What a block read needs of an opened file to find a tile's record: the kernel's argument and the host look-up's.
+// ---- The tile directory of an opened file and the rules of reading through it, for every reader, host and kernel.  A reader
+// says how bytes are loaded (GfLoadLe: any host image; GfLoadAligned: an 8-byte aligned image) and keeps its own reaction. ----
 struct GfFileDir {
-    uint64_t entriesPos, contentPos;
-    int32_t extended, row0, col0, nRows, nCols;
-    int32_t nColsOfTiles;
+    uint64_t entriesPos, contentPos;        // the first entry (a multiple of 8); where the records begin
+    int32_t extended, row0, col0, nRows, nCols;   // entries: int64 positions, else unsigned int32, position = entry * 8; the rectangle of tiles
+    int32_t nColsOfTiles;                   // of the grid
 };
 
 inline GfFileDir gfFileDirOf(const gf_file_info &f)
@@ -234,24 +235,96 @@ inline GfFileDir gfFileDirOf(const gf_file_info &f)
     return d;
 }
 
-// One tile looked up in an image in host memory, judged exactly as k_file_locate (gvrs_file.hip) judges it: *pos = the entry's
-// position (0: the file holds no such tile), *size = the record's size word when the status is GF_OK and the tile is present.
+struct GfLoadLe {
+    const uint8_t *image;
+    uint64_t word64(uint64_t at) const { return gfLe(image + at, 8); }
+    uint32_t word(uint64_t at) const { return (uint32_t)gfLe(image + at, 4); }
+    GfU4 head(uint64_t P) const { return GfU4{(uint32_t)gfLe(image + P - 8, 4), (uint32_t)gfLe(image + P - 4, 4), (uint32_t)gfLe(image + P, 4), 0}; }
+};
+struct GfLoadAligned {                      // at: a multiple of the word's size (little-endian hosts, as the library's kernels)
+    const uint8_t *image;
+    GF_HD uint64_t word64(uint64_t at) const { return *reinterpret_cast<const uint64_t *>(image + at); }
+    GF_HD uint32_t word(uint64_t at) const { return *reinterpret_cast<const uint32_t *>(image + at); }
+    // size, type, tile index in ONE 16-byte load at P - 8; it ends at P + 8, inside an image that holds 12 bytes behind a multiple of 8
+    GF_HD GfU4 head(uint64_t P) const { return *reinterpret_cast<const GfU4 *>(image + (P - 8)); }
+};
+
+// the entry of tile (row, col) of the grid, or of a tile index; -1: the tile lies outside the directory's rectangle
+GF_HD int64_t gfDirEntryAt(const GfFileDir &d, int32_t row, int32_t col)
+{
+    const int32_t tr = row - d.row0, tc = col - d.col0;
+    return tr >= 0 && tr < d.nRows && tc >= 0 && tc < d.nCols ? (int64_t)((uint64_t)tr * (uint64_t)d.nCols + (uint64_t)tc) : -1;
+}
+GF_HD int64_t gfDirEntryOfTile(const GfFileDir &d, int32_t tileIndex) { return gfDirEntryAt(d, tileIndex / d.nColsOfTiles, tileIndex % d.nColsOfTiles); }
+// ... and back: the tile index of entry k < nRows * nCols
+GF_HD int32_t gfDirTileOfEntry(const GfFileDir &d, uint64_t k)
+{
+    return (d.row0 + (int32_t)(k / (uint64_t)d.nCols)) * d.nColsOfTiles + d.col0 + (int32_t)(k % (uint64_t)d.nCols);
+}
+GF_HD bool gfDirEntriesAligned(const GfFileDir &d) { return (d.entriesPos & 7) == 0; }   // what GfLoadAligned needs; gfFileParse's are
+// entry k of image[0, bytes): *pos = the content position it holds (0: no such tile); false: the entry lies outside the image
+template <class Load>
+GF_HD bool gfDirEntryPos(const GfFileDir &d, uint64_t bytes, uint64_t k, uint64_t *pos, Load load)
+{
+    const uint64_t w = d.extended ? 8u : 4u, at = d.entriesPos + k * w;
+    *pos = 0;
+    if (at > bytes || w > bytes - at) return false;
+    *pos = d.extended ? load.word64(at) : (uint64_t)load.word(at) * 8u;
+    return true;
+}
+
+// THE PLACE RULE: may the head of the record whose content lies at P be read?  No record lies in the header and a content lies
+// behind its 8-byte head; records lie on the 8-byte grid; `behind` bytes from P on lie inside the image: 12 where size, type and
+// tile index are read (P - 8 .. P + 4), 0 where only the 8 bytes in front of P are.  The answer: the first clause that fails.
+enum GfPlace { GF_PLACE_OK = 0, GF_PLACE_IN_HEADER, GF_PLACE_OFF_GRID, GF_PLACE_BEHIND_END, GF_PLACE_HEAD_CUT };
+GF_HD GfPlace gfRecordPlace(uint64_t contentPos, uint64_t bytes, uint64_t P, uint64_t behind)
+{
+    if (P < contentPos + 8) return GF_PLACE_IN_HEADER;
+    if ((P & 7) != 0) return GF_PLACE_OFF_GRID;
+    if (P > bytes) return GF_PLACE_BEHIND_END;
+    if (behind > bytes - P) return GF_PLACE_HEAD_CUT;
+    return GF_PLACE_OK;
+}
+
+// One tile looked up through its entry k (gfDirEntryAt / gfDirEntryOfTile): *pos = its entry's position (0: no such tile), *head = the record's size, type and tile-index words when
+// GF_OK and present.  An entry outside the image or a position that fails the place rule is GF_ERR_BOUNDS and nothing is read
+// there; a head with another tile's index (the entry leads to another tile's record, or to none) is GF_ERR_FORMAT.  The size word
+// is NOT judged: a block read leaves it to the framing walk (its host form refuses size < 20, the smallest record with an
+// element), an update to gfFsTileRecord (size < 24, the smallest it can free); k_inspect_anchors takes the type's low byte and
+// the tile index only, as GvrsInspector reads them.
+template <class Load>
+GF_HD gf_status gfFileLocateHead(const GfFileDir &d, uint64_t bytes, int64_t k, int32_t tileIndex, uint64_t *pos, GfU4 *head, Load load)
+{
+    *pos = 0, *head = GfU4{0, 0, 0, 0};
+    if (k < 0) return GF_OK;
+    if (!gfDirEntryPos(d, bytes, (uint64_t)k, pos, load)) return GF_ERR_BOUNDS;
+    if (*pos == 0) return GF_OK;
+    if (gfRecordPlace(d.contentPos, bytes, *pos, 12) != GF_PLACE_OK) return GF_ERR_BOUNDS;
+    *head = load.head(*pos);
+    return (int32_t)head->z == tileIndex ? GF_OK : GF_ERR_FORMAT;
+}
+// ... in a host image by its index: *size = the size word (0 unless GF_OK and present)
 inline gf_status gfFileLocate(const GfFileDir &d, const uint8_t *image, uint64_t bytes, int32_t tileIndex, uint64_t *pos, uint32_t *size)
 {
-    *pos = 0, *size = 0;
-    const int64_t tr = tileIndex / d.nColsOfTiles - d.row0, tc = tileIndex % d.nColsOfTiles - d.col0;
-    if (tr < 0 || tr >= d.nRows || tc < 0 || tc >= d.nCols) return GF_OK;
-    const uint64_t k = (uint64_t)tr * (uint64_t)d.nCols + (uint64_t)tc, w = d.extended ? 8 : 4, at = d.entriesPos + k * w;
-    if (at > bytes || w > bytes - at) return GF_ERR_BOUNDS;
-    const uint64_t p = d.extended ? gfLe(image + at, 8) : gfLe(image + at, 4) * 8;
-    *pos = p;
-    if (p == 0) return GF_OK;
-    if (p < d.contentPos + 8 || (p & 7) != 0 || p > bytes || 12 > bytes - p) return GF_ERR_BOUNDS;
-    uint32_t head[3];
-    memcpy(head, image + p - 8, 12);
-    if ((int32_t)head[2] != tileIndex) return GF_ERR_FORMAT;
-    *size = head[0];
-    return GF_OK;
+    GfU4 head;
+    const gf_status s = gfFileLocateHead(d, bytes, gfDirEntryOfTile(d, tileIndex), tileIndex, pos, &head, GfLoadLe{image});
+    *size = s == GF_OK ? head.x : 0;
+    return s;
+}
+
+// The rectangle of tiles [tileRow0, +nTileRows) x [tileCol0, +nTileCols) looked up in a host image, slot j = row-major:
+// each(j, verdict, pos, sizeWord) with gfFileLocate's answers; the caller judges the size word its own way.
+template <class Each>
+inline void gfFileLocateRect(const GfFileDir &d, const uint8_t *image, uint64_t bytes, int32_t tileRow0, int32_t tileCol0, int32_t nTileRows,
+                             int32_t nTileCols, Each each)
+{
+    for (size_t j = 0; j < (size_t)nTileRows * (size_t)nTileCols; j++) {
+        const int32_t tileIndex = (tileRow0 + (int32_t)(j / (size_t)nTileCols)) * d.nColsOfTiles + tileCol0 + (int32_t)(j % (size_t)nTileCols);
+        uint64_t pos;
+        uint32_t sizeWord;
+        const gf_status v = gfFileLocate(d, image, bytes, tileIndex, &pos, &sizeWord);
+        each(j, v, pos, sizeWord);
+    }
 }
 
 #pragma GCC visibility pop

@@ -106,19 +106,37 @@ struct GfFileUpdate {
     std::vector<uint8_t> metaDir;                                 // the old metadata directory record, whole; empty: the file has none
 };
 
-// The head of the record whose content lies at P, judged before anything of it is trusted: P a multiple of 8 behind the header
-// record, the head inside the image, the type, a size that is a multiple of 8 of at least minSize and ends inside the image.
-inline gf_status gfFsRecordHead(const uint8_t *image, uint64_t bytes, uint64_t contentPos, uint64_t P, int type, uint64_t minSize, uint64_t *size)
+// THE RECORD-HEAD RULE: the head of the record whose content lies at P, judged before anything of it is trusted.  The place rule
+// with the 8 bytes in front of P -- P is a header's or a directory's word, so one in the header or off the 8-byte grid is damage,
+// GF_ERR_FORMAT, and only one behind the image GF_ERR_BOUNDS --, then the type, a size that is a multiple of 8 of at least minSize
+// (GF_ERR_FORMAT) and ends inside the image (GF_ERR_BOUNDS).
+GF_HD gf_status gfFsHeadWords(uint64_t bytes, uint64_t P, uint32_t sizeWord, uint32_t typeWord, int type, uint64_t minSize, uint64_t *size)
 {
+    const int32_t s = (int32_t)sizeWord;
     *size = 0;
-    if ((P & 7) != 0 || P < contentPos + 8 || P > (1ull << 62)) return GF_ERR_FORMAT;
-    if (P > bytes) return GF_ERR_BOUNDS;
-    const int32_t s = (int32_t)(uint32_t)gfLe(image + P - 8, 4);
-    if (gfLe(image + P - 4, 4) != (uint64_t)type) return GF_ERR_FORMAT;
-    if (s < (int64_t)minSize || (s & 7) != 0) return GF_ERR_FORMAT;
+    if (typeWord != (uint32_t)type || s < (int64_t)minSize || (s & 7) != 0) return GF_ERR_FORMAT;
     if ((uint64_t)s > bytes - (P - 8)) return GF_ERR_BOUNDS;
     *size = (uint64_t)s;
     return GF_OK;
+}
+template <class Load>
+GF_HD gf_status gfFsRecordHead(uint64_t bytes, uint64_t contentPos, uint64_t P, int type, uint64_t minSize, uint64_t *size, Load load)
+{
+    *size = 0;
+    const GfPlace place = gfRecordPlace(contentPos, bytes, P, 0);
+    if (place == GF_PLACE_IN_HEADER || place == GF_PLACE_OFF_GRID || P > (1ull << 62)) return GF_ERR_FORMAT;
+    if (place != GF_PLACE_OK) return GF_ERR_BOUNDS;
+    return gfFsHeadWords(bytes, P, load.word(P - 8), load.word(P - 4), type, minSize, size);
+}
+// THE TILE-RECORD RULE of an update, host and kernel: a tile's old record found through the directory (gfFileLocateHead, whose
+// place rule covers the head's) and the head it loaded judged before the record is freed or rewritten.  *pos = 0: no such tile.
+template <class Load>
+GF_HD gf_status gfFsTileRecord(const GfFileDir &d, uint64_t bytes, int32_t tileIndex, uint64_t *pos, uint64_t *size, Load load)
+{
+    GfU4 head;
+    const gf_status v = gfFileLocateHead(d, bytes, gfDirEntryOfTile(d, tileIndex), tileIndex, pos, &head, load);
+    *size = 0;
+    return v == GF_OK && *pos != 0 ? gfFsHeadWords(bytes, *pos, head.x, head.y, GF_FILE_REC_TILE, 24, size) : v;
 }
 
 // gf_file_update_begin behind its null checks: info = the gf_file_info gf_file_open made of this image
@@ -137,7 +155,7 @@ inline gf_status gfFileUpdateBegin(const gf_file_info &info, const uint8_t *imag
     const uint64_t F = info.freespace_dir_pos, M = info.metadata_dir_pos, T = info.tile_dir_pos;
     uint64_t freeDirSize = 0;
     if (F != 0) {
-        if ((s = gfFsRecordHead(image, bytes, info.content_pos, F, GF_FILE_REC_FREE_DIR, 16, &freeDirSize)) != GF_OK) return s;
+        if ((s = gfFsRecordHead(bytes, info.content_pos, F, GF_FILE_REC_FREE_DIR, 16, &freeDirSize, GfLoadLe{image})) != GF_OK) return s;
         const int32_t count = (int32_t)(uint32_t)gfLe(image + F, 4);                       // (16 bytes of record: the word is inside)
         if (count < 0 || 4 + 12 * (uint64_t)count > freeDirSize - 12) return GF_ERR_FORMAT;  // (a count the record can hold)
         u.freePos.resize((size_t)count + 3), u.freeSize.resize((size_t)count + 3);
@@ -163,12 +181,12 @@ inline gf_status gfFileUpdateBegin(const gf_file_info &info, const uint8_t *imag
         gfFsDealloc(u.freePos.data(), u.freeSize.data(), n, cap, F - 8, freeDirSize);
     }
     if (M != 0) {
-        if ((s = gfFsRecordHead(image, bytes, info.content_pos, M, GF_FILE_REC_METADATA_DIR, 16, &size)) != GF_OK) return s;
+        if ((s = gfFsRecordHead(bytes, info.content_pos, M, GF_FILE_REC_METADATA_DIR, 16, &size, GfLoadLe{image})) != GF_OK) return s;
         if (gfFsOverlaps(u.freePos.data(), u.freeSize.data(), n, M - 8, size)) return GF_ERR_FORMAT;
         u.metaDir.assign(image + M - 8, image + M - 8 + size);
         gfFsDealloc(u.freePos.data(), u.freeSize.data(), n, cap, M - 8, size);
     }
-    if ((s = gfFsRecordHead(image, bytes, info.content_pos, T, GF_FILE_REC_TILE_DIR, 40, &size)) != GF_OK) return s;
+    if ((s = gfFsRecordHead(bytes, info.content_pos, T, GF_FILE_REC_TILE_DIR, 40, &size, GfLoadLe{image})) != GF_OK) return s;
     const uint64_t nEntries = (uint64_t)info.dir_n_rows * (uint64_t)info.dir_n_cols;
     const GfTilesOfGrid tiles = gfTilesOfGrid(info.grid);
     if (nEntries != 0 && ((int64_t)info.dir_row0 + info.dir_n_rows > tiles.rows || (int64_t)info.dir_col0 + info.dir_n_cols > tiles.cols))
@@ -229,14 +247,9 @@ inline gf_status gfFileUpdateAssemble(const GfFileUpdate &u, uint8_t *image, uin
         const uint64_t len = offsets[r + 1] - offsets[r];
         const int32_t st = status ? status[r] : len ? GF_OK : GF_DECLINED;
         if (st < 0) continue;                                                            // the tile stays as it is: record and entry
-        uint64_t oldPos = 0, oldSize = 0;
-        uint32_t sizeWord;
-        const gf_status v = gfFileLocate(d, image, u.imageBytes, tileIndices[r], &oldPos, &sizeWord);
+        uint64_t oldPos, oldSize;
+        const gf_status v = gfFsTileRecord(d, u.imageBytes, tileIndices[r], &oldPos, &oldSize, GfLoadLe{image});
         if (v != GF_OK) return v;
-        if (oldPos != 0) {                                                               // the old record's head, judged before it is freed
-            const gf_status h = gfFsRecordHead(image, u.imageBytes, f.content_pos, oldPos, GF_FILE_REC_TILE, 24, &oldSize);
-            if (h != GF_OK) return h;
-        }
         const bool inPlace = len != 0 && !compression && oldPos != 0;
         if (inPlace) {
             if (len != oldSize) return GF_ERR_ARG;                                       // (a standard record has one size)
@@ -279,11 +292,11 @@ inline gf_status gfFileUpdateAssemble(const GfFileUpdate &u, uint8_t *image, uin
     // ---- from here on the image is written ----
     // the old entries first: the old directory record is free space since opening and may lie under a new record
     std::vector<uint64_t> positions((size_t)nEntries, 0);
-    for (int64_t tr = 0; tr < d.nRows; tr++)
-        for (int64_t tc = 0; tc < d.nCols; tc++) {
-            const uint8_t *e = image + d.entriesPos + (uint64_t)(tr * d.nCols + tc) * (d.extended ? 8 : 4);
-            positions[(size_t)((tr + d.row0 - r0) * nCols + (tc + d.col0 - c0))] = d.extended ? gfLe(e, 8) : gfLe(e, 4) * 8;
-        }
+    // (they lie inside the old image: gfFileUpdateBegin has checked the old directory record against its rectangle)
+    for (uint64_t k = 0; k < (uint64_t)d.nRows * (uint64_t)d.nCols; k++) {
+        const int64_t t = gfDirTileOfEntry(d, k);
+        gfDirEntryPos(d, u.imageBytes, k, &positions[(size_t)((t / nColsOfTiles - r0) * nCols + (t % nColsOfTiles - c0))], GfLoadLe{image});
+    }
     for (const Placed &p : placed) {
         positions[(size_t)((p.tile / nColsOfTiles - r0) * nCols + (p.tile % nColsOfTiles - c0))] = p.pos;
         if (p.pos != 0) memcpy(image + p.pos - 8, blob + offsets[p.record], (size_t)(offsets[p.record + 1] - offsets[p.record]));

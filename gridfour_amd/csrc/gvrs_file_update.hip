@@ -32,13 +32,9 @@ __global__ __launch_bounds__(256) void k_update_snapshot(const GfFileUpdateArgs 
 {
     const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (t >= (uint64_t)a.nTilesGrid) return;
-    const int64_t tr = (int64_t)(t / (uint32_t)a.nColsOfTiles) - a.dirRow0, tc = (int64_t)(t % (uint32_t)a.nColsOfTiles) - a.dirCol0;
+    const int64_t k = gfDirEntryOfTile(a.dir, (int32_t)t);
     uint64_t p = 0;
-    if (tr >= 0 && tr < a.dirNRows && tc >= 0 && tc < a.dirNCols) {
-        const uint64_t k = (uint64_t)tr * (uint32_t)a.dirNCols + (uint64_t)tc, w = a.oldExtended ? 8u : 4u, at = a.entriesPos + k * w;
-        if (at + w <= a.oldBytes)
-            p = a.oldExtended ? *reinterpret_cast<const uint64_t *>(a.image + at) : (uint64_t)*reinterpret_cast<const uint32_t *>(a.image + at) * 8u;
-    }
+    if (k >= 0) (void)gfDirEntryPos(a.dir, a.oldBytes, (uint64_t)k, &p, GfLoadAligned{a.image});
     a.grid[t] = p;
 }
 
@@ -194,37 +190,18 @@ __global__ __launch_bounds__(64) void k_update_alloc(const GfFileUpdateArgs a)
         if (__ballot(bad) != 0ull) verdict = GF_K_ERR_ARG;
     }
     uint64_t fileSize = a.oldBytes;
-    uint32_t extended = (a.oldExtended || a.forceExtended) ? 1u : 0u;
-    const bool oldEmpty = a.dirNRows == 0 || a.dirNCols == 0;
-    int64_t r0 = oldEmpty ? 0x7fffffff : a.dirRow0, r1 = oldEmpty ? -1 : (int64_t)a.dirRow0 + a.dirNRows - 1;
-    int64_t c0 = oldEmpty ? 0x7fffffff : a.dirCol0, c1 = oldEmpty ? -1 : (int64_t)a.dirCol0 + a.dirNCols - 1;
+    uint32_t extended = (a.dir.extended || a.forceExtended) ? 1u : 0u;
+    const bool oldEmpty = a.dir.nRows == 0 || a.dir.nCols == 0;
+    int64_t r0 = oldEmpty ? 0x7fffffff : a.dir.row0, r1 = oldEmpty ? -1 : (int64_t)a.dir.row0 + a.dir.nRows - 1;
+    int64_t c0 = oldEmpty ? 0x7fffffff : a.dir.col0, c1 = oldEmpty ? -1 : (int64_t)a.dir.col0 + a.dir.nCols - 1;
     for (uint64_t r = 0; r < a.nRecords && verdict == GF_K_OK; r++) {
         const uint64_t len = a.offsets[r + 1u] - a.offsets[r];
         const int32_t s = a.status ? a.status[r] : len ? GF_K_OK : 1;
         uint64_t place = GF_UPDATE_UNTOUCHED;
         if (s >= 0) {
             const int32_t tile = a.tiles[r];
-            // the old record, found and judged as gfFileLocate and gfFsRecordHead judge it
-            uint64_t oldPos = 0, oldSize = 0;
-            const int64_t tr = tile / a.nColsOfTiles - a.dirRow0, tc = tile % a.nColsOfTiles - a.dirCol0;
-            if (tr >= 0 && tr < a.dirNRows && tc >= 0 && tc < a.dirNCols) {
-                const uint64_t k = (uint64_t)tr * (uint32_t)a.dirNCols + (uint64_t)tc, w = a.oldExtended ? 8u : 4u, at = a.entriesPos + k * w;
-                if (at > a.oldBytes || w > a.oldBytes - at) verdict = GF_K_ERR_BOUNDS;
-                else {
-                    const uint64_t p = a.oldExtended ? *reinterpret_cast<const uint64_t *>(a.image + at)
-                                                     : (uint64_t)*reinterpret_cast<const uint32_t *>(a.image + at) * 8u;
-                    if (p != 0u) {
-                        if (p < a.contentPos + 8u || (p & 7u) != 0u || p > a.oldBytes || 12u > a.oldBytes - p) verdict = GF_K_ERR_BOUNDS;
-                        else {
-                            const uint32_t *head = reinterpret_cast<const uint32_t *>(a.image + p - 8u);
-                            const int32_t sizeWord = (int32_t)head[0];
-                            if ((int32_t)head[2] != tile || head[1] != (uint32_t)GF_FILE_REC_TILE || sizeWord < 24 || (sizeWord & 7) != 0) verdict = GF_K_ERR_FORMAT;
-                            else if ((uint64_t)sizeWord > a.oldBytes - (p - 8u)) verdict = GF_K_ERR_BOUNDS;
-                            else oldPos = p, oldSize = (uint64_t)sizeWord;
-                        }
-                    }
-                }
-            }
+            uint64_t oldPos, oldSize;                                // (the statuses are the verdicts' numbers)
+            verdict = gfFsTileRecord(a.dir, a.oldBytes, tile, &oldPos, &oldSize, GfLoadAligned{a.image});
             if (verdict != GF_K_OK && a.tileStatus) {                 // the block form: the tile's own verdict, and the tile stays
                 if (lane == 0u) a.tileStatus[r] = verdict, a.recPos[r] = GF_UPDATE_UNTOUCHED;
                 verdict = GF_K_OK;
@@ -243,7 +220,7 @@ __global__ __launch_bounds__(64) void k_update_alloc(const GfFileUpdateArgs a)
                     else {
                         place = wl_alloc(l, fileSize, len, lane) + 8u;
                         if (place > GF_FILE_MAX_COMPACT_POS) extended = 1u;
-                        const int64_t row = tile / a.nColsOfTiles, col = tile % a.nColsOfTiles;
+                        const int64_t row = tile / a.dir.nColsOfTiles, col = tile % a.dir.nColsOfTiles;
                         r0 = row < r0 ? row : r0, r1 = row > r1 ? row : r1, c0 = col < c0 ? col : c0, c1 = col > c1 ? col : c1;
                     }
                 }
@@ -256,7 +233,7 @@ __global__ __launch_bounds__(64) void k_update_alloc(const GfFileUpdateArgs a)
         st.metaDirAt = a.metaDirBytes ? wl_alloc(l, fileSize, a.metaDirBytes, lane) : 0u;
         const bool empty = r1 < 0;
         st.nRows = empty ? 0u : (uint32_t)(r1 - r0 + 1), st.nCols = empty ? 0u : (uint32_t)(c1 - c0 + 1);
-        st.row0 = empty ? (uint32_t)a.dirRow0 : (uint32_t)r0, st.col0 = empty ? (uint32_t)a.dirCol0 : (uint32_t)c0;
+        st.row0 = empty ? (uint32_t)a.dir.row0 : (uint32_t)r0, st.col0 = empty ? (uint32_t)a.dir.col0 : (uint32_t)c0;
         st.extended = extended;
         st.tileDirSize = gfFileTileDirSize((uint64_t)st.nRows * st.nCols, extended != 0u);
         if (st.tileDirSize > 0x7fffffffull) verdict = GF_K_ERR_UNSUPPORTED;
@@ -346,7 +323,7 @@ __global__ __launch_bounds__(256) void k_update_dir(const GfFileUpdateArgs a)
     const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (s.verdict != GF_K_OK || w >= s.tileDirSize / 8u) return;
     tile_dir_store_word(a.image, upd_dir(s), w, a.checksums != 0,
-                        [&](uint32_t row, uint32_t col) { return a.grid[(uint64_t)row * (uint32_t)a.nColsOfTiles + col]; });
+                        [&](uint32_t row, uint32_t col) { return a.grid[(uint64_t)row * (uint32_t)a.dir.nColsOfTiles + col]; });
 }
 
 __global__ __launch_bounds__(256) void k_update_dir_crc(const GfFileUpdateArgs a)
@@ -429,11 +406,11 @@ __global__ __launch_bounds__(64) void k_update_finish(const GfFileUpdateArgs a)
         tile_dir_fold(a.image, upd_dir(s), a.chunkCrc, lane);
         // the header record's checksum: bytes [16, contentPos - 4)
         const uint32_t *head = reinterpret_cast<const uint32_t *>(a.image + 16u);
-        headCrc = head_crc(table, (uint32_t)(a.contentPos - 16u - 4u) / 4u, lane, fields, [&](uint32_t i) { return head[i]; });
+        headCrc = head_crc(table, (uint32_t)(a.dir.contentPos - 16u - 4u) / 4u, lane, fields, [&](uint32_t i) { return head[i]; });
     }
     if (lane == 0u) {
         head_store(a.image, fields);
-        if (a.checksums) *reinterpret_cast<uint32_t *>(a.image + a.contentPos - 4u) = headCrc;
+        if (a.checksums) *reinterpret_cast<uint32_t *>(a.image + a.dir.contentPos - 4u) = headCrc;
     }
 }
 
@@ -442,8 +419,8 @@ __global__ __launch_bounds__(64) void k_update_finish(const GfFileUpdateArgs a)
 hipError_t gf_launch_file_update(const GfFileUpdateArgs &a, hipStream_t stream)
 {
     if (((uintptr_t)a.image & 7u) != 0 || ((uintptr_t)a.blob & 7u) != 0 || ((uintptr_t)a.metaDir & 7u) != 0 || (a.metaDirBytes & 7u) != 0 ||
-        (a.contentPos & 7u) != 0 || a.contentPos < 128u || a.contentPos > a.oldBytes || a.oldBytes > a.imageCap || (a.oldBytes & 7u) != 0 ||
-        a.nTilesGrid < 1 || a.nColsOfTiles < 1 || a.nOpened > a.listCap || a.nRecords > 0x7fffffffull)
+        (a.dir.contentPos & 7u) != 0 || a.dir.contentPos < 128u || a.dir.contentPos > a.oldBytes || a.oldBytes > a.imageCap || (a.oldBytes & 7u) != 0 ||
+        a.nTilesGrid < 1 || a.dir.nColsOfTiles < 1 || a.nOpened > a.listCap || a.nRecords > 0x7fffffffull)
         return hipErrorInvalidValue;
     const uint64_t n = (uint64_t)a.nTilesGrid;
     const uint64_t maxDir = gfFileTileDirSize(n, true), maxChunks = (maxDir + GF_FILE_CRC_CHUNK - 1) / GF_FILE_CRC_CHUNK;

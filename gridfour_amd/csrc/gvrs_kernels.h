@@ -13,6 +13,7 @@
 #include "gvrs_image_common.h"
 #include "gvrs_tabulate_common.h"
 #include "gvrs_lsop_container.h"
+#include "gvrs_file_parse.h"
 
 // per-tile status values written by the kernels; identical to gf_status in
 // include/gvrs_hip_codec.h
@@ -572,11 +573,7 @@ constexpr int32_t GF_FILE_LOCATED = 1;       // the record's extent is emitted: 
 struct GfFileLocateArgs {
     const uint8_t *image;      // 8-byte aligned
     uint64_t imageBytes;
-    uint64_t entriesPos;       // the directory's first entry: a multiple of 8
-    uint64_t contentPos;       // where the records begin
-    int32_t extended;          // entries: int64 positions; else unsigned int32, position = entry * 8
-    int32_t dirRow0, dirCol0, dirNRows, dirNCols;       // the directory's rectangle of tiles
-    int32_t nColsOfTiles;
+    GfFileDir dir;             // the tile directory (gvrs_file_parse.h)
     int32_t tileRow0, tileCol0, nTileRows, nTileCols;   // the block's rectangle of tiles: nTileRows * nTileCols <= 0x7fffffff slots
     uint64_t *starts, *ends;   // per slot: the record's extent [position - 8, min(imageBytes, position - 8 + size))
     int32_t *verdict;          // per slot
@@ -638,10 +635,9 @@ constexpr uint64_t GF_UPDATE_UNTOUCHED = ~0ull;   // recPos of a record that cha
 constexpr uint32_t GF_UPDATE_LDS_NODES = 2048;    // a list of up to this capacity lives in LDS (32 KiB), a larger one in scratch
 struct GfFileUpdateArgs {
     uint8_t *image;            // 8-byte aligned; the old image in its first oldBytes bytes
-    uint64_t imageCap, oldBytes, contentPos;
-    uint64_t entriesPos;       // the old tile directory: its entries and rectangle
-    int32_t oldExtended, dirRow0, dirCol0, dirNRows, dirNCols;
-    int32_t nColsOfTiles, nTilesGrid;
+    uint64_t imageCap, oldBytes;
+    GfFileDir dir;             // the OLD tile directory (gvrs_file_parse.h)
+    int32_t nTilesGrid;
     int32_t checksums, compression, forceExtended;
     int64_t timeModified;
     const uint8_t *blob;       // 8-byte aligned

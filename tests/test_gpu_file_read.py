@@ -217,6 +217,25 @@ def test_damage_entry_cleared(ctx):
         assert present.tolist() == [1, 1, 1, 1, 0, 1, 1, 1, 1]
 
 
+@pytest.mark.parametrize("extended", [False, True], ids=["compact", "extended"])
+def test_last_entry_behind_the_image_end(ctx, extended):
+    """the directory is the image's last record: an image cut inside, or in front of, its last entry refuses that tile alone"""
+    rows, cols = np.meshgrid(np.arange(16), np.arange(16), indexing="ij")
+    cells = (rows * 100 + cols + 1).astype(np.int32)
+    records = {t: B.standard_record(t, [cells[(t // 2) * 8:(t // 2) * 8 + 8, (t % 2) * 8:(t % 2) * 8 + 8]]) for t in range(4)}
+    image, _ = B.build_image((16, 16, 8, 8), [B.element("z", "int")], records, extended=extended)
+    f = gridfour_amd.GvrsFileHip(image)
+    at, w = B.entry_offset(image, f.info, 3)
+    # entry 3 is the directory's last and the directory the image's last record: only its padding and checksum lie behind
+    assert f.info["dir_n_rows"] * f.info["dir_n_cols"] == 4 and len(image) - (at + w) == 8
+    want = cells.copy()
+    want[8:, 8:] = INT_MIN
+    for cut in (at + w - 1, at):
+        blocks, status, present = both_forms(f, ctx, (0, 0, 16, 16), image=image[:cut])
+        assert status.tolist() == [[OK, OK, OK, ERR_BOUNDS]] and present.tolist() == [1, 1, 1, 0]
+        assert np.array_equal(blocks[0], want)
+
+
 @pytest.mark.parametrize("size", [0, 12, 16, 124, 1 << 20, -8])
 def test_damage_size_word(ctx, size):
     check_damage(ctx, True, lambda im, named, f: put(im, named[4] - 8, struct.pack("<i", size)), 4, ERR_BOUNDS)
