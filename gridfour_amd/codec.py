@@ -1917,7 +1917,8 @@ class GvrsFileFacts:
 class GvrsFileHip:
     """org.gridfour.gvrs.GvrsFile(file, "r") with GvrsElement.readBlock for all elements: a version 1.04 file opened from its path
     or its bytes (gf_file_open: the header record and the tile directory's prefix, parsed on the host), blocks read from the file
-    image by gf_file_read_block_elems[_dev]; and, as static methods, new file images written: assemble (tile records in, host
+    image by gf_file_read_block_elems[_dev], cells and interpolated values at scattered points by gf_file_read_points_elems[_dev] and
+    gf_file_interp_points[_dev] (only the tiles the points touch are decoded); and, as static methods, new file images written: assemble (tile records in, host
     memory), write_image (blocks in device memory in, the image out) and write_image_host.  .info is the gf_file_info as a dict, with the elements' names, the codec ids and the
     product label; .elems are the elements as the record calls of CodecMasterHip take them."""
 
@@ -1988,6 +1989,139 @@ class GvrsFileHip:
         _call("gf_file_read_block_elems", ctx.handle, self._h, _ptr(image), image.size, _ptr(rect), int(bool(verify_checksums)), _ptrs(out),
               _ptr(status), _ptr(present))
         return out, status, present
+
+    # ---- reads at points (gf_file_cells_tiles, gf_file_interp_tiles, gf_file_read_points_elems[_dev], gf_file_interp_points[_dev]) ----
+    def points_spec(self, elem=0, **kw):
+        """interp_spec() for element elem of this file over its whole grid: wrap, target, row_spacing, col_spacing, row_fringe and
+        col_fringe as there.  The point reads take grid, type and fill from the file; the block route reads them from the spec."""
+        el = self.info["elems"][elem]
+        return interp_spec(self.grid[0], self.grid[1], elem_type=el["type"], fill_i=el["fill_i"], **kw)
+
+    def _touched(self, name, head, rows, cols):
+        n = C.c_size_t()
+        _call(name, *head, rows.size, _ptr(rows), _ptr(cols), None, 0, C.byref(n))
+        tiles = np.zeros(n.value, np.int32)
+        _call(name, *head, rows.size, _ptr(rows), _ptr(cols), _ptr(tiles) if tiles.size else None, tiles.size, C.byref(n))
+        return tiles
+
+    def cells_tiles(self, rows, cols):
+        """gf_file_cells_tiles: the distinct tiles the cells (rows[i], cols[i]) touch, ascending; a cell outside the grid touches none."""
+        rows, cols = np.ascontiguousarray(rows, np.int32).ravel(), np.ascontiguousarray(cols, np.int32).ravel()
+        assert rows.size == cols.size
+        return self._touched("gf_file_cells_tiles", (self._h,), rows, cols)
+
+    def interp_tiles(self, spec, rows, cols):
+        """gf_file_interp_tiles: the distinct tiles the 4 x 4 windows of the query points touch, ascending (spec: wrap and fringes)."""
+        rows, cols = np.ascontiguousarray(rows, np.float64).ravel(), np.ascontiguousarray(cols, np.float64).ravel()
+        assert rows.size == cols.size
+        return self._touched("gf_file_interp_tiles", (self._h, _ptr(spec)), rows, cols)
+
+    @staticmethod
+    def _points_done(name, st, return_code):
+        if st != _lib.ERR_CAPACITY or not return_code:
+            check(st, name)
+
+    def read_points_dev(self, ctx, rows, cols, verify_checksums=True, image=None, max_tiles=None, return_code=False):
+        """gf_file_read_points_elems_dev: the cells (rows[i], cols[i]) of every element read from the file image in device memory
+        (uploaded here), decoding only the tiles they touch.  max_tiles: the pool's room in tiles (default: the host's count).
+        Returns ([values [n] per element], status [n_elems, n], the touched tiles' count); return_code: ERR_CAPACITY does not
+        raise and (..., the call's status, the 16 bytes behind every output buffer) is returned, the outputs as they were pre-set
+        (every byte 0x7f) where the call wrote nothing."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        rows, cols = np.ascontiguousarray(rows, np.int32).ravel(), np.ascontiguousarray(cols, np.int32).ravel()
+        assert rows.size == cols.size
+        n = rows.size
+        max_tiles = self.cells_tiles(rows, cols).size if max_tiles is None else int(max_tiles)
+        touched = C.c_size_t()
+        with _DeviceScope(ctx) as s:
+            d_image = s.upload(image, slack=32, fill=0)
+            d_rows, d_cols = s.upload(rows, slack=16), s.upload(cols, slack=16)
+            d_val = [s.alloc(n * np.dtype(dt).itemsize + 16, fill=0x7f) for dt in self._dtypes]
+            d_st = s.alloc(self.n_elems * n * 4 + 16, fill=0x7f)
+            st = lib().gf_file_read_points_elems_dev(ctx.handle, self._h, d_image.ptr, image.size, n, d_rows.ptr, d_cols.ptr,
+                                                     int(bool(verify_checksums)), max_tiles, s.ptrs(d_val), d_st.ptr, C.byref(touched))
+            self._points_done("gf_file_read_points_elems_dev", st, return_code)
+            ctx.synchronize()
+            out = ([b.download(dt, n) for b, dt in zip(d_val, self._dtypes)], d_st.download(np.int32, self.n_elems * n).reshape(self.n_elems, n),
+                   touched.value)
+            if not return_code:
+                return out
+            slack = [b.download(np.uint8, 16, n * np.dtype(dt).itemsize) for b, dt in zip(d_val, self._dtypes)]
+            return out + (st, slack + [d_st.download(np.uint8, 16, self.n_elems * n * 4)])
+
+    def read_points(self, ctx, rows, cols, verify_checksums=True, image=None, max_tiles=None, return_code=False):
+        """The same through gf_file_read_points_elems, the host-memory form: only the touched tiles' records are staged.
+        return_code: (..., the call's status)."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        rows, cols = np.ascontiguousarray(rows, np.int32).ravel(), np.ascontiguousarray(cols, np.int32).ravel()
+        assert rows.size == cols.size
+        n = rows.size
+        max_tiles = self.cells_tiles(rows, cols).size if max_tiles is None else int(max_tiles)
+        out = [np.full(n, 0x7f, np.uint8).repeat(np.dtype(dt).itemsize).view(dt) for dt in self._dtypes]
+        status = np.full((self.n_elems, n), 0x7f7f7f7f, np.int32)
+        touched = C.c_size_t()
+        st = lib().gf_file_read_points_elems(ctx.handle, self._h, _ptr(image), image.size, n, _ptr(rows), _ptr(cols), int(bool(verify_checksums)),
+                                             max_tiles, _ptrs(out), _ptr(status), C.byref(touched))
+        self._points_done("gf_file_read_points_elems", st, return_code)
+        return (out, status, touched.value) + ((st,) if return_code else ())
+
+    @staticmethod
+    def _interp_names(target):
+        return ["z"] + (["zx", "zy"] if target >= INTERP_FIRST else []) + (["zxx", "zxy", "zyy"] if target >= INTERP_SECOND else [])
+
+    def interp_points_dev(self, ctx, elem, spec, rows, cols, col_spacing=None, verify_checksums=True, image=None, max_tiles=None,
+                          return_code=False):
+        """gf_file_interp_points_dev: B-spline interpolation of element elem at the query points, from the file image in device
+        memory (uploaded here); of spec (points_spec()) wrap, target, spacings and fringes are read.  Returns (the dict
+        GvrsHipContext.interp_points returns, the touched tiles' count); return_code: ERR_CAPACITY does not raise and (..., the
+        call's status) is returned, the outputs as they were pre-set (every byte 0x7f) where the call wrote nothing."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        rows, cols = np.ascontiguousarray(rows, np.float64).ravel(), np.ascontiguousarray(cols, np.float64).ravel()
+        assert rows.size == cols.size
+        n, target = rows.size, int(spec["target"][0])
+        cs = None if col_spacing is None else np.ascontiguousarray(col_spacing, np.float64).ravel()
+        assert cs is None or cs.size == n
+        max_tiles = self.interp_tiles(spec, rows, cols).size if max_tiles is None else int(max_tiles)
+        sizes = {k: n * 8 for k in self._interp_names(target)}
+        if target >= INTERP_FIRST:
+            sizes["normal"] = n * 24
+        sizes["status"] = n * 4
+        touched = C.c_size_t()
+        with _DeviceScope(ctx) as s:
+            d_image = s.upload(image, slack=32, fill=0)
+            d_rows, d_cols = s.upload(rows, slack=16), s.upload(cols, slack=16)
+            d_cs = None if cs is None else s.upload(cs, slack=16)
+            d_out = {k: s.alloc(b + 16, fill=0x7f) for k, b in sizes.items()}
+            o = _out_struct(_INTERP_OUT, {k: b.ptr for k, b in d_out.items()})
+            st = lib().gf_file_interp_points_dev(ctx.handle, self._h, d_image.ptr, image.size, int(elem), _ptr(spec), n, d_rows.ptr, d_cols.ptr,
+                                                 None if d_cs is None else d_cs.ptr, int(bool(verify_checksums)), max_tiles, _ptr(o),
+                                                 C.byref(touched))
+            self._points_done("gf_file_interp_points_dev", st, return_code)
+            ctx.synchronize()
+            res = {k: d_out[k].download(np.int32 if k == "status" else np.float64, sizes[k] // (4 if k == "status" else 8)) for k in sizes}
+            if "normal" in res:
+                res["normal"] = res["normal"].reshape(n, 3)
+            return (res, touched.value) + ((st,) if return_code else ())
+
+    def interp_points(self, ctx, elem, spec, rows, cols, col_spacing=None, verify_checksums=True, image=None, max_tiles=None, return_code=False):
+        """The same through gf_file_interp_points, the host-memory form."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        rows, cols = np.ascontiguousarray(rows, np.float64).ravel(), np.ascontiguousarray(cols, np.float64).ravel()
+        assert rows.size == cols.size
+        n, target = rows.size, int(spec["target"][0])
+        cs = None if col_spacing is None else np.ascontiguousarray(col_spacing, np.float64).ravel()
+        assert cs is None or cs.size == n
+        max_tiles = self.interp_tiles(spec, rows, cols).size if max_tiles is None else int(max_tiles)
+        res = {k: np.full(n, 0x7f, np.uint8).repeat(8).view(np.float64) for k in self._interp_names(target)}
+        if target >= INTERP_FIRST:
+            res["normal"] = np.full(n * 3, 0x7f, np.uint8).repeat(8).view(np.float64).reshape(n, 3)
+        res["status"] = np.full(n, 0x7f7f7f7f, np.int32)
+        o = _out_struct(_INTERP_OUT, {k: a.ctypes.data for k, a in res.items()})
+        touched = C.c_size_t()
+        st = lib().gf_file_interp_points(ctx.handle, self._h, _ptr(image), image.size, int(elem), _ptr(spec), n, _ptr(rows), _ptr(cols),
+                                         None if cs is None else _ptr(cs), int(bool(verify_checksums)), max_tiles, _ptr(o), C.byref(touched))
+        self._points_done("gf_file_interp_points", st, return_code)
+        return (res, touched.value) + ((st,) if return_code else ())
 
     # ---- files written (gf_file_assemble, gf_file_write_block_elems[_dev]) ----
     @staticmethod

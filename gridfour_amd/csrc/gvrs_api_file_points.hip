@@ -1,0 +1,409 @@
+// gvrs_api_file_points.hip -- GVRS files read at scattered POINTS: cells (GvrsElement.readValue / readValueInt over a batch) and
+// B-spline interpolation (GvrsInterpolatorBSpline.z / zNormal over a batch) straight from a file image, decoding only the tiles
+// the points touch.  gf_file_cells_tiles / gf_file_interp_tiles are host arithmetic (gvrs_file_points.h; no device, no context).
+// The device forms mark and rank the touched tiles (k_points_mark, k_points_rank), learn their count (the first synchronisation),
+// locate their records in the image (k_file_locate over the list), decode them into a pool through the records' pipeline of
+// gvrs_api_records_dev.hip (the second synchronisation) and sample the pool (k_points_cells, k_points_interp).  The host forms
+// take the touched tiles from the two host functions, look their records up in the host image and stage them end to end, as
+// gf_file_read_block_elems does; the tail behind the lookup is one function for both.
+// Reference: gvrs/TileAccessIndices.java:78-92, gvrs/GvrsElement.java (readValue), gvrs/GvrsInterpolatorBSpline.java:283-334, :374-484.
+
+#include "gvrs_api_internal.h"
+
+namespace {
+
+constexpr int64_t POINTS_MAX_TILES_GRID = (int64_t)1 << 27;                    // bitmap and prefixes: 16 MB each at the most
+
+GfPointsGrid gridOf(const gf_file_info &i) { return gf_points_grid(i.grid.n_rows_grid, i.grid.n_cols_grid, i.grid.n_rows_tile, i.grid.n_cols_tile); }
+
+// ---- the touched tiles on the host: the bitmap the kernels build, built by the same functions ----
+void setBit(std::vector<uint32_t> &bits, int32_t tile) { bits[(uint32_t)tile >> 5] |= 1u << ((uint32_t)tile & 31u); }
+
+std::vector<uint32_t> cellsBits(const GfPointsGrid &g, size_t n, const int32_t *rows, const int32_t *cols)
+{
+    std::vector<uint32_t> bits(gf_points_words(g.nTilesGrid), 0u);
+    for (size_t t = 0; t < n; t++) {
+        int32_t tile, at;
+        if (gf_points_cell(g, rows[t], cols[t], tile, at)) setBit(bits, tile);
+    }
+    return bits;
+}
+
+std::vector<uint32_t> windowsBits(const GfPointsGrid &g, const GfInterpGeom &ig, size_t n, const double *rows, const double *cols)
+{
+    std::vector<uint32_t> bits(gf_points_words(g.nTilesGrid), 0u);
+    for (size_t t = 0; t < n; t++) {
+        GfInterpWindow w;
+        if (gf_interp_window(ig, rows[t], cols[t], w) != GF_IP_OK) continue;
+        const GfWindowTiles wt = gf_points_window_tiles(g, w.row0, w.col0, w.n1);
+        for (int32_t k = 0, nk = wt.count(); k < nk; k++) setBit(bits, wt.at(k));
+    }
+    return bits;
+}
+
+// the bitmap's tiles in ascending order: at most cap of them into tiles, all of them counted
+size_t listBits(const std::vector<uint32_t> &bits, int32_t *tiles, size_t cap)
+{
+    size_t n = 0;
+    for (size_t w = 0; w < bits.size(); w++)
+        for (uint32_t word = bits[w]; word != 0u; word &= word - 1u, n++)
+            if (n < cap) tiles[n] = (int32_t)(w * 32u + (uint32_t)__builtin_ctz(word));
+    return n;
+}
+
+// ---- argument checks (before the context or a device is looked at) ----
+// what the interpolation forms read of a spec; fills ig for the whole grid of the file and element elem (elem < 0: no element)
+gf_status pointsSpecArgs(const gf_file_info &i, const gf_interp_spec *spec, int elem, bool perPointSpacing, GfInterpGeom &ig)
+{
+    if (!spec) return GF_ERR_ARG;
+    if (i.grid.n_rows_grid < 4 || i.grid.n_cols_grid < 4) return GF_ERR_ARG;                       // (GvrsInterpolatorBSpline.java:113-116)
+    if (spec->wrap < 0 || spec->wrap > 2 || spec->target < GF_INTERP_VALUE || spec->target > GF_INTERP_SECOND) return GF_ERR_ARG;
+    if (elem >= i.n_elems) return GF_ERR_ARG;
+    if (elem >= 0 && spec->target >= GF_INTERP_FIRST && (spec->row_spacing == 0 || (spec->col_spacing == 0 && !perPointSpacing))) return GF_ERR_ARG;
+    ig = GfInterpGeom{};
+    gf_points_whole_grid(ig, gridOf(i));
+    ig.elemType = elem >= 0 ? i.elems[elem].type : GF_ELEM_INT, ig.fillI = elem >= 0 ? i.elems[elem].fill_i : 0;
+    ig.wrap = spec->wrap, ig.target = spec->target;
+    ig.rowSpacing = spec->row_spacing, ig.colSpacing = spec->col_spacing;
+    ig.rowFringe0 = spec->row_fringe0, ig.rowFringe1 = spec->row_fringe1, ig.colFringe0 = spec->col_fringe0, ig.colFringe1 = spec->col_fringe1;
+    return GF_OK;
+}
+
+// what all four reads check of file, image and counts; fills the codec list and the fills' bits as the records' calls take them
+gf_status pointsFileArgs(const gf_context *c, const gf_file_info &i, const uint8_t *image, size_t imageBytes, bool onDevice, size_t nPoints,
+                         size_t maxTiles, int *codecs, uint32_t *fill)
+{
+    if (!c || !image) return GF_ERR_ARG;
+    if (onDevice && ((uintptr_t)image & 7) != 0) return GF_ERR_ARG;
+    if (imageBytes < i.content_pos) return GF_ERR_ARG;                            // (not the image that was opened)
+    for (int k = 0; k < i.n_codecs; k++) codecs[k] = i.codecs[k] == GF_CODEC_UNKNOWN ? GF_CODEC_NONE : i.codecs[k];
+    // (values, offsets and statuses of the records' checks: their places are taken by the image, which is only looked at for null)
+    const void *some[GF_MAX_ELEMS];
+    for (int e = 0; e < GF_MAX_ELEMS; e++) some[e] = image;
+    const gf_status sa = elemsArgs(c, codecs, i.n_codecs, i.elems, i.n_elems, i.grid.n_rows_tile, i.grid.n_cols_tile, 0, image, onDevice,
+                                   (const uint64_t *)image, (void *const *)some, (const int32_t *)image);
+    const gf_status s = firstOf(sa, elemFills(i.elems, i.n_elems, fill));
+    if (s != GF_OK) return s;
+    for (int k = 0; k < i.n_codecs; k++)
+        if (i.codecs[k] == GF_CODEC_UNKNOWN) return GF_ERR_UNSUPPORTED;
+    if (gfTilesOfGrid(i.grid).count() > POINTS_MAX_TILES_GRID) return GF_ERR_UNSUPPORTED;
+    if (nPoints > 0x7fffffffull || maxTiles > 0x7fffffffull / (size_t)i.n_elems) return GF_ERR_UNSUPPORTED;   // (they travel as 32 bits)
+    return GF_OK;
+}
+
+gf_status interpOutArgs(const gf_interp_spec *spec, const gf_interp_out *out)
+{
+    if (!spec || !out || !out->z) return GF_ERR_ARG;
+    if (spec->target == GF_INTERP_VALUE && out->normal) return GF_ERR_ARG;
+    return GF_OK;
+}
+
+// ---- the device side ----
+// the context's part of a call, sized by maxTiles before the first launch (the count is learnt behind it, and a buffer that grew
+// would have moved): bitmap | prefixes | count || list | starts | ends | verdicts | the records' tile indices | slot statuses
+struct PointsBuf {
+    uint32_t *bits, *prefix, *count;
+    int32_t *list, *verdict, *indices, *slotStatus;
+    uint64_t *starts, *ends;
+    size_t nWords;
+};
+gf_status pointsBuf(gf_context *c, const GfPointsGrid &g, int nElems, size_t maxTiles, bool withExtents, PointsBuf &b)
+{
+    Carve k;
+    b.nWords = gf_points_words(g.nTilesGrid);
+    const size_t bitsAt = k.add(b.nWords * 4), prefixAt = k.add(b.nWords * 4), countAt = k.add(16), listAt = k.add(maxTiles * 4);
+    const size_t startsAt = k.add(withExtents ? maxTiles * 8 : 0), endsAt = k.add(withExtents ? maxTiles * 8 : 0);
+    const size_t verdictAt = k.add(withExtents ? maxTiles * 4 : 0), indicesAt = k.add(maxTiles * 4), statusAt = k.add((size_t)nElems * maxTiles * 4);
+    const gf_status s = c->dFilePoints.ensure(k);
+    if (s != GF_OK) return s;
+    const DevBuf &B = c->dFilePoints;
+    b.bits = B.at<uint32_t>(bitsAt), b.prefix = B.at<uint32_t>(prefixAt), b.count = B.at<uint32_t>(countAt);
+    b.list = B.at<int32_t>(listAt), b.starts = B.at<uint64_t>(startsAt), b.ends = B.at<uint64_t>(endsAt);
+    b.verdict = B.at<int32_t>(verdictAt), b.indices = B.at<int32_t>(indicesAt), b.slotStatus = B.at<int32_t>(statusAt);
+    return GF_OK;
+}
+
+// what a call samples: cells of every element, or the windows of one
+struct PointsWhat {
+    bool windows;
+    size_t nPoints;
+    const int32_t *rowsI, *colsI;                 // cells (device)
+    void *const *values;                          // HOST array of device pointers
+    int32_t *status;
+    GfInterpGeom ig;                              // windows
+    int elem;
+    const double *rowsD, *colsD, *colSpacing;
+    GfInterpArgs out;                             // its output pointers alone
+};
+
+// bitmap zeroed, k_points_mark, k_points_rank (enqueued)
+gf_status pointsMarkRank(hipStream_t st, const GfPointsGrid &g, const PointsWhat &w, const PointsBuf &b, size_t maxTiles)
+{
+    GF_HIP(hipMemsetAsync(b.bits, 0, b.nWords * 4, st));
+    GfPointsMarkArgs m{};
+    m.g = g, m.ig = w.ig, m.nPoints = w.nPoints;
+    m.rowsI = w.rowsI, m.colsI = w.colsI, m.rowsD = w.rowsD, m.colsD = w.colsD;
+    m.bits = b.bits;
+    GF_HIP(gf_launch_points_mark(m, w.windows, st));
+    GfPointsRankArgs r{};
+    r.bits = b.bits, r.nWords = (uint32_t)b.nWords, r.prefix = b.prefix, r.list = b.list, r.maxTiles = (uint32_t)maxTiles, r.count = b.count;
+    GF_HIP(gf_launch_points_rank(r, st));
+    return GF_OK;
+}
+
+// THE TAIL both forms share: the n touched tiles' records -- slot s = [dStarts[s], dEnds[s]) of dBlob, the empty extent where
+// dVerdict[s] is not GF_FILE_LOCATED -- decoded into the pool (n * cells items per element, in dBlockTmp: one stream at a time,
+// as the block reads), the verdicts put into the slots' statuses, the pool sampled.  No lock taken, no argument checked.
+gf_status pointsTail(gf_context *c, hipStream_t st, const gf_file_info &i, const GfPointsGrid &g, const int *codecs, const uint32_t *fill, size_t n,
+                     const uint8_t *dBlob, size_t blobBytes, const uint64_t *dStarts, const uint64_t *dEnds, const int32_t *dVerdict,
+                     int verifyChecksum, const PointsBuf &b, const PointsWhat &w)
+{
+    const size_t cells = (size_t)g.nRowsTile * (size_t)g.nColsTile;
+    void *dPool[GF_MAX_ELEMS];
+    gf_status s;
+    if ((s = elemArrays(c->dBlockTmp, i.elems, i.n_elems, n * cells, dPool)) != GF_OK) return s;
+    if (n) {
+        s = recordsDecodeDev(c, st, codecs, i.n_codecs, i.elems, i.n_elems, g.nRowsTile, g.nColsTile, n, dBlob, blobBytes, dStarts, nullptr,
+                             verifyChecksum, b.indices, dPool, b.slotStatus, dEnds);
+        if (s != GF_OK) return s;
+        GF_HIP(gf_launch_file_status(dVerdict, b.slotStatus, n, i.n_elems, st));
+    }
+    GfPointsLookup look{b.bits, b.prefix, dVerdict, b.slotStatus, (uint32_t)n, (uint32_t)cells};
+    if (!w.windows) {
+        GfPointsCellsArgs a{};
+        a.g = g, a.look = look, a.nPoints = w.nPoints, a.rows = w.rowsI, a.cols = w.colsI, a.status = w.status, a.nElems = i.n_elems;
+        for (int e = 0; e < i.n_elems; e++) a.elems[e] = GfPointsElem{dPool[e], w.values[e], fill[e], (uint32_t)elemItemBytes(i.elems[e].type)};
+        GF_HIP(gf_launch_points_cells(a, st));
+    } else {
+        GfPointsInterpArgs a{};
+        a.g = g, a.ig = w.ig, a.look = look;
+        a.look.slotStatus = b.slotStatus + (size_t)w.elem * n;
+        a.pool = dPool[w.elem], a.fillBits = fill[w.elem];
+        a.nPoints = w.nPoints, a.rows = w.rowsD, a.cols = w.colsD, a.colSpacing = w.colSpacing;
+        a.z = w.out.z, a.zx = w.out.zx, a.zy = w.out.zy, a.zxx = w.out.zxx, a.zxy = w.out.zxy, a.zyy = w.out.zyy;
+        a.normal = w.out.normal, a.status = w.out.status;
+        GF_HIP(gf_launch_points_interp(a, st));
+    }
+    return GF_OK;
+}
+
+// the device forms behind their checks: mark, rank, the count (synchronises), locate over the list, the tail
+gf_status pointsDev(gf_context *c, const gf_file_info &i, const uint8_t *dImage, size_t imageBytes, const int *codecs, const uint32_t *fill,
+                    int verifyChecksum, size_t maxTiles, const PointsWhat &w, size_t *nTouched)
+{
+    *nTouched = 0;
+    if (w.nPoints == 0) return GF_OK;
+    if (!i.checksum_enabled) verifyChecksum = 0;                                  // (the records of such a file carry none)
+    const GfPointsGrid g = gridOf(i);
+    if (maxTiles > (size_t)g.nTilesGrid) maxTiles = (size_t)g.nTilesGrid;         // (no set of points touches more)
+    GF_CTX_LOCK(c);
+    GF_HIP(hipSetDevice(c->device));
+    const hipStream_t st = c->stream;
+    PointsBuf b;
+    gf_status s;
+    if ((s = pointsBuf(c, g, i.n_elems, maxTiles, true, b)) != GF_OK) return s;
+    if ((s = c->hRecCounts.ensure(256 * 4)) != GF_OK) return s;
+    if ((s = pointsMarkRank(st, g, w, b, maxTiles)) != GF_OK) return s;
+    // the first synchronisation: the host sizes the pool and the records' pipeline by the count
+    GF_HIP(hipMemcpyAsync(c->hRecCounts.p, b.count, 4, hipMemcpyDeviceToHost, st));
+    GF_HIP(hipStreamSynchronize(st));
+    const size_t n = *(const uint32_t *)c->hRecCounts.p;
+    *nTouched = n;
+    if (n > maxTiles) return GF_ERR_CAPACITY;                                     // (nothing of the outputs has been written)
+    GfFileLocateArgs a{};
+    a.image = dImage, a.imageBytes = imageBytes, a.dir = gfFileDirOf(i);
+    a.starts = b.starts, a.ends = b.ends, a.verdict = b.verdict;
+    a.tileList = b.list, a.nList = (uint32_t)n;
+    GF_HIP(gf_launch_file_locate(a, st));
+    return pointsTail(c, st, i, g, codecs, fill, n, dImage, imageBytes, b.starts, b.ends, b.verdict, verifyChecksum, b, w);
+}
+
+// The host forms behind their checks.  The touched tiles (bits: the host's bitmap) are looked up in the host image; a record the
+// framing walk would refuse for its size word is refused here, so that the staged records are whole, multiples of 8 and end to
+// end (as gf_file_read_block_elems).  stage(sg, w) declares the call's coordinates and outputs and fills w with their places.
+template <class Declare, class Place>
+gf_status pointsHost(gf_context *c, const gf_file_info &i, const uint8_t *image, size_t imageBytes, const int *codecs, const uint32_t *fill,
+                     int verifyChecksum, size_t maxTiles, const std::vector<uint32_t> &bits, PointsWhat &w, size_t *nTouched, Declare declare,
+                     Place place)
+{
+    *nTouched = 0;
+    if (w.nPoints == 0) return GF_OK;
+    if (!i.checksum_enabled) verifyChecksum = 0;
+    const GfPointsGrid g = gridOf(i);
+    const size_t n = listBits(bits, nullptr, 0);
+    *nTouched = n;
+    if (n > maxTiles) return GF_ERR_CAPACITY;
+    std::vector<int32_t> list(n), verdict(n);
+    listBits(bits, list.data(), n);
+    std::vector<uint64_t> from, starts(n, 0), ends(n, 0);
+    uint64_t blobBytes = 0;
+    const GfFileDir dir = gfFileDirOf(i);
+    for (size_t s = 0; s < n; s++) {
+        uint64_t pos;
+        uint32_t size;
+        int32_t v = gfFileLocate(dir, image, imageBytes, list[s], &pos, &size);
+        if (v == GF_OK && pos != 0) {
+            if (size < 20u || (size & 7u) != 0u || (uint64_t)size > imageBytes - (pos - 8)) v = GF_ERR_BOUNDS;
+            else {
+                v = GF_FILE_LOCATED;
+                from.push_back(pos - 8);
+                starts[s] = blobBytes, ends[s] = blobBytes + size;
+                blobBytes += size;
+            }
+        }
+        verdict[s] = v;
+    }
+    std::vector<uint8_t> blob((size_t)blobBytes + 16);
+    for (size_t s = 0, r = 0; s < n; s++)
+        if (verdict[s] == GF_FILE_LOCATED) memcpy(blob.data() + starts[s], image + from[r++], (size_t)(ends[s] - starts[s]));
+    GF_CTX_LOCK(c);
+    GF_HIP(hipSetDevice(c->device));
+    const hipStream_t st = c->stream;
+    PointsBuf b;
+    gf_status s;
+    if ((s = pointsBuf(c, g, i.n_elems, n, false, b)) != GF_OK) return s;
+    // staging: the records | starts | ends | verdicts | the call's coordinates and outputs
+    HostStage sg(c);
+    const int blobP = sg.in(blob.data(), (size_t)blobBytes, 32), startsP = sg.in(starts.data(), n * 8), endsP = sg.in(ends.data(), n * 8);
+    const int verdictP = sg.in(verdict.data(), n * 4);
+    declare(sg);
+    if ((s = sg.begin()) != GF_OK) return s;
+    place(sg, w);
+    // the slots of the tiles on the device come from the device's own bitmap of the staged points (no list, no count read back)
+    if ((s = pointsMarkRank(st, g, w, b, 0)) != GF_OK) return s;
+    s = pointsTail(c, st, i, g, codecs, fill, n, sg.ptr<uint8_t>(blobP), (size_t)blobBytes, sg.ptr<uint64_t>(startsP), sg.ptr<uint64_t>(endsP),
+                   sg.ptr<int32_t>(verdictP), verifyChecksum, b, w);
+    return s != GF_OK ? s : sg.end();
+}
+
+}  // namespace
+
+extern "C" {
+
+gf_status gf_file_cells_tiles(const gf_file *f, size_t nPoints, const int32_t *rows, const int32_t *cols, int32_t *tiles, size_t tilesCap,
+                              size_t *nTiles)
+{
+    if (!f || !nTiles || (nPoints && (!rows || !cols)) || (tilesCap && !tiles)) return GF_ERR_ARG;
+    *nTiles = 0;
+    gf_file_info i;
+    const gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK) return s;
+    if (gfTilesOfGrid(i.grid).count() > POINTS_MAX_TILES_GRID) return GF_ERR_UNSUPPORTED;
+    *nTiles = listBits(cellsBits(gridOf(i), nPoints, rows, cols), tiles, tilesCap);
+    return GF_OK;
+}
+
+gf_status gf_file_interp_tiles(const gf_file *f, const gf_interp_spec *spec, size_t nPoints, const double *rows, const double *cols, int32_t *tiles,
+                               size_t tilesCap, size_t *nTiles)
+{
+    if (!f || !spec || !nTiles || (nPoints && (!rows || !cols)) || (tilesCap && !tiles)) return GF_ERR_ARG;
+    *nTiles = 0;
+    gf_file_info i;
+    gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK) return s;
+    GfInterpGeom ig;
+    if ((s = pointsSpecArgs(i, spec, -1, true, ig)) != GF_OK) return s;
+    if (gfTilesOfGrid(i.grid).count() > POINTS_MAX_TILES_GRID) return GF_ERR_UNSUPPORTED;
+    *nTiles = listBits(windowsBits(gridOf(i), ig, nPoints, rows, cols), tiles, tilesCap);
+    return GF_OK;
+}
+
+gf_status gf_file_read_points_elems_dev(gf_context *c, const gf_file *f, const uint8_t *dImage, size_t imageBytes, size_t nPoints,
+                                        const int32_t *dRows, const int32_t *dCols, int verifyChecksum, size_t maxTiles, void *const *dValues,
+                                        int32_t *dStatus, size_t *nTouched)
+{
+    if (!c || !f || !dImage || !dValues || !dStatus || !nTouched || (nPoints && (!dRows || !dCols))) return GF_ERR_ARG;
+    gf_file_info i;
+    gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK) return s;
+    for (int e = 0; e < i.n_elems; e++)
+        if (!dValues[e]) return GF_ERR_ARG;
+    int codecs[255];
+    uint32_t fill[GF_MAX_ELEMS];
+    if ((s = pointsFileArgs(c, i, dImage, imageBytes, true, nPoints, maxTiles, codecs, fill)) != GF_OK) return s;
+    PointsWhat w{};
+    w.windows = false, w.nPoints = nPoints, w.rowsI = dRows, w.colsI = dCols, w.values = dValues, w.status = dStatus;
+    return pointsDev(c, i, dImage, imageBytes, codecs, fill, verifyChecksum, maxTiles, w, nTouched);
+}
+
+gf_status gf_file_interp_points_dev(gf_context *c, const gf_file *f, const uint8_t *dImage, size_t imageBytes, int elem, const gf_interp_spec *spec,
+                                    size_t nPoints, const double *dRows, const double *dCols, const double *dColSpacing, int verifyChecksum,
+                                    size_t maxTiles, const gf_interp_out *out, size_t *nTouched)
+{
+    if (!c || !f || !dImage || !nTouched || elem < 0 || (nPoints && (!dRows || !dCols))) return GF_ERR_ARG;
+    gf_file_info i;
+    gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK || (s = interpOutArgs(spec, out)) != GF_OK) return s;
+    PointsWhat w{};
+    if ((s = pointsSpecArgs(i, spec, elem, dColSpacing != nullptr, w.ig)) != GF_OK) return s;
+    int codecs[255];
+    uint32_t fill[GF_MAX_ELEMS];
+    if ((s = pointsFileArgs(c, i, dImage, imageBytes, true, nPoints, maxTiles, codecs, fill)) != GF_OK) return s;
+    w.windows = true, w.nPoints = nPoints, w.elem = elem, w.rowsD = dRows, w.colsD = dCols, w.colSpacing = dColSpacing;
+    w.out.z = out->z, w.out.zx = out->zx, w.out.zy = out->zy, w.out.zxx = out->zxx, w.out.zxy = out->zxy, w.out.zyy = out->zyy;
+    w.out.normal = out->normal, w.out.status = out->status;
+    return pointsDev(c, i, dImage, imageBytes, codecs, fill, verifyChecksum, maxTiles, w, nTouched);
+}
+
+gf_status gf_file_read_points_elems(gf_context *c, const gf_file *f, const uint8_t *image, size_t imageBytes, size_t nPoints, const int32_t *rows,
+                                    const int32_t *cols, int verifyChecksum, size_t maxTiles, void *const *values, int32_t *status,
+                                    size_t *nTouched)
+{
+    if (!c || !f || !image || !values || !status || !nTouched || (nPoints && (!rows || !cols))) return GF_ERR_ARG;
+    gf_file_info i;
+    gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK) return s;
+    for (int e = 0; e < i.n_elems; e++)
+        if (!values[e]) return GF_ERR_ARG;
+    int codecs[255];
+    uint32_t fill[GF_MAX_ELEMS];
+    if ((s = pointsFileArgs(c, i, image, imageBytes, false, nPoints, maxTiles, codecs, fill)) != GF_OK) return s;
+    PointsWhat w{};
+    w.windows = false, w.nPoints = nPoints;
+    int rowsP = 0, colsP = 0, valueP[GF_MAX_ELEMS], statusP = 0;
+    void *dValues[GF_MAX_ELEMS];
+    return pointsHost(
+        c, i, image, imageBytes, codecs, fill, verifyChecksum, maxTiles, cellsBits(gridOf(i), nPoints, rows, cols), w, nTouched,
+        [&](HostStage &sg) {
+            rowsP = sg.in(rows, nPoints * 4), colsP = sg.in(cols, nPoints * 4);
+            stageElems(sg, STAGE_OUT, i.elems, i.n_elems, nPoints, values, valueP);
+            statusP = sg.out(status, (size_t)i.n_elems * nPoints * 4);
+        },
+        [&](HostStage &sg, PointsWhat &p) {
+            sg.ptrs(valueP, i.n_elems, dValues);
+            p.rowsI = sg.ptr<int32_t>(rowsP), p.colsI = sg.ptr<int32_t>(colsP), p.values = dValues, p.status = sg.ptr<int32_t>(statusP);
+        });
+}
+
+gf_status gf_file_interp_points(gf_context *c, const gf_file *f, const uint8_t *image, size_t imageBytes, int elem, const gf_interp_spec *spec,
+                                size_t nPoints, const double *rows, const double *cols, const double *colSpacing, int verifyChecksum,
+                                size_t maxTiles, const gf_interp_out *out, size_t *nTouched)
+{
+    if (!c || !f || !image || !nTouched || elem < 0 || (nPoints && (!rows || !cols))) return GF_ERR_ARG;
+    gf_file_info i;
+    gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK || (s = interpOutArgs(spec, out)) != GF_OK) return s;
+    PointsWhat w{};
+    if ((s = pointsSpecArgs(i, spec, elem, colSpacing != nullptr, w.ig)) != GF_OK) return s;
+    int codecs[255];
+    uint32_t fill[GF_MAX_ELEMS];
+    if ((s = pointsFileArgs(c, i, image, imageBytes, false, nPoints, maxTiles, codecs, fill)) != GF_OK) return s;
+    w.windows = true, w.nPoints = nPoints, w.elem = elem;
+    double *const host[6] = {out->z, out->zx, out->zy, out->zxx, out->zxy, out->zyy};
+    int rowsP = 0, colsP = 0, csP = 0, devP[6], normalP = 0, statusP = 0;
+    return pointsHost(
+        c, i, image, imageBytes, codecs, fill, verifyChecksum, maxTiles, windowsBits(gridOf(i), w.ig, nPoints, rows, cols), w, nTouched,
+        [&](HostStage &sg) {
+            rowsP = sg.in(rows, nPoints * 8), colsP = sg.in(cols, nPoints * 8), csP = sg.in(colSpacing, nPoints * 8);
+            for (int k = 0; k < 6; k++) devP[k] = sg.out(host[k], nPoints * 8);
+            normalP = sg.out(out->normal, nPoints * 24), statusP = sg.out(out->status, nPoints * 4);
+        },
+        [&](HostStage &sg, PointsWhat &p) {
+            p.rowsD = sg.ptr<double>(rowsP), p.colsD = sg.ptr<double>(colsP), p.colSpacing = sg.ptr<double>(csP);
+            p.out.z = sg.ptr<double>(devP[0]), p.out.zx = sg.ptr<double>(devP[1]), p.out.zy = sg.ptr<double>(devP[2]);
+            p.out.zxx = sg.ptr<double>(devP[3]), p.out.zxy = sg.ptr<double>(devP[4]), p.out.zyy = sg.ptr<double>(devP[5]);
+            p.out.normal = sg.ptr<double>(normalP), p.out.status = sg.ptr<int32_t>(statusP);
+        });
+}
+
+}  // extern "C"

@@ -154,6 +154,8 @@ struct gf_context {
     DevBuf dTabPartials{this}, dTabSort{this};  // tabulation (gvrs_api_tabulate.hip): k_tabulate_dense's partials (fixed size); the symbol form's
                                                 // keys, histograms and runs, a strip's table and the merge's chunk counts
     DevBuf dFileLoc{this};                      // file images (gvrs_api_file.hip): the extents and verdicts of the rectangle's tiles
+    DevBuf dFilePoints{this};                   // file images read at points (gvrs_api_file_points.hip): the bitmap of touched tiles, its prefixes,
+                                                // the list with its extents and verdicts, the slots' statuses; the pool itself lies in dBlockTmp
     DevBuf dFileWrite{this};                    // file images written (gvrs_api_file_write.hip): the kernels' state, the records' offsets, the
                                                 // metadata directory on its way to its place, the tile directory's chunk checksums
     DevBuf dFileUpdateBlob{this};               // ... the records of a rectangle on their way into the image, and their offsets

@@ -13,7 +13,8 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// k_file_locate: a lane per tile of the block's rectangle of tiles, slot j = row-major.  The lanes of a wave run along a tile row,
+// k_file_locate: a lane per tile of the block's rectangle of tiles, slot j = row-major, or per tile of a list in ascending order
+// (the tiles that a set of points touches: gvrs_file_points.hip).  The lanes of a wave run along a tile row,
 // so their directory entries are neighbours: one coalesced 4- or 8-byte load each (the entries start at a multiple of 8 of an
 // 8-byte aligned image).  The tile is looked up by gfFileLocateHead (gvrs_file_parse.h), the head in one 16-byte load; a tile
 // that is present and passes is GF_FILE_LOCATED.  The size word is not judged here: the extent [position - 8, min(imageBytes,
@@ -24,9 +25,16 @@ namespace {
 __global__ __launch_bounds__(256) void k_file_locate(const GfFileLocateArgs a)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-    if (j >= (uint32_t)a.nTileRows * (uint32_t)a.nTileCols) return;
-    const int32_t ty = (int32_t)(j / (uint32_t)a.nTileCols), tx = (int32_t)(j - (uint32_t)ty * (uint32_t)a.nTileCols);
-    const int32_t tileRow = a.tileRow0 + ty, tileCol = a.tileCol0 + tx;
+    int32_t tileRow, tileCol;
+    if (a.tileList) {                                                                  // (uniform) slot j = the list's tile j
+        if (j >= a.nList) return;
+        const int32_t t = a.tileList[j];
+        tileRow = t / a.dir.nColsOfTiles, tileCol = t - tileRow * a.dir.nColsOfTiles;
+    } else {
+        if (j >= (uint32_t)a.nTileRows * (uint32_t)a.nTileCols) return;
+        const int32_t ty = (int32_t)(j / (uint32_t)a.nTileCols), tx = (int32_t)(j - (uint32_t)ty * (uint32_t)a.nTileCols);
+        tileRow = a.tileRow0 + ty, tileCol = a.tileCol0 + tx;
+    }
     const int32_t tileIndex = tileRow * a.dir.nColsOfTiles + tileCol;                 // (< the grid's tiles <= 0x7fffffff)
     uint64_t p, start = 0, end = 0;
     GfU4 h;
@@ -60,8 +68,9 @@ __global__ __launch_bounds__(256) void k_file_status(const int32_t *__restrict__
 
 hipError_t gf_launch_file_locate(const GfFileLocateArgs &a, hipStream_t stream)
 {
-    const uint64_t n = (uint64_t)a.nTileRows * (uint64_t)a.nTileCols;
-    if (a.nTileRows < 1 || a.nTileCols < 1 || n > 0x7fffffffull || a.dir.nColsOfTiles < 1) return hipErrorInvalidValue;
+    const uint64_t n = a.tileList ? (uint64_t)a.nList : (uint64_t)a.nTileRows * (uint64_t)a.nTileCols;
+    if (a.tileList && n == 0) return hipSuccess;
+    if ((!a.tileList && (a.nTileRows < 1 || a.nTileCols < 1)) || n > 0x7fffffffull || a.dir.nColsOfTiles < 1) return hipErrorInvalidValue;
     if (((uintptr_t)a.image & 7u) != 0 || !gfDirEntriesAligned(a.dir)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_file_locate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
     return hipGetLastError();

@@ -14,6 +14,7 @@
 #include "gvrs_tabulate_common.h"
 #include "gvrs_lsop_container.h"
 #include "gvrs_file_parse.h"
+#include "gvrs_file_points.h"
 
 // per-tile status values written by the kernels; identical to gf_status in
 // include/gvrs_hip_codec.h
@@ -578,10 +579,72 @@ struct GfFileLocateArgs {
     uint64_t *starts, *ends;   // per slot: the record's extent [position - 8, min(imageBytes, position - 8 + size))
     int32_t *verdict;          // per slot
     uint8_t *present;          // may be null; per slot: 1 where the directory's entry is not 0
+    const int32_t *tileList;   // may be null; else slot j = the tile tileList[j] of the grid, j < nList, and the rectangle is not read
+    uint32_t nList;            // <= 0x7fffffff
 };
 hipError_t gf_launch_file_locate(const GfFileLocateArgs &a, hipStream_t stream);
 // status[e * nSlots + j] = verdict[j] wherever that is not GF_FILE_LOCATED
 hipError_t gf_launch_file_status(const int32_t *verdict, int32_t *status, size_t nSlots, int nElems, hipStream_t stream);
+
+// A file image read at POINTS (gvrs_file_points.hip; driven by gvrs_api_file_points.hip; the arithmetic is gvrs_file_points.h).
+// k_points_mark sets the bit of every tile a point needs in a bitmap of one bit per tile of the grid (zeroed by the host): cells
+// (rowsI / colsI) or the 4 x 4 windows of interpolation points (rowsD / colsD through gf_interp_window of ig); a refused point
+// marks nothing.  k_points_rank, ONE workgroup, writes per word the exclusive prefix of the popcounts, the touched tiles in
+// ascending order (at most maxTiles of them) and their count.  The touched tiles' records are then located (k_file_locate over
+// the list) and decoded by the records' pipeline into a pool, tile of slot s at pool + s * cells items, and k_points_cells /
+// k_points_interp sample the pool: a tile's slot is gf_points_slot(bits, prefix, tile).
+constexpr uint32_t GF_POINTS_RANK_CHUNK = 1024;    // words of the bitmap a turn of k_points_rank's loop takes (= its lanes)
+struct GfPointsMarkArgs {
+    GfPointsGrid g;
+    GfInterpGeom ig;           // windows: the whole grid as the block; wrap and the fringes
+    size_t nPoints;            // <= 0x7fffffff
+    const int32_t *rowsI, *colsI;
+    const double *rowsD, *colsD;
+    uint32_t *bits;
+};
+hipError_t gf_launch_points_mark(const GfPointsMarkArgs &a, bool windows, hipStream_t stream);
+struct GfPointsRankArgs {
+    const uint32_t *bits;
+    uint32_t nWords;           // <= 2^22
+    uint32_t *prefix;          // nWords
+    int32_t *list;             // maxTiles entries
+    uint32_t maxTiles;
+    uint32_t *count;           // one word: the touched tiles, whatever maxTiles is
+};
+hipError_t gf_launch_points_rank(const GfPointsRankArgs &a, hipStream_t stream);
+struct GfPointsElem {          // an element of the file for k_points_cells
+    const void *pool;          // decoded tiles, slot s at pool + s * cells items
+    void *values;              // per point, in the delivered type
+    uint32_t fillBits, itemBytes;
+};
+struct GfPointsLookup {        // what both sampling kernels take of the touched tiles
+    const uint32_t *bits, *prefix;
+    const int32_t *verdict;    // per slot: GF_FILE_LOCATED or what k_file_locate found
+    const int32_t *slotStatus; // [e * nSlots + s]: the records' pipeline's, with the verdicts put in (k_file_status)
+    uint32_t nSlots, cells;
+};
+struct GfPointsCellsArgs {
+    GfPointsGrid g;
+    GfPointsLookup look;
+    size_t nPoints;
+    const int32_t *rows, *cols;
+    int32_t *status;           // [e * nPoints + i]
+    int nElems;
+    GfPointsElem elems[GF_K_MAX_ELEMS];
+};
+hipError_t gf_launch_points_cells(const GfPointsCellsArgs &a, hipStream_t stream);
+struct GfPointsInterpArgs {
+    GfPointsGrid g;
+    GfInterpGeom ig;           // the whole grid as the block; the element's type and fill
+    GfPointsLookup look;       // slotStatus: the element's row of it
+    const void *pool;          // the element's
+    uint32_t fillBits;
+    size_t nPoints;
+    const double *rows, *cols, *colSpacing;
+    double *z, *zx, *zy, *zxx, *zxy, *zyy, *normal;
+    int32_t *status;
+};
+hipError_t gf_launch_points_interp(const GfPointsInterpArgs &a, hipStream_t stream);
 
 // A file image WRITTEN (gvrs_file_write.hip; driven by gvrs_api_file_write.hip): behind the record writer, which has laid the records
 // of the rectangle's tiles into the image from firstRecordPos on and left their offsets, the kernels find the bounding rectangle of

@@ -1341,6 +1341,69 @@ gf_status gf_file_read_block_elems_dev(gf_context *ctx, const gf_file *f, const 
 gf_status gf_file_read_block_elems(gf_context *ctx, const gf_file *f, const uint8_t *image, size_t image_bytes,
                                    const gf_rect *rect, int verify_checksum, void *const *blocks, int32_t *status, uint8_t *present);
 
+/* ---- GVRS files read at POINTS: cells and B-spline interpolation at scattered points, straight from a file image -----------------
+ * (gvrs/GvrsElement.java readValue / readValueInt, gvrs/TileAccessIndices.java:78-92 computeAccessIndices,
+ * gvrs/GvrsInterpolatorBSpline.java:283-334 z / zNormal, :374-484 the window)
+ * The reference's primary read interface is one cell or one query point at a time, and its tile cache loads only the tiles a
+ * point needs.  These calls do the same for a BATCH: they find the tiles the points touch, decode those tiles alone into a pool
+ * of the context and sample the pool; no block is built.  A track across an ETOPO1-shaped grid decodes its few hundred tiles,
+ * not the 12,960 of its bounding rectangle.
+ *   gf_file_cells_tiles / gf_file_interp_tiles need no device and no context (host arithmetic, like gf_file_open): the distinct
+ *   tiles the points touch, in ascending tile index.  *n_tiles is always the full count; at most tiles_cap entries are written;
+ *   tiles may be NULL with a cap of 0, which is the way to size max_tiles.  A cell's tile is (row / n_rows_tile) * tiles across +
+ *   col / n_cols_tile; a cell outside the grid touches none.  An interpolation point touches the tiles of its 4 x 4 window -- rows
+ *   row0 .. row0 + 3, columns col0 .. col0 + n1 - 1 and, where the window wraps, columns 0 .. 3 - n1 -- and none when it has no
+ *   window: a NaN coordinate, a point outside the fringe, a wrapped window the reference's readBlock rejects.
+ *   THE DEVICE FORMS take the image in device memory as gf_file_read_block_elems_dev does (8-byte aligned, readable to the end of
+ *   the aligned 16-byte piece that holds its last byte), coordinates and outputs in device memory, and run on the CONTEXT'S
+ *   stream: they take no stream argument.  They synchronise that stream TWICE -- once to learn how many tiles are touched, once
+ *   inside the records' pipeline -- and are not capture-safe; the sampling kernel is enqueued behind the second and not waited for.
+ *   CELL READS (gf_file_read_points_elems_dev; d_values a HOST array of n_elems device pointers, d_values[e] of n_points items in
+ *   the element's delivered type; d_status[e * n_points + i]): d_values[e][i] is bit for bit the cell gf_file_read_block_elems_dev
+ *   delivers at (rows[i], cols[i]) for element e, the fill where the directory names no record for the tile.  A point outside the
+ *   grid: GF_ERR_ARG for every element, the fill, and no tile touched (the reference throws).  Where the tile's directory entry or
+ *   record is refused, or the element fails to decode, the point carries the status the block read puts at that tile and element,
+ *   and the fill.  Duplicate points are fine; outputs are in point order.
+ *   INTERPOLATION (gf_file_interp_points_dev; element elem of the file): of spec the fields wrap, target, the spacings and the
+ *   fringes are read; n_rows_grid, n_cols_grid, block, elem_type and fill_i are NOT: they come from the file -- its grid, the whole
+ *   grid as the block, element elem.  For every point outputs and status equal what gf_block_interp_points_dev gives over the
+ *   whole-grid block of element elem read by gf_file_read_block_elems_dev: GF_ERR_ARG / GF_DECLINED / GF_OK in its order
+ *   (GF_ERR_BOUNDS cannot arise).  ONE ADDITION: if element elem of any tile of the window did not decode to GF_OK, the point takes
+ *   the status of the lowest-indexed such tile and all its outputs are NaN -- the block route silently interpolates fill there.
+ *   max_tiles: the pool holds touched * cells items per element (in the buffer of the context the block reads decode into: one
+ *   call at a time, one stream).  If the points touch more than max_tiles tiles the call returns GF_ERR_CAPACITY,
+ *   *n_tiles_touched holds the count and NO output item and no status has been written.  Otherwise it returns GF_OK whatever the
+ *   per-point statuses are and *n_tiles_touched is the count.  n_points == 0: GF_OK, a count of 0, nothing written; max_tiles == 0
+ *   with points that touch nothing is GF_OK.  Checksums are verified only where the file enables them, as in the block read.
+ *   THE HOST FORMS (gf_file_read_points_elems, gf_file_interp_points): image, coordinates and outputs in host memory.  The touched
+ *   tiles come from the two host functions, their records are looked up in the host image and staged end to end -- never the whole
+ *   image -- exactly as gf_file_read_block_elems stages; then the same device tail runs.
+ * GF_ERR_ARG, before the context or a device is looked at: null pointers (coordinates may be NULL with n_points == 0; out->z is
+ * required, the other outputs are not); an unaligned d_image; image_bytes < content_pos; elem out of range; wrap or target out of
+ * range; with target >= GF_INTERP_FIRST a zero row_spacing, or a zero col_spacing without per-point spacings; normal with target
+ * GF_INTERP_VALUE; a grid under 4 x 4 for the interpolation forms.  GF_ERR_UNSUPPORTED: a codec list that holds GF_CODEC_UNKNOWN;
+ * more than 2^27 tiles in the grid (bitmap and prefixes stay under 16 MB each); n_points or max_tiles * n_elems beyond 0x7fffffff
+ * (they travel as 32 bits in the pipeline).                                                                                       */
+gf_status gf_file_cells_tiles(const gf_file *f, size_t n_points, const int32_t *rows, const int32_t *cols,
+                              int32_t *tiles, size_t tiles_cap, size_t *n_tiles);
+gf_status gf_file_interp_tiles(const gf_file *f, const gf_interp_spec *spec, size_t n_points, const double *rows,
+                               const double *cols, int32_t *tiles, size_t tiles_cap, size_t *n_tiles);
+gf_status gf_file_read_points_elems_dev(gf_context *ctx, const gf_file *f, const uint8_t *d_image, size_t image_bytes,
+                                        size_t n_points, const int32_t *d_rows, const int32_t *d_cols, int verify_checksum,
+                                        size_t max_tiles, void *const *d_values /* HOST array of n_elems device pointers */,
+                                        int32_t *d_status /* [e * n_points + i] */, size_t *n_tiles_touched);
+gf_status gf_file_read_points_elems(gf_context *ctx, const gf_file *f, const uint8_t *image, size_t image_bytes,
+                                    size_t n_points, const int32_t *rows, const int32_t *cols, int verify_checksum,
+                                    size_t max_tiles, void *const *values, int32_t *status, size_t *n_tiles_touched);
+gf_status gf_file_interp_points_dev(gf_context *ctx, const gf_file *f, const uint8_t *d_image, size_t image_bytes, int elem,
+                                    const gf_interp_spec *spec, size_t n_points, const double *d_rows, const double *d_cols,
+                                    const double *d_col_spacing, int verify_checksum, size_t max_tiles,
+                                    const gf_interp_out *out, size_t *n_tiles_touched);
+gf_status gf_file_interp_points(gf_context *ctx, const gf_file *f, const uint8_t *image, size_t image_bytes, int elem,
+                                const gf_interp_spec *spec, size_t n_points, const double *rows, const double *cols,
+                                const double *col_spacing, int verify_checksum, size_t max_tiles,
+                                const gf_interp_out *out, size_t *n_tiles_touched);
+
 /* ---- GVRS files WRITTEN: a new file image from a rectangle of the raster, in one call ------------------------------------------
  * (gvrs/GvrsFile.java:239-300 the constructor that writes the header, :584-616 close; gvrs/GvrsFileSpecification.java:1170-1285
  * write; gvrs/GvrsMetadata.java:217-234 write; gvrs/RecordManager.java:161-204, 218-219 a record's frame and size, :670-719

@@ -50,12 +50,10 @@ def _series(timer, fns):
                 "spread_ms": round(max(v) - min(v), 4), "reps": REPS} for k, v in ms.items()}
 
 
-def main(argv):
-    out_path = argv[argv.index("--out") + 1] if "--out" in argv else None
-    tile_rows = int(argv[argv.index("--tile-rows") + 1]) if "--tile-rows" in argv else 90
+def etopo_image(ctx, tile_rows=90):
+    """The ETOPO1-shaped file image (tools/file_points_rate.py reads it too): (image bytes, the grid's shape, the raster the records
+    hold, the tiles' cells [nt, cells], the writer's record blob with its offsets and tile indices and the codec each record used)"""
     nt = tile_rows * TILES_ACROSS
-    L = lib()
-    ctx = gridfour_amd.GvrsHipContext(0)
     b = DeviceTileBatch(ctx, N_ROWS, N_COLS, nt, slot_stride=16)
     b.synth_dem(0x9E3779B97F4A7C15 + 2, TILES_ACROSS)
     ctx.synchronize()
@@ -67,13 +65,24 @@ def main(argv):
     whole = (0, 0) + grid_shape
     idx, blob, off, used, st = master.write_block_dev(N_ROWS, N_COLS, grid_shape, whole, [want], ["int"], raw=True)
     assert not st.any() and sorted(idx.tolist()) == list(range(nt))
-    total = int(off[nt])
     # the file image: the writer's records in shuffled order, a metadata record in front of every third one
     rng = np.random.default_rng(12960)
     records = {int(idx[t]): blob[int(off[t]):int(off[t + 1])].tobytes() for t in range(nt)}
     image, positions = FB.build_image(grid_shape + (N_ROWS, N_COLS), [FB.element("z", "int")], records, codec_ids=IDS,
                                       order=[int(t) for t in rng.permutation(nt)], extended=True,
                                       between=lambda k: FB.other_record(FB.RECORD_METADATA, 64, seed=k) if k % 3 == 0 else b"")
+    return image, grid_shape, want, vals, blob, off, idx, used
+
+
+def main(argv):
+    out_path = argv[argv.index("--out") + 1] if "--out" in argv else None
+    tile_rows = int(argv[argv.index("--tile-rows") + 1]) if "--tile-rows" in argv else 90
+    nt = tile_rows * TILES_ACROSS
+    L = lib()
+    ctx = gridfour_amd.GvrsHipContext(0)
+    image, grid_shape, want, vals, blob, off, idx, used = etopo_image(ctx, tile_rows)
+    whole = (0, 0) + grid_shape
+    total = int(off[nt])
     f = gridfour_amd.GvrsFileHip(image)
     sparse = bytearray(image)
     for t in range(0, nt, 4):
