@@ -154,6 +154,11 @@ SIGNATURES = {
     "gf_file_update_records_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_int64, C.c_int, C.c_size_t, _vp, _vp]),
     "gf_file_update_block_elems_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     "gf_file_update_block_elems": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int64, _vp, C.c_size_t, C.POINTER(C.c_uint64), _vp, _vp, _vp]),
+    "gf_file_update_plan_tiles": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gf_file_update_points_elems_dev": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int64, _vp, C.c_size_t, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, C.POINTER(C.c_size_t)]),
+    "gf_file_update_points_elems": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int64, _vp, C.c_size_t,
+                                              C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, C.POINTER(C.c_size_t)]),
     "gf_file_inspect_plan": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gf_file_inspect": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     "gf_file_inspect_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),

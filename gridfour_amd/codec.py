@@ -1919,7 +1919,8 @@ class GvrsFileHip:
     or its bytes (gf_file_open: the header record and the tile directory's prefix, parsed on the host), blocks read from the file
     image by gf_file_read_block_elems[_dev], cells and interpolated values at scattered points by gf_file_read_points_elems[_dev] and
     gf_file_interp_points[_dev] (only the tiles the points touch are decoded); and, as static methods, new file images written: assemble (tile records in, host
-    memory), write_image (blocks in device memory in, the image out) and write_image_host.  .info is the gf_file_info as a dict, with the elements' names, the codec ids and the
+    memory), write_image (blocks in device memory in, the image out) and write_image_host; an image updated in place by
+    update_image[_host] (a rectangle) and update_points[_host] (scattered cells: only the touched tiles are rewritten).  .info is the gf_file_info as a dict, with the elements' names, the codec ids and the
     product label; .elems are the elements as the record calls of CodecMasterHip take them."""
 
     _ELEM_NAMES = {kind.type: name for name, kind in _ELEM_KINDS.items()}
@@ -2296,6 +2297,86 @@ class GvrsFileHip:
             return rc, need, image[:n].tobytes(), idx, status, used
         check(rc, "gf_file_update_block_elems")
         return image[:n].tobytes(), idx, status, used
+
+    # ---- writes at scattered points (gf_file_update_plan_tiles, gf_file_update_points_elems[_dev]) ----
+    @staticmethod
+    def update_plan_tiles(upd, n_tiles):
+        """gf_file_update_plan_tiles: GvrsFileUpdate.plan for a count of touched tiles in place of a rectangle -> (the largest
+        image an update of that many tiles can need, the free list's capacity for it)."""
+        most, cap = C.c_uint64(), C.c_uint64()
+        _call("gf_file_update_plan_tiles", upd.handle, int(n_tiles), C.byref(most), C.byref(cap))
+        return most.value, cap.value
+
+    def _points_args(self, upd, rows, cols, values, image_cap, max_tiles):
+        rows, cols = np.ascontiguousarray(rows, np.int32).ravel(), np.ascontiguousarray(cols, np.int32).ravel()
+        assert rows.size == cols.size and len(values) == self.n_elems
+        values = [np.ascontiguousarray(v, dt).ravel() for v, dt in zip(values, self._dtypes)]
+        assert all(v.size == rows.size for v in values)
+        room = self.cells_tiles(rows, cols).size if max_tiles is None else int(max_tiles)
+        cap = self.update_plan_tiles(upd, min(room, self.cells_tiles(rows, cols).size))[0] if image_cap is None else int(image_cap)
+        return rows, cols, values, room, cap
+
+    def update_points(self, ctx, upd, rows, cols, values, time_modified, flags=0, image_cap=None, max_tiles=None, raw=False):
+        """gf_file_update_points_elems_dev: values (per element [n]: int32 / int16 / float32, an "icf" element's float VALUES)
+        stored into the cells (rows[i], cols[i]) of the image upd was begun on, in device memory, as element.writeValue point after
+        point and close() would.  Uploads, calls, synchronises, downloads: (image bytes, point status [n_elems, n], tile indices
+        [t], tile status [t], codec used [n_elems, t]) over the t touched tiles, ascending.  max_tiles: the room in tiles (default:
+        the host's count); image_cap: the room of the image (default: the plan's for the touched tiles).  raw: (the call's return
+        value, file status, the size the image has or needs, the whole buffer of image_cap + 64 bytes -- the old image, then 0xA5
+        --, point status, tile indices [room + 4], tile status [room + 4], codec used [n_elems * room + 16], the touched tiles'
+        count), every output pre-set to bytes 0x7f, and nothing raises."""
+        rows, cols, values, room, cap = self._points_args(upd, rows, cols, values, image_cap, max_tiles)
+        n, ne = rows.size, self.n_elems
+        buf = np.full(cap + 64, 0xA5, np.uint8)
+        buf[:min(cap, upd.image.size)] = upd.image[:min(cap, upd.image.size)]
+        touched = C.c_size_t()
+        with _DeviceScope(ctx) as s:
+            d_rows, d_cols = s.upload(rows, slack=16), s.upload(cols, slack=16)
+            d_val = [s.upload(v, slack=16) for v in values]
+            d_image = s.upload(buf)
+            d_bytes, d_fst = s.alloc(16, fill=0x7f), s.alloc(16, fill=0x7f)
+            d_pst = s.alloc(ne * n * 4 + 16, fill=0x7f)
+            d_idx, d_st = s.alloc((room + 4) * 4, fill=0x7f), s.alloc((room + 4) * 4, fill=0x7f)
+            d_used = s.alloc(ne * room + 16, fill=0x7f)
+            rc = lib().gf_file_update_points_elems_dev(ctx.handle, upd.handle, n, d_rows.ptr, d_cols.ptr, s.ptrs(d_val), room, int(flags),
+                                                       int(time_modified), d_image.ptr, cap, d_bytes.ptr, d_fst.ptr, d_pst.ptr, d_idx.ptr,
+                                                       d_st.ptr, d_used.ptr, C.byref(touched))
+            ctx.synchronize()
+            t = touched.value
+            fst, n_bytes = int(d_fst.download(np.int32, 1)[0]), int(d_bytes.download(np.uint64, 1)[0])
+            image = d_image.download(np.uint8, cap + 64)
+            pst = d_pst.download(np.int32, ne * n).reshape(ne, n)
+            idx, st, used = d_idx.download(np.int32, room + 4), d_st.download(np.int32, room + 4), d_used.download(np.uint8, ne * room + 16)
+        if raw:
+            return rc, fst, n_bytes, image.tobytes(), pst, idx, st, used, t
+        check(rc, "gf_file_update_points_elems_dev")
+        if n:
+            check(fst, "gf_file_update_points_elems_dev")
+        else:
+            n_bytes = upd.image.size                                 # (nothing was enqueued: the image is the old one)
+        return image[:n_bytes].tobytes(), pst, idx[:t], st[:t], used[:ne * t].reshape(ne, t)
+
+    def update_points_host(self, ctx, upd, rows, cols, values, time_modified, flags=0, image_cap=None, max_tiles=None, return_code=False):
+        """gf_file_update_points_elems: the same through host memory, any codec list -> (image bytes, point status, tile indices,
+        tile status, codec used); a negative per-tile status raises unless return_code is set: then (the call's return value, the
+        size the image has or needs, the touched tiles' count) come first, and the arrays are whole: tile indices and status
+        [room], codec used [n_elems * room], pre-set to bytes 0x7f."""
+        rows, cols, values, room, cap = self._points_args(upd, rows, cols, values, image_cap, max_tiles)
+        n, ne = rows.size, self.n_elems
+        image = np.full(max(cap, 1), 0xA5, np.uint8)
+        image[:min(cap, upd.image.size)] = upd.image[:min(cap, upd.image.size)]
+        pst = np.full((ne, n), 0x7f7f7f7f, np.int32)
+        idx, st = np.full(room + 1, 0x7f7f7f7f, np.int32), np.full(room + 1, 0x7f7f7f7f, np.int32)
+        used = np.full(ne * room + 1, 0x7f, np.uint8)
+        need, touched = C.c_uint64(), C.c_size_t()
+        rc = lib().gf_file_update_points_elems(ctx.handle, upd.handle, n, _ptr(rows), _ptr(cols), _ptrs(values), room, int(flags), int(time_modified),
+                                               _ptr(image), cap, C.byref(need), _ptr(pst), _ptr(idx), _ptr(st), _ptr(used), C.byref(touched))
+        t = touched.value
+        nb = min(need.value, cap) if rc != _lib.ERR_CAPACITY else min(upd.image.size, cap)
+        if return_code:
+            return rc, need.value, t, image[:nb].tobytes(), pst, idx[:room], st[:room], used[:ne * room]
+        check(rc, "gf_file_update_points_elems")
+        return image[:nb].tobytes(), pst, idx[:t], st[:t], used[:ne * t].reshape(ne, t)
 
     # ---- files inspected (gf_file_inspect[_dev]) ----
     def inspect_plan(self, image_bytes=None):

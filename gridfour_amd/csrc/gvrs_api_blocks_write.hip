@@ -19,8 +19,11 @@ uint32_t floatBits(float f)
     return u;
 }
 
+}  // namespace
+
 // the cut's description of every element (block, tiles and old tiles are set later); GF_ERR_ARG for a range with min > max or a NaN
 // bound.  ranges == null: the default constructors of GvrsElementSpecification{Int,Short,Float,IntCodedFloat}.
+// (gvrs_api_file_points.hip shares it)
 gf_status cutElems(const gf_elem_spec *elems, const gf_elem_range *ranges, int nElems, GfBlockCutElem *t)
 {
     for (int e = 0; e < nElems; e++) {
@@ -54,8 +57,6 @@ gf_status cutElems(const gf_elem_spec *elems, const gf_elem_range *ranges, int n
     }
     return GF_OK;
 }
-
-}  // namespace
 
 // what the host can check, before the context or a device is looked at; fills g and the cut's element descriptions
 // (gvrs_api_image.hip shares it)
@@ -176,6 +177,74 @@ gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCod
                             blobCap, dOffsets, dCodecUsed, dStatus, (const int32_t *)((uint8_t *)c->dBwMeta.p + m.pre));
 }
 
+// the tail of a host form that writes records (gvrs_api_internal.h); gf_block_write_elems and gf_file_update_points_elems end in it
+gf_status hostWriteTail(gf_context *c, HostStage &sg, const HostWriteParts &p, bool onDevice, const int *codecs, int nCodecs, const gf_elem_spec *elems,
+                        int nElems, int nRowsTile, int nColsTile, size_t nOut, const void *const *dTiles, const int32_t *dPre, int checksumEnabled,
+                        size_t maxBlob, uint8_t *blob, size_t blobCap, uint64_t *offsets, int32_t *tileIndices, uint8_t *codecUsed, int32_t *status)
+{
+    const size_t cells = (size_t)nRowsTile * (size_t)nColsTile, nInst = (size_t)nElems * nOut;
+    gf_status s;
+    if (onDevice) {
+        s = recordsEncodeDev(c, c->stream, codecs, nCodecs, elems, nElems, nRowsTile, nColsTile, nOut, sg.ptr<int32_t>(p.indices), dTiles,
+                             checksumEnabled, sg.ptr<uint8_t>(p.blob), maxBlob, sg.ptr<uint64_t>(p.offsets), sg.ptr<uint8_t>(p.used),
+                             sg.ptr<int32_t>(p.status), dPre);
+        if (s != GF_OK || (s = sg.flush()) != GF_OK) return s;
+        gf_status first = GF_OK;
+        for (size_t t = 0; t < nOut && first == GF_OK; t++)
+            if (status[t] < 0) first = (gf_status)status[t];
+        if (offsets[nOut] > blobCap) return first != GF_OK ? first : GF_ERR_CAPACITY;
+        if (offsets[nOut] && ((s = sg.fetch(p.blob, (size_t)offsets[nOut])) != GF_OK || (s = sg.end()) != GF_OK)) return s;
+        return first;
+    }
+    // a list that needs the host's zlib: the cut tiles and the verdicts come back from the device form's temporaries, the tiles that
+    // get a record go through the host encoders (which stage for themselves: this call's stage ends first), and the records are
+    // laid out with zero-length records for the others
+    std::vector<std::vector<uint8_t>> tiles(nElems);
+    for (int e = 0; e < nElems; e++) {
+        const size_t tb = nOut * cells * elemItemBytes(elems[e].type);
+        tiles[e].resize(tb + 4);                                                // (4 spare bytes: readable to the end of a SHORT array's last word)
+        GF_HIP(hipMemcpyAsync(tiles[e].data(), dTiles[e], tb, hipMemcpyDeviceToHost, c->stream));
+    }
+    GF_HIP(hipMemcpyAsync(status, dPre, nOut * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((s = sg.end()) != GF_OK) return s;
+    std::vector<size_t> keep;
+    gf_status first = GF_OK;
+    for (size_t t = 0; t < nOut; t++) {
+        if (status[t] == GF_OK) keep.push_back(t);
+        else if (status[t] < 0 && first == GF_OK) first = (gf_status)status[t];
+    }
+    const size_t nKeep = keep.size();
+    std::vector<int32_t> keptIdx(nKeep);
+    const void *keptValues[GF_MAX_ELEMS];
+    for (int e = 0; e < nElems; e++) {                                          // (compacted in place: keep[k] >= k)
+        const size_t tb = cells * elemItemBytes(elems[e].type);
+        for (size_t k = 0; k < nKeep; k++)
+            if (keep[k] != k) memmove(tiles[e].data() + k * tb, tiles[e].data() + keep[k] * tb, tb);
+        tiles[e].resize(nKeep * tb + 4);                                        // (never grows: sized with the spare bytes above)
+        keptValues[e] = tiles[e].data();
+    }
+    for (size_t k = 0; k < nKeep; k++) keptIdx[k] = tileIndices[keep[k]];
+    std::vector<uint64_t> keptOff(nKeep + 1, 0);
+    std::vector<uint8_t> keptUsed(nInst ? (size_t)nElems * nKeep + 1 : 1);
+    if (nKeep) {
+        s = recordsEncodeHost(c, codecs, nCodecs, elems, nElems, nRowsTile, nColsTile, nKeep, keptIdx.data(), keptValues, checksumEnabled, blob,
+                              blobCap, keptOff.data(), keptUsed.data());
+        if (s != GF_OK && s != GF_ERR_CAPACITY) return s;
+    } else s = GF_OK;
+    if (codecUsed) memset(codecUsed, 0xff, nInst);
+    size_t k = 0;
+    for (size_t t = 0; t < nOut; t++) {
+        offsets[t] = keptOff[k];
+        if (k < nKeep && keep[k] == t) {
+            if (codecUsed)
+                for (int e = 0; e < nElems; e++) codecUsed[(size_t)e * nOut + t] = keptUsed[(size_t)e * nKeep + k];
+            k++;
+        }
+    }
+    offsets[nOut] = keptOff[nKeep];
+    return first != GF_OK ? first : s;
+}
+
 extern "C" {
 
 gf_status gf_block_tile_rect(const gf_grid_spec *grid, const gf_rect *rect, int32_t *tileRow0, int32_t *tileCol0, int32_t *nTileRows,
@@ -241,7 +310,7 @@ gf_status gf_block_write_elems(gf_context *c, const int *codecs, int nCodecs, co
     GF_HIP(hipSetDevice(c->device));
     if (nCodecs < 0) nCodecs = 0;
     const bool onDevice = deviceList(codecs, nCodecs, elems, nElems);
-    const size_t cells = (size_t)g.nRowsTile * (size_t)g.nColsTile, nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
+    const size_t nOut = (size_t)g.nTileRows * (size_t)g.nTileCols;
     const size_t blockCells = (size_t)g.nRows * (size_t)g.nCols, oldBytes = nOld ? (size_t)oldOffsets[nOld] : 0;
     const size_t nInst = (size_t)nElems * nOut;
     const size_t maxBlob = onDevice ? nOut * gf_tile_record_max_bytes_elems(elems, nElems, g.nRowsTile, g.nColsTile) : 0;
@@ -264,65 +333,8 @@ gf_status gf_block_write_elems(gf_context *c, const int *codecs, int nCodecs, co
     s = blockCutDev(c, c->stream, codecs, nCodecs, elems, nElems, g, cut, dBlocks, nOld, sg.ptr<uint8_t>(oldP), oldBytes, sg.ptr<uint64_t>(oldOffP),
                     verifyOldChecksum, sg.ptr<int32_t>(indicesP), dTiles);
     if (s != GF_OK) return s;
-    if (onDevice) {
-        s = recordsEncodeDev(c, c->stream, codecs, nCodecs, elems, nElems, g.nRowsTile, g.nColsTile, nOut, sg.ptr<int32_t>(indicesP), dTiles,
-                             checksumEnabled, sg.ptr<uint8_t>(blobP), maxBlob, sg.ptr<uint64_t>(offsetsP), sg.ptr<uint8_t>(usedP),
-                             sg.ptr<int32_t>(statusP), dPre);
-        if (s != GF_OK || (s = sg.flush()) != GF_OK) return s;
-        gf_status first = GF_OK;
-        for (size_t t = 0; t < nOut && first == GF_OK; t++)
-            if (status[t] < 0) first = (gf_status)status[t];
-        if (offsets[nOut] > blobCap) return first != GF_OK ? first : GF_ERR_CAPACITY;
-        if (offsets[nOut] && ((s = sg.fetch(blobP, (size_t)offsets[nOut])) != GF_OK || (s = sg.end()) != GF_OK)) return s;
-        return first;
-    }
-    // a list that needs the host's zlib: the cut tiles and the verdicts come back from the device form's temporaries, the tiles that
-    // get a record go through the host encoders (which stage for themselves: this call's stage ends first), and the records are
-    // laid out with zero-length records for the others
-    std::vector<std::vector<uint8_t>> tiles(nElems);
-    for (int e = 0; e < nElems; e++) {
-        const size_t tb = nOut * cells * elemItemBytes(elems[e].type);
-        tiles[e].resize(tb + 4);                                                // (4 spare bytes: readable to the end of a SHORT array's last word)
-        GF_HIP(hipMemcpyAsync(tiles[e].data(), dTiles[e], tb, hipMemcpyDeviceToHost, c->stream));
-    }
-    GF_HIP(hipMemcpyAsync(status, dPre, nOut * 4, hipMemcpyDeviceToHost, c->stream));
-    if ((s = sg.end()) != GF_OK) return s;
-    std::vector<size_t> keep;
-    gf_status first = GF_OK;
-    for (size_t t = 0; t < nOut; t++) {
-        if (status[t] == GF_OK) keep.push_back(t);
-        else if (status[t] < 0 && first == GF_OK) first = (gf_status)status[t];
-    }
-    const size_t nKeep = keep.size();
-    std::vector<int32_t> keptIdx(nKeep);
-    const void *keptValues[GF_MAX_ELEMS];
-    for (int e = 0; e < nElems; e++) {                                          // (compacted in place: keep[k] >= k)
-        const size_t tb = cells * elemItemBytes(elems[e].type);
-        for (size_t k = 0; k < nKeep; k++)
-            if (keep[k] != k) memmove(tiles[e].data() + k * tb, tiles[e].data() + keep[k] * tb, tb);
-        tiles[e].resize(nKeep * tb + 4);                                        // (never grows: sized with the spare bytes above)
-        keptValues[e] = tiles[e].data();
-    }
-    for (size_t k = 0; k < nKeep; k++) keptIdx[k] = tileIndices[keep[k]];
-    std::vector<uint64_t> keptOff(nKeep + 1, 0);
-    std::vector<uint8_t> keptUsed(nInst ? (size_t)nElems * nKeep + 1 : 1);
-    if (nKeep) {
-        s = recordsEncodeHost(c, codecs, nCodecs, elems, nElems, g.nRowsTile, g.nColsTile, nKeep, keptIdx.data(), keptValues, checksumEnabled, blob,
-                              blobCap, keptOff.data(), keptUsed.data());
-        if (s != GF_OK && s != GF_ERR_CAPACITY) return s;
-    } else s = GF_OK;
-    if (codecUsed) memset(codecUsed, 0xff, nInst);
-    size_t k = 0;
-    for (size_t t = 0; t < nOut; t++) {
-        offsets[t] = keptOff[k];
-        if (k < nKeep && keep[k] == t) {
-            if (codecUsed)
-                for (int e = 0; e < nElems; e++) codecUsed[(size_t)e * nOut + t] = keptUsed[(size_t)e * nKeep + k];
-            k++;
-        }
-    }
-    offsets[nOut] = keptOff[nKeep];
-    return first != GF_OK ? first : s;
+    return hostWriteTail(c, sg, HostWriteParts{indicesP, blobP, offsetsP, statusP, usedP}, onDevice, codecs, nCodecs, elems, nElems, g.nRowsTile,
+                         g.nColsTile, nOut, dTiles, dPre, checksumEnabled, maxBlob, blob, blobCap, offsets, tileIndices, codecUsed, status);
 }
 
 }  // extern "C"

@@ -6,9 +6,19 @@
 // gvrs_api_records_dev.hip (the second synchronisation) and sample the pool (k_points_cells, k_points_interp).  The host forms
 // take the touched tiles from the two host functions, look their records up in the host image and stage them end to end, as
 // gf_file_read_block_elems does; the tail behind the lookup is one function for both.
-// Reference: gvrs/TileAccessIndices.java:78-92, gvrs/GvrsElement.java (readValue), gvrs/GvrsInterpolatorBSpline.java:283-334, :374-484.
+// And WRITTEN at scattered points (GvrsElement.writeValue / writeValueInt over a batch into a file opened "rw", then close()):
+// gf_file_update_points_elems[_dev] mark, rank and locate the touched tiles as the reads do, judge the old records' heads as an
+// update does (k_points_heads; the host form on the host), decode them into the pool, store the points' values into it by the
+// cell rule of gvrs_file_points_store.h (k_points_prepare, k_points_claim, k_points_store, k_points_verdict:
+// gvrs_file_points_write.hip; pointsWriteCells is that stretch for both forms), write the touched tiles' records from the pool
+// (the record writer of gvrs_api_records_enc.hip with the verdict as its pre-status; the host form through hostWriteTail, which
+// takes any codec list) and place them in ascending tile index (updateRecordsDev of gvrs_api_file_update.hip; the host form
+// through gfFileUpdateAssemble).
+// Reference: gvrs/TileAccessIndices.java:78-92, gvrs/GvrsElement.java (readValue), gvrs/GvrsInterpolatorBSpline.java:283-334, :374-484,
+// gvrs/TileElement{Int,Short,Float,IntCodedFloat}.java (setValue), gvrs/RasterTileCache.java, gvrs/RecordManager.java:386-490.
 
 #include "gvrs_api_internal.h"
+#include "gvrs_file_update.h"
 
 namespace {
 
@@ -276,6 +286,77 @@ gf_status pointsHost(gf_context *c, const gf_file_info &i, const uint8_t *image,
     return s != GF_OK ? s : sg.end();
 }
 
+// ---- writes at points ----
+// what both write forms check of handle, image and counts (pointsFileArgs on the handle's file; fills the codec list)
+gf_status pointsWriteArgs(const gf_context *c, const GfFileUpdate &h, const uint8_t *image, size_t imageCap, bool onDevice, size_t nPoints, size_t maxTiles,
+                          const void *const *values, int *codecs, size_t &maxRecord)
+{
+    const gf_file_info &i = h.info;
+    if (imageCap < h.imageBytes) return GF_ERR_ARG;
+    for (int e = 0; e < i.n_elems; e++)
+        if (!values[e]) return GF_ERR_ARG;
+    uint32_t fill[GF_MAX_ELEMS];
+    gf_status s = pointsFileArgs(c, i, image, (size_t)h.imageBytes, onDevice, nPoints, maxTiles, codecs, fill);
+    if (s != GF_OK) return s;
+    GfBlockGeom g{};
+    g.nRowsTile = i.grid.n_rows_tile, g.nColsTile = i.grid.n_cols_tile;
+    return fileMaxRecord(i.elems, i.n_elems, g, maxRecord);
+}
+
+// THE CELLS of both write forms: the n touched tiles' old records -- slot s = [dStarts[s], dEnds[s]) of dBlob, the empty extent
+// where dVerdict[s] is not GF_FILE_LOCATED -- decoded into the pool (dBlockTmp, in the record writer's types: an ICF element as
+// INT, its codes), new tiles filled, the points' values stored by the rule "the highest point index whose value passed owns the
+// cell" (one owner plane per element in dBwTiles, zeroed here), the points' statuses, the tiles' indices and the pre-status
+// (dBwMeta) that the record writer takes.  dList: the touched tiles, ascending.  No lock taken, no argument checked.
+gf_status pointsWriteCells(gf_context *c, hipStream_t st, const gf_file_info &i, const GfPointsGrid &g, size_t n, const uint8_t *dBlob,
+                           size_t blobBytes, const uint64_t *dStarts, const uint64_t *dEnds, const int32_t *dVerdict, const PointsBuf &b,
+                           const int32_t *dList, size_t nPoints, const int32_t *dRows, const int32_t *dCols, const void *const *dValues,
+                           int32_t *dPointStatus, int32_t *dTileIndices, void **dPool, const int32_t **dPre)
+{
+    const size_t cells = (size_t)g.nRowsTile * (size_t)g.nColsTile;
+    GfBlockCutElem cut[GF_MAX_ELEMS];
+    gf_status s;
+    if ((s = cutElems(i.elems, nullptr, i.n_elems, cut)) != GF_OK) return s;
+    if ((s = elemArrays(c->dBlockTmp, i.elems, i.n_elems, n * cells, dPool, 4)) != GF_OK) return s;   // (room behind a SHORT array's last word)
+    Carve planes, meta;
+    size_t planeAt[GF_MAX_ELEMS];
+    for (int e = 0; e < i.n_elems; e++) planeAt[e] = planes.add(n * cells * 4);
+    const size_t oldAt = meta.add(n * 4), storedAt = meta.add(n * 4), preAt = meta.add(n * 4);
+    if ((s = c->dBwTiles.ensure(planes)) != GF_OK || (s = c->dBwMeta.ensure(meta)) != GF_OK) return s;
+    if (n) {
+        gf_elem_spec asInt[GF_MAX_ELEMS];
+        for (int e = 0; e < i.n_elems; e++) {
+            asInt[e] = i.elems[e];
+            if (asInt[e].type == GF_ELEM_ICF) asInt[e].type = GF_ELEM_INT;
+        }
+        s = recordsDecodeDev(c, st, i.codecs, i.n_codecs, asInt, i.n_elems, g.nRowsTile, g.nColsTile, n, dBlob, blobBytes, dStarts, nullptr,
+                             i.checksum_enabled, b.indices, dPool, b.slotStatus, dEnds);
+        if (s != GF_OK) return s;
+        GF_HIP(gf_launch_file_status(dVerdict, b.slotStatus, n, i.n_elems, st));
+        GF_HIP(hipMemsetAsync(c->dBwTiles.p, 0, planes.total, st));
+    }
+    GfPointsWriteArgs a{};
+    a.g = g;
+    a.look = GfPointsLookup{b.bits, b.prefix, dVerdict, b.slotStatus, (uint32_t)n, (uint32_t)cells};
+    a.nPoints = nPoints, a.rows = dRows, a.cols = dCols, a.pointStatus = dPointStatus;
+    a.list = dList;
+    a.slotOld = c->dBwMeta.at<int32_t>(oldAt), a.stored = c->dBwMeta.at<uint32_t>(storedAt);
+    a.tileIndices = dTileIndices, a.preStatus = c->dBwMeta.at<int32_t>(preAt);
+    a.nElems = i.n_elems;
+    for (int e = 0; e < i.n_elems; e++) {
+        GfPointsWriteElem &d = a.elems[e];
+        d.pool = dPool[e], d.values = dValues[e], d.owner = c->dBwTiles.at<uint32_t>(planeAt[e]);
+        d.type = cut[e].type, d.fillBits = cut[e].fillBits, d.fillFBits = cut[e].fillFBits, d.minBits = cut[e].minBits, d.maxBits = cut[e].maxBits;
+        d.scale = cut[e].scale, d.offset = cut[e].offset;
+    }
+    GF_HIP(gf_launch_points_prepare(a, st));
+    GF_HIP(gf_launch_points_claim(a, st));
+    GF_HIP(gf_launch_points_store(a, st));
+    GF_HIP(gf_launch_points_verdict(a, st));
+    *dPre = a.preStatus;
+    return GF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -404,6 +485,160 @@ gf_status gf_file_interp_points(gf_context *c, const gf_file *f, const uint8_t *
             p.out.zxx = sg.ptr<double>(devP[3]), p.out.zxy = sg.ptr<double>(devP[4]), p.out.zyy = sg.ptr<double>(devP[5]);
             p.out.normal = sg.ptr<double>(normalP), p.out.status = sg.ptr<int32_t>(statusP);
         });
+}
+
+gf_status gf_file_update_points_elems_dev(gf_context *c, const gf_file_update *u, size_t nPoints, const int32_t *dRows, const int32_t *dCols,
+                                          const void *const *dValues, size_t maxTiles, int flags, int64_t timeModified, uint8_t *dImage,
+                                          size_t imageCap, uint64_t *dImageBytes, int32_t *dFileStatus, int32_t *dPointStatus,
+                                          int32_t *dTileIndices, int32_t *dTileStatus, uint8_t *dCodecUsed, size_t *nTouched)
+{
+    if (!c || !u || !dValues || !dImage || ((uintptr_t)dImage & 7) != 0 || !dImageBytes || !dFileStatus || !dPointStatus || !dTileIndices ||
+        !dTileStatus || !nTouched || (nPoints && (!dRows || !dCols))) return GF_ERR_ARG;
+    *nTouched = 0;
+    const GfFileUpdate &h = fileUpdateOf(u);
+    const gf_file_info &i = h.info;
+    int codecs[255];
+    size_t maxRecord;
+    gf_status s = pointsWriteArgs(c, h, dImage, imageCap, true, nPoints, maxTiles, dValues, codecs, maxRecord);
+    if (s != GF_OK) return s;
+    if (!deviceList(i.codecs, i.n_codecs, i.elems, i.n_elems)) return GF_ERR_UNSUPPORTED;
+    if (nPoints == 0) return GF_OK;                                               // (nothing is enqueued: the image is not even closed anew)
+    const GfPointsGrid g = gridOf(i);
+    if (maxTiles > (size_t)g.nTilesGrid) maxTiles = (size_t)g.nTilesGrid;         // (no set of points touches more)
+    GF_CTX_LOCK(c);
+    GF_HIP(hipSetDevice(c->device));
+    const hipStream_t st = c->stream;
+    PointsBuf b;
+    if ((s = pointsBuf(c, g, i.n_elems, maxTiles, true, b)) != GF_OK) return s;
+    if ((s = c->hRecCounts.ensure(256 * 4)) != GF_OK) return s;
+    PointsWhat w{};
+    w.windows = false, w.nPoints = nPoints, w.rowsI = dRows, w.colsI = dCols;
+    if ((s = pointsMarkRank(st, g, w, b, maxTiles)) != GF_OK) return s;
+    // the first synchronisation: the host sizes pool, planes and the records' room by the count
+    GF_HIP(hipMemcpyAsync(c->hRecCounts.p, b.count, 4, hipMemcpyDeviceToHost, st));
+    GF_HIP(hipStreamSynchronize(st));
+    const size_t n = *(const uint32_t *)c->hRecCounts.p;
+    *nTouched = n;
+    if (n > maxTiles) return GF_ERR_CAPACITY;                                     // (no output and no byte of the image has been written)
+    GfFileLocateArgs a{};
+    a.image = dImage, a.imageBytes = h.imageBytes, a.dir = gfFileDirOf(i);
+    a.starts = b.starts, a.ends = b.ends, a.verdict = b.verdict;
+    a.tileList = b.list, a.nList = (uint32_t)n;
+    GF_HIP(gf_launch_file_locate(a, st));
+    GF_HIP(gf_launch_points_heads(GfPointsHeadsArgs{dImage, h.imageBytes, b.starts, b.ends, b.verdict, (uint32_t)n}, st));
+    Carve kb;
+    const size_t blobAt = kb.add(n * maxRecord), offsetsAt = kb.add((n + 1) * 8);
+    if ((s = c->dFileUpdateBlob.ensure(kb)) != GF_OK) return s;
+    uint8_t *dBlob = c->dFileUpdateBlob.at<uint8_t>(blobAt);
+    uint64_t *dOffsets = c->dFileUpdateBlob.at<uint64_t>(offsetsAt);
+    void *dPool[GF_MAX_ELEMS];
+    const int32_t *dPre = nullptr;
+    // (the second synchronisation is the records' pipeline's, inside)
+    s = pointsWriteCells(c, st, i, g, n, dImage, (size_t)h.imageBytes, b.starts, b.ends, b.verdict, b, b.list, nPoints, dRows, dCols, dValues,
+                         dPointStatus, dTileIndices, dPool, &dPre);
+    if (s != GF_OK) return s;
+    if (n) {
+        s = recordsEncodeDev(c, st, i.codecs, i.n_codecs, i.elems, i.n_elems, g.nRowsTile, g.nColsTile, n, dTileIndices, (const void *const *)dPool,
+                             i.checksum_enabled, dBlob, n * maxRecord, dOffsets, dCodecUsed, dTileStatus, dPre);
+        if (s != GF_OK) return s;
+    } else GF_HIP(hipMemsetAsync(dOffsets, 0, 8, st));                            // (every point lies outside the grid: the file is closed anew)
+    // the allocator takes the records in ascending tile index; a tile with a negative status stays, record and entry
+    return updateRecordsDev(c, h, dImage, imageCap, dBlob, dOffsets, dTileIndices, dTileStatus, dTileStatus, n, n * maxRecord, timeModified, flags, 0,
+                            dImageBytes, dFileStatus);
+}
+
+gf_status gf_file_update_points_elems(gf_context *c, const gf_file_update *u, size_t nPoints, const int32_t *rows, const int32_t *cols,
+                                      const void *const *values, size_t maxTiles, int flags, int64_t timeModified, uint8_t *image, size_t imageCap,
+                                      uint64_t *imageBytes, int32_t *pointStatus, int32_t *tileIndices, int32_t *tileStatus, uint8_t *codecUsed,
+                                      size_t *nTouched)
+{
+    if (!c || !u || !values || !image || !imageBytes || !pointStatus || !tileIndices || !tileStatus || !nTouched || (nPoints && (!rows || !cols)))
+        return GF_ERR_ARG;
+    *nTouched = 0;
+    const GfFileUpdate &h = fileUpdateOf(u);
+    const gf_file_info &i = h.info;
+    *imageBytes = h.imageBytes;
+    int codecs[255];
+    size_t maxRecord;
+    gf_status s = pointsWriteArgs(c, h, image, imageCap, false, nPoints, maxTiles, values, codecs, maxRecord);
+    if (s != GF_OK) return s;
+    if (nPoints == 0) return GF_OK;                                               // (the image is not even closed anew)
+    const GfPointsGrid g = gridOf(i);
+    const std::vector<uint32_t> bits = cellsBits(g, nPoints, rows, cols);
+    const size_t n = listBits(bits, nullptr, 0);
+    *nTouched = n;
+    if (n > maxTiles) return GF_ERR_CAPACITY;
+    if (n == 0) {                                                                 // every point lies outside the grid: the file is closed anew
+        for (size_t k = 0; k < (size_t)i.n_elems * nPoints; k++) pointStatus[k] = GF_ERR_ARG;
+        const uint64_t none = 0;
+        return gfFileUpdateAssemble(h, image, imageCap, nullptr, &none, nullptr, nullptr, 0, timeModified, flags, imageBytes);
+    }
+    // the touched tiles' old records, looked up and judged by their heads as gf_file_update_block_elems judges them, staged end to end
+    std::vector<int32_t> list(n), verdict(n);
+    listBits(bits, list.data(), n);
+    std::vector<uint64_t> from, starts(n, 0), ends(n, 0);
+    uint64_t oldBytes = 0;
+    const GfFileDir dir = gfFileDirOf(i);
+    for (size_t k = 0; k < n; k++) {
+        uint64_t pos, size = 0;
+        uint32_t sizeWord;
+        int32_t v = gfFileLocate(dir, image, h.imageBytes, list[k], &pos, &sizeWord);
+        if (v == GF_OK && pos != 0) {
+            v = gfFsRecordHead(h.imageBytes, i.content_pos, pos, GF_FILE_REC_TILE, 24, &size, GfLoadLe{image});
+            if (v == GF_OK) {
+                v = GF_FILE_LOCATED;
+                from.push_back(pos - 8);
+                starts[k] = oldBytes, ends[k] = oldBytes + size;
+                oldBytes += size;
+            }
+        }
+        verdict[k] = v;
+    }
+    std::vector<uint8_t> old((size_t)oldBytes + 16);
+    for (size_t k = 0, r = 0; k < n; k++)
+        if (verdict[k] == GF_FILE_LOCATED) memcpy(old.data() + starts[k], image + from[r++], (size_t)(ends[k] - starts[k]));
+    const bool onDevice = deviceList(i.codecs, i.n_codecs, i.elems, i.n_elems);
+    const size_t maxBlob = n * maxRecord;
+    std::vector<uint8_t> blob(maxBlob + 16);
+    std::vector<uint64_t> offsets(n + 1, 0);
+    GF_CTX_LOCK(c);
+    GF_HIP(hipSetDevice(c->device));
+    const hipStream_t st = c->stream;
+    PointsBuf b;
+    if ((s = pointsBuf(c, g, i.n_elems, n, false, b)) != GF_OK) return s;
+    // staging: the old records | starts | ends | verdicts | the list | rows | cols | the values of element 0, 1, ... | the points'
+    // statuses | tile indices, and for a device list the records at their largest | offsets | the tiles' statuses | codec used
+    HostStage sg(c);
+    const int oldP = sg.in(old.data(), (size_t)oldBytes, 32), startsP = sg.in(starts.data(), n * 8), endsP = sg.in(ends.data(), n * 8);
+    const int verdictP = sg.in(verdict.data(), n * 4), listP = sg.in(list.data(), n * 4);
+    const int rowsP = sg.in(rows, nPoints * 4), colsP = sg.in(cols, nPoints * 4);
+    int valueP[GF_MAX_ELEMS];
+    stageElems(sg, STAGE_IN, i.elems, i.n_elems, nPoints, values, valueP);
+    const int pointP = sg.out(pointStatus, (size_t)i.n_elems * nPoints * 4);
+    HostWriteParts parts;
+    parts.indices = sg.out(tileIndices, n * 4);
+    parts.blob = sg.held(blob.data(), onDevice ? maxBlob : 0), parts.offsets = sg.out(onDevice ? offsets.data() : nullptr, (n + 1) * 8);
+    parts.status = sg.out(onDevice ? tileStatus : nullptr, n * 4), parts.used = sg.out(onDevice ? codecUsed : nullptr, (size_t)i.n_elems * n);
+    if ((s = sg.begin()) != GF_OK) return s;
+    // the slots of the tiles on the device come from the device's own bitmap of the staged points
+    PointsWhat w{};
+    w.windows = false, w.nPoints = nPoints, w.rowsI = sg.ptr<int32_t>(rowsP), w.colsI = sg.ptr<int32_t>(colsP);
+    if ((s = pointsMarkRank(st, g, w, b, 0)) != GF_OK) return s;
+    void *dValues[GF_MAX_ELEMS], *dPool[GF_MAX_ELEMS];
+    sg.ptrs(valueP, i.n_elems, dValues);
+    const int32_t *dPre = nullptr;
+    s = pointsWriteCells(c, st, i, g, n, sg.ptr<uint8_t>(oldP), (size_t)oldBytes, sg.ptr<uint64_t>(startsP), sg.ptr<uint64_t>(endsP),
+                         sg.ptr<int32_t>(verdictP), b, sg.ptr<int32_t>(listP), nPoints, w.rowsI, w.colsI, dValues, sg.ptr<int32_t>(pointP),
+                         sg.ptr<int32_t>(parts.indices), dPool, &dPre);
+    if (s != GF_OK) return s;
+    s = hostWriteTail(c, sg, parts, onDevice, i.codecs, i.n_codecs, i.elems, i.n_elems, g.nRowsTile, g.nColsTile, n, (const void *const *)dPool, dPre,
+                      i.checksum_enabled, maxBlob, blob.data(), maxBlob, offsets.data(), tileIndices, codecUsed, tileStatus);
+    if (s == GF_ERR_ARG || s == GF_ERR_UNSUPPORTED || s == GF_ERR_HIP || s == GF_ERR_CAPACITY) return s;   // (not a tile's verdict)
+    gf_status first = GF_OK;
+    for (size_t k = 0; k < n && first == GF_OK; k++)
+        if (tileStatus[k] < 0) first = (gf_status)tileStatus[k];
+    s = gfFileUpdateAssemble(h, image, imageCap, blob.data(), offsets.data(), tileIndices, tileStatus, n, timeModified, flags, imageBytes);
+    return s != GF_OK ? s : first;                                // (a refusal of the whole update comes before a tile's status)
 }
 
 }  // extern "C"

@@ -57,6 +57,20 @@ gf_status gf_file_update_plan(const gf_file_update *u, const gf_rect *rect, uint
     return GF_OK;
 }
 
+gf_status gf_file_update_plan_tiles(const gf_file_update *u, size_t nTiles, uint64_t *maxImageBytes, uint64_t *freeListCapacity)
+{
+    if (!u) return GF_ERR_ARG;
+    const gf_file_info &i = u->u.info;
+    if ((uint64_t)nTiles > (uint64_t)gfTilesOfGrid(i.grid).count()) return GF_ERR_ARG;   // (no update writes more tiles than the grid has)
+    GfBlockGeom g{};
+    g.nRowsTile = i.grid.n_rows_tile, g.nColsTile = i.grid.n_cols_tile;
+    size_t maxRecord;
+    const gf_status s = fileMaxRecord(i.elems, i.n_elems, g, maxRecord);
+    if (s != GF_OK) return s;
+    gfFileUpdatePlan(u->u, (uint64_t)nTiles, maxRecord, maxImageBytes, freeListCapacity);
+    return GF_OK;
+}
+
 gf_status gf_file_update_assemble(const gf_file_update *u, uint8_t *image, size_t imageCap, const uint8_t *blob, const uint64_t *offsets,
                                   const int32_t *tileIndices, const int32_t *status, size_t nRecords, int64_t timeModified, int flags,
                                   uint64_t *imageBytes)
@@ -66,9 +80,13 @@ gf_status gf_file_update_assemble(const gf_file_update *u, uint8_t *image, size_
     return gfFileUpdateAssemble(u->u, image, imageCap, blob, offsets, tileIndices, status, nRecords, timeModified, flags, imageBytes);
 }
 
+}  // extern "C"
+
+const GfFileUpdate &fileUpdateOf(const gf_file_update *u) { return u->u; }
+
 // the records form behind its null checks (the caller holds the context's lock).  dTileStatus: null, or the block form's statuses,
 // into which a refused old record puts its tile's verdict
-static gf_status updateRecordsDev(gf_context *c, const GfFileUpdate &h, uint8_t *dImage, size_t imageCap, const uint8_t *dBlob, const uint64_t *dOffsets,
+gf_status updateRecordsDev(gf_context *c, const GfFileUpdate &h, uint8_t *dImage, size_t imageCap, const uint8_t *dBlob, const uint64_t *dOffsets,
                                   const int32_t *dTileIndices, const int32_t *dStatus, int32_t *dTileStatus, size_t nRecords, size_t blobBytes,
                                   int64_t timeModified, int flags, size_t listCapacity, uint64_t *dImageBytes, int32_t *dFileStatus)
 {
@@ -115,6 +133,8 @@ static gf_status updateRecordsDev(gf_context *c, const GfFileUpdate &h, uint8_t 
     GF_HIP(gf_launch_file_update(a, st));
     return GF_OK;
 }
+
+extern "C" {
 
 gf_status gf_file_update_records_dev(gf_context *c, const gf_file_update *u, uint8_t *dImage, size_t imageCap, const uint8_t *dBlob,
                                      const uint64_t *dOffsets, const int32_t *dTileIndices, const int32_t *dStatus, size_t nRecords,

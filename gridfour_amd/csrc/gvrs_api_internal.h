@@ -146,7 +146,9 @@ struct gf_context {
                                                 // the gather's element table and the records' tile indices, the slot table of the block's tiles
     DevBuf dRecMeta{this}, dRecSub{this}, dRecTmp{this};          // records / mixed packings in device memory (gvrs_api_records_dev.hip): per-record framing
                                                 // results, the partition by codec, decoded tiles on their way to their place
-    DevBuf dBwTiles{this}, dBwMeta{this};       // a block written (gvrs_api_blocks_write.hip): the elements' cut tiles, the tiles' flags and pre-status
+    DevBuf dBwTiles{this}, dBwMeta{this};       // a block written (gvrs_api_blocks_write.hip): the elements' cut tiles, the tiles' flags and pre-status;
+                                                // a file written at points (gvrs_api_file_points.hip): the elements' owner planes, the slots' old
+                                                // status, stored flag and pre-status (its pool lies in dBlockTmp, its records in dFileUpdateBlob)
     DevBuf dEncSlots{this}, dEncMeta{this}, dEncWide{this};       // records written in device memory (gvrs_api_records_enc.hip): the codecs' candidate slots,
                                                 // their lengths / statuses and the records' layout, SHORT cells widened for the codecs
     DevBuf dDsBlocks{this};                     // downsampling (gvrs_api_downsample.hip): the record forms' full-resolution blocks
@@ -344,6 +346,22 @@ gf_status blockWriteDev(gf_context *c, void *stream, const int *codecs, int nCod
                         const GfBlockCutElem *cut, const void *const *dBlocks, size_t nOld, const uint8_t *dOldBlob, size_t oldBlobBytes,
                         const uint64_t *dOldOffsets, int verifyOldChecksum, int checksumEnabled, uint8_t *dBlob, size_t blobCap, uint64_t *dOffsets,
                         int32_t *dTileIndices, uint8_t *dCodecUsed, int32_t *dStatus, const uint64_t *dOldEnds = nullptr);
+// ... the cut's description of every element (block, tiles and old tiles are left null); ranges == null: the default ranges
+gf_status cutElems(const gf_elem_spec *elems, const gf_elem_range *ranges, int nElems, GfBlockCutElem *t);
+// ... and the tail of a host form that writes records: the nOut tiles dTiles of the device, with the pre-status dPre, to records
+// in HOST memory.  sg is the call's begun stage and holds the parts named here (indices: out; blob: held, maxBlob bytes; offsets,
+// status, used: out, declared with their host places for a device list and with null otherwise); the tail ends the stage.  A
+// device list goes through recordsEncodeDev, any other brings tiles and verdicts back and goes through recordsEncodeHost.
+struct HostWriteParts { int indices, blob, offsets, status, used; };
+gf_status hostWriteTail(gf_context *c, HostStage &sg, const HostWriteParts &p, bool onDevice, const int *codecs, int nCodecs, const gf_elem_spec *elems,
+                        int nElems, int nRowsTile, int nColsTile, size_t nOut, const void *const *dTiles, const int32_t *dPre, int checksumEnabled,
+                        size_t maxBlob, uint8_t *blob, size_t blobCap, uint64_t *offsets, int32_t *tileIndices, uint8_t *codecUsed, int32_t *status);
+// gvrs_api_file_update.hip: the handle's content, and the records form behind its null checks (the caller holds the lock)
+struct GfFileUpdate;
+const GfFileUpdate &fileUpdateOf(const gf_file_update *u);
+gf_status updateRecordsDev(gf_context *c, const GfFileUpdate &h, uint8_t *dImage, size_t imageCap, const uint8_t *dBlob, const uint64_t *dOffsets,
+                           const int32_t *dTileIndices, const int32_t *dStatus, int32_t *dTileStatus, size_t nRecords, size_t blobBytes,
+                           int64_t timeModified, int flags, size_t listCapacity, uint64_t *dImageBytes, int32_t *dFileStatus);
 // gvrs_api_file.hip: k_file_locate for the rectangle's tiles on a stream (no lock taken): a.starts, a.ends, a.verdict lie in dFileLoc
 gf_status fileLocateDev(gf_context *c, hipStream_t st, const gf_file_info &i, const uint8_t *dImage, size_t imageBytes, const GfBlockGeom &g,
                         uint8_t *dPresent, GfFileLocateArgs &a);

@@ -15,47 +15,13 @@
 #include "gvrs_kernels.h"
 #include "gvrs_common.h"
 #include "gvrs_blocks_common.h"
+#include "gvrs_file_points_store.h"
 
 namespace {
 
-// an element's constants in registers (workgroup-uniform)
-struct BwElem {
-    uint32_t fill;             // the tile's fill cell (SHORT: 16 bits)
-    uint32_t fillF;            // ICF: fill_f's bits
-    uint32_t lo, hi;           // the range: int32, or float bits
-    float scale, offset;
-    bool nanFill;              // FLOAT: the fill is a NaN; ICF: fill_f is
-};
-
-// "this cell is data": TileElement*.hasValidData on the TILE's cell (an ICF's is its code)
-template <int K>
-__device__ __forceinline__ bool bw_valid(uint32_t o, const BwElem &p)
-{
-    if (K == GF_K_ELEM_FLOAT) {
-        const float f = __uint_as_float(o);
-        return p.nanFill ? !(f != f) : f != __uint_as_float(p.fill);         // (the float comparison: -0.0 is the fill 0.0, a NaN is data)
-    }
-    return o != p.fill;
-}
-
-// Float.equals: the bits, any NaN being one value
-__device__ __forceinline__ bool bw_float_equals(uint32_t v, uint32_t fillBits, bool nanFill)
-{
-    const float f = __uint_as_float(v);
-    return v == fillBits || (nanFill && f != f);
-}
-
-// (int) Math.floor((double)((v - offset) * scale) + 0.5): subtraction and product rounded once each in float32, the sum and the floor
-// in double, the cast saturating as Java's does (a NaN: 0)
-__device__ __forceinline__ uint32_t bw_icf_code(float v, float scale, float offset)
-{
-    const float d = __fmul_rn(__fsub_rn(v, offset), scale);
-    const double x = floor((double)d + 0.5);
-    if (x != x) return 0u;
-    if (x >= 2147483647.0) return 0x7fffffffu;
-    if (x <= -2147483648.0) return 0x80000000u;
-    return (uint32_t)(int32_t)x;
-}
+// an element's constants in registers (workgroup-uniform); the cell rule itself -- gf_store_value, gf_store_valid and what they
+// are made of -- is gvrs_file_points_store.h, which the writes at scattered points read too
+typedef GfStoreElem BwElem;
 
 // One cell on its way: OLD, a cell of the old tile, is only looked at; a cell of the block goes through setValue / setIntValue.
 // An out-of-range cell sets GF_BW_FLAG_BOUNDS (the tile gets no record; an ICF's code is then the fill's).
@@ -63,27 +29,8 @@ template <int K, bool OLD>
 __device__ __forceinline__ uint32_t bw_cell(uint32_t v, const BwElem &p, uint32_t &fl)
 {
     uint32_t o = v;
-    if (!OLD) {
-        bool ok;
-        if (K == GF_K_ELEM_INT) {
-            ok = ((int32_t)v >= (int32_t)p.lo && (int32_t)v <= (int32_t)p.hi) || v == p.fill;
-        } else if (K == GF_K_ELEM_SHORT) {
-            const int32_t s = (int32_t)(int16_t)v;
-            ok = (s >= (int32_t)p.lo && s <= (int32_t)p.hi) || v == p.fill;
-        } else {
-            const float f = __uint_as_float(v);
-            const bool inRange = __uint_as_float(p.lo) <= f && f <= __uint_as_float(p.hi);
-            if (K == GF_K_ELEM_FLOAT) {
-                ok = inRange || bw_float_equals(v, p.fill, p.nanFill);
-            } else {
-                const bool isFill = bw_float_equals(v, p.fillF, p.nanFill);
-                ok = isFill || inRange;
-                o = (isFill || !inRange) ? p.fill : bw_icf_code(f, p.scale, p.offset);
-            }
-        }
-        if (!ok) fl |= GF_BW_FLAG_BOUNDS;
-    }
-    if (bw_valid<K>(o, p)) fl |= GF_BW_FLAG_VALID;
+    if (!OLD && !gf_store_value<K>(v, p, o)) fl |= GF_BW_FLAG_BOUNDS;
+    if (gf_store_valid<K>(o, p)) fl |= GF_BW_FLAG_VALID;
     return o;
 }
 
@@ -165,15 +112,7 @@ template <int K>
 __device__ __forceinline__ uint32_t bw_tile(const GfBlockCutElemsArgs &a, const GfBlockCutElem &d, size_t k)
 {
     constexpr uint32_t item = K == GF_K_ELEM_SHORT ? 2u : 4u;
-    BwElem e;
-    e.fill = K == GF_K_ELEM_SHORT ? d.fillBits & 0xffffu : d.fillBits;
-    e.fillF = d.fillFBits;
-    e.lo = d.minBits, e.hi = d.maxBits;
-    e.scale = d.scale, e.offset = d.offset;
-    {
-        const float f = __uint_as_float(K == GF_K_ELEM_ICF ? d.fillFBits : d.fillBits);
-        e.nanFill = f != f;
-    }
+    const BwElem e = gf_store_elem(K, d.fillBits, d.fillFBits, d.minBits, d.maxBits, d.scale, d.offset);
     const uint32_t fillWord = blk_fill_word(d.fillBits, item);
     const int64_t ty = (int64_t)(k / (size_t)a.g.nTileCols), tx = (int64_t)(k - (size_t)ty * (size_t)a.g.nTileCols);
     const int64_t gr0 = (a.g.tileRow0 + ty) * a.g.nRowsTile, gc0 = (a.g.tileCol0 + tx) * a.g.nColsTile;   // the tile's first cell on the grid

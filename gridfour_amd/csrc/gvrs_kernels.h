@@ -646,6 +646,50 @@ struct GfPointsInterpArgs {
 };
 hipError_t gf_launch_points_interp(const GfPointsInterpArgs &a, hipStream_t stream);
 
+// A file image WRITTEN at points (gvrs_file_points_write.hip; driven by gvrs_api_file_points.hip; the cell rule is
+// gvrs_file_points_store.h).  Behind mark, rank and k_file_locate, k_points_heads judges the head of every located record as an
+// update does (gfFsHeadWords: a refused one becomes its slot's verdict and the empty extent); behind the records' pipeline and
+// k_file_status, k_points_prepare folds the elements' statuses into one per slot, clears the slot's "stored" flag and fills the
+// pool slots of the tiles without a record; k_points_claim lets the highest point index whose value passed own a cell
+// (atomicMax into the element's owner plane, pre-zeroed, one word per pool cell); k_points_store lets the owners store, writes
+// the points' statuses and sets the tiles' flags; k_points_verdict writes the touched tiles' indices and the pre-status that the
+// record writer takes.  Every index into pool, planes and flags is slot * cells + indexInTile with slot < nSlots and indexInTile
+// < cells, or slot < nSlots.
+struct GfPointsHeadsArgs {
+    const uint8_t *image;      // 8-byte aligned
+    uint64_t imageBytes;
+    uint64_t *starts, *ends;   // per slot, as k_file_locate left them
+    int32_t *verdict;
+    uint32_t nSlots;
+};
+hipError_t gf_launch_points_heads(const GfPointsHeadsArgs &a, hipStream_t stream);
+struct GfPointsWriteElem {     // an element of the file, in the kernel arguments
+    void *pool;                // decoded tiles in the record writer's type (an ICF's: codes), slot s at pool + s * cells items
+    const void *values;        // per point: int32 (INT), int16 (SHORT), float32 (FLOAT and the VALUES of an ICF)
+    uint32_t *owner;           // one word per pool cell, pre-zeroed: the highest point index + 1 whose value passed
+    int32_t type;              // GF_K_ELEM_*
+    uint32_t fillBits, fillFBits, minBits, maxBits;   // as GfBlockCutElem's
+    float scale, offset;
+};
+struct GfPointsWriteArgs {
+    GfPointsGrid g;
+    GfPointsLookup look;       // slotStatus: the records' pipeline's, with the verdicts put in (k_file_status)
+    size_t nPoints;
+    const int32_t *rows, *cols;
+    int32_t *pointStatus;      // [e * nPoints + i]
+    const int32_t *list;       // the touched tiles, ascending: slot s is tile list[s]
+    int32_t *slotOld;          // per slot: the first element status that is not GF_K_OK (the tile cannot be rewritten), else GF_K_OK
+    uint32_t *stored;          // per slot: != 0 once a point stored a value of any element into the tile
+    int32_t *tileIndices;      // out, per slot
+    int32_t *preStatus;        // out, per slot: what the record writer takes
+    int nElems;
+    GfPointsWriteElem elems[GF_K_MAX_ELEMS];
+};
+hipError_t gf_launch_points_prepare(const GfPointsWriteArgs &a, hipStream_t stream);
+hipError_t gf_launch_points_claim(const GfPointsWriteArgs &a, hipStream_t stream);
+hipError_t gf_launch_points_store(const GfPointsWriteArgs &a, hipStream_t stream);
+hipError_t gf_launch_points_verdict(const GfPointsWriteArgs &a, hipStream_t stream);
+
 // A file image WRITTEN (gvrs_file_write.hip; driven by gvrs_api_file_write.hip): behind the record writer, which has laid the records
 // of the rectangle's tiles into the image from firstRecordPos on and left their offsets, the kernels find the bounding rectangle of
 // the tiles with a record (k_file_dir_rect), write the tile directory (k_file_dir_entries), checksum it in chunks (k_file_dir_crc)

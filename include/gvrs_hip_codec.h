@@ -1586,6 +1586,59 @@ gf_status gf_file_write_block_elems(gf_context *ctx, const gf_file_facts *facts,
  *   stays), gf_block_write_elems merges the old cells of partly covered tiles, then gf_file_update_assemble in row-major order of
  *   the rectangle's tiles.  Cells are checked against the default ranges (the handle does not keep the header's).  Returns the
  *   assembler's status when it refuses the update (GF_ERR_CAPACITY: *image_bytes = the need), else the first negative per-tile status.
+ *   WRITES AT SCATTERED POINTS (gf_file_update_points_elems_dev, gf_file_update_points_elems; gf_file_update_plan_tiles): what
+ *   for i in 0 .. n_points - 1: for e: element[e].writeValue(rows[i], cols[i], values[e][i]) does to a file opened "rw", followed
+ *   by close() (gvrs/GvrsElement.java writeValue / writeValueInt; the tile cache loads, modifies and rewrites only the tiles the
+ *   cells fall in).  d_values is a HOST array of n_elems device pointers, d_values[e] of n_points items: int32 (INT), int16
+ *   (SHORT), float32 (FLOAT) and float32 VALUES for an ICF element, the block write's types.  Only the tiles the points touch are
+ *   decoded and written again; their count comes back in *n_tiles_touched, and max_tiles is the room of d_tile_indices,
+ *   d_tile_status and (n_elems * max_tiles bytes, may be NULL) d_codec_used, which are the block write's outputs over the touched
+ *   tiles in ascending tile index: d_codec_used[e * *n_tiles_touched + s].
+ *   THE CELL RULE is TileElement*.setValue's, under "RANGES" and "ICF, per cell" of gf_block_write_elems_dev, and one piece of
+ *   code with the block write (gvrs_file_points_store.h): the DEFAULT ranges apply (the handle does not keep the header's),
+ *   Float.equals decides whether a value is the fill, an ICF's code is (int)Math.floor((double)((v - offset) * scale) + 0.5) with
+ *   the saturating cast.
+ *   PER POINT AND ELEMENT d_point_status[e * n_points + i], first match: GF_ERR_ARG for every element of a point outside the grid
+ *   (the reference throws), and no tile is touched; the TILE'S status for every element where the point's tile cannot be
+ *   rewritten -- a refused directory entry or record head (judged as an update judges it: type 2, a size >= 24 that is a multiple
+ *   of 8 inside the image), a failed checksum where the file enables them, an element of the old record that did not decode to
+ *   GF_OK: the status of the first such element, as in the block write's merge -- and nothing is stored; GF_ERR_BOUNDS for the
+ *   (e, i) whose value is out of range, alone: nothing is stored for it, the other elements of the point still store (the
+ *   reference throws from that one setValue and the earlier stores stand); else GF_OK.
+ *   DUPLICATES: of several points on one cell the HIGHEST POINT INDEX WHOSE VALUE PASSED wins, per element, as the sequence
+ *   gives it.  The result does not depend on timing: k_points_claim raises an owner word per pool cell to that index with
+ *   atomicMax, and only behind it k_points_store lets the owners write.
+ *   PER TOUCHED TILE d_tile_indices[s], d_tile_status[s], s < *n_tiles_touched, first match: the old record's failure as above
+ *   (the tile stays, record and entry); GF_ERR_BOUNDS where no point stored anything into the tile (the reference sets
+ *   writingRequired only in a successful store, TileElementInt.java:121: the tile is never written and stays; a tile whose stores
+ *   happen to equal the old cells IS rewritten); GF_DECLINED where every element is all fill after the stores (the old record is
+ *   freed and the entry set to 0, as in gf_file_update_assemble); else the record writer's verdict.  A tile the directory names no
+ *   record for is a new tile: fill everywhere (cells beyond the grid's edge included), then the stores.
+ *   THE FILE: the records go to the allocator in ascending tile index under the rules, the all-or-nothing rule, the
+ *   *d_file_status / *d_image_bytes and the deviation for compressed files of gf_file_update_records_dev.  ONE MORE DEVIATION: the
+ *   reference writes tiles in the order in which its cache evicts and flushes them, which depends on the cache's size and the
+ *   access pattern; here the order is ascending tile index.
+ *   More than max_tiles touched tiles: GF_ERR_CAPACITY, *n_tiles_touched holds the count, no status is written and not one byte of
+ *   the image changes.  n_points == 0: GF_OK, *n_tiles_touched = 0, nothing is written and the image is left as it is -- it is
+ *   NOT EVEN CLOSED ANEW (no modification time, no directories; the host form sets *image_bytes to the old size).  Points that all
+ *   lie outside the grid touch no tile and the file IS closed anew.
+ *   gf_file_update_points_elems_dev runs on the context's stream; the codec list must be one the device record writer takes
+ *   (GF_ERR_UNSUPPORTED otherwise, from the arguments alone); old checksums are verified where the file enables them.  It
+ *   SYNCHRONISES TWICE -- the read-back of the touched tiles' count, by which the host sizes the pool, and the decode of the old
+ *   records (the records' pipeline's) -- and is NOT CAPTURE-SAFE.  Order: k_points_mark, k_points_rank, the count, k_file_locate
+ *   over the list, k_points_heads, the records' pipeline into a tile-major pool (an ICF element as codes), k_file_status,
+ *   k_points_prepare (new tiles filled), k_points_claim, k_points_store, k_points_verdict, the record writer from the pool with the
+ *   verdict as its pre-status, the kernels of gf_file_update_records_dev with d_tile_status as the statuses.
+ *   gf_file_update_points_elems: the same through host memory, for any codec list.  The touched tiles are gf_file_cells_tiles's;
+ *   their records are looked up and their heads judged on the host, as gf_file_update_block_elems does, and staged end to end; the
+ *   same device decode and store follow; a device-capable list goes on through the device record writer, any other brings tiles
+ *   and verdicts back and goes through the host encoders; then gf_file_update_assemble's rules.  Its return value follows
+ *   gf_file_update_block_elems: the assembler's status when it refuses the update, else the first negative per-tile status.
+ *   gf_file_update_plan_tiles: gf_file_update_plan for n_tiles touched tiles in place of a rectangle (GF_ERR_ARG: more tiles than
+ *   the grid has).
+ *   GF_ERR_ARG / GF_ERR_UNSUPPORTED before the context or a device is looked at: null pointers (d_codec_used may be NULL), an
+ *   unaligned d_image, image_cap below the old size; GF_CODEC_UNKNOWN in the list, more than 2^27 tiles in the grid, n_points or
+ *   n_elems * max_tiles beyond 0x7fffffff.
  * Not here: adding, changing or removing metadata, versions <= 1.03, the tile cache and its
  * flush order, truncating a file whose last record became free (the reference does not either).                                 */
 typedef struct gf_file_update gf_file_update;
@@ -1606,6 +1659,17 @@ gf_status gf_file_update_block_elems_dev(gf_context *ctx, const gf_file_update *
 gf_status gf_file_update_block_elems(gf_context *ctx, const gf_file_update *u, const gf_rect *rect, const void *const *blocks,
                                      int flags, int64_t time_modified, uint8_t *image, size_t image_cap, uint64_t *image_bytes,
                                      int32_t *tile_indices, int32_t *status, uint8_t *codec_used);
+gf_status gf_file_update_plan_tiles(const gf_file_update *u, size_t n_tiles, uint64_t *max_image_bytes, uint64_t *free_list_capacity);
+gf_status gf_file_update_points_elems_dev(gf_context *ctx, const gf_file_update *u, size_t n_points, const int32_t *d_rows,
+                                          const int32_t *d_cols, const void *const *d_values /* HOST array of n_elems device pointers */,
+                                          size_t max_tiles, int flags, int64_t time_modified, uint8_t *d_image, size_t image_cap,
+                                          uint64_t *d_image_bytes, int32_t *d_file_status, int32_t *d_point_status,
+                                          int32_t *d_tile_indices, int32_t *d_tile_status, uint8_t *d_codec_used /* may be NULL */,
+                                          size_t *n_tiles_touched);
+gf_status gf_file_update_points_elems(gf_context *ctx, const gf_file_update *u, size_t n_points, const int32_t *rows, const int32_t *cols,
+                                      const void *const *values, size_t max_tiles, int flags, int64_t time_modified, uint8_t *image,
+                                      size_t image_cap, uint64_t *image_bytes, int32_t *point_status, int32_t *tile_indices,
+                                      int32_t *tile_status, uint8_t *codec_used /* may be NULL */, size_t *n_tiles_touched);
 
 /* ---- GVRS files INSPECTED: every record walked and checksummed, as the file is laid out ----------------------------------------
  * (gvrs/GvrsInspector.java:213-312 inspectContent, :314-337 testRecordChecksum)
