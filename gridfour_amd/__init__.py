@@ -12,7 +12,7 @@ from .codec import (CodecMasterHip, STANDARD_CODEC_LIST, CodecHuffmanHip, CodecD
                     INT4_NULL_CODE, CODEC_STATS_DTYPE, CANON_STATS_DTYPE, interp_spec, INTERP_VALUE, INTERP_FIRST, INTERP_SECOND, ELEM_TYPES,
                     Palette, palette_records, palette_spec, render_light, PALETTE_RGB, PALETTE_HSV, PALETTE_MAX_RECORDS, RENDER_UNLIMITED, RENDER_Z,
                     IMAGE_RGB, IMAGE_YCOCG, IMAGE_MODELS, CODEC_NONE, CODEC_HUFFMAN, CODEC_DEFLATE, CODEC_CANON_HUFFMAN, CODEC_LSOP12,
-                    CODEC_LSOP08, CODEC_UNKNOWN)
+                    CODEC_LSOP08, CODEC_UNKNOWN, COORDS_GRID, COORDS_FILE, MAP_GEO_TO_GRID, MAP_MODEL_TO_GRID, MAP_GRID_TO_GEO, MAP_GRID_TO_MODEL)
 from .sharding import shard_range, GvrsHipMulti, PinnedArray, TileReadAhead  # noqa: F401
 
 __all__ = ["CodecHuffmanHip", "CodecCanonHuffmanHip", "CodecDeflateHip", "CodecFloatHip", "LsCodecHip", "LsCodec08Hip", "GvrsFileHip", "GvrsFileFacts", "GvrsFileUpdate", "GvrsInspection", "GvrsHipContext", "GvrsHipError", "INT4_NULL_CODE", "lib", "lib_path",

@@ -142,7 +142,15 @@ SIGNATURES = {
                                             C.POINTER(C.c_size_t)]),
     "gf_file_interp_points": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int, C.c_size_t, _vp,
                                         C.POINTER(C.c_size_t)]),
-    "gf_file_write_plan": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gf_file_interp_spec": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "gf_file_map_points": (C.c_int, [_vp, C.c_int, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gf_file_map_points_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gf_file_interp_coords_tiles": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gf_file_interp_coords_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int, C.c_size_t,
+                                            _vp, _vp, C.POINTER(C.c_size_t)]),
+    "gf_file_interp_coords": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int, C.c_size_t,
+                                        _vp, _vp, C.POINTER(C.c_size_t)]),
+    "gf_file_write_plan":(C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gf_file_assemble": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gf_file_write_block_elems_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     "gf_file_write_block_elems": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_uint64), _vp, _vp, _vp]),

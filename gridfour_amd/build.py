@@ -24,7 +24,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgvrs_hip.so")
 LIB_DIAG = os.path.join(LIBDIR, "libgvrs_hip_diag.so")
 SOURCES = ["gvrs_api.hip", "gvrs_api_route.hip", "gvrs_api_host.hip", "gvrs_api_float.hip", "gvrs_api_lsop.hip",
-           "gvrs_api_deflate.hip", "gvrs_api_records.hip", "gvrs_api_records_dev.hip", "gvrs_records.hip", "gvrs_api_records_enc.hip", "gvrs_records_enc.hip", "gvrs_api_blocks.hip", "gvrs_blocks.hip", "gvrs_api_blocks_write.hip", "gvrs_blocks_write.hip", "gvrs_api_interp.hip", "gvrs_interp.hip", "gvrs_api_render.hip", "gvrs_render.hip", "gvrs_api_downsample.hip", "gvrs_downsample.hip", "gvrs_api_tabulate.hip", "gvrs_tabulate.hip", "gvrs_api_image.hip", "gvrs_image.hip", "gvrs_api_file.hip", "gvrs_file.hip", "gvrs_api_file_points.hip", "gvrs_file_points.hip", "gvrs_file_points_write.hip", "gvrs_api_file_write.hip", "gvrs_file_write.hip", "gvrs_api_file_update.hip", "gvrs_file_update.hip", "gvrs_api_file_inspect.hip", "gvrs_file_inspect.hip", "gvrs_api_analyze.hip", "gvrs_multi.hip", "gvrs_encode.hip",
+           "gvrs_api_deflate.hip", "gvrs_api_records.hip", "gvrs_api_records_dev.hip", "gvrs_records.hip", "gvrs_api_records_enc.hip", "gvrs_records_enc.hip", "gvrs_api_blocks.hip", "gvrs_blocks.hip", "gvrs_api_blocks_write.hip", "gvrs_blocks_write.hip", "gvrs_api_interp.hip", "gvrs_interp.hip", "gvrs_api_render.hip", "gvrs_render.hip", "gvrs_api_downsample.hip", "gvrs_downsample.hip", "gvrs_api_tabulate.hip", "gvrs_tabulate.hip", "gvrs_api_image.hip", "gvrs_image.hip", "gvrs_api_file.hip", "gvrs_file.hip", "gvrs_api_file_points.hip", "gvrs_file_points.hip", "gvrs_file_points_write.hip", "gvrs_api_coords.hip", "gvrs_coords.hip","gvrs_api_file_write.hip", "gvrs_file_write.hip", "gvrs_api_file_update.hip", "gvrs_file_update.hip", "gvrs_api_file_inspect.hip", "gvrs_file_inspect.hip", "gvrs_api_analyze.hip", "gvrs_multi.hip", "gvrs_encode.hip",
            "gvrs_decode.hip", "gvrs_aux.hip", "gvrs_float.hip", "gvrs_canon_encode.hip", "gvrs_canon_decode.hip", "gvrs_lsop.hip",
            "gvrs_lsop_decode.hip", "gvrs_lsop8.hip", "gvrs_inflate.hip", "gvrs_readahead.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17", "-fno-gpu-rdc",

@@ -89,6 +89,8 @@ _INTERP_SPEC = np.dtype([("n_rows_grid", np.int32), ("n_cols_grid", np.int32), (
                          ("fill_i", np.int32), ("wrap", np.int32), ("target", np.int32), ("row_spacing", np.float64),
                          ("col_spacing", np.float64), ("row_fringe0", np.float64), ("row_fringe1", np.float64),
                          ("col_fringe0", np.float64), ("col_fringe1", np.float64)], align=True)                      # gf_interp_spec
+COORDS_GRID, COORDS_FILE = 0, 1                                          # GF_COORDS_*
+MAP_GEO_TO_GRID, MAP_MODEL_TO_GRID, MAP_GRID_TO_GEO, MAP_GRID_TO_MODEL = 0, 1, 2, 3   # GF_MAP_*
 _INTERP_OUT = np.dtype([(k, np.uint64) for k in ("z", "zx", "zy", "zxx", "zxy", "zyy", "normal", "status")])        # gf_interp_out
 _INTERP_LATTICE = np.dtype([("row0", np.float64), ("col0", np.float64), ("row_step", np.float64), ("col_step", np.float64),
                             ("n_rows", np.int64), ("n_cols", np.int64)])                                            # gf_interp_lattice
@@ -259,8 +261,9 @@ def interp_spec(n_rows_grid, n_cols_grid, block=None, elem_type="float", fill_i=
     """A gf_interp_spec: the raster's size, the rectangle block = (row0, col0, n_rows, n_cols) of it that the block holds (None:
     all of it), the element ("int", "short", "float", "icf" or GF_ELEM_*; fill_i: the cell of an int / short element that reads as
     NaN), wrap (0; 1 the longitudes wrap; 2 they wrap and bracket), the target and the spacings dv, du of the derivatives.
-    The default fringe is (-0.5, n - 0.5) per axis: the reference widens it by 4 ulp of the MODEL coordinates at the raster's
-    edge (GvrsFileSpecification.java:437-440), which the library does not know -- a caller that has them passes the fringes."""
+    The default fringe is (-0.5, n - 0.5) per axis: the reference widens it by 4 ulp of the grid's size, (double) n, on either
+    side (GvrsFileSpecification.java:435-440) -- GvrsFileHip.coords_spec() gives those fringes, with wrap and the spacings, for
+    a file; a caller that works without a file passes the fringes."""
     s = np.zeros(1, _INTERP_SPEC)
     s["n_rows_grid"], s["n_cols_grid"] = n_rows_grid, n_cols_grid
     s["block"] = (0, 0, n_rows_grid, n_cols_grid) if block is None else block
@@ -1918,7 +1921,8 @@ class GvrsFileHip:
     """org.gridfour.gvrs.GvrsFile(file, "r") with GvrsElement.readBlock for all elements: a version 1.04 file opened from its path
     or its bytes (gf_file_open: the header record and the tile directory's prefix, parsed on the host), blocks read from the file
     image by gf_file_read_block_elems[_dev], cells and interpolated values at scattered points by gf_file_read_points_elems[_dev] and
-    gf_file_interp_points[_dev] (only the tiles the points touch are decoded); and, as static methods, new file images written: assemble (tile records in, host
+    gf_file_interp_points[_dev] (only the tiles the points touch are decoded), the same at longitude / latitude or model x / y by
+    map_points[_dev], read_coords and interp_coords[_dev]; and, as static methods, new file images written: assemble (tile records in, host
     memory), write_image (blocks in device memory in, the image out) and write_image_host; an image updated in place by
     update_image[_host] (a rectangle) and update_points[_host] (scattered cells: only the touched tiles are rewritten).  .info is the gf_file_info as a dict, with the elements' names, the codec ids and the
     product label; .elems are the elements as the record calls of CodecMasterHip take them."""
@@ -2123,6 +2127,125 @@ class GvrsFileHip:
                                          None if cs is None else _ptr(cs), int(bool(verify_checksums)), max_tiles, _ptr(o), C.byref(touched))
         self._points_done("gf_file_interp_points", st, return_code)
         return (res, touched.value) + ((st,) if return_code else ())
+
+    # ---- queries at coordinates (gf_file_interp_spec, gf_file_map_points[_dev], gf_file_interp_coords_tiles, gf_file_interp_coords[_dev]) ----
+    def coords_spec(self, elem=0, target=INTERP_VALUE):
+        """gf_file_interp_spec: the gf_interp_spec the reference's interpolator works with on this file, every field from the file:
+        wrap (checkGeographicCoverage), row_spacing = dv, col_spacing = du and the four fringes."""
+        s = np.zeros(1, _INTERP_SPEC)
+        _call("gf_file_interp_spec", self._h, int(elem), int(target), _ptr(s))
+        return s
+
+    @staticmethod
+    def _ab(a, b):
+        a, b = np.ascontiguousarray(a, np.float64).ravel(), np.ascontiguousarray(b, np.float64).ravel()
+        assert a.size == b.size
+        return a, b
+
+    def map_points(self, kind, a, b):
+        """gf_file_map_points (host arithmetic).  To-grid kinds (MAP_GEO_TO_GRID, MAP_MODEL_TO_GRID): (a, b) = (x, y), x the longitude
+        and y the latitude -> dict(row, col, irow, icol, col_spacing, status).  From-grid kinds: (a, b) = (row, col) -> dict(x, y)."""
+        a, b = self._ab(a, b)
+        n = a.size
+        oa, ob = (np.full(n, 0x7f, np.uint8).repeat(8).view(np.float64) for _ in range(2))
+        if kind >= MAP_GRID_TO_GEO:
+            _call("gf_file_map_points", self._h, int(kind), n, _ptr(a), _ptr(b), _ptr(oa), _ptr(ob), None, None, None, None)
+            return {"x": oa, "y": ob}
+        ir, ic, st = (np.full(n, 0x7f7f7f7f, np.int32) for _ in range(3))
+        cs = np.full(n, 0x7f, np.uint8).repeat(8).view(np.float64)
+        _call("gf_file_map_points", self._h, int(kind), n, _ptr(a), _ptr(b), _ptr(oa), _ptr(ob), _ptr(ir), _ptr(ic), _ptr(cs), _ptr(st))
+        return {"row": oa, "col": ob, "irow": ir, "icol": ic, "col_spacing": cs, "status": st}
+
+    def map_points_dev(self, ctx, kind, a, b):
+        """The same through gf_file_map_points_dev (k_coords_map): the arrays are uploaded here, the call only enqueues."""
+        a, b = self._ab(a, b)
+        n = a.size
+        to_grid = kind < MAP_GRID_TO_GEO
+        with _DeviceScope(ctx) as s:
+            d_a, d_b = s.upload(a, slack=16), s.upload(b, slack=16)
+            d_oa, d_ob = s.alloc(n * 8 + 16, fill=0x7f), s.alloc(n * 8 + 16, fill=0x7f)
+            d_ir, d_ic, d_st = ((s.alloc(n * 4 + 16, fill=0x7f) for _ in range(3)) if to_grid else (None, None, None))
+            d_cs = s.alloc(n * 8 + 16, fill=0x7f) if to_grid else None
+            s.run("gf_file_map_points_dev", ctx.handle, self._h, int(kind), n, d_a.ptr, d_b.ptr, d_oa.ptr, d_ob.ptr,
+                  *(x.ptr if x is not None else None for x in (d_ir, d_ic, d_cs, d_st)))
+            ctx.synchronize()
+            oa, ob = d_oa.download(np.float64, n), d_ob.download(np.float64, n)
+            if not to_grid:
+                return {"x": oa, "y": ob}
+            return {"row": oa, "col": ob, "irow": d_ir.download(np.int32, n), "icol": d_ic.download(np.int32, n),
+                    "col_spacing": d_cs.download(np.float64, n), "status": d_st.download(np.int32, n)}
+
+    def interp_coords_tiles(self, kind, spec, a, b):
+        """gf_file_interp_coords_tiles: the distinct tiles the windows of the points touch, ascending; the points given as kind says
+        (COORDS_GRID: rows, columns; COORDS_FILE: x, y).  A point the latitude check refuses touches none."""
+        a, b = self._ab(a, b)
+        return self._touched("gf_file_interp_coords_tiles", (self._h, int(kind), _ptr(spec)), a, b)
+
+    def interp_coords_dev(self, ctx, elem, kind, spec, a, b, col_spacing=None, verify_checksums=True, image=None, max_tiles=None,
+                          return_code=False):
+        """gf_file_interp_coords_dev: interp_points_dev for points given as kind says, mapped inside the kernels; spec is normally
+        coords_spec().  col_spacing None: the file's column-spacing rule.  Returns (the dict interp_points_dev returns plus
+        col_spacing_used, the touched tiles' count) and with return_code the call's status."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        a, b = self._ab(a, b)
+        n, target = a.size, int(spec["target"][0])
+        cs = None if col_spacing is None else np.ascontiguousarray(col_spacing, np.float64).ravel()
+        assert cs is None or cs.size == n
+        max_tiles = self.interp_coords_tiles(kind, spec, a, b).size if max_tiles is None else int(max_tiles)
+        sizes = {k: n * 8 for k in self._interp_names(target)}
+        if target >= INTERP_FIRST:
+            sizes["normal"] = n * 24
+        sizes["status"] = n * 4
+        touched = C.c_size_t()
+        with _DeviceScope(ctx) as s:
+            d_image = s.upload(image, slack=32, fill=0)
+            d_a, d_b = s.upload(a, slack=16), s.upload(b, slack=16)
+            d_cs = None if cs is None else s.upload(cs, slack=16)
+            d_out = {k: s.alloc(v + 16, fill=0x7f) for k, v in sizes.items()}
+            d_used = s.alloc(n * 8 + 16, fill=0x7f)
+            o = _out_struct(_INTERP_OUT, {k: v.ptr for k, v in d_out.items()})
+            st = lib().gf_file_interp_coords_dev(ctx.handle, self._h, d_image.ptr, image.size, int(elem), int(kind), _ptr(spec), n, d_a.ptr,
+                                                 d_b.ptr, None if d_cs is None else d_cs.ptr, int(bool(verify_checksums)), max_tiles, _ptr(o),
+                                                 d_used.ptr, C.byref(touched))
+            self._points_done("gf_file_interp_coords_dev", st, return_code)
+            ctx.synchronize()
+            res = {k: d_out[k].download(np.int32 if k == "status" else np.float64, sizes[k] // (4 if k == "status" else 8)) for k in sizes}
+            if "normal" in res:
+                res["normal"] = res["normal"].reshape(n, 3)
+            res["col_spacing_used"] = d_used.download(np.float64, n)
+            return (res, touched.value) + ((st,) if return_code else ())
+
+    def interp_coords(self, ctx, elem, kind, spec, a, b, col_spacing=None, verify_checksums=True, image=None, max_tiles=None, return_code=False):
+        """The same through gf_file_interp_coords, the host-memory form."""
+        image = self.image if image is None else np.frombuffer(bytes(image), np.uint8)
+        a, b = self._ab(a, b)
+        n, target = a.size, int(spec["target"][0])
+        cs = None if col_spacing is None else np.ascontiguousarray(col_spacing, np.float64).ravel()
+        assert cs is None or cs.size == n
+        max_tiles = self.interp_coords_tiles(kind, spec, a, b).size if max_tiles is None else int(max_tiles)
+        res = {k: np.full(n, 0x7f, np.uint8).repeat(8).view(np.float64) for k in self._interp_names(target)}
+        if target >= INTERP_FIRST:
+            res["normal"] = np.full(n * 3, 0x7f, np.uint8).repeat(8).view(np.float64).reshape(n, 3)
+        res["status"] = np.full(n, 0x7f7f7f7f, np.int32)
+        o = _out_struct(_INTERP_OUT, {k: v.ctypes.data for k, v in res.items()})
+        res["col_spacing_used"] = np.full(n, 0x7f, np.uint8).repeat(8).view(np.float64)
+        touched = C.c_size_t()
+        st = lib().gf_file_interp_coords(ctx.handle, self._h, _ptr(image), image.size, int(elem), int(kind), _ptr(spec), n, _ptr(a), _ptr(b),
+                                         None if cs is None else _ptr(cs), int(bool(verify_checksums)), max_tiles, _ptr(o),
+                                         _ptr(res["col_spacing_used"]), C.byref(touched))
+        self._points_done("gf_file_interp_coords", st, return_code)
+        return (res, touched.value) + ((st,) if return_code else ())
+
+    def read_coords(self, ctx, x, y, verify_checksums=True, image=None):
+        """GvrsElement.readValue(GridPoint) at coordinates (x, y) as z() reads them: map_points (MAP_GEO_TO_GRID for a geographic
+        file, MAP_MODEL_TO_GRID otherwise), then read_points at the GridPoint's integer row and column.  Returns ([values [n] per
+        element], the cells' status [n_elems, n], the mapping's status [n]); a point the mapping refuses, or whose GridPoint lies
+        outside the grid, carries ERR_ARG in the cells' status and the fill."""
+        kind = MAP_GEO_TO_GRID if self.info["coordinate_system"] == 2 else MAP_MODEL_TO_GRID
+        m = self.map_points(kind, x, y)
+        irow = np.where(m["status"] == 0, m["irow"], -1).astype(np.int32)        # (a refused point: outside the grid)
+        values, status, _ = self.read_points(ctx, irow, m["icol"], verify_checksums, image)
+        return values, status, m["status"]
 
     # ---- files written (gf_file_assemble, gf_file_write_block_elems[_dev]) ----
     @staticmethod

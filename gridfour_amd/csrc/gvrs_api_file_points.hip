@@ -51,6 +51,20 @@ std::vector<uint32_t> windowsBits(const GfPointsGrid &g, const GfInterpGeom &ig,
     return bits;
 }
 
+// ... of points given as kind says (gf_coords_query, the function the kernels call): a refused point touches no tile
+std::vector<uint32_t> coordsBits(const GfPointsGrid &g, const GfInterpGeom &ig, const GfCoords &co, int kind, size_t n, const double *a, const double *b)
+{
+    std::vector<uint32_t> bits(gf_points_words(g.nTilesGrid), 0u);
+    for (size_t t = 0; t < n; t++) {
+        GfCoordsQuery q;
+        GfInterpWindow w;
+        if (gf_coords_query(co, kind, a[t], b[t], 0.0, false, q) != GF_IP_OK || gf_interp_window(ig, q.row, q.col, w) != GF_IP_OK) continue;
+        const GfWindowTiles wt = gf_points_window_tiles(g, w.row0, w.col0, w.n1);
+        for (int32_t k = 0, nk = wt.count(); k < nk; k++) setBit(bits, wt.at(k));
+    }
+    return bits;
+}
+
 // the bitmap's tiles in ascending order: at most cap of them into tiles, all of them counted
 size_t listBits(const std::vector<uint32_t> &bits, int32_t *tiles, size_t cap)
 {
@@ -101,6 +115,13 @@ gf_status pointsFileArgs(const gf_context *c, const gf_file_info &i, const uint8
     return GF_OK;
 }
 
+// the answer of the forms at coordinates to a NULL context: what can be judged of the image without one comes first
+gf_status pointsNoContext(const gf_file_info &i, const uint8_t *image, size_t imageBytes, bool onDevice)
+{
+    if ((onDevice && ((uintptr_t)image & 7) != 0) || imageBytes < i.content_pos) return GF_ERR_ARG;
+    return noContext();
+}
+
 gf_status interpOutArgs(const gf_interp_spec *spec, const gf_interp_out *out)
 {
     if (!spec || !out || !out->z) return GF_ERR_ARG;
@@ -144,6 +165,10 @@ struct PointsWhat {
     int elem;
     const double *rowsD, *colsD, *colSpacing;
     GfInterpArgs out;                             // its output pointers alone
+    bool coords;                                  // windows of points given as kind says: rowsD / colsD are their a / b
+    int kind;
+    GfCoords co;
+    double *spacingUsed;                          // may be null
 };
 
 // bitmap zeroed, k_points_mark, k_points_rank (enqueued)
@@ -154,7 +179,8 @@ gf_status pointsMarkRank(hipStream_t st, const GfPointsGrid &g, const PointsWhat
     m.g = g, m.ig = w.ig, m.nPoints = w.nPoints;
     m.rowsI = w.rowsI, m.colsI = w.colsI, m.rowsD = w.rowsD, m.colsD = w.colsD;
     m.bits = b.bits;
-    GF_HIP(gf_launch_points_mark(m, w.windows, st));
+    if (w.coords) GF_HIP(gf_launch_points_mark_coords(GfPointsMarkCoordsArgs{m, w.co, w.kind}, st));
+    else GF_HIP(gf_launch_points_mark(m, w.windows, st));
     GfPointsRankArgs r{};
     r.bits = b.bits, r.nWords = (uint32_t)b.nWords, r.prefix = b.prefix, r.list = b.list, r.maxTiles = (uint32_t)maxTiles, r.count = b.count;
     GF_HIP(gf_launch_points_rank(r, st));
@@ -192,7 +218,8 @@ gf_status pointsTail(gf_context *c, hipStream_t st, const gf_file_info &i, const
         a.nPoints = w.nPoints, a.rows = w.rowsD, a.cols = w.colsD, a.colSpacing = w.colSpacing;
         a.z = w.out.z, a.zx = w.out.zx, a.zy = w.out.zy, a.zxx = w.out.zxx, a.zxy = w.out.zxy, a.zyy = w.out.zyy;
         a.normal = w.out.normal, a.status = w.out.status;
-        GF_HIP(gf_launch_points_interp(a, st));
+        if (w.coords) GF_HIP(gf_launch_points_interp_coords(GfPointsInterpCoordsArgs{a, w.co, w.kind, w.spacingUsed}, st));
+        else GF_HIP(gf_launch_points_interp(a, st));
     }
     return GF_OK;
 }
@@ -424,6 +451,79 @@ gf_status gf_file_interp_points_dev(gf_context *c, const gf_file *f, const uint8
     w.out.z = out->z, w.out.zx = out->zx, w.out.zy = out->zy, w.out.zxx = out->zxx, w.out.zxy = out->zxy, w.out.zyy = out->zyy;
     w.out.normal = out->normal, w.out.status = out->status;
     return pointsDev(c, i, dImage, imageBytes, codecs, fill, verifyChecksum, maxTiles, w, nTouched);
+}
+
+gf_status gf_file_interp_coords_tiles(const gf_file *f, int kind, const gf_interp_spec *spec, size_t nPoints, const double *a, const double *b,
+                                      int32_t *tiles, size_t tilesCap, size_t *nTiles)
+{
+    if (!f || !spec || !nTiles || (kind != GF_COORDS_GRID && kind != GF_COORDS_FILE) || (nPoints && (!a || !b)) || (tilesCap && !tiles)) return GF_ERR_ARG;
+    *nTiles = 0;
+    gf_file_info i;
+    gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK) return s;
+    GfInterpGeom ig;
+    if ((s = pointsSpecArgs(i, spec, -1, true, ig)) != GF_OK) return s;
+    if (gfTilesOfGrid(i.grid).count() > POINTS_MAX_TILES_GRID) return GF_ERR_UNSUPPORTED;
+    *nTiles = listBits(coordsBits(gridOf(i), ig, coordsOf(i), kind, nPoints, a, b), tiles, tilesCap);
+    return GF_OK;
+}
+
+gf_status gf_file_interp_coords_dev(gf_context *c, const gf_file *f, const uint8_t *dImage, size_t imageBytes, int elem, int kind,
+                                    const gf_interp_spec *spec, size_t nPoints, const double *dA, const double *dB, const double *dColSpacing,
+                                    int verifyChecksum, size_t maxTiles, const gf_interp_out *out, double *dColSpacingUsed, size_t *nTouched)
+{
+    if (!f || !dImage || !nTouched || elem < 0 || (kind != GF_COORDS_GRID && kind != GF_COORDS_FILE) || (nPoints && (!dA || !dB))) return GF_ERR_ARG;
+    gf_file_info i;
+    gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK || (s = interpOutArgs(spec, out)) != GF_OK) return s;
+    PointsWhat w{};
+    // (a geographic file's spacing comes from the rule unless the caller brings one: a zero du is refused either way, as a zero
+    // col_spacing without per-point spacings is)
+    if ((s = pointsSpecArgs(i, spec, elem, dColSpacing != nullptr, w.ig)) != GF_OK) return s;
+    if (!c) return pointsNoContext(i, dImage, imageBytes, true);
+    int codecs[255];
+    uint32_t fill[GF_MAX_ELEMS];
+    if ((s = pointsFileArgs(c, i, dImage, imageBytes, true, nPoints, maxTiles, codecs, fill)) != GF_OK) return s;
+    w.windows = true, w.nPoints = nPoints, w.elem = elem, w.rowsD = dA, w.colsD = dB, w.colSpacing = dColSpacing;
+    w.coords = true, w.kind = kind, w.co = coordsOf(i), w.spacingUsed = dColSpacingUsed;
+    w.out.z = out->z, w.out.zx = out->zx, w.out.zy = out->zy, w.out.zxx = out->zxx, w.out.zxy = out->zxy, w.out.zyy = out->zyy;
+    w.out.normal = out->normal, w.out.status = out->status;
+    return pointsDev(c, i, dImage, imageBytes, codecs, fill, verifyChecksum, maxTiles, w, nTouched);
+}
+
+gf_status gf_file_interp_coords(gf_context *c, const gf_file *f, const uint8_t *image, size_t imageBytes, int elem, int kind,
+                                const gf_interp_spec *spec, size_t nPoints, const double *a, const double *b, const double *colSpacing,
+                                int verifyChecksum, size_t maxTiles, const gf_interp_out *out, double *colSpacingUsed, size_t *nTouched)
+{
+    if (!f || !image || !nTouched || elem < 0 || (kind != GF_COORDS_GRID && kind != GF_COORDS_FILE) || (nPoints && (!a || !b))) return GF_ERR_ARG;
+    gf_file_info i;
+    gf_status s = gf_file_get_info(f, &i);
+    if (s != GF_OK || (s = interpOutArgs(spec, out)) != GF_OK) return s;
+    PointsWhat w{};
+    if ((s = pointsSpecArgs(i, spec, elem, colSpacing != nullptr, w.ig)) != GF_OK) return s;
+    if (!c) return pointsNoContext(i, image, imageBytes, false);
+    int codecs[255];
+    uint32_t fill[GF_MAX_ELEMS];
+    if ((s = pointsFileArgs(c, i, image, imageBytes, false, nPoints, maxTiles, codecs, fill)) != GF_OK) return s;
+    w.windows = true, w.nPoints = nPoints, w.elem = elem;
+    w.coords = true, w.kind = kind, w.co = coordsOf(i);
+    double *const host[6] = {out->z, out->zx, out->zy, out->zxx, out->zxy, out->zyy};
+    int aP = 0, bP = 0, csP = 0, devP[6], normalP = 0, statusP = 0, usedP = 0;
+    return pointsHost(
+        c, i, image, imageBytes, codecs, fill, verifyChecksum, maxTiles, coordsBits(gridOf(i), w.ig, w.co, kind, nPoints, a, b), w, nTouched,
+        [&](HostStage &sg) {
+            aP = sg.in(a, nPoints * 8), bP = sg.in(b, nPoints * 8), csP = sg.in(colSpacing, nPoints * 8);
+            for (int k = 0; k < 6; k++) devP[k] = sg.out(host[k], nPoints * 8);
+            normalP = sg.out(out->normal, nPoints * 24), statusP = sg.out(out->status, nPoints * 4);
+            usedP = sg.out(colSpacingUsed, nPoints * 8);
+        },
+        [&](HostStage &sg, PointsWhat &p) {
+            p.rowsD = sg.ptr<double>(aP), p.colsD = sg.ptr<double>(bP), p.colSpacing = sg.ptr<double>(csP);
+            p.out.z = sg.ptr<double>(devP[0]), p.out.zx = sg.ptr<double>(devP[1]), p.out.zy = sg.ptr<double>(devP[2]);
+            p.out.zxx = sg.ptr<double>(devP[3]), p.out.zxy = sg.ptr<double>(devP[4]), p.out.zyy = sg.ptr<double>(devP[5]);
+            p.out.normal = sg.ptr<double>(normalP), p.out.status = sg.ptr<int32_t>(statusP);
+            p.spacingUsed = sg.ptr<double>(usedP);
+        });
 }
 
 gf_status gf_file_read_points_elems(gf_context *c, const gf_file *f, const uint8_t *image, size_t imageBytes, size_t nPoints, const int32_t *rows,

@@ -376,6 +376,11 @@ inline gf_status fileMaxRecord(const gf_elem_spec *elems, int nElems, const GfBl
 }
 // gvrs_api_interp.hip: what the host can check of an interpolation spec (fills g)
 gf_status interpSpecArgs(const gf_context *c, const gf_interp_spec *spec, const void *block, bool perPointSpacing, GfInterpGeom &g);
+// gvrs_api_coords.hip: the coordinate facts of a file as the rules of gvrs_coords.h take them, with what the reference derives;
+// and the answer to a NULL context behind every other argument check: GF_ERR_NO_DEVICE on a machine without a device (no
+// context can be had there), GF_ERR_ARG otherwise
+GfCoords coordsOf(const gf_file_info &i);
+gf_status noContext();
 // gvrs_api_records.hip
 size_t elemStandardSize(int elemType, size_t cells);
 // gvrs_api_lsop.hip: gf_lsop08_decode_batch_i32_dev on a stream (the public form runs on the context's own)

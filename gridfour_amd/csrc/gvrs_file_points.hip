@@ -4,6 +4,8 @@
 // 283-334), in the order in which gvrs_api_file_points.hip launches them around k_file_locate (gvrs_file.hip) and the records'
 // pipeline (gvrs_records.hip), which runs untouched.  The arithmetic is gvrs_file_points.h and gvrs_interp_common.h, shared with
 // the host forms and the CPU program; this file is the data path.  Built with -ffp-contract=off like the interpolation kernels.
+// k_points_mark<true> and k_points_interp have a second instantiation each for points given at longitude / latitude or model
+// x / y (GvrsInterpolatorBSpline.z / zNormal, :166-248): the mapping of gvrs_coords.h in registers, then the same body.
 
 #include <hip/hip_runtime.h>
 
@@ -50,14 +52,59 @@ __device__ __forceinline__ void mark_step(uint32_t *__restrict__ bits, bool has,
     }
 }
 
+// WHERE POINT t OF A CALL LIES, for k_points_mark<true> and k_points_interp: its grid coordinates and column spacing, or
+// GF_IP_ERR_ARG for a point refused before its window is looked at.  PtGiven: rows and columns as the call brought them.
+// PtMapped: (a[t], b[t]) mapped in registers by gf_coords_query (gvrs_coords.h) -- the one function both kernels call, so they
+// cannot disagree about a point's window; the mark kernel asks for no spacing and the cosine falls away there.
+struct PtGiven {
+    using MarkArgs = GfPointsMarkArgs;
+    using InterpArgs = GfPointsInterpArgs;
+    static __device__ __forceinline__ const GfPointsMarkArgs &mark(const MarkArgs &A) { return A; }
+    static __device__ __forceinline__ const GfPointsInterpArgs &interp(const InterpArgs &A) { return A; }
+    static __device__ __forceinline__ int at(const MarkArgs &A, size_t t, GfCoordsQuery &q)
+    {
+        q.row = A.rowsD[t], q.col = A.colsD[t], q.spacing = 0;
+        return GF_IP_OK;
+    }
+    static __device__ __forceinline__ int at(const InterpArgs &A, size_t t, GfCoordsQuery &q)
+    {
+        q.row = A.rows[t], q.col = A.cols[t], q.spacing = A.colSpacing ? A.colSpacing[t] : A.ig.colSpacing;
+        return GF_IP_OK;
+    }
+    static __device__ __forceinline__ void used(const InterpArgs &, size_t, double) {}
+};
+struct PtMapped {
+    using MarkArgs = GfPointsMarkCoordsArgs;
+    using InterpArgs = GfPointsInterpCoordsArgs;
+    static __device__ __forceinline__ const GfPointsMarkArgs &mark(const MarkArgs &A) { return A.m; }
+    static __device__ __forceinline__ const GfPointsInterpArgs &interp(const InterpArgs &A) { return A.p; }
+    static __device__ __forceinline__ int at(const MarkArgs &A, size_t t, GfCoordsQuery &q)
+    {
+        return gf_coords_query(A.c, A.kind, A.m.rowsD[t], A.m.colsD[t], 0.0, false, q);
+    }
+    static __device__ __forceinline__ int at(const InterpArgs &A, size_t t, GfCoordsQuery &q)
+    {
+        const bool rule = A.p.colSpacing == nullptr;                           // (uniform)
+        const int s = gf_coords_query(A.c, A.kind, A.p.rows[t], A.p.cols[t], A.p.ig.colSpacing, rule, q);
+        if (!rule && s == GF_IP_OK) q.spacing = A.p.colSpacing[t];
+        return s;
+    }
+    static __device__ __forceinline__ void used(const InterpArgs &A, size_t t, double spacing)   // (NaN for a refused point)
+    {
+        if (A.colSpacingUsed) A.colSpacingUsed[t] = spacing;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 // k_points_mark: a lane per point, grid-stride in whole waves (the loop's trip count is wave-uniform: mark_step needs every lane).
 // WINDOWS false: int32 cells, one tile each (gf_points_cell); true: double coordinates, the tiles of the 4 x 4 window
-// (gf_interp_window, gf_points_window_tiles), one tile per step.  A refused point has no tile and marks nothing.
+// (gf_interp_window, gf_points_window_tiles), one tile per step.  A refused point has no tile and marks nothing.  Where (windows
+// only): PtGiven, the coordinates are the grid's; PtMapped, they are mapped first.
 // ------------------------------------------------------------------------------------------------
-template <bool WINDOWS>
-__global__ __launch_bounds__(PT_THREADS) void k_points_mark(const GfPointsMarkArgs a)
+template <bool WINDOWS, class Where = PtGiven>
+__global__ __launch_bounds__(PT_THREADS) void k_points_mark(const typename Where::MarkArgs A)
 {
+    const GfPointsMarkArgs &a = Where::mark(A);
     const size_t stride = (size_t)gridDim.x * PT_THREADS;
     for (size_t base = (size_t)blockIdx.x * PT_THREADS + (threadIdx.x & ~63u); base < a.nPoints; base += stride) {
         const size_t t = base + (threadIdx.x & 63u);
@@ -70,8 +117,9 @@ __global__ __launch_bounds__(PT_THREADS) void k_points_mark(const GfPointsMarkAr
             GfWindowTiles wt{};
             int32_t n = 0;
             if (live) {
+                GfCoordsQuery q;
                 GfInterpWindow w;
-                if (gf_interp_window(a.ig, a.rowsD[t], a.colsD[t], w) == GF_IP_OK) {
+                if (Where::at(A, t, q) == GF_IP_OK && gf_interp_window(a.ig, q.row, q.col, w) == GF_IP_OK) {
                     wt = gf_points_window_tiles(a.g, w.row0, w.col0, w.n1);
                     n = wt.count();
                 }
@@ -181,16 +229,23 @@ __global__ __launch_bounds__(PT_THREADS) void k_points_cells(const GfPointsCells
 // the fill's where the tile has none to read, converted exactly as gf_interp_samples converts a block's cell.  If the element of
 // any tile of the window did not decode, the point takes the status of the lowest-indexed such tile and NaN.  Outputs are
 // structure-of-arrays; every item is written exactly once.  No LDS, no scratch.
+// Where: PtGiven, the points in grid coordinates with the call's spacings; PtMapped, the points mapped first (a point the latitude
+// check refuses is GF_K_ERR_ARG, in front of everything the window decides) and the spacing each was evaluated with stored.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PT_THREADS) void k_points_interp(const GfPointsInterpArgs a)
+template <class Where>
+__global__ __launch_bounds__(PT_THREADS) void k_points_interp(const typename Where::InterpArgs A)
 {
+    const GfPointsInterpArgs &a = Where::interp(A);
     const size_t t = ((size_t)blockIdx.x + (size_t)blockIdx.y * gridDim.x) * PT_THREADS + threadIdx.x;
     if (t >= a.nPoints) return;
-    const double row = a.rows[t], col = a.cols[t], cs = a.colSpacing ? a.colSpacing[t] : a.ig.colSpacing;
+    GfCoordsQuery q;
+    const int refused = Where::at(A, t, q);
+    const double row = q.row, col = q.col, cs = q.spacing;
+    Where::used(A, t, cs);                                                     // (stored at once: one register pair less to carry)
     GfInterpResult res;
     gf_interp_nullify(res);
     GfInterpWindow w;
-    int status = gf_interp_window(a.ig, row, col, w);
+    int status = refused != GF_IP_OK ? refused : gf_interp_window(a.ig, row, col, w);
     if (status == GF_IP_OK && a.ig.target != GF_IP_VALUE && (cs == 0 || a.ig.rowSpacing == 0)) status = GF_IP_ERR_ARG;
     if (status == GF_IP_OK) {
         const int32_t nRT = a.g.nRowsTile, nCT = a.g.nColsTile;
@@ -301,6 +356,26 @@ hipError_t gf_launch_points_interp(const GfPointsInterpArgs &a, hipStream_t stre
 {
     if (a.nPoints == 0) return hipSuccess;
     if (!a.rows || !a.cols || !a.z) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_points_interp, gf_tile_grid((a.nPoints + PT_THREADS - 1) / PT_THREADS), dim3(PT_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_points_interp<PtGiven>, gf_tile_grid((a.nPoints + PT_THREADS - 1) / PT_THREADS), dim3(PT_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+static bool coordsKind(int32_t kind) { return kind == GF_CO_GRID || kind == GF_CO_FILE; }
+
+hipError_t gf_launch_points_mark_coords(const GfPointsMarkCoordsArgs &a, hipStream_t stream)
+{
+    if (a.m.nPoints == 0) return hipSuccess;
+    if (a.m.nPoints > 0x7fffffffull || !a.m.bits || a.m.g.nTilesGrid < 1 || !a.m.rowsD || !a.m.colsD || !coordsKind(a.kind)) return hipErrorInvalidValue;
+    const size_t need = (a.m.nPoints + PT_THREADS - 1) / PT_THREADS;           // (as gf_launch_points_mark)
+    const unsigned grid = (unsigned)(need < 4096 ? need : 4096);
+    hipLaunchKernelGGL((k_points_mark<true, PtMapped>), dim3(grid), dim3(PT_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_points_interp_coords(const GfPointsInterpCoordsArgs &a, hipStream_t stream)
+{
+    if (a.p.nPoints == 0) return hipSuccess;
+    if (!a.p.rows || !a.p.cols || !a.p.z || !coordsKind(a.kind)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_points_interp<PtMapped>, gf_tile_grid((a.p.nPoints + PT_THREADS - 1) / PT_THREADS), dim3(PT_THREADS), 0, stream, a);
     return hipGetLastError();
 }

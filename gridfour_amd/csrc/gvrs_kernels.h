@@ -15,6 +15,7 @@
 #include "gvrs_lsop_container.h"
 #include "gvrs_file_parse.h"
 #include "gvrs_file_points.h"
+#include "gvrs_coords.h"
 
 // per-tile status values written by the kernels; identical to gf_status in
 // include/gvrs_hip_codec.h
@@ -645,6 +646,37 @@ struct GfPointsInterpArgs {
     int32_t *status;
 };
 hipError_t gf_launch_points_interp(const GfPointsInterpArgs &a, hipStream_t stream);
+
+// A file queried at COORDINATES (the rules are gvrs_coords.h).  k_coords_map (gvrs_coords.hip), a lane per point, is
+// gf_coords_map over a batch: the direction and the outputs that were passed are wave-uniform branches, every output item is
+// written exactly once.  The fused forms are second instantiations of k_points_mark<true> and k_points_interp
+// (gvrs_file_points.hip): point t is gf_coords_query of (m.rowsD[t], m.colsD[t]) / (p.rows[t], p.cols[t]), given as kind says,
+// mapped in registers; the body behind it is the one the grid-coordinate instantiations run.  p.colSpacing, where not null,
+// replaces the rule's spacing; a point the latitude check refuses is GF_K_ERR_ARG with NaN outputs and marks nothing.
+struct GfCoordsMapArgs {
+    GfCoords c;
+    int32_t kind;              // GF_CO_GEO_TO_GRID .. GF_CO_GRID_TO_MODEL
+    size_t nPoints;
+    const double *a, *b;
+    double *outA, *outB;
+    int32_t *iRow, *iCol;      // may be null; to-grid kinds only
+    double *colSpacing;        // may be null; to-grid kinds only
+    int32_t *status;           // may be null; to-grid kinds only
+};
+hipError_t gf_launch_coords_map(const GfCoordsMapArgs &a, hipStream_t stream);
+struct GfPointsMarkCoordsArgs {
+    GfPointsMarkArgs m;        // rowsD / colsD: the points' a / b
+    GfCoords c;
+    int32_t kind;              // GF_CO_GRID, GF_CO_FILE
+};
+hipError_t gf_launch_points_mark_coords(const GfPointsMarkCoordsArgs &a, hipStream_t stream);
+struct GfPointsInterpCoordsArgs {
+    GfPointsInterpArgs p;      // rows / cols: the points' a / b; ig.colSpacing: du
+    GfCoords c;
+    int32_t kind;
+    double *colSpacingUsed;    // may be null; per point the spacing it was evaluated with, NaN for a refused point
+};
+hipError_t gf_launch_points_interp_coords(const GfPointsInterpCoordsArgs &a, hipStream_t stream);
 
 // A file image WRITTEN at points (gvrs_file_points_write.hip; driven by gvrs_api_file_points.hip; the cell rule is
 // gvrs_file_points_store.h).  Behind mark, rank and k_file_locate, k_points_heads judges the head of every located record as an

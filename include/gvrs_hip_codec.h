@@ -757,9 +757,10 @@ gf_status gf_block_read_elems(gf_context *ctx, const int *codecs, int n_codecs, 
  *   (TileElementInt.java:150-156, TileElementShort.java:167-173), widened to double (InterpolatorBSpline.java:231-249).
  *   wrap: 0, or what GvrsFileSpecification reports: 1 doGeographicCoordinatesWrapLongitude, 2 ... and ...BracketLongitude
  *   (nColsForWrap = n_cols_grid - 1, GvrsInterpolatorBSpline.java:139-143).  The fringes are GvrsFileSpecification.java:437-440.
- *   NOT DONE HERE, left to the caller: mapModelToGridPoint / mapGeographicToGridPoint, and zNormal's column spacing
- *   cos(latitude) * du with its dx < 1 -> 1 clamp (:291-299; libm's cosine does not reproduce bit for bit): pass the resulting
- *   column spacing per point (d_col_spacing) or per lattice row (d_col_spacing_rows); NULL: spec->col_spacing for all.
+ *   NOT DONE BY THESE CALLS: mapModelToGridPoint / mapGeographicToGridPoint, and zNormal's column spacing cos(latitude) * du
+ *   with its dx < 1 -> 1 clamp (:291-299).  Both are the section "GVRS files queried at COORDINATES" below: gf_file_map_points
+ *   gives rows, columns and the column spacing per point for these calls (d_col_spacing; per lattice row: d_col_spacing_rows;
+ *   NULL: spec->col_spacing for all), and gf_file_interp_coords_dev does mapping, spacing and interpolation in one.
  *   LATTICE FORM: point (i, j), 0 <= i < n_rows, 0 <= j < n_cols, has row = row0 + (double)i * row_step, col = col0 + (double)j *
  *   col_step, one product and one sum, each rounded once; outputs are row-major n_rows x n_cols.  It gives the bits the points
  *   form gives for those coordinates (one kernel serves both).
@@ -1403,6 +1404,76 @@ gf_status gf_file_interp_points(gf_context *ctx, const gf_file *f, const uint8_t
                                 const gf_interp_spec *spec, size_t n_points, const double *rows, const double *cols,
                                 const double *col_spacing, int verify_checksum, size_t max_tiles,
                                 const gf_interp_out *out, size_t *n_tiles_touched);
+
+/* ---- GVRS files queried at COORDINATES: longitude / latitude or model x / y instead of rows and columns ---------------------------
+ * (gvrs/GvrsInterpolatorBSpline.java:166-181 z, :222-248 zNormal, :120-131 du and dv; gvrs/GvrsFileSpecification.java:2122-2126
+ * mapModelToGridPoint, :2159-2173 mapGeographicToGridPoint, :2198-2212 makeGridPointUsingFringe, :2230-2234 mapGridToGeoPoint,
+ * :2101-2105 mapGridToModelPoint, :695-707 checkGeographicCoverage, :435-440 the fringes; util/Angle.java:57-85)
+ * The rules are stated once (gvrs_coords.h), in double, in the reference's operation order, without fused multiply-add; Java's % is
+ * fmod; toRadians(a) = a * 0.017453292519943295 (JDK 9 and later; JDK 8's a / 180.0 * PI differs in the last bit).
+ *   TWO DELIBERATE DEVIATIONS.  (1) The cosine of the column-spacing rule is StrictMath.cos's value (fdlibm's algorithm, which is
+ *   specified exactly); the reference calls Math.cos, which is specified to within 1 ulp and may return exactly that value: on a JVM
+ *   where it does not, the spacing differs by that ulp for some latitudes.  A caller who needs another cosine passes per-point
+ *   spacings.  (2) z() refuses |y| > 90.0001 by throwing (:169-172), zNormal() omits the check; here a point of a GEOGRAPHIC file
+ *   (coordinate_system == 2) whose latitude has |lat| > 90.0001 is refused with the per-point status GF_ERR_ARG at every target
+ *   (a NaN passes, as in Java, and is refused later by the window).  That keeps the cosine's argument below 3 pi / 4.
+ *   THE COLUMN-SPACING RULE (:226-232, :291-299): geographic file: dx = cos(toRadians(lat)) * du, and dx < 1 -> 1; any other
+ *   file: du.  lat is the query's y, or mapGridToGeoPoint's latitude for a point given in grid coordinates.
+ *   gf_file_interp_spec fills EVERY field of spec from the file, as the reference's interpolator sets itself up: the grid, the whole
+ *   grid as the block, element elem's type and fill_i, wrap (checkGeographicCoverage; 0 for a file that is not geographic),
+ *   row_spacing = dv and col_spacing = du (rEarth * toRadians(cell size), rEarth = 6371007.2, for a geographic file; the cell
+ *   sizes otherwise) and the four fringes (-0.5 - 4 ulp((double) n), n - 0.5 + 4 ulp((double) n)).
+ *   gf_file_map_points, kind GF_MAP_GEO_TO_GRID / GF_MAP_MODEL_TO_GRID: (a, b) = (x, y) -- X IS THE LONGITUDE, Y THE LATITUDE, the
+ *   argument order of z() -- to out_a = row, out_b = column, the GridPoint's integer row and column (irow, icol: floor(v + 0.5)
+ *   with Java's saturating cast, snapped to 0 / n - 1 inside the fringe), the column spacing of the rule with the file's du, and
+ *   status: GF_ERR_ARG where the latitude check refuses y (then NaN, NaN, 0, 0, NaN), else GF_OK.  Kind GF_MAP_GRID_TO_GEO /
+ *   GF_MAP_GRID_TO_MODEL: (a, b) = (row, column) to out_a = x (the longitude), out_b = y (the latitude); irow, icol, col_spacing
+ *   and status must be NULL.  Any output may be NULL except out_a and out_b.  The geo kinds work on any file (the reference's
+ *   mapping functions do not ask which system is set); the latitude check and the spacing rule ask the file, as the interpolator does.
+ *   gf_file_map_points_dev: the same for arrays in device memory, bit for bit; it ONLY ENQUEUES on the context's stream, allocates
+ *   nothing, never synchronises and is safe for hipGraph capture.
+ *   CELLS AT COORDINATES need no call of their own: GvrsElement.readValue(GridPoint) reads the GridPoint's integers, so irow / icol
+ *   go to gf_file_read_points_elems[_dev].
+ *   gf_file_interp_coords_tiles is gf_file_interp_tiles with the mapping in front; a refused point touches no tile.
+ *   gf_file_interp_coords_dev is gf_file_interp_points_dev for points given as kind says -- GF_COORDS_GRID: (a, b) = (row, column),
+ *   zInterpGrid / zNormalGrid; GF_COORDS_FILE: (a, b) = (x, y) as z() / zNormal() read them -- mapped in registers by the kernels
+ *   that mark the tiles and sample the pool: no row, column or spacing array is written in between.  spec is read as there
+ *   (target, the spacings, wrap and the fringes; the rest comes from the file); the normal case is a spec of gf_file_interp_spec.
+ *   d_col_spacing NULL: the rule above with du = spec->col_spacing; not NULL: the caller's spacings, the rule is bypassed.
+ *   d_col_spacing_used (may be NULL) receives the spacing each point was evaluated with and NaN for a point the latitude check
+ *   refused; it always has a source -- the caller's array or the rule -- so no argument error belongs to it.  PER-POINT STATUS:
+ *   first GF_ERR_ARG with NaN outputs for a point the latitude check refuses (it touches no tile); then the order of
+ *   gf_file_interp_points_dev, its ONE ADDITION included.  Streams, the two synchronisations, max_tiles, GF_ERR_CAPACITY with
+ *   nothing written and *n_tiles_touched are as there.  gf_file_interp_coords: the same through host memory, built as
+ *   gf_file_interp_points is (the touched tiles come from gf_file_interp_coords_tiles' arithmetic; only their records are staged).
+ * GF_ERR_ARG, before the context or a device is looked at: null pointers with the allowances of the section above (coordinates
+ * may be NULL with n == 0); a kind out of range; a non-NULL irow, icol, col_spacing or status with a from-grid kind; what
+ * gf_file_interp_points_dev refuses of spec, elem, out and the image; for gf_file_interp_spec a bad elem or target or a grid under
+ * 4 x 4.  A NULL ctx is judged LAST: GF_ERR_NO_DEVICE on a machine without a HIP device (no context can be had there),
+ * GF_ERR_ARG otherwise.                                                                                                          */
+#define GF_COORDS_GRID 0   /* (row, col) as given: zInterpGrid / zNormalGrid                                  */
+#define GF_COORDS_FILE 1   /* (x, y) as z() / zNormal() read them: longitude, latitude for a geographic file, */
+                           /* model x, y through m2r otherwise                                                */
+#define GF_MAP_GEO_TO_GRID 0
+#define GF_MAP_MODEL_TO_GRID 1
+#define GF_MAP_GRID_TO_GEO 2
+#define GF_MAP_GRID_TO_MODEL 3
+gf_status gf_file_interp_spec(const gf_file *f, int elem, int target, gf_interp_spec *spec);
+gf_status gf_file_map_points(const gf_file *f, int kind, size_t n, const double *a, const double *b, double *out_a, double *out_b,
+                             int32_t *irow, int32_t *icol, double *col_spacing, int32_t *status);
+gf_status gf_file_map_points_dev(gf_context *ctx, const gf_file *f, int kind, size_t n, const double *d_a, const double *d_b,
+                                 double *d_out_a, double *d_out_b, int32_t *d_irow, int32_t *d_icol, double *d_col_spacing,
+                                 int32_t *d_status);
+gf_status gf_file_interp_coords_tiles(const gf_file *f, int kind, const gf_interp_spec *spec, size_t n, const double *a,
+                                      const double *b, int32_t *tiles, size_t tiles_cap, size_t *n_tiles);
+gf_status gf_file_interp_coords_dev(gf_context *ctx, const gf_file *f, const uint8_t *d_image, size_t image_bytes, int elem, int kind,
+                                    const gf_interp_spec *spec, size_t n_points, const double *d_a, const double *d_b,
+                                    const double *d_col_spacing, int verify_checksum, size_t max_tiles, const gf_interp_out *out,
+                                    double *d_col_spacing_used, size_t *n_tiles_touched);
+gf_status gf_file_interp_coords(gf_context *ctx, const gf_file *f, const uint8_t *image, size_t image_bytes, int elem, int kind,
+                                const gf_interp_spec *spec, size_t n_points, const double *a, const double *b,
+                                const double *col_spacing, int verify_checksum, size_t max_tiles, const gf_interp_out *out,
+                                double *col_spacing_used, size_t *n_tiles_touched);
 
 /* ---- GVRS files WRITTEN: a new file image from a rectangle of the raster, in one call ------------------------------------------
  * (gvrs/GvrsFile.java:239-300 the constructor that writes the header, :584-616 close; gvrs/GvrsFileSpecification.java:1170-1285
